@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- end-to-end SIFT extraction throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps of the headline leg (`value` / end_to_end below) and prints the
+result line; `ms_per_step` is the time of one timed step.  --full adds every other leg and figure listed below (the
+parity check, the C-ABI legs, roofline, CPU baseline, ...).  --dump-outputs DIR writes what the headline leg returned
+for a fixed, seeded sample of the frames of its LAST timed step (write_outputs): the inputs are the same on every run
+with the same arguments, so two builds can be compared output for output.
 
 Workload (BASELINE.json configs[1] / BASELINE.md workload 2): 1920x1080 grayscale u8 frames, config 1's Config
 (default Config, setOctaves(5), levels=3, setMode(VLFeat): BASELINE.md section 3; x2 upsample => octave 0 is
@@ -60,6 +66,9 @@ SUSTAINED_S = float(os.environ.get("POPSIFT_BENCH_SUSTAINED_S", "3.0"))
 SUSTAINED_FRAMES = int(os.environ.get("POPSIFT_BENCH_SUSTAINED_FRAMES", "8000"))
 WINDOW = 256                                                 # frames per sustained-leg window
 SUB = 64                                                     # the sustained leg advances in sub-steps of SUB frames
+DUMP_FRAMES = 4                                              # --dump-outputs: frames of the last timed step written out
+DUMP_SEED = 20261016                                         # ... picked by this seed
+DUMP_BYTES = 64 << 20                                        # ... at most this many bytes in all
 
 # Config profiles of the end-to-end legs (keyword overrides of capi.default_config)
 HEADLINE_KW = dict(octaves=5, sift_mode=2)                   # BASELINE config 1's Config: setOctaves(5), setMode(VLFeat)
@@ -202,8 +211,9 @@ class GpuBackend:
         self.np, self.torch, self.capi = np, torch, capi
         self.device = local_rank
         self.dev = torch.device("cuda", local_rank)
+        self.synth, self.rank, self.world = synth, rank, world
         self.frames_dense = make_frames(rank, world, synth)
-        self.frames_sparse = make_frames(rank, world, synth, sparse=True)
+        self.frames_sparse = None                                  # made by the first e2e_select("sparse") (--full)
         self.frames_float = None
         self.frames_np = self.frames_dense
         self.cfg = capi.default_config(**HEADLINE_KW)
@@ -211,6 +221,9 @@ class GpuBackend:
         self.ps = None
         self.ctxs = []
         self.desc_total = 0
+        self.keep_idx = set()       # --dump-outputs: frame numbers of the sequence whose FeaturesHost is held
+        self.kept_jobs = {}         # job handle -> frame number, from enqueue to get
+        self.kept = []              # (frame number, FeaturesHost handle), from get to e2e_outputs
 
     def sync(self):
         self.torch.cuda.synchronize()
@@ -236,8 +249,48 @@ class GpuBackend:
         self.desc_total += no
         return ne
 
+    def e2e_keep(self, indices):
+        """--dump-outputs: hold the FeaturesHost of these frame numbers of the end-to-end sequence for e2e_outputs(); until
+        then e2e_enqueue / e2e_get are the keeping variants below (without --dump-outputs the timed loop runs the plain ones)"""
+        self.keep_idx = set(indices)
+        self.e2e_enqueue, self.e2e_get = self._enqueue_keeping, self._get_keeping
+
+    def _enqueue_keeping(self, i):
+        job = GpuBackend.e2e_enqueue(self, i)
+        if i in self.keep_idx:
+            self.kept_jobs[job] = i
+        return job
+
+    def _get_keeping(self, job):
+        if job not in self.kept_jobs:
+            return GpuBackend.e2e_get(self, job)
+        # SiftJob::get as in e2e_get, but the FeaturesHost is held (not copied) until e2e_outputs()
+        H = self.capi.host_lib()
+        f = H.popsift_c_get(job)
+        if not f:
+            raise self.capi.PopSiftError("SiftJob::get failed: %s" % H.popsift_c_last_error().decode())
+        self.kept.append((self.kept_jobs.pop(job), f))
+        self.desc_total += H.popsift_c_descriptor_count(f)
+        return H.popsift_c_feature_count(f)
+
+    def e2e_outputs(self):
+        """[(frame number, Feature records, descriptors)] of the held FeaturesHost objects, which are deleted"""
+        H, np = self.capi.host_lib(), self.np
+        out = []
+        for i, f in sorted(self.kept, key=lambda t: t[0]):
+            feats = np.zeros((H.popsift_c_feature_count(f),), dtype=self.capi.FEATURE_DTYPE)
+            desc = np.zeros((H.popsift_c_descriptor_count(f), 128), dtype=np.float32)
+            H.popsift_c_copy(f, feats.ctypes.data, desc.ctypes.data)
+            H.popsift_c_free(f)
+            out.append((i, feats, desc))
+        self.keep_idx, self.kept_jobs, self.kept = set(), {}, []
+        del self.e2e_enqueue, self.e2e_get                         # the plain methods again
+        return out
+
     def e2e_select(self, which):
         """frame set of the following end-to-end legs: 'dense' (default, ~7 keypoints / 1000 px) or 'sparse' (~2)"""
+        if which == "sparse" and self.frames_sparse is None:
+            self.frames_sparse = make_frames(self.rank, self.world, self.synth, sparse=True)
         self.frames_np = self.frames_sparse if which == "sparse" else self.frames_dense
 
     def e2e_parity(self, indices):
@@ -407,9 +460,64 @@ def run(args, backend_cls=GpuBackend, out=sys.stdout):
 
     # ---- leg 1 (headline): the public C++ API, host frames in, FeaturesHost out; config 1's Config (VLFeat mode) ----
     be.e2e_open("headline")
+    dump = getattr(args, "dump_outputs", None) if rank == 0 else None
+    if dump:
+        be.e2e_keep(dump_frame_numbers(args.warmup, args.steps, per_rank))
     dt_e2e, kps_e2e, descs_e2e = timed(e2e_step, e2e_drain, desc_probe)
+    if dump:
+        write_outputs(dump, be.e2e_outputs())
+    t_wall["headline"] = time.perf_counter()
 
-    # ---- outside the timed region, same PopSift object: parity of timed frames, sustained run, sparse frame set ----
+    n_frames = world * per_rank * args.steps
+    result = None
+    if rank == 0:
+        mode_name = SIFT_MODE_NAMES[HEADLINE_KW.get("sift_mode", 0)]
+        result = {
+            "metric": "Mpixels/sec end-to-end SIFT (5 oct, 3 lvl/oct) + keypoints/sec",
+            "value": round(n_frames * W * H / dt_e2e / 1e6, 1), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(dt_e2e / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": "BASELINE config 2: 1920x1080 u8 host frames (%d distinct per GPU) -> PopSift::enqueue -> SiftJob::get -> "
+                                   "FeaturesHost (C++ API of libpopsift.so, upload and result delivery inside the timed "
+                                   "region); config 1's Config: setOctaves(5), levels=3, setMode(%s), ByteImages, grid filter off, "
+                                   "RootSift x1, upscale x2 (octave 0 = 3840x2160), full pipe (pyramid, extrema, orientation, "
+                                   "descriptors)" % (NDISTINCT, mode_name),
+                       "sift_mode": mode_name, "input": "u8 (ByteImages)", "grid_filter": "off",
+                       "frames_per_step_per_gpu": per_rank, "frames_timed": n_frames,
+                       "jobs_outstanding_per_gpu": MAX_OUT,
+                       "pipe_depth": os.environ.get("POPSIFT_PIPE_DEPTH", "8 (4 when this replica's share of the host is below two cores)"),
+                       "parallelism": "replicas x%d (frame i -> GPU i mod N, no collective)%s" % (
+                           world, "; --strong: %d frames per step in total (BASELINE config 4's shape)" % (per_rank * world) if args.strong else "")},
+            "keypoints_per_s": round(kps_e2e / dt_e2e, 1),
+            "keypoints_per_frame": round(kps_e2e / n_frames, 1),
+            "ms_per_frame": round(dt_e2e / (per_rank * args.steps) * 1e3, 4),
+            "keypoints_per_1000px": round(kps_e2e / n_frames / (W * H / 1000.0), 2),
+        }
+        if hasattr(be, "desc_total"):
+            # PCIe inside the timed region of `value` (warm-up excluded): the u8 frame up, 52-byte records + 512-byte
+            # descriptors down
+            h2d = n_frames * W * H
+            d2h = kps_e2e * 52 + descs_e2e * 512 * (world if world > 1 else 1)
+            result["pcie_gbs"] = {"h2d": round(h2d / dt_e2e / 1e9, 2), "d2h": round(d2h / dt_e2e / 1e9, 2),
+                                  "what": "host<->device bytes of the end-to-end leg's timed steps / its time (all GPUs; D2H from rank 0's descriptor count)"}
+        if dump:
+            result["outputs_dumped"] = dump
+
+    if not getattr(args, "full", False):
+        # a plain run: the headline figure and nothing else
+        be.e2e_close()
+        if rank == 0:
+            result["wall_s"] = {"setup_frames_and_import": round(t_wall["setup"] - t_wall["start"], 1),
+                                "end_to_end_leg": round(t_wall["headline"] - t_wall["setup"], 1),
+                                "total": round(time.perf_counter() - t_wall["start"], 1)}
+            print(json.dumps(result), file=out, flush=True)
+        if dist is not None:
+            barrier()
+            dist.destroy_process_group()
+        return result
+
+    # ---- --full.  Outside the timed region, same PopSift object: parity of timed frames, sustained run, sparse frame set ----
     parity = sustained = sparse = popsift_leg = caller_leg = None
     extra_legs = hasattr(be, "e2e_parity") and not args.no_extras
     quick = bool(getattr(args, "quick", False))      # the headline leg, its parity check and the C-ABI legs only
@@ -509,33 +617,10 @@ def run(args, backend_cls=GpuBackend, out=sys.stdout):
     dt_x, _, _ = timed(abi_step, abi_drain)
     be.abi_export(False)
 
-    n_frames = world * per_rank * args.steps
     rate = lambda dt: round(n_frames * W * H / dt / 1e6, 1)
 
-    result = None
     if rank == 0:
-        mode_name = SIFT_MODE_NAMES[HEADLINE_KW.get("sift_mode", 0)]
-        result = {
-            "metric": "Mpixels/sec end-to-end SIFT (5 oct, 3 lvl/oct) + keypoints/sec",
-            "value": rate(dt_e2e), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt_e2e / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE config 2: 1920x1080 u8 host frames (%d distinct per GPU) -> PopSift::enqueue -> SiftJob::get -> "
-                                   "FeaturesHost (C++ API of libpopsift.so, upload and result delivery inside the timed "
-                                   "region); config 1's Config: setOctaves(5), levels=3, setMode(%s), ByteImages, grid filter off, "
-                                   "RootSift x1, upscale x2 (octave 0 = 3840x2160), full pipe (pyramid, extrema, orientation, "
-                                   "descriptors)" % (NDISTINCT, mode_name),
-                       "sift_mode": mode_name, "input": "u8 (ByteImages)", "grid_filter": "off",
-                       "frames_per_step_per_gpu": per_rank, "frames_timed": n_frames,
-                       "jobs_outstanding_per_gpu": MAX_OUT,
-                       "pipe_depth": os.environ.get("POPSIFT_PIPE_DEPTH", "8 (4 when this replica's share of the host is below two cores)"),
-                       "parallelism": "replicas x%d (frame i -> GPU i mod N, no collective)%s" % (
-                           world, "; --strong: %d frames per step in total (BASELINE config 4's shape)" % (per_rank * world) if args.strong else "")},
-            "keypoints_per_s": round(kps_e2e / dt_e2e, 1),
-            "keypoints_per_frame": round(kps_e2e / n_frames, 1),
-            "ms_per_frame": round(dt_e2e / (per_rank * args.steps) * 1e3, 4),
-            "keypoints_per_1000px": round(kps_e2e / n_frames / (W * H / 1000.0), 2),
+        result.update({
             "parity_checked": parity, "sustained": sustained, "sparse_frames": sparse,
             "popsift_mode": popsift_leg, "caller_profile": caller_leg,
             "device_resident": {"value": rate(dt_dev), "unit": "Mpix/s", "ms_per_step": round(dt_dev / args.steps * 1e3, 4),
@@ -543,14 +628,7 @@ def run(args, backend_cls=GpuBackend, out=sys.stdout):
                                 "what": "C-ABI psx_extract, inputs and results resident in HBM (no PCIe in the timed region)"},
             "host_export": {"value": rate(dt_x), "unit": "Mpix/s", "ms_per_step": round(dt_x / args.steps * 1e3, 4),
                             "what": "C-ABI, inputs resident in HBM, Feature records + descriptors streamed into pinned host memory"},
-        }
-        if hasattr(be, "desc_total"):
-            # PCIe inside the timed region of `value` (warm-up excluded): the u8 frame up, 52-byte records + 512-byte
-            # descriptors down
-            h2d = n_frames * W * H
-            d2h = kps_e2e * 52 + descs_e2e * 512 * (world if world > 1 else 1)
-            result["pcie_gbs"] = {"h2d": round(h2d / dt_e2e / 1e9, 2), "d2h": round(d2h / dt_e2e / 1e9, 2),
-                                  "what": "host<->device bytes of the end-to-end leg's timed steps / its time (all GPUs; D2H from rank 0's descriptor count)"}
+        })
         stage_b, pipe_b = algorithmic_bytes(W, H, 5)
         result["pipe_roofline"] = {
             "algorithmic_bytes_per_frame": pipe_b, "unit": "GB/s", "peak": HBM_PEAK_GBS,
@@ -562,7 +640,7 @@ def run(args, backend_cls=GpuBackend, out=sys.stdout):
         if not args.no_extras and not quick:
             result.update(be.extras(args, world))
         t_wall["extras"] = time.perf_counter()
-        # where this run's wall time went (the driver allows the default run about a minute)
+        # where this run's wall time went
         result["wall_s"] = {"setup_frames_and_import": round(t_wall["setup"] - t_wall["start"], 1),
                             "end_to_end_legs": round(t_wall["e2e_legs"] - t_wall["setup"], 1),
                             "c_abi_legs": round(t_wall["abi_legs"] - t_wall["e2e_legs"], 1),
@@ -597,7 +675,61 @@ def parse_args(argv=None):
                          "pinning, per-rank parity) on a box with one GPU; the aggregate is then ONE GPU's rate shared by the ranks")
     ap.add_argument("--extras", action="store_true",
                     help="also the slow informational legs (every alternative Gauss / descriptor mode, BASELINE config 3, the full host-ceiling sweep)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline leg every other leg and figure: parity check, sustained, sparse frames, PopSift mode, caller "
+                         "profile, the two C-ABI legs, roofline, CPU baseline, ... (the --no-* / --quick / --extras options shape this run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline leg returned for %d seeded frames of its last timed step as DIR/<name>.npy" % DUMP_FRAMES)
+    a = ap.parse_args(argv)
+    only_full = [o for o, on in (("--quick", a.quick), ("--extras", a.extras), ("--no-cpu-baseline", a.no_cpu_baseline),
+                                 ("--no-parity", a.no_parity), ("--no-extras", a.no_extras), ("--no-host-ceiling", a.no_host_ceiling)) if on]
+    if only_full and not a.full:
+        ap.error("%s only shape a --full run (a plain run times the headline leg alone)" % " ".join(only_full))
+    return a
+
+
+def dump_frame_numbers(warmup, steps, per_rank):
+    """Frame numbers of the end-to-end sequence (warm-up steps included) that --dump-outputs writes: a fixed, seeded
+    sample of the last timed step's frames."""
+    import numpy as np
+    first = (warmup + steps - 1) * per_rank
+    pick = np.random.default_rng(DUMP_SEED).choice(per_rank, min(DUMP_FRAMES, per_rank), replace=False)
+    return sorted(first + int(k) for k in pick)
+
+
+def write_outputs(path, outputs, log=sys.stderr):
+    """--dump-outputs: what SiftJob::get returned for each (frame number, Feature records, descriptors), in a canonical
+    order (the order of a FeaturesHost is the order of the device's atomics, not a contract):
+      features.npy    float64 (n, 6 + ORI_MAX): frame number, octave, x, y, sigma, orientation count, orientations
+                      (unused slots 0); rows sorted lexicographically, rows equal in every column by their descriptors' bytes
+      descriptors.npy float32 (m, 128): each feature's descriptors in the order of its rows and orientation slots
+    Frames are taken in order while the two files stay within DUMP_BYTES; the frames left out are named on `log`."""
+    import numpy as np
+    from popsift_amd.capi import ORI_MAX as ori_max
+    feats, descs, nbytes, cut = [], [], 0, []
+    for i, f, d in outputs:
+        slot = np.arange(ori_max)[None, :] < f["num_ori"][:, None]
+        ori = np.where(slot, f["orientation"], np.float32(0))
+        cols = [np.full(len(f), i), f["debug_octave"], f["xpos"], f["ypos"], f["sigma"], f["num_ori"]]
+        rows = np.column_stack(cols + [ori[:, k] for k in range(ori_max)]).astype(np.float64)
+        # last key: the rank of each row's descriptors by their bytes (ties only between rows equal in every column)
+        own = np.zeros((len(f), ori_max, 128), np.float32)
+        own[slot] = d[f["desc_idx"][slot]]
+        _, tie = np.unique(own.reshape(len(f), -1).view(np.dtype((np.void, ori_max * 128 * 4))).ravel(), return_inverse=True)
+        order = np.lexsort([tie.ravel()] + [rows[:, c] for c in range(rows.shape[1] - 1, -1, -1)])
+        dsel = own[order][slot[order]]
+        if cut or nbytes + rows.nbytes + dsel.nbytes > DUMP_BYTES:
+            cut.append(i)
+            continue
+        feats.append(rows[order])
+        descs.append(dsel)
+        nbytes += rows.nbytes + dsel.nbytes
+    if cut:
+        print("bench.py --dump-outputs: frames %s left out (more than %d bytes in all); written: %d frames"
+              % (cut, DUMP_BYTES, len(feats)), file=log, flush=True)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "features.npy"), np.concatenate(feats) if feats else np.zeros((0, 6 + ori_max)))
+    np.save(os.path.join(path, "descriptors.npy"), np.concatenate(descs) if descs else np.zeros((0, 128), np.float32))
 
 
 def main():

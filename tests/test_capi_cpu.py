@@ -2,6 +2,7 @@
 include/popsift_hip.h declares, its device-free entry points agree with the oracle, and the
 product fails loudly (never falls back to a CPU path) without a GPU."""
 import ctypes as C
+import io
 import os
 import re
 import subprocess
@@ -183,6 +184,167 @@ def test_bench_algorithmic_bytes_match_the_survey():
     assert abs(pipe - 0.764e9) < 1e6 and abs(stage - 499.2e6) < 1e5
     assert bench.BATCH * 20 >= 200                      # the driver's 20 steps time >= 200 frames per GPU
     assert bench.octave_pixels(75, 61, 3) == [150 * 122, 75 * 61, 38 * 31]
+
+
+def test_bench_dump_outputs_are_canonical_and_bounded(tmp_path):
+    """--dump-outputs: a fixed, seeded sample of the last timed step's frames; features and descriptors written in
+    float, in an order that does not depend on the order of the FeaturesHost records, within the byte bound."""
+    import bench
+    from popsift_amd.capi import FEATURE_DTYPE, ORI_MAX
+    a = bench.dump_frame_numbers(3, 20, bench.BATCH)
+    assert a == bench.dump_frame_numbers(3, 20, bench.BATCH) and len(a) == bench.DUMP_FRAMES == len(set(a))
+    assert all(22 * bench.BATCH <= i < 23 * bench.BATCH for i in a)
+    assert bench.dump_frame_numbers(0, 1, 2) == [0, 1]
+    rng = np.random.default_rng(1)
+
+    def frame(n):
+        f = np.zeros((n,), dtype=FEATURE_DTYPE)
+        f["debug_octave"] = rng.integers(0, 3, n); f["xpos"] = rng.random(n) * 100; f["ypos"] = rng.random(n) * 80
+        f["sigma"] = 1 + rng.random(n); f["num_ori"] = rng.integers(1, ORI_MAX + 1, n)
+        f["orientation"] = rng.random((n, ORI_MAX)) * 6
+        nd = int(f["num_ori"].sum())
+        perm = rng.permutation(nd)
+        k = 0
+        for j in range(n):
+            for s in range(f["num_ori"][j]):
+                f["desc_idx"][j, s] = perm[k]; k += 1
+        return f, rng.random((nd, 128)).astype(np.float32)
+
+    outs = [(i, *frame(50 + 10 * i)) for i in range(3)]
+    bench.write_outputs(str(tmp_path / "a"), outs)
+    shuffled = []
+    for i, f, d in outs:                                   # same results, records and descriptors in another order
+        p, q = rng.permutation(len(f)), rng.permutation(len(d))
+        g = f[p].copy()
+        inv = np.argsort(q)
+        g["desc_idx"] = np.where(np.arange(ORI_MAX)[None, :] < g["num_ori"][:, None], inv[g["desc_idx"]], 99)
+        g["orientation"] = np.where(np.arange(ORI_MAX)[None, :] < g["num_ori"][:, None], g["orientation"], 7.0)
+        shuffled.append((i, g, d[q]))
+    bench.write_outputs(str(tmp_path / "b"), shuffled)
+    for name in ("features", "descriptors"):
+        x, y = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), name
+    feats = np.load(tmp_path / "a" / "features.npy")
+    desc = np.load(tmp_path / "a" / "descriptors.npy")
+    assert feats.shape == (sum(len(f) for _, f, _ in outs), 6 + ORI_MAX) and len(desc) == sum(len(d) for _, _, d in outs)
+    # row r's first descriptor is the one its record pointed to
+    i, f, d = outs[0]
+    r0 = feats[0]
+    j = np.flatnonzero((f["xpos"] == np.float32(r0[2])) & (f["ypos"] == np.float32(r0[3])))[0]
+    assert np.array_equal(desc[0], d[f["desc_idx"][j, 0]])
+    # rows equal in every column: ordered by their descriptors' bytes, whatever order the records came in
+    f, d = frame(2)
+    f[1] = f[0]
+    f["num_ori"] = 1
+    f["desc_idx"][:, 0] = [0, 1]
+    d = d[:2]
+    d[0, 0], d[1, 0] = 0.75, 0.25
+    g = f[::-1].copy()
+    for name, recs in (("t1", f), ("t2", g)):
+        bench.write_outputs(str(tmp_path / name), [(9, recs, d)])
+    x, y = np.load(tmp_path / "t1" / "descriptors.npy"), np.load(tmp_path / "t2" / "descriptors.npy")
+    assert np.array_equal(x, y) and sorted(x[:, 0]) == [0.25, 0.75]
+    # over the byte bound: whole frames are left out, and the run says which
+    log = io.StringIO()
+    old = bench.DUMP_BYTES
+    try:
+        i, f, d = outs[0]
+        bench.DUMP_BYTES = len(f) * (6 + ORI_MAX) * 8 + d.nbytes       # room for the first frame only
+        bench.write_outputs(str(tmp_path / "c"), outs, log=log)
+        bench.DUMP_BYTES = 100                                         # not even the first one
+        bench.write_outputs(str(tmp_path / "e"), outs, log=log)
+    finally:
+        bench.DUMP_BYTES = old
+    c = np.load(tmp_path / "c" / "features.npy")
+    assert set(c[:, 0]) == {0.0} and len(c) == len(outs[0][1])
+    assert len(np.load(tmp_path / "e" / "features.npy")) == 0
+    lines = log.getvalue().splitlines()
+    assert "frames [1, 2] left out" in lines[0] and "written: 1 frames" in lines[0]
+    assert "frames [0, 1, 2] left out" in lines[1] and "written: 0 frames" in lines[1]
+
+
+def test_bench_dump_outputs_hold_the_timed_frames(tmp_path, monkeypatch):
+    """--dump-outputs through bench.run() and GpuBackend's own methods over a stand-in for libpopsift: the frames of the
+    sample are the ones the timed loop collected (one of them by the drain after the last step), their FeaturesHost is
+    held instead of freed by get_counts, copied and freed after the timed region, and the plain methods are back."""
+    import ctypes
+    import bench
+    from popsift_amd.capi import FEATURE_DTYPE
+    steps, warmup = 2, 1
+    last = (warmup + steps) * bench.BATCH - 1                    # collected by the drain, not by a step
+    pick = [(warmup + steps - 1) * bench.BATCH + 7, last]
+    monkeypatch.setattr(bench, "dump_frame_numbers", lambda w, s, n: pick)
+    freed, counted = [], []
+
+    class Host:                                                  # popsift_c_*: FeaturesHost of frame i has i % 5 + 1 records
+        def popsift_c_get(self, job):
+            return ("fh", job[1])
+
+        def popsift_c_feature_count(self, f):
+            return f[1] % 5 + 1
+
+        def popsift_c_descriptor_count(self, f):
+            return f[1] % 5 + 1
+
+        def popsift_c_copy(self, f, fa, da):
+            n = f[1] % 5 + 1
+            feats = np.frombuffer((ctypes.c_char * (n * FEATURE_DTYPE.itemsize)).from_address(fa), dtype=FEATURE_DTYPE)
+            desc = np.frombuffer((ctypes.c_float * (n * 128)).from_address(da), dtype=np.float32)
+            feats["xpos"] = np.arange(n); feats["num_ori"] = 1; feats["desc_idx"][:, 0] = np.arange(n)
+            desc[:] = f[1]
+
+        def popsift_c_free(self, f):
+            freed.append(f[1])
+
+    class Capi:
+        PopSiftError = RuntimeError
+
+        def host_lib(self):
+            return Host()
+    Capi.FEATURE_DTYPE = FEATURE_DTYPE
+
+    class PS:                                                    # jobs are numbered in enqueue order = frame number
+        def __init__(self):
+            self.n = 0
+
+        def enqueue(self, img):
+            self.n += 1
+            return ("job", self.n - 1)
+
+        def get_counts(self, job):
+            counted.append(job[1])
+            return job[1] % 5 + 1, job[1] % 5 + 1
+
+    class Backend(bench.GpuBackend):
+        def __init__(self, rank, local_rank, world):
+            self.np, self.capi, self.ps, self.desc_total = np, Capi(), None, 0
+            self.frames_np = [None] * bench.NDISTINCT
+            self.keep_idx, self.kept_jobs, self.kept = set(), {}, []
+
+        def e2e_open(self, profile="headline"):
+            self.ps = PS()
+
+        def e2e_close(self):
+            holder.append(self)
+
+        def sync(self):
+            pass
+
+    holder = []
+    out = io.StringIO()
+    args = bench.parse_args(["--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path / "d")])
+    res = bench.run(args, backend_cls=Backend, out=out)
+    be = holder[0]
+    assert res["outputs_dumped"] == str(tmp_path / "d")
+    n = (warmup + steps) * bench.BATCH
+    assert sorted(counted + freed) == list(range(n))             # every frame collected once: held ones not by get_counts
+    assert sorted(freed) == pick and not set(pick) & set(counted)
+    assert res["keypoints_per_frame"] * steps * bench.BATCH == sum(i % 5 + 1 for i in range(warmup * bench.BATCH, n))
+    assert "e2e_get" not in vars(be) and "e2e_enqueue" not in vars(be) and not be.kept and not be.kept_jobs
+    feats = np.load(tmp_path / "d" / "features.npy")
+    desc = np.load(tmp_path / "d" / "descriptors.npy")
+    assert sorted(set(feats[:, 0])) == pick and len(feats) == sum(i % 5 + 1 for i in pick)
+    assert np.array_equal(desc[:, 0], feats[:, 0].astype(np.float32))
 
 
 def test_bench_has_no_undefined_names():

@@ -114,11 +114,12 @@ def _worker(rank, world, port, steps, warmup, q, extra=()):
 
 @pytest.mark.parametrize("steps,warmup", [(3, 1), (5, 0)])
 def test_bench_control_flow_two_ranks(steps, warmup):
+    """--full: every leg, in order, with the parity counts of both ranks."""
     world = 2
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, steps, warmup, q)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, steps, warmup, q, ("--full",))) for r in range(world)]
     for p in procs:
         p.start()
     res = sorted([q.get(timeout=180) for _ in range(world)], key=lambda r: r[0])
@@ -166,7 +167,7 @@ def test_bench_strong_scaling_shape_two_ranks():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, steps, warmup, q, ("--strong", "--no-extras"))) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, steps, warmup, q, ("--full", "--strong", "--no-extras"))) for r in range(world)]
     for p in procs:
         p.start()
     res = sorted([q.get(timeout=180) for _ in range(world)], key=lambda r: r[0])
@@ -181,3 +182,34 @@ def test_bench_strong_scaling_shape_two_ranks():
     # every rank enqueued (warmup + steps) * BATCH / world frames on the end-to-end leg
     for r in res:
         assert r[4] == (warmup + steps) * bench.BATCH // world
+
+
+def test_bench_plain_run_is_the_headline_leg_only_two_ranks():
+    """Without --full the bench runs the headline leg and nothing else: warm-up and exactly K timed steps of the
+    end-to-end leg, then ONE JSON line with the headline figure and ms_per_step."""
+    world, steps, warmup = 2, 3, 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, steps, warmup, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = sorted([q.get(timeout=180) for _ in range(world)], key=lambda r: r[0])
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    import bench
+    (_, r0, out0, log0, n0), (_, r1, out1, log1, n1) = res
+    assert r1 is None and out1 == ""
+    lines = [l for l in out0.splitlines() if l.strip()]
+    assert len(lines) == 1 and json.loads(lines[0]) == r0
+    assert log0 == log1 == ["e2e_open headline", "e2e_close"]
+    assert n0 == n1 == (warmup + steps) * bench.BATCH
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in r0, k
+    assert r0["steps"] == steps and r0["unit"] == "Mpix/s" and r0["higher_is_better"] is True and r0["dtype"] == "f32"
+    assert r0["config"]["frames_timed"] == world * bench.BATCH * steps
+    t = r0["config"]["frames_timed"] * bench.W * bench.H / (r0["value"] * 1e6)
+    assert abs(r0["ms_per_step"] - t / steps * 1e3) < 0.05 * r0["ms_per_step"] + 1e-3
+    for k in ("parity_checked", "device_resident", "host_export", "caller_profile", "roofline", "cpu_baseline"):
+        assert k not in r0, k

@@ -33,7 +33,7 @@ def _free_port():
 
 
 def _bench(world, extra=()):
-    args = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--quick", "--no-cpu-baseline", "--no-host-ceiling"] + list(extra)
+    args = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--full", "--quick", "--no-cpu-baseline", "--no-host-ceiling"] + list(extra)
     if world > 1:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port())] + args

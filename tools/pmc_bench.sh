@@ -6,13 +6,13 @@
 # mix, not the counters of kernels overlapping each other.
 C=$1; OUT=${2:-/dev/stdout}; case "$OUT" in /*) ;; *) OUT="$PWD/$OUT";; esac
 R=$GRAFT_REPO_ROOT
-cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/pmcb
-rocprofv3 --pmc $C --kernel-trace -d /tmp/pmcb -o r --output-format csv -- python $R/bench.py --quick --steps 1 --warmup 1 --no-cpu-baseline --no-parity --no-host-ceiling > /tmp/pmcb.log 2>&1
-python - "$OUT" <<'PY'
+W=$(mktemp -d) && cd "$W" && export TMPDIR="$W" || exit 1
+timeout -k 10 600 rocprofv3 --pmc $C --kernel-trace -d "$W/pmcb" -o r --output-format csv -- python $R/bench.py --full --quick --steps 1 --warmup 1 --no-cpu-baseline --no-parity --no-host-ceiling > "$W/pmcb.log" 2>&1 \
+  || { rc=$?; tail -20 "$W/pmcb.log"; echo "pmc_bench.sh: the counter pass failed (exit $rc)"; exit 1; }
+python - "$OUT" "$W" <<'PY' || exit 1
 import csv, collections, sys, glob
-f = glob.glob("/tmp/pmcb/**/*counter_collection.csv", recursive=True)
-if not f: print(open("/tmp/pmcb.log").read()[-3000:]); sys.exit(1)
+f = glob.glob(sys.argv[2] + "/pmcb/**/*counter_collection.csv", recursive=True)
+if not f: print(open(sys.argv[2] + "/pmcb.log").read()[-3000:]); sys.exit(1)
 rows = list(csv.DictReader(open(f[0])))
 agg = collections.defaultdict(lambda: collections.defaultdict(float))
 calls = collections.Counter()
@@ -31,4 +31,4 @@ with open(sys.argv[1], "w") as o:
         for n in names: tot[n] += agg[k][n]
     o.write("%-42s %7s " % ("TOTAL", "") + " ".join("%15.0f" % tot[n] for n in names) + "\n")
 PY
-tail -2 /tmp/pmcb.log | cut -c1-300
+tail -2 "$W/pmcb.log" | cut -c1-300

@@ -27,7 +27,7 @@ import os as _os
 if _os.path.exists(bench_trace):
   by_grid(bench_trace, out + "/bench_kernel_by_grid.txt",
         "# rocprofv3 --kernel-trace, per (kernel, workgroups): calls avg_us min_us max_us\n"
-        "# command: python bench.py --steps 10 --warmup 2 --no-cpu-baseline   (contexts in flight overlap: durations include co-running kernels)\n")
+        "# command: python bench.py --full --quick --steps 10 --warmup 2 --no-cpu-baseline --no-parity --no-host-ceiling   (contexts in flight overlap: durations include co-running kernels)\n")
 by_grid(single_trace, out + "/single_kernel_by_grid.txt",
         "# rocprofv3 --kernel-trace, per (kernel, workgroups): calls avg_us min_us max_us\n"
         "# command: python tools/single_stream.py 20   (one context, uncontended kernel durations)\n")

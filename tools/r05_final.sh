@@ -2,11 +2,14 @@
 # round-5 closing run on the GPU box: full GPU suite, smoke, default bench line (-> profiles/r05_bench_line.json), descriptor SHA
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05_final; mkdir -p $O
-timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
+# every GPU step under its own time limit; the first that fails ends the script
+set -o pipefail
+timeout -k 10 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; rc=$?; echo "pytest rc=$rc" >> $O/pytest_gpu.log
 tail -4 $O/pytest_gpu.log
-python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | cut -c1-160
+[ $rc -eq 0 ] || exit 1
+timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | cut -c1-160 || exit 1
 T0=$(date +%s)
-python bench.py > $O/bench_line.json 2> $O/bench.err
+timeout -k 10 600 python bench.py --full > $O/bench_line.json 2> $O/bench.err || { echo "bench.py failed"; tail -5 $O/bench.err; exit 1; }
 echo "bench default wall: $(( $(date +%s) - T0 )) s"
 python - <<'PY'
 import json
