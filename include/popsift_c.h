@@ -24,6 +24,10 @@ typedef struct popsift_c_features popsift_c_features;   /* popsift::FeaturesHost
  * popsift::Config through its public setters.  image_mode: 0 ByteImages, 1 FloatImages;
  * processing_mode: 0 ExtractingMode (MatchingMode results are device resident and have no C view). */
 popsift_c_handle* popsift_c_create(const psx_config* cfg, int image_mode, int device);
+/* popsift_c_create with Config::setDescriptorFormat (sift_conf.h): descriptor_format PSX_DESCFMT_F32 (as
+ * popsift_c_create) or PSX_DESCFMT_U8 (SiftJob::get returns byte descriptors, include/popsift_hip.h); any other
+ * value returns NULL before a device is touched. */
+popsift_c_handle* popsift_c_create_fmt(const psx_config* cfg, int image_mode, int device, int descriptor_format);
 /* PopSift::uninit + destructor */
 void popsift_c_destroy(popsift_c_handle* h);
 /* PopSift::enqueue, popsift.h:219-232: deep-copies the image; NULL when the image is refused */
@@ -37,8 +41,17 @@ int popsift_c_descriptor_count(const popsift_c_features* f);
 /* Copies the keypoints as psx_feature records (Descriptor* turned into indices into the descriptor
  * array) and the descriptors (128 floats each); either pointer may be NULL. */
 int popsift_c_copy(const popsift_c_features* f, psx_feature* features, float* descriptors);
-/* direct view of the FeaturesHost descriptor array (getDescriptors()), valid until popsift_c_free */
+/* direct view of the FeaturesHost descriptor array (getDescriptors()), valid until popsift_c_free; NULL for a
+ * byte result.  popsift_c_copy with a non-NULL descriptor pointer fails on a byte result (PSX_ERR_STATE). */
 const float* popsift_c_descriptors(const popsift_c_features* f);
+/* PSX_DESCFMT_F32 or PSX_DESCFMT_U8: the form of the result's descriptors (FeaturesHost::hasByteDescriptors) */
+int popsift_c_descriptor_format(const popsift_c_features* f);
+/* popsift_c_copy for a byte result: records (desc_idx = rows of 128 bytes) and num_descriptors * 128 bytes; either
+ * pointer may be NULL; PSX_ERR_STATE with a byte pointer on a float result */
+int popsift_c_copy_u8(const popsift_c_features* f, psx_feature* features, unsigned char* descriptors);
+/* direct view of the byte descriptors (FeaturesHost::getDescriptorBytes), valid until popsift_c_free; NULL for a
+ * float result */
+const unsigned char* popsift_c_descriptor_bytes(const popsift_c_features* f);
 /* delete the FeaturesHost */
 void popsift_c_free(popsift_c_features* f);
 /* message of the last failure on the calling thread */

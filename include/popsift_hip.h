@@ -267,6 +267,51 @@ int psx_match(int device, const float* d_left, int l_len, const float* d_right, 
  * calls); optional -- the scratch is also released when the thread exits. */
 int psx_match_release(void);
 
+/* ---- byte descriptors ------------------------------------------------------------------
+ * The form AliceVision's popSIFT describer hands on (setNormalizationMultiplier(9) and a conversion of every float
+ * descriptor to unsigned char[128] on the host), and the byte convention of popsift-demo --write-as-uchar
+ * (features.cu:310-330, which prints roundf of each float).  One rule everywhere:
+ *     q = (uint8) min(255, max(0, roundf(d)))
+ * d = the float the float path produces for that bin (after the normalisation and the norm_multi scale); roundf rounds
+ * half away from zero.  Saturation at 255 is the one departure from the reference's text output. */
+#define PSX_DESCFMT_F32 0   /* float descriptors (default) */
+#define PSX_DESCFMT_U8  1   /* float descriptors AND their quantised bytes */
+
+/* Descriptor format of a context's next extractions.  In byte mode the descriptor kernels also store the quantised
+ * bytes into a device byte array of the context; the float array stays complete (psx_download, psx_device_results and
+ * psx_clone_results are unchanged).  Any other value returns PSX_ERR_INVALID (ctx is not touched).  Switching to
+ * PSX_DESCFMT_F32 detaches a byte export. */
+int psx_set_descriptor_format(psx_ctx* ctx, int fmt);
+
+/* psx_download with the bytes: num_features records and num_descriptors * 128 bytes (capacities in elements);
+ * PSX_ERR_STATE when the context (or its last extraction) is in float mode.  Synchronises. */
+int psx_download_u8(psx_ctx* ctx, psx_feature* features, int feature_capacity,
+                    unsigned char* descriptors, int descriptor_capacity);
+
+/* psx_attach_export / psx_attach_export_mapped for byte mode: the descriptor kernels stream the 128 bytes of each
+ * descriptor into host_descriptors instead of floats.  Attaching a float export detaches the byte export and vice
+ * versa; PSX_ERR_STATE in float mode. */
+int psx_attach_export_u8(psx_ctx* ctx, psx_feature* host_features, int feature_capacity,
+                         unsigned char* host_descriptors, int descriptor_capacity);
+int psx_attach_export_mapped_u8(psx_ctx* ctx, psx_feature* host_features, int feature_capacity,
+                                unsigned char* host_descriptors, int descriptor_capacity);
+
+/* The rule above on n descriptors already on the device: d_src n*128 floats -> d_dst n*128 bytes (DEVICE pointers;
+ * d_src 16-byte aligned, d_dst 4-byte aligned: the kernel reads float4 and writes 32-bit words).  Synchronous. */
+int psx_quantize_desc(int device, const float* d_src, int n, unsigned char* d_dst);
+
+/* FeaturesDev::match (features.cu:160-304) on byte descriptors: for every left descriptor the two right descriptors
+ * that are smallest under the (squared distance, index) order -- what the reference's scan with strict '<' keeps,
+ * ties to the earlier index.  Every quantity is an integer: a squared distance is at most 128 * 255^2 < 2^24, so the
+ * reference's own float operation tree is exact on byte-valued inputs and this integer matcher (i8 MFMA on values
+ * shifted by -128, i32 accumulation) returns the reference's result bit for bit.  d_left / d_right: DEVICE pointers
+ * to l_len / r_len descriptors of 128 bytes, 16-byte aligned (rows are read as 16-byte vectors).  host_match[3*i..3*i+2] = {best, second, accept} with
+ * accept = ((float)d_best / (float)d_second < 0.8f); host_dist (may be NULL) [2*i..2*i+1] = the two squared
+ * distances, INT_MAX where psx_match reports +inf (r_len 0 or 1).  Scratch as psx_match (psx_match_release).
+ * Synchronous. */
+int psx_match_u8(int device, const unsigned char* d_left, int l_len, const unsigned char* d_right, int r_len,
+                 int* host_match, int* host_dist);
+
 /* device_prop_t (common/device_prop.h:23-108): enumeration only; there are no texture limits. */
 int psx_device_count(int* count);
 int psx_device_info(int device, char* name, int name_len, size_t* total_mem, int* compute_units, int* clock_khz);

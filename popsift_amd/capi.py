@@ -63,7 +63,12 @@ SYMBOLS = [
     "psx_host_alloc", "psx_host_alloc_near", "psx_host_free", "psx_dev_alloc", "psx_dev_free", "psx_dev_read", "psx_dev_write", "psx_clone_results", "psx_match", "psx_match_release", "psx_device_count", "psx_device_info", "psx_device_pci",
     "psx_enable_blur_probe", "psx_blur_probe_times", "psx_copy_bench", "psx_upload_pinned", "psx_attach_export_mapped",
     "psx_print_gauss_tables", "psx_flow_trace", "psx_debug_cross_stream", "psx_probe_extra_times",
+    "psx_set_descriptor_format", "psx_download_u8", "psx_attach_export_u8", "psx_attach_export_mapped_u8",
+    "psx_quantize_desc", "psx_match_u8",
 ]
+
+DESCFMT_F32 = 0      # PSX_DESCFMT_F32
+DESCFMT_U8 = 1       # PSX_DESCFMT_U8
 
 _LIB = None
 
@@ -159,6 +164,79 @@ def match(left, right, device=0):
                          mm.ctypes.data_as(C.c_void_p), dd.ctypes.data_as(C.c_void_p))
         if rc != 0:
             raise PopSiftError("psx_match failed (%d)" % rc)
+        return mm, dd
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def quantize_rule(desc):
+    """The byte rule of include/popsift_hip.h on the host: (uint8) min(255, max(0, roundf(d))), roundf = half away from zero."""
+    d = np.asarray(desc, dtype=np.float32)
+    # roundf(d) = sign(d) floor(|d| + 0.5) with an EXACT sum (in float32, 0.49999997 + 0.5 rounds to 1): float64 holds it
+    exact = np.floor(np.abs(d).astype(np.float64) + 0.5)
+    r = np.where(d >= 0, exact, -exact)
+    return np.nan_to_num(np.clip(r, 0, 255), nan=0.0).astype(np.uint8)
+
+
+def _to_device(L, device, arrays, bufs):
+    L.psx_dev_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.psx_dev_free.argtypes = [C.c_int, C.c_void_p]
+    L.psx_dev_write.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+    ptrs = []
+    for arr in arrays:
+        p = C.c_void_p()
+        if arr.nbytes:
+            if L.psx_dev_alloc(device, arr.nbytes, C.byref(p)) != 0:
+                raise PopSiftError("psx_dev_alloc failed")
+            bufs.append(p)
+            if L.psx_dev_write(device, p, arr.ctypes.data_as(C.c_void_p), arr.nbytes) != 0:
+                raise PopSiftError("psx_dev_write failed")
+        ptrs.append(p)
+    return ptrs
+
+
+def quantize(desc, device=0):
+    """psx_quantize_desc on a host array of (n,128) float32 descriptors (through device buffers): (n,128) uint8."""
+    L = lib()
+    L.psx_quantize_desc.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.psx_dev_read.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+    desc = np.ascontiguousarray(desc, dtype=np.float32).reshape(-1, 128)
+    out = np.zeros(desc.shape, np.uint8)
+    bufs = []
+    try:
+        (ps,) = _to_device(L, device, [desc], bufs)
+        pd = C.c_void_p()
+        if len(desc):
+            if L.psx_dev_alloc(device, out.nbytes, C.byref(pd)) != 0:
+                raise PopSiftError("psx_dev_alloc failed")
+            bufs.append(pd)
+        rc = L.psx_quantize_desc(device, ps, len(desc), pd)
+        if rc != 0:
+            raise PopSiftError("psx_quantize_desc failed (%d)" % rc)
+        if len(desc) and L.psx_dev_read(device, out.ctypes.data_as(C.c_void_p), pd, out.nbytes) != 0:
+            raise PopSiftError("psx_dev_read failed")
+        return out
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def match_u8(left, right, device=0):
+    """psx_match_u8 on host arrays of (n,128) / (m,128) uint8 descriptors: (match (n,3) int32 = best, second, accept;
+    dist (n,2) int32 squared distances, INT_MAX where there is no neighbour)."""
+    L = lib()
+    L.psx_match_u8.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    left = np.ascontiguousarray(left, dtype=np.uint8).reshape(-1, 128)
+    right = np.ascontiguousarray(right, dtype=np.uint8).reshape(-1, 128)
+    bufs = []
+    try:
+        pl, pr = _to_device(L, device, [left, right], bufs)
+        mm = np.zeros((len(left), 3), np.int32)
+        dd = np.zeros((len(left), 2), np.int32)
+        rc = L.psx_match_u8(device, pl, len(left), pr, len(right), mm.ctypes.data_as(C.c_void_p), dd.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise PopSiftError("psx_match_u8 failed (%d)" % rc)
         return mm, dd
     finally:
         for p in bufs:
@@ -325,6 +403,39 @@ class Context:
                                      desc.ctypes.data_as(C.c_void_p), no))
         return feats, desc
 
+    def set_descriptor_format(self, fmt):
+        """psx_set_descriptor_format: DESCFMT_F32 (default) or DESCFMT_U8 (floats and their quantised bytes)."""
+        lib().psx_set_descriptor_format.argtypes = [C.c_void_p, C.c_int]
+        self._chk(lib().psx_set_descriptor_format(self._h, fmt))
+
+    def download_u8(self):
+        """psx_download_u8: (features, (n,128) uint8 descriptors) of the last extraction in byte mode."""
+        lib().psx_download_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        ne, no = self.counts()
+        feats = np.zeros((ne,), dtype=FEATURE_DTYPE)
+        desc = np.zeros((no, 128), dtype=np.uint8)
+        self._chk(lib().psx_download_u8(self._h, feats.ctypes.data_as(C.c_void_p), ne,
+                                        desc.ctypes.data_as(C.c_void_p), no))
+        return feats, desc
+
+    def attach_export_u8(self, feat_buf, desc_buf):
+        """psx_attach_export_u8: as attach_export, desc_buf a uint8 buffer of m*128 bytes; exported() then returns bytes."""
+        L = lib()
+        L.psx_attach_export_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        if feat_buf is None:
+            self._chk(L.psx_attach_export_u8(self._h, None, 0, None, 0))
+            self._export = None
+            return
+
+        def ptr_n(b, itemsize):
+            if hasattr(b, "data_ptr"):
+                return b.data_ptr(), b.numel() * b.element_size() // itemsize
+            return b.ctypes.data, b.nbytes // itemsize
+        fp_, fn = ptr_n(feat_buf, FEATURE_DTYPE.itemsize)
+        dp_, dn = ptr_n(desc_buf, 128)
+        self._chk(L.psx_attach_export_u8(self._h, C.c_void_p(fp_), fn, C.c_void_p(dp_), dn))
+        self._export = (feat_buf, desc_buf, np.uint8)
+
     def clone_results(self, device=0):
         """psx_clone_results into caller-owned device buffers (what FeaturesDev holds), read back:
         (Feature records with device pointers, descriptors, descriptor->extremum map, device address of descriptor 0)."""
@@ -371,11 +482,12 @@ class Context:
     def exported(self):
         """After counts(): numpy views (no copy) of the exported features / descriptors."""
         ne, no = self.counts()
-        fb, db = self._export
+        fb, db = self._export[:2]
+        dt = self._export[2] if len(self._export) > 2 else np.float32
         fa = fb.numpy() if hasattr(fb, "numpy") else fb
         da = db.numpy() if hasattr(db, "numpy") else db
         feats = fa.view(np.uint8).reshape(-1)[: ne * FEATURE_DTYPE.itemsize].view(FEATURE_DTYPE)
-        desc = da.view(np.float32).reshape(-1)[: no * 128].reshape(no, 128)
+        desc = da.view(dt).reshape(-1)[: no * 128].reshape(no, 128)
         return feats, desc
 
     def dump_plane(self, kind, octave, level):
@@ -451,7 +563,8 @@ def copy_bench(device=0, nbytes=0, reps=10):
 HOST_LIB_PATH = os.environ.get("POPSIFT_HOST_LIB") or os.path.join(_HERE, "lib", "libpopsift.so")
 HOST_SYMBOLS = ["popsift_c_create", "popsift_c_destroy", "popsift_c_enqueue_u8", "popsift_c_enqueue_f32",
                 "popsift_c_get", "popsift_c_feature_count", "popsift_c_descriptor_count", "popsift_c_copy",
-                "popsift_c_descriptors", "popsift_c_free", "popsift_c_last_error", "popsift_c_pool_stats"]
+                "popsift_c_descriptors", "popsift_c_free", "popsift_c_last_error", "popsift_c_pool_stats",
+                "popsift_c_create_fmt", "popsift_c_descriptor_format", "popsift_c_copy_u8", "popsift_c_descriptor_bytes"]
 _HOST = None
 
 
@@ -465,6 +578,12 @@ def host_lib():
         vp = C.c_void_p
         H.popsift_c_create.argtypes = [C.POINTER(Config), C.c_int, C.c_int]
         H.popsift_c_create.restype = vp
+        H.popsift_c_create_fmt.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int]
+        H.popsift_c_create_fmt.restype = vp
+        H.popsift_c_descriptor_format.argtypes = [vp]
+        H.popsift_c_copy_u8.argtypes = [vp, vp, vp]
+        H.popsift_c_descriptor_bytes.argtypes = [vp]
+        H.popsift_c_descriptor_bytes.restype = vp
         H.popsift_c_destroy.argtypes = [vp]
         H.popsift_c_destroy.restype = None
         for n in ("popsift_c_enqueue_u8", "popsift_c_enqueue_f32"):
@@ -497,12 +616,17 @@ class PopSift:
     """PopSift / SiftJob / FeaturesHost of the C++ library (popsift/popsift.h), through popsift_c.h:
     enqueue(img) -> job handle, get(job) -> (features, descriptors) numpy arrays or just the counts."""
 
-    def __init__(self, cfg=None, device=0, float_images=False):
+    def __init__(self, cfg=None, device=0, float_images=False, byte_descriptors=False):
+        """byte_descriptors: Config::ByteDescriptors -- get() returns (n,128) uint8 descriptors."""
         self.cfg = cfg if cfg is not None else default_config()
-        self._h = host_lib().popsift_c_create(C.byref(self.cfg), 1 if float_images else 0, device)
+        if byte_descriptors:
+            self._h = host_lib().popsift_c_create_fmt(C.byref(self.cfg), 1 if float_images else 0, device, DESCFMT_U8)
+        else:
+            self._h = host_lib().popsift_c_create(C.byref(self.cfg), 1 if float_images else 0, device)
         if not self._h:
             raise PopSiftError("popsift_c_create failed: %s" % host_lib().popsift_c_last_error().decode())
         self._float = float_images
+        self._bytes = byte_descriptors
 
     def enqueue(self, img):
         """img: C-contiguous (h, w) numpy array, uint8 or float32 (matching the image mode)."""
@@ -530,9 +654,15 @@ class PopSift:
             raise PopSiftError("SiftJob::get failed: %s" % H.popsift_c_last_error().decode())
         ne, no = H.popsift_c_feature_count(f), H.popsift_c_descriptor_count(f)
         feats = np.zeros((ne,), dtype=FEATURE_DTYPE)
-        desc = np.zeros((no, 128), dtype=np.float32)
-        H.popsift_c_copy(f, feats.ctypes.data, desc.ctypes.data)
+        if H.popsift_c_descriptor_format(f) == DESCFMT_U8:
+            desc = np.zeros((no, 128), dtype=np.uint8)
+            rc = H.popsift_c_copy_u8(f, feats.ctypes.data, desc.ctypes.data)
+        else:
+            desc = np.zeros((no, 128), dtype=np.float32)
+            rc = H.popsift_c_copy(f, feats.ctypes.data, desc.ctypes.data)
         H.popsift_c_free(f)
+        if rc != 0:
+            raise PopSiftError("popsift_c_copy failed: %s" % H.popsift_c_last_error().decode())
         return feats, desc
 
     def close(self):

@@ -126,6 +126,9 @@ struct psx_ctx {
     psx_extremum* d_extrema = nullptr; size_t extrema_cap = 0;
     psx_feature* d_features = nullptr; size_t features_cap = 0;
     float* d_desc = nullptr;           size_t desc_cap = 0;       // floats
+    // byte descriptors (psx_set_descriptor_format): the quantised copy of d_desc, 128 bytes per descriptor, grown with it
+    int desc_fmt = PSX_DESCFMT_F32;
+    unsigned char* d_desc_u8 = nullptr; size_t desc_u8_cap = 0;  // bytes
     int* d_feat_to_ext = nullptr;      size_t f2e_cap = 0;
     int* d_ext_nori = nullptr;         size_t nori_cap = 0;
 
@@ -149,11 +152,15 @@ struct psx_ctx {
     psx_feature* x_dev_feat = nullptr;  float* x_dev_desc = nullptr;
     int x_feat_cap = 0, x_desc_cap = 0;
     bool x_registered_feat = false, x_registered_desc = false;
+    // the byte export (psx_attach_export_u8): replaces x_host_desc; x_desc_cap is its capacity
+    unsigned char* x_host_u8 = nullptr; unsigned char* x_dev_u8 = nullptr;
+    bool x_registered_u8 = false;
     int* h_xcnt = nullptr;             // pinned [4]: ext_total, ori_total, ori_raw
     // the export targets the frame in flight was LAUNCHED with (psx_orientation): the attach calls may change the
     // targets of the next frame before this one's counters and results have been fetched
     PsxExport fx{};
     psx_feature* fx_host_feat = nullptr; float* fx_host_desc = nullptr;
+    unsigned char* fx_host_u8 = nullptr;
     bool fx_on = false;
 
     // MEASUREMENT switch PSX_NULL_DEVICE_WORK (bench.py host_ceiling): 1 = after a context's first frame psx_extract launches
@@ -210,15 +217,18 @@ PsxExport export_of(const psx_ctx* c)
 {
     PsxExport x;
     x.features = c->x_dev_feat; x.desc = c->x_dev_desc;
-    x.counts = (c->x_dev_feat || c->x_dev_desc) ? c->h_xcnt : nullptr;
+    x.counts = (c->x_dev_feat || c->x_dev_desc || c->x_dev_u8) ? c->h_xcnt : nullptr;
     x.feat_capacity = c->x_feat_cap; x.desc_capacity = c->x_desc_cap;
+    const bool bytes = c->desc_fmt == PSX_DESCFMT_U8;
+    x.desc_u8 = bytes ? c->d_desc_u8 : nullptr;
+    x.xdesc_u8 = bytes ? c->x_dev_u8 : nullptr;
     return x;
 }
-inline bool exporting(const psx_ctx* c) { return c->x_dev_feat != nullptr || c->x_dev_desc != nullptr; }
+inline bool exporting(const psx_ctx* c) { return c->x_dev_feat != nullptr || c->x_dev_desc != nullptr || c->x_dev_u8 != nullptr; }
 inline void snapshot_export(psx_ctx* c)
 {
     c->fx = export_of(c);
-    c->fx_host_feat = c->x_host_feat; c->fx_host_desc = c->x_host_desc;
+    c->fx_host_feat = c->x_host_feat; c->fx_host_desc = c->x_host_desc; c->fx_host_u8 = c->x_host_u8;
     c->fx_on = exporting(c);
 }
 
@@ -702,6 +712,7 @@ int psx_destroy(psx_ctx* ctx)
     if (ctx->h_cnt) (void)hipHostFree(ctx->h_cnt);
     if (ctx->x_registered_feat) (void)hipHostUnregister(ctx->x_host_feat);
     if (ctx->x_registered_desc) (void)hipHostUnregister(ctx->x_host_desc);
+    if (ctx->x_registered_u8) (void)hipHostUnregister(ctx->x_host_u8);
     if (ctx->h_xcnt) (void)hipHostFree(ctx->h_xcnt);
     (void)hipFree(ctx->d_input_own); (void)hipFree(ctx->d_pyr); (void)hipFree(ctx->d_up);
     (void)hipFree(ctx->d_intm); (void)hipFree(ctx->d_vbuf);
@@ -712,6 +723,7 @@ int psx_destroy(psx_ctx* ctx)
     (void)hipFree(ctx->d_iext); (void)hipFree(ctx->d_iext_off); (void)hipFree(ctx->d_cand);
     (void)hipFree(ctx->d_extrema); (void)hipFree(ctx->d_features);
     (void)hipFree(ctx->d_desc); (void)hipFree(ctx->d_feat_to_ext); (void)hipFree(ctx->d_ext_nori);
+    (void)hipFree(ctx->d_desc_u8);
     for (int i = 0; i < 5; i++) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->ev_t0) (void)hipEventDestroy(ctx->ev_t0);
     if (ctx->ev_t1) (void)hipEventDestroy(ctx->ev_t1);
@@ -840,6 +852,7 @@ int psx_resize(psx_ctx* ctx, int w, int h)
     if ((rc = grow(ctx, &ctx->d_extrema, &ctx->extrema_cap, iext_need)) != PSX_OK) return rc;
     if ((rc = grow(ctx, &ctx->d_features, &ctx->features_cap, iext_need)) != PSX_OK) return rc;
     if ((rc = grow(ctx, &ctx->d_desc, &ctx->desc_cap, ori_need * 128)) != PSX_OK) return rc;
+    if (ctx->desc_fmt == PSX_DESCFMT_U8 && (rc = grow(ctx, &ctx->d_desc_u8, &ctx->desc_u8_cap, ctx->desc_cap)) != PSX_OK) return rc;
     if ((rc = grow(ctx, &ctx->d_feat_to_ext, &ctx->f2e_cap, ori_need)) != PSX_OK) return rc;
     if ((rc = grow(ctx, &ctx->d_ext_nori, &ctx->nori_cap, iext_need + 64)) != PSX_OK) return rc;
     for (int o = 0; o < P.num_octaves; o++) {
@@ -1355,6 +1368,11 @@ static int regrow_descriptors(psx_ctx* ctx, int ori_raw)
     PSX_HIP(hipStreamSynchronize(ctx->stream));
     if ((rc = grow(ctx, &ctx->d_desc, &ctx->desc_cap, need * 128)) != PSX_OK) return rc;
     if ((rc = grow(ctx, &ctx->d_feat_to_ext, &ctx->f2e_cap, need)) != PSX_OK) return rc;
+    // the byte array of a frame launched in byte mode grows with the floats (it is a kernel argument: the repeat carries the new one)
+    if (ctx->fx.desc_u8 != nullptr) {
+        if ((rc = grow(ctx, &ctx->d_desc_u8, &ctx->desc_u8_cap, ctx->desc_cap)) != PSX_OK) return rc;
+        ctx->fx.desc_u8 = ctx->d_desc_u8;
+    }
     P.desc = ctx->d_desc;
     P.feat_to_ext = ctx->d_feat_to_ext;
     P.ori_capacity = (int)need;
@@ -1439,6 +1457,13 @@ int psx_download(psx_ctx* ctx, psx_feature* features, int feature_capacity, floa
     return wait_stream(ctx);
 }
 
+// the byte export is detached by every attach call (float or byte); the caller has waited for the stream if it was registered
+static void detach_u8(psx_ctx* ctx)
+{
+    if (ctx->x_registered_u8) { (void)hipHostUnregister(ctx->x_host_u8); ctx->x_registered_u8 = false; }
+    ctx->x_host_u8 = ctx->x_dev_u8 = nullptr;
+}
+
 static int map_host(psx_ctx* ctx, void* host, size_t bytes, void** dev, bool* registered)
 {
     *registered = false;
@@ -1462,6 +1487,7 @@ int psx_attach_export(psx_ctx* ctx, psx_feature* host_features, int feature_capa
     PSX_HIP(hipStreamSynchronize(ctx->stream));
     if (ctx->x_registered_feat) { (void)hipHostUnregister(ctx->x_host_feat); ctx->x_registered_feat = false; }
     if (ctx->x_registered_desc) { (void)hipHostUnregister(ctx->x_host_desc); ctx->x_registered_desc = false; }
+    detach_u8(ctx);
     ctx->x_host_feat = nullptr; ctx->x_host_desc = nullptr;
     ctx->x_dev_feat = nullptr; ctx->x_dev_desc = nullptr;
     ctx->x_feat_cap = ctx->x_desc_cap = 0;
@@ -1491,12 +1517,13 @@ int psx_attach_export_mapped(psx_ctx* ctx, psx_feature* host_features, int featu
     // any) keeps the targets it was launched with, and its counters / results are still fetched from those
     // (psx_ctx::fx).  Only buffers an earlier psx_attach_export had to register are a reason to wait: the frame
     // in flight may still be storing into them.
-    if (ctx->x_registered_feat || ctx->x_registered_desc) {
+    if (ctx->x_registered_feat || ctx->x_registered_desc || ctx->x_registered_u8) {
         PSX_HIP(hipSetDevice(ctx->device));
         PSX_HIP(hipStreamSynchronize(ctx->stream));
     }
     if (ctx->x_registered_feat) { (void)hipHostUnregister(ctx->x_host_feat); ctx->x_registered_feat = false; }
     if (ctx->x_registered_desc) { (void)hipHostUnregister(ctx->x_host_desc); ctx->x_registered_desc = false; }
+    detach_u8(ctx);
     // psx_host_alloc memory: mapped, and its device address is its host address (checked at allocation)
     ctx->x_host_feat = ctx->x_dev_feat = (host_features && feature_capacity > 0) ? host_features : nullptr;
     ctx->x_host_desc = ctx->x_dev_desc = (host_descriptors && descriptor_capacity > 0) ? host_descriptors : nullptr;
@@ -1504,6 +1531,94 @@ int psx_attach_export_mapped(psx_ctx* ctx, psx_feature* host_features, int featu
     ctx->x_desc_cap = ctx->x_dev_desc ? descriptor_capacity : 0;
     if (ctx->graph) { (void)hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
     return PSX_OK;
+}
+
+// ---- byte descriptors ---------------------------------------------------------------------------------------------------
+
+int psx_set_descriptor_format(psx_ctx* ctx, int fmt)
+{
+    if (fmt != PSX_DESCFMT_F32 && fmt != PSX_DESCFMT_U8) {
+        if (ctx) ctx->err = "psx_set_descriptor_format: unknown descriptor format";
+        return PSX_ERR_INVALID;
+    }
+    if (!ctx) return PSX_ERR_INVALID;
+    if (fmt == ctx->desc_fmt) return PSX_OK;
+    PSX_HIP(hipSetDevice(ctx->device));
+    // switching back to float mode keeps the byte array (a frame in flight may still be storing into it).  grow() replaces
+    // it only when the float array has grown since it was sized; hipFree waits for the device to be idle, so no frame in
+    // flight still stores into the old one -- the same rule as every other buffer grow() replaces
+    if (fmt == PSX_DESCFMT_U8 && ctx->desc_cap > 0) {
+        const int rc = grow(ctx, &ctx->d_desc_u8, &ctx->desc_u8_cap, ctx->desc_cap);
+        if (rc != PSX_OK) return rc;
+    }
+    if (fmt == PSX_DESCFMT_F32 && ctx->x_dev_u8) {
+        if (ctx->x_registered_u8) PSX_HIP(hipStreamSynchronize(ctx->stream));
+        detach_u8(ctx);
+        ctx->x_desc_cap = 0;
+    }
+    ctx->desc_fmt = fmt;
+    if (ctx->graph) { (void)hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }      // the byte array is a kernel argument
+    return PSX_OK;
+}
+
+int psx_download_u8(psx_ctx* ctx, psx_feature* features, int feature_capacity, unsigned char* descriptors,
+                    int descriptor_capacity)
+{
+    if (!ctx) return PSX_ERR_INVALID;
+    if (ctx->desc_fmt != PSX_DESCFMT_U8) return fail(ctx, PSX_ERR_STATE, "psx_download_u8: the context is not in byte mode");
+    int rc = fetch_counts(ctx);
+    if (rc != PSX_OK) return rc;
+    // the frame must have been launched in byte mode (the format switched after its launch leaves no bytes of it)
+    if (ctx->fx.desc_u8 == nullptr) return fail(ctx, PSX_ERR_STATE, "psx_download_u8: the last extraction ran in float mode");
+    const int ne = ctx->h_cnt->ext_total, no = ctx->h_cnt->ori_total;
+    if (ne > feature_capacity || no > descriptor_capacity)
+        return fail(ctx, PSX_ERR_INVALID, "psx_download_u8: output capacity too small");
+    if (ne > 0 && !features) return fail(ctx, PSX_ERR_INVALID, "psx_download_u8: null feature buffer");
+    if (no > 0 && !descriptors) return fail(ctx, PSX_ERR_INVALID, "psx_download_u8: null descriptor buffer");
+    const bool feat_exported = (ctx->fx_on && features == ctx->fx_host_feat && ne <= ctx->fx.feat_capacity);
+    const bool desc_exported = (ctx->fx_on && descriptors == ctx->fx_host_u8 && no <= ctx->fx.desc_capacity);
+    if (ne > 0 && !feat_exported)
+        PSX_HIP(hipMemcpyAsync(features, ctx->d_features, (size_t)ne * sizeof(psx_feature),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    if (no > 0 && !desc_exported)
+        PSX_HIP(hipMemcpyAsync(descriptors, ctx->d_desc_u8, (size_t)no * 128, hipMemcpyDeviceToHost, ctx->stream));
+    return wait_stream(ctx);
+}
+
+// both byte attach calls: the float descriptor export is detached, the feature export is replaced
+static int attach_u8_common(psx_ctx* ctx, psx_feature* host_features, int feature_capacity,
+                            unsigned char* host_descriptors, int descriptor_capacity, bool mapped)
+{
+    if (!ctx) return PSX_ERR_INVALID;
+    if (ctx->desc_fmt != PSX_DESCFMT_U8 && host_descriptors && descriptor_capacity > 0)
+        return fail(ctx, PSX_ERR_STATE, "psx_attach_export_u8: the context is not in byte mode");
+    int rc = mapped ? psx_attach_export_mapped(ctx, host_features, feature_capacity, nullptr, 0)
+                    : psx_attach_export(ctx, host_features, feature_capacity, nullptr, 0);
+    if (rc != PSX_OK) return rc;
+    if (host_descriptors && descriptor_capacity > 0) {
+        if (mapped) {
+            ctx->x_host_u8 = ctx->x_dev_u8 = host_descriptors;
+        } else {
+            void* d = nullptr;
+            rc = map_host(ctx, host_descriptors, (size_t)descriptor_capacity * 128, &d, &ctx->x_registered_u8);
+            if (rc != PSX_OK) return rc;
+            ctx->x_host_u8 = host_descriptors; ctx->x_dev_u8 = static_cast<unsigned char*>(d);
+        }
+        ctx->x_desc_cap = descriptor_capacity;
+    }
+    return PSX_OK;
+}
+
+int psx_attach_export_u8(psx_ctx* ctx, psx_feature* host_features, int feature_capacity,
+                         unsigned char* host_descriptors, int descriptor_capacity)
+{
+    return attach_u8_common(ctx, host_features, feature_capacity, host_descriptors, descriptor_capacity, false);
+}
+
+int psx_attach_export_mapped_u8(psx_ctx* ctx, psx_feature* host_features, int feature_capacity,
+                                unsigned char* host_descriptors, int descriptor_capacity)
+{
+    return attach_u8_common(ctx, host_features, feature_capacity, host_descriptors, descriptor_capacity, true);
 }
 
 int psx_device_results(psx_ctx* ctx, const psx_feature** d_features, const float** d_descriptors,

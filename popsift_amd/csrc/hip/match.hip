@@ -23,6 +23,7 @@
 // of the reference produces.
 #include "psx_internal.h"
 
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -536,10 +537,11 @@ __global__ __launch_bounds__(256) void k_match_exact(const float* __restrict__ l
 // the device is synchronised) and buffers that only ever grow.  Freed when the thread exits.
 namespace {
 struct MatchScratch {
+    static constexpr int NBUF = 13;      // 0-9: psx_match, 10-12: psx_match_u8
     int device = -1;
     hipStream_t stream = nullptr;
-    void* buf[10] = {};
-    size_t cap[10] = {};
+    void* buf[NBUF] = {};
+    size_t cap[NBUF] = {};
     void* hpin = nullptr;                // pinned staging of the results: a DMA into pageable caller memory goes through the
     size_t hpin_cap = 0;                 // runtime's own bounce buffers, ~0.5 ms per call on this stack
     bool tidy = false;                   // the prefilter's counters are zero (left so by the previous call's last kernel)
@@ -549,13 +551,22 @@ struct MatchScratch {
         int cur = -1;                                        // the caller's current device is left as it was
         if (hipGetDevice(&cur) != hipSuccess) cur = -1;
         (void)hipSetDevice(device);
-        for (int i = 0; i < 10; i++) { (void)hipFree(buf[i]); buf[i] = nullptr; cap[i] = 0; }
+        for (int i = 0; i < NBUF; i++) { (void)hipFree(buf[i]); buf[i] = nullptr; cap[i] = 0; }
         tidy = false;
         if (hpin) (void)hipHostFree(hpin);
         hpin = nullptr; hpin_cap = 0;
         if (stream) (void)hipStreamDestroy(stream);
         stream = nullptr; device = -1;
         if (cur >= 0) (void)hipSetDevice(cur);
+    }
+    // the scratch of `device` (a call for another device releases the previous one's first)
+    bool bind(int dev)
+    {
+        if (device == dev) return true;
+        release();
+        if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return false;
+        device = dev;
+        return true;
     }
     bool need_pinned(size_t bytes)
     {
@@ -582,7 +593,7 @@ struct MatchScratch {
 thread_local MatchScratch t_scratch;
 } // namespace
 
-// frees the calling thread's matcher scratch (stream + up to 10 device buffers); an explicit user call -- PopSift::uninit
+// frees the calling thread's matcher scratch (stream + up to 13 device buffers); an explicit user call -- PopSift::uninit
 // does NOT call it: the scratch belongs to the thread, not to one PopSift object (another replica may be using it)
 extern "C" int psx_match_release(void)
 {
@@ -598,11 +609,7 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
     if (l_len == 0) return PSX_OK;
     if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
     MatchScratch& sc = t_scratch;
-    if (sc.device != device) {
-        sc.release();
-        if (hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking) != hipSuccess) return PSX_ERR_HIP;
-        sc.device = device;
-    }
+    if (!sc.bind(device)) return PSX_ERR_HIP;
     // enough (left group, chunk) waves to fill the chip: 256 CUs x 4 SIMDs x 2 waves
     const int lgroups = (l_len + 63) / 64;
     int nchunks = (2048 + lgroups - 1) / lgroups;
@@ -737,5 +744,240 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
     }
     memcpy(host_match, hp, mb);
     if (host_dist) memcpy(host_dist, hp + mb, db);
+    return PSX_OK;
+}
+
+
+// =====================================================================================================================
+// Byte descriptors: the quantisation rule and the exact integer matcher (psx_quantize_desc, psx_match_u8)
+//
+// For descriptors of 128 bytes every quantity of the matcher is an integer: a squared distance is at most
+// 128 * 255^2 = 8 323 200 < 2^23, so no prefilter, no margin and no re-evaluation are needed.  gfx950 has no u8 MFMA:
+// both sides are shifted by -128 into i8 (x ^ 0x80 on the bytes, done on the fly), which leaves every difference --
+// hence every distance -- unchanged:  d = |l'|^2 + |r'|^2 - 2 <l', r'>, with <l', r'> from v_mfma_i32_32x32x32_i8
+// (exact in i32: |<l', r'>| <= 128 * 128^2 = 2^21).  The reference's float tree is exact on byte-valued inputs too
+// (every partial sum is an integer below 2^24), so the result is the reference's bit for bit.
+//
+// Top-2 per (left descriptor, chunk of <= 512 right descriptors) on 32-bit KEYS  key = d << 9 | (index within the chunk):
+// d < 2^23 leaves 9 bits, and the (distance, index) order -- what the reference's scan with strict '<' keeps -- is the
+// unsigned order of the keys, so the running pair is one v_min_u32 and one median (min / max) per value.  Lanes of the
+// two half waves see disjoint rows of the same column and merge through one shuffle; k_match_u8_merge combines the
+// chunks in index order as k_match_merge does.
+// MFMA operand layout as in k_match_mfma: lane l supplies row / column l & 31 and the 16 bytes of half l >> 5 of each
+// 32-byte k-step, the SAME bytes of a descriptor on both sides; C/D: column = lane & 31, row = (reg & 3) + 8 (reg >> 2)
+// + 4 (lane >> 5).  A = right descriptors (rows), B = left descriptors (columns).
+// =====================================================================================================================
+namespace {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int U8_TILE = 32;                  // right descriptors per MFMA tile
+constexpr int U8_CHUNK_MAX = 512;            // right descriptors per chunk: 9 index bits in the key
+constexpr unsigned U8_NONE = 0xffffffffu;    // empty key: larger than any real one (d << 9 | 511 < 2^32 - 1)
+
+__global__ void k_quantize_desc(const float* __restrict__ src, size_t n4, unsigned* __restrict__ dst)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // four values per thread
+    if (i >= n4) return;
+    const float4 v = reinterpret_cast<const float4*>(src)[i];
+    dst[i] = psx_quantize_u8(v.x) | (psx_quantize_u8(v.y) << 8) | (psx_quantize_u8(v.z) << 16) | (psx_quantize_u8(v.w) << 24);
+}
+
+// |x - 128|^2 of every descriptor of both sets (blocks [0, blocks_a): the first set); 8 lanes per descriptor (16 bytes
+// each).  The norm arrays are written up to a multiple of U8_TILE plus one tile with zeros: the matcher reads whole tiles.
+__global__ void k_u8_norms(const unsigned char* __restrict__ src_a, int n_a, int* __restrict__ norm_a, int blocks_a,
+                           const unsigned char* __restrict__ src_b, int n_b, int* __restrict__ norm_b)
+{
+    const bool second = (int)blockIdx.x >= blocks_a;
+    const unsigned char* src = second ? src_b : src_a;
+    const int n = second ? n_b : n_a;
+    int* norm = second ? norm_b : norm_a;
+    const int g = ((int)blockIdx.x - (second ? blocks_a : 0)) * blockDim.x + threadIdx.x;
+    const int d = g >> 3, q = g & 7;
+    const int npad = ((n + U8_TILE - 1) / U8_TILE + 1) * U8_TILE;
+    if (d >= npad) return;
+    int ss = 0;
+    if (d < n) {
+        const uint4 v = reinterpret_cast<const uint4*>(src + (size_t)d * 128)[q];
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+#pragma unroll
+            for (int b = 0; b < 4; b++) { const int x = (int)((w[k] >> (8 * b)) & 0xffu) - 128; ss += x * x; }
+    }
+    ss += __shfl_xor(ss, 4, 8); ss += __shfl_xor(ss, 2, 8); ss += __shfl_xor(ss, 1, 8);
+    if (q == 0) norm[d] = ss;
+}
+
+__device__ __forceinline__ i32x4 u8_frag(const unsigned char* __restrict__ p)
+{
+    const uint4 v = *reinterpret_cast<const uint4*>(p);
+    return (i32x4){(int)(v.x ^ 0x80808080u), (int)(v.y ^ 0x80808080u), (int)(v.z ^ 0x80808080u), (int)(v.w ^ 0x80808080u)};
+}
+
+__device__ __forceinline__ void key_insert(unsigned& m1, unsigned& m2, unsigned k)
+{
+    m2 = min(m2, max(m1, k));                // m1 <= m2: the median of (m1, m2, k)
+    m1 = min(m1, k);
+}
+
+// grid (ceil(l_len / 256), nchunks), 256 threads: wave w owns left descriptors [256 bx + 64 w, + 64) as two B fragment sets
+// of 32 columns; every wave walks the chunk's right descriptors in tiles of 32 (A fragments straight from global memory:
+// the four waves of a workgroup read the same rows, the L1 serves the other three).  partial[chunk * l_len + left] =
+// (smallest, second smallest key).
+__global__ __launch_bounds__(256) void k_match_u8(const unsigned char* __restrict__ left, const int* __restrict__ ln2, int l_len,
+                                                  const unsigned char* __restrict__ right, const int* __restrict__ rn2, int r_len,
+                                                  int chunk_len, uint2* __restrict__ partial)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = lane & 31, half = lane >> 5;
+    const int r0 = blockIdx.y * chunk_len, r1 = min(r0 + chunk_len, r_len);
+    i32x4 bfrag[2][4];
+    int nl[2], lidx[2];
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        const int li = blockIdx.x * 256 + wave * 64 + c * 32 + col;
+        lidx[c] = li;
+        const int lq = min(li, l_len - 1);                  // idle columns repeat the last descriptor
+        const unsigned char* lp = left + (size_t)lq * 128 + half * 16;
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) bfrag[c][kk] = u8_frag(lp + kk * 32);
+        nl[c] = ln2[lq];
+    }
+    unsigned m1[2] = {U8_NONE, U8_NONE}, m2[2] = {U8_NONE, U8_NONE};
+    for (int base = r0; base < r1; base += U8_TILE) {
+        const unsigned char* rp = right + (size_t)min(base + col, r_len - 1) * 128 + half * 16;
+        i32x4 a[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) a[kk] = u8_frag(rp + kk * 32);
+        // this lane's 16 rows: base + 8 g + 4 half + e (the norm arrays are padded by a tile of zeros)
+        int nr[16];
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const int4 v = *reinterpret_cast<const int4*>(rn2 + base + 8 * g + 4 * half);
+            nr[4 * g] = v.x; nr[4 * g + 1] = v.y; nr[4 * g + 2] = v.z; nr[4 * g + 3] = v.w;
+        }
+        i32x16 acc[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            acc[c] = (i32x16){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int kk = 0; kk < 4; kk++) acc[c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[kk], bfrag[c][kk], acc[c], 0, 0, 0);
+        }
+        const unsigned loc0 = (unsigned)(base - r0 + 4 * half);
+        const bool full = base + U8_TILE <= r1;             // wave uniform: only a chunk's last tile can be partial
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+#pragma unroll
+            for (int reg = 0; reg < 16; reg++) {
+                const int roff = 8 * (reg >> 2) + (reg & 3);
+                const unsigned d = (unsigned)(nl[c] + nr[reg] - 2 * acc[c][reg]);
+                unsigned key = (d << 9) | (loc0 + (unsigned)roff);
+                if (!full && base + 4 * half + roff >= r1) key = U8_NONE;
+                key_insert(m1[c], m2[c], key);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        const unsigned o1 = __shfl_xor(m1[c], 32), o2 = __shfl_xor(m2[c], 32);
+        key_insert(m1[c], m2[c], o1);
+        key_insert(m1[c], m2[c], o2);
+        if (half == 0 && lidx[c] < l_len) partial[(size_t)blockIdx.y * l_len + lidx[c]] = make_uint2(m1[c], m2[c]);
+    }
+}
+
+// out[3 l .. 3 l + 2] = (best, second, accept), out[3 l_len + 2 l ..] = the two distances (INT_MAX: none)
+__global__ void k_match_u8_merge(const uint2* __restrict__ partial, int l_len, int nchunks, int chunk_len, int* __restrict__ out)
+{
+    const int li = blockIdx.x * blockDim.x + threadIdx.x;
+    if (li >= l_len) return;
+    // the reference starts from (inf, inf, index 0, index 0); chunks are visited in index order and a chunk's two entries
+    // are in (distance, index) order, so strict '<' on the distance reproduces the sequential scan
+    int d1 = INT_MAX, d2 = INT_MAX, i1 = 0, i2 = 0;
+    for (int c = 0; c < nchunks; c++) {
+        const uint2 p = partial[(size_t)c * l_len + li];
+        const unsigned k[2] = {p.x, p.y};
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            if (k[e] == U8_NONE) continue;
+            const int d = (int)(k[e] >> 9), i = c * chunk_len + (int)(k[e] & 511u);
+            if (d < d1) { d2 = d1; i2 = i1; d1 = d; i1 = i; }
+            else if (d < d2) { d2 = d; i2 = i; }
+        }
+    }
+    // IEEE division (no v_rcp): the integers are exact in float; a missing neighbour is +inf, as in psx_match
+    const float f1 = d1 == INT_MAX ? INFINITY : (float)d1, f2 = d2 == INT_MAX ? INFINITY : (float)d2;
+    const bool accept = (f1 / f2 < 0.8f);
+    out[3 * li + 0] = i1; out[3 * li + 1] = i2; out[3 * li + 2] = accept ? 1 : 0;
+    out[3 * (size_t)l_len + 2 * li + 0] = d1; out[3 * (size_t)l_len + 2 * li + 1] = d2;
+}
+
+} // namespace
+
+extern "C" int psx_quantize_desc(int device, const float* d_src, int n, unsigned char* d_dst)
+{
+    if (n < 0 || (n > 0 && (!d_src || !d_dst))) return PSX_ERR_INVALID;
+    if (n == 0) return PSX_OK;
+    if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
+    MatchScratch& sc = t_scratch;
+    if (!sc.bind(device)) return PSX_ERR_HIP;
+    const size_t n4 = (size_t)n * 32;
+    hipLaunchKernelGGL(k_quantize_desc, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, sc.stream, d_src, n4,
+                       reinterpret_cast<unsigned*>(d_dst));
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(sc.stream) != hipSuccess) return PSX_ERR_HIP;
+    return PSX_OK;
+}
+
+extern "C" int psx_match_u8(int device, const unsigned char* d_left, int l_len, const unsigned char* d_right, int r_len,
+                            int* host_match, int* host_dist)
+{
+    if (l_len < 0 || r_len < 0 || (l_len > 0 && (!d_left || !host_match)) || (r_len > 0 && !d_right))
+        return PSX_ERR_INVALID;
+    if (l_len == 0) return PSX_OK;
+    if (r_len == 0) {
+        // what psx_match returns: no neighbour, indices 0, rejected
+        for (int i = 0; i < l_len; i++) {
+            host_match[3 * i] = host_match[3 * i + 1] = host_match[3 * i + 2] = 0;
+            if (host_dist) host_dist[2 * i] = host_dist[2 * i + 1] = INT_MAX;
+        }
+        return PSX_OK;
+    }
+    if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
+    MatchScratch& sc = t_scratch;
+    if (!sc.bind(device)) return PSX_ERR_HIP;
+    // chunks of at most U8_CHUNK_MAX right descriptors (the key's index bits), whole tiles, enough workgroups for the chip
+    const int lblocks = (l_len + 255) / 256;
+    int nchunks = (2048 + lblocks - 1) / lblocks;
+    const int min_chunks = (r_len + U8_CHUNK_MAX - 1) / U8_CHUNK_MAX;
+    if (nchunks < min_chunks) nchunks = min_chunks;
+    if (nchunks > (r_len + U8_TILE - 1) / U8_TILE) nchunks = (r_len + U8_TILE - 1) / U8_TILE;
+    int chunk_len = (r_len + nchunks - 1) / nchunks;
+    chunk_len = ((chunk_len + U8_TILE - 1) / U8_TILE) * U8_TILE;
+    nchunks = (r_len + chunk_len - 1) / chunk_len;
+
+    const size_t lpad = ((size_t)(l_len + U8_TILE - 1) / U8_TILE + 1) * U8_TILE;
+    const size_t rpad = ((size_t)(r_len + U8_TILE - 1) / U8_TILE + 1) * U8_TILE;
+    const size_t ob = sizeof(int) * 5 * (size_t)l_len;
+    if (!sc.need(10, sizeof(uint2) * (size_t)nchunks * l_len) || !sc.need(11, sizeof(int) * (lpad + rpad)) || !sc.need(12, ob))
+        return PSX_ERR_NOMEM;
+    uint2* d_partial = static_cast<uint2*>(sc.buf[10]);
+    int* d_ln2 = static_cast<int*>(sc.buf[11]);
+    int* d_rn2 = d_ln2 + lpad;                   // lpad is a multiple of U8_TILE: 16-byte aligned
+    int* d_out = static_cast<int*>(sc.buf[12]);
+    hipStream_t st = sc.stream;
+    const int rnb = (int)((rpad * 8 + 255) / 256), lnb = (int)((lpad * 8 + 255) / 256);
+    hipLaunchKernelGGL(k_u8_norms, dim3(rnb + lnb), dim3(256), 0, st, d_right, r_len, d_rn2, rnb, d_left, l_len, d_ln2);
+    hipLaunchKernelGGL(k_match_u8, dim3(lblocks, nchunks), dim3(256), 0, st, d_left, d_ln2, l_len, d_right, d_rn2, r_len,
+                       chunk_len, d_partial);
+    hipLaunchKernelGGL(k_match_u8_merge, dim3((l_len + 255) / 256), dim3(256), 0, st, d_partial, l_len, nchunks, chunk_len, d_out);
+    if (!sc.need_pinned(ob)) return PSX_ERR_NOMEM;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(sc.hpin, d_out, ob, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return PSX_ERR_HIP;
+    const int* hp = static_cast<const int*>(sc.hpin);
+    memcpy(host_match, hp, sizeof(int) * 3 * (size_t)l_len);
+    if (host_dist) memcpy(host_dist, hp + 3 * (size_t)l_len, sizeof(int) * 2 * (size_t)l_len);
     return PSX_OK;
 }

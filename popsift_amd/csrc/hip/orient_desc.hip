@@ -560,7 +560,7 @@ __global__ __launch_bounds__(SCAN_NT) void k_scan(const PsxParams* __restrict__ 
 }
 
 // normalize_histogram (s_desc_norm_rs.h:42-77 / s_desc_norm_l2.h:86-135); the lane owns bins 2*lane, 2*lane+1 of
-// descriptor j and stores them (device array and, when attached, the zero-copy export)
+// descriptor j and stores them (device array and, when attached, the zero-copy export; in byte mode also the bytes)
 __device__ __forceinline__ void normalize_store(const PsxParams* P, const PsxExport& X, int j, int lane, float a, float b)
 {
     if (P->norm_mode == PSX_NORM_ROOTSIFT) {
@@ -580,6 +580,13 @@ __device__ __forceinline__ void normalize_store(const PsxParams* P, const PsxExp
     reinterpret_cast<float2*>(P->desc + (size_t)j * 128)[lane] = make_float2(a, b);
     if (X.desc != nullptr && j < X.desc_capacity)
         reinterpret_cast<float2*>(X.desc + (size_t)j * 128)[lane] = make_float2(a, b);
+    // byte mode (wave uniform): the two bins quantised, one 16-bit store per lane = one 128-byte row per wave
+    if (X.desc_u8 != nullptr) {
+        const unsigned short q = (unsigned short)(psx_quantize_u8(a) | (psx_quantize_u8(b) << 8));
+        reinterpret_cast<unsigned short*>(X.desc_u8 + (size_t)j * 128)[lane] = q;
+        if (X.xdesc_u8 != nullptr && j < X.desc_capacity)
+            reinterpret_cast<unsigned short*>(X.xdesc_u8 + (size_t)j * 128)[lane] = q;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

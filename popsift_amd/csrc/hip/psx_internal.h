@@ -69,7 +69,21 @@ struct PsxExport {
     int*          counts;                // [0]=ext_total [1]=ori_total [2]=ori_raw, pinned host memory
     int           feat_capacity;
     int           desc_capacity;
+    // byte descriptors (psx_set_descriptor_format PSX_DESCFMT_U8): the context's device byte array (nullptr in float mode:
+    // the descriptor kernels' one wave-uniform branch) and the byte export target (nullptr when none is attached;
+    // desc_capacity is its capacity then)
+    unsigned char* desc_u8;
+    unsigned char* xdesc_u8;
 };
+
+// The one quantisation rule of byte descriptors: q = (uint8) min(255, max(0, roundf(d))).  roundf rounds half away from
+// zero, as the reference's --write-as-uchar text output does (features.cu:310-330); rintf / v_rndne_f32 round half to
+// even and differ on every exact .5.  NaN becomes 0.
+__device__ __forceinline__ unsigned psx_quantize_u8(float d)
+{
+    const float r = fminf(fmaxf(roundf(d), 0.0f), 255.0f);
+    return (unsigned)r;
+}
 
 // ExtremaCounters (sift_pyramid.h:21-33), kept in device memory of the context.
 struct PsxCounters {

@@ -48,6 +48,10 @@ static void parseargs( int argc, char** argv, popsift::Config& config, string& i
     all.flag( "print-time-info", 0, "A debug output printing image processing time after load()", [&]() { print_time_info = true; } );
     all.flag( "write-as-uchar", 0, "Output descriptors rounded to int. Should be combined with --norm-multi=9 or similar", [&]() { write_as_uchar = true; } );
     all.flag( "dont-write", 0, "Suppress descriptor output", [&]() { dont_write = true; } );
+    // not in the reference tool: the pipeline hands back byte descriptors (Config::ByteDescriptors); output-features.txt
+    // is written from the bytes (the --write-as-uchar line format)
+    all.flag( "uchar-descriptors", 0, "Extract byte descriptors (roundf, saturated at 255) and write them as integers",
+              [&]() { config.setDescriptorFormat( popsift::Config::ByteDescriptors ); } );
     all.flag( "pgmread-loading", 0, "Use the PGM/PPM loader (the only loader of this build)", []() {} );
     all.flag( "float-mode", 0, "Upload image to GPU as float instead of byte", [&]() { float_mode = true; } );
     // not in the reference tool: several replicas in one process, image i goes to replica i mod N (BASELINE config 4)

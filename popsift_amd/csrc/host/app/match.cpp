@@ -18,6 +18,7 @@
 using namespace std;
 
 static bool print_dev_info = false;
+static bool uchar_desc = false;
 
 static bool is_file( const string& p ) { struct stat st; return stat( p.c_str(), &st ) == 0 && S_ISREG( st.st_mode ); }
 
@@ -50,6 +51,8 @@ int main( int argc, char** argv )
     all.flag( "print-time-info", 0, "accepted for compatibility", []() {} );
     all.flag( "write-as-uchar", 0, "accepted for compatibility", []() {} );
     all.flag( "dont-write", 0, "accepted for compatibility", []() {} );
+    // not in the reference tool: quantise both descriptor sets to bytes and run the exact integer matcher
+    all.flag( "uchar-descriptors", 0, "Match byte descriptors (FeaturesDev::matchBytes)", [&]() { uchar_desc = true; } );
     all.flag( "pgmread-loading", 0, "Use the PGM/PPM loader (the only loader of this build)", []() {} );
     try {
         all.parse( argc, argv );
@@ -79,7 +82,8 @@ int main( int argc, char** argv )
         cout << "Number of features:    " << rFeatures->getFeatureCount() << endl;
         cout << "Number of descriptors: " << rFeatures->getDescriptorCount() << endl;
         cout.flush();
-        lFeatures->match( rFeatures );
+        if( uchar_desc ) lFeatures->matchBytes( rFeatures );
+        else             lFeatures->match( rFeatures );
         fflush( stdout );
         delete lFeatures; delete rFeatures; delete lJob; delete rJob;
         sift.uninit();

@@ -247,9 +247,9 @@ Stats pinned_stats( int device )
 }
 } // namespace pool
 
-FeaturesHost::FeaturesHost( ) : _ext( nullptr ), _ori( nullptr ), _ext_cap( 0 ), _ori_cap( 0 ) { }
+FeaturesHost::FeaturesHost( ) : _ext( nullptr ), _ori( nullptr ), _ext_cap( 0 ), _ori_cap( 0 ), _bytes( false ) { }
 
-FeaturesHost::FeaturesHost( int num_ext, int num_ori ) : _ext( nullptr ), _ori( nullptr ), _ext_cap( 0 ), _ori_cap( 0 )
+FeaturesHost::FeaturesHost( int num_ext, int num_ori ) : _ext( nullptr ), _ori( nullptr ), _ext_cap( 0 ), _ori_cap( 0 ), _bytes( false )
 {
     reset( num_ext, num_ori );
 }
@@ -264,6 +264,53 @@ void FeaturesHost::release( )
     if( _ext_cap ) pool::put_plain( _ext, _ext_cap ); else free( _ext );
     if( _ori_cap ) pool::put_pinned( _ori, _ori_cap ); else free( _ori );
     _ext = nullptr; _ori = nullptr; _ext_cap = _ori_cap = 0;
+    _bytes = false;
+    _desc_idx.clear();
+}
+
+void FeaturesHost::adoptBytes( int num_ext, int num_ori, Feature* ext, size_t ext_cap, unsigned char* bytes, size_t bytes_cap,
+                               std::vector<int>&& desc_idx )
+{
+    release();
+    _ext = ext; _ext_cap = ext_cap;
+    _ori = reinterpret_cast<Descriptor*>( bytes ); _ori_cap = bytes_cap;
+    _bytes = true;
+    _desc_idx = std::move( desc_idx );
+    setFeatureCount( num_ext );
+    setDescriptorCount( num_ori );
+}
+
+void FeaturesHost::resetBytes( int num_ext, int num_ori )
+{
+    release();
+    _ext = (Feature*)page_alloc( (size_t)num_ext * sizeof(Feature) );
+    _ori = (Descriptor*)page_alloc( (size_t)num_ori * 128 );
+    if( _ext == nullptr || _ori == nullptr ) {
+        std::ostringstream ss;
+        ss << "Runtime error:" << std::endl
+           << "    Failed to (re)allocate memory for downloading " << num_ext << " features and " << num_ori << " byte descriptors";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    _bytes = true;
+    _desc_idx.assign( (size_t)num_ext * ORIENTATION_MAX_COUNT, -1 );
+    setFeatureCount( num_ext );
+    setDescriptorCount( num_ori );
+}
+
+int FeaturesHost::descriptorIndex( int feature, int ori ) const
+{
+    if( feature < 0 || feature >= size() || ori < 0 || ori >= ORIENTATION_MAX_COUNT ) return -1;
+    if( _bytes ) return _desc_idx[(size_t)feature * ORIENTATION_MAX_COUNT + ori];
+    const Descriptor* d = _ext[feature].desc[ori];
+    return d ? (int)( d - _ori ) : -1;
+}
+
+const unsigned char* FeaturesHost::descriptorBytes( int feature, int ori ) const
+{
+    if( !_bytes ) return nullptr;
+    const int j = descriptorIndex( feature, ori );
+    if( j < 0 || j >= getDescriptorCount() ) return nullptr;
+    return reinterpret_cast<const unsigned char*>( _ori ) + (size_t)j * 128;
 }
 
 void FeaturesHost::adopt( int num_ext, int num_ori, Feature* ext, size_t ext_cap, Descriptor* ori, size_t ori_cap )
@@ -302,7 +349,22 @@ void FeaturesHost::unpin( ) { }
 
 void FeaturesHost::print( std::ostream& ostr, bool write_as_uchar ) const
 {
-    for( int i = 0; i < size(); i++ ) _ext[i].print( ostr, write_as_uchar );
+    if( !_bytes ) {
+        for( int i = 0; i < size(); i++ ) _ext[i].print( ostr, write_as_uchar );
+        return;
+    }
+    // byte result: the usual line with the bytes as integers (what --write-as-uchar prints for values <= 255)
+    for( int i = 0; i < size(); i++ ) {
+        const Feature& f = _ext[i];
+        const float sigval = 1.0f / ( f.sigma * f.sigma );
+        for( int ori = 0; ori < f.num_ori; ori++ ) {
+            ostr << f.xpos << " " << f.ypos << " " << sigval << " 0 " << sigval << " ";
+            const unsigned char* b = descriptorBytes( i, ori );
+            if( b != nullptr )
+                for( int k = 0; k < 128; k++ ) ostr << (int)b[k] << " ";
+            ostr << std::endl;
+        }
+    }
 }
 
 std::ostream& operator<<( std::ostream& ostr, const FeaturesHost& feature )
@@ -317,7 +379,9 @@ void Feature::print( std::ostream& ostr, bool write_as_uchar ) const
     const float sigval = 1.0f / ( sigma * sigma );
     for( int ori = 0; ori < num_ori; ori++ ) {
         ostr << xpos << " " << ypos << " " << sigval << " 0 " << sigval << " ";
-        if( write_as_uchar ) {
+        if( desc[ori] == nullptr ) {
+            // a byte result (Config::ByteDescriptors) has no float descriptors: FeaturesHost::print writes its bytes
+        } else if( write_as_uchar ) {
             for( int i = 0; i < 128; i++ ) ostr << roundf( desc[ori]->features[i] ) << " ";
         } else {
             ostr << std::setprecision(3);
@@ -393,6 +457,41 @@ void FeaturesDev::match( FeaturesDev* other )
                 r_len > 0 ? r_fem[m1] : 0, m1,
                 r_len > 0 ? r_fem[m2] : 0, m2,
                 dd[2*i], dd[2*i+1] );
+    }
+}
+
+// FeaturesDev::matchBytes: both descriptor sets quantised on the device with the byte rule, then psx_match_u8 (exact:
+// the reference's result on the bytes, bit for bit); same lines as match(), the integer distances printed alike
+void FeaturesDev::matchBytes( FeaturesDev* other )
+{
+    if( other == nullptr ) fatal( __FILE__, __LINE__, "FeaturesDev::matchBytes: null argument" );
+    const int l_len = getDescriptorCount();
+    const int r_len = other->getDescriptorCount();
+    if( l_len <= 0 ) return;
+    std::vector<int> mm( 3 * (size_t)l_len ), dd( 2 * (size_t)l_len );
+    std::vector<int> l_fem( l_len ), r_fem( r_len > 0 ? r_len : 1 );
+    void *lb = nullptr, *rb = nullptr;
+    bool ok = psx_dev_alloc( _device, (size_t)l_len * 128, &lb ) == PSX_OK &&
+              psx_dev_alloc( _device, (size_t)( r_len > 0 ? r_len : 1 ) * 128, &rb ) == PSX_OK &&
+              psx_quantize_desc( _device, (const float*)_ori, l_len, (unsigned char*)lb ) == PSX_OK &&
+              psx_quantize_desc( _device, (const float*)other->_ori, r_len, (unsigned char*)rb ) == PSX_OK &&
+              psx_match_u8( _device, (const unsigned char*)lb, l_len, (const unsigned char*)rb, r_len, mm.data(), dd.data() ) == PSX_OK &&
+              psx_dev_read( _device, l_fem.data(), _rev, (size_t)l_len * sizeof(int) ) == PSX_OK &&
+              ( r_len <= 0 || psx_dev_read( other->_device, r_fem.data(), other->_rev, (size_t)r_len * sizeof(int) ) == PSX_OK );
+    psx_dev_free( _device, lb );
+    psx_dev_free( _device, rb );
+    if( !ok ) fatal( __FILE__, __LINE__, "FeaturesDev::matchBytes failed" );
+    for( int i = 0; i < l_len; i++ )
+    {
+        const int m1 = mm[3*i], m2 = mm[3*i+1];
+        const float d1 = dd[2*i] == INT32_MAX ? INFINITY : (float)dd[2*i];
+        const float d2 = dd[2*i+1] == INT32_MAX ? INFINITY : (float)dd[2*i+1];
+        printf( "%s feat %4d [%4d] matches feat %4d [%4d] ( 2nd feat %4d [%4d] ) dist %.3f vs %.3f\n",
+                mm[3*i+2] ? "accept" : "reject",
+                l_fem[i], i,
+                r_len > 0 ? r_fem[m1] : 0, m1,
+                r_len > 0 ? r_fem[m2] : 0, m2,
+                d1, d2 );
     }
 }
 

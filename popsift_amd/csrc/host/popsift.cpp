@@ -437,6 +437,73 @@ popsift::FeaturesHost* collect_host( Slot& s, std::atomic<int>& want_desc, doubl
     return f;
 }
 
+// Config::ByteDescriptors: the same three paths as collect_host (DMA into a pooled pinned buffer, the zero-copy export
+// with POPSIFT_EXPORT=1, pageable arrays beyond the pinned limit) with the quantised bytes -- 128 per descriptor -- as
+// the result's descriptor storage; Feature::desc[] stay nullptr, the rows come from psx_feature::desc_idx
+popsift::FeaturesHost* collect_host_bytes( Slot& s, std::atomic<int>& want_desc, double* t_frame )
+{
+    int ne = 0, no = 0;
+    const double t0 = pnow();
+    check( s.ctx, psx_counts( s.ctx, &ne, &no ), "psx_counts" );       // waits for the frame
+    *t_frame += pnow() - t0;
+    if( no == 0 ) cerr << "Warning: no descriptors extracted" << endl;   // sift_desc.cu:88-92
+    want_desc = std::max( 32768, no + no / 2 );
+    popsift::FeaturesHost* f = new popsift::FeaturesHost();
+    size_t ext_cap = 0;
+    popsift::Feature* dst = (popsift::Feature*)popsift::pool::get_plain( (size_t)std::max( ne, 1 ) * sizeof(popsift::Feature), &ext_cap );
+    if( dst == nullptr ) { delete f; throw std::runtime_error( "out of host memory for features" ); }
+    const psx_feature* src = s.xfeat;
+    std::vector<psx_feature> tmp;
+    unsigned char* xbytes = reinterpret_cast<unsigned char*>( s.xdesc );
+    const bool exported = xbytes != nullptr && s.desc_cap > 0 && ne <= EXPORT_FEATURES && no <= s.desc_cap;
+    const bool hoarding = popsift::pool::pinned_in_use() > pinned_limit();
+    if( !exported && xbytes != nullptr && no > s.desc_cap ) {
+        popsift::pool::put_pinned( s.xdesc, s.xdesc_cap );       // too small: the next frame attaches a want_desc-sized one
+        s.xdesc = nullptr; s.xdesc_cap = 0; s.desc_cap = 0;
+    }
+    std::vector<int> idx( (size_t)ne * ORIENTATION_MAX_COUNT, -1 );
+    try {
+        if( hoarding ) {
+            popsift::pool::put_plain( dst, ext_cap );
+            f->resetBytes( ne, no );
+            dst = f->getFeatures();
+        }
+        if( !exported ) {
+            psx_feature* ftarget = s.xfeat;
+            if( ftarget == nullptr || ne > EXPORT_FEATURES ) { tmp.resize( std::max( ne, 1 ) ); ftarget = tmp.data(); }
+            unsigned char* bytes = f->byteStorage();
+            size_t cap = 0;
+            if( !hoarding ) {
+                bytes = (unsigned char*)popsift::pool::get_pinned( (size_t)std::max( no, 1 ) * 128, &cap );
+                if( bytes == nullptr ) { popsift::pool::put_plain( dst, ext_cap ); dst = nullptr; throw std::runtime_error( "out of host memory for descriptors" ); }
+                f->adoptBytes( ne, no, dst, ext_cap, bytes, cap, std::vector<int>() );
+            }
+            check( s.ctx, psx_download_u8( s.ctx, ftarget, ne, bytes, no ), "psx_download_u8" );
+            src = ftarget;
+        } else if( hoarding ) {
+            memcpy( f->byteStorage(), xbytes, (size_t)no * 128 );
+        } else {
+            // the GPU wrote the bytes straight into s.xdesc: the result object takes the buffer over
+            f->adoptBytes( ne, no, dst, ext_cap, xbytes, s.xdesc_cap, std::vector<int>() );
+            s.xdesc = nullptr; s.xdesc_cap = 0; s.desc_cap = 0;
+        }
+    } catch( ... ) { delete f; throw; }
+    for( int i = 0; i < ne; i++ ) {
+        const psx_feature& a = src[i];
+        popsift::Feature&  b = dst[i];
+        b.debug_octave = a.debug_octave;
+        b.xpos = a.xpos; b.ypos = a.ypos; b.sigma = a.sigma;
+        b.num_ori = a.num_ori;
+        for( int k = 0; k < ORIENTATION_MAX_COUNT; k++ ) {
+            b.orientation[k] = a.orientation[k];
+            b.desc[k] = nullptr;
+            idx[(size_t)i * ORIENTATION_MAX_COUNT + k] = ( a.desc_idx[k] >= 0 && a.desc_idx[k] < no ) ? a.desc_idx[k] : -1;
+        }
+    }
+    f->byteIndex() = std::move( idx );
+    return f;
+}
+
 popsift::FeaturesDev* collect_dev( Slot& s, int device )
 {
     int ne = 0, no = 0;
@@ -468,6 +535,8 @@ void PopSift::dispatchLoop( )
     pin_to_device_numa_node( _device );
     popsift::pool::set_thread_device( _device );        // result and export buffers: this device's pinned pool
     double t_attach = 0, t_upload = 0, t_submit = 0, t_frame = 0, t_wrap = 0, t_pool = 0; int n_done = 0;
+    // configure() is refused once a context exists, so the format read here holds for every frame of this worker
+    bool bytes_out = false;
 
     for( ;; ) {
         SiftJob* job = p.queue.pull();
@@ -482,6 +551,8 @@ void PopSift::dispatchLoop( )
                     p.contexts_exist = true;
                     to_psx( _config, pc );
                     if( pc.octaves < 0 && p.octaves_resolved >= 0 ) pc.octaves = p.octaves_resolved;
+                    bytes_out = _proc_mode == popsift::Config::ExtractingMode &&
+                                _config.getDescriptorFormat() == popsift::Config::ByteDescriptors;
                 }
                 if( psx_create( _device, &pc, &s.ctx ) != PSX_OK ) {
                     const char* m = psx_last_error( nullptr );
@@ -489,6 +560,8 @@ void PopSift::dispatchLoop( )
                     throw std::runtime_error( std::string( "psx_create failed:\n    " ) + ( m ? m : "" ) );
                 }
                 psx_set_wait_mode( s.ctx, 1 );                       // sleep, do not spin: there are PIPE_DEPTH of us
+                // byte descriptors for host results (device results stay float: FeaturesDev)
+                if( bytes_out ) check( s.ctx, psx_set_descriptor_format( s.ctx, PSX_DESCFMT_U8 ), "psx_set_descriptor_format" );
                 if( _proc_mode == popsift::Config::ExtractingMode ) {
                     s.xfeat = (psx_feature*)popsift::pool::get_pinned( (size_t)EXPORT_FEATURES * sizeof(psx_feature), &s.xfeat_cap );
                     if( s.xfeat == nullptr ) throw std::runtime_error( "out of host memory for export buffers" );
@@ -505,11 +578,15 @@ void PopSift::dispatchLoop( )
                 // the previous result took this context's descriptor buffer with it: attach a fresh one
                 const int want = p.want_desc;
                 const double tp0 = pnow();
-                s.xdesc = (float*)popsift::pool::get_pinned( (size_t)want * sizeof(popsift::Descriptor), &s.xdesc_cap );
+                const size_t row = bytes_out ? 128 : sizeof(popsift::Descriptor);
+                s.xdesc = (float*)popsift::pool::get_pinned( (size_t)want * row, &s.xdesc_cap );
                 t_pool += pnow() - tp0;
                 if( s.xdesc == nullptr ) throw std::runtime_error( "out of host memory for export buffers" );
-                s.desc_cap = (int)std::min<size_t>( s.xdesc_cap / sizeof(popsift::Descriptor), (size_t)1 << 30 );
-                check( s.ctx, psx_attach_export_mapped( s.ctx, s.xfeat, EXPORT_FEATURES, s.xdesc, s.desc_cap ), "psx_attach_export_mapped" );
+                s.desc_cap = (int)std::min<size_t>( s.xdesc_cap / row, (size_t)1 << 30 );
+                if( bytes_out )
+                    check( s.ctx, psx_attach_export_mapped_u8( s.ctx, s.xfeat, EXPORT_FEATURES, (unsigned char*)s.xdesc, s.desc_cap ), "psx_attach_export_mapped_u8" );
+                else
+                    check( s.ctx, psx_attach_export_mapped( s.ctx, s.xfeat, EXPORT_FEATURES, s.xdesc, s.desc_cap ), "psx_attach_export_mapped" );
             }
             const double t1 = pnow();
             popsift::trace::Range r_frame( "popsift frame" );
@@ -528,7 +605,7 @@ void PopSift::dispatchLoop( )
             double tf = 0;
             if( _proc_mode == popsift::Config::ExtractingMode ) {
                 popsift::trace::Range r_dl( "download descriptors" );              // sift_pyramid.cu:288-319
-                f = collect_host( s, p.want_desc, &tf );
+                f = bytes_out ? collect_host_bytes( s, p.want_desc, &tf ) : collect_host( s, p.want_desc, &tf );
                 if( _config.getLogMode() == popsift::Config::All ) {      // popsift.cpp:330-338
                     // the reference writes these dumps from its single worker (popsift.cpp:330-338); here PIPE_DEPTH
                     // workers would interleave writes to the same dir-octave / dir-dog / dir-desc files

@@ -50,6 +50,23 @@ popsift_c_handle* popsift_c_create( const psx_config* cfg, int image_mode, int d
     } catch( const std::exception& e ) { t_err = e.what(); return nullptr; }
 }
 
+popsift_c_handle* popsift_c_create_fmt( const psx_config* cfg, int image_mode, int device, int descriptor_format )
+{
+    if( descriptor_format != PSX_DESCFMT_F32 && descriptor_format != PSX_DESCFMT_U8 ) {
+        t_err = "popsift_c_create_fmt: unknown descriptor format";
+        return nullptr;
+    }
+    try {
+        psx_config d;
+        if( cfg == nullptr ) { psx_config_default( &d ); cfg = &d; }
+        popsift::Config k = to_config( *cfg );
+        k.setDescriptorFormat( descriptor_format == PSX_DESCFMT_U8 ? popsift::Config::ByteDescriptors : popsift::Config::FloatDescriptors );
+        PopSift* p = new PopSift( k, popsift::Config::ExtractingMode,
+                                  image_mode ? PopSift::FloatImages : PopSift::ByteImages, device );
+        return reinterpret_cast<popsift_c_handle*>( p );
+    } catch( const std::exception& e ) { t_err = e.what(); return nullptr; }
+}
+
 void popsift_c_destroy( popsift_c_handle* h )
 {
     delete reinterpret_cast<PopSift*>( h );              // the destructor calls uninit()
@@ -95,27 +112,61 @@ const float* popsift_c_descriptors( const popsift_c_features* f )
     return reinterpret_cast<const float*>( fh->getDescriptors() );
 }
 
+namespace {
+void copy_records( popsift::FeaturesHost* fh, psx_feature* features )
+{
+    const int ne = fh->getFeatureCount();
+    const popsift::Feature* src = fh->getFeatures();
+    for( int i = 0; i < ne; i++ ) {
+        psx_feature& o = features[i];
+        o.debug_octave = src[i].debug_octave;
+        o.xpos = src[i].xpos; o.ypos = src[i].ypos; o.sigma = src[i].sigma;
+        o.num_ori = src[i].num_ori;
+        for( int k = 0; k < PSX_ORI_MAX; k++ ) {
+            o.orientation[k] = src[i].orientation[k];
+            o.desc_idx[k] = fh->descriptorIndex( i, k );
+        }
+    }
+}
+} // namespace
+
 int popsift_c_copy( const popsift_c_features* f, psx_feature* features, float* descriptors )
 {
     if( f == nullptr ) return PSX_ERR_INVALID;
     popsift::FeaturesHost* fh = const_cast<popsift::FeaturesHost*>( reinterpret_cast<const popsift::FeaturesHost*>( f ) );
-    const int ne = fh->getFeatureCount(), no = fh->getDescriptorCount();
-    const popsift::Descriptor* base = fh->getDescriptors();
-    if( features != nullptr ) {
-        const popsift::Feature* src = fh->getFeatures();
-        for( int i = 0; i < ne; i++ ) {
-            psx_feature& o = features[i];
-            o.debug_octave = src[i].debug_octave;
-            o.xpos = src[i].xpos; o.ypos = src[i].ypos; o.sigma = src[i].sigma;
-            o.num_ori = src[i].num_ori;
-            for( int k = 0; k < PSX_ORI_MAX; k++ ) {
-                o.orientation[k] = src[i].orientation[k];
-                o.desc_idx[k] = src[i].desc[k] ? (int)( src[i].desc[k] - base ) : -1;
-            }
-        }
+    const int no = fh->getDescriptorCount();
+    if( descriptors != nullptr && fh->hasByteDescriptors() ) {
+        t_err = "popsift_c_copy: the result holds byte descriptors (use popsift_c_copy_u8)";
+        return PSX_ERR_STATE;
     }
-    if( descriptors != nullptr && no > 0 ) memcpy( descriptors, base, (size_t)no * sizeof(popsift::Descriptor) );
+    if( features != nullptr ) copy_records( fh, features );
+    if( descriptors != nullptr && no > 0 ) memcpy( descriptors, fh->getDescriptors(), (size_t)no * sizeof(popsift::Descriptor) );
     return PSX_OK;
+}
+
+int popsift_c_copy_u8( const popsift_c_features* f, psx_feature* features, unsigned char* descriptors )
+{
+    if( f == nullptr ) return PSX_ERR_INVALID;
+    popsift::FeaturesHost* fh = const_cast<popsift::FeaturesHost*>( reinterpret_cast<const popsift::FeaturesHost*>( f ) );
+    const int no = fh->getDescriptorCount();
+    if( descriptors != nullptr && !fh->hasByteDescriptors() ) {
+        t_err = "popsift_c_copy_u8: the result holds float descriptors (use popsift_c_copy)";
+        return PSX_ERR_STATE;
+    }
+    if( features != nullptr ) copy_records( fh, features );
+    if( descriptors != nullptr && no > 0 ) memcpy( descriptors, fh->getDescriptorBytes(), (size_t)no * 128 );
+    return PSX_OK;
+}
+
+int popsift_c_descriptor_format( const popsift_c_features* f )
+{
+    if( f == nullptr ) return PSX_ERR_INVALID;
+    return reinterpret_cast<const popsift::FeaturesHost*>( f )->hasByteDescriptors() ? PSX_DESCFMT_U8 : PSX_DESCFMT_F32;
+}
+
+const unsigned char* popsift_c_descriptor_bytes( const popsift_c_features* f )
+{
+    return f ? reinterpret_cast<const popsift::FeaturesHost*>( f )->getDescriptorBytes() : nullptr;
 }
 
 void popsift_c_free( popsift_c_features* f )

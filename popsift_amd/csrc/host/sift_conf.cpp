@@ -40,6 +40,7 @@ Config::Config( )
     , _normalization_mode( getNormModeDefault() )
     , _normalization_multiplier( 0 )
     , _print_gauss_tables( false )
+    , _descriptor_format( FloatDescriptors )
 { }
 
 void Config::setMode( Config::SiftMode m )       { _sift_mode = m; }

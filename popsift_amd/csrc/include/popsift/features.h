@@ -54,9 +54,11 @@ public:
 class FeaturesHost : public FeaturesBase
 {
     Feature*     _ext;
-    Descriptor*  _ori;
+    Descriptor*  _ori;       // byte results: the no x 128 bytes (getDescriptorBytes)
     size_t       _ext_cap;   // bytes; 0: _ext came from posix_memalign
     size_t       _ori_cap;   // bytes; 0: _ori came from posix_memalign
+    bool         _bytes;     // Config::ByteDescriptors: _ori holds bytes, Feature::desc[] are nullptr
+    std::vector<int> _desc_idx;   // byte results: descriptor row of (feature, orientation), 4 per feature (psx_feature::desc_idx)
 
 public:
     FeaturesHost( );
@@ -77,12 +79,28 @@ public:
     void unpin( );
 
     inline Feature*    getFeatures()    { return _ext; }
-    inline Descriptor* getDescriptors() { return _ori; }
+    /// float descriptors; nullptr for a byte result (no caller may read bytes as floats)
+    inline Descriptor* getDescriptors() { return _bytes ? nullptr : _ori; }
+
+    /// byte results (Config::ByteDescriptors): getDescriptorCount() rows of 128 bytes; nullptr for a float result
+    inline bool hasByteDescriptors() const { return _bytes; }
+    inline const unsigned char* getDescriptorBytes() const { return _bytes ? reinterpret_cast<const unsigned char*>( _ori ) : nullptr; }
+    /// the 128 bytes of orientation `ori` of feature `feature`; nullptr for a float result or an orientation without descriptor
+    const unsigned char* descriptorBytes( int feature, int ori ) const;
+    /// row of (feature, ori) in the descriptor array, -1 when it has none (both formats)
+    int descriptorIndex( int feature, int ori ) const;
 
     void print( std::ostream& ostr, bool write_as_uchar ) const;
 
     /// internal (PopSift): take ownership of pooled buffers (see host_pool.h); caps in bytes
     void adopt( int num_ext, int num_ori, Feature* ext, size_t ext_cap, Descriptor* ori, size_t ori_cap );
+    /// internal (PopSift): the same for a byte result; bytes = num_ori x 128, desc_idx = 4 rows per feature
+    void adoptBytes( int num_ext, int num_ori, Feature* ext, size_t ext_cap, unsigned char* bytes, size_t bytes_cap,
+                     std::vector<int>&& desc_idx );
+    /// internal (PopSift): pageable arrays for a byte result (the pinned-pool limit is exceeded)
+    void resetBytes( int num_ext, int num_ori );
+    inline unsigned char* byteStorage() { return _bytes ? reinterpret_cast<unsigned char*>( _ori ) : nullptr; }
+    inline std::vector<int>& byteIndex() { return _desc_idx; }
 
 protected:
     friend class Pyramid;
@@ -111,6 +129,9 @@ public:
     /// brute-force 2-NN matcher of the reference (features.cu:160-304): prints one accept/reject line
     /// per descriptor of *this, as the reference's show_distance does
     void match( FeaturesDev* other );
+    /// the same on bytes: both float arrays quantised on the device (psx_quantize_desc), then the exact integer
+    /// matcher psx_match_u8; prints the same accept / reject lines as match()
+    void matchBytes( FeaturesDev* other );
 
     inline Feature*    getFeatures()    { return _ext; }
     inline Descriptor* getDescriptors() { return _ori; }

@@ -39,6 +39,12 @@ struct Config
     enum GridFilterMode { RandomScale, LargestScaleFirst, SmallestScaleFirst };
     /// what is kept after processing
     enum ProcessingMode { ExtractingMode, MatchingMode };
+    /// form of the descriptors SiftJob::get() hands back (parallel to PopSift::ImageMode): floats, or bytes
+    /// q = (uint8) min(255, max(0, roundf(d))) of the same floats (include/popsift_hip.h, psx_set_descriptor_format)
+    enum DescriptorFormat { FloatDescriptors, ByteDescriptors };
+
+    void setDescriptorFormat( DescriptorFormat f ) { _descriptor_format = f; }
+    DescriptorFormat getDescriptorFormat( ) const  { return _descriptor_format; }
 
     void setGaussMode( const std::string& m );
     void setGaussMode( GaussMode m );
@@ -129,6 +135,7 @@ private:
     NormMode  _normalization_mode;
     int       _normalization_multiplier;
     bool      _print_gauss_tables;
+    DescriptorFormat _descriptor_format;
 };
 
 inline bool operator==( const Config& l, const Config& r ) { return l.equal( r ); }
