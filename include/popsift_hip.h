@@ -144,8 +144,7 @@ int psx_print_gauss_tables(const psx_config* cfg, int columns);
 
 /* Replaces PopSift::PopSift + applyConfiguration (popsift.cpp:25-48, 91-107): selects the
  * device, uploads Gauss tables / constants into the context (no global symbols), creates the
- * stream.  Modes outside the default branch of build_pyramid (s_pyramid_build.cu:547-575) and
- * DescMode != Loop return PSX_ERR_INVALID ("not yet", sift_desc.cu:80-82). */
+ * stream.  The environment switches of the library are read here, once per context. */
 int psx_create(int device, const psx_config* cfg, psx_ctx** out);
 int psx_destroy(psx_ctx* ctx);
 const char* psx_last_error(const psx_ctx* ctx);   /* ctx may be NULL: last create() error */

@@ -82,6 +82,7 @@ constexpr size_t CAND_CT_BYTES = sizeof(int) * (size_t)PSX_MAX_OCTAVES * PSX_CAN
 struct psx_ctx {
     int         device = 0;
     psx_config  cfg{};
+    PsxTuning   tune;                  // the environment switches as psx_create found them, and the device's CU count
     std::string err;
     hipStream_t stream = nullptr;
 
@@ -144,7 +145,7 @@ struct psx_ctx {
     // everything else the kernels read is device resident (PsxParams) or constant per context (taps)
     hipGraphExec_t graph = nullptr;
     const void* graph_input = nullptr; int graph_is_float = 0, graph_w = 0, graph_h = 0;
-    bool graph_off = true;             // enabled with POPSIFT_HIP_GRAPH=1; switched off again if a capture fails
+    bool graph_off = true;             // !tune.hip_graph (POPSIFT_HIP_GRAPH=1 enables it); switched off again if a capture fails
     bool ext_launched = false;         // ... which has happened for the current frame
 
     // zero-copy export
@@ -167,7 +168,6 @@ struct psx_ctx {
     // nothing -- uploads, the counter read-back and the result downloads still run, on the first frame's results (same
     // counts, same bytes): what the HOST path and PCIe sustain without the kernels; 2 = the DMAs are skipped as well: the
     // host software alone (threads, queues, pools, the per-keypoint record loop).  Results are stale by construction.
-    int  null_work = 0;
     bool null_primed = false;
     bool timers = false;
     bool blocking_wait = false;        // psx_set_wait_mode: sleep on an event instead of spinning in hipStreamSynchronize
@@ -184,7 +184,6 @@ struct psx_ctx {
     // k_pyramid_flow (POPSIFT_FLOW: 0 = one launch per level -- the default: the one-launch kernel measured 172 us against
     // 190 us of launches for a single 1080p frame but -10 % throughput with several frames in flight, DESIGN.md 3.1b --,
     // 1 = every blur level of the frame in one launch, 2 = octave 0 by launches, octaves >= 1 in one launch)
-    int  flow_mode = 0, flow_ld = 2, flow_order = 0;
     bool flow_on = false;              // a plan exists for the current size
     int  flow_first = 0, flow_nitems = 0, flow_grid = 0, flow_ncnt = 0, flow_njobs = 0;
     size_t flow_bytes = 0;             // ticket words + chunk counters, between PsxCounters and the candidate counters
@@ -200,15 +199,12 @@ struct psx_ctx {
     // 8 x 8 block (addresses, predicates, stores) is ~2x its filter arithmetic, and the halo work is 1.65x.
     // POPSIFT_TILE_MAXPX: largest plane (pixels) that takes the tile kernel; POPSIFT_TILE_TY / POPSIFT_TILE_NT: tile rows
     // (32 / 64) and threads per workgroup (512 / 1024); POPSIFT_TILE_SMALL=0: no 32 x 32 tiles for the tiny octaves
-    int  tile_mode = 0, tile_ty = 64, tile_nt = 1024;
-    long long tile_maxpx = 3ll << 20;
     bool tile_on = false;              // a tile schedule exists for the current size
     int  tile_first = 0;               // first octave on the tile kernel; the octaves in front keep one launch per level
     struct TileLaunch { int job0, njobs, grid; size_t lds; };
     std::vector<TileLaunch> tile_launches;
     PsxTileJob* d_tile_jobs = nullptr; size_t tile_jobs_cap = 0;
-    int  resident_blocks = 1024;       // 4 x compute units
-    bool batch_octaves = true;         // diagonal schedule: two octaves' levels in one launch (POPSIFT_BATCH_OCTAVES=0: one plane per launch)
+    int  resident_blocks = 1024;       // 4 x tune.cus
 };
 
 namespace {
@@ -348,9 +344,8 @@ int grow(psx_ctx* ctx, T** ptr, size_t* cap, size_t need)
 struct TileSched { std::vector<PsxTileJob> jobs; std::vector<psx_ctx::TileLaunch> launches; std::vector<int> octave, l0, slot; int first = 0; };
 // false: nothing to run on the tile kernel (no octave small enough, or a level it is not built for)
 static bool tile_schedule(const PsxParams& P, const int* inc_span, const float* inc_filter, int tile_ty, int tile_nt,
-                          long long maxpx, TileSched& out)
+                          long long maxpx, bool small_tiles, TileSched& out)
 {
-    static const bool small_tiles = [] { const char* e = getenv("POPSIFT_TILE_SMALL"); return !(e != nullptr && e[0] == '0'); }();
     const int L = P.L, D = L - 3;
     int first = 0;
     while (first < P.num_octaves && (long long)P.oct[first].w * P.oct[first].h > maxpx) first++;
@@ -422,9 +417,10 @@ static int plan_tiles(psx_ctx* ctx)
 {
     ctx->tile_on = false;
     ctx->tile_launches.clear();
-    if (ctx->tile_mode == 0 || ctx->alt_pyramid || ctx->flow_on) return PSX_OK;
+    const PsxTuning& t = ctx->tune;
+    if (t.tile == 0 || ctx->alt_pyramid || ctx->flow_on) return PSX_OK;
     TileSched sc;
-    if (!tile_schedule(ctx->hp, ctx->inc_span, ctx->inc_filter, ctx->tile_ty, ctx->tile_nt, ctx->tile_maxpx, sc)) return PSX_OK;
+    if (!tile_schedule(ctx->hp, ctx->inc_span, ctx->inc_filter, t.tile_ty, t.tile_nt, t.tile_maxpx, t.tile_small, sc)) return PSX_OK;
     int rc = grow(ctx, &ctx->d_tile_jobs, &ctx->tile_jobs_cap, sc.jobs.size());
     if (rc != PSX_OK) return rc;
     PSX_HIP(hipMemcpy(ctx->d_tile_jobs, sc.jobs.data(), sizeof(PsxTileJob) * sc.jobs.size(), hipMemcpyHostToDevice));
@@ -457,7 +453,7 @@ extern "C" int psx_tile_selfcheck(int w0, int h0, int num_octaves, int levels, c
     }
     std::vector<float> filt((size_t)PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN, 0.0f);
     TileSched sc;
-    if (!tile_schedule(P, spans, filt.data(), tile_ty, tile_nt, maxpx, sc)) return 0;
+    if (!tile_schedule(P, spans, filt.data(), tile_ty, tile_nt, maxpx, psx_tuning_from_env().tile_small, sc)) return 0;
     const int L = P.L, D = L - 3;
     std::vector<int> writer((size_t)num_octaves * L, -1), wslot((size_t)num_octaves * L, -1);
     for (size_t q = 0; q < sc.jobs.size(); q++) {
@@ -624,15 +620,16 @@ int psx_create(int device, const psx_config* cfg, psx_ctx** out)
     if (!n) return fail(nullptr, PSX_ERR_NOMEM, "out of host memory");
     n->device = device;
     n->cfg = c;
+    {
+        std::string bad;
+        n->tune = psx_tuning_from_env(&bad);
+        if (!bad.empty()) { delete n; return fail(nullptr, PSX_ERR_INVALID, bad); }
+    }
+    if (hipDeviceGetAttribute(&n->tune.cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n->tune.cus <= 0) n->tune.cus = 256;
+    n->resident_blocks = 4 * n->tune.cus;
     // opt-in: measured on MI355X / ROCm 7.2 the replayed graph is not faster than the 36 stream launches
     // (single frame 0.63 vs 0.63 ms, throughput equal): kernel-to-kernel dependencies cost the same either way
-    { const char* g = getenv("POPSIFT_HIP_GRAPH"); n->graph_off = !(g != nullptr && g[0] == '1'); }
-    { const char* g = getenv("POPSIFT_BATCH_OCTAVES"); n->batch_octaves = !(g != nullptr && g[0] == '0'); }
-    { const char* g = getenv("PSX_NULL_DEVICE_WORK"); if (g != nullptr && (g[0] == '1' || g[0] == '2')) n->null_work = g[0] - '0'; }
-    { const char* g = getenv("POPSIFT_TILE"); if (g != nullptr && (g[0] == '0' || g[0] == '1')) n->tile_mode = g[0] - '0'; }
-    { const char* g = getenv("POPSIFT_TILE_TY"); if (g != nullptr) { const int v = atoi(g); if (v >= 8 && v <= 128 && (v & 3) == 0) n->tile_ty = v; } }
-    { const char* g = getenv("POPSIFT_TILE_NT"); if (g != nullptr) { const int v = atoi(g); if (v == 512 || v == 1024) n->tile_nt = v; } }
-    { const char* g = getenv("POPSIFT_TILE_MAXPX"); if (g != nullptr) { const long long v = atoll(g); if (v >= 0) n->tile_maxpx = v; } }
+    n->graph_off = !n->tune.hip_graph;
     std::string why;
     int rc = compute_tables(&n->cfg, n->inc_filter, n->inc_span, n->inc_sigma, n->dd_filter, n->dd_span,
                             n->dd_sigma, &why);
@@ -654,11 +651,9 @@ int psx_create(int device, const psx_config* cfg, psx_ctx** out)
         // POPSIFT_CU_PARTITIONS=P (measurement switch, default off): the contexts of a process take turns over P partitions of
         // the chip, each context's stream masked to its partition.  POPSIFT_CU_PARTITION_MODE: 0 = by XCD (mask bit b belongs to
         // XCD b % 8: partition = a set of whole XCDs with their own L2s), 1 = a slice of the CUs of every XCD.
-        static const int parts = [] { const char* e = getenv("POPSIFT_CU_PARTITIONS"); const int v = e ? atoi(e) : 0; return v >= 2 && v <= 8 ? v : 0; }();
-        static const int pmode = [] { const char* e = getenv("POPSIFT_CU_PARTITION_MODE"); return e ? atoi(e) : 0; }();
+        const int parts = n->tune.cu_partitions, pmode = n->tune.cu_partition_mode, cus = n->tune.cus;
         static std::atomic<int> next_part{0};
-        int cus = 0;
-        if (parts > 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus >= 64) {
+        if (parts > 0 && cus >= 64) {
             const int part = next_part.fetch_add(1) % parts;
             uint32_t mask[16] = {0};
             const int nbits = cus < 512 ? cus : 512;
@@ -671,7 +666,6 @@ int psx_create(int device, const psx_config* cfg, psx_ctx** out)
         } else
             PSX_HIPC(hipStreamCreateWithFlags(&n->stream, hipStreamNonBlocking));
     }
-    { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) n->resident_blocks = 4 * cus; }
     PSX_HIPC(hipMalloc(reinterpret_cast<void**>(&n->d_params), sizeof(PsxParams)));
     PSX_HIPC(hipHostMalloc(reinterpret_cast<void**>(&n->h_params_pin), sizeof(PsxParams), hipHostMallocDefault));
     // frame counters and the candidate sub-list counters in ONE allocation: one fill kernel clears both per frame
@@ -680,16 +674,6 @@ int psx_create(int device, const psx_config* cfg, psx_ctx** out)
     // used prefix of it
     PSX_HIPC(hipMalloc(reinterpret_cast<void**>(&n->d_cnt), CNT_BLOCK + FLOW_MAX_BYTES + CAND_CT_BYTES));
     n->d_cand_ct = reinterpret_cast<int*>(reinterpret_cast<char*>(n->d_cnt) + CNT_BLOCK);
-    {
-        const char* g = getenv("POPSIFT_FLOW");
-        if (g != nullptr && g[0] >= '0' && g[0] <= '2' && g[1] == 0) n->flow_mode = g[0] - '0';
-        else if (g != nullptr && g[0] != 0) {          // a mislabelled A/B run is worse than no run
-            psx_destroy(n);
-            return fail(nullptr, PSX_ERR_INVALID, std::string("POPSIFT_FLOW=") + g + ": valid values are 0 (one launch per level), 1 (every level in one launch), 2 (octave 0 by launches)");
-        }
-    }
-    { const char* g = getenv("POPSIFT_FLOW_LD"); if (g != nullptr && (g[0] == '1' || g[0] == '2')) n->flow_ld = g[0] - '0'; }
-    { const char* g = getenv("POPSIFT_FLOW_ORDER"); if (g != nullptr && g[0] >= '0' && g[0] <= '2') n->flow_order = g[0] - '0'; }
     PSX_HIPC(hipHostMalloc(reinterpret_cast<void**>(&n->h_cnt), sizeof(PsxCounters), hipHostMallocDefault));
     PSX_HIPC(hipMemset(n->d_cnt, 0, CNT_BLOCK + FLOW_MAX_BYTES + CAND_CT_BYTES));
     PSX_HIPC(hipHostMalloc(reinterpret_cast<void**>(&n->h_xcnt), 4 * sizeof(int), hipHostMallocDefault));
@@ -821,10 +805,10 @@ int psx_resize(psx_ctx* ctx, int w, int h)
     // k_pyramid_flow: work list of this size (default pyramid modes only), and where the candidate counters start behind
     // its ticket words and chunk counters
     ctx->flow_on = false; ctx->flow_bytes = 0;
-    if (!ctx->alt_pyramid && ctx->flow_mode != 0) {
+    if (!ctx->alt_pyramid && ctx->tune.flow != 0) {
         PsxFlowPlan plan{};
-        const int first = ctx->flow_mode == 2 ? 1 : 0;
-        if (first < P.num_octaves && psx_flow_plan(P, ctx->inc_filter, ctx->inc_span, first, ctx->resident_blocks, ctx->flow_order, &plan)) {
+        const int first = ctx->tune.flow == 2 ? 1 : 0;
+        if (first < P.num_octaves && psx_flow_plan(ctx->tune, P, ctx->inc_filter, ctx->inc_span, first, ctx->resident_blocks, ctx->tune.flow_order, &plan)) {
             bool ok = grow(ctx, &ctx->d_flow_jobs, &ctx->flow_jobs_cap, (size_t)plan.njobs) == PSX_OK &&
                       grow(ctx, &ctx->d_flow_items, &ctx->flow_items_cap, (size_t)plan.nitems) == PSX_OK;
             ok = ok && hipMemcpy(ctx->d_flow_jobs, plan.jobs, sizeof(PsxFlowJob) * (size_t)plan.njobs, hipMemcpyHostToDevice) == hipSuccess &&
@@ -917,7 +901,7 @@ static int upload_common(psx_ctx* ctx, const void* host, int w, int h, int is_fl
     }
     // DMA engine, not a kernel: a copy kernel that reads the mapped host image over PCIe itself was measured
     // (GPU-initiated reads are slow: +0.8 ms per frame in flight, -8 % end-to-end throughput)
-    if (!(ctx->null_work == 2 && ctx->null_primed))        // PSX_NULL_DEVICE_WORK=2: host software only, no DMA
+    if (!(ctx->tune.null_device_work == 2 && ctx->null_primed))        // PSX_NULL_DEVICE_WORK=2: host software only, no DMA
         PSX_HIP(hipMemcpyAsync(ctx->d_input_own, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     if (src == ctx->h_stage) PSX_HIP(hipEventRecord(ctx->ev_upload, ctx->stream));
     ctx->d_input = ctx->d_input_own;
@@ -963,7 +947,7 @@ static PsxBlurJob blur_job(const psx_ctx* ctx, int o, int level)
 static int launch_blur_level(psx_ctx* ctx, int o, int level, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr)
 {
     const PsxBlurJob j = blur_job(ctx, o, level);
-    PSX_HIP(psx_launch_blur(j.src, j.dst, j.W, j.H, j.pitch, j.taps, j.span, j.half_dst, j.half_pitch, ctx->stream, ev0, ev1));
+    PSX_HIP(psx_launch_blur(ctx->tune, j.src, j.dst, j.W, j.H, j.pitch, j.taps, j.span, j.half_dst, j.half_pitch, ctx->stream, ev0, ev1));
     return PSX_OK;
 }
 
@@ -974,6 +958,19 @@ static int launch_extrema_set(psx_ctx* ctx, const int* octaves, int n)
         const int m = n - i < PSX_EXT_BATCH ? n - i : PSX_EXT_BATCH;
         PSX_HIP(psx_launch_extrema_batch(ctx->d_params, ctx->hp, ctx->d_cnt, octaves + i, m, ctx->stream));
     }
+    return PSX_OK;
+}
+
+// The extrema scan of octave o.  A large octave's scan goes out at once (right behind its last level its planes are as
+// cache-resident as they will ever be), bracketed by the probe events when it is octave 0; an octave whose tiles do not fill
+// the chip (a few hundred tiles, a latency-bound launch) is put on `deferred` and shares one launch with the others.
+static int scan_or_defer(psx_ctx* ctx, int o, int* deferred, int* ndef)
+{
+    if (psx_extrema_tiles(ctx->hp, o) < ctx->resident_blocks) { deferred[(*ndef)++] = o; return PSX_OK; }
+    const bool px = ctx->blur_probe && o == 0;
+    if (px) PSX_HIP(hipEventRecord(ctx->ev_x[2], ctx->stream));
+    PSX_HIP(psx_launch_extrema(ctx->d_params, ctx->hp, ctx->d_cnt, o, ctx->stream));
+    if (px) { PSX_HIP(hipEventRecord(ctx->ev_x[3], ctx->stream)); ctx->probe_ext0 = true; }
     return PSX_OK;
 }
 
@@ -991,7 +988,7 @@ int psx_build_pyramid(psx_ctx* ctx)
 
     if (ctx->alt_pyramid) {
         PsxAltArgs q;
-        q.hp = &ctx->hp;
+        q.tune = &ctx->tune; q.hp = &ctx->hp;
         q.img = ctx->d_input; q.w = ctx->in_w; q.h = ctx->in_h; q.is_float = ctx->input_is_float;
         q.gauss_mode = c.gauss_mode; q.scaling_mode = c.scaling_mode; q.sift_mode = c.sift_mode;
         q.upscale_factor = c.upscale_factor;
@@ -1031,7 +1028,7 @@ int psx_build_pyramid(psx_ctx* ctx)
     a.taps_h = taps_from(ctx->dd_filter); a.span_h = ctx->dd_span[0];
     a.taps_v = taps_from(ctx->inc_filter); a.span_v = ctx->inc_span[0];
     if (ctx->blur_probe) PSX_HIP(hipEventRecord(ctx->ev_x[0], ctx->stream));
-    PSX_HIP(psx_launch_level0(a, ctx->stream));
+    PSX_HIP(psx_launch_level0(ctx->tune, a, ctx->stream));
     if (ctx->blur_probe) PSX_HIP(hipEventRecord(ctx->ev_x[1], ctx->stream));
 
     ctx->ext_launched = false;
@@ -1047,8 +1044,8 @@ int psx_build_pyramid(psx_ctx* ctx)
         }
         const bool pf = probe && ctx->flow_first == 0;
         int* state = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->d_cnt) + CNT_BLOCK);
-        PSX_HIP(psx_launch_flow(ctx->d_flow_jobs, ctx->d_flow_items, ctx->flow_nitems, state, &ctx->d_cnt->flow_error,
-                                ctx->flow_grid, ctx->flow_ld, ctx->stream, pf ? ctx->ev_blur[0] : nullptr, pf ? ctx->ev_blur[1] : nullptr,
+        PSX_HIP(psx_launch_flow(ctx->tune, ctx->d_flow_jobs, ctx->d_flow_items, ctx->flow_nitems, state, &ctx->d_cnt->flow_error,
+                                ctx->flow_grid, ctx->tune.flow_ld, ctx->stream, pf ? ctx->ev_blur[0] : nullptr, pf ? ctx->ev_blur[1] : nullptr,
                                 ctx->d_flow_trace));
         if (probe) {
             if (pf) { ctx->blur_probe_n = 1; ctx->blur_probe_bytes = ctx->flow_algo_bytes; }
@@ -1062,17 +1059,7 @@ int psx_build_pyramid(psx_ctx* ctx)
         // then the tile launches (several levels of up to two octaves each); then the scans of the small octaves
         double probe_bytes = 0.0;
         int deferred[PSX_MAX_OCTAVES], ndef = 0;
-        auto scan_after = [&](int o) -> int {
-            if (!ctx->interleave) return PSX_OK;
-            if (psx_extrema_tiles(P, o) >= ctx->resident_blocks) {
-                const bool px = probe && o == 0;
-                if (px) PSX_HIP(hipEventRecord(ctx->ev_x[2], ctx->stream));
-                PSX_HIP(psx_launch_extrema(ctx->d_params, ctx->hp, ctx->d_cnt, o, ctx->stream));
-                if (px) { PSX_HIP(hipEventRecord(ctx->ev_x[3], ctx->stream)); ctx->probe_ext0 = true; }
-            } else
-                deferred[ndef++] = o;
-            return PSX_OK;
-        };
+        auto scan_after = [&](int o) -> int { return ctx->interleave ? scan_or_defer(ctx, o, deferred, &ndef) : PSX_OK; };
         for (int o = 0; o < ctx->tile_first; o++) {
             for (int level = 1; level < P.L; level++) {
                 const bool pl = probe && o == 0;
@@ -1085,7 +1072,7 @@ int psx_build_pyramid(psx_ctx* ctx)
             if (rc != PSX_OK) return rc;
         }
         for (const psx_ctx::TileLaunch& ln : ctx->tile_launches)
-            PSX_HIP(psx_launch_blur_tile(ctx->d_tile_jobs + ln.job0, ln.njobs, ln.grid, ln.lds, ctx->tile_nt, ctx->stream));
+            PSX_HIP(psx_launch_blur_tile(ctx->d_tile_jobs + ln.job0, ln.njobs, ln.grid, ln.lds, ctx->tune.tile_nt, ctx->stream));
         for (int o = ctx->tile_first; o < P.num_octaves; o++) { const int rc = scan_after(o); if (rc != PSX_OK) return rc; }
         if (ndef > 0) { const int rc = launch_extrema_set(ctx, deferred, ndef); if (rc != PSX_OK) return rc; }
         if (probe) { ctx->blur_probe_n = P.L - 1; ctx->blur_probe_bytes = probe_bytes / (P.L - 1); }
@@ -1105,8 +1092,8 @@ int psx_build_pyramid(psx_ctx* ctx)
     t0[0] = 0;
     for (int o = 0; o + 1 < P.num_octaves; o++) {
         const int span = ctx->inc_span[P.L - 1];
-        const bool fits = ctx->batch_octaves &&
-            psx_blur_pair_ok(P.oct[o].w, P.oct[o].h, P.oct[o + 1].w, P.oct[o + 1].h, span, ctx->resident_blocks);
+        const bool fits = ctx->tune.batch_octaves &&
+            psx_blur_pair_ok(ctx->tune, P.oct[o].w, P.oct[o].h, P.oct[o + 1].w, P.oct[o + 1].h, span, ctx->resident_blocks);
         t0[o + 1] = t0[o] + (fits ? D : P.L - 1);
     }
     const int T = t0[P.num_octaves - 1] + P.L - 1;
@@ -1124,15 +1111,15 @@ int psx_build_pyramid(psx_ctx* ctx)
             hipEvent_t e0 = pl ? ctx->ev_blur[2 * (level - 1)] : nullptr, e1 = pl ? ctx->ev_blur[2 * (level - 1) + 1] : nullptr;
             // only when both fit into one round of resident workgroups (4 per CU): behind a launch that fills the
             // chip the second plane would just queue, and it would run on the larger radius' kernel for nothing
-            bool pair = q + 1 < nj && ctx->batch_octaves;
+            bool pair = q + 1 < nj && ctx->tune.batch_octaves;
             if (pair) {
                 const int o2 = jo[q + 1], level2 = t - t0[o2];
                 const int span = ctx->inc_span[level] > ctx->inc_span[level2] ? ctx->inc_span[level] : ctx->inc_span[level2];
-                pair = psx_blur_pair_ok(P.oct[o].w, P.oct[o].h, P.oct[o2].w, P.oct[o2].h, span, ctx->resident_blocks);
+                pair = psx_blur_pair_ok(ctx->tune, P.oct[o].w, P.oct[o].h, P.oct[o2].w, P.oct[o2].h, span, ctx->resident_blocks);
             }
             if (pair) {
                 const int o2 = jo[q + 1], level2 = t - t0[o2];
-                PSX_HIP(psx_launch_blur2(blur_job(ctx, o, level), blur_job(ctx, o2, level2), ctx->stream, e0, e1));
+                PSX_HIP(psx_launch_blur2(ctx->tune, blur_job(ctx, o, level), blur_job(ctx, o2, level2), ctx->stream, e0, e1));
                 if (pl) probe_bytes += 8.0 * ((double)P.oct[o].w * P.oct[o].h + (double)P.oct[o2].w * P.oct[o2].h);
             } else {
                 int rc = launch_blur_level(ctx, o, level, e0, e1);
@@ -1148,13 +1135,8 @@ int psx_build_pyramid(psx_ctx* ctx)
         // be.  The small octaves' scans (a few hundred tiles each, latency-bound launches) wait and share one launch.
         for (int q = 0; q < nj; q++)
             if (t - t0[jo[q]] == P.L - 1 && ctx->interleave) {
-                if (psx_extrema_tiles(P, jo[q]) >= ctx->resident_blocks) {
-                    const bool px = probe && jo[q] == 0;
-                    if (px) PSX_HIP(hipEventRecord(ctx->ev_x[2], ctx->stream));
-                    PSX_HIP(psx_launch_extrema(ctx->d_params, ctx->hp, ctx->d_cnt, jo[q], ctx->stream));
-                    if (px) { PSX_HIP(hipEventRecord(ctx->ev_x[3], ctx->stream)); ctx->probe_ext0 = true; }
-                } else
-                    deferred[ndef++] = jo[q];
+                const int rc = scan_or_defer(ctx, jo[q], deferred, &ndef);
+                if (rc != PSX_OK) return rc;
             }
     }
     if (ndef > 0) { int rc = launch_extrema_set(ctx, deferred, ndef); if (rc != PSX_OK) return rc; }
@@ -1172,7 +1154,7 @@ static int wait_stream(psx_ctx* ctx)
         // 86 % busy -- 7 cores per GPU, 54 on an 8-GPU host); asking the event and sleeping in between costs a few
         // microseconds of CPU per frame and, with several frames in flight per worker pool, no throughput.
         // POPSIFT_WAIT_SLEEP_US (default 40; 0 = the runtime's blocking wait).
-        static const int sleep_us = [] { const char* e = getenv("POPSIFT_WAIT_SLEEP_US"); const int v = e ? atoi(e) : 40; return v < 0 ? 0 : v; }();
+        const int sleep_us = ctx->tune.wait_sleep_us;
         if (!ctx->ev_wait) PSX_HIP(hipEventCreateWithFlags(&ctx->ev_wait, hipEventBlockingSync | hipEventDisableTiming));
         PSX_HIP(hipEventRecord(ctx->ev_wait, ctx->stream));
         if (sleep_us == 0) { PSX_HIP(hipEventSynchronize(ctx->ev_wait)); return PSX_OK; }
@@ -1224,13 +1206,8 @@ int psx_find_extrema(psx_ctx* ctx)
     if (!ctx->ext_launched) {
         int small[PSX_MAX_OCTAVES], ns = 0;
         for (int o = 0; o < ctx->hp.num_octaves; o++) {
-            if (psx_extrema_tiles(ctx->hp, o) >= ctx->resident_blocks) {
-                const bool px = ctx->blur_probe && o == 0;
-                if (px) PSX_HIP(hipEventRecord(ctx->ev_x[2], ctx->stream));
-                PSX_HIP(psx_launch_extrema(ctx->d_params, ctx->hp, ctx->d_cnt, o, ctx->stream));
-                if (px) { PSX_HIP(hipEventRecord(ctx->ev_x[3], ctx->stream)); ctx->probe_ext0 = true; }
-            } else
-                small[ns++] = o;
+            const int rc = scan_or_defer(ctx, o, small, &ns);
+            if (rc != PSX_OK) return rc;
         }
         if (ns > 0) { int rc = launch_extrema_set(ctx, small, ns); if (rc != PSX_OK) return rc; }
     }
@@ -1250,7 +1227,7 @@ int psx_orientation(psx_ctx* ctx)
         int rc = grid_filter(ctx);
         if (rc != PSX_OK) return rc;
     }
-    PSX_HIP(psx_launch_orientation(ctx->d_params, ctx->d_cnt, ctx->stream));
+    PSX_HIP(psx_launch_orientation(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->stream));
     snapshot_export(ctx);
     PSX_HIP(psx_launch_scan(ctx->d_params, ctx->d_cnt, ctx->fx, ctx->stream));
     if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
@@ -1263,9 +1240,9 @@ int psx_descriptors(psx_ctx* ctx)
     if (!ctx->d_pyr) return fail(ctx, PSX_ERR_STATE, "psx_descriptors: no pyramid");
     PSX_HIP(hipSetDevice(ctx->device));
     if (ctx->cfg.desc_mode == PSX_DESC_LOOP)
-        PSX_HIP(psx_launch_descriptors(ctx->d_params, ctx->d_cnt, ctx->fx, ctx->resident_blocks / 4, ctx->stream));
+        PSX_HIP(psx_launch_descriptors(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->fx, ctx->stream));
     else
-        PSX_HIP(psx_launch_descriptors_alt(ctx->d_params, ctx->d_cnt, ctx->cfg.desc_mode, ctx->fx, ctx->resident_blocks / 4, ctx->stream));
+        PSX_HIP(psx_launch_descriptors_alt(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->cfg.desc_mode, ctx->fx, ctx->stream));
     if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
     return PSX_OK;
 }
@@ -1291,9 +1268,9 @@ int psx_extract(psx_ctx* ctx)
 {
     if (!ctx) return PSX_ERR_INVALID;
     if (!ctx->d_input || !ctx->d_pyr) return fail(ctx, PSX_ERR_STATE, "psx_extract: no input image");
-    if (ctx->null_work != 0) {
+    if (ctx->tune.null_device_work != 0) {
         if (ctx->null_primed) {                    // measurement: no kernels; the first frame's results stand in
-            if (ctx->null_work == 1) ctx->counts_valid = false;      // mode 1 reads the counters back per frame, like a real frame
+            if (ctx->tune.null_device_work == 1) ctx->counts_valid = false;      // mode 1 reads the counters back per frame, like a real frame
             snapshot_export(ctx);
             return PSX_OK;
         }
@@ -1382,9 +1359,9 @@ static int regrow_descriptors(psx_ctx* ctx, int ori_raw)
     // same targets as the launch being repeated
     PSX_HIP(psx_launch_scan(ctx->d_params, ctx->d_cnt, ctx->fx, ctx->stream));
     if (ctx->cfg.desc_mode == PSX_DESC_LOOP)
-        PSX_HIP(psx_launch_descriptors(ctx->d_params, ctx->d_cnt, ctx->fx, ctx->resident_blocks / 4, ctx->stream));
+        PSX_HIP(psx_launch_descriptors(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->fx, ctx->stream));
     else
-        PSX_HIP(psx_launch_descriptors_alt(ctx->d_params, ctx->d_cnt, ctx->cfg.desc_mode, ctx->fx, ctx->resident_blocks / 4, ctx->stream));
+        PSX_HIP(psx_launch_descriptors_alt(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->cfg.desc_mode, ctx->fx, ctx->stream));
     return PSX_OK;
 }
 
@@ -1444,8 +1421,8 @@ int psx_download(psx_ctx* ctx, psx_feature* features, int feature_capacity, floa
     const bool desc_exported = (ctx->fx_on && descriptors == ctx->fx_host_desc && no <= ctx->fx.desc_capacity);
     // PSX_NULL_DEVICE_WORK=2: one real download per CONTEXT keeps its host records well formed (a process-wide flag was a
     // data race between the workers and left every context but the first with uninitialised host buffers)
-    if (ctx->null_work == 2 && ctx->null_primed && ctx->null_dl_done) return PSX_OK;
-    if (ctx->null_work == 2 && ctx->null_primed) ctx->null_dl_done = true;
+    if (ctx->tune.null_device_work == 2 && ctx->null_primed && ctx->null_dl_done) return PSX_OK;
+    if (ctx->tune.null_device_work == 2 && ctx->null_primed) ctx->null_dl_done = true;
     if (ne > 0 && !feat_exported)
         PSX_HIP(hipMemcpyAsync(features, ctx->d_features, (size_t)ne * sizeof(psx_feature),
                                hipMemcpyDeviceToHost, ctx->stream));

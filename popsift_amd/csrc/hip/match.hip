@@ -545,6 +545,8 @@ struct MatchScratch {
     void* hpin = nullptr;                // pinned staging of the results: a DMA into pageable caller memory goes through the
     size_t hpin_cap = 0;                 // runtime's own bounce buffers, ~0.5 ms per call on this stack
     bool tidy = false;                   // the prefilter's counters are zero (left so by the previous call's last kernel)
+    PsxTuning tune;                      // the POPSIFT_MATCH_* switches and the CU count of `device`: taken in bind()
+    int mfma_per_cu = 0;                 // workgroups of the prefilter kernel resident per CU on `device` (0: not asked yet)
     void release()
     {
         if (device < 0) return;
@@ -566,6 +568,9 @@ struct MatchScratch {
         release();
         if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return false;
         device = dev;
+        tune = psx_tuning_from_env();
+        if (hipDeviceGetAttribute(&tune.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || tune.cus <= 0) tune.cus = 256;
+        mfma_per_cu = 0;
         return true;
     }
     bool need_pinned(size_t bytes)
@@ -631,7 +636,7 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
     hipStream_t st = sc.stream;
     // POPSIFT_MATCH_MFMA=0: the exact scan of every pair (rounds 1-4); default: MFMA prefilter + exact evaluation of the
     // candidates (identical results by construction; used from 2 * MF_SEED = 4096 right / 256 left descriptors on)
-    static const bool use_mfma = [] { const char* e = getenv("POPSIFT_MATCH_MFMA"); return !(e != nullptr && e[0] == '0'); }();
+    const bool use_mfma = sc.tune.match_mfma;
     bool exact_scan = true;
     int* d_flag_used = nullptr;
     int* d_cct_used = nullptr;
@@ -653,15 +658,13 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
         int* d_cct = static_cast<int*>(sc.buf[8]);
         int* d_cand = static_cast<int*>(sc.buf[9]);
         // workgroups the prefilter kernel keeps resident (the occupancy the runtime computes from its registers and LDS: 3 per CU)
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-        static const int per_cu = [] {
+        const int cus = sc.tune.cus;
+        if (sc.mfma_per_cu == 0) {
             int n = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_match_mfma<false>, 256, 0) != hipSuccess || n < 1) n = 2;
-            if (const char* e = getenv("POPSIFT_MATCH_WGS_PER_CU")) { const int v = atoi(e); if (v >= 1 && v <= 8) n = v; }
-            return n;
-        }();
-        const int resident = per_cu * cus;
+            sc.mfma_per_cu = sc.tune.match_wgs_per_cu > 0 ? sc.tune.match_wgs_per_cu : n;     // POPSIFT_MATCH_WGS_PER_CU
+        }
+        const int resident = sc.mfma_per_cu * cus;
         const int lblocks = (l_len + 255) / 256;
         // seeding pass: the first ~MF_SEED right descriptors in at most MF_SEEDCH chunks, ONE round of resident workgroups
         // (8 chunks x 72 left blocks were 576 workgroups on 512 slots: a second, nearly empty round); the slots of the
@@ -670,7 +673,7 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
         if (nseed > MF_SEEDCH) nseed = MF_SEEDCH;
         if (nseed < 1) nseed = 1;
         const int seedlen = (((MF_SEED + nseed - 1) / nseed + MF_TILE - 1) / MF_TILE) * MF_TILE;
-        static const bool stats = getenv("POPSIFT_MATCH_STATS") != nullptr;       // measurement: candidates per left descriptor
+        const bool stats = sc.tune.match_stats;               // measurement: candidates per left descriptor
         // the candidate counts and the maximum slots: zeroed here after an allocation or a call that did not finish the usual
         // way, otherwise left at zero by the previous call's k_match_exact
         if (!sc.tidy && (hipMemsetAsync(d_cct, 0, sc.cap[8], st) != hipSuccess ||
@@ -689,8 +692,7 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
         // every chunk of the right side: FULL rounds of resident workgroups (15 chunks x 72 left blocks = 1080 workgroups on 768 slots
         // ran 1.4 rounds, i.e. the time of two), whole tiles per chunk
         // POPSIFT_MATCH_ROUNDS: rounds of resident workgroups the chunking aims at (measurement switch)
-        static const int rounds = [] { const char* e = getenv("POPSIFT_MATCH_ROUNDS"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 4 ? v : 1; }();
-        int mchunks = (rounds * resident) / lblocks;
+        int mchunks = (sc.tune.match_rounds * resident) / lblocks;
         if (mchunks > (r_len + 8 * MF_TILE - 1) / (8 * MF_TILE)) mchunks = (r_len + 8 * MF_TILE - 1) / (8 * MF_TILE);
         if (mchunks > MF_SEGS / 2) mchunks = MF_SEGS / 2;          // one candidate segment per (chunk, half wave)
         if (mchunks < 1) mchunks = 1;
@@ -719,7 +721,7 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
     if (!exact_scan) {
         if (!fetch()) return PSX_ERR_HIP;
         const int h_flag = *h_flagp;
-        static const bool stats = getenv("POPSIFT_MATCH_STATS") != nullptr;
+        const bool stats = sc.tune.match_stats;
         if (stats) {
             std::vector<int> h((size_t)l_len * MF_SEGS);
             if (hipMemcpy(h.data(), d_cct_used, sizeof(int) * h.size(), hipMemcpyDeviceToHost) == hipSuccess) {

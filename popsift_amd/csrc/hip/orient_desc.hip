@@ -1261,12 +1261,11 @@ __global__ __launch_bounds__(NT) void k_descriptors_alt(const PsxParams* __restr
 
 } // namespace
 
-hipError_t psx_launch_orientation(const PsxParams* d_params, PsxCounters* d_cnt, hipStream_t s)
+hipError_t psx_launch_orientation(const PsxTuning& t, const PsxParams* d_params, PsxCounters* d_cnt, hipStream_t s)
 {
     // POPSIFT_ORI_WPB=1 / 4: waves per workgroup (as k_descriptors: a keypoint's window grows with sigma^2); measured: no difference
     // (profiles/r06_desc_waves_per_workgroup.txt), four stays
-    static const int wb = [] { const char* e = getenv("POPSIFT_ORI_WPB"); const int v = e ? atoi(e) : 0; return v == 1 || v == 4 ? v : 4; }();
-    if (wb == 1) hipLaunchKernelGGL(k_orientation<1>, dim3(2048 * 4), dim3(PSX_WAVE), 0, s, d_params, d_cnt);
+    if (t.ori_wpb == 1) hipLaunchKernelGGL(k_orientation<1>, dim3(2048 * 4), dim3(PSX_WAVE), 0, s, d_params, d_cnt);
     else         hipLaunchKernelGGL(k_orientation<4>, dim3(2048), dim3(NT), 0, s, d_params, d_cnt);
     return hipGetLastError();
 }
@@ -1277,13 +1276,12 @@ hipError_t psx_launch_scan(const PsxParams* d_params, PsxCounters* d_cnt, const 
     return hipGetLastError();
 }
 
-hipError_t psx_launch_descriptors_alt(const PsxParams* d_params, const PsxCounters* d_cnt, int desc_mode, const PsxExport& x, int cus, hipStream_t s)
+hipError_t psx_launch_descriptors_alt(const PsxTuning& t, const PsxParams* d_params, const PsxCounters* d_cnt, int desc_mode, const PsxExport& x, hipStream_t s)
 {
-    // 4 workgroups (38 KB of LDS each) are resident per CU; the workgroups loop over the descriptors
-    static const int per_cu = [] { const char* e = getenv("POPSIFT_ALT_WGS"); const int v = e ? atoi(e) : 0; return v > 0 && v <= 64 ? v : 8; }();
+    // 4 workgroups (38 KB of LDS each) are resident per CU; the workgroups loop over the descriptors (POPSIFT_ALT_WGS per CU)
     // POPSIFT_ALT_WINDOW=0: measurement / test switch, every texel from the plane in HBM (what large-sigma keypoints do anyway)
-    static const int win = [] { const char* e = getenv("POPSIFT_ALT_WINDOW"); return (e != nullptr && e[0] == '0') ? 0 : 1; }();
-    const dim3 grid((cus > 0 ? cus : 256) * per_cu), block(NT);
+    const int win = t.alt_window ? 1 : 0;
+    const dim3 grid(t.cus * t.alt_wgs), block(NT);
     switch (desc_mode) {
     case PSX_DESC_ILOOP:  hipLaunchKernelGGL(k_descriptors_alt<PSX_DESC_ILOOP>, grid, block, 0, s, d_params, d_cnt, x, win); break;
     case PSX_DESC_GRID:   hipLaunchKernelGGL(k_descriptors_alt<PSX_DESC_GRID>, grid, block, 0, s, d_params, d_cnt, x, win); break;
@@ -1294,7 +1292,7 @@ hipError_t psx_launch_descriptors_alt(const PsxParams* d_params, const PsxCounte
     return hipGetLastError();
 }
 
-hipError_t psx_launch_descriptors(const PsxParams* d_params, const PsxCounters* d_cnt, const PsxExport& x, int cus, hipStream_t s)
+hipError_t psx_launch_descriptors(const PsxTuning& t, const PsxParams* d_params, const PsxCounters* d_cnt, const PsxExport& x, hipStream_t s)
 {
     const bool exporting = x.desc != nullptr;
     // 6 workgroups (24 waves, 26 KB of LDS each; 5 of 32 KB until round 6) are resident per CU; two full rounds measured best for
@@ -1302,21 +1300,21 @@ hipError_t psx_launch_descriptors(const PsxParams* d_params, const PsxCounters* 
     // at 20).  With the zero-copy export attached every wave ends in stores that cross PCIe; fewer resident waves
     // leave room for the other streams' kernels meanwhile (3 per CU measured +11 % on the export leg of bench.py; with six resident
     // workgroups per CU, round 6: 2 per CU 5534 Mpix/s, 3: 5204, 4 and more: 5050).
-    // cus = compute units of the CONTEXT's device (one PopSift per GPU may sit on unequal devices).
-    if (cus <= 0) cus = 256;
+    // t.cus = compute units of the CONTEXT's device (one PopSift per GPU may sit on unequal devices).
+    const int cus = t.cus;
     // POPSIFT_DESC_OCC=5: the instantiation padded to round 5's LDS footprint (five workgroups per CU), the A/B partner of the
     // overlapped histogram copies (six per CU: descriptor stage 0.111-0.114 -> 0.107-0.108 ms with two full rounds = 12 per CU)
-    static const bool occ5 = [] { const char* e = getenv("POPSIFT_DESC_OCC"); return e != nullptr && e[0] == '5'; }();
+    const bool occ5 = t.desc_occ == 5;
     // POPSIFT_DESC_WGS=<workgroups per CU>: measurement switch for the grid (the waves loop over the descriptors)
-    static const int per_cu = [] { const char* e = getenv("POPSIFT_DESC_WGS"); const int v = e ? atoi(e) : 0; return v > 0 && v <= 64 ? v : 0; }();
+    const int per_cu = t.desc_wgs;
     const int grid = per_cu ? per_cu * cus : exporting ? (occ5 ? 3 : 2) * cus : (occ5 ? 10 : 12) * cus;
     // POPSIFT_DESC_DENORM=0: round 2's conversion path (v_cvt_u32_f32 of every contribution) instead of the denormal products
-    static const bool denorm = [] { const char* e = getenv("POPSIFT_DESC_DENORM"); return !(e != nullptr && e[0] == '0'); }();
+    const bool denorm = t.desc_denorm;
     // POPSIFT_DESC_WPB=1 / 2 / 4: waves per workgroup (the grid keeps its number of waves).  Default: ONE wave per workgroup (a wave's
     // LDS and slot are free the moment IT is done, not when the slowest of four is: end to end 6806-6847 -> 6872-6879 Mpix/s, device
     // resident 7005-7011 -> 7047-7058 in three A/B pairs, profiles/r06_desc_waves_per_workgroup.txt); four with the zero-copy export
     // attached (5451 against 5386 Mpix/s on that leg)
-    static const int wb = [] { const char* e = getenv("POPSIFT_DESC_WPB"); const int v = e ? atoi(e) : 0; return v == 1 || v == 2 || v == 4 ? v : 0; }();
+    const int wb = t.desc_wpb;
     if (!denorm)      hipLaunchKernelGGL((k_descriptors<false, 5, 4>), dim3(grid), dim3(NT), 0, s, d_params, d_cnt, x);
     else if (occ5)    hipLaunchKernelGGL((k_descriptors<true, 5, 4>), dim3(grid), dim3(NT), 0, s, d_params, d_cnt, x);
     else if (wb == 1 || (wb == 0 && !exporting)) hipLaunchKernelGGL((k_descriptors<true, 6, 1>), dim3(grid * 4), dim3(PSX_WAVE), 0, s, d_params, d_cnt, x);

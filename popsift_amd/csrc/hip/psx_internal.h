@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "popsift_hip.h"
+#include "psx_tuning.h"
 
 #define PSX_WAVE 64
 #define PSX_CAND_SUB 64
@@ -99,6 +100,8 @@ struct PsxCounters {
 struct PsxTaps { float g[PSX_GAUSS_ALIGN]; };
 
 // ---- host-side launch helpers implemented in the .hip files ---------------------------------
+// t: the context's snapshot of the environment switches and its device's CU count (psx_tuning.h); nothing below api.hip
+// asks the environment or the current device
 // columns of the resampled input kept on each side of the plane (>= the largest filter halo, 32)
 #define PSX_LEVEL0_PAD 32
 struct PsxLevel0Args {
@@ -112,14 +115,14 @@ struct PsxLevel0Args {
     // absoluteSourceInterpolated::vert instead of absoluteSource::vert; nullptr otherwise
     const float* v_ifilter = nullptr; int v_ispan = 0;
 };
-bool psx_level0_interp_ok(const PsxLevel0Args& a);
+bool psx_level0_interp_ok(const PsxTuning& t, const PsxLevel0Args& a);
 
-hipError_t psx_launch_level0(const PsxLevel0Args& a, hipStream_t s);
+hipError_t psx_launch_level0(const PsxTuning& t, const PsxLevel0Args& a, hipStream_t s);
 // per-tap texture coordinates exactly as the reference forms them (pyramid_alt.hip): what psx_launch_level0 runs when
 // the image / octave ratio is not a power of two (psx_level0_exact)
 hipError_t psx_launch_level0_literal(const PsxLevel0Args& a, hipStream_t s);
 bool psx_level0_exact(int w, int h, int W, int H);
-hipError_t psx_launch_blur(const float* src, float* dst, int W, int H, int pitch,
+hipError_t psx_launch_blur(const PsxTuning& t, const float* src, float* dst, int W, int H, int pitch,
                            const PsxTaps& taps, int span,
                            float* half_dst, int half_pitch, hipStream_t s,
                            hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
@@ -129,9 +132,9 @@ struct PsxBlurJob {
     int W, H, pitch, half_pitch;
     PsxTaps taps; int span;
 };
-int psx_blur_grid(int W, int H, int span);
-bool psx_blur_pair_ok(int W1, int H1, int W2, int H2, int span, int resident_marching);
-hipError_t psx_launch_blur2(const PsxBlurJob& a, const PsxBlurJob& b, hipStream_t s,
+int psx_blur_grid(const PsxTuning& t, int W, int H, int span);
+bool psx_blur_pair_ok(const PsxTuning& t, int W1, int H1, int W2, int H2, int span, int resident_marching);
+hipError_t psx_launch_blur2(const PsxTuning& t, const PsxBlurJob& a, const PsxBlurJob& b, hipStream_t s,
                             hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // ---- k_pyramid_flow: every plane-to-plane blur of a frame in ONE launch (pyramid.hip) ----------------------------------
 // Work items = (job = (octave, level), 64-column strip, chunk of rows); a persistent grid takes tickets in a host-computed
@@ -161,16 +164,17 @@ struct PsxFlowPlan {
 };
 // jobs: the blur levels 1..L-1 of the octaves first_octave..; false when the configuration is outside what the kernel is
 // instantiated for (a radius above 13, too many chunk counters): the caller keeps the launch-per-level schedule
-bool psx_flow_plan(const PsxParams& P, const float* inc_filter, const int* inc_span, int first_octave,
+bool psx_flow_plan(const PsxTuning& t, const PsxParams& P, const float* inc_filter, const int* inc_span, int first_octave,
                    int resident_blocks, int order, PsxFlowPlan* out);
 // state: PSX_FLOW_HEAD_INTS ticket words + ncounters * PSX_FLOW_CNT_STRIDE ints of chunk counters, zeroed before the launch; err: set to 1 by a workgroup
 // whose dependency wait ran into its bound (never in a correct run)
-hipError_t psx_launch_flow(const PsxFlowJob* d_jobs, const PsxFlowItem* d_items, int nitems, int* d_state, int* d_err,
+hipError_t psx_launch_flow(const PsxTuning& t, const PsxFlowJob* d_jobs, const PsxFlowItem* d_items, int nitems, int* d_state, int* d_err,
                            int grid, int ldmode, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
                            long long* trace = nullptr);
 
 // every non-default branch of Pyramid::build_pyramid (pyramid_alt.hip)
 struct PsxAltArgs {
+    const PsxTuning* tune;
     const PsxParams* hp;
     const void* img; int w, h, is_float;
     int gauss_mode, scaling_mode, sift_mode;
@@ -206,19 +210,18 @@ struct PsxFixedOctaveArgs {
 };
 // GaussMode VLFeat_Relative: one fused H + V launch per level (pyramid_interp.hip); fi / ispan: the level's row of the
 // interpolated table; psx_blur_interp_ok: the pair count the kernel is instantiated for
-bool psx_blur_interp_ok(int ispan);
+bool psx_blur_interp_ok(const PsxTuning& t, int ispan);
 struct PsxInterpJob {
     const float* src; float* dst; float* half_dst;     // half_dst: level 0 of the next octave (level L - 3 only), or nullptr
     int W, H, pitch, half_pitch;
     const float* fi; int ispan;                         // the level's row of the interpolated table (host), its odd span
 };
-hipError_t psx_launch_blur_interp(const PsxInterpJob& j, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
-hipError_t psx_launch_blur_interp2(const PsxInterpJob& a, const PsxInterpJob& b, hipStream_t s);
-int psx_blur_interp_grid(int W, int H, int ispan);
-bool psx_blur_interp_pair_ok(int W1, int H1, int ispan1, int W2, int H2, int ispan2);
-bool psx_fixed_octave0_ok(int w, int h, int W, int H);
-bool psx_fixed_octave_enabled();
-hipError_t psx_launch_fixed_octave(const PsxFixedOctaveArgs& a, hipStream_t s);
+hipError_t psx_launch_blur_interp(const PsxTuning& t, const PsxInterpJob& j, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+hipError_t psx_launch_blur_interp2(const PsxTuning& t, const PsxInterpJob& a, const PsxInterpJob& b, hipStream_t s);
+int psx_blur_interp_grid(const PsxTuning& t, int W, int H, int ispan);
+bool psx_blur_interp_pair_ok(const PsxTuning& t, int W1, int H1, int ispan1, int W2, int H2, int ispan2);
+bool psx_fixed_octave0_ok(const PsxTuning& t, int w, int h, int W, int H);
+hipError_t psx_launch_fixed_octave(const PsxTuning& t, const PsxFixedOctaveArgs& a, hipStream_t s);
 hipError_t psx_launch_dog(const float* a, const float* b, float* d, int W, int H, int pitch, hipStream_t s);
 // k_extrema scans the tiles of up to PSX_EXT_BATCH octaves in one launch
 #define PSX_EXT_BATCH 4
@@ -236,12 +239,12 @@ hipError_t psx_launch_gridfilter(const PsxParams* d_params, PsxCounters* d_cnt, 
                                  int filter_max, unsigned long long* keys_in, unsigned long long* keys_out,
                                  unsigned* vals_in, unsigned* vals_out, void* temp, size_t temp_bytes,
                                  int* scratch, hipStream_t s);
-hipError_t psx_launch_orientation(const PsxParams* d_params, PsxCounters* d_cnt, hipStream_t s);
+hipError_t psx_launch_orientation(const PsxTuning& t, const PsxParams* d_params, PsxCounters* d_cnt, hipStream_t s);
 hipError_t psx_launch_scan(const PsxParams* d_params, PsxCounters* d_cnt, const PsxExport& x, hipStream_t s);
 hipError_t psx_launch_feature_ptrs(const psx_feature* in, psx_feature_dev* out, int n, float* desc_base, int num_desc,
                                    hipStream_t s);
-hipError_t psx_launch_descriptors(const PsxParams* d_params, const PsxCounters* d_cnt, const PsxExport& x, int cus, hipStream_t s);
-hipError_t psx_launch_descriptors_alt(const PsxParams* d_params, const PsxCounters* d_cnt, int desc_mode, const PsxExport& x, int cus, hipStream_t s);
+hipError_t psx_launch_descriptors(const PsxTuning& t, const PsxParams* d_params, const PsxCounters* d_cnt, const PsxExport& x, hipStream_t s);
+hipError_t psx_launch_descriptors_alt(const PsxTuning& t, const PsxParams* d_params, const PsxCounters* d_cnt, int desc_mode, const PsxExport& x, hipStream_t s);
 
 // ---- multi-level tile kernel (pyramid_tile.hip, blur_tile_core.h): several consecutive levels of an octave per launch ----
 struct PsxTileJob;

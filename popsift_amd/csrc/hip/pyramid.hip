@@ -1380,33 +1380,17 @@ __global__ void k_dog(const float* a, const float* b, float* d, int W, int H, in
     d[i] = b[i] - a[i];
 }
 
-// Tuning switches for A/B measurements on the GPU (read once): POPSIFT_BLUR_STEPS = marching steps per chunk
-// on large planes (default 5), POPSIFT_BLUR_DEFER=0 stores the vertical results at once (the round-1 kernel).
-struct BlurTuning { int steps; bool defer; int dma; int dma_steps; };
-inline const BlurTuning& blur_tuning()
-{
-    static const BlurTuning t = [] {
-        BlurTuning v{5, true, 0, 0};
-        // POPSIFT_BLUR_DMA: 0 = register-staged k_blur, 2 / 3 = LDS-DMA staging with 2 / 3 stage buffers (k_blur_dma)
-        // (a dedicated loader wave, H and V on different waves and a one-shot tile kernel for the small planes were built
-        // on top of it in round 3, measured slower and removed again: profiles/r03_blur_staging_experiments.txt, git history)
-        // 1 = one stage buffer (the next batch goes out after the H pass): the least LDS, up to 5 workgroups per CU
-        if (const char* e = getenv("POPSIFT_BLUR_DMA")) { const int n = atoi(e); if (n >= 0 && n <= 3) v.dma = n; }
-        if (const char* e = getenv("POPSIFT_BLUR_DMA_STEPS")) { const int n = atoi(e); if (n >= 2 && n <= 64) v.dma_steps = n; }
-        if (const char* e = getenv("POPSIFT_BLUR_STEPS")) { const int n = atoi(e); if (n >= 2 && n <= 64) v.steps = n; }
-        if (const char* e = getenv("POPSIFT_BLUR_DEFER")) v.defer = e[0] != '0';
-        return v;
-    }();
-    return t;
-}
-
-inline void chunking(int W, int H, int R, int& chunk_rows, int& nchunks)
+// POPSIFT_BLUR_DMA: 0 = register-staged k_blur, 2 / 3 = LDS-DMA staging with 2 / 3 stage buffers (k_blur_dma)
+// (a dedicated loader wave, H and V on different waves and a one-shot tile kernel for the small planes were built
+// on top of it in round 3, measured slower and removed again: profiles/r03_blur_staging_experiments.txt, git history)
+// 1 = one stage buffer (the next batch goes out after the H pass): the least LDS, up to 5 workgroups per CU
+inline void chunking(const PsxTuning& t, int W, int H, int R, int& chunk_rows, int& nchunks)
 {
     // S marching steps per chunk: the 2R warm-up rows cost ~2R/(S*BR) extra horizontal work, but a
     // chunk is a serial chain of S steps.  Large planes take S=5; small octaves trade efficiency
     // for more, shorter workgroups (they are latency bound, not bandwidth bound).
     const int nstrips = (W + TW - 1) / TW;
-    int S = blur_tuning().steps;
+    int S = t.blur_steps;
     // planes that fill the chip four times over even with longer chunks take 7 steps: less warm-up work per output
     // row (8192 x 8192 planes: 0.574 -> 0.593 of 8 TB/s; at 3840 x 2160 7 steps would leave 660 workgroups: slower)
     if (S == 5 && nstrips * ((H + (7 * BR - 2 * R) - 1) / (7 * BR - 2 * R)) >= 4096) S = 7;
@@ -1416,8 +1400,7 @@ inline void chunking(int W, int H, int R, int& chunk_rows, int& nchunks)
     }
     // POPSIFT_BLUR_ONESTEP=1 (measurement switch, round 6): the small octaves as one-step chunks where one step still yields
     // >= 12 rows (what took the fixed-span and interpolated kernels' small launches from ~9 to ~5.5 us)
-    static const bool onestep = [] { const char* e = getenv("POPSIFT_BLUR_ONESTEP"); return e != nullptr && e[0] == '1'; }();
-    if (onestep && S == 2 && BR - 2 * R >= 12 && nstrips * ((H + (2 * BR - 2 * R) - 1) / (2 * BR - 2 * R)) < 256) S = 1;
+    if (t.blur_onestep && S == 2 && BR - 2 * R >= 12 && nstrips * ((H + (2 * BR - 2 * R) - 1) / (2 * BR - 2 * R)) < 256) S = 1;
     int cr = S * BR - 2 * R;
     if (cr < BR / 2 && S > 1) cr = BR / 2;
     if (cr > H) cr = H;
@@ -1427,32 +1410,26 @@ inline void chunking(int W, int H, int R, int& chunk_rows, int& nchunks)
 
 // fills the arguments of one plane-to-plane blur; returns its number of workgroups
 template <int R>
-int fill_job(BlurArgs& a, const PsxBlurJob& j)
+int fill_job(const PsxTuning& t, BlurArgs& a, const PsxBlurJob& j)
 {
     a.src = j.src; a.dst = j.dst; a.half_dst = j.half_dst;
     a.W = j.W; a.H = j.H; a.pitch = j.pitch; a.half_pitch = j.half_pitch;
     a.src_pitch = j.pitch; a.src_xoff = 0; a.src_width = j.W;
     a.nstrips = (j.W + TW - 1) / TW;
     int nchunks;
-    chunking(j.W, j.H, R, a.chunk_rows, nchunks);
+    chunking(t, j.W, j.H, R, a.chunk_rows, nchunks);
     a.taps = j.taps; a.taps_v = j.taps;
 #ifdef PSX_PHASE_TIMING
-    { const char* e = getenv("POPSIFT_BLUR_DBG"); a.dbg = e ? atoi(e) : 0; }
+    a.dbg = t.blur_dbg;
 #endif
     return a.nstrips * nchunks;
 }
 
-inline int device_cus()
-{
-    static const int n = [] { int d = 0, c = 0; if (hipGetDevice(&d) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || c <= 0) c = 256; return c; }();
-    return n;
-}
-
 template <int R>
-hipError_t launch_blur2_r(const PsxBlurJob& ja, const PsxBlurJob& jb, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+hipError_t launch_blur2_r(const PsxTuning& t, const PsxBlurJob& ja, const PsxBlurJob& jb, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
     BlurArgs a, b;
-    const int na = fill_job<R>(a, ja), nb = fill_job<R>(b, jb);
+    const int na = fill_job<R>(t, a, ja), nb = fill_job<R>(t, b, jb);
     const dim3 grid(na + nb), block(NT);
     if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((k_blur2<R>), grid, block, 0, s, ev0, ev1, 0, a, b, na);
     else                                  hipLaunchKernelGGL((k_blur2<R>), grid, block, 0, s, a, b, na);
@@ -1465,11 +1442,11 @@ constexpr int dma_ring(int R) { return (BR + 2 * R + 15) & ~15; }
 // Chunking for k_blur_dma.  A plane that fits one round of resident workgroups should be exactly one round (a second,
 // nearly empty round doubles the launch): take the smallest S >= 5 steps per chunk that fits; planes of several rounds
 // take 7 steps (less warm-up work per output row), small planes fewer (they are latency chains).
-inline void chunking_dma(int W, int H, int R, int slots, int& chunk_rows, int& nchunks)
+inline void chunking_dma(const PsxTuning& t, int W, int H, int R, int slots, int& chunk_rows, int& nchunks)
 {
     const int nstrips = (W + TW - 1) / TW;
     auto nwg = [&](int S) { const int cr = S * BR - 2 * R; return nstrips * ((H + cr - 1) / cr); };
-    int S = blur_tuning().dma_steps;
+    int S = t.blur_dma_steps;
     if (S == 0) {
         S = 5;
         if (nwg(5) > slots) {
@@ -1488,36 +1465,36 @@ inline void chunking_dma(int W, int H, int R, int slots, int& chunk_rows, int& n
 }
 
 template <int R, bool LEVEL0, int NBUF>
-void launch_dma(BlurArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+void launch_dma(const PsxTuning& t, BlurArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
     constexpr int RING = dma_ring(R);
     int nchunks;
-    chunking_dma(a.W, a.H, R, dma_wg_per_cu<R, NBUF, RING>() * device_cus(), a.chunk_rows, nchunks);
+    chunking_dma(t, a.W, a.H, R, dma_wg_per_cu<R, NBUF, RING>() * t.cus, a.chunk_rows, nchunks);
     const dim3 grid(a.nstrips * nchunks), block(NT);
     if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((k_blur_dma<R, LEVEL0, NBUF, RING>), grid, block, 0, s, ev0, ev1, 0, a);
     else                                  hipLaunchKernelGGL((k_blur_dma<R, LEVEL0, NBUF, RING>), grid, block, 0, s, a);
 }
 
 template <int R>
-hipError_t launch_blur_r(const float* src, float* dst, int W, int H, int pitch, const PsxTaps& taps,
+hipError_t launch_blur_r(const PsxTuning& t, const float* src, float* dst, int W, int H, int pitch, const PsxTaps& taps,
                          float* half_dst, int half_pitch, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
     BlurArgs a;
     PsxBlurJob j;
     j.src = src; j.dst = dst; j.half_dst = half_dst; j.W = W; j.H = H; j.pitch = pitch; j.half_pitch = half_pitch;
     j.taps = taps; j.span = R + 1;
-    const dim3 grid(fill_job<R>(a, j)), block(NT);
+    const dim3 grid(fill_job<R>(t, a, j)), block(NT);
     if constexpr (R <= 13) {
-        const int dma = blur_tuning().dma;
-        if (dma == 1) { launch_dma<R, false, 1>(a, s, ev0, ev1); return hipGetLastError(); }
-        if (dma == 2) { launch_dma<R, false, 2>(a, s, ev0, ev1); return hipGetLastError(); }
-        if (dma == 3) { launch_dma<R, false, 3>(a, s, ev0, ev1); return hipGetLastError(); }
+        const int dma = t.blur_dma;
+        if (dma == 1) { launch_dma<R, false, 1>(t, a, s, ev0, ev1); return hipGetLastError(); }
+        if (dma == 2) { launch_dma<R, false, 2>(t, a, s, ev0, ev1); return hipGetLastError(); }
+        if (dma == 3) { launch_dma<R, false, 3>(t, a, s, ev0, ev1); return hipGetLastError(); }
     }
     const bool ext = ev0 != nullptr || ev1 != nullptr;       // kernel begin / end timestamps of THIS dispatch (what rocprofv3 --kernel-trace reports)
-    if (blur_tuning().defer) {
+    if (t.blur_defer) {
         // POPSIFT_BLUR_LDS_PAD (measurement switch): extra dynamic LDS per workgroup, i.e. fewer resident k_blur
         // workgroups per CU, leaving room for another stream's kernels on the same CUs
-        static const unsigned pad = [] { const char* e = getenv("POPSIFT_BLUR_LDS_PAD"); return e ? (unsigned)atoi(e) : 0u; }();
+        const unsigned pad = (unsigned)t.blur_lds_pad;
         if (ext) hipExtLaunchKernelGGL((k_blur<R, false, true>), grid, block, pad, s, ev0, ev1, 0, a);
         else     hipLaunchKernelGGL((k_blur<R, false, true>), grid, block, pad, s, a);
     } else {
@@ -1527,38 +1504,30 @@ hipError_t launch_blur_r(const float* src, float* dst, int W, int H, int pitch, 
     return hipGetLastError();
 }
 
-// POPSIFT_LEVEL0_FUSED=0 keeps k_upscale + k_blur<R, true> for every configuration
-inline bool level0_fused_enabled()
-{
-    static const bool on = [] { const char* e = getenv("POPSIFT_LEVEL0_FUSED"); return !(e != nullptr && e[0] == '0'); }();
-    return on;
-}
-
 template <int R>
-hipError_t launch_level0_r(const PsxLevel0Args& h, hipStream_t s)
+hipError_t launch_level0_r(const PsxTuning& t, const PsxLevel0Args& h, hipStream_t s)
 {
     if constexpr (R <= 8) {
         // the default x2 upsampling: W = 2w, H = 2h exactly, with the sampling shift of a SiftMode (1.0 PopSift / VLFeat,
         // 0.5 OpenCV).  The kernel's staging assumes what holds for exactly these: the 8 texel columns of 4 adjacent
         // outputs lie within 4 consecutive texels and a 32-row step touches at most NTX texel rows (checked for both
         // shifts incl. the al = 1 knife edge); any other shift or scale keeps k_upscale, which tests the condition itself
-        if (level0_fused_enabled() && h.W == 2 * h.w && h.H == 2 * h.h && h.w >= 4 && (h.shift == 1.0f || h.shift == 0.5f)) {
+        // POPSIFT_LEVEL0_FUSED=0 keeps k_upscale + k_blur<R, true> for every configuration
+        if (t.level0_fused && h.W == 2 * h.w && h.H == 2 * h.h && h.w >= 4 && (h.shift == 1.0f || h.shift == 0.5f)) {
             L0Args f;
             f.img = h.img; f.w = h.w; f.h = h.h; f.dst = h.dst; f.W = h.W; f.H = h.H; f.pitch = h.pitch; f.shift = h.shift;
             f.nstrips = (h.W + TW - 1) / TW;
             int nchunks;
-            chunking(h.W, h.H, R, f.chunk_rows, nchunks);
+            chunking(t, h.W, h.H, R, f.chunk_rows, nchunks);
             f.taps = h.taps_h; f.taps_v = h.taps_v;
             const dim3 grid(f.nstrips * nchunks), block(NT);
             // POPSIFT_LEVEL0_X2=0: round 3's k_level0_fused (general weights) instead of the x2-specialised kernel
-            static const bool x2 = [] { const char* e = getenv("POPSIFT_LEVEL0_X2"); return !(e != nullptr && e[0] == '0'); }();
             if constexpr (R == 8) {
                 if (h.v_ifilter != nullptr) {
                     // VLFeat_Relative: the interpolated vertical pass; np pairs run on the next instantiation (zero-weight pairs)
                     const int np = (h.v_ispan - 1) / 2;
                     f.vg0 = h.v_ifilter[0];
-                    static const int force = [] { const char* e = getenv("POPSIFT_INTERP_LITERAL"); return e != nullptr && e[0] == '1' ? 1 : 0; }();
-                    f.vforce = force;
+                    f.vforce = t.interp_literal ? 1 : 0;
                     for (int p = 0; p < 4; p++) {
                         const int offset = 2 * p + 1;
                         const float u = p < np ? h.v_ifilter[offset] : 0.0f;
@@ -1577,7 +1546,7 @@ hipError_t launch_level0_r(const PsxLevel0Args& h, hipStream_t s)
                 }
             }
             if (h.v_ifilter != nullptr) return hipErrorNotSupported;
-            if (x2) {
+            if (t.level0_x2) {
                 const bool s1 = h.shift == 1.0f;
                 if (h.is_float) { if (s1) hipLaunchKernelGGL((k_level0_x2<R, true, true>), grid, block, 0, s, f);  else hipLaunchKernelGGL((k_level0_x2<R, true, false>), grid, block, 0, s, f); }
                 else            { if (s1) hipLaunchKernelGGL((k_level0_x2<R, false, true>), grid, block, 0, s, f); else hipLaunchKernelGGL((k_level0_x2<R, false, false>), grid, block, 0, s, f); }
@@ -1605,15 +1574,15 @@ hipError_t launch_level0_r(const PsxLevel0Args& h, hipStream_t s)
     a.src_pitch = h.tmp_pitch; a.src_xoff = pad; a.src_width = wr + 2 * pad;
     a.nstrips = (h.W + TW - 1) / TW;
     int nchunks;
-    chunking(h.W, h.H, R, a.chunk_rows, nchunks);
+    chunking(t, h.W, h.H, R, a.chunk_rows, nchunks);
     a.taps = h.taps_h; a.taps_v = h.taps_v;
 #ifdef PSX_PHASE_TIMING
     a.dbg = 0;
 #endif
     if constexpr (R <= 8) {
-        const int dma = blur_tuning().dma;
-        if (dma == 2) { launch_dma<R, true, 2>(a, s, nullptr, nullptr); return hipGetLastError(); }
-        if (dma == 3) { launch_dma<R, true, 3>(a, s, nullptr, nullptr); return hipGetLastError(); }
+        const int dma = t.blur_dma;
+        if (dma == 2) { launch_dma<R, true, 2>(t, a, s, nullptr, nullptr); return hipGetLastError(); }
+        if (dma == 3) { launch_dma<R, true, 3>(t, a, s, nullptr, nullptr); return hipGetLastError(); }
     }
     hipLaunchKernelGGL((k_blur<R, true>), dim3(a.nstrips * nchunks), dim3(NT), 0, s, a);
     return hipGetLastError();
@@ -1624,59 +1593,56 @@ hipError_t launch_level0_r(const PsxLevel0Args& h, hipStream_t s)
 // span = one-sided tap count including the centre (GaussTable::span); radius R = span-1.
 // Kernels are instantiated for a set of radii; a smaller radius runs on the next larger
 // instantiation with zero weights, which is bit-exact (fma(x, 0, acc) == acc).
-hipError_t psx_launch_blur(const float* src, float* dst, int W, int H, int pitch, const PsxTaps& taps,
+hipError_t psx_launch_blur(const PsxTuning& t, const float* src, float* dst, int W, int H, int pitch, const PsxTaps& taps,
                            int span, float* half_dst, int half_pitch, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
     const int R = span - 1;
-    if (R <= 5)  return launch_blur_r<5>(src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
-    if (R <= 7)  return launch_blur_r<7>(src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
-    if (R <= 8)  return launch_blur_r<8>(src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
-    if (R <= 10) return launch_blur_r<10>(src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
-    if (R <= 13) return launch_blur_r<13>(src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
-    if (R <= 16) return launch_blur_r<16>(src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
-    if (R <= 22) return launch_blur_r<22>(src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
-    if (R <= 30) return launch_blur_r<30>(src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
+    if (R <= 5)  return launch_blur_r<5>(t, src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
+    if (R <= 7)  return launch_blur_r<7>(t, src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
+    if (R <= 8)  return launch_blur_r<8>(t, src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
+    if (R <= 10) return launch_blur_r<10>(t, src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
+    if (R <= 13) return launch_blur_r<13>(t, src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
+    if (R <= 16) return launch_blur_r<16>(t, src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
+    if (R <= 22) return launch_blur_r<22>(t, src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
+    if (R <= 30) return launch_blur_r<30>(t, src, dst, W, H, pitch, taps, half_dst, half_pitch, s, ev0, ev1);
     return hipErrorInvalidValue;
 }
 
 // Pairing rule of the diagonal schedule: the level launches of two planes share ONE launch when both chunk grids fit one
 // round of resident workgroups
-bool psx_blur_pair_ok(int W1, int H1, int W2, int H2, int span, int resident_marching)
+bool psx_blur_pair_ok(const PsxTuning& t, int W1, int H1, int W2, int H2, int span, int resident_marching)
 {
-    return psx_blur_grid(W1, H1, span) + psx_blur_grid(W2, H2, span) <= resident_marching;
+    return psx_blur_grid(t, W1, H1, span) + psx_blur_grid(t, W2, H2, span) <= resident_marching;
 }
 
 // workgroups a blur of a W x H plane is launched with
-int psx_blur_grid(int W, int H, int span)
+int psx_blur_grid(const PsxTuning& t, int W, int H, int span)
 {
     int cr, nchunks;
-    chunking(W, H, span - 1, cr, nchunks);
+    chunking(t, W, H, span - 1, cr, nchunks);
     return ((W + TW - 1) / TW) * nchunks;
 }
 
 // two independent blurs in one launch; the kernel is instantiated for the larger radius (zero taps for the other)
-hipError_t psx_launch_blur2(const PsxBlurJob& a, const PsxBlurJob& b, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+hipError_t psx_launch_blur2(const PsxTuning& t, const PsxBlurJob& a, const PsxBlurJob& b, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
     const int R = (a.span > b.span ? a.span : b.span) - 1;
-    if (R <= 5)  return launch_blur2_r<5>(a, b, s, ev0, ev1);
-    if (R <= 7)  return launch_blur2_r<7>(a, b, s, ev0, ev1);
-    if (R <= 8)  return launch_blur2_r<8>(a, b, s, ev0, ev1);
-    if (R <= 10) return launch_blur2_r<10>(a, b, s, ev0, ev1);
-    if (R <= 13) return launch_blur2_r<13>(a, b, s, ev0, ev1);
-    if (R <= 16) return launch_blur2_r<16>(a, b, s, ev0, ev1);
-    if (R <= 22) return launch_blur2_r<22>(a, b, s, ev0, ev1);
-    if (R <= 30) return launch_blur2_r<30>(a, b, s, ev0, ev1);
+    if (R <= 5)  return launch_blur2_r<5>(t, a, b, s, ev0, ev1);
+    if (R <= 7)  return launch_blur2_r<7>(t, a, b, s, ev0, ev1);
+    if (R <= 8)  return launch_blur2_r<8>(t, a, b, s, ev0, ev1);
+    if (R <= 10) return launch_blur2_r<10>(t, a, b, s, ev0, ev1);
+    if (R <= 13) return launch_blur2_r<13>(t, a, b, s, ev0, ev1);
+    if (R <= 16) return launch_blur2_r<16>(t, a, b, s, ev0, ev1);
+    if (R <= 22) return launch_blur2_r<22>(t, a, b, s, ev0, ev1);
+    if (R <= 30) return launch_blur2_r<30>(t, a, b, s, ev0, ev1);
     return hipErrorInvalidValue;
 }
 
 // ---- k_pyramid_flow: host side ------------------------------------------------------------------------------------
 // marching steps per work item of octave o (0 = the chunking of the launch-per-level schedule)
-static int flow_steps(int o)
+static int flow_steps(const std::string& t, int o)
 {
-    // read per plan (psx_resize), not once per process: tests switch it between contexts
     std::vector<int> tab;
-    const char* e = getenv("POPSIFT_FLOW_STEPS");
-    std::string t = e ? e : "3,2,1";
     size_t p = 0;
     while (p <= t.size()) {
         const size_t q = t.find(',', p);
@@ -1688,7 +1654,7 @@ static int flow_steps(int o)
     return tab[(size_t)std::min<int>(o, (int)tab.size() - 1)];
 }
 
-bool psx_flow_plan(const PsxParams& P, const float* inc_filter, const int* inc_span, int first_octave,
+bool psx_flow_plan(const PsxTuning& t, const PsxParams& P, const float* inc_filter, const int* inc_span, int first_octave,
                    int resident_blocks, int order, PsxFlowPlan* out)
 {
     const int L = P.L, nlev = L - 1;
@@ -1717,12 +1683,12 @@ bool psx_flow_plan(const PsxParams& P, const float* inc_filter, const int* inc_s
             j.W = oc.w; j.H = oc.h; j.pitch = oc.pitch;
             j.nstrips = (oc.w + TW - 1) / TW;
             j.rsel = rsel[l];
-            chunking(oc.w, oc.h, flow_radius(j.rsel), j.chunk_rows, j.nchunks);
+            chunking(t, oc.w, oc.h, flow_radius(j.rsel), j.chunk_rows, j.nchunks);
             // The octaves that cannot fill the chip are a CHAIN of dependent levels (o+1 starts when level L-3 of o is
             // done): what counts there is the latency of one item, i.e. its number of marching steps, not the warm-up rows
             // it recomputes.  POPSIFT_FLOW_STEPS="s0,s1,s2,.." overrides the steps per item of octave 0, 1, 2, .. (0 = keep)
             {
-                const int so = flow_steps(o - 0);
+                const int so = flow_steps(t.flow_steps, o - 0);
                 if (so > 0) {
                     int cr = so * BR - 2 * flow_radius(j.rsel);
                     if (cr < 4) cr = 4;
@@ -1782,7 +1748,7 @@ bool psx_flow_plan(const PsxParams& P, const float* inc_filter, const int* inc_s
         // small octaves (a chain of ~14 dependent levels) then run as soon as their rows exist instead of queueing behind
         // octave 0's bulk.  The order of the simulated starts is topological (a consumer starts after its producers end).
         int P_ = std::min(resident_blocks, (int)std::min<size_t>(nitems, 1u << 20));
-        if (const char* e = getenv("POPSIFT_FLOW_GRID")) { const int v = atoi(e); if (v >= PSX_FLOW_SHARDS) P_ = v; }
+        if (t.flow_grid > 0) P_ = t.flow_grid;
         std::vector<int> base((size_t)njobs + 1, 0);
         for (int ji = 0; ji < njobs; ji++) base[(size_t)ji + 1] = base[(size_t)ji] + jobs[(size_t)ji].nchunks;
         const int nn = base[(size_t)njobs];
@@ -1874,7 +1840,8 @@ bool psx_flow_plan(const PsxParams& P, const float* inc_filter, const int* inc_s
     }
     out->njobs = njobs; out->nitems = (int)nitems; out->ncounters = ncnt;
     int grid = std::min(resident_blocks, (int)((nitems + PSX_FLOW_SHARDS - 1) / PSX_FLOW_SHARDS) * PSX_FLOW_SHARDS);
-    if (const char* e = getenv("POPSIFT_FLOW_GRID")) { const int v = atoi(e); if (v >= PSX_FLOW_SHARDS) grid = v; }
+    static_assert(PSX_FLOW_SHARDS == 8, "the lower bound of POPSIFT_FLOW_GRID in psx_tuning.h");
+    if (t.flow_grid > 0) grid = t.flow_grid;
     out->grid = (grid / PSX_FLOW_SHARDS) * PSX_FLOW_SHARDS;
     out->jobs = static_cast<PsxFlowJob*>(malloc(sizeof(PsxFlowJob) * (size_t)njobs));
     out->items = static_cast<PsxFlowItem*>(malloc(sizeof(PsxFlowItem) * nitems));
@@ -1906,7 +1873,7 @@ extern "C" int psx_flow_selfcheck(int w0, int h0, int num_octaves, int levels, c
     }
     std::vector<float> filt((size_t)PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN, 0.0f);
     PsxFlowPlan plan{};
-    if (!psx_flow_plan(P, filt.data(), spans, first_octave, resident_blocks, order, &plan)) return -2;
+    if (!psx_flow_plan(psx_tuning_from_env(), P, filt.data(), spans, first_octave, resident_blocks, order, &plan)) return -2;
     int rc = plan.nitems, maxwait = 0;
     std::vector<std::vector<int>> last_pos((size_t)plan.njobs), seen((size_t)plan.njobs);
     for (int j = 0; j < plan.njobs; j++) {
@@ -1956,13 +1923,13 @@ extern "C" int psx_flow_selfcheck(int w0, int h0, int num_octaves, int levels, c
     return rc;
 }
 
-hipError_t psx_launch_flow(const PsxFlowJob* d_jobs, const PsxFlowItem* d_items, int nitems, int* d_state, int* d_err,
+hipError_t psx_launch_flow(const PsxTuning& t, const PsxFlowJob* d_jobs, const PsxFlowItem* d_items, int nitems, int* d_state, int* d_err,
                            int grid, int ldmode, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, long long* trace)
 {
     const dim3 g(grid), b(NT);
     const bool ext = ev0 != nullptr || ev1 != nullptr;
     // measurement switch (results are wrong with it): 1 = no dependency waits, 2 = no arithmetic (tickets, waits and publishes only)
-    static const int dbg = [] { const char* e = getenv("POPSIFT_FLOW_DEBUG"); return e ? atoi(e) : 0; }();
+    const int dbg = t.flow_debug;
     if (ldmode == 2) {
         if (ext) hipExtLaunchKernelGGL((k_pyramid_flow<2>), g, b, 0, s, ev0, ev1, 0, d_jobs, d_items, nitems, d_state, d_err, dbg, trace);
         else     hipLaunchKernelGGL((k_pyramid_flow<2>), g, b, 0, s, d_jobs, d_items, nitems, d_state, d_err, dbg, trace);
@@ -1991,22 +1958,21 @@ bool psx_level0_exact(int w, int h, int W, int H)
 
 // level 0 with the interpolated vertical pass of GaussMode VLFeat_Relative (a.v_ifilter / a.v_ispan): covered by the x2 kernel for
 // up to 4 tap pairs and a "dd" radius up to 8
-bool psx_level0_interp_ok(const PsxLevel0Args& a)
+bool psx_level0_interp_ok(const PsxTuning& t, const PsxLevel0Args& a)
 {
-    static const bool off = [] { const char* e = getenv("POPSIFT_INTERP_FUSED"); return e != nullptr && e[0] == '0'; }();
-    return !off && level0_fused_enabled() && a.W == 2 * a.w && a.H == 2 * a.h && a.w >= 4 && (a.shift == 1.0f || a.shift == 0.5f) &&
+    return t.interp_fused && t.level0_fused && a.W == 2 * a.w && a.H == 2 * a.h && a.w >= 4 && (a.shift == 1.0f || a.shift == 0.5f) &&
            (a.v_ispan - 1) / 2 <= 4 && a.span_h - 1 <= 8 && psx_level0_exact(a.w, a.h, a.W, a.H);
 }
 
-hipError_t psx_launch_level0(const PsxLevel0Args& a, hipStream_t s)
+hipError_t psx_launch_level0(const PsxTuning& t, const PsxLevel0Args& a, hipStream_t s)
 {
-    if (a.v_ifilter != nullptr) return psx_level0_interp_ok(a) ? launch_level0_r<8>(a, s) : hipErrorNotSupported;
+    if (a.v_ifilter != nullptr) return psx_level0_interp_ok(t, a) ? launch_level0_r<8>(t, a, s) : hipErrorNotSupported;
     if (!psx_level0_exact(a.w, a.h, a.W, a.H)) return psx_launch_level0_literal(a, s);
     const int R = (a.span_h > a.span_v ? a.span_h : a.span_v) - 1;
-    if (R <= 5)  return launch_level0_r<5>(a, s);
-    if (R <= 8)  return launch_level0_r<8>(a, s);
-    if (R <= 16) return launch_level0_r<16>(a, s);
-    if (R <= 30) return launch_level0_r<30>(a, s);
+    if (R <= 5)  return launch_level0_r<5>(t, a, s);
+    if (R <= 8)  return launch_level0_r<8>(t, a, s);
+    if (R <= 16) return launch_level0_r<16>(t, a, s);
+    if (R <= 30) return launch_level0_r<30>(t, a, s);
     return hipErrorInvalidValue;
 }
 

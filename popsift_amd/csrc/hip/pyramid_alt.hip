@@ -241,6 +241,19 @@ hipError_t psx_launch_level0_literal(const PsxLevel0Args& a, hipStream_t s)
     return hipGetLastError();
 }
 
+// level l of octave o on the fused kernel of pyramid_interp.hip; feeds: the launch also writes level 0 of octave o + 1
+static PsxInterpJob interp_job(const PsxAltArgs& a, int o, int l, bool feeds)
+{
+    const PsxParams& P = *a.hp;
+    const PsxOctave& oc = P.oct[o];
+    PsxInterpJob j;
+    j.src = oc.data + (size_t)(l - 1) * oc.plane; j.dst = oc.data + (size_t)l * oc.plane;
+    j.half_dst = feeds ? P.oct[o + 1].data : nullptr; j.half_pitch = feeds ? P.oct[o + 1].pitch : 0;
+    j.W = oc.w; j.H = oc.h; j.pitch = oc.pitch;
+    j.fi = a.inc_ifilter + l * PSX_GAUSS_ALIGN; j.ispan = a.inc_ispan[l];
+    return j;
+}
+
 // GaussMode VLFeat_Relative with the default scaling, every level on the fused kernels (pyramid_interp.hip): the diagonal
 // schedule of the default pyramid (psx_build_pyramid).  Level l of octave o needs level l - 1 of its octave, and level 0 of octave
 // o + 1 is written by the launch of level D = L - 3 of octave o; so (o, l) runs in launch slot l + D o, and the jobs of a slot -- two
@@ -249,17 +262,9 @@ hipError_t psx_launch_level0_literal(const PsxLevel0Args& a, hipStream_t s)
 static hipError_t relative_diagonal(const PsxAltArgs& a, hipStream_t s)
 {
     const PsxParams& P = *a.hp;
+    const PsxTuning& tune = *a.tune;
     const int L = P.L, D = L - 3, noct = P.num_octaves;
-    auto job = [&](int o, int l) {
-        const PsxOctave& oc = P.oct[o];
-        PsxInterpJob j;
-        j.src = oc.data + (size_t)(l - 1) * oc.plane; j.dst = oc.data + (size_t)l * oc.plane;
-        const bool feeds = l == D && o + 1 < noct;
-        j.half_dst = feeds ? P.oct[o + 1].data : nullptr; j.half_pitch = feeds ? P.oct[o + 1].pitch : 0;
-        j.W = oc.w; j.H = oc.h; j.pitch = oc.pitch;
-        j.fi = a.inc_ifilter + l * PSX_GAUSS_ALIGN; j.ispan = a.inc_ispan[l];
-        return j;
-    };
+    auto job = [&](int o, int l) { return interp_job(a, o, l, l == D && o + 1 < noct); };
     for (int t = 1; t <= (L - 1) + D * (noct - 1); t++) {
         int os[PSX_MAX_OCTAVES], n = 0;
         for (int o = noct - 1; o >= 0; o--) {           // the deeper octave (the head of the dependency chain) first
@@ -271,14 +276,14 @@ static hipError_t relative_diagonal(const PsxAltArgs& a, hipStream_t s)
             hipError_t e;
             if (i + 1 < n) {
                 const int o2 = os[i + 1], l2 = t - D * o2;
-                if (psx_blur_interp_pair_ok(P.oct[o1].w, P.oct[o1].h, a.inc_ispan[l1], P.oct[o2].w, P.oct[o2].h, a.inc_ispan[l2])) {
-                    e = psx_launch_blur_interp2(job(o1, l1), job(o2, l2), s);
+                if (psx_blur_interp_pair_ok(tune, P.oct[o1].w, P.oct[o1].h, a.inc_ispan[l1], P.oct[o2].w, P.oct[o2].h, a.inc_ispan[l2])) {
+                    e = psx_launch_blur_interp2(tune, job(o1, l1), job(o2, l2), s);
                     if (e != hipSuccess) return e;
                     i += 2;
                     continue;
                 }
             }
-            e = psx_launch_blur_interp(job(o1, l1), s);
+            e = psx_launch_blur_interp(tune, job(o1, l1), s);
             if (e != hipSuccess) return e;
             i++;
         }
@@ -294,6 +299,7 @@ static hipError_t relative_diagonal(const PsxAltArgs& a, hipStream_t s)
 hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
 {
     const PsxParams& P = *a.hp;
+    const PsxTuning& t = *a.tune;
     const int gm = a.gauss_mode;
     const bool fixed = (gm == PSX_GAUSS_FIXED9 || gm == PSX_GAUSS_FIXED15);
     const bool direct = (a.scaling_mode == PSX_SCALE_DIRECT);
@@ -321,14 +327,17 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
         // level 0 of the default pyramid is, so it goes through psx_launch_level0: the default path's kernels (k_level0_x2
         // at x2 with a radius <= 8, k_upscale + k_blur<R, true> otherwise) when the image / octave ratio is a power of two
         // (bit-identical planes, ~10x faster on octave 0), k_alt_h_input + k_alt_v_plain when it is not
-        auto level_from_input = [&](float* dst, const PsxTaps& th, int sh, const PsxTaps& tv, int sv) -> hipError_t {
+        auto level0_args = [&](float* dst, const PsxTaps& th, int sh, const PsxTaps& tv, int sv) {
             PsxLevel0Args l0;
             l0.img = a.img; l0.w = a.w; l0.h = a.h; l0.is_float = a.is_float;
             l0.dst = dst; l0.W = W; l0.H = H; l0.pitch = pitch;
             l0.tmp = a.up; l0.tmp_pitch = a.up_pitch;
             l0.shift = shift;
             l0.taps_h = th; l0.span_h = sh; l0.taps_v = tv; l0.span_v = sv;
-            return psx_launch_level0(l0, s);
+            return l0;
+        };
+        auto level_from_input = [&](float* dst, const PsxTaps& th, int sh, const PsxTaps& tv, int sv) -> hipError_t {
+            return psx_launch_level0(t, level0_args(dst, th, sh, tv, sv), s);
         };
         auto fixed_levels = [&](int first, bool from_input) {
             const int vpitch = a.vbuf_pitch;
@@ -348,7 +357,7 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
         if (fixed) {
             // one launch per octave (pyramid_fixed.hip: level 0 read once, every derived level and the next octave's level 0
             // written from LDS) wherever that kernel applies; the per-level kernels above otherwise
-            const bool fused = psx_fixed_octave_enabled();
+            const bool fused = t.fixed_fused;
             PsxFixedOctaveArgs fo;
             fo.src_w = a.w; fo.src_h = a.h; fo.is_float = a.is_float;
             fo.shift = SHIFT; fo.plane = oc.plane; fo.W = W; fo.H = H; fo.pitch = pitch;
@@ -356,12 +365,12 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
             if (!direct && o + 1 < P.num_octaves) { fo.half_dst = P.oct[o + 1].data; fo.half_pitch = P.oct[o + 1].pitch; }
             fo.ev0 = fo.ev1 = nullptr;
             if (o == 0) {
-                if (fused && psx_fixed_octave0_ok(a.w, a.h, W, H) && a.upscale_factor == 1.0f) {
+                if (fused && psx_fixed_octave0_ok(t, a.w, a.h, W, H) && a.upscale_factor == 1.0f) {
                     fo.src = a.img; fo.from_input = 1; fo.nlev = 6; fo.dst = plane(0); fo.half_level = P.L - 3;
                     fo.scale = 255.0f; fo.taps = a.abs0_filter;
                     fo.ev0 = a.probe_ev0; fo.ev1 = a.probe_ev1;
                     if (a.probe_hit) *a.probe_hit = 1;
-                    const hipError_t e2 = psx_launch_fixed_octave(fo, s);
+                    const hipError_t e2 = psx_launch_fixed_octave(t, fo, s);
                     fo.ev0 = fo.ev1 = nullptr;
                     if (e2 != hipSuccess) return e2;
                     next_l0_done = fo.half_dst != nullptr;
@@ -374,7 +383,7 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
                 if (fused) {
                     fo.src = plane(0); fo.from_input = 0; fo.nlev = 5; fo.dst = plane(1); fo.half_level = P.L - 3 - 1;
                     fo.scale = 1.0f; fo.taps = a.absN_filter + PSX_GAUSS_ALIGN;
-                    const hipError_t e2 = psx_launch_fixed_octave(fo, s);
+                    const hipError_t e2 = psx_launch_fixed_octave(t, fo, s);
                     if (e2 != hipSuccess) return e2;
                     next_l0_done = fo.half_dst != nullptr;
                 } else { fixed_levels(1, false); next_l0_done = false; }
@@ -386,17 +395,13 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
                     // ScaleDirect with the plain tables: level 0 of every octave straight from the input image, the other
                     // levels absoluteSource::horiz + vert -- the default path's fused kernels
                     const hipError_t e2 = level == 0 ? level_from_input(plane(0), taps(a.dd_filter + o * PSX_GAUSS_ALIGN), a.dd_span[o], inc(0), a.inc_span[0])
-                                                     : psx_launch_blur(plane(level - 1), plane(level), W, H, pitch, inc(level), a.inc_span[level], nullptr, 0, s);
+                                                     : psx_launch_blur(t, plane(level - 1), plane(level), W, H, pitch, inc(level), a.inc_span[level], nullptr, 0, s);
                     if (e2 != hipSuccess) return e2;
                     continue;
                 }
-                if (level > 0 && psx_blur_interp_ok(a.inc_ispan[level])) {
+                if (level > 0 && psx_blur_interp_ok(t, a.inc_ispan[level])) {
                     // the fused kernel of pyramid_interp.hip (no decimation: ScaleDirect takes level 0 of every octave from the input)
-                    PsxInterpJob ij;
-                    ij.src = plane(level - 1); ij.dst = plane(level); ij.W = W; ij.H = H; ij.pitch = pitch;
-                    ij.half_dst = nullptr; ij.half_pitch = 0;
-                    ij.fi = a.inc_ifilter + level * PSX_GAUSS_ALIGN; ij.ispan = a.inc_ispan[level];
-                    const hipError_t e2 = psx_launch_blur_interp(ij, s);
+                    const hipError_t e2 = psx_launch_blur_interp(t, interp_job(a, o, level, false), s);
                     if (e2 != hipSuccess) return e2;
                     continue;
                 }
@@ -406,24 +411,19 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
             }
         } else if (gm == PSX_GAUSS_VLFEAT_RELATIVE) {
             bool all_fused = P.L >= 4;
-            for (int level = 1; level < P.L; level++) all_fused = all_fused && psx_blur_interp_ok(a.inc_ispan[level]);
-            static const bool diag = [] { const char* e = getenv("POPSIFT_INTERP_DIAGONAL"); return !(e != nullptr && e[0] == '0'); }();
+            for (int level = 1; level < P.L; level++) all_fused = all_fused && psx_blur_interp_ok(t, a.inc_ispan[level]);
             for (int level = 0; level < P.L; level++) {
-                if (level == 1 && o == 0 && all_fused && diag) {
+                if (level == 1 && o == 0 && all_fused && t.interp_diagonal) {
                     // every remaining level of the frame (and the extrema scans behind the octaves' last levels): diagonal schedule
                     return relative_diagonal(a, s);
                 }
                 if (level == 0) {
                     if (o == 0) {
                         // the x2 level-0 kernel of pyramid.hip with the interpolated vertical pass where it applies
-                        PsxLevel0Args l0;
-                        l0.img = a.img; l0.w = a.w; l0.h = a.h; l0.is_float = a.is_float;
-                        l0.dst = plane(0); l0.W = W; l0.H = H; l0.pitch = pitch;
-                        l0.tmp = a.up; l0.tmp_pitch = a.up_pitch; l0.shift = shift;
-                        l0.taps_h = taps(a.dd_filter); l0.span_h = a.dd_span[0]; l0.taps_v = inc(0); l0.span_v = a.inc_span[0];
+                        PsxLevel0Args l0 = level0_args(plane(0), taps(a.dd_filter), a.dd_span[0], inc(0), a.inc_span[0]);
                         l0.v_ifilter = a.inc_ifilter; l0.v_ispan = a.inc_ispan[0];
-                        if (psx_level0_interp_ok(l0)) {
-                            const hipError_t e2 = psx_launch_level0(l0, s);
+                        if (psx_level0_interp_ok(t, l0)) {
+                            const hipError_t e2 = psx_launch_level0(t, l0, s);
                             if (e2 != hipSuccess) return e2;
                         } else {
                             hipLaunchKernelGGL(k_alt_h_input, g, b, 0, s, img, a.intm, W, H, pitch, taps(a.dd_filter), a.dd_span[0], shift);
@@ -431,14 +431,10 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
                         }
                     } else if (!next_l0_done) downscale();
                     next_l0_done = false;
-                } else if (psx_blur_interp_ok(a.inc_ispan[level])) {
+                } else if (psx_blur_interp_ok(t, a.inc_ispan[level])) {
                     // one fused launch per level (pyramid_interp.hip); level L - 3 also writes level 0 of the next octave
                     const bool feeds = level == P.L - 3 && o + 1 < P.num_octaves;
-                    PsxInterpJob ij;
-                    ij.src = plane(level - 1); ij.dst = plane(level); ij.W = W; ij.H = H; ij.pitch = pitch;
-                    ij.half_dst = feeds ? P.oct[o + 1].data : nullptr; ij.half_pitch = feeds ? P.oct[o + 1].pitch : 0;
-                    ij.fi = a.inc_ifilter + level * PSX_GAUSS_ALIGN; ij.ispan = a.inc_ispan[level];
-                    const hipError_t e2 = psx_launch_blur_interp(ij, s);
+                    const hipError_t e2 = psx_launch_blur_interp(t, interp_job(a, o, level, feeds), s);
                     if (e2 != hipSuccess) return e2;
                     if (feeds) next_l0_done = true;
                 } else {
@@ -458,7 +454,7 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
             if (o == 0) return hipErrorInvalidValue;       // not reached: the default branch is psx_build_pyramid's own
             downscale();
             for (int level = 1; level < P.L; level++) {
-                hipError_t e = psx_launch_blur(plane(level - 1), plane(level), W, H, pitch, inc(level), a.inc_span[level], nullptr, 0, s);
+                hipError_t e = psx_launch_blur(t, plane(level - 1), plane(level), W, H, pitch, inc(level), a.inc_span[level], nullptr, 0, s);
                 if (e != hipSuccess) return e;
             }
         }

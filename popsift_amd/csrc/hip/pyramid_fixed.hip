@@ -360,27 +360,19 @@ __global__ __launch_bounds__(NT, GeomF<S>::WGPC) void k_fixed_octave(FixedArgs<S
     }
 }
 
-inline int device_cus()
-{
-    static const int n = [] { int d = 0, c = 0; if (hipGetDevice(&d) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || c <= 0) c = 256; return c; }();
-    return n;
-}
-
 // Rows per chunk.  A large plane is ONE round of resident workgroups (a second, nearly empty round would double the
 // launch), its chunks as long as that allows (the 2 SHIFT warm-up rows of a chunk are recomputed work); a small plane
 // is cut into chunks of two steps so that it still spreads over the chip.  POPSIFT_FIXED_WGS overrides the number of
 // workgroups aimed at (measurement switch).
 template <int S>
-void fixed_chunking(int W, int H, int& chunk_rows, int& nchunks)
+void fixed_chunking(const PsxTuning& t, int W, int H, int& chunk_rows, int& nchunks)
 {
     using G = GeomF<S>;
     const int nstrips = (W + TW - 1) / TW;
-    static const int want = [] { const char* e = getenv("POPSIFT_FIXED_WGS"); return e ? atoi(e) : 0; }();
-    const int slots = want > 0 ? want : G::WGPC * device_cus();
+    const int slots = t.fixed_wgs > 0 ? t.fixed_wgs : G::WGPC * t.cus;
     int maxc = slots / nstrips; if (maxc < 1) maxc = 1;
     // POPSIFT_FIXED_MINSTEPS: steps per chunk of a plane that does not fill the chip (measurement switch)
-    static const int minsteps = [] { const char* e = getenv("POPSIFT_FIXED_MINSTEPS"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 8 ? v : 1; }();
-    const int cr_min = minsteps * G::BR - 2 * S;
+    const int cr_min = t.fixed_minsteps * G::BR - 2 * S;
     int nc = (H + cr_min - 1) / cr_min; if (nc > maxc) nc = maxc; if (nc < 1) nc = 1;
     int cr = (H + nc - 1) / nc;
     // full steps: a chunk of n steps yields n BR - 2 SHIFT rows
@@ -392,7 +384,7 @@ void fixed_chunking(int W, int H, int& chunk_rows, int& nchunks)
 }
 
 template <int S, int NLEV, int SRC>
-hipError_t launch_fixed(const PsxFixedOctaveArgs& h, hipStream_t s)
+hipError_t launch_fixed(const PsxTuning& t, const PsxFixedOctaveArgs& h, hipStream_t s)
 {
     FixedArgs<S, NLEV> a;
     a.src = h.src; a.src_w = h.src_w; a.src_h = h.src_h;
@@ -401,7 +393,7 @@ hipError_t launch_fixed(const PsxFixedOctaveArgs& h, hipStream_t s)
     a.W = h.W; a.H = h.H; a.pitch = h.pitch;
     a.nstrips = (h.W + TW - 1) / TW;
     int nchunks;
-    fixed_chunking<S>(h.W, h.H, a.chunk_rows, nchunks);
+    fixed_chunking<S>(t, h.W, h.H, a.chunk_rows, nchunks);
     a.scale = h.scale;
     for (int l = 0; l < NLEV; l++)
         for (int i = 0; i <= S; i++) a.g[l][i] = h.taps[l * PSX_GAUSS_ALIGN + i];
@@ -414,27 +406,21 @@ hipError_t launch_fixed(const PsxFixedOctaveArgs& h, hipStream_t s)
 } // namespace
 
 // true when psx_launch_fixed_octave covers octave 0 of this configuration (otherwise: the per-level kernels of pyramid_alt.hip)
-bool psx_fixed_octave0_ok(int w, int h, int W, int H)
+bool psx_fixed_octave0_ok(const PsxTuning& t, int w, int h, int W, int H)
 {
-    static const bool off = [] { const char* e = getenv("POPSIFT_FIXED_FUSED"); return e != nullptr && e[0] == '0'; }();
     // up to 4096 texels per side the float coordinates stay within 1e-3 texel of the half-texel grid, far from the 1/512
     // rounding boundaries of the 1.8 weight (tests/test_numeric_tricks_cpu.py checks every column); larger images: the literal kernels
-    return !off && W == 2 * w && H == 2 * h && w >= 4 && w <= 4096 && h <= 4096;
-}
-bool psx_fixed_octave_enabled()
-{
-    static const bool off = [] { const char* e = getenv("POPSIFT_FIXED_FUSED"); return e != nullptr && e[0] == '0'; }();
-    return !off;
+    return t.fixed_fused && W == 2 * w && H == 2 * h && w >= 4 && w <= 4096 && h <= 4096;
 }
 
-hipError_t psx_launch_fixed_octave(const PsxFixedOctaveArgs& h, hipStream_t s)
+hipError_t psx_launch_fixed_octave(const PsxTuning& t, const PsxFixedOctaveArgs& h, hipStream_t s)
 {
     if (h.shift != 4 && h.shift != 7) return hipErrorInvalidValue;
     if (h.from_input) {
         if (h.nlev != 6) return hipErrorInvalidValue;
-        if (h.shift == 4) return h.is_float ? launch_fixed<4, 6, SRC_F32X2>(h, s) : launch_fixed<4, 6, SRC_U8X2>(h, s);
-        return h.is_float ? launch_fixed<7, 6, SRC_F32X2>(h, s) : launch_fixed<7, 6, SRC_U8X2>(h, s);
+        if (h.shift == 4) return h.is_float ? launch_fixed<4, 6, SRC_F32X2>(t, h, s) : launch_fixed<4, 6, SRC_U8X2>(t, h, s);
+        return h.is_float ? launch_fixed<7, 6, SRC_F32X2>(t, h, s) : launch_fixed<7, 6, SRC_U8X2>(t, h, s);
     }
     if (h.nlev != 5) return hipErrorInvalidValue;
-    return h.shift == 4 ? launch_fixed<4, 5, SRC_PLANE>(h, s) : launch_fixed<7, 5, SRC_PLANE>(h, s);
+    return h.shift == 4 ? launch_fixed<4, 5, SRC_PLANE>(t, h, s) : launch_fixed<7, 5, SRC_PLANE>(t, h, s);
 }

@@ -260,27 +260,18 @@ __global__ __launch_bounds__(NT, GeomI<NP>::WGPC) void k_blur_interp2(InterpArgs
     else          interp_body<NP>(b, lid - na, s_stage, s_ring, s_tab, s_mask);
 }
 
-inline int device_cus()
-{
-    static const int n = [] { int d = 0, c = 0; if (hipGetDevice(&d) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || c <= 0) c = 256; return c; }();
-    return n;
-}
-
 // steps per chunk as k_blur chooses them: 5 on planes that fill the chip, fewer on the small octaves (latency chains)
-inline void interp_chunking(int W, int H, int RI, int& chunk_rows, int& nchunks)
+inline void interp_chunking(const PsxTuning& t, int W, int H, int RI, int& chunk_rows, int& nchunks)
 {
     const int nstrips = (W + TW - 1) / TW;
-    static const int steps = [] { const char* e = getenv("POPSIFT_INTERP_STEPS"); const int v = e ? atoi(e) : 0; return v >= 2 && v <= 64 ? v : 5; }();
-    static const int minwg = [] { const char* e = getenv("POPSIFT_INTERP_MINWG"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 384; }();
-    int S = steps;
+    int S = t.interp_steps;
     for (; S > 2; S--) {
         const int cr = S * BR - 2 * RI;
-        if (cr >= BR && nstrips * ((H + cr - 1) / cr) >= minwg) break;
+        if (cr >= BR && nstrips * ((H + cr - 1) / cr) >= t.interp_minwg) break;
     }
     // the small octaves are latency chains: where the filter is narrow enough that ONE step still yields >= 12 rows, a plane
     // that does not fill a quarter of the chip with two-step chunks is cut into one-step chunks (POPSIFT_INTERP_ONESTEP=0: off)
-    static const bool onestep = [] { const char* e = getenv("POPSIFT_INTERP_ONESTEP"); return !(e != nullptr && e[0] == '0'); }();
-    if (onestep && S == 2 && BR - 2 * RI >= 12 && nstrips * ((H + (2 * BR - 2 * RI) - 1) / (2 * BR - 2 * RI)) < 256) S = 1;
+    if (t.interp_onestep && S == 2 && BR - 2 * RI >= 12 && nstrips * ((H + (2 * BR - 2 * RI) - 1) / (2 * BR - 2 * RI)) < 256) S = 1;
     int cr = S * BR - 2 * RI;
     if (cr < 4) cr = 4;
     if (cr > H) cr = H;
@@ -289,16 +280,15 @@ inline void interp_chunking(int W, int H, int RI, int& chunk_rows, int& nchunks)
 }
 
 template <int NP>
-int fill_interp(InterpArgs<NP>& a, const PsxInterpJob& j)
+int fill_interp(const PsxTuning& t, InterpArgs<NP>& a, const PsxInterpJob& j)
 {
     a.src = j.src; a.dst = j.dst; a.half_dst = j.half_dst;
     a.W = j.W; a.H = j.H; a.pitch = j.pitch; a.half_pitch = j.half_pitch;
     a.nstrips = (j.W + TW - 1) / TW;
     int nchunks;
-    interp_chunking(j.W, j.H, GeomI<NP>::RI, a.chunk_rows, nchunks);
+    interp_chunking(t, j.W, j.H, GeomI<NP>::RI, a.chunk_rows, nchunks);
     const int npairs = (j.ispan - 1) / 2;
-    static const int force = [] { const char* e = getenv("POPSIFT_INTERP_LITERAL"); return e != nullptr && e[0] == '1' ? 1 : 0; }();
-    a.force_literal = force;
+    a.force_literal = t.interp_literal ? 1 : 0;
     a.g0 = j.fi[0];
     for (int p = 0; p < NP; p++) {
         const int offset = 2 * p + 1;
@@ -311,20 +301,20 @@ int fill_interp(InterpArgs<NP>& a, const PsxInterpJob& j)
 }
 
 template <int NP>
-hipError_t launch_interp(const PsxInterpJob& j, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+hipError_t launch_interp(const PsxTuning& t, const PsxInterpJob& j, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
     InterpArgs<NP> a;
-    const dim3 grid(fill_interp<NP>(a, j)), block(NT);
+    const dim3 grid(fill_interp<NP>(t, a, j)), block(NT);
     if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((k_blur_interp<NP>), grid, block, 0, s, ev0, ev1, 0, a);
     else                                  hipLaunchKernelGGL((k_blur_interp<NP>), grid, block, 0, s, a);
     return hipGetLastError();
 }
 
 template <int NP>
-hipError_t launch_interp2(const PsxInterpJob& ja, const PsxInterpJob& jb, hipStream_t s)
+hipError_t launch_interp2(const PsxTuning& t, const PsxInterpJob& ja, const PsxInterpJob& jb, hipStream_t s)
 {
     InterpArgs<NP> a, b;
-    const int na = fill_interp<NP>(a, ja), nb = fill_interp<NP>(b, jb);
+    const int na = fill_interp<NP>(t, a, ja), nb = fill_interp<NP>(t, b, jb);
     hipLaunchKernelGGL((k_blur_interp2<NP>), dim3(na + nb), dim3(NT), 0, s, a, b, na);
     return hipGetLastError();
 }
@@ -334,53 +324,51 @@ hipError_t launch_interp2(const PsxInterpJob& ja, const PsxInterpJob& jb, hipStr
 // fi: the level's row of the interpolated table (i_filter: [0] centre, [2p+1] = u, [2p+2] = a + b), ispan: its odd span.
 // The loop of the reference runs offset = 1, 3, .. <= ispan; the table is zero from index ispan on, so the pairs that count
 // are offset <= ispan - 2.  Returns hipErrorNotSupported beyond 8 pairs (the caller keeps the per-level kernels).
-bool psx_blur_interp_ok(int ispan)
+bool psx_blur_interp_ok(const PsxTuning& t, int ispan)
 {
-    static const bool off = [] { const char* e = getenv("POPSIFT_INTERP_FUSED"); return e != nullptr && e[0] == '0'; }();
-    return !off && (ispan - 1) / 2 <= 8;
+    return t.interp_fused && (ispan - 1) / 2 <= 8;
 }
 
-hipError_t psx_launch_blur_interp(const PsxInterpJob& j, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+hipError_t psx_launch_blur_interp(const PsxTuning& t, const PsxInterpJob& j, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
     const int np = (j.ispan - 1) / 2;
-    if (np <= 3) return launch_interp<3>(j, s, ev0, ev1);
-    if (np <= 4) return launch_interp<4>(j, s, ev0, ev1);
-    if (np <= 5) return launch_interp<5>(j, s, ev0, ev1);
-    if (np <= 6) return launch_interp<6>(j, s, ev0, ev1);
-    if (np <= 7) return launch_interp<7>(j, s, ev0, ev1);
-    if (np <= 8) return launch_interp<8>(j, s, ev0, ev1);
+    if (np <= 3) return launch_interp<3>(t, j, s, ev0, ev1);
+    if (np <= 4) return launch_interp<4>(t, j, s, ev0, ev1);
+    if (np <= 5) return launch_interp<5>(t, j, s, ev0, ev1);
+    if (np <= 6) return launch_interp<6>(t, j, s, ev0, ev1);
+    if (np <= 7) return launch_interp<7>(t, j, s, ev0, ev1);
+    if (np <= 8) return launch_interp<8>(t, j, s, ev0, ev1);
     return hipErrorNotSupported;
 }
 
 // workgroups a level of a W x H plane is launched with
-int psx_blur_interp_grid(int W, int H, int ispan)
+int psx_blur_interp_grid(const PsxTuning& t, int W, int H, int ispan)
 {
     const int np = (ispan - 1) / 2, npt = np <= 3 ? 3 : np;      // the instantiation's pair count sets the chunk length
     int cr, nchunks;
-    interp_chunking(W, H, 2 * npt, cr, nchunks);
+    interp_chunking(t, W, H, 2 * npt, cr, nchunks);
     return ((W + TW - 1) / TW) * nchunks;
 }
 
 // pairing rule of the diagonal schedule: two levels share ONE launch when both grids fit one round of resident workgroups
-bool psx_blur_interp_pair_ok(int W1, int H1, int ispan1, int W2, int H2, int ispan2)
+bool psx_blur_interp_pair_ok(const PsxTuning& t, int W1, int H1, int ispan1, int W2, int H2, int ispan2)
 {
     const int isp = ispan1 > ispan2 ? ispan1 : ispan2;
     const int wgpc = (isp - 1) / 2 >= 5 && PSX_INTERP_WGPC_BIG > 0 ? PSX_INTERP_WGPC_BIG : 4;
     // POPSIFT_INTERP_PAIR_ROUNDS (measurement switch): percent of one round the two grids together may take (150 / 200, i.e. octave 0's
     // levels 4 and 5 sharing a launch with octave 1's levels 1 and 2: pyramid 0.315 -> 0.319 / 0.322 ms, profiles/r06_interp_pair_rounds.txt)
-    static const int pct = [] { const char* e = getenv("POPSIFT_INTERP_PAIR_ROUNDS"); const int v = e ? atoi(e) : 0; return v >= 50 && v <= 1000 ? v : 100; }();
-    return (psx_blur_interp_grid(W1, H1, isp) + psx_blur_interp_grid(W2, H2, isp)) * 100 <= wgpc * device_cus() * pct;
+    return (psx_blur_interp_grid(t, W1, H1, isp) + psx_blur_interp_grid(t, W2, H2, isp)) * 100 <= wgpc * t.cus * t.interp_pair_rounds;
 }
 
 // two independent levels in one launch; the kernel is instantiated for the larger pair count (zero-weight pairs for the other)
-hipError_t psx_launch_blur_interp2(const PsxInterpJob& a, const PsxInterpJob& b, hipStream_t s)
+hipError_t psx_launch_blur_interp2(const PsxTuning& t, const PsxInterpJob& a, const PsxInterpJob& b, hipStream_t s)
 {
     const int np = ((a.ispan > b.ispan ? a.ispan : b.ispan) - 1) / 2;
-    if (np <= 3) return launch_interp2<3>(a, b, s);
-    if (np <= 4) return launch_interp2<4>(a, b, s);
-    if (np <= 5) return launch_interp2<5>(a, b, s);
-    if (np <= 6) return launch_interp2<6>(a, b, s);
-    if (np <= 7) return launch_interp2<7>(a, b, s);
-    if (np <= 8) return launch_interp2<8>(a, b, s);
+    if (np <= 3) return launch_interp2<3>(t, a, b, s);
+    if (np <= 4) return launch_interp2<4>(t, a, b, s);
+    if (np <= 5) return launch_interp2<5>(t, a, b, s);
+    if (np <= 6) return launch_interp2<6>(t, a, b, s);
+    if (np <= 7) return launch_interp2<7>(t, a, b, s);
+    if (np <= 8) return launch_interp2<8>(t, a, b, s);
     return hipErrorNotSupported;
 }

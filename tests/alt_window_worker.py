@@ -1,6 +1,6 @@
 """Helper of tests/test_gpu_modes.py::test_alt_descriptor_window_equals_plane: prints, per (configuration, DescMode), an
-order-independent digest of the descriptors.  Run once with POPSIFT_ALT_WINDOW=1 and once with =0 (the switch is read once
-per process): the LDS window of k_descriptors_alt must give the bits of the plane in HBM."""
+order-independent digest of the descriptors.  Run once with POPSIFT_ALT_WINDOW=1 and once with =0 (the switch is read at
+psx_create; one process per setting): the LDS window of k_descriptors_alt must give the bits of the plane in HBM."""
 import hashlib
 import json
 import os

@@ -1,5 +1,5 @@
 """Worker of tests/test_gpu_parity.py::test_descriptor_lds_layouts_give_identical_descriptors: one process = one setting of
-POPSIFT_DESC_OCC (read once per process).  Prints one JSON line: for every case the number of descriptors and a
+POPSIFT_DESC_OCC (read at psx_create).  Prints one JSON line: for every case the number of descriptors and a
 SHA-1 over (feature record, descriptor) rows sorted by the record -- the order of the extrema list is not deterministic, its
 content is."""
 import hashlib

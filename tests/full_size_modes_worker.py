@@ -1,5 +1,5 @@
-"""Worker of tests/test_gpu_modes_full_size.py: one process = one setting of the environment switches (they are read once per
-process).  argv: a JSON file {"cases": [names], "features": bool}, and an output directory.  Writes <case>.npz per case:
+"""Worker of tests/test_gpu_modes_full_size.py: one process = one setting of the environment switches (they are read at
+psx_create).  argv: a JSON file {"cases": [names], "features": bool}, and an output directory.  Writes <case>.npz per case:
 the octave dimensions, the digests of every Gaussian plane (tests/full_size_cases.plane_digests), the initial extrema of every
 octave and, with "features", the features and descriptors; prints one JSON line of the cases done."""
 import json

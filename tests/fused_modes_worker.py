@@ -1,5 +1,5 @@
 """Worker of tests/test_gpu_modes.py::test_fused_mode_kernels_equal_per_level_kernels: one process = one setting of the
-environment switches (they are read once per process).  Prints one JSON line: for every case a SHA-1 over all Gaussian
+environment switches (they are read at psx_create).  Prints one JSON line: for every case a SHA-1 over all Gaussian
 planes and the keypoint count."""
 import hashlib
 import json

@@ -256,7 +256,7 @@ print("SWITCH-OK")
                                  dict(POPSIFT_BLUR_DEFER="0"), dict(POPSIFT_DESC_WGS="3"), dict(POPSIFT_BLUR_DMA="2"), dict(POPSIFT_BLUR_DMA="3"),
                                  dict(POPSIFT_BLUR_STEPS="3")])
 def test_documented_fallback_switches_keep_parity(env):
-    """The kernel-variant switches of INTEGRATION.md (read once per process, hence a subprocess each): the older variants
+    """The kernel-variant switches of INTEGRATION.md (read once per context, at psx_create; a subprocess each keeps the settings apart): the older variants
     they select stay bit-exact on the planes and within the feature budget on three frames."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

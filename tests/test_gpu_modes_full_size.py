@@ -3,7 +3,7 @@ frames, planes across the 2048 / 4096 / 8192 binades, the Fixed-mode size bound 
 kernels.  The small-size tests of tests/test_gpu_modes.py never reach the long-march chunking, the pairing rule at 1080p or
 the columns where the relative mode's weights vary; test_fused_mode_kernels_equal_per_level_kernels compares HIP with HIP.
 
-The chunking and schedule switches are read once per process, so every setting runs in a fresh child
+The chunking and schedule switches are read once per context (psx_create); every setting runs in a fresh child
 (tests/full_size_modes_worker.py) with a clean environment: every POPSIFT_* removed, then the setting's own values.  A
 setting runs the cases its switches can change; the defaults run every case and also compare features and descriptors.
 Planes are compared through digests (whole plane, every row, every column): a failure names the case, the setting, the

@@ -1,4 +1,4 @@
-"""psx_match with and without the MFMA prefilter (one subprocess per setting: the switch is read once per process):
+"""psx_match with and without the MFMA prefilter (one subprocess per setting: the switch is read when a thread first uses the matcher on a device):
 seconds and G pairs/s (device-resident descriptors in, results in host memory out), results compared by SHA-1.
   python tools/match_ab.py [n]     n unit-norm random descriptors per side (default 18432);
                                    n = 0: the real descriptors of two 1080p bench frames"""

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """A/B of pyramid schedules / kernel switches on the GPU, one subprocess per environment so that every POPSIFT_* switch is
-read fresh (they are read at psx_create or once per process).  Per variant: stage times of one frame on one context (HIP
+read fresh (the HIP library reads them once per context, at psx_create; the host library once per process).  Per variant: stage times of one frame on one context (HIP
 events), median wall time of one frame, in-pipeline k_blur probe, device-resident throughput over NCTX contexts.
 
   python tools/sched_ab.py [--size W H] [--repeat N] 'POPSIFT_TILE=0' 'POPSIFT_TILE=1 POPSIFT_TILE_TY=32' ...
 
 Every positional argument is one variant: space-separated NAME=VALUE pairs ('' = the defaults).  Variants run in the given
 order, the whole list --repeat times (boxes drift: compare neighbours, and list the baseline first and last).
-Valid switches are listed in tools/README.md; psx_create ignores values it does not know (e.g. POPSIFT_FLOW accepts 0..2)."""
+Valid switches are listed in tools/README.md; psx_create ignores values it does not accept, except for POPSIFT_FLOW (0..2), where it fails."""
 import json
 import os
 import subprocess
