@@ -33,6 +33,13 @@ void popsift_c_destroy(popsift_c_handle* h);
 /* PopSift::enqueue, popsift.h:219-232: deep-copies the image; NULL when the image is refused */
 popsift_c_job* popsift_c_enqueue_u8(popsift_c_handle* h, int w, int hgt, const unsigned char* img);
 popsift_c_job* popsift_c_enqueue_f32(popsift_c_handle* h, int w, int hgt, const float* img);
+/* PopSift::enqueue with caller-supplied keypoints (psx_keypoint, include/popsift_hip.h): the detector does not run, the
+ * n records are deep-copied and described; kps NULL or n 0 gives an empty result */
+popsift_c_job* popsift_c_enqueue_u8_kp(popsift_c_handle* h, int w, int hgt, const unsigned char* img, const psx_keypoint* kps, int n);
+popsift_c_job* popsift_c_enqueue_f32_kp(popsift_c_handle* h, int w, int hgt, const float* img, const psx_keypoint* kps, int n);
+/* FeaturesHost::getSourceIndices: the input record of every feature of a keypoint job.  Returns their number (0 for a
+ * detector job, -1 for NULL) and copies at most capacity of them into out (may be NULL). */
+int popsift_c_source_indices(const popsift_c_features* f, int* out, int capacity);
 /* SiftJob::get + delete job, popsift.h:75-81: blocks until the frame is done.  NULL on error. */
 popsift_c_features* popsift_c_get(popsift_c_job* job);
 /* FeaturesHost::getFeatureCount / getDescriptorCount */

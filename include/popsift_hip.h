@@ -143,8 +143,10 @@ int psx_print_gauss_tables(const psx_config* cfg, int columns);
 /* ---- context -------------------------------------------------------------------------- */
 
 /* Replaces PopSift::PopSift + applyConfiguration (popsift.cpp:25-48, 91-107): selects the
- * device, uploads Gauss tables / constants into the context (no global symbols), creates the
- * stream.  The environment switches of the library are read here, once per context. */
+ * device, computes the Gauss tables and constants of the context on the host (no global symbols; the
+ * parameter block goes to the device with psx_resize, the filter taps travel as kernel arguments) and
+ * creates the stream.  The environment switches of the library are read here, once per
+ * context. */
 int psx_create(int device, const psx_config* cfg, psx_ctx** out);
 int psx_destroy(psx_ctx* ctx);
 const char* psx_last_error(const psx_ctx* ctx);   /* ctx may be NULL: last create() error */
@@ -310,6 +312,52 @@ int psx_quantize_desc(int device, const float* d_src, int n, unsigned char* d_ds
  * Synchronous. */
 int psx_match_u8(int device, const unsigned char* d_left, int l_len, const unsigned char* d_right, int r_len,
                  int* host_match, int* host_dist);
+
+/* ---- caller-supplied keypoints ------------------------------------------------------------
+ * Describing points the caller brings along instead of the ones the DoG detector finds (what OpenCV calls
+ * useProvidedKeypoints and VLFeat calls frames; the reference has no counterpart).  A record carries what a
+ * psx_feature reports, in INPUT-IMAGE units; INTEGRATION.md ("Caller-supplied keypoints") states the placement and
+ * acceptance rule in words. */
+#define PSX_KP_AUTO (-1)
+typedef struct psx_keypoint {      /* 40 bytes */
+    float xpos, ypos, sigma;       /* INPUT-IMAGE units, exactly what psx_feature reports */
+    int   octave;                  /* >= 0: explicit;  PSX_KP_AUTO: placed by the bounds table */
+    int   lpos;                    /* Gaussian level of the octave (explicit placement only) */
+    int   num_ori;                 /* 0: the library assigns orientations; 1..4: orientation[] is given */
+    float orientation[PSX_ORI_MAX];/* radians, as psx_feature reports them */
+} psx_keypoint;
+
+#define PSX_DESCRIBE_REUSE_PYRAMID 1
+
+/* The levels + 1 level boundaries of automatic placement, b_l = (float)(sigma * 2^((l + 0.5) / levels)) for
+ * l = 0 .. levels, computed in double and rounded once; *n = levels + 1.  PSX_ERR_INVALID when capacity is smaller.
+ * Host arithmetic only. */
+int psx_keypoint_bounds(const psx_config* cfg, float* bounds, int capacity, int* n);
+
+/* The placement and acceptance rule on the host, for n records and an input of w x h pixels: octave[i] / lpos[i] =
+ * where record i lands, octave[i] = -1 for a record the rule drops.  No device and no context are involved; with
+ * octaves = -1 in the configuration the octave count is the one a fresh context takes for w x h.  The device kernel and
+ * this function call one inline function. */
+int psx_place_keypoints(const psx_config* cfg, int w, int h, const psx_keypoint* kps, int n, int* octave, int* lpos);
+
+/* The keypoints of the next psx_describe.  The host form copies the n records in stream order (the caller's array is
+ * free again on return); the device form takes no copy: the pointer (8-byte aligned) must stay valid until the
+ * describe call has been waited for.  n = 0 is a valid, empty list (the pointer may be NULL then).  PSX_ERR_STATE
+ * without an input image / pyramid dimensions. */
+int psx_set_keypoints(psx_ctx* ctx, const psx_keypoint* host, int n);
+int psx_set_keypoints_dev(psx_ctx* ctx, const psx_keypoint* dev, int n);
+
+/* Orientation (for the records with num_ori = 0), scan and descriptors at the keypoints set before, asynchronous on
+ * the context's stream like psx_extract; the detector does not run and the grid filter is never applied.  flags = 0
+ * builds the pyramid of the current input first; PSX_DESCRIBE_REUSE_PYRAMID uses the one the context already holds for
+ * it (PSX_ERR_STATE when there is none).  Output order: octave-major, caller order within an octave; per octave the
+ * first max_extrema accepted records are kept.  Every result call (counts, downloads, exports, device results, clone,
+ * extrema dump, stage timers: [1] is then the keypoint injection) works on the outcome as on an extraction's. */
+int psx_describe(psx_ctx* ctx, int flags);
+
+/* host_src[i] = index of the input record output feature i of the last psx_describe came from; *count = number of
+ * features.  PSX_ERR_STATE when the last results are not a describe call's.  Synchronises. */
+int psx_keypoint_map(psx_ctx* ctx, int* host_src, int capacity, int* count);
 
 /* device_prop_t (common/device_prop.h:23-108): enumeration only; there are no texture limits. */
 int psx_device_count(int* count);

@@ -51,6 +51,33 @@ IEXT_DTYPE = np.dtype([("xpos", "<f4"), ("ypos", "<f4"), ("lpos", "<i4"), ("sigm
 EXT_DTYPE = np.dtype([("xpos", "<f4"), ("ypos", "<f4"), ("lpos", "<i4"), ("sigma", "<f4"),
                       ("octave", "<i4"), ("num_ori", "<i4"), ("idx_ori", "<i4"),
                       ("orientation", "<f4", (ORI_MAX,))])
+KP_AUTO = -1                     # PSX_KP_AUTO
+DESCRIBE_REUSE_PYRAMID = 1       # PSX_DESCRIBE_REUSE_PYRAMID
+# psx_keypoint (40 bytes): a caller-supplied keypoint in input-image units
+KEYPOINT_DTYPE = np.dtype([("xpos", "<f4"), ("ypos", "<f4"), ("sigma", "<f4"), ("octave", "<i4"), ("lpos", "<i4"),
+                           ("num_ori", "<i4"), ("orientation", "<f4", (ORI_MAX,))])
+
+
+class Keypoint(C.Structure):
+    """psx_keypoint as a ctypes structure (KEYPOINT_DTYPE is the same record for numpy arrays)."""
+    _fields_ = [("xpos", C.c_float), ("ypos", C.c_float), ("sigma", C.c_float), ("octave", C.c_int), ("lpos", C.c_int),
+                ("num_ori", C.c_int), ("orientation", C.c_float * ORI_MAX)]
+
+    dtype = KEYPOINT_DTYPE
+
+
+def keypoints_array(kps):
+    """A C-contiguous KEYPOINT_DTYPE array of kps: such an array, a sequence of Keypoint structures, or None (empty)."""
+    if kps is None:
+        return np.zeros((0,), dtype=KEYPOINT_DTYPE)
+    if isinstance(kps, np.ndarray):
+        if kps.dtype != KEYPOINT_DTYPE:
+            raise TypeError("keypoints must have capi.KEYPOINT_DTYPE")
+        return np.ascontiguousarray(kps).reshape(-1)
+    out = np.zeros((len(kps),), dtype=KEYPOINT_DTYPE)
+    for i, k in enumerate(kps):
+        out[i] = (k.xpos, k.ypos, k.sigma, k.octave, k.lpos, k.num_ori, tuple(k.orientation))
+    return out
 
 # every symbol include/popsift_hip.h declares
 SYMBOLS = [
@@ -65,6 +92,8 @@ SYMBOLS = [
     "psx_print_gauss_tables", "psx_flow_trace", "psx_debug_cross_stream", "psx_probe_extra_times",
     "psx_set_descriptor_format", "psx_download_u8", "psx_attach_export_u8", "psx_attach_export_mapped_u8",
     "psx_quantize_desc", "psx_match_u8",
+    "psx_keypoint_bounds", "psx_place_keypoints", "psx_set_keypoints", "psx_set_keypoints_dev", "psx_describe",
+    "psx_keypoint_map",
 ]
 
 DESCFMT_F32 = 0      # PSX_DESCFMT_F32
@@ -121,6 +150,12 @@ def lib():
         L.psx_blur_probe_times.argtypes = [vp, fp, C.c_int, ip, C.POINTER(C.c_double)]
         L.psx_copy_bench.argtypes = [C.c_int, C.c_size_t, C.c_int, fp, C.POINTER(C.c_double)]
         L.psx_device_pci.argtypes = [C.c_int, C.c_char_p, C.c_int]
+        L.psx_keypoint_bounds.argtypes = [C.POINTER(Config), fp, C.c_int, ip]
+        L.psx_place_keypoints.argtypes = [C.POINTER(Config), C.c_int, C.c_int, vp, C.c_int, vp, vp]
+        L.psx_set_keypoints.argtypes = [vp, vp, C.c_int]
+        L.psx_set_keypoints_dev.argtypes = [vp, vp, C.c_int]
+        L.psx_describe.argtypes = [vp, C.c_int]
+        L.psx_keypoint_map.argtypes = [vp, vp, C.c_int, ip]
         _LIB = L
     return _LIB
 
@@ -133,6 +168,29 @@ def default_config(**kw):
             raise AttributeError(k)
         setattr(c, k, v)
     return c
+
+
+def keypoint_bounds(cfg):
+    """psx_keypoint_bounds: the levels + 1 float32 level boundaries of automatic keypoint placement."""
+    out = (C.c_float * GAUSS_LEVELS)()
+    n = C.c_int()
+    rc = lib().psx_keypoint_bounds(C.byref(cfg), out, GAUSS_LEVELS, C.byref(n))
+    if rc != 0:
+        raise PopSiftError("psx_keypoint_bounds failed (%d)" % rc)
+    return np.array(out[:n.value], dtype=np.float32)
+
+
+def place_keypoints(cfg, w, h, kps):
+    """psx_place_keypoints: (octave, lpos) int32 arrays for the records kps; octave = -1 where the rule drops one.
+    Host only."""
+    kps = keypoints_array(kps)
+    octave = np.zeros((len(kps),), np.int32)
+    lpos = np.zeros((len(kps),), np.int32)
+    rc = lib().psx_place_keypoints(C.byref(cfg), w, h, kps.ctypes.data_as(C.c_void_p), len(kps),
+                                   octave.ctypes.data_as(C.c_void_p), lpos.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PopSiftError("psx_place_keypoints failed (%d)" % rc)
+    return octave, lpos
 
 
 def match(left, right, device=0):
@@ -313,6 +371,7 @@ class Context:
             msg = lib().psx_last_error(None)
             raise PopSiftError("psx_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
         self._keep = None
+        self._keep_kps = None
 
     def _chk(self, rc):
         if rc != 0:
@@ -375,6 +434,35 @@ class Context:
 
     def sync(self):
         self._chk(lib().psx_sync(self._h))
+
+    # ---- caller-supplied keypoints -------------------------------------------------------------
+    def set_keypoints(self, kps):
+        """The keypoints of the next describe(): a KEYPOINT_DTYPE numpy array / a sequence of Keypoint (copied in
+        stream order), or a contiguous torch uint8 / int32 / float32 tensor on this context's device that holds such
+        records (no copy: it is kept alive here until the next call)."""
+        if hasattr(kps, "data_ptr"):
+            assert kps.is_contiguous() and kps.is_cuda
+            nbytes = kps.numel() * kps.element_size()
+            assert nbytes % KEYPOINT_DTYPE.itemsize == 0
+            self._keep_kps = kps
+            self._chk(lib().psx_set_keypoints_dev(self._h, C.c_void_p(kps.data_ptr()), nbytes // KEYPOINT_DTYPE.itemsize))
+            return
+        arr = keypoints_array(kps)
+        self._keep_kps = None
+        self._chk(lib().psx_set_keypoints(self._h, arr.ctypes.data_as(C.c_void_p), len(arr)))
+
+    def describe(self, reuse_pyramid=False):
+        """psx_describe: orientation (where a record brings none) and descriptors at the keypoints set before."""
+        self._chk(lib().psx_describe(self._h, DESCRIBE_REUSE_PYRAMID if reuse_pyramid else 0))
+
+    def keypoint_map(self):
+        """psx_keypoint_map: int32 array, entry i = index of the input record output feature i came from."""
+        n = C.c_int()
+        self._chk(lib().psx_keypoint_map(self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value,), np.int32)
+        if n.value:
+            self._chk(lib().psx_keypoint_map(self._h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return out
 
     # ---- results -----------------------------------------------------------------------------
     @property
@@ -564,7 +652,8 @@ HOST_LIB_PATH = os.environ.get("POPSIFT_HOST_LIB") or os.path.join(_HERE, "lib",
 HOST_SYMBOLS = ["popsift_c_create", "popsift_c_destroy", "popsift_c_enqueue_u8", "popsift_c_enqueue_f32",
                 "popsift_c_get", "popsift_c_feature_count", "popsift_c_descriptor_count", "popsift_c_copy",
                 "popsift_c_descriptors", "popsift_c_free", "popsift_c_last_error", "popsift_c_pool_stats",
-                "popsift_c_create_fmt", "popsift_c_descriptor_format", "popsift_c_copy_u8", "popsift_c_descriptor_bytes"]
+                "popsift_c_create_fmt", "popsift_c_descriptor_format", "popsift_c_copy_u8", "popsift_c_descriptor_bytes",
+                "popsift_c_enqueue_u8_kp", "popsift_c_enqueue_f32_kp", "popsift_c_source_indices"]
 _HOST = None
 
 
@@ -589,6 +678,10 @@ def host_lib():
         for n in ("popsift_c_enqueue_u8", "popsift_c_enqueue_f32"):
             getattr(H, n).argtypes = [vp, C.c_int, C.c_int, vp]
             getattr(H, n).restype = vp
+        for n in ("popsift_c_enqueue_u8_kp", "popsift_c_enqueue_f32_kp"):
+            getattr(H, n).argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int]
+            getattr(H, n).restype = vp
+        H.popsift_c_source_indices.argtypes = [vp, vp, C.c_int]
         H.popsift_c_get.argtypes = [vp]
         H.popsift_c_get.restype = vp
         H.popsift_c_feature_count.argtypes = [vp]
@@ -628,11 +721,18 @@ class PopSift:
         self._float = float_images
         self._bytes = byte_descriptors
 
-    def enqueue(self, img):
-        """img: C-contiguous (h, w) numpy array, uint8 or float32 (matching the image mode)."""
+    def enqueue(self, img, keypoints=None):
+        """img: C-contiguous (h, w) numpy array, uint8 or float32 (matching the image mode).  keypoints: None (the
+        detector runs) or the records to describe instead (KEYPOINT_DTYPE array or a sequence of Keypoint, may be
+        empty); get_sources() of the result then maps the features back to them."""
         h, w = img.shape
-        f = host_lib().popsift_c_enqueue_f32 if self._float else host_lib().popsift_c_enqueue_u8
-        job = f(self._h, w, h, img.ctypes.data)
+        if keypoints is not None:
+            kps = keypoints_array(keypoints)
+            f = host_lib().popsift_c_enqueue_f32_kp if self._float else host_lib().popsift_c_enqueue_u8_kp
+            job = f(self._h, w, h, img.ctypes.data, kps.ctypes.data, len(kps))
+        else:
+            f = host_lib().popsift_c_enqueue_f32 if self._float else host_lib().popsift_c_enqueue_u8
+            job = f(self._h, w, h, img.ctypes.data)
         if not job:
             raise PopSiftError("enqueue refused the image: %s" % host_lib().popsift_c_last_error().decode())
         return job
@@ -647,13 +747,18 @@ class PopSift:
         H.popsift_c_free(f)
         return n
 
-    def get(self, job):
+    def get(self, job, with_sources=False):
+        """(features, descriptors) of a job; with_sources: also the int32 input-record index of every feature (a job
+        enqueued with keypoints; empty for a detector job)."""
         H = host_lib()
         f = H.popsift_c_get(job)
         if not f:
             raise PopSiftError("SiftJob::get failed: %s" % H.popsift_c_last_error().decode())
         ne, no = H.popsift_c_feature_count(f), H.popsift_c_descriptor_count(f)
         feats = np.zeros((ne,), dtype=FEATURE_DTYPE)
+        src = np.zeros((max(H.popsift_c_source_indices(f, None, 0), 0),), np.int32)
+        if len(src):
+            H.popsift_c_source_indices(f, src.ctypes.data, len(src))
         if H.popsift_c_descriptor_format(f) == DESCFMT_U8:
             desc = np.zeros((no, 128), dtype=np.uint8)
             rc = H.popsift_c_copy_u8(f, feats.ctypes.data, desc.ctypes.data)
@@ -663,6 +768,8 @@ class PopSift:
         H.popsift_c_free(f)
         if rc != 0:
             raise PopSiftError("popsift_c_copy failed: %s" % H.popsift_c_last_error().decode())
+        if with_sources:
+            return feats, desc, src
         return feats, desc
 
     def close(self):

@@ -13,6 +13,7 @@
 // round-trips and four device-wide syncs per image).
 #include "psx_internal.h"
 #include "blur_tile_core.h"
+#include "kp_place.h"
 
 #include <atomic>
 #include <cmath>
@@ -205,6 +206,19 @@ struct psx_ctx {
     std::vector<TileLaunch> tile_launches;
     PsxTileJob* d_tile_jobs = nullptr; size_t tile_jobs_cap = 0;
     int  resident_blocks = 1024;       // 4 x tune.cus
+
+    // caller-supplied keypoints (psx_set_keypoints / psx_describe, keypoints.hip)
+    bool pyr_ready = false;            // the pyramid has been (queued to be) built from the current input
+    bool kp_set = false;               // a keypoint list is set (possibly empty)
+    bool kp_results = false;           // the last results are a psx_describe's (psx_keypoint_map)
+    const psx_keypoint* d_kp = nullptr; int kp_n = 0;                // the list of the next psx_describe
+    psx_keypoint* d_kp_own = nullptr;  size_t kp_own_cap = 0;        // device copy of a host list
+    psx_keypoint* h_kp_stage = nullptr; size_t kp_stage_cap = 0;     // pinned staging of that copy
+    hipEvent_t ev_kp = nullptr;        // the DMA out of h_kp_stage has finished
+    int*   d_kp_tbl = nullptr;         size_t kp_tbl_cap = 0;
+    int*   d_kp_src = nullptr;         size_t kp_src_cap = 0;
+    int*   d_kp_gnori = nullptr;       size_t kp_gnori_cap = 0;
+    float* d_kp_gori = nullptr;        size_t kp_gori_cap = 0;
 };
 
 namespace {
@@ -708,6 +722,10 @@ int psx_destroy(psx_ctx* ctx)
     (void)hipFree(ctx->d_extrema); (void)hipFree(ctx->d_features);
     (void)hipFree(ctx->d_desc); (void)hipFree(ctx->d_feat_to_ext); (void)hipFree(ctx->d_ext_nori);
     (void)hipFree(ctx->d_desc_u8);
+    (void)hipFree(ctx->d_kp_own); (void)hipFree(ctx->d_kp_tbl); (void)hipFree(ctx->d_kp_src);
+    (void)hipFree(ctx->d_kp_gnori); (void)hipFree(ctx->d_kp_gori);
+    if (ctx->h_kp_stage) (void)hipHostFree(ctx->h_kp_stage);
+    if (ctx->ev_kp) (void)hipEventDestroy(ctx->ev_kp);
     for (int i = 0; i < 5; i++) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->ev_t0) (void)hipEventDestroy(ctx->ev_t0);
     if (ctx->ev_t1) (void)hipEventDestroy(ctx->ev_t1);
@@ -855,6 +873,7 @@ int psx_resize(psx_ctx* ctx, int w, int h)
     PSX_HIP(hipMemcpy(ctx->d_params, &P, sizeof(P), hipMemcpyHostToDevice));
     ctx->in_w = w; ctx->in_h = h;
     ctx->counts_valid = false;
+    ctx->pyr_ready = false;
     return PSX_OK;
 }
 
@@ -906,6 +925,7 @@ static int upload_common(psx_ctx* ctx, const void* host, int w, int h, int is_fl
     if (src == ctx->h_stage) PSX_HIP(hipEventRecord(ctx->ev_upload, ctx->stream));
     ctx->d_input = ctx->d_input_own;
     ctx->input_is_float = is_float;
+    ctx->pyr_ready = false;
     return PSX_OK;
 }
 
@@ -923,6 +943,7 @@ int psx_set_input_dev(psx_ctx* ctx, const void* dev_ptr, int w, int h, int is_fl
     if (rc != PSX_OK) return rc;
     ctx->d_input = dev_ptr;
     ctx->input_is_float = is_float ? 1 : 0;
+    ctx->pyr_ready = false;
     return PSX_OK;
 }
 
@@ -982,6 +1003,7 @@ int psx_build_pyramid(psx_ctx* ctx)
     const PsxParams& P = ctx->hp;
     const psx_config& c = ctx->cfg;
     ctx->counts_valid = false;
+    ctx->pyr_ready = true; ctx->kp_results = false;
     if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
     // Pyramid::reset_extrema_mgmt, sift_pyramid.cu:364-371
     PSX_HIP(hipMemsetAsync(ctx->d_cnt, 0, CNT_BLOCK + ctx->flow_bytes + sizeof(int) * (size_t)P.num_octaves * PSX_CAND_SUB * 32, ctx->stream));
@@ -1306,8 +1328,119 @@ int psx_extract(psx_ctx* ctx)
     }
     ctx->counts_valid = false;
     ctx->filtered = false;
+    ctx->pyr_ready = true; ctx->kp_results = false;
     snapshot_export(ctx);             // the captured kernels carry the targets attached at capture time; attach drops the graph
     PSX_HIP(hipGraphLaunch(ctx->graph, ctx->stream));
+    return PSX_OK;
+}
+
+static int fetch_counts(psx_ctx* ctx);
+
+// ---- caller-supplied keypoints (keypoints.hip) --------------------------------------------------------------------------
+
+static int set_keypoints_common(psx_ctx* ctx, const psx_keypoint* p, int n, bool on_device)
+{
+    if (!ctx) return PSX_ERR_INVALID;
+    if (n < 0 || (n > 0 && !p)) return fail(ctx, PSX_ERR_INVALID, "psx_set_keypoints: bad list");
+    if (!ctx->d_input || !ctx->d_pyr) return fail(ctx, PSX_ERR_STATE, "psx_set_keypoints: no input image");
+    if (on_device) {
+        if (((uintptr_t)p & 7u) != 0) return fail(ctx, PSX_ERR_INVALID, "psx_set_keypoints_dev: the records must be 8-byte aligned");
+        ctx->d_kp = n > 0 ? p : nullptr; ctx->kp_n = n; ctx->kp_set = true;
+        return PSX_OK;
+    }
+    PSX_HIP(hipSetDevice(ctx->device));
+    if (n > 0) {
+        int rc;
+        if ((size_t)n > ctx->kp_own_cap) {
+            PSX_HIP(hipStreamSynchronize(ctx->stream));       // a describe call in flight may still read the old copy
+            if ((rc = grow(ctx, &ctx->d_kp_own, &ctx->kp_own_cap, (size_t)n + (size_t)n / 4)) != PSX_OK) return rc;
+        }
+        if (!ctx->ev_kp) PSX_HIP(hipEventCreateWithFlags(&ctx->ev_kp, hipEventDisableTiming));
+        else PSX_HIP(hipEventSynchronize(ctx->ev_kp));        // previous DMA out of the staging buffer
+        if ((size_t)n > ctx->kp_stage_cap) {
+            if (ctx->h_kp_stage) PSX_HIP(hipHostFree(ctx->h_kp_stage));
+            ctx->h_kp_stage = nullptr; ctx->kp_stage_cap = 0;
+            PSX_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_kp_stage), ((size_t)n + (size_t)n / 4) * sizeof(psx_keypoint), hipHostMallocDefault));
+            ctx->kp_stage_cap = (size_t)n + (size_t)n / 4;
+        }
+        memcpy(ctx->h_kp_stage, p, (size_t)n * sizeof(psx_keypoint));
+        PSX_HIP(hipMemcpyAsync(ctx->d_kp_own, ctx->h_kp_stage, (size_t)n * sizeof(psx_keypoint), hipMemcpyHostToDevice, ctx->stream));
+        PSX_HIP(hipEventRecord(ctx->ev_kp, ctx->stream));
+    }
+    ctx->d_kp = n > 0 ? ctx->d_kp_own : nullptr; ctx->kp_n = n; ctx->kp_set = true;
+    return PSX_OK;
+}
+
+int psx_set_keypoints(psx_ctx* ctx, const psx_keypoint* host, int n) { return set_keypoints_common(ctx, host, n, false); }
+int psx_set_keypoints_dev(psx_ctx* ctx, const psx_keypoint* dev, int n) { return set_keypoints_common(ctx, dev, n, true); }
+
+int psx_describe(psx_ctx* ctx, int flags)
+{
+    if (!ctx) return PSX_ERR_INVALID;
+    if ((flags & ~PSX_DESCRIBE_REUSE_PYRAMID) != 0) return fail(ctx, PSX_ERR_INVALID, "psx_describe: unknown flag");
+    if (!ctx->d_input || !ctx->d_pyr) return fail(ctx, PSX_ERR_STATE, "psx_describe: no input image");
+    if (!ctx->kp_set) return fail(ctx, PSX_ERR_STATE, "psx_describe: no keypoints set");
+    const bool reuse = (flags & PSX_DESCRIBE_REUSE_PYRAMID) != 0;
+    if (reuse && !ctx->pyr_ready) return fail(ctx, PSX_ERR_STATE, "psx_describe: the context holds no pyramid of the current input");
+    PSX_HIP(hipSetDevice(ctx->device));
+    const PsxParams& P = ctx->hp;
+
+    // side arrays: one entry per extremum that can come out of this list
+    int rc;
+    const size_t side = (size_t)imax(1, imin(ctx->kp_n, P.ext_capacity));
+    const size_t tbl_need = psx_kp_table_ints(P.num_octaves, ctx->kp_n);
+    if (side > ctx->kp_src_cap || tbl_need > ctx->kp_tbl_cap) {
+        PSX_HIP(hipStreamSynchronize(ctx->stream));
+        const size_t room = side + side / 4;
+        if ((rc = grow(ctx, &ctx->d_kp_tbl, &ctx->kp_tbl_cap, tbl_need + tbl_need / 4)) != PSX_OK) return rc;
+        if ((rc = grow(ctx, &ctx->d_kp_src, &ctx->kp_src_cap, room)) != PSX_OK) return rc;
+        if ((rc = grow(ctx, &ctx->d_kp_gnori, &ctx->kp_gnori_cap, room)) != PSX_OK) return rc;
+        if ((rc = grow(ctx, &ctx->d_kp_gori, &ctx->kp_gori_cap, 4 * room)) != PSX_OK) return rc;
+    }
+
+    if (!reuse) {
+        ctx->interleave = false;                   // no detector: the extrema scans are not launched
+        if ((rc = psx_build_pyramid(ctx)) != PSX_OK) return rc;
+    } else {
+        ctx->counts_valid = false;
+        if (ctx->timers) { PSX_HIP(hipEventRecord(ctx->ev[0], ctx->stream)); PSX_HIP(hipEventRecord(ctx->ev[1], ctx->stream)); }
+    }
+    ctx->ext_launched = false;
+    ctx->filtered = false;
+
+    PsxKpGeom g;
+    memset(&g, 0, sizeof(g));
+    psx_kp_geom_scale(&ctx->cfg, &g);
+    g.num_octaves = P.num_octaves;
+    for (int o = 0; o < P.num_octaves; o++) { g.w[o] = P.oct[o].w; g.h[o] = P.oct[o].h; }
+    PsxKpBuffers b;
+    b.kps = ctx->d_kp; b.n = ctx->kp_n;
+    b.tbl = ctx->d_kp_tbl; b.src = ctx->d_kp_src; b.gnori = ctx->d_kp_gnori; b.gori = ctx->d_kp_gori;
+    // every counter the later stages read is written by the injection (ext_ct of all octaves) or by the scan
+    PSX_HIP(psx_launch_kp_inject(ctx->tune, ctx->d_params, ctx->d_cnt, g, b, ctx->stream));
+    if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+    PSX_HIP(psx_launch_orientation(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->stream));
+    PSX_HIP(psx_launch_kp_adopt(ctx->tune, ctx->d_params, b, ctx->stream));
+    snapshot_export(ctx);
+    PSX_HIP(psx_launch_scan(ctx->d_params, ctx->d_cnt, ctx->fx, ctx->stream));
+    if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+    rc = psx_descriptors(ctx);
+    ctx->kp_results = rc == PSX_OK;
+    return rc;
+}
+
+int psx_keypoint_map(psx_ctx* ctx, int* host_src, int capacity, int* count)
+{
+    if (!ctx) return PSX_ERR_INVALID;
+    if (!ctx->kp_results) return fail(ctx, PSX_ERR_STATE, "psx_keypoint_map: the last results are not a psx_describe call's");
+    int rc = fetch_counts(ctx);
+    if (rc != PSX_OK) return rc;
+    const int n = ctx->h_cnt->ext_total;
+    if (count) *count = n;
+    if (host_src) {
+        if (n > capacity) return fail(ctx, PSX_ERR_INVALID, "psx_keypoint_map: output capacity too small");
+        if (n > 0) PSX_HIP(hipMemcpy(host_src, ctx->d_kp_src, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    }
     return PSX_OK;
 }
 

@@ -246,6 +246,23 @@ hipError_t psx_launch_feature_ptrs(const psx_feature* in, psx_feature_dev* out, 
 hipError_t psx_launch_descriptors(const PsxTuning& t, const PsxParams* d_params, const PsxCounters* d_cnt, const PsxExport& x, hipStream_t s);
 hipError_t psx_launch_descriptors_alt(const PsxTuning& t, const PsxParams* d_params, const PsxCounters* d_cnt, int desc_mode, const PsxExport& x, hipStream_t s);
 
+// ---- caller-supplied keypoints (keypoints.hip, kp_place.h) ---------------------------------------------------------------
+struct PsxKpGeom;
+struct PsxKpBuffers {
+    const psx_keypoint* kps; int n;   // device records
+    int*   tbl;                       // psx_kp_table_ints(): octave bases, total, per-chunk per-octave counts
+    int*   src;                       // input index of every extremum (octave-major), min(n, ext_capacity) entries, like the two below
+    int*   gnori;                     // num_ori the record carried (0: the orientation kernel's result stands)
+    float* gori;                      // its orientations, 4 floats per extremum (16-byte aligned)
+};
+size_t     psx_kp_table_ints(int num_octaves, int n);
+void       psx_kp_geom_scale(const psx_config* cfg, PsxKpGeom* g);
+// classify -> offsets -> scatter: fills iext / iext_off / ext_ct / iext_ct and the side arrays from the records
+hipError_t psx_launch_kp_inject(const PsxTuning& t, const PsxParams* d_params, PsxCounters* d_cnt, const PsxKpGeom& g,
+                                const PsxKpBuffers& b, hipStream_t s);
+// behind psx_launch_orientation: given orientations replace the computed ones
+hipError_t psx_launch_kp_adopt(const PsxTuning& t, const PsxParams* d_params, const PsxKpBuffers& b, hipStream_t s);
+
 // ---- multi-level tile kernel (pyramid_tile.hip, blur_tile_core.h): several consecutive levels of an octave per launch ----
 struct PsxTileJob;
 // nt: 512 or 1024 threads per workgroup; lds_bytes: the largest LDS need among the jobs (<= 80 KB: two workgroups per CU at nt = 512)

@@ -142,6 +142,30 @@ SiftJob::SiftJob( int w, int h, const float* imageData )
     _imageData = job_image( imageData, (size_t)w * h * sizeof(float), &_pinned_cap );
 }
 
+namespace {
+// the list a keypoint job describes: negative counts and null lists are empty lists
+std::vector<popsift::Keypoint> job_keypoints( const popsift::Keypoint* kps, int n )
+{
+    static_assert( sizeof(popsift::Keypoint) == sizeof(psx_keypoint), "popsift::Keypoint mirrors psx_keypoint" );
+    if( kps == nullptr || n <= 0 ) return std::vector<popsift::Keypoint>();
+    return std::vector<popsift::Keypoint>( kps, kps + n );
+}
+} // namespace
+
+SiftJob::SiftJob( int w, int h, const unsigned char* imageData, const popsift::Keypoint* kps, int n )
+    : SiftJob( w, h, imageData )
+{
+    _has_kps = true;
+    _kps = job_keypoints( kps, n );
+}
+
+SiftJob::SiftJob( int w, int h, const float* imageData, const popsift::Keypoint* kps, int n )
+    : SiftJob( w, h, imageData )
+{
+    _has_kps = true;
+    _kps = job_keypoints( kps, n );
+}
+
 SiftJob::~SiftJob( )
 {
     if( _pinned_cap ) popsift::pool::put_pinned( _imageData, _pinned_cap ); else free( _imageData );
@@ -347,6 +371,36 @@ SiftJob* PopSift::enqueue( int w, int h, const float* imageData )
     SiftJob* job = new SiftJob( w, h, imageData );
     _impl->queue.push( job );
     return job;
+}
+
+// the keypoint overloads: the checks of the plain ones, then a job that carries the list
+SiftJob* PopSift::enqueueChecked( int w, int h, const void* imageData, bool is_float, const popsift::Keypoint* kps, int n )
+{
+    if( is_float && _image_mode != FloatImages )
+        POP_FATAL( "Image mode error\nE    Cannot load float images into a PopSift pipeline configured for byte images" );
+    if( !is_float && _image_mode != ByteImages )
+        POP_FATAL( "Image mode error\nE    Cannot load byte images into a PopSift pipeline configured for float images" );
+    AllocTest a = testTextureFit( w, h );
+    if( a != AllocTest::Ok ) {
+        cerr << __FILE__ << ":" << __LINE__ << " Image too large" << endl << testTextureFitErrorString( a, w, h );
+        return nullptr;
+    }
+    resolveOctaves( w, h );
+    popsift::pool::DeviceScope pool_of( _device );
+    SiftJob* job = is_float ? new SiftJob( w, h, (const float*)imageData, kps, n )
+                            : new SiftJob( w, h, (const unsigned char*)imageData, kps, n );
+    _impl->queue.push( job );
+    return job;
+}
+
+SiftJob* PopSift::enqueue( int w, int h, const unsigned char* imageData, const popsift::Keypoint* kps, int n )
+{
+    return enqueueChecked( w, h, imageData, false, kps, n );
+}
+
+SiftJob* PopSift::enqueue( int w, int h, const float* imageData, const popsift::Keypoint* kps, int n )
+{
+    return enqueueChecked( w, h, imageData, true, kps, n );
 }
 
 namespace {
@@ -599,6 +653,12 @@ void PopSift::dispatchLoop( )
                 check( s.ctx, psx_upload_u8( s.ctx, job->getData(), job->getWidth(), job->getHeight() ), "psx_upload_u8" );
             }
             const double t2 = pnow();
+            if( job->hasKeypoints() ) {
+                popsift::trace::Range r_ex( "describe (launch chain)" );
+                const std::vector<popsift::Keypoint>& kps = job->getKeypoints();
+                check( s.ctx, psx_set_keypoints( s.ctx, reinterpret_cast<const psx_keypoint*>( kps.data() ), (int)kps.size() ), "psx_set_keypoints" );
+                check( s.ctx, psx_describe( s.ctx, 0 ), "psx_describe" );
+            } else
             { popsift::trace::Range r_ex( "extract (launch chain)" );
               check( s.ctx, psx_extract( s.ctx ), "psx_extract" ); }
             const double t3 = pnow();
@@ -606,6 +666,14 @@ void PopSift::dispatchLoop( )
             if( _proc_mode == popsift::Config::ExtractingMode ) {
                 popsift::trace::Range r_dl( "download descriptors" );              // sift_pyramid.cu:288-319
                 f = bytes_out ? collect_host_bytes( s, p.want_desc, &tf ) : collect_host( s, p.want_desc, &tf );
+                if( job->hasKeypoints() ) {
+                    popsift::FeaturesHost* fh = static_cast<popsift::FeaturesHost*>( f );
+                    std::vector<int>& src = fh->sourceIndices();
+                    src.resize( (size_t)fh->getFeatureCount() );
+                    int nsrc = 0;
+                    try { check( s.ctx, psx_keypoint_map( s.ctx, src.data(), (int)src.size(), &nsrc ), "psx_keypoint_map" ); }
+                    catch( ... ) { delete f; f = nullptr; throw; }
+                }
                 if( _config.getLogMode() == popsift::Config::All ) {      // popsift.cpp:330-338
                     // the reference writes these dumps from its single worker (popsift.cpp:330-338); here PIPE_DEPTH
                     // workers would interleave writes to the same dir-octave / dir-dog / dir-desc files

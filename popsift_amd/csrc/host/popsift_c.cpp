@@ -8,6 +8,7 @@
 #include <cstring>
 #include <exception>
 #include <string>
+#include <vector>
 
 namespace {
 thread_local std::string t_err;
@@ -82,6 +83,28 @@ popsift_c_job* popsift_c_enqueue_f32( popsift_c_handle* h, int w, int hgt, const
 {
     try { return reinterpret_cast<popsift_c_job*>( reinterpret_cast<PopSift*>( h )->enqueue( w, hgt, img ) ); }
     catch( const std::exception& e ) { t_err = e.what(); return nullptr; }
+}
+
+popsift_c_job* popsift_c_enqueue_u8_kp( popsift_c_handle* h, int w, int hgt, const unsigned char* img, const psx_keypoint* kps, int n )
+{
+    static_assert( sizeof(popsift::Keypoint) == sizeof(psx_keypoint), "popsift::Keypoint mirrors psx_keypoint" );
+    try { return reinterpret_cast<popsift_c_job*>( reinterpret_cast<PopSift*>( h )->enqueue( w, hgt, img, reinterpret_cast<const popsift::Keypoint*>( kps ), n ) ); }
+    catch( const std::exception& e ) { t_err = e.what(); return nullptr; }
+}
+
+popsift_c_job* popsift_c_enqueue_f32_kp( popsift_c_handle* h, int w, int hgt, const float* img, const psx_keypoint* kps, int n )
+{
+    try { return reinterpret_cast<popsift_c_job*>( reinterpret_cast<PopSift*>( h )->enqueue( w, hgt, img, reinterpret_cast<const popsift::Keypoint*>( kps ), n ) ); }
+    catch( const std::exception& e ) { t_err = e.what(); return nullptr; }
+}
+
+int popsift_c_source_indices( const popsift_c_features* f, int* out, int capacity )
+{
+    if( f == nullptr ) return -1;
+    const std::vector<int>& src = reinterpret_cast<const popsift::FeaturesHost*>( f )->getSourceIndices();
+    const int n = (int)src.size();
+    if( out != nullptr && n > 0 ) memcpy( out, src.data(), sizeof(int) * (size_t)( n < capacity ? n : capacity ) );
+    return n;
 }
 
 popsift_c_features* popsift_c_get( popsift_c_job* job )

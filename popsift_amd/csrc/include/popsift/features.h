@@ -59,6 +59,7 @@ class FeaturesHost : public FeaturesBase
     size_t       _ori_cap;   // bytes; 0: _ori came from posix_memalign
     bool         _bytes;     // Config::ByteDescriptors: _ori holds bytes, Feature::desc[] are nullptr
     std::vector<int> _desc_idx;   // byte results: descriptor row of (feature, orientation), 4 per feature (psx_feature::desc_idx)
+    std::vector<int> _src_idx;    // results at caller-supplied keypoints: input record of every feature; empty for detector jobs
 
 public:
     FeaturesHost( );
@@ -101,6 +102,12 @@ public:
     void resetBytes( int num_ext, int num_ori );
     inline unsigned char* byteStorage() { return _bytes ? reinterpret_cast<unsigned char*>( _ori ) : nullptr; }
     inline std::vector<int>& byteIndex() { return _desc_idx; }
+
+    /// results of a job enqueued with keypoints: getSourceIndices()[i] = index of the input record feature i came from
+    /// (records the placement rule dropped are absent); empty for detector jobs
+    inline const std::vector<int>& getSourceIndices() const { return _src_idx; }
+    /// internal (PopSift)
+    inline std::vector<int>& sourceIndices() { return _src_idx; }
 
 protected:
     friend class Pyramid;

@@ -32,6 +32,21 @@ namespace popsift
     class FeaturesBase;
     class FeaturesHost;
     class FeaturesDev;
+
+    /// A caller-supplied keypoint: the fields of psx_keypoint (include/popsift_hip.h), in input-image units as a
+    /// Feature reports them.  octave = KeypointAuto lets the library place the keypoint by its sigma; num_ori = 0 lets
+    /// it assign the orientations, 1..4 adopts orientation[] verbatim.
+    enum { KeypointAuto = -1 };
+    struct Keypoint
+    {
+        float xpos;
+        float ypos;
+        float sigma;
+        int   octave;
+        int   lpos;
+        int   num_ori;
+        float orientation[ORIENTATION_MAX_COUNT];
+    };
 } // namespace popsift
 
 class SiftJob
@@ -44,12 +59,17 @@ class SiftJob
     size_t              _pinned_cap;   ///< > 0: _imageData is pinned, GPU-mapped pool memory (direct DMA source)
     bool                _is_float;
     std::exception_ptr  _err;
+    bool                _has_kps = false;          ///< describe _kps instead of running the detector
+    std::vector<popsift::Keypoint> _kps;           ///< deep copy of the caller's keypoints
 
 public:
     /// byte image, value range 0..255
     SiftJob( int w, int h, const unsigned char* imageData );
     /// float image, value range [0..1[
     SiftJob( int w, int h, const float* imageData );
+    /// the same with caller-supplied keypoints (deep-copied; kps may be null when n is 0)
+    SiftJob( int w, int h, const unsigned char* imageData, const popsift::Keypoint* kps, int n );
+    SiftJob( int w, int h, const float* imageData, const popsift::Keypoint* kps, int n );
     ~SiftJob( );
 
     /// deprecated alias of getHost()
@@ -68,6 +88,8 @@ public:
     bool isFloat() const   { return _is_float; }
     const unsigned char* getData() const { return _imageData; }
     bool isPinned() const  { return _pinned_cap != 0; }
+    bool hasKeypoints() const { return _has_kps; }
+    const std::vector<popsift::Keypoint>& getKeypoints() const { return _kps; }
 };
 
 class PopSift
@@ -108,6 +130,11 @@ public:
 
     SiftJob* enqueue( int w, int h, const unsigned char* imageData );
     SiftJob* enqueue( int w, int h, const float* imageData );
+    /// Describe the caller's keypoints instead of running the detector (orientations are assigned where a record
+    /// brings none).  A null or zero-length list yields an empty result.  FeaturesHost::getSourceIndices() maps the
+    /// features back to the records.
+    SiftJob* enqueue( int w, int h, const unsigned char* imageData, const popsift::Keypoint* kps, int n );
+    SiftJob* enqueue( int w, int h, const float* imageData, const popsift::Keypoint* kps, int n );
 
     /// deprecated
     inline void uninit( int /*pipe*/ ) { uninit(); }
@@ -128,6 +155,7 @@ private:
     void start();
     void dispatchLoop();
     void resolveOctaves( int w, int h );
+    SiftJob* enqueueChecked( int w, int h, const void* imageData, bool is_float, const popsift::Keypoint* kps, int n );
 
     std::unique_ptr<Impl> _impl;
     popsift::Config _config;
