@@ -37,6 +37,11 @@ popsift_c_job* popsift_c_enqueue_f32(popsift_c_handle* h, int w, int hgt, const 
  * n records are deep-copied and described; kps NULL or n 0 gives an empty result */
 popsift_c_job* popsift_c_enqueue_u8_kp(popsift_c_handle* h, int w, int hgt, const unsigned char* img, const psx_keypoint* kps, int n);
 popsift_c_job* popsift_c_enqueue_f32_kp(popsift_c_handle* h, int w, int hgt, const float* img, const psx_keypoint* kps, int n);
+/* PopSift::enqueue with a detection mask (psx_set_mask, include/popsift_hip.h): a tight mask_w x mask_h plane of bytes,
+ * non-zero = keypoints allowed, deep-copied.  mask NULL with mask_w = mask_h = 0 runs unmasked.  NULL for a NULL handle
+ * and for a mask whose size is not the image's (refused before a device is touched). */
+popsift_c_job* popsift_c_enqueue_u8_mask(popsift_c_handle* h, int w, int hgt, const unsigned char* img, const unsigned char* mask, int mask_w, int mask_h);
+popsift_c_job* popsift_c_enqueue_f32_mask(popsift_c_handle* h, int w, int hgt, const float* img, const unsigned char* mask, int mask_w, int mask_h);
 /* FeaturesHost::getSourceIndices: the input record of every feature of a keypoint job.  Returns their number (0 for a
  * detector job, -1 for NULL) and copies at most capacity of them into out (may be NULL). */
 int popsift_c_source_indices(const popsift_c_features* f, int* out, int capacity);

@@ -359,6 +359,33 @@ int psx_describe(psx_ctx* ctx, int flags);
  * features.  PSX_ERR_STATE when the last results are not a describe call's.  Synchronises. */
 int psx_keypoint_map(psx_ctx* ctx, int* host_src, int capacity, int* count);
 
+/* ---- detection mask ------------------------------------------------------------------------
+ * A region of interest for the detector (OpenCV's detectAndCompute(image, mask, ...), AliceVision's per-view mask; the
+ * reference has no counterpart).  A mask is a tight w x h plane of bytes, the size of the INPUT image; non-zero means
+ * "keypoints allowed here".  One rule, applied inside the extrema kernels after the contrast and edge tests: a refined
+ * extremum that the feature record will report at (xpos, ypos) is kept iff mask[yi * w + xi] != 0 with
+ *     xi = clamp((int)floorf(xpos + 0.5f), 0, w - 1),   yi = clamp((int)floorf(ypos + 0.5f), 0, h - 1)
+ * in float32 arithmetic ("Detection mask").  A masked-out point takes no slot of the extremum arrays: it
+ * does not count toward max_extrema or toward the grid filter's "int(filter_max_extrema * 1.1) < number of extrema"
+ * test and sees no orientation or descriptor work.
+ *   - Sticky per context: the mask holds until it is replaced or cleared.
+ *   - The size is checked when extrema are searched: psx_find_extrema / psx_extract return PSX_ERR_STATE (the message
+ *     names both sizes) while the mask's w x h differs from the current input's; a mask is never dropped silently.
+ *   - psx_describe IGNORES the mask: the caller chose those points.
+ *   - An all-zero mask gives 0 features and 0 descriptors, and no error.
+ * The host form copies the plane in stream order (the caller's array is free again on return); the device form takes no
+ * copy: the pointer must stay valid, and its contents ordered against psx_stream, until the extraction has been waited
+ * for.  mask == NULL with w == h == 0 clears the mask.  A non-positive size, or NULL with a non-zero size, returns
+ * PSX_ERR_INVALID and leaves the context as it was. */
+int psx_set_mask(psx_ctx* ctx, const unsigned char* host_mask, int w, int h);
+int psx_set_mask_dev(psx_ctx* ctx, const unsigned char* dev_mask, int w, int h);
+
+/* The rule on the host for n reported positions (psx_feature.xpos / ypos): keep_out[i] = 1 where position i is allowed,
+ * else 0.  No device and no context are involved; the extrema kernels and this function call one inline function.
+ * PSX_ERR_INVALID for a NULL mask, a non-positive size, n < 0, or n > 0 with a NULL array. */
+int psx_mask_keep(const unsigned char* mask, int w, int h, const float* xpos, const float* ypos, int n,
+                  unsigned char* keep_out);
+
 /* device_prop_t (common/device_prop.h:23-108): enumeration only; there are no texture limits. */
 int psx_device_count(int* count);
 int psx_device_info(int device, char* name, int name_len, size_t* total_mem, int* compute_units, int* clock_khz);

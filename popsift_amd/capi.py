@@ -94,6 +94,7 @@ SYMBOLS = [
     "psx_quantize_desc", "psx_match_u8",
     "psx_keypoint_bounds", "psx_place_keypoints", "psx_set_keypoints", "psx_set_keypoints_dev", "psx_describe",
     "psx_keypoint_map",
+    "psx_set_mask", "psx_set_mask_dev", "psx_mask_keep",
 ]
 
 DESCFMT_F32 = 0      # PSX_DESCFMT_F32
@@ -156,6 +157,9 @@ def lib():
         L.psx_set_keypoints_dev.argtypes = [vp, vp, C.c_int]
         L.psx_describe.argtypes = [vp, C.c_int]
         L.psx_keypoint_map.argtypes = [vp, vp, C.c_int, ip]
+        L.psx_set_mask.argtypes = [vp, vp, C.c_int, C.c_int]
+        L.psx_set_mask_dev.argtypes = [vp, vp, C.c_int, C.c_int]
+        L.psx_mask_keep.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]
         _LIB = L
     return _LIB
 
@@ -191,6 +195,30 @@ def place_keypoints(cfg, w, h, kps):
     if rc != 0:
         raise PopSiftError("psx_place_keypoints failed (%d)" % rc)
     return octave, lpos
+
+
+def mask_array(mask):
+    """A C-contiguous (h, w) uint8 array of a detection mask given as a 2-D uint8 or bool array (non-zero = allowed)."""
+    m = np.asarray(mask)
+    if m.ndim != 2 or m.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+        raise TypeError("a mask is a 2-D uint8 or bool array")
+    return np.ascontiguousarray(m).view(np.uint8)
+
+
+def mask_keep(mask, xpos, ypos):
+    """psx_mask_keep: the detection mask's rule on the host.  mask: (h, w) uint8 / bool; xpos, ypos: reported positions
+    (psx_feature.xpos / ypos).  Returns a bool array, True where a keypoint at that position is allowed.  No device."""
+    m = mask_array(mask)
+    x = np.ascontiguousarray(xpos, dtype=np.float32).reshape(-1)
+    y = np.ascontiguousarray(ypos, dtype=np.float32).reshape(-1)
+    if len(x) != len(y):
+        raise ValueError("xpos and ypos differ in length")
+    keep = np.zeros((len(x),), np.uint8)
+    rc = lib().psx_mask_keep(m.ctypes.data_as(C.c_void_p), m.shape[1], m.shape[0], x.ctypes.data_as(C.c_void_p),
+                             y.ctypes.data_as(C.c_void_p), len(x), keep.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PopSiftError("psx_mask_keep failed (%d)" % rc)
+    return keep.astype(bool)
 
 
 def match(left, right, device=0):
@@ -372,6 +400,7 @@ class Context:
             raise PopSiftError("psx_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
         self._keep = None
         self._keep_kps = None
+        self._keep_mask = None
 
     def _chk(self, rc):
         if rc != 0:
@@ -450,6 +479,28 @@ class Context:
         arr = keypoints_array(kps)
         self._keep_kps = None
         self._chk(lib().psx_set_keypoints(self._h, arr.ctypes.data_as(C.c_void_p), len(arr)))
+
+    # ---- detection mask -------------------------------------------------------------------------
+    def set_mask(self, mask):
+        """psx_set_mask: mask = (h, w) uint8 / bool numpy array, non-zero = keypoints allowed (copied in stream order),
+        or None to clear.  Sticky: it holds for every later find_extrema / extract until replaced or cleared; its size
+        is checked there against the input's.  describe() ignores it."""
+        self._keep_mask = None
+        if mask is None:
+            self._chk(lib().psx_set_mask(self._h, None, 0, 0))
+            return
+        m = mask_array(mask)
+        self._chk(lib().psx_set_mask(self._h, m.ctypes.data_as(C.c_void_p), m.shape[1], m.shape[0]))
+
+    def set_mask_tensor(self, t):
+        """psx_set_mask_dev: t = contiguous 2-D torch uint8 / bool tensor on this context's device (no copy: it is kept
+        alive here until the mask is replaced or cleared).  Work that writes t on another stream must be ordered against
+        the context's stream (Context.stream) by the caller, as for set_input_tensor."""
+        import torch
+        assert t.is_contiguous() and t.dim() == 2 and t.is_cuda
+        assert t.dtype in (torch.uint8, torch.bool)
+        self._chk(lib().psx_set_mask_dev(self._h, C.c_void_p(t.data_ptr()), t.shape[1], t.shape[0]))
+        self._keep_mask = t
 
     def describe(self, reuse_pyramid=False):
         """psx_describe: orientation (where a record brings none) and descriptors at the keypoints set before."""
@@ -653,7 +704,8 @@ HOST_SYMBOLS = ["popsift_c_create", "popsift_c_destroy", "popsift_c_enqueue_u8",
                 "popsift_c_get", "popsift_c_feature_count", "popsift_c_descriptor_count", "popsift_c_copy",
                 "popsift_c_descriptors", "popsift_c_free", "popsift_c_last_error", "popsift_c_pool_stats",
                 "popsift_c_create_fmt", "popsift_c_descriptor_format", "popsift_c_copy_u8", "popsift_c_descriptor_bytes",
-                "popsift_c_enqueue_u8_kp", "popsift_c_enqueue_f32_kp", "popsift_c_source_indices"]
+                "popsift_c_enqueue_u8_kp", "popsift_c_enqueue_f32_kp", "popsift_c_source_indices",
+                "popsift_c_enqueue_u8_mask", "popsift_c_enqueue_f32_mask"]
 _HOST = None
 
 
@@ -680,6 +732,9 @@ def host_lib():
             getattr(H, n).restype = vp
         for n in ("popsift_c_enqueue_u8_kp", "popsift_c_enqueue_f32_kp"):
             getattr(H, n).argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int]
+            getattr(H, n).restype = vp
+        for n in ("popsift_c_enqueue_u8_mask", "popsift_c_enqueue_f32_mask"):
+            getattr(H, n).argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int]
             getattr(H, n).restype = vp
         H.popsift_c_source_indices.argtypes = [vp, vp, C.c_int]
         H.popsift_c_get.argtypes = [vp]
@@ -721,12 +776,20 @@ class PopSift:
         self._float = float_images
         self._bytes = byte_descriptors
 
-    def enqueue(self, img, keypoints=None):
+    def enqueue(self, img, keypoints=None, mask=None):
         """img: C-contiguous (h, w) numpy array, uint8 or float32 (matching the image mode).  keypoints: None (the
         detector runs) or the records to describe instead (KEYPOINT_DTYPE array or a sequence of Keypoint, may be
-        empty); get_sources() of the result then maps the features back to them."""
+        empty); get_sources() of the result then maps the features back to them.  mask: None or the detection mask of
+        this job, a (h', w') uint8 / bool array (deep-copied; refused when its size is not the image's); a job without
+        one runs unmasked.  Keypoint jobs take no mask (the caller chose those points)."""
         h, w = img.shape
-        if keypoints is not None:
+        if mask is not None:
+            if keypoints is not None:
+                raise ValueError("a job takes keypoints or a mask, not both")
+            m = mask_array(mask)
+            f = host_lib().popsift_c_enqueue_f32_mask if self._float else host_lib().popsift_c_enqueue_u8_mask
+            job = f(self._h, w, h, img.ctypes.data, m.ctypes.data, m.shape[1], m.shape[0])
+        elif keypoints is not None:
             kps = keypoints_array(keypoints)
             f = host_lib().popsift_c_enqueue_f32_kp if self._float else host_lib().popsift_c_enqueue_u8_kp
             job = f(self._h, w, h, img.ctypes.data, kps.ctypes.data, len(kps))

@@ -14,6 +14,7 @@
 #include "psx_internal.h"
 #include "blur_tile_core.h"
 #include "kp_place.h"
+#include "mask_rule.h"
 
 #include <atomic>
 #include <cmath>
@@ -219,6 +220,13 @@ struct psx_ctx {
     int*   d_kp_src = nullptr;         size_t kp_src_cap = 0;
     int*   d_kp_gnori = nullptr;       size_t kp_gnori_cap = 0;
     float* d_kp_gori = nullptr;        size_t kp_gori_cap = 0;
+
+    // detection mask (psx_set_mask / psx_set_mask_dev, mask_rule.h): sticky until replaced or cleared
+    const unsigned char* d_mask = nullptr; int mask_w = 0, mask_h = 0;   // the mask in force (nullptr: none)
+    unsigned char* d_mask_own = nullptr;  size_t mask_own_cap = 0;      // device copy of a host mask (bytes)
+    unsigned char* h_mask_stage = nullptr; size_t mask_stage_cap = 0;   // pinned staging of that copy
+    hipEvent_t ev_mask = nullptr;      // the DMA out of h_mask_stage has finished
+    const unsigned char* graph_mask = nullptr;                          // the mask the captured graph's kernels carry
 };
 
 namespace {
@@ -233,6 +241,17 @@ PsxExport export_of(const psx_ctx* c)
     x.desc_u8 = bytes ? c->d_desc_u8 : nullptr;
     x.xdesc_u8 = bytes ? c->x_dev_u8 : nullptr;
     return x;
+}
+inline PsxMask mask_of(const psx_ctx* c) { return PsxMask{c->d_mask, c->mask_w, c->mask_h}; }
+// PSX_OK, or PSX_ERR_STATE when a mask is set whose size is not the current input's (never dropped silently)
+int fail(psx_ctx* c, int code, const std::string& msg);
+int check_mask(psx_ctx* c, const char* who)
+{
+    if (!c->d_mask || (c->mask_w == c->in_w && c->mask_h == c->in_h)) return PSX_OK;
+    char buf[256];
+    snprintf(buf, sizeof(buf), "%s: the detection mask is %d x %d but the input image is %d x %d", who, c->mask_w, c->mask_h,
+             c->in_w, c->in_h);
+    return fail(c, PSX_ERR_STATE, buf);
 }
 inline bool exporting(const psx_ctx* c) { return c->x_dev_feat != nullptr || c->x_dev_desc != nullptr || c->x_dev_u8 != nullptr; }
 inline void snapshot_export(psx_ctx* c)
@@ -726,6 +745,9 @@ int psx_destroy(psx_ctx* ctx)
     (void)hipFree(ctx->d_kp_gnori); (void)hipFree(ctx->d_kp_gori);
     if (ctx->h_kp_stage) (void)hipHostFree(ctx->h_kp_stage);
     if (ctx->ev_kp) (void)hipEventDestroy(ctx->ev_kp);
+    (void)hipFree(ctx->d_mask_own);
+    if (ctx->h_mask_stage) (void)hipHostFree(ctx->h_mask_stage);
+    if (ctx->ev_mask) (void)hipEventDestroy(ctx->ev_mask);
     for (int i = 0; i < 5; i++) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->ev_t0) (void)hipEventDestroy(ctx->ev_t0);
     if (ctx->ev_t1) (void)hipEventDestroy(ctx->ev_t1);
@@ -977,7 +999,7 @@ static int launch_extrema_set(psx_ctx* ctx, const int* octaves, int n)
 {
     for (int i = 0; i < n; i += PSX_EXT_BATCH) {
         const int m = n - i < PSX_EXT_BATCH ? n - i : PSX_EXT_BATCH;
-        PSX_HIP(psx_launch_extrema_batch(ctx->d_params, ctx->hp, ctx->d_cnt, octaves + i, m, ctx->stream));
+        PSX_HIP(psx_launch_extrema_batch(ctx->d_params, ctx->hp, ctx->d_cnt, octaves + i, m, mask_of(ctx), ctx->stream));
     }
     return PSX_OK;
 }
@@ -990,7 +1012,7 @@ static int scan_or_defer(psx_ctx* ctx, int o, int* deferred, int* ndef)
     if (psx_extrema_tiles(ctx->hp, o) < ctx->resident_blocks) { deferred[(*ndef)++] = o; return PSX_OK; }
     const bool px = ctx->blur_probe && o == 0;
     if (px) PSX_HIP(hipEventRecord(ctx->ev_x[2], ctx->stream));
-    PSX_HIP(psx_launch_extrema(ctx->d_params, ctx->hp, ctx->d_cnt, o, ctx->stream));
+    PSX_HIP(psx_launch_extrema(ctx->d_params, ctx->hp, ctx->d_cnt, o, mask_of(ctx), ctx->stream));
     if (px) { PSX_HIP(hipEventRecord(ctx->ev_x[3], ctx->stream)); ctx->probe_ext0 = true; }
     return PSX_OK;
 }
@@ -1022,7 +1044,7 @@ int psx_build_pyramid(psx_ctx* ctx)
         q.user = ctx;
         q.after_octave = ctx->interleave ? +[](void* u, int o) -> hipError_t {
             psx_ctx* cx = static_cast<psx_ctx*>(u);
-            return psx_launch_extrema(cx->d_params, cx->hp, cx->d_cnt, o, cx->stream);
+            return psx_launch_extrema(cx->d_params, cx->hp, cx->d_cnt, o, mask_of(cx), cx->stream);
         } : nullptr;
         ctx->ext_launched = false;
         int probe_hit = 0;
@@ -1224,6 +1246,7 @@ int psx_find_extrema(psx_ctx* ctx)
 {
     if (!ctx) return PSX_ERR_INVALID;
     if (!ctx->d_pyr) return fail(ctx, PSX_ERR_STATE, "psx_find_extrema: no pyramid");
+    { const int mrc = check_mask(ctx, "psx_find_extrema"); if (mrc != PSX_OK) return mrc; }
     PSX_HIP(hipSetDevice(ctx->device));
     if (!ctx->ext_launched) {
         int small[PSX_MAX_OCTAVES], ns = 0;
@@ -1234,7 +1257,7 @@ int psx_find_extrema(psx_ctx* ctx)
         if (ns > 0) { int rc = launch_extrema_set(ctx, small, ns); if (rc != PSX_OK) return rc; }
     }
     ctx->ext_launched = false;
-    PSX_HIP(psx_launch_refine(ctx->d_params, ctx->hp, ctx->d_cnt, ctx->stream));
+    PSX_HIP(psx_launch_refine(ctx->d_params, ctx->hp, ctx->d_cnt, mask_of(ctx), ctx->stream));
     ctx->filtered = false;
     if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
     return PSX_OK;
@@ -1290,6 +1313,7 @@ int psx_extract(psx_ctx* ctx)
 {
     if (!ctx) return PSX_ERR_INVALID;
     if (!ctx->d_input || !ctx->d_pyr) return fail(ctx, PSX_ERR_STATE, "psx_extract: no input image");
+    { const int mrc = check_mask(ctx, "psx_extract"); if (mrc != PSX_OK) return mrc; }
     if (ctx->tune.null_device_work != 0) {
         if (ctx->null_primed) {                    // measurement: no kernels; the first frame's results stand in
             if (ctx->tune.null_device_work == 1) ctx->counts_valid = false;      // mode 1 reads the counters back per frame, like a real frame
@@ -1304,7 +1328,7 @@ int psx_extract(psx_ctx* ctx)
     if (!use_graph) return extract_chain(ctx);
     PSX_HIP(hipSetDevice(ctx->device));
     if (ctx->graph && (ctx->graph_input != ctx->d_input || ctx->graph_is_float != ctx->input_is_float ||
-                       ctx->graph_w != ctx->in_w || ctx->graph_h != ctx->in_h))
+                       ctx->graph_w != ctx->in_w || ctx->graph_h != ctx->in_h || ctx->graph_mask != ctx->d_mask))
         drop_graph(ctx);
     if (!ctx->graph) {
         hipGraph_t g = nullptr;
@@ -1325,6 +1349,7 @@ int psx_extract(psx_ctx* ctx)
         (void)hipGraphDestroy(g);
         ctx->graph_input = ctx->d_input; ctx->graph_is_float = ctx->input_is_float;
         ctx->graph_w = ctx->in_w; ctx->graph_h = ctx->in_h;
+        ctx->graph_mask = ctx->d_mask;
     }
     ctx->counts_valid = false;
     ctx->filtered = false;
@@ -1427,6 +1452,55 @@ int psx_describe(psx_ctx* ctx, int flags)
     rc = psx_descriptors(ctx);
     ctx->kp_results = rc == PSX_OK;
     return rc;
+}
+
+// ---- detection mask (mask_rule.h) ---------------------------------------------------------------------------------------
+
+static int set_mask_common(psx_ctx* ctx, const unsigned char* p, int w, int h, bool on_device)
+{
+    if (!ctx) return PSX_ERR_INVALID;
+    const char* who = on_device ? "psx_set_mask_dev" : "psx_set_mask";
+    if (!p) {
+        if (w != 0 || h != 0) return fail(ctx, PSX_ERR_INVALID, std::string(who) + ": a null mask with a non-zero size");
+        ctx->d_mask = nullptr; ctx->mask_w = 0; ctx->mask_h = 0;         // cleared
+        return PSX_OK;
+    }
+    if (w <= 0 || h <= 0) return fail(ctx, PSX_ERR_INVALID, std::string(who) + ": non-positive mask size");
+    if (on_device) {
+        ctx->d_mask = p; ctx->mask_w = w; ctx->mask_h = h;
+        return PSX_OK;
+    }
+    PSX_HIP(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)w * (size_t)h;
+    if (bytes > ctx->mask_own_cap) {
+        PSX_HIP(hipStreamSynchronize(ctx->stream));           // an extraction in flight may still read the old plane
+        int rc;
+        if ((rc = grow(ctx, &ctx->d_mask_own, &ctx->mask_own_cap, bytes)) != PSX_OK) return rc;
+    }
+    if (!ctx->ev_mask) PSX_HIP(hipEventCreateWithFlags(&ctx->ev_mask, hipEventDisableTiming));
+    else PSX_HIP(hipEventSynchronize(ctx->ev_mask));          // previous DMA out of the staging buffer
+    if (bytes > ctx->mask_stage_cap) {
+        if (ctx->h_mask_stage) PSX_HIP(hipHostFree(ctx->h_mask_stage));
+        ctx->h_mask_stage = nullptr; ctx->mask_stage_cap = 0;
+        PSX_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_mask_stage), bytes, hipHostMallocDefault));
+        ctx->mask_stage_cap = bytes;
+    }
+    memcpy(ctx->h_mask_stage, p, bytes);
+    PSX_HIP(hipMemcpyAsync(ctx->d_mask_own, ctx->h_mask_stage, bytes, hipMemcpyHostToDevice, ctx->stream));
+    PSX_HIP(hipEventRecord(ctx->ev_mask, ctx->stream));
+    ctx->d_mask = ctx->d_mask_own; ctx->mask_w = w; ctx->mask_h = h;
+    return PSX_OK;
+}
+
+int psx_set_mask(psx_ctx* ctx, const unsigned char* host, int w, int h) { return set_mask_common(ctx, host, w, h, false); }
+int psx_set_mask_dev(psx_ctx* ctx, const unsigned char* dev, int w, int h) { return set_mask_common(ctx, dev, w, h, true); }
+
+int psx_mask_keep(const unsigned char* mask, int w, int h, const float* xpos, const float* ypos, int n, unsigned char* keep_out)
+{
+    if (!mask || w <= 0 || h <= 0 || n < 0) return PSX_ERR_INVALID;
+    if (n > 0 && (!xpos || !ypos || !keep_out)) return PSX_ERR_INVALID;
+    for (int i = 0; i < n; i++) keep_out[i] = psx_mask_allows(mask, w, h, xpos[i], ypos[i]) ? 1 : 0;
+    return PSX_OK;
 }
 
 int psx_keypoint_map(psx_ctx* ctx, int* host_src, int capacity, int* count)
@@ -1963,7 +2037,8 @@ int psx_time_blur(psx_ctx* ctx, int octave, int level, int reps, float* avg_ms, 
 #ifdef PSX_PHASE_TIMING
 int psx_debug_launch_extrema(psx_ctx* ctx, int o)
 {
-    PSX_HIP(psx_launch_extrema(ctx->d_params, ctx->hp, ctx->d_cnt, o, ctx->stream));
+    { const int mrc = check_mask(ctx, "psx_debug_launch_extrema"); if (mrc != PSX_OK) return mrc; }
+    PSX_HIP(psx_launch_extrema(ctx->d_params, ctx->hp, ctx->d_cnt, o, mask_of(ctx), ctx->stream));
     return PSX_OK;
 }
 #endif

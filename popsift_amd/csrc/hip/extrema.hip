@@ -11,6 +11,7 @@
 // DoG).  Survivors are compacted with a 64-bit wave ballot and one atomicAdd per wave (wave64
 // re-design of extrema_count, s_extrema.cu:22-44).
 #include "psx_internal.h"
+#include "mask_rule.h"
 
 namespace {
 
@@ -111,10 +112,11 @@ struct DogView {
     }
 };
 
-// find_extrema_in_dog_sub after the extremum test, s_extrema.cu:341-503
-template <int MODE>
+// find_extrema_in_dog_sub after the extremum test, s_extrema.cu:341-503.  MASKED: the detection mask (mask_rule.h) is the
+// last test, so a masked-out point takes no slot; the unmasked instantiation carries no trace of it.
+template <int MODE, bool MASKED>
 __device__ bool refine(const PsxParams* P, const DogView& dv, int octave, int x, int y, int level,
-                       float val, psx_iext& ec)
+                       float val, const PsxMask& mk, psx_iext& ec)
 {
     const PsxOctave& oc = dv.oc;
     const int width = oc.w, height = oc.h;
@@ -177,6 +179,10 @@ __device__ bool refine(const PsxParams* P, const DogView& dv, int octave, int x,
     if (det <= 0.0f) return false;
     if (fabsf(contr) < 2.0f * thr) return false;
     if (edgeval >= (P->edge_limit + 1.0f) * (P->edge_limit + 1.0f) / P->edge_limit) return false;
+    if (MASKED) {
+        const float s = psx_mask_scale(octave, P->up_fac);
+        if (!psx_mask_allows(mk.data, mk.w, mk.h, xn * s, yn * s)) return false;
+    }
 
     ec.xpos  = xn;
     ec.ypos  = yn;
@@ -194,8 +200,8 @@ __device__ long long* g_dbg = nullptr;
 #define STAMP(i)
 #endif
 
-template <int MODE>
-__global__ __launch_bounds__(NT) void k_extrema(const PsxParams* __restrict__ P, PsxCounters* cnt, const PsxExtBatch b)
+template <int MODE, bool MASKED>
+__global__ __launch_bounds__(NT) void k_extrema(const PsxParams* __restrict__ P, PsxCounters* cnt, const PsxExtBatch b, const PsxMask mk)
 {
     STAMP(0);
     // the tiles of up to PSX_EXT_BATCH octaves share the launch (the small octaves: 36 .. 510 tiles each would be
@@ -402,7 +408,7 @@ __global__ __launch_bounds__(NT) void k_extrema(const PsxParams* __restrict__ P,
                 const DogView dv{oc, sD, NL, tx0, ty0};
                 const float v = sD[(z * THP + ly + 1) * TWP + cx + 1];
                 psx_iext ec;
-                if (refine<MODE>(P, dv, octave, tx0 + cx, ty0 + ly, z, v, ec)) {
+                if (refine<MODE, MASKED>(P, dv, octave, tx0 + cx, ty0 + ly, z, v, mk, ec)) {
                     const int o = atomicAdd(&cnt->ext_ct[octave], 1);
                     if (o < P->max_extrema) { P->iext[octave][o] = ec; P->iext_off[octave][o] = o; }
                 }
@@ -428,8 +434,8 @@ __global__ __launch_bounds__(NT) void k_extrema(const PsxParams* __restrict__ P,
 // 0.081 / 0.082 / 0.085 ms, the kernel 21.6 -> 17.2 us (profiles/r05_refine_ab.txt).  What is left is the chain itself.
 constexpr int REFINE_NT = 512;
 
-template <int MODE>
-__global__ __launch_bounds__(REFINE_NT) void k_refine(const PsxParams* __restrict__ P, PsxCounters* cnt)
+template <int MODE, bool MASKED>
+__global__ __launch_bounds__(REFINE_NT) void k_refine(const PsxParams* __restrict__ P, PsxCounters* cnt, const PsxMask mk)
 {
     constexpr int NW = REFINE_NT / PSX_WAVE;
     __shared__ int s_cnt[NW], s_base;
@@ -450,7 +456,7 @@ __global__ __launch_bounds__(REFINE_NT) void k_refine(const PsxParams* __restric
             const unsigned long long code = list[e];
             const int x = (int)(code & 0xffffffu), z = (int)((code >> 24) & 0xffu), y = (int)(code >> 32);
             const float v = rdog(oc, NL, x, y, z);
-            ok = refine<MODE>(P, dv, o, x, y, z, v, ec);
+            ok = refine<MODE, MASKED>(P, dv, o, x, y, z, v, mk, ec);
         }
         const unsigned long long mask = __ballot(ok);
         if (lane == 0) s_cnt[wave] = __popcll(mask);
@@ -479,8 +485,31 @@ __global__ __launch_bounds__(REFINE_NT) void k_refine(const PsxParams* __restric
 extern "C" void psx_debug_set_buffer(long long* d) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_dbg), &d, sizeof(d)); }
 #endif
 
+// the kernels' instantiation for (sift mode, mask in force)
+template <bool MASKED>
+static hipError_t launch_extrema_t(const PsxParams* d_params, const PsxParams& hp, PsxCounters* d_cnt, const PsxExtBatch& b,
+                                   const PsxMask& mk, dim3 grid, dim3 block, size_t smem, hipStream_t s)
+{
+    // levels >= 7 need more than the 64 KiB of dynamic LDS a kernel gets by default (72..107 KB of the 160 KB per CU)
+    if (smem > 64 * 1024) {
+        hipError_t e = hipSuccess;
+        switch (hp.sift_mode) {
+        case PSX_MODE_VLFEAT: e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_extrema<PSX_MODE_VLFEAT, MASKED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); break;
+        case PSX_MODE_OPENCV: e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_extrema<PSX_MODE_OPENCV, MASKED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); break;
+        default:              e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_extrema<PSX_MODE_POPSIFT, MASKED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); break;
+        }
+        if (e != hipSuccess) return e;
+    }
+    switch (hp.sift_mode) {
+    case PSX_MODE_VLFEAT: hipLaunchKernelGGL((k_extrema<PSX_MODE_VLFEAT, MASKED>), grid, block, smem, s, d_params, d_cnt, b, mk); break;
+    case PSX_MODE_OPENCV: hipLaunchKernelGGL((k_extrema<PSX_MODE_OPENCV, MASKED>), grid, block, smem, s, d_params, d_cnt, b, mk); break;
+    default:              hipLaunchKernelGGL((k_extrema<PSX_MODE_POPSIFT, MASKED>), grid, block, smem, s, d_params, d_cnt, b, mk); break;
+    }
+    return hipGetLastError();
+}
+
 hipError_t psx_launch_extrema_batch(const PsxParams* d_params, const PsxParams& hp, PsxCounters* d_cnt,
-                                    const int* octaves, int n, hipStream_t s)
+                                    const int* octaves, int n, const PsxMask& mk, hipStream_t s)
 {
     const int NL = hp.L - 1, NZ = hp.L - 3;
     if (NZ < 1 || n < 1) return hipSuccess;
@@ -498,28 +527,14 @@ hipError_t psx_launch_extrema_batch(const PsxParams* d_params, const PsxParams& 
     }
     const size_t smem = sizeof(float) * (size_t)NL * THP * TWP + sizeof(unsigned short) * (size_t)NZ * QCAP;
     const dim3 grid(tiles), block(NT);
-    // levels >= 7 need more than the 64 KiB of dynamic LDS a kernel gets by default (72..107 KB of the 160 KB per CU)
-    if (smem > 64 * 1024) {
-        hipError_t e = hipSuccess;
-        switch (hp.sift_mode) {
-        case PSX_MODE_VLFEAT: e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_extrema<PSX_MODE_VLFEAT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); break;
-        case PSX_MODE_OPENCV: e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_extrema<PSX_MODE_OPENCV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); break;
-        default:              e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_extrema<PSX_MODE_POPSIFT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); break;
-        }
-        if (e != hipSuccess) return e;
-    }
-    switch (hp.sift_mode) {
-    case PSX_MODE_VLFEAT: hipLaunchKernelGGL(k_extrema<PSX_MODE_VLFEAT>, grid, block, smem, s, d_params, d_cnt, b); break;
-    case PSX_MODE_OPENCV: hipLaunchKernelGGL(k_extrema<PSX_MODE_OPENCV>, grid, block, smem, s, d_params, d_cnt, b); break;
-    default:              hipLaunchKernelGGL(k_extrema<PSX_MODE_POPSIFT>, grid, block, smem, s, d_params, d_cnt, b); break;
-    }
-    return hipGetLastError();
+    return mk.data ? launch_extrema_t<true>(d_params, hp, d_cnt, b, mk, grid, block, smem, s)
+                   : launch_extrema_t<false>(d_params, hp, d_cnt, b, mk, grid, block, smem, s);
 }
 
 hipError_t psx_launch_extrema(const PsxParams* d_params, const PsxParams& hp, PsxCounters* d_cnt,
-                              int octave, hipStream_t s)
+                              int octave, const PsxMask& mk, hipStream_t s)
 {
-    return psx_launch_extrema_batch(d_params, hp, d_cnt, &octave, 1, s);
+    return psx_launch_extrema_batch(d_params, hp, d_cnt, &octave, 1, mk, s);
 }
 
 // tiles of one octave (what decides whether its scan is worth a launch of its own)
@@ -529,14 +544,22 @@ int psx_extrema_tiles(const PsxParams& hp, int octave)
     return ((oc.w + ETW - 1) / ETW) * ((oc.h + ETH - 1) / ETH);
 }
 
-hipError_t psx_launch_refine(const PsxParams* d_params, const PsxParams& hp, PsxCounters* d_cnt, hipStream_t s)
+template <bool MASKED>
+static hipError_t launch_refine_t(const PsxParams* d_params, const PsxParams& hp, PsxCounters* d_cnt, const PsxMask& mk,
+                                  dim3 grid, dim3 block, hipStream_t s)
+{
+    switch (hp.sift_mode) {
+    case PSX_MODE_VLFEAT: hipLaunchKernelGGL((k_refine<PSX_MODE_VLFEAT, MASKED>), grid, block, 0, s, d_params, d_cnt, mk); break;
+    case PSX_MODE_OPENCV: hipLaunchKernelGGL((k_refine<PSX_MODE_OPENCV, MASKED>), grid, block, 0, s, d_params, d_cnt, mk); break;
+    default:              hipLaunchKernelGGL((k_refine<PSX_MODE_POPSIFT, MASKED>), grid, block, 0, s, d_params, d_cnt, mk); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t psx_launch_refine(const PsxParams* d_params, const PsxParams& hp, PsxCounters* d_cnt, const PsxMask& mk, hipStream_t s)
 {
     if (hp.L - 3 < 1) return hipSuccess;
     const dim3 grid(hp.num_octaves * PSX_CAND_SUB), block(REFINE_NT);
-    switch (hp.sift_mode) {
-    case PSX_MODE_VLFEAT: hipLaunchKernelGGL(k_refine<PSX_MODE_VLFEAT>, grid, block, 0, s, d_params, d_cnt); break;
-    case PSX_MODE_OPENCV: hipLaunchKernelGGL(k_refine<PSX_MODE_OPENCV>, grid, block, 0, s, d_params, d_cnt); break;
-    default:              hipLaunchKernelGGL(k_refine<PSX_MODE_POPSIFT>, grid, block, 0, s, d_params, d_cnt); break;
-    }
-    return hipGetLastError();
+    return mk.data ? launch_refine_t<true>(d_params, hp, d_cnt, mk, grid, block, s)
+                   : launch_refine_t<false>(d_params, hp, d_cnt, mk, grid, block, s);
 }

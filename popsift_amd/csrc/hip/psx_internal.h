@@ -226,12 +226,14 @@ hipError_t psx_launch_dog(const float* a, const float* b, float* d, int W, int H
 // k_extrema scans the tiles of up to PSX_EXT_BATCH octaves in one launch
 #define PSX_EXT_BATCH 4
 struct PsxExtBatch { int n; int octave[PSX_EXT_BATCH]; int tiles_x[PSX_EXT_BATCH]; int tile_end[PSX_EXT_BATCH]; };
+// mk: the detection mask in force (mask_rule.h); mk.data == nullptr launches the unmasked instantiation
+struct PsxMask;
 hipError_t psx_launch_extrema_batch(const PsxParams* d_params, const PsxParams& h_params, PsxCounters* d_cnt,
-                                    const int* octaves, int n, hipStream_t s);
+                                    const int* octaves, int n, const PsxMask& mk, hipStream_t s);
 int psx_extrema_tiles(const PsxParams& h_params, int octave);
 hipError_t psx_launch_extrema(const PsxParams* d_params, const PsxParams& h_params, PsxCounters* d_cnt,
-                              int octave, hipStream_t s);
-hipError_t psx_launch_refine(const PsxParams* d_params, const PsxParams& h_params, PsxCounters* d_cnt, hipStream_t s);
+                              int octave, const PsxMask& mk, hipStream_t s);
+hipError_t psx_launch_refine(const PsxParams* d_params, const PsxParams& h_params, PsxCounters* d_cnt, const PsxMask& mk, hipStream_t s);
 // grid filter (gridfilter.hip)
 size_t     psx_gridfilter_scratch_ints(int grid_size);
 hipError_t psx_gridfilter_sort_bytes(int total, size_t* bytes);

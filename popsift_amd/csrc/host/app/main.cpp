@@ -24,6 +24,7 @@
 #include <queue>
 #include <string>
 #include <vector>
+#include <cstdio>
 #include <cstdlib>
 
 using namespace std;
@@ -34,6 +35,9 @@ static bool write_as_uchar  = false;
 static bool dont_write      = false;
 static bool float_mode      = false;
 static std::vector<int> device_list;          // one PopSift replica per entry (popsift.h:158,166-168); default: device 0
+static string mask_file;                      // --mask: a detection mask applied to every input image
+static std::vector<unsigned char> mask_data;  // its plane, mask_w x mask_h bytes, non-zero = keypoints allowed
+static int mask_w = 0, mask_h = 0;
 
 static void parseargs( int argc, char** argv, popsift::Config& config, string& inputFile )
 {
@@ -52,6 +56,9 @@ static void parseargs( int argc, char** argv, popsift::Config& config, string& i
     // is written from the bytes (the --write-as-uchar line format)
     all.flag( "uchar-descriptors", 0, "Extract byte descriptors (roundf, saturated at 255) and write them as integers",
               [&]() { config.setDescriptorFormat( popsift::Config::ByteDescriptors ); } );
+    // not in the reference tool: a detection mask (PopSift::enqueue with a popsift::Mask)
+    all.add( "mask", 0, true, "Detection mask: an 8-bit grey PGM (P2 / P5) of the input's size, non-zero = keypoints allowed",
+             [&]( const string& s ) { if( s.empty() ) throw runtime_error( "--mask needs a file name" ); mask_file = s; } );
     all.flag( "pgmread-loading", 0, "Use the PGM/PPM loader (the only loader of this build)", []() {} );
     all.flag( "float-mode", 0, "Upload image to GPU as float instead of byte", [&]() { float_mode = true; } );
     // not in the reference tool: several replicas in one process, image i goes to replica i mod N (BASELINE config 4)
@@ -104,19 +111,65 @@ static void collectFilenames( list<string>& inputFiles, const string& dir )
     }
 }
 
+// type (2, 3, 5, 6), size and maxval of a PGM / PPM file from its three header lines (pgmread.cpp); false when unreadable
+static bool pgm_header( const string& file, int& type, int& w, int& h, int& maxval )
+{
+    ifstream f( file.c_str(), ios::binary );
+    string fields[3];
+    for( int k = 0; k < 3; ) {
+        string line;
+        if( !getline( f, line ) ) return false;
+        const size_t b = line.find_first_not_of( " \t\r" );
+        if( b == string::npos || line[b] == '#' ) { if( k == 0 && b == string::npos ) return false; continue; }
+        fields[k++] = line.substr( b );
+    }
+    if( fields[0].size() < 2 || fields[0][0] != 'P' || fields[0][1] < '2' || fields[0][1] > '6' || fields[0][1] == '4' ) return false;
+    type = fields[0][1] - '0';
+    return sscanf( fields[1].c_str(), "%d %d", &w, &h ) == 2 && sscanf( fields[2].c_str(), "%d", &maxval ) == 1;
+}
+
+// --mask: 8-bit grey only, then every input must have the mask's size -- checked from the file headers, before a device
+// is touched.  false (after a message on stderr) when the mask cannot be used.
+static bool load_mask( const list<string>& inputFiles )
+{
+    int type = 0, maxval = 0;
+    if( !pgm_header( mask_file, type, mask_w, mask_h, maxval ) ) {
+        cerr << "Error: the mask " << mask_file << " is not a readable PGM file" << endl;
+        return false;
+    }
+    if( ( type != 2 && type != 5 ) || maxval < 1 || maxval > 255 ) {
+        cerr << "Error: the mask " << mask_file << " must be an 8-bit grey PGM (P2 or P5, maxval <= 255)" << endl;
+        return false;
+    }
+    unsigned char* m = readPGMfile( mask_file, mask_w, mask_h );
+    if( m == nullptr ) return false;
+    mask_data.assign( m, m + (size_t)mask_w * mask_h );
+    delete[] m;
+    for( const string& f : inputFiles ) {
+        int t = 0, w = 0, h = 0, mv = 0;
+        if( pgm_header( f, t, w, h, mv ) && ( w != mask_w || h != mask_h ) ) {
+            cerr << "Error: the mask " << mask_file << " is " << mask_w << " x " << mask_h << " but the image " << f
+                 << " is " << w << " x " << h << endl;
+            return false;
+        }
+    }
+    return true;
+}
+
 static SiftJob* process_image( const string& inputFile, PopSift& sift )
 {
     int w = 0, h = 0;
     unsigned char* image_data = readPGMfile( inputFile, w, h );
     if( image_data == nullptr ) exit( EXIT_FAILURE );
     cout << "Loading " << w << " x " << h << " image " << inputFile << endl;
+    const popsift::Mask mask = mask_data.empty() ? popsift::Mask{ nullptr, 0, 0 } : popsift::Mask{ mask_data.data(), mask_w, mask_h };
     SiftJob* job;
     if( !float_mode ) {
-        job = sift.enqueue( w, h, image_data );
+        job = sift.enqueue( w, h, image_data, mask );         // a mask of another size is refused (runtime_error)
     } else {
         float* f = new float[(size_t)w * h];
         for( size_t i = 0; i < (size_t)w * h; i++ ) f[i] = float( image_data[i] ) / 256.0f;       // main.cpp:241-245
-        job = sift.enqueue( w, h, f );
+        try { job = sift.enqueue( w, h, f, mask ); } catch( ... ) { delete[] f; delete[] image_data; throw; }
         delete[] f;
     }
     delete[] image_data;
@@ -160,6 +213,8 @@ int main( int argc, char** argv )
         cout << "Input file is neither regular file nor directory, nothing to do" << endl;
         return EXIT_FAILURE;
     }
+
+    if( !mask_file.empty() && !load_mask( inputFiles ) ) return EXIT_FAILURE;
 
     if( device_list.empty() ) device_list.push_back( 0 );
     popsift::cuda::device_prop_t deviceInfo;

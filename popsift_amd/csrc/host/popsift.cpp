@@ -166,8 +166,37 @@ SiftJob::SiftJob( int w, int h, const float* imageData, const popsift::Keypoint*
     _kps = job_keypoints( kps, n );
 }
 
+namespace {
+// a mask that can go with a w x h image: none at all, or a plane of exactly that size
+void check_mask( int w, int h, const popsift::Mask& mask )
+{
+    if( mask.data == nullptr && mask.w == 0 && mask.h == 0 ) return;
+    if( mask.data == nullptr || mask.w != w || mask.h != h ) {
+        std::ostringstream o;
+        o << "Mask size error\nE    The detection mask is " << mask.w << " x " << mask.h
+          << ( mask.data == nullptr ? " (null plane)" : "" ) << " but the image is " << w << " x " << h;
+        POP_FATAL( o.str() );
+    }
+}
+} // namespace
+
+SiftJob::SiftJob( int w, int h, const unsigned char* imageData, const popsift::Mask& mask )
+    : SiftJob( w, h, imageData )
+{
+    check_mask( w, h, mask );
+    if( mask.data != nullptr ) _mask = job_image( mask.data, (size_t)w * h, &_mask_pinned_cap );
+}
+
+SiftJob::SiftJob( int w, int h, const float* imageData, const popsift::Mask& mask )
+    : SiftJob( w, h, imageData )
+{
+    check_mask( w, h, mask );
+    if( mask.data != nullptr ) _mask = job_image( mask.data, (size_t)w * h, &_mask_pinned_cap );
+}
+
 SiftJob::~SiftJob( )
 {
+    if( _mask != nullptr ) { if( _mask_pinned_cap ) popsift::pool::put_pinned( _mask, _mask_pinned_cap ); else free( _mask ); }
     if( _pinned_cap ) popsift::pool::put_pinned( _imageData, _pinned_cap ); else free( _imageData );
 }
 
@@ -401,6 +430,37 @@ SiftJob* PopSift::enqueue( int w, int h, const unsigned char* imageData, const p
 SiftJob* PopSift::enqueue( int w, int h, const float* imageData, const popsift::Keypoint* kps, int n )
 {
     return enqueueChecked( w, h, imageData, true, kps, n );
+}
+
+// the mask overloads: the size check first (no device, no queue), then the checks of the plain ones
+SiftJob* PopSift::enqueueMasked( int w, int h, const void* imageData, bool is_float, const popsift::Mask& mask )
+{
+    check_mask( w, h, mask );
+    if( is_float && _image_mode != FloatImages )
+        POP_FATAL( "Image mode error\nE    Cannot load float images into a PopSift pipeline configured for byte images" );
+    if( !is_float && _image_mode != ByteImages )
+        POP_FATAL( "Image mode error\nE    Cannot load byte images into a PopSift pipeline configured for float images" );
+    AllocTest a = testTextureFit( w, h );
+    if( a != AllocTest::Ok ) {
+        cerr << __FILE__ << ":" << __LINE__ << " Image too large" << endl << testTextureFitErrorString( a, w, h );
+        return nullptr;
+    }
+    resolveOctaves( w, h );
+    popsift::pool::DeviceScope pool_of( _device );      // image and mask come from THIS device's pinned pool
+    SiftJob* job = is_float ? new SiftJob( w, h, (const float*)imageData, mask )
+                            : new SiftJob( w, h, (const unsigned char*)imageData, mask );
+    _impl->queue.push( job );
+    return job;
+}
+
+SiftJob* PopSift::enqueue( int w, int h, const unsigned char* imageData, const popsift::Mask& mask )
+{
+    return enqueueMasked( w, h, imageData, false, mask );
+}
+
+SiftJob* PopSift::enqueue( int w, int h, const float* imageData, const popsift::Mask& mask )
+{
+    return enqueueMasked( w, h, imageData, true, mask );
 }
 
 namespace {
@@ -660,6 +720,11 @@ void PopSift::dispatchLoop( )
                 check( s.ctx, psx_describe( s.ctx, 0 ), "psx_describe" );
             } else
             { popsift::trace::Range r_ex( "extract (launch chain)" );
+              // the context's mask is sticky and contexts are reused across jobs: every detector job sets or clears it
+              if( job->hasMask() )
+                  check( s.ctx, psx_set_mask( s.ctx, job->getMask(), job->getWidth(), job->getHeight() ), "psx_set_mask" );
+              else
+                  check( s.ctx, psx_set_mask( s.ctx, nullptr, 0, 0 ), "psx_set_mask" );
               check( s.ctx, psx_extract( s.ctx ), "psx_extract" ); }
             const double t3 = pnow();
             double tf = 0;

@@ -98,6 +98,20 @@ popsift_c_job* popsift_c_enqueue_f32_kp( popsift_c_handle* h, int w, int hgt, co
     catch( const std::exception& e ) { t_err = e.what(); return nullptr; }
 }
 
+popsift_c_job* popsift_c_enqueue_u8_mask( popsift_c_handle* h, int w, int hgt, const unsigned char* img, const unsigned char* mask, int mask_w, int mask_h )
+{
+    if( h == nullptr ) { t_err = "popsift_c_enqueue_u8_mask: NULL handle"; return nullptr; }
+    try { return reinterpret_cast<popsift_c_job*>( reinterpret_cast<PopSift*>( h )->enqueue( w, hgt, img, popsift::Mask{ mask, mask_w, mask_h } ) ); }
+    catch( const std::exception& e ) { t_err = e.what(); return nullptr; }
+}
+
+popsift_c_job* popsift_c_enqueue_f32_mask( popsift_c_handle* h, int w, int hgt, const float* img, const unsigned char* mask, int mask_w, int mask_h )
+{
+    if( h == nullptr ) { t_err = "popsift_c_enqueue_f32_mask: NULL handle"; return nullptr; }
+    try { return reinterpret_cast<popsift_c_job*>( reinterpret_cast<PopSift*>( h )->enqueue( w, hgt, img, popsift::Mask{ mask, mask_w, mask_h } ) ); }
+    catch( const std::exception& e ) { t_err = e.what(); return nullptr; }
+}
+
 int popsift_c_source_indices( const popsift_c_features* f, int* out, int capacity )
 {
     if( f == nullptr ) return -1;

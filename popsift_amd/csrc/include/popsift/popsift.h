@@ -47,6 +47,16 @@ namespace popsift
         int   num_ori;
         float orientation[ORIENTATION_MAX_COUNT];
     };
+
+    /// A detection mask: a tight w x h plane of bytes, the size of the image it goes with; non-zero = keypoints
+    /// allowed here (psx_set_mask, include/popsift_hip.h; INTEGRATION.md "Detection mask").  data = nullptr (with
+    /// w = h = 0) means "no mask".  The plane is deep-copied at enqueue.
+    struct Mask
+    {
+        const unsigned char* data;
+        int w;
+        int h;
+    };
 } // namespace popsift
 
 class SiftJob
@@ -61,6 +71,8 @@ class SiftJob
     std::exception_ptr  _err;
     bool                _has_kps = false;          ///< describe _kps instead of running the detector
     std::vector<popsift::Keypoint> _kps;           ///< deep copy of the caller's keypoints
+    unsigned char*      _mask = nullptr;           ///< deep copy of the caller's detection mask (_w x _h bytes), or null
+    size_t              _mask_pinned_cap = 0;      ///< > 0: _mask is pinned pool memory
 
 public:
     /// byte image, value range 0..255
@@ -70,6 +82,9 @@ public:
     /// the same with caller-supplied keypoints (deep-copied; kps may be null when n is 0)
     SiftJob( int w, int h, const unsigned char* imageData, const popsift::Keypoint* kps, int n );
     SiftJob( int w, int h, const float* imageData, const popsift::Keypoint* kps, int n );
+    /// the detector with a detection mask (deep-copied; mask.data null: no mask; its size must be the image's)
+    SiftJob( int w, int h, const unsigned char* imageData, const popsift::Mask& mask );
+    SiftJob( int w, int h, const float* imageData, const popsift::Mask& mask );
     ~SiftJob( );
 
     /// deprecated alias of getHost()
@@ -90,6 +105,8 @@ public:
     bool isPinned() const  { return _pinned_cap != 0; }
     bool hasKeypoints() const { return _has_kps; }
     const std::vector<popsift::Keypoint>& getKeypoints() const { return _kps; }
+    bool hasMask() const { return _mask != nullptr; }
+    const unsigned char* getMask() const { return _mask; }
 };
 
 class PopSift
@@ -135,6 +152,12 @@ public:
     /// features back to the records.
     SiftJob* enqueue( int w, int h, const unsigned char* imageData, const popsift::Keypoint* kps, int n );
     SiftJob* enqueue( int w, int h, const float* imageData, const popsift::Keypoint* kps, int n );
+    /// Run the detector under a detection mask: only keypoints whose reported position falls on a non-zero mask pixel
+    /// are found (they take no slot, orientation or descriptor work otherwise).  mask.data = nullptr: no mask.  A mask
+    /// whose size is not the image's is refused with a std::runtime_error before a device is touched.  A job without a
+    /// mask runs unmasked, whatever the job before it on the same context carried.
+    SiftJob* enqueue( int w, int h, const unsigned char* imageData, const popsift::Mask& mask );
+    SiftJob* enqueue( int w, int h, const float* imageData, const popsift::Mask& mask );
 
     /// deprecated
     inline void uninit( int /*pipe*/ ) { uninit(); }
@@ -156,6 +179,7 @@ private:
     void dispatchLoop();
     void resolveOctaves( int w, int h );
     SiftJob* enqueueChecked( int w, int h, const void* imageData, bool is_float, const popsift::Keypoint* kps, int n );
+    SiftJob* enqueueMasked( int w, int h, const void* imageData, bool is_float, const popsift::Mask& mask );
 
     std::unique_ptr<Impl> _impl;
     popsift::Config _config;
