@@ -7,11 +7,14 @@
 // device; the batch dispatcher uses that to keep several frames in flight per GPU.
 //
 // Stream model: every context owns one HIP stream; a frame is one stream-ordered chain
-//   memset(counters) -> k_upscale -> k_blur<R,true> -> per octave { k_blur x (L-1) -> k_extrema } -> k_refine
+//   memset(counters) -> k_level0_fused -> k_blur / k_blur2 in the diagonal schedule of psx_build_pyramid, a large octave's
+//   k_extrema right behind its last level and one batched k_extrema for the small octaves -> k_refine
 //   -> k_orientation -> k_scan -> k_descriptors
-// with no host synchronisation inside the chain (the reference has four blocking counter
-// round-trips and four device-wide syncs per image).
+// (default configuration; the other Gauss and scaling modes build their pyramid in pyramid_alt.hip, POPSIFT_FLOW and
+// POPSIFT_TILE select other launch schedules) with no host synchronisation inside the chain (the reference has four
+// blocking counter round-trips and four device-wide syncs per image).
 #include "psx_internal.h"
+#include "psx_owned.h"
 #include "blur_tile_core.h"
 #include "kp_place.h"
 #include "mask_rule.h"
@@ -82,117 +85,118 @@ constexpr size_t FLOW_MAX_BYTES = sizeof(int) * (size_t)(PSX_FLOW_HEAD_INTS + PS
 constexpr size_t CAND_CT_BYTES = sizeof(int) * (size_t)PSX_MAX_OCTAVES * PSX_CAND_SUB * 32;
 
 struct psx_ctx {
+    // Members are destroyed in reverse order of declaration: the stream goes last, after every buffer, event and graph
+    // that work queued on it may use (psx_destroy has waited for it by then).
+    Stream      stream;
     int         device = 0;
     psx_config  cfg{};
     PsxTuning   tune;                  // the environment switches as psx_create found them, and the device's CU count
     std::string err;
-    hipStream_t stream = nullptr;
 
-    float inc_filter[PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN];
-    int   inc_span[PSX_GAUSS_LEVELS];
-    float inc_sigma[PSX_GAUSS_LEVELS];
-    float dd_filter[PSX_MAX_OCTAVES * PSX_GAUSS_ALIGN];
-    int   dd_span[PSX_MAX_OCTAVES];
-    float dd_sigma[PSX_MAX_OCTAVES];
-    // tables of the alternative pyramid modes (gauss_filter.cu:188-214, 373-410)
-    float abs0_filter[PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN]; int abs0_span[PSX_GAUSS_LEVELS];
-    float absN_filter[PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN]; int absN_span[PSX_GAUSS_LEVELS];
-    float inc_ifilter[PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN]; int inc_ispan[PSX_GAUSS_LEVELS];
+    PsxGaussTables tab;
     bool  alt_pyramid = false;         // any branch of build_pyramid other than the default one
-    float* d_intm = nullptr;           size_t intm_cap = 0;     // scratch planes of the alternative branches
-    float* d_vbuf = nullptr;           size_t vbuf_cap = 0;
+    DevBuf<float> d_intm, d_vbuf;      // scratch planes of the alternative branches
 
     int in_w = 0, in_h = 0;
     int octaves_resolved = -1;         // sticky auto-octave value (popsift.cpp:118-122)
     PsxParams    hp{};
-    PsxParams*   d_params = nullptr;
-    PsxParams*   h_params_pin = nullptr;   // pinned mirror: source of the asynchronous parameter updates
+    DevBuf<PsxParams>    d_params;
+    PinnedBuf<PsxParams> h_params_pin; // pinned mirror: source of the asynchronous parameter updates
+    // frame counters, flow state and candidate sub-list counters in ONE allocation (psx_create); d_cnt and d_cand_ct point into it
+    DevBuf<unsigned char> d_cnt_block;
     PsxCounters* d_cnt = nullptr;
-    PsxCounters* h_cnt = nullptr;      // pinned
+    int* d_cand_ct = nullptr;
+    PinnedBuf<PsxCounters> h_cnt;
     bool counts_valid = false;
     bool counts_partial = false;       // only ext_total / ori_total valid (export fast path)
 
-    void*       d_input_own = nullptr; size_t input_cap = 0;
-    // pageable caller memory is staged through a pinned buffer: hipMemcpyAsync from pageable memory took
-    // 4.9 ms for a 2 MB frame (measured), a host memcpy + DMA from pinned memory takes ~0.1 ms
-    void*       h_stage = nullptr;     size_t stage_cap = 0;
-    hipEvent_t  ev_upload = nullptr;   // the DMA out of h_stage has finished
+    Staged<unsigned char> input_own;   // device copy of a host image (bytes); pinned caller memory skips its staging block
     const void* d_input = nullptr;     int input_is_float = 0;
 
-    float* d_pyr = nullptr;            size_t pyr_cap = 0;      // floats
-    float* d_up = nullptr;             size_t up_cap = 0;       // resampled input of octave 0 (floats)
+    DevBuf<float> d_pyr;
+    DevBuf<float> d_up;                // resampled input of octave 0
     int up_pitch = 0;
-    psx_iext* d_iext = nullptr;        size_t iext_cap = 0;
-    int* d_iext_off = nullptr;         size_t iext_off_cap = 0;
-    unsigned long long* d_cand = nullptr; size_t cand_cap = 0;
-    int* d_cand_ct = nullptr;          // behind d_cnt in the same allocation
-    psx_extremum* d_extrema = nullptr; size_t extrema_cap = 0;
-    psx_feature* d_features = nullptr; size_t features_cap = 0;
-    float* d_desc = nullptr;           size_t desc_cap = 0;       // floats
+    DevBuf<psx_iext> d_iext;
+    DevBuf<int> d_iext_off;
+    DevBuf<unsigned long long> d_cand;
+    DevBuf<psx_extremum> d_extrema;
+    DevBuf<psx_feature> d_features;
+    DevBuf<float> d_desc;
     // byte descriptors (psx_set_descriptor_format): the quantised copy of d_desc, 128 bytes per descriptor, grown with it
     int desc_fmt = PSX_DESCFMT_F32;
-    unsigned char* d_desc_u8 = nullptr; size_t desc_u8_cap = 0;  // bytes
-    int* d_feat_to_ext = nullptr;      size_t f2e_cap = 0;
-    int* d_ext_nori = nullptr;         size_t nori_cap = 0;
+    DevBuf<unsigned char> d_desc_u8;
+    DevBuf<int> d_feat_to_ext;
+    DevBuf<int> d_ext_nori;
 
     // grid filter scratch (allocated on first use)
-    unsigned long long* d_gf_keys = nullptr; size_t gf_keys_cap = 0;    // 2 x total
-    unsigned* d_gf_vals = nullptr;           size_t gf_vals_cap = 0;    // 2 x total
-    unsigned char* d_gf_temp = nullptr;      size_t gf_temp_cap = 0;
-    int* d_gf_scratch = nullptr;             size_t gf_scratch_cap = 0;
+    DevBuf<unsigned long long> d_gf_keys;    // 2 x total
+    DevBuf<unsigned> d_gf_vals;              // 2 x total
+    DevBuf<unsigned char> d_gf_temp;
+    DevBuf<int> d_gf_scratch;
     bool filtered = false;             // the grid filter ran on the current frame
-    bool null_dl_done = false;         // PSX_NULL_DEVICE_WORK=2: this context's one real download has happened
     bool interleave = false;           // psx_extract: launch an octave's extrema scan right behind its last blur level
-    // psx_extract's whole launch chain captured as a hipGraph; valid for one (input pointer, type, size);
-    // everything else the kernels read is device resident (PsxParams) or constant per context (taps)
-    hipGraphExec_t graph = nullptr;
-    const void* graph_input = nullptr; int graph_is_float = 0, graph_w = 0, graph_h = 0;
-    bool graph_off = true;             // !tune.hip_graph (POPSIFT_HIP_GRAPH=1 enables it); switched off again if a capture fails
     bool ext_launched = false;         // ... which has happened for the current frame
+    bool pyr_ready = false;            // the pyramid has been (queued to be) built from the current input
+    int  resident_blocks = 1024;       // 4 x tune.cus
+    bool blocking_wait = false;        // psx_set_wait_mode: sleep on an event instead of spinning in hipStreamSynchronize
+    Event ev_wait;
+
+    // psx_extract's whole launch chain captured as a hipGraph; valid for one (input pointer, type, size, mask);
+    // everything else the kernels read is device resident (PsxParams) or constant per context (taps)
+    struct {
+        GraphExec exec;
+        const void* input = nullptr; int is_float = 0, w = 0, h = 0;
+        const unsigned char* mask = nullptr;                             // the mask the captured graph's kernels carry
+        bool off = true;               // !tune.hip_graph (POPSIFT_HIP_GRAPH=1 enables it); switched off again if a capture fails
+    } graph;
 
     // zero-copy export
-    psx_feature* x_host_feat = nullptr; float* x_host_desc = nullptr;
-    psx_feature* x_dev_feat = nullptr;  float* x_dev_desc = nullptr;
-    int x_feat_cap = 0, x_desc_cap = 0;
-    bool x_registered_feat = false, x_registered_desc = false;
-    // the byte export (psx_attach_export_u8): replaces x_host_desc; x_desc_cap is its capacity
-    unsigned char* x_host_u8 = nullptr; unsigned char* x_dev_u8 = nullptr;
-    bool x_registered_u8 = false;
-    int* h_xcnt = nullptr;             // pinned [4]: ext_total, ori_total, ori_raw
-    // the export targets the frame in flight was LAUNCHED with (psx_orientation): the attach calls may change the
-    // targets of the next frame before this one's counters and results have been fetched
-    PsxExport fx{};
-    psx_feature* fx_host_feat = nullptr; float* fx_host_desc = nullptr;
-    unsigned char* fx_host_u8 = nullptr;
-    bool fx_on = false;
+    struct {
+        MappedHost feat, desc;
+        MappedHost u8;                 // the byte export (psx_attach_export_u8): replaces desc
+        PinnedBuf<int> counts;         // [4]: ext_total, ori_total, ori_raw, flow_error
+        // the export targets the frame in flight was LAUNCHED with (psx_orientation): the attach calls may change the
+        // targets of the next frame before this one's counters and results have been fetched
+        PsxExport fx{};
+        const void *fx_host_feat = nullptr, *fx_host_desc = nullptr, *fx_host_u8 = nullptr;
+        bool fx_on = false;
+    } xp;
 
     // MEASUREMENT switch PSX_NULL_DEVICE_WORK (bench.py host_ceiling): 1 = after a context's first frame psx_extract launches
     // nothing -- uploads, the counter read-back and the result downloads still run, on the first frame's results (same
     // counts, same bytes): what the HOST path and PCIe sustain without the kernels; 2 = the DMAs are skipped as well: the
     // host software alone (threads, queues, pools, the per-keypoint record loop).  Results are stale by construction.
-    bool null_primed = false;
-    bool timers = false;
-    bool blocking_wait = false;        // psx_set_wait_mode: sleep on an event instead of spinning in hipStreamSynchronize
-    hipEvent_t ev_wait = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
-    // in-pipeline timing of the octave-0 separable-Gaussian launches (psx_enable_blur_probe)
-    bool blur_probe = false;
-    hipEvent_t ev_blur[2 * PSX_GAUSS_LEVELS] = {};     // [2l], [2l+1]: begin / end of the level-(l+1) kernel
-    hipEvent_t ev_x[4] = {};           // the probe also brackets octave 0's level 0 [0,1] and its extrema scan [2,3] (stream events)
-    bool probe_ext0 = false;           // octave 0's extrema scan was a launch of its own in the last extraction
-    int  blur_probe_n = 0;             // levels timed in the last extraction
-    double blur_probe_bytes = 0.0;     // algorithmic bytes per timed launch (8 B per pixel of every plane the launch blurs), averaged
+    struct {
+        bool primed = false;
+        bool dl_done = false;          // mode 2: this context's one real download has happened
+    } nulldev;
+
+    struct {
+        bool on = false;               // psx_enable_timers: ev[0..4] bracket the four stages
+        Event ev[5];
+        Event t0, t1;                  // psx_time_blur
+        // in-pipeline timing of the octave-0 separable-Gaussian launches (psx_enable_blur_probe)
+        bool probe = false;
+        Event ev_blur[2 * PSX_GAUSS_LEVELS];   // [2l], [2l+1]: begin / end of the level-(l+1) kernel
+        Event ev_x[4];                 // the probe also brackets octave 0's level 0 [0,1] and its extrema scan [2,3] (stream events)
+        bool probe_ext0 = false;       // octave 0's extrema scan was a launch of its own in the last extraction
+        int  probe_n = 0;              // levels timed in the last extraction
+        double probe_bytes = 0.0;      // algorithmic bytes per timed launch (8 B per pixel of every plane the launch blurs), averaged
+    } tm;
+
     // k_pyramid_flow (POPSIFT_FLOW: 0 = one launch per level -- the default: the one-launch kernel measured 172 us against
     // 190 us of launches for a single 1080p frame but -10 % throughput with several frames in flight, DESIGN.md 3.1b --,
     // 1 = every blur level of the frame in one launch, 2 = octave 0 by launches, octaves >= 1 in one launch)
-    bool flow_on = false;              // a plan exists for the current size
-    int  flow_first = 0, flow_nitems = 0, flow_grid = 0, flow_ncnt = 0, flow_njobs = 0;
-    size_t flow_bytes = 0;             // ticket words + chunk counters, between PsxCounters and the candidate counters
-    double flow_algo_bytes = 0.0;      // algorithmic bytes of the launch (8 B per pixel and blurred plane + 4 B per decimated pixel)
-    PsxFlowJob*  d_flow_jobs = nullptr;  size_t flow_jobs_cap = 0;
-    PsxFlowItem* d_flow_items = nullptr; size_t flow_items_cap = 0;
-    long long*   d_flow_trace = nullptr;     // psx_flow_trace only
+    struct {
+        bool on = false;               // a plan exists for the current size
+        int  first = 0, nitems = 0, grid = 0, ncnt = 0, njobs = 0;
+        size_t bytes = 0;              // ticket words + chunk counters, between PsxCounters and the candidate counters
+        double algo_bytes = 0.0;       // algorithmic bytes of the launch (8 B per pixel and blurred plane + 4 B per decimated pixel)
+        DevBuf<PsxFlowJob>  jobs;
+        DevBuf<PsxFlowItem> items;
+        long long* trace = nullptr;    // psx_flow_trace's buffer while it runs
+    } flow;
+
     // k_blur_tile (pyramid_tile.hip): the octaves that cannot fill the chip run several levels per launch on LDS-resident
     // tiles -- levels 1..L-3 (+ the decimation) of octave o together with levels L-2..L-1 of octave o-1 in ONE launch.
     // OPT-IN (POPSIFT_TILE=1; default: one launch per level, the diagonal schedule): bit-exact, five pyramid launches
@@ -201,64 +205,62 @@ struct psx_ctx {
     // 8 x 8 block (addresses, predicates, stores) is ~2x its filter arithmetic, and the halo work is 1.65x.
     // POPSIFT_TILE_MAXPX: largest plane (pixels) that takes the tile kernel; POPSIFT_TILE_TY / POPSIFT_TILE_NT: tile rows
     // (32 / 64) and threads per workgroup (512 / 1024); POPSIFT_TILE_SMALL=0: no 32 x 32 tiles for the tiny octaves
-    bool tile_on = false;              // a tile schedule exists for the current size
-    int  tile_first = 0;               // first octave on the tile kernel; the octaves in front keep one launch per level
     struct TileLaunch { int job0, njobs, grid; size_t lds; };
-    std::vector<TileLaunch> tile_launches;
-    PsxTileJob* d_tile_jobs = nullptr; size_t tile_jobs_cap = 0;
-    int  resident_blocks = 1024;       // 4 x tune.cus
+    struct {
+        bool on = false;               // a tile schedule exists for the current size
+        int  first = 0;                // first octave on the tile kernel; the octaves in front keep one launch per level
+        std::vector<TileLaunch> launches;
+        DevBuf<PsxTileJob> jobs;
+    } tile;
 
     // caller-supplied keypoints (psx_set_keypoints / psx_describe, keypoints.hip)
-    bool pyr_ready = false;            // the pyramid has been (queued to be) built from the current input
-    bool kp_set = false;               // a keypoint list is set (possibly empty)
-    bool kp_results = false;           // the last results are a psx_describe's (psx_keypoint_map)
-    const psx_keypoint* d_kp = nullptr; int kp_n = 0;                // the list of the next psx_describe
-    psx_keypoint* d_kp_own = nullptr;  size_t kp_own_cap = 0;        // device copy of a host list
-    psx_keypoint* h_kp_stage = nullptr; size_t kp_stage_cap = 0;     // pinned staging of that copy
-    hipEvent_t ev_kp = nullptr;        // the DMA out of h_kp_stage has finished
-    int*   d_kp_tbl = nullptr;         size_t kp_tbl_cap = 0;
-    int*   d_kp_src = nullptr;         size_t kp_src_cap = 0;
-    int*   d_kp_gnori = nullptr;       size_t kp_gnori_cap = 0;
-    float* d_kp_gori = nullptr;        size_t kp_gori_cap = 0;
+    struct {
+        bool set = false;              // a keypoint list is set (possibly empty)
+        bool results = false;          // the last results are a psx_describe's (psx_keypoint_map)
+        const psx_keypoint* list = nullptr; int n = 0;                   // the list of the next psx_describe
+        Staged<psx_keypoint> own;      // device copy of a host list
+        DevBuf<int>   tbl, src, gnori; // side arrays of psx_describe (PsxKpBuffers)
+        DevBuf<float> gori;
+    } kp;
 
     // detection mask (psx_set_mask / psx_set_mask_dev, mask_rule.h): sticky until replaced or cleared
-    const unsigned char* d_mask = nullptr; int mask_w = 0, mask_h = 0;   // the mask in force (nullptr: none)
-    unsigned char* d_mask_own = nullptr;  size_t mask_own_cap = 0;      // device copy of a host mask (bytes)
-    unsigned char* h_mask_stage = nullptr; size_t mask_stage_cap = 0;   // pinned staging of that copy
-    hipEvent_t ev_mask = nullptr;      // the DMA out of h_mask_stage has finished
-    const unsigned char* graph_mask = nullptr;                          // the mask the captured graph's kernels carry
+    struct {
+        const unsigned char* data = nullptr; int w = 0, h = 0;           // the mask in force (nullptr: none)
+        Staged<unsigned char> own;     // device copy of a host mask
+    } mask;
 };
 
 namespace {
 
+inline bool exporting(const psx_ctx* c) { return c->xp.feat.dev != nullptr || c->xp.desc.dev != nullptr || c->xp.u8.dev != nullptr; }
 PsxExport export_of(const psx_ctx* c)
 {
     PsxExport x;
-    x.features = c->x_dev_feat; x.desc = c->x_dev_desc;
-    x.counts = (c->x_dev_feat || c->x_dev_desc || c->x_dev_u8) ? c->h_xcnt : nullptr;
-    x.feat_capacity = c->x_feat_cap; x.desc_capacity = c->x_desc_cap;
+    x.features = static_cast<psx_feature*>(c->xp.feat.dev); x.desc = static_cast<float*>(c->xp.desc.dev);
+    x.counts = exporting(c) ? c->xp.counts.p : nullptr;
+    // one descriptor target at a time: every attach call detaches the other one
+    x.feat_capacity = c->xp.feat.capacity; x.desc_capacity = c->xp.desc.dev ? c->xp.desc.capacity : c->xp.u8.capacity;
     const bool bytes = c->desc_fmt == PSX_DESCFMT_U8;
-    x.desc_u8 = bytes ? c->d_desc_u8 : nullptr;
-    x.xdesc_u8 = bytes ? c->x_dev_u8 : nullptr;
+    x.desc_u8 = bytes ? c->d_desc_u8.p : nullptr;
+    x.xdesc_u8 = bytes ? static_cast<unsigned char*>(c->xp.u8.dev) : nullptr;
     return x;
 }
-inline PsxMask mask_of(const psx_ctx* c) { return PsxMask{c->d_mask, c->mask_w, c->mask_h}; }
+inline PsxMask mask_of(const psx_ctx* c) { return PsxMask{c->mask.data, c->mask.w, c->mask.h}; }
 // PSX_OK, or PSX_ERR_STATE when a mask is set whose size is not the current input's (never dropped silently)
 int fail(psx_ctx* c, int code, const std::string& msg);
 int check_mask(psx_ctx* c, const char* who)
 {
-    if (!c->d_mask || (c->mask_w == c->in_w && c->mask_h == c->in_h)) return PSX_OK;
+    if (!c->mask.data || (c->mask.w == c->in_w && c->mask.h == c->in_h)) return PSX_OK;
     char buf[256];
-    snprintf(buf, sizeof(buf), "%s: the detection mask is %d x %d but the input image is %d x %d", who, c->mask_w, c->mask_h,
+    snprintf(buf, sizeof(buf), "%s: the detection mask is %d x %d but the input image is %d x %d", who, c->mask.w, c->mask.h,
              c->in_w, c->in_h);
     return fail(c, PSX_ERR_STATE, buf);
 }
-inline bool exporting(const psx_ctx* c) { return c->x_dev_feat != nullptr || c->x_dev_desc != nullptr || c->x_dev_u8 != nullptr; }
 inline void snapshot_export(psx_ctx* c)
 {
-    c->fx = export_of(c);
-    c->fx_host_feat = c->x_host_feat; c->fx_host_desc = c->x_host_desc; c->fx_host_u8 = c->x_host_u8;
-    c->fx_on = exporting(c);
+    c->xp.fx = export_of(c);
+    c->xp.fx_host_feat = c->xp.feat.host; c->xp.fx_host_desc = c->xp.desc.host; c->xp.fx_host_u8 = c->xp.u8.host;
+    c->xp.fx_on = exporting(c);
 }
 
 int fail(psx_ctx* c, int code, const std::string& msg)
@@ -278,8 +280,7 @@ int fail(psx_ctx* c, int code, const std::string& msg)
         }                                                                                       \
     } while (0)
 
-int compute_tables(const psx_config* cfg, float* inc_filter, int* inc_span, float* inc_sigma,
-                   float* dd_filter, int* dd_span, float* dd_sigma, std::string* why)
+int compute_tables(const psx_config* cfg, PsxGaussTables* t, std::string* why)
 {
     const float sigma0 = cfg->sigma;
     const int levels = cfg->levels;
@@ -292,52 +293,50 @@ int compute_tables(const psx_config* cfg, float* inc_filter, int* inc_span, floa
         if (why) *why = "ERROR: The mode for computing Gauss filter scan is invalid";
         return PSX_ERR_INVALID;
     }
-    memset(inc_filter, 0, sizeof(float) * PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN);
-    memset(inc_sigma, 0, sizeof(float) * PSX_GAUSS_LEVELS);
-    memset(dd_filter, 0, sizeof(float) * PSX_MAX_OCTAVES * PSX_GAUSS_ALIGN);
+    memset(t->inc_filter, 0, sizeof(float) * PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN);
+    memset(t->inc_sigma, 0, sizeof(float) * PSX_GAUSS_LEVELS);
+    memset(t->dd_filter, 0, sizeof(float) * PSX_MAX_OCTAVES * PSX_GAUSS_ALIGN);
     const int stages = levels + 3;
     const float initial_blur = cfg->assume_initial_blur
                              ? cfg->initial_blur * powf(2.0f, cfg->upscale_factor) : 0.0f;
-    inc_sigma[0] = cfg->assume_initial_blur
+    t->inc_sigma[0] = cfg->assume_initial_blur
                  ? sqrtf(fabsf(sigma0 * sigma0 - initial_blur * initial_blur)) : sigma0;
     for (int lvl = 1; lvl < stages; lvl++) {
         const float sigmaP = sigma0 * powf(2.0f, (float)(lvl - 1) / (float)levels);
         const float sigmaS = sigma0 * powf(2.0f, (float)(lvl) / (float)levels);
-        inc_sigma[lvl] = sqrtf(sigmaS * sigmaS - sigmaP * sigmaP);
+        t->inc_sigma[lvl] = sqrtf(sigmaS * sigmaS - sigmaP * sigmaP);
     }
-    blur_table(cfg->gauss_mode, PSX_GAUSS_LEVELS, inc_sigma, inc_span, inc_filter);
+    blur_table(cfg->gauss_mode, PSX_GAUSS_LEVELS, t->inc_sigma, t->inc_span, t->inc_filter);
     for (int oct = 0; oct < PSX_MAX_OCTAVES; oct++) {
         const float oct_sigma = scalbnf(sigma0, oct);
         const float b = sqrtf(fabsf(oct_sigma * oct_sigma - initial_blur * initial_blur));
-        dd_sigma[oct] = scalbnf(b, -oct);
+        t->dd_sigma[oct] = scalbnf(b, -oct);
     }
-    blur_table(cfg->gauss_mode, PSX_MAX_OCTAVES, dd_sigma, dd_span, dd_filter);
+    blur_table(cfg->gauss_mode, PSX_MAX_OCTAVES, t->dd_sigma, t->dd_span, t->dd_filter);
     return PSX_OK;
 }
 
 // abs_o0, abs_oN and the interpolated (ratio, multiplier) form of the inc table
-void compute_alt_tables(psx_ctx* n, float* abs0_sigma = nullptr, float* absN_sigma = nullptr)
+void compute_alt_tables(const psx_config& c, PsxGaussTables* t)
 {
-    const psx_config& c = n->cfg;
     const float sigma0 = c.sigma;
     const int levels = c.levels, stages = levels + 3;
     const float initial_blur = c.assume_initial_blur ? c.initial_blur * powf(2.0f, c.upscale_factor) : 0.0f;
-    float s0[PSX_GAUSS_LEVELS] = {0}, sN[PSX_GAUSS_LEVELS] = {0};
+    float *const s0 = t->abs0_sigma, *const sN = t->absN_sigma;
+    for (int lvl = 0; lvl < PSX_GAUSS_LEVELS; lvl++) s0[lvl] = sN[lvl] = 0.0f;
     for (int lvl = 0; lvl < stages; lvl++) {
         const float sigmaS = sigma0 * powf(2.0f, (float)(lvl) / (float)levels);
         s0[lvl] = sqrtf(fabsf(sigmaS * sigmaS - initial_blur * initial_blur));
         if (lvl > 0) sN[lvl] = sqrtf(sigmaS * sigmaS - sigma0 * sigma0);
     }
-    blur_table(c.gauss_mode, PSX_GAUSS_LEVELS, s0, n->abs0_span, n->abs0_filter);
-    blur_table(c.gauss_mode, PSX_GAUSS_LEVELS, sN, n->absN_span, n->absN_filter);
-    if (abs0_sigma) memcpy(abs0_sigma, s0, sizeof(s0));
-    if (absN_sigma) memcpy(absN_sigma, sN, sizeof(sN));
+    blur_table(c.gauss_mode, PSX_GAUSS_LEVELS, s0, t->abs0_span, t->abs0_filter);
+    blur_table(c.gauss_mode, PSX_GAUSS_LEVELS, sN, t->absN_span, t->absN_filter);
     for (int level = 0; level < PSX_GAUSS_LEVELS; level++) {       // GaussTable::transformBlurTable
-        int isp = n->inc_span[level];
+        int isp = t->inc_span[level];
         if (!(isp & 1)) isp += 1;
-        n->inc_ispan[level] = isp;
-        const float* f = n->inc_filter + level * PSX_GAUSS_ALIGN;
-        float* fi = n->inc_ifilter + level * PSX_GAUSS_ALIGN;
+        t->inc_ispan[level] = isp;
+        const float* f = t->inc_filter + level * PSX_GAUSS_ALIGN;
+        float* fi = t->inc_ifilter + level * PSX_GAUSS_ALIGN;
         for (int x = 0; x < PSX_GAUSS_ALIGN; x++) fi[x] = 0.0f;
         for (int x = 1; x < isp; x += 2) {
             const float a = f[x], b = f[x + 1];
@@ -355,15 +354,8 @@ PsxTaps taps_from(const float* row)
     return t;
 }
 
-template <class T>
-int grow(psx_ctx* ctx, T** ptr, size_t* cap, size_t need)
-{
-    if (need <= *cap && *ptr) return PSX_OK;
-    if (*ptr) { PSX_HIP(hipFree(*ptr)); *ptr = nullptr; *cap = 0; }
-    PSX_HIP(hipMalloc(reinterpret_cast<void**>(ptr), need * sizeof(T)));
-    *cap = need;
-    return PSX_OK;
-}
+// the captured graph carries the input, the mask, the export targets and the descriptor arrays as kernel arguments
+void drop_graph(psx_ctx* ctx) { ctx->graph.exec.reset(); }
 
 } // namespace
 
@@ -448,18 +440,17 @@ static bool tile_schedule(const PsxParams& P, const int* inc_span, const float* 
 
 static int plan_tiles(psx_ctx* ctx)
 {
-    ctx->tile_on = false;
-    ctx->tile_launches.clear();
+    ctx->tile.on = false;
+    ctx->tile.launches.clear();
     const PsxTuning& t = ctx->tune;
-    if (t.tile == 0 || ctx->alt_pyramid || ctx->flow_on) return PSX_OK;
+    if (t.tile == 0 || ctx->alt_pyramid || ctx->flow.on) return PSX_OK;
     TileSched sc;
-    if (!tile_schedule(ctx->hp, ctx->inc_span, ctx->inc_filter, t.tile_ty, t.tile_nt, t.tile_maxpx, t.tile_small, sc)) return PSX_OK;
-    int rc = grow(ctx, &ctx->d_tile_jobs, &ctx->tile_jobs_cap, sc.jobs.size());
-    if (rc != PSX_OK) return rc;
-    PSX_HIP(hipMemcpy(ctx->d_tile_jobs, sc.jobs.data(), sizeof(PsxTileJob) * sc.jobs.size(), hipMemcpyHostToDevice));
-    ctx->tile_launches = sc.launches;
-    ctx->tile_on = true;
-    ctx->tile_first = sc.first;
+    if (!tile_schedule(ctx->hp, ctx->tab.inc_span, ctx->tab.inc_filter, t.tile_ty, t.tile_nt, t.tile_maxpx, t.tile_small, sc)) return PSX_OK;
+    PSX_HIP(ctx->tile.jobs.grow(sc.jobs.size()));
+    PSX_HIP(hipMemcpy(ctx->tile.jobs, sc.jobs.data(), sizeof(PsxTileJob) * sc.jobs.size(), hipMemcpyHostToDevice));
+    ctx->tile.launches = sc.launches;
+    ctx->tile.on = true;
+    ctx->tile.first = sc.first;
     return PSX_OK;
 }
 
@@ -568,7 +559,14 @@ int psx_gauss_tables(const psx_config* cfg, float* inc_filter, int* inc_span, fl
 {
     if (!cfg || !inc_filter || !inc_span || !inc_sigma || !dd_filter || !dd_span || !dd_sigma)
         return PSX_ERR_INVALID;
-    return compute_tables(cfg, inc_filter, inc_span, inc_sigma, dd_filter, dd_span, dd_sigma, nullptr);
+    PsxGaussTables t{};
+    const int rc = compute_tables(cfg, &t, nullptr);
+    if (rc != PSX_OK) return rc;
+    memcpy(inc_filter, t.inc_filter, sizeof(t.inc_filter)); memcpy(inc_span, t.inc_span, sizeof(t.inc_span));
+    memcpy(inc_sigma, t.inc_sigma, sizeof(t.inc_sigma));
+    memcpy(dd_filter, t.dd_filter, sizeof(t.dd_filter)); memcpy(dd_span, t.dd_span, sizeof(t.dd_span));
+    memcpy(dd_sigma, t.dd_sigma, sizeof(t.dd_sigma));
+    return PSX_OK;
 }
 
 // Config::setPrintGaussTables: what init_filter prints (gauss_filter.cu:146-161) and what its device-side
@@ -576,12 +574,10 @@ int psx_gauss_tables(const psx_config* cfg, float* inc_filter, int* inc_span, fl
 int psx_print_gauss_tables(const psx_config* cfg, int columns)
 {
     if (!cfg) return PSX_ERR_INVALID;
-    std::unique_ptr<psx_ctx> n(new psx_ctx);
-    n->cfg = *cfg;
-    const int rc = compute_tables(cfg, n->inc_filter, n->inc_span, n->inc_sigma, n->dd_filter, n->dd_span, n->dd_sigma, nullptr);
+    PsxGaussTables t{};
+    const int rc = compute_tables(cfg, &t, nullptr);
     if (rc != PSX_OK) return rc;
-    float s0[PSX_GAUSS_LEVELS], sN[PSX_GAUSS_LEVELS];
-    compute_alt_tables(n.get(), s0, sN);
+    compute_alt_tables(*cfg, &t);
     printf("\n"
            "Upscaling factor: %f (i.e. original image is scaled by a factor of %f)\n"
            "\n"
@@ -601,20 +597,20 @@ int psx_print_gauss_tables(const psx_config* cfg, int columns)
         }
     };
     printf("\nGauss tables\n      level span sigma : center value -> edge value\n    relative sigma\n");
-    table(stages, n->inc_span, n->inc_sigma, n->inc_filter, true);
+    table(stages, t.inc_span, t.inc_sigma, t.inc_filter, true);
     printf("\n");
     printf("\nGauss tables for hardware interpolation\n"
            "      level span sigma : center value -> ( interpolation value, multiplier ) [one edge value] \n");
-    table(stages, n->inc_ispan, n->inc_sigma, n->inc_ifilter, true);
+    table(stages, t.inc_ispan, t.inc_sigma, t.inc_ifilter, true);
     printf("\n");
     printf("\nGauss tables\n      level span sigma : center value -> edge value\n"
            "      absolute filters octave 0 (compute level 0, all other levels directly from level 0)\n");
-    table(stages, n->abs0_span, s0, n->abs0_filter, false);
+    table(stages, t.abs0_span, t.abs0_sigma, t.abs0_filter, false);
     printf("\n      absolute filters other octaves\n      (level 0 via downscaling, all other levels directly from level 0)\n");
-    table(stages, n->absN_span, sN, n->absN_filter, false);
+    table(stages, t.absN_span, t.absN_sigma, t.absN_filter, false);
     printf("\n");
     printf("    level 0-filters for direct downscaling\n");
-    table(PSX_MAX_OCTAVES, n->dd_span, n->dd_sigma, n->dd_filter, false);
+    table(PSX_MAX_OCTAVES, t.dd_span, t.dd_sigma, t.dd_filter, false);
     printf("\n");
     fflush(stdout);
     return PSX_OK;
@@ -649,37 +645,26 @@ int psx_create(int device, const psx_config* cfg, psx_ctx** out)
         return fail(nullptr, PSX_ERR_INVALID, "invalid grid_filter_mode");
 
     PSX_HIP(hipSetDevice(device));
-    psx_ctx* n = new (std::nothrow) psx_ctx();
+    std::unique_ptr<psx_ctx> n(new (std::nothrow) psx_ctx());   // a failure below deletes the half-built context
     if (!n) return fail(nullptr, PSX_ERR_NOMEM, "out of host memory");
     n->device = device;
     n->cfg = c;
     {
         std::string bad;
         n->tune = psx_tuning_from_env(&bad);
-        if (!bad.empty()) { delete n; return fail(nullptr, PSX_ERR_INVALID, bad); }
+        if (!bad.empty()) return fail(nullptr, PSX_ERR_INVALID, bad);
     }
     if (hipDeviceGetAttribute(&n->tune.cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n->tune.cus <= 0) n->tune.cus = 256;
     n->resident_blocks = 4 * n->tune.cus;
     // opt-in: measured on MI355X / ROCm 7.2 the replayed graph is not faster than the 36 stream launches
     // (single frame 0.63 vs 0.63 ms, throughput equal): kernel-to-kernel dependencies cost the same either way
-    n->graph_off = !n->tune.hip_graph;
+    n->graph.off = !n->tune.hip_graph;
     std::string why;
-    int rc = compute_tables(&n->cfg, n->inc_filter, n->inc_span, n->inc_sigma, n->dd_filter, n->dd_span,
-                            n->dd_sigma, &why);
-    if (rc != PSX_OK) { delete n; return fail(nullptr, rc, why); }
-    compute_alt_tables(n);
+    int rc = compute_tables(&n->cfg, &n->tab, &why);
+    if (rc != PSX_OK) return fail(nullptr, rc, why);
+    compute_alt_tables(n->cfg, &n->tab);
     n->alt_pyramid = !(c.scaling_mode == PSX_SCALE_DEFAULT &&
                        (c.gauss_mode == PSX_GAUSS_VLFEAT_COMPUTE || c.gauss_mode == PSX_GAUSS_OPENCV_COMPUTE));
-    ctx = nullptr;
-#define PSX_HIPC(call)                                                                          \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            std::string m__ = std::string(#call) + " failed: " + hipGetErrorString(e__);         \
-            psx_destroy(n);                                                                     \
-            return fail(nullptr, PSX_ERR_HIP, m__);                                             \
-        }                                                                                       \
-    } while (0)
     {
         // POPSIFT_CU_PARTITIONS=P (measurement switch, default off): the contexts of a process take turns over P partitions of
         // the chip, each context's stream masked to its partition.  POPSIFT_CU_PARTITION_MODE: 0 = by XCD (mask bit b belongs to
@@ -695,27 +680,27 @@ int psx_create(int device, const psx_config* cfg, psx_ctx** out)
                 const bool mine = pmode == 0 ? (xcd * parts / 8 == part) : (cu % parts == part);
                 if (mine) mask[b / 32] |= 1u << (b % 32);
             }
-            PSX_HIPC(hipExtStreamCreateWithCUMask(&n->stream, (uint32_t)((nbits + 31) / 32), mask));
+            PSX_HIP(hipExtStreamCreateWithCUMask(&n->stream.h, (uint32_t)((nbits + 31) / 32), mask));
         } else
-            PSX_HIPC(hipStreamCreateWithFlags(&n->stream, hipStreamNonBlocking));
+            PSX_HIP(hipStreamCreateWithFlags(&n->stream.h, hipStreamNonBlocking));
     }
-    PSX_HIPC(hipMalloc(reinterpret_cast<void**>(&n->d_params), sizeof(PsxParams)));
-    PSX_HIPC(hipHostMalloc(reinterpret_cast<void**>(&n->h_params_pin), sizeof(PsxParams), hipHostMallocDefault));
+    PSX_HIP(n->d_params.grow(1));
+    PSX_HIP(n->h_params_pin.grow(1));
     // frame counters and the candidate sub-list counters in ONE allocation: one fill kernel clears both per frame
     static_assert(sizeof(PsxCounters) <= CNT_BLOCK, "PsxCounters outgrew its slot");
-    // layout: [PsxCounters | flow state (flow_bytes, set per size) | candidate counters]; the per-frame fill covers the
+    // layout: [PsxCounters | flow state (flow.bytes, set per size) | candidate counters]; the per-frame fill covers the
     // used prefix of it
-    PSX_HIPC(hipMalloc(reinterpret_cast<void**>(&n->d_cnt), CNT_BLOCK + FLOW_MAX_BYTES + CAND_CT_BYTES));
-    n->d_cand_ct = reinterpret_cast<int*>(reinterpret_cast<char*>(n->d_cnt) + CNT_BLOCK);
-    PSX_HIPC(hipHostMalloc(reinterpret_cast<void**>(&n->h_cnt), sizeof(PsxCounters), hipHostMallocDefault));
-    PSX_HIPC(hipMemset(n->d_cnt, 0, CNT_BLOCK + FLOW_MAX_BYTES + CAND_CT_BYTES));
-    PSX_HIPC(hipHostMalloc(reinterpret_cast<void**>(&n->h_xcnt), 4 * sizeof(int), hipHostMallocDefault));
-    n->h_xcnt[0] = n->h_xcnt[1] = n->h_xcnt[2] = n->h_xcnt[3] = 0;
-    for (int i = 0; i < 5; i++) PSX_HIPC(hipEventCreate(&n->ev[i]));
-    PSX_HIPC(hipEventCreate(&n->ev_t0));
-    PSX_HIPC(hipEventCreate(&n->ev_t1));
-#undef PSX_HIPC
-    *out = n;
+    PSX_HIP(n->d_cnt_block.grow(CNT_BLOCK + FLOW_MAX_BYTES + CAND_CT_BYTES));
+    n->d_cnt = reinterpret_cast<PsxCounters*>(n->d_cnt_block.p);
+    n->d_cand_ct = reinterpret_cast<int*>(n->d_cnt_block.p + CNT_BLOCK);
+    PSX_HIP(n->h_cnt.grow(1));
+    PSX_HIP(hipMemset(n->d_cnt, 0, CNT_BLOCK + FLOW_MAX_BYTES + CAND_CT_BYTES));
+    PSX_HIP(n->xp.counts.grow(4));
+    n->xp.counts[0] = n->xp.counts[1] = n->xp.counts[2] = n->xp.counts[3] = 0;
+    for (int i = 0; i < 5; i++) PSX_HIP(n->tm.ev[i].get(hipEventDefault));
+    PSX_HIP(n->tm.t0.get(hipEventDefault));
+    PSX_HIP(n->tm.t1.get(hipEventDefault));
+    *out = n.release();
     return PSX_OK;
 }
 
@@ -724,40 +709,6 @@ int psx_destroy(psx_ctx* ctx)
     if (!ctx) return PSX_OK;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(ctx->d_params); (void)hipFree(ctx->d_cnt);
-    if (ctx->h_params_pin) (void)hipHostFree(ctx->h_params_pin);
-    if (ctx->h_cnt) (void)hipHostFree(ctx->h_cnt);
-    if (ctx->x_registered_feat) (void)hipHostUnregister(ctx->x_host_feat);
-    if (ctx->x_registered_desc) (void)hipHostUnregister(ctx->x_host_desc);
-    if (ctx->x_registered_u8) (void)hipHostUnregister(ctx->x_host_u8);
-    if (ctx->h_xcnt) (void)hipHostFree(ctx->h_xcnt);
-    (void)hipFree(ctx->d_input_own); (void)hipFree(ctx->d_pyr); (void)hipFree(ctx->d_up);
-    (void)hipFree(ctx->d_intm); (void)hipFree(ctx->d_vbuf);
-    (void)hipFree(ctx->d_flow_jobs); (void)hipFree(ctx->d_flow_items);
-    (void)hipFree(ctx->d_tile_jobs);
-    (void)hipFree(ctx->d_gf_keys); (void)hipFree(ctx->d_gf_vals); (void)hipFree(ctx->d_gf_temp);
-    (void)hipFree(ctx->d_gf_scratch);
-    (void)hipFree(ctx->d_iext); (void)hipFree(ctx->d_iext_off); (void)hipFree(ctx->d_cand);
-    (void)hipFree(ctx->d_extrema); (void)hipFree(ctx->d_features);
-    (void)hipFree(ctx->d_desc); (void)hipFree(ctx->d_feat_to_ext); (void)hipFree(ctx->d_ext_nori);
-    (void)hipFree(ctx->d_desc_u8);
-    (void)hipFree(ctx->d_kp_own); (void)hipFree(ctx->d_kp_tbl); (void)hipFree(ctx->d_kp_src);
-    (void)hipFree(ctx->d_kp_gnori); (void)hipFree(ctx->d_kp_gori);
-    if (ctx->h_kp_stage) (void)hipHostFree(ctx->h_kp_stage);
-    if (ctx->ev_kp) (void)hipEventDestroy(ctx->ev_kp);
-    (void)hipFree(ctx->d_mask_own);
-    if (ctx->h_mask_stage) (void)hipHostFree(ctx->h_mask_stage);
-    if (ctx->ev_mask) (void)hipEventDestroy(ctx->ev_mask);
-    for (int i = 0; i < 5; i++) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-    if (ctx->ev_t0) (void)hipEventDestroy(ctx->ev_t0);
-    if (ctx->ev_t1) (void)hipEventDestroy(ctx->ev_t1);
-    for (int i = 0; i < 2 * PSX_GAUSS_LEVELS; i++) if (ctx->ev_blur[i]) (void)hipEventDestroy(ctx->ev_blur[i]);
-    for (int i = 0; i < 4; i++) if (ctx->ev_x[i]) (void)hipEventDestroy(ctx->ev_x[i]);
-    if (ctx->graph) (void)hipGraphExecDestroy(ctx->graph);
-    if (ctx->ev_wait) (void)hipEventDestroy(ctx->ev_wait);
-    if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
-    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return PSX_OK;
 }
@@ -769,7 +720,7 @@ int psx_resize(psx_ctx* ctx, int w, int h)
     if (w == ctx->in_w && h == ctx->in_h && ctx->d_pyr) return PSX_OK;
     PSX_HIP(hipSetDevice(ctx->device));
     PSX_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->graph) { (void)hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
+    drop_graph(ctx);
 
     const psx_config& c = ctx->cfg;
     // PopSift::private_apply_scale_factor, popsift.cpp:109-126
@@ -821,14 +772,13 @@ int psx_resize(psx_ctx* ctx, int w, int h)
         oh = (int)ceilf(oh / 2.0f);
     }
     total += 64;   // slack: vector loads never run past the last plane
-    int rc;
-    if ((rc = grow(ctx, &ctx->d_pyr, &ctx->pyr_cap, total)) != PSX_OK) return rc;
+    PSX_HIP(ctx->d_pyr.grow(total));
     ctx->up_pitch = ((P.oct[0].w + 63) / 64) * 64 + 2 * PSX_LEVEL0_PAD;
-    if ((rc = grow(ctx, &ctx->d_up, &ctx->up_cap, (size_t)ctx->up_pitch * P.oct[0].h)) != PSX_OK) return rc;
+    PSX_HIP(ctx->d_up.grow((size_t)ctx->up_pitch * P.oct[0].h));
     for (int o = 0; o < P.num_octaves; o++) P.oct[o].data = ctx->d_pyr + offs[o];
     if (ctx->alt_pyramid) {
-        if ((rc = grow(ctx, &ctx->d_intm, &ctx->intm_cap, P.oct[0].plane + 64)) != PSX_OK) return rc;
-        if ((rc = grow(ctx, &ctx->d_vbuf, &ctx->vbuf_cap, (size_t)(P.oct[0].pitch + 64) * P.oct[0].h)) != PSX_OK) return rc;
+        PSX_HIP(ctx->d_intm.grow(P.oct[0].plane + 64));
+        PSX_HIP(ctx->d_vbuf.grow((size_t)(P.oct[0].pitch + 64) * P.oct[0].h));
     }
 
     // Extrema buffers are sized for the worst case (max_extrema per octave, 100 B per entry); the descriptor
@@ -837,48 +787,47 @@ int psx_resize(psx_ctx* ctx, int w, int h)
     // (regrow_descriptors below; the reference reallocates in Pyramid::reallocExtrema the same way).
     const size_t iext_need = (size_t)P.num_octaves * c.max_extrema;
     const size_t ori_floor = (size_t)imax(2 * c.max_extrema, c.max_extrema + c.max_extrema / 4);
-    const size_t ori_need = ctx->desc_cap / 128 > ori_floor ? ctx->desc_cap / 128 : ori_floor;
-    if ((rc = grow(ctx, &ctx->d_iext, &ctx->iext_cap, iext_need)) != PSX_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_iext_off, &ctx->iext_off_cap, iext_need)) != PSX_OK) return rc;
+    const size_t ori_need = ctx->d_desc.cap / 128 > ori_floor ? ctx->d_desc.cap / 128 : ori_floor;
+    PSX_HIP(ctx->d_iext.grow(iext_need));
+    PSX_HIP(ctx->d_iext_off.grow(iext_need));
     // candidates before refinement: ~1.3x the survivors on natural images; room for 4x the cap per octave,
     // split over PSX_CAND_SUB sub-lists; a candidate that finds its sub-list full is refined in place
     // k_pyramid_flow: work list of this size (default pyramid modes only), and where the candidate counters start behind
     // its ticket words and chunk counters
-    ctx->flow_on = false; ctx->flow_bytes = 0;
+    ctx->flow.on = false; ctx->flow.bytes = 0;
     if (!ctx->alt_pyramid && ctx->tune.flow != 0) {
         PsxFlowPlan plan{};
         const int first = ctx->tune.flow == 2 ? 1 : 0;
-        if (first < P.num_octaves && psx_flow_plan(ctx->tune, P, ctx->inc_filter, ctx->inc_span, first, ctx->resident_blocks, ctx->tune.flow_order, &plan)) {
-            bool ok = grow(ctx, &ctx->d_flow_jobs, &ctx->flow_jobs_cap, (size_t)plan.njobs) == PSX_OK &&
-                      grow(ctx, &ctx->d_flow_items, &ctx->flow_items_cap, (size_t)plan.nitems) == PSX_OK;
-            ok = ok && hipMemcpy(ctx->d_flow_jobs, plan.jobs, sizeof(PsxFlowJob) * (size_t)plan.njobs, hipMemcpyHostToDevice) == hipSuccess &&
-                       hipMemcpy(ctx->d_flow_items, plan.items, sizeof(PsxFlowItem) * (size_t)plan.nitems, hipMemcpyHostToDevice) == hipSuccess;
+        if (first < P.num_octaves && psx_flow_plan(ctx->tune, P, ctx->tab.inc_filter, ctx->tab.inc_span, first, ctx->resident_blocks, ctx->tune.flow_order, &plan)) {
+            bool ok = ctx->flow.jobs.grow((size_t)plan.njobs) == hipSuccess && ctx->flow.items.grow((size_t)plan.nitems) == hipSuccess;
+            ok = ok && hipMemcpy(ctx->flow.jobs, plan.jobs, sizeof(PsxFlowJob) * (size_t)plan.njobs, hipMemcpyHostToDevice) == hipSuccess &&
+                       hipMemcpy(ctx->flow.items, plan.items, sizeof(PsxFlowItem) * (size_t)plan.nitems, hipMemcpyHostToDevice) == hipSuccess;
             if (ok) {
-                ctx->flow_on = true; ctx->flow_first = first; ctx->flow_nitems = plan.nitems; ctx->flow_grid = plan.grid;
-                ctx->flow_ncnt = plan.ncounters; ctx->flow_njobs = plan.njobs;
-                ctx->flow_bytes = sizeof(int) * ((size_t)PSX_FLOW_HEAD_INTS + (size_t)plan.ncounters * PSX_FLOW_CNT_STRIDE);
+                ctx->flow.on = true; ctx->flow.first = first; ctx->flow.nitems = plan.nitems; ctx->flow.grid = plan.grid;
+                ctx->flow.ncnt = plan.ncounters; ctx->flow.njobs = plan.njobs;
+                ctx->flow.bytes = sizeof(int) * ((size_t)PSX_FLOW_HEAD_INTS + (size_t)plan.ncounters * PSX_FLOW_CNT_STRIDE);
                 double by = 0.0;
                 for (int q = 0; q < plan.njobs; q++) {
                     by += 8.0 * (double)plan.jobs[q].W * plan.jobs[q].H;
                     if (plan.jobs[q].half_dst) by += 4.0 * (double)((plan.jobs[q].W + 1) / 2) * ((plan.jobs[q].H + 1) / 2);
                 }
-                ctx->flow_algo_bytes = by;
+                ctx->flow.algo_bytes = by;
             }
             free(plan.jobs); free(plan.items);
             if (!ok) return fail(ctx, PSX_ERR_HIP, "psx_resize: could not upload the pyramid work list");
         }
     }
     { const int trc = plan_tiles(ctx); if (trc != PSX_OK) return trc; }
-    ctx->d_cand_ct = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->d_cnt) + CNT_BLOCK + ctx->flow_bytes);
+    ctx->d_cand_ct = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->d_cnt) + CNT_BLOCK + ctx->flow.bytes);
     P.cand_capacity = (4 * c.max_extrema + PSX_CAND_SUB - 1) / PSX_CAND_SUB;
-    if ((rc = grow(ctx, &ctx->d_cand, &ctx->cand_cap, (size_t)P.num_octaves * PSX_CAND_SUB * P.cand_capacity)) != PSX_OK) return rc;
+    PSX_HIP(ctx->d_cand.grow((size_t)P.num_octaves * PSX_CAND_SUB * P.cand_capacity));
     P.cand_ct = ctx->d_cand_ct;
-    if ((rc = grow(ctx, &ctx->d_extrema, &ctx->extrema_cap, iext_need)) != PSX_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_features, &ctx->features_cap, iext_need)) != PSX_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_desc, &ctx->desc_cap, ori_need * 128)) != PSX_OK) return rc;
-    if (ctx->desc_fmt == PSX_DESCFMT_U8 && (rc = grow(ctx, &ctx->d_desc_u8, &ctx->desc_u8_cap, ctx->desc_cap)) != PSX_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_feat_to_ext, &ctx->f2e_cap, ori_need)) != PSX_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_ext_nori, &ctx->nori_cap, iext_need + 64)) != PSX_OK) return rc;
+    PSX_HIP(ctx->d_extrema.grow(iext_need));
+    PSX_HIP(ctx->d_features.grow(iext_need));
+    PSX_HIP(ctx->d_desc.grow(ori_need * 128));
+    if (ctx->desc_fmt == PSX_DESCFMT_U8) PSX_HIP(ctx->d_desc_u8.grow(ctx->d_desc.cap));
+    PSX_HIP(ctx->d_feat_to_ext.grow(ori_need));
+    PSX_HIP(ctx->d_ext_nori.grow(iext_need + 64));
     for (int o = 0; o < P.num_octaves; o++) {
         P.iext[o] = ctx->d_iext + (size_t)o * c.max_extrema;
         P.iext_off[o] = ctx->d_iext_off + (size_t)o * c.max_extrema;
@@ -916,36 +865,20 @@ static int upload_common(psx_ctx* ctx, const void* host, int w, int h, int is_fl
     if (rc != PSX_OK) return rc;
     PSX_HIP(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)w * h * (is_float ? 4 : 1);
-    if (bytes > ctx->input_cap) {
-        PSX_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->d_input_own) PSX_HIP(hipFree(ctx->d_input_own));
-        ctx->d_input_own = nullptr; ctx->input_cap = 0;
-        PSX_HIP(hipMalloc(&ctx->d_input_own, bytes + 64));
-        ctx->input_cap = bytes;
-    }
-    const void* src = host;
+    Staged<unsigned char>& in = ctx->input_own;
+    PSX_HIP(in.reserve(bytes, bytes, 64, ctx->stream));               // 64 bytes of slack behind the image
+    const bool dma = !(ctx->tune.null_device_work == 2 && ctx->nulldev.primed);       // PSX_NULL_DEVICE_WORK=2: host software only, no DMA
     hipPointerAttribute_t attr;
+    // DMA engine, not a kernel: a copy kernel that reads the mapped host image over PCIe itself was measured
+    // (GPU-initiated reads are slow: +0.8 ms per frame in flight, -8 % end-to-end throughput).
     // hipPointerGetAttributes costs ~0.2 ms per call in a process with many mappings: callers that KNOW their
     // buffer is pinned (psx_host_alloc) say so
     if (!known_pinned && (hipPointerGetAttributes(&attr, host) != hipSuccess || attr.type == hipMemoryTypeUnregistered)) {
         (void)hipGetLastError();
-        if (!ctx->ev_upload) PSX_HIP(hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming));
-        else PSX_HIP(hipEventSynchronize(ctx->ev_upload));            // previous DMA out of the staging buffer
-        if (bytes > ctx->stage_cap) {
-            if (ctx->h_stage) PSX_HIP(hipHostFree(ctx->h_stage));
-            ctx->h_stage = nullptr; ctx->stage_cap = 0;
-            PSX_HIP(hipHostMalloc(&ctx->h_stage, bytes, hipHostMallocDefault));
-            ctx->stage_cap = bytes;
-        }
-        memcpy(ctx->h_stage, host, bytes);
-        src = ctx->h_stage;
-    }
-    // DMA engine, not a kernel: a copy kernel that reads the mapped host image over PCIe itself was measured
-    // (GPU-initiated reads are slow: +0.8 ms per frame in flight, -8 % end-to-end throughput)
-    if (!(ctx->tune.null_device_work == 2 && ctx->null_primed))        // PSX_NULL_DEVICE_WORK=2: host software only, no DMA
-        PSX_HIP(hipMemcpyAsync(ctx->d_input_own, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (src == ctx->h_stage) PSX_HIP(hipEventRecord(ctx->ev_upload, ctx->stream));
-    ctx->d_input = ctx->d_input_own;
+        PSX_HIP(in.push(static_cast<const unsigned char*>(host), bytes, bytes, bytes, ctx->stream, 64, dma));
+    } else if (dma)
+        PSX_HIP(hipMemcpyAsync(in.dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    ctx->d_input = in.dev;
     ctx->input_is_float = is_float;
     ctx->pyr_ready = false;
     return PSX_OK;
@@ -982,8 +915,8 @@ static PsxBlurJob blur_job(const psx_ctx* ctx, int o, int level)
         j.half_pitch = P.oct[o + 1].pitch;
     }
     j.W = oc.w; j.H = oc.h; j.pitch = oc.pitch;
-    j.taps = taps_from(ctx->inc_filter + level * PSX_GAUSS_ALIGN);
-    j.span = ctx->inc_span[level];
+    j.taps = taps_from(ctx->tab.inc_filter + level * PSX_GAUSS_ALIGN);
+    j.span = ctx->tab.inc_span[level];
     return j;
 }
 
@@ -1010,10 +943,10 @@ static int launch_extrema_set(psx_ctx* ctx, const int* octaves, int n)
 static int scan_or_defer(psx_ctx* ctx, int o, int* deferred, int* ndef)
 {
     if (psx_extrema_tiles(ctx->hp, o) < ctx->resident_blocks) { deferred[(*ndef)++] = o; return PSX_OK; }
-    const bool px = ctx->blur_probe && o == 0;
-    if (px) PSX_HIP(hipEventRecord(ctx->ev_x[2], ctx->stream));
+    const bool px = ctx->tm.probe && o == 0;
+    if (px) PSX_HIP(hipEventRecord(ctx->tm.ev_x[2].h, ctx->stream));
     PSX_HIP(psx_launch_extrema(ctx->d_params, ctx->hp, ctx->d_cnt, o, mask_of(ctx), ctx->stream));
-    if (px) { PSX_HIP(hipEventRecord(ctx->ev_x[3], ctx->stream)); ctx->probe_ext0 = true; }
+    if (px) { PSX_HIP(hipEventRecord(ctx->tm.ev_x[3].h, ctx->stream)); ctx->tm.probe_ext0 = true; }
     return PSX_OK;
 }
 
@@ -1025,10 +958,10 @@ int psx_build_pyramid(psx_ctx* ctx)
     const PsxParams& P = ctx->hp;
     const psx_config& c = ctx->cfg;
     ctx->counts_valid = false;
-    ctx->pyr_ready = true; ctx->kp_results = false;
-    if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
+    ctx->pyr_ready = true; ctx->kp.results = false;
+    if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[0].h, ctx->stream));
     // Pyramid::reset_extrema_mgmt, sift_pyramid.cu:364-371
-    PSX_HIP(hipMemsetAsync(ctx->d_cnt, 0, CNT_BLOCK + ctx->flow_bytes + sizeof(int) * (size_t)P.num_octaves * PSX_CAND_SUB * 32, ctx->stream));
+    PSX_HIP(hipMemsetAsync(ctx->d_cnt, 0, CNT_BLOCK + ctx->flow.bytes + sizeof(int) * (size_t)P.num_octaves * PSX_CAND_SUB * 32, ctx->stream));
 
     if (ctx->alt_pyramid) {
         PsxAltArgs q;
@@ -1036,9 +969,7 @@ int psx_build_pyramid(psx_ctx* ctx)
         q.img = ctx->d_input; q.w = ctx->in_w; q.h = ctx->in_h; q.is_float = ctx->input_is_float;
         q.gauss_mode = c.gauss_mode; q.scaling_mode = c.scaling_mode; q.sift_mode = c.sift_mode;
         q.upscale_factor = c.upscale_factor;
-        q.inc_filter = ctx->inc_filter; q.inc_ifilter = ctx->inc_ifilter; q.dd_filter = ctx->dd_filter;
-        q.abs0_filter = ctx->abs0_filter; q.absN_filter = ctx->absN_filter;
-        q.inc_span = ctx->inc_span; q.inc_ispan = ctx->inc_ispan; q.dd_span = ctx->dd_span; q.abs0_span = ctx->abs0_span;
+        q.tab = &ctx->tab;
         q.up = ctx->d_up; q.up_pitch = ctx->up_pitch;
         q.intm = ctx->d_intm; q.vbuf = ctx->d_vbuf; q.vbuf_pitch = P.oct[0].pitch + 64;
         q.user = ctx;
@@ -1048,17 +979,17 @@ int psx_build_pyramid(psx_ctx* ctx)
         } : nullptr;
         ctx->ext_launched = false;
         int probe_hit = 0;
-        if (ctx->blur_probe) { q.probe_ev0 = ctx->ev_blur[0]; q.probe_ev1 = ctx->ev_blur[1]; q.probe_hit = &probe_hit; ctx->blur_probe_n = 0; }
+        if (ctx->tm.probe) { q.probe_ev0 = ctx->tm.ev_blur[0].h; q.probe_ev1 = ctx->tm.ev_blur[1].h; q.probe_hit = &probe_hit; ctx->tm.probe_n = 0; }
         const hipError_t e = psx_launch_pyramid_alt(q, ctx->stream);
         if (probe_hit) {
             // Fixed9 / Fixed15: the one-kernel octave 0 (six planes written from the input image: 24 B per pixel + the image)
-            ctx->blur_probe_n = 1;
-            ctx->blur_probe_bytes = 24.0 * (double)P.oct[0].w * P.oct[0].h + (double)ctx->in_w * ctx->in_h * (ctx->input_is_float ? 4 : 1);
+            ctx->tm.probe_n = 1;
+            ctx->tm.probe_bytes = 24.0 * (double)P.oct[0].w * P.oct[0].h + (double)ctx->in_w * ctx->in_h * (ctx->input_is_float ? 4 : 1);
         }
         if (e == hipErrorInvalidValue) return fail(ctx, PSX_ERR_INVALID, "Unsupported number of levels for making all octaves at once");
         PSX_HIP(e);
         ctx->ext_launched = ctx->interleave;
-        if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
+        if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[1].h, ctx->stream));
         return PSX_OK;
     }
 
@@ -1069,45 +1000,45 @@ int psx_build_pyramid(psx_ctx* ctx)
     a.shift = 0.5f;                                                    // s_pyramid_build.cu:109-114
     if (c.sift_mode == PSX_MODE_POPSIFT || c.sift_mode == PSX_MODE_VLFEAT)
         a.shift = 0.5f * powf(2.0f, c.upscale_factor - 0);
-    a.taps_h = taps_from(ctx->dd_filter); a.span_h = ctx->dd_span[0];
-    a.taps_v = taps_from(ctx->inc_filter); a.span_v = ctx->inc_span[0];
-    if (ctx->blur_probe) PSX_HIP(hipEventRecord(ctx->ev_x[0], ctx->stream));
+    a.taps_h = taps_from(ctx->tab.dd_filter); a.span_h = ctx->tab.dd_span[0];
+    a.taps_v = taps_from(ctx->tab.inc_filter); a.span_v = ctx->tab.inc_span[0];
+    if (ctx->tm.probe) PSX_HIP(hipEventRecord(ctx->tm.ev_x[0].h, ctx->stream));
     PSX_HIP(psx_launch_level0(ctx->tune, a, ctx->stream));
-    if (ctx->blur_probe) PSX_HIP(hipEventRecord(ctx->ev_x[1], ctx->stream));
+    if (ctx->tm.probe) PSX_HIP(hipEventRecord(ctx->tm.ev_x[1].h, ctx->stream));
 
     ctx->ext_launched = false;
-    const bool probe = ctx->blur_probe;
-    if (ctx->flow_on) {
+    const bool probe = ctx->tm.probe;
+    if (ctx->flow.on) {
         // k_pyramid_flow: octave 0's levels by launches first when the plan starts at octave 1 (POPSIFT_FLOW=2), then every
         // remaining blur level of the frame in ONE launch with device-side dependencies; the extrema scans follow in
         // psx_find_extrema
-        for (int level = 1; ctx->flow_first > 0 && level < P.L; level++) {
-            hipEvent_t e0 = probe ? ctx->ev_blur[2 * (level - 1)] : nullptr, e1 = probe ? ctx->ev_blur[2 * (level - 1) + 1] : nullptr;
+        for (int level = 1; ctx->flow.first > 0 && level < P.L; level++) {
+            hipEvent_t e0 = probe ? ctx->tm.ev_blur[2 * (level - 1)].h : nullptr, e1 = probe ? ctx->tm.ev_blur[2 * (level - 1) + 1].h : nullptr;
             const int rc = launch_blur_level(ctx, 0, level, e0, e1);
             if (rc != PSX_OK) return rc;
         }
-        const bool pf = probe && ctx->flow_first == 0;
+        const bool pf = probe && ctx->flow.first == 0;
         int* state = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->d_cnt) + CNT_BLOCK);
-        PSX_HIP(psx_launch_flow(ctx->tune, ctx->d_flow_jobs, ctx->d_flow_items, ctx->flow_nitems, state, &ctx->d_cnt->flow_error,
-                                ctx->flow_grid, ctx->tune.flow_ld, ctx->stream, pf ? ctx->ev_blur[0] : nullptr, pf ? ctx->ev_blur[1] : nullptr,
-                                ctx->d_flow_trace));
+        PSX_HIP(psx_launch_flow(ctx->tune, ctx->flow.jobs, ctx->flow.items, ctx->flow.nitems, state, &ctx->d_cnt->flow_error,
+                                ctx->flow.grid, ctx->tune.flow_ld, ctx->stream, pf ? ctx->tm.ev_blur[0].h : nullptr, pf ? ctx->tm.ev_blur[1].h : nullptr,
+                                ctx->flow.trace));
         if (probe) {
-            if (pf) { ctx->blur_probe_n = 1; ctx->blur_probe_bytes = ctx->flow_algo_bytes; }
-            else    { ctx->blur_probe_n = P.L - 1; ctx->blur_probe_bytes = 8.0 * (double)P.oct[0].w * P.oct[0].h; }
+            if (pf) { ctx->tm.probe_n = 1; ctx->tm.probe_bytes = ctx->flow.algo_bytes; }
+            else    { ctx->tm.probe_n = P.L - 1; ctx->tm.probe_bytes = 8.0 * (double)P.oct[0].w * P.oct[0].h; }
         }
-        if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
+        if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[1].h, ctx->stream));
         return PSX_OK;
     }
-    if (ctx->tile_on && !(probe && ctx->tile_first == 0)) {
+    if (ctx->tile.on && !(probe && ctx->tile.first == 0)) {
         // octaves in front of tile_first: one launch per level, the octave's extrema scan right behind its last level;
         // then the tile launches (several levels of up to two octaves each); then the scans of the small octaves
         double probe_bytes = 0.0;
         int deferred[PSX_MAX_OCTAVES], ndef = 0;
         auto scan_after = [&](int o) -> int { return ctx->interleave ? scan_or_defer(ctx, o, deferred, &ndef) : PSX_OK; };
-        for (int o = 0; o < ctx->tile_first; o++) {
+        for (int o = 0; o < ctx->tile.first; o++) {
             for (int level = 1; level < P.L; level++) {
                 const bool pl = probe && o == 0;
-                hipEvent_t e0 = pl ? ctx->ev_blur[2 * (level - 1)] : nullptr, e1 = pl ? ctx->ev_blur[2 * (level - 1) + 1] : nullptr;
+                hipEvent_t e0 = pl ? ctx->tm.ev_blur[2 * (level - 1)].h : nullptr, e1 = pl ? ctx->tm.ev_blur[2 * (level - 1) + 1].h : nullptr;
                 const int rc = launch_blur_level(ctx, o, level, e0, e1);
                 if (rc != PSX_OK) return rc;
                 if (pl) probe_bytes += 8.0 * (double)P.oct[o].w * P.oct[o].h;
@@ -1115,13 +1046,13 @@ int psx_build_pyramid(psx_ctx* ctx)
             const int rc = scan_after(o);
             if (rc != PSX_OK) return rc;
         }
-        for (const psx_ctx::TileLaunch& ln : ctx->tile_launches)
-            PSX_HIP(psx_launch_blur_tile(ctx->d_tile_jobs + ln.job0, ln.njobs, ln.grid, ln.lds, ctx->tune.tile_nt, ctx->stream));
-        for (int o = ctx->tile_first; o < P.num_octaves; o++) { const int rc = scan_after(o); if (rc != PSX_OK) return rc; }
+        for (const psx_ctx::TileLaunch& ln : ctx->tile.launches)
+            PSX_HIP(psx_launch_blur_tile(ctx->tile.jobs + ln.job0, ln.njobs, ln.grid, ln.lds, ctx->tune.tile_nt, ctx->stream));
+        for (int o = ctx->tile.first; o < P.num_octaves; o++) { const int rc = scan_after(o); if (rc != PSX_OK) return rc; }
         if (ndef > 0) { const int rc = launch_extrema_set(ctx, deferred, ndef); if (rc != PSX_OK) return rc; }
-        if (probe) { ctx->blur_probe_n = P.L - 1; ctx->blur_probe_bytes = probe_bytes / (P.L - 1); }
+        if (probe) { ctx->tm.probe_n = P.L - 1; ctx->tm.probe_bytes = probe_bytes / (P.L - 1); }
         ctx->ext_launched = ctx->interleave;
-        if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
+        if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[1].h, ctx->stream));
         return PSX_OK;
     }
     // Diagonal schedule.  Level l of octave o only needs level l-1 of the same octave, and level 0 of octave o+1
@@ -1135,7 +1066,7 @@ int psx_build_pyramid(psx_ctx* ctx)
     int t0[PSX_MAX_OCTAVES];                       // level l of octave o runs in launch slot t0[o] + l
     t0[0] = 0;
     for (int o = 0; o + 1 < P.num_octaves; o++) {
-        const int span = ctx->inc_span[P.L - 1];
+        const int span = ctx->tab.inc_span[P.L - 1];
         const bool fits = ctx->tune.batch_octaves &&
             psx_blur_pair_ok(ctx->tune, P.oct[o].w, P.oct[o].h, P.oct[o + 1].w, P.oct[o + 1].h, span, ctx->resident_blocks);
         t0[o + 1] = t0[o] + (fits ? D : P.L - 1);
@@ -1152,13 +1083,13 @@ int psx_build_pyramid(psx_ctx* ctx)
         for (int q = 0; q < nj; q += 2) {
             const int o = jo[q], level = t - t0[o];
             const bool pl = probe && o == 0;
-            hipEvent_t e0 = pl ? ctx->ev_blur[2 * (level - 1)] : nullptr, e1 = pl ? ctx->ev_blur[2 * (level - 1) + 1] : nullptr;
+            hipEvent_t e0 = pl ? ctx->tm.ev_blur[2 * (level - 1)].h : nullptr, e1 = pl ? ctx->tm.ev_blur[2 * (level - 1) + 1].h : nullptr;
             // only when both fit into one round of resident workgroups (4 per CU): behind a launch that fills the
             // chip the second plane would just queue, and it would run on the larger radius' kernel for nothing
             bool pair = q + 1 < nj && ctx->tune.batch_octaves;
             if (pair) {
                 const int o2 = jo[q + 1], level2 = t - t0[o2];
-                const int span = ctx->inc_span[level] > ctx->inc_span[level2] ? ctx->inc_span[level] : ctx->inc_span[level2];
+                const int span = ctx->tab.inc_span[level] > ctx->tab.inc_span[level2] ? ctx->tab.inc_span[level] : ctx->tab.inc_span[level2];
                 pair = psx_blur_pair_ok(ctx->tune, P.oct[o].w, P.oct[o].h, P.oct[o2].w, P.oct[o2].h, span, ctx->resident_blocks);
             }
             if (pair) {
@@ -1184,9 +1115,9 @@ int psx_build_pyramid(psx_ctx* ctx)
             }
     }
     if (ndef > 0) { int rc = launch_extrema_set(ctx, deferred, ndef); if (rc != PSX_OK) return rc; }
-    if (probe) { ctx->blur_probe_n = P.L - 1; ctx->blur_probe_bytes = probe_bytes / (P.L - 1); }
+    if (probe) { ctx->tm.probe_n = P.L - 1; ctx->tm.probe_bytes = probe_bytes / (P.L - 1); }
     ctx->ext_launched = ctx->interleave;
-    if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
+    if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[1].h, ctx->stream));
     return PSX_OK;
 }
 
@@ -1199,7 +1130,7 @@ static int wait_stream(psx_ctx* ctx)
         // microseconds of CPU per frame and, with several frames in flight per worker pool, no throughput.
         // POPSIFT_WAIT_SLEEP_US (default 40; 0 = the runtime's blocking wait).
         const int sleep_us = ctx->tune.wait_sleep_us;
-        if (!ctx->ev_wait) PSX_HIP(hipEventCreateWithFlags(&ctx->ev_wait, hipEventBlockingSync | hipEventDisableTiming));
+        PSX_HIP(ctx->ev_wait.get(hipEventBlockingSync | hipEventDisableTiming));
         PSX_HIP(hipEventRecord(ctx->ev_wait, ctx->stream));
         if (sleep_us == 0) { PSX_HIP(hipEventSynchronize(ctx->ev_wait)); return PSX_OK; }
         for (;;) {
@@ -1225,14 +1156,12 @@ static int grid_filter(psx_ctx* ctx)
     const int fmax = ctx->cfg.filter_max_extrema;
     if (!((int)(fmax * 1.1) < total)) return PSX_OK;
 
-    int rc;
     size_t temp_bytes = 0;
     PSX_HIP(psx_gridfilter_sort_bytes(total, &temp_bytes));
-    if ((rc = grow(ctx, &ctx->d_gf_keys, &ctx->gf_keys_cap, 2 * (size_t)total)) != PSX_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_gf_vals, &ctx->gf_vals_cap, 2 * (size_t)total)) != PSX_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_gf_temp, &ctx->gf_temp_cap, temp_bytes + 256)) != PSX_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_gf_scratch, &ctx->gf_scratch_cap,
-                   psx_gridfilter_scratch_ints(ctx->cfg.filter_grid_size))) != PSX_OK) return rc;
+    PSX_HIP(ctx->d_gf_keys.grow(2 * (size_t)total));
+    PSX_HIP(ctx->d_gf_vals.grow(2 * (size_t)total));
+    PSX_HIP(ctx->d_gf_temp.grow(temp_bytes + 256));
+    PSX_HIP(ctx->d_gf_scratch.grow(psx_gridfilter_scratch_ints(ctx->cfg.filter_grid_size)));
     PSX_HIP(psx_launch_gridfilter(ctx->d_params, ctx->d_cnt, ctx->cfg.grid_filter_mode, total, fmax,
                                   ctx->d_gf_keys, ctx->d_gf_keys + total, ctx->d_gf_vals,
                                   ctx->d_gf_vals + total, ctx->d_gf_temp, temp_bytes, ctx->d_gf_scratch,
@@ -1259,7 +1188,7 @@ int psx_find_extrema(psx_ctx* ctx)
     ctx->ext_launched = false;
     PSX_HIP(psx_launch_refine(ctx->d_params, ctx->hp, ctx->d_cnt, mask_of(ctx), ctx->stream));
     ctx->filtered = false;
-    if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+    if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[2].h, ctx->stream));
     return PSX_OK;
 }
 
@@ -1274,8 +1203,18 @@ int psx_orientation(psx_ctx* ctx)
     }
     PSX_HIP(psx_launch_orientation(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->stream));
     snapshot_export(ctx);
-    PSX_HIP(psx_launch_scan(ctx->d_params, ctx->d_cnt, ctx->fx, ctx->stream));
-    if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+    PSX_HIP(psx_launch_scan(ctx->d_params, ctx->d_cnt, ctx->xp.fx, ctx->stream));
+    if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[3].h, ctx->stream));
+    return PSX_OK;
+}
+
+// the descriptor kernel of the configured mode, with the export targets of the frame in flight
+static int launch_descriptor_stage(psx_ctx* ctx)
+{
+    if (ctx->cfg.desc_mode == PSX_DESC_LOOP)
+        PSX_HIP(psx_launch_descriptors(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->xp.fx, ctx->stream));
+    else
+        PSX_HIP(psx_launch_descriptors_alt(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->cfg.desc_mode, ctx->xp.fx, ctx->stream));
     return PSX_OK;
 }
 
@@ -1284,18 +1223,15 @@ int psx_descriptors(psx_ctx* ctx)
     if (!ctx) return PSX_ERR_INVALID;
     if (!ctx->d_pyr) return fail(ctx, PSX_ERR_STATE, "psx_descriptors: no pyramid");
     PSX_HIP(hipSetDevice(ctx->device));
-    if (ctx->cfg.desc_mode == PSX_DESC_LOOP)
-        PSX_HIP(psx_launch_descriptors(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->fx, ctx->stream));
-    else
-        PSX_HIP(psx_launch_descriptors_alt(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->cfg.desc_mode, ctx->fx, ctx->stream));
-    if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
+    { const int rc = launch_descriptor_stage(ctx); if (rc != PSX_OK) return rc; }
+    if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[4].h, ctx->stream));
     return PSX_OK;
 }
 
 static int extract_chain(psx_ctx* ctx)
 {
     int rc;
-    ctx->interleave = !ctx->timers;        // per-stage timers need the stages back to back
+    ctx->interleave = !ctx->tm.on;        // per-stage timers need the stages back to back
     rc = psx_build_pyramid(ctx);
     ctx->interleave = false;
     if (rc != PSX_OK) return rc;
@@ -1304,58 +1240,53 @@ static int extract_chain(psx_ctx* ctx)
     return psx_descriptors(ctx);
 }
 
-static void drop_graph(psx_ctx* ctx)
-{
-    if (ctx->graph) { (void)hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
-}
-
 int psx_extract(psx_ctx* ctx)
 {
     if (!ctx) return PSX_ERR_INVALID;
     if (!ctx->d_input || !ctx->d_pyr) return fail(ctx, PSX_ERR_STATE, "psx_extract: no input image");
     { const int mrc = check_mask(ctx, "psx_extract"); if (mrc != PSX_OK) return mrc; }
     if (ctx->tune.null_device_work != 0) {
-        if (ctx->null_primed) {                    // measurement: no kernels; the first frame's results stand in
+        if (ctx->nulldev.primed) {                    // measurement: no kernels; the first frame's results stand in
             if (ctx->tune.null_device_work == 1) ctx->counts_valid = false;      // mode 1 reads the counters back per frame, like a real frame
             snapshot_export(ctx);
             return PSX_OK;
         }
-        ctx->null_primed = true;
+        ctx->nulldev.primed = true;
     }
     // Optionally replay the 36-launch chain as one hipGraph (POPSIFT_HIP_GRAPH=1).  Not with the grid filter
     // (it reads counters on the host in mid-chain) and not with the per-stage timers.
-    const bool use_graph = !ctx->graph_off && !ctx->timers && !ctx->blur_probe && ctx->cfg.filter_max_extrema <= 0;
+    const bool use_graph = !ctx->graph.off && !ctx->tm.on && !ctx->tm.probe && ctx->cfg.filter_max_extrema <= 0;
     if (!use_graph) return extract_chain(ctx);
     PSX_HIP(hipSetDevice(ctx->device));
-    if (ctx->graph && (ctx->graph_input != ctx->d_input || ctx->graph_is_float != ctx->input_is_float ||
-                       ctx->graph_w != ctx->in_w || ctx->graph_h != ctx->in_h || ctx->graph_mask != ctx->d_mask))
+    if (ctx->graph.exec.h && (ctx->graph.input != ctx->d_input || ctx->graph.is_float != ctx->input_is_float ||
+                       ctx->graph.w != ctx->in_w || ctx->graph.h != ctx->in_h || ctx->graph.mask != ctx->mask.data))
         drop_graph(ctx);
-    if (!ctx->graph) {
+    if (!ctx->graph.exec.h) {
         hipGraph_t g = nullptr;
         if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            ctx->graph_off = true;
+            ctx->graph.off = true;
             return extract_chain(ctx);
         }
         const int rc = extract_chain(ctx);
         const hipError_t e = hipStreamEndCapture(ctx->stream, &g);
         if (rc != PSX_OK || e != hipSuccess || g == nullptr ||
-            hipGraphInstantiate(&ctx->graph, g, nullptr, nullptr, 0) != hipSuccess) {
+            hipGraphInstantiate(&ctx->graph.exec.h, g, nullptr, nullptr, 0) != hipSuccess) {
             if (g) (void)hipGraphDestroy(g);
-            ctx->graph = nullptr;
-            ctx->graph_off = true;
+            ctx->graph.exec.h = nullptr;
+            ctx->graph.off = true;
             (void)hipGetLastError();
             return rc != PSX_OK ? rc : extract_chain(ctx);
         }
         (void)hipGraphDestroy(g);
-        ctx->graph_input = ctx->d_input; ctx->graph_is_float = ctx->input_is_float;
-        ctx->graph_w = ctx->in_w; ctx->graph_h = ctx->in_h;
-        ctx->graph_mask = ctx->d_mask;
+        ctx->graph.input = ctx->d_input; ctx->graph.is_float = ctx->input_is_float;
+        ctx->graph.w = ctx->in_w; ctx->graph.h = ctx->in_h;
+        ctx->graph.mask = ctx->mask.data;
     }
     ctx->counts_valid = false;
     ctx->filtered = false;
-    ctx->pyr_ready = true; ctx->kp_results = false;
+    ctx->pyr_ready = true; ctx->kp.results = false;
     snapshot_export(ctx);             // the captured kernels carry the targets attached at capture time; attach drops the graph
-    PSX_HIP(hipGraphLaunch(ctx->graph, ctx->stream));
+    PSX_HIP(hipGraphLaunch(ctx->graph.exec.h, ctx->stream));
     return PSX_OK;
 }
 
@@ -1370,29 +1301,15 @@ static int set_keypoints_common(psx_ctx* ctx, const psx_keypoint* p, int n, bool
     if (!ctx->d_input || !ctx->d_pyr) return fail(ctx, PSX_ERR_STATE, "psx_set_keypoints: no input image");
     if (on_device) {
         if (((uintptr_t)p & 7u) != 0) return fail(ctx, PSX_ERR_INVALID, "psx_set_keypoints_dev: the records must be 8-byte aligned");
-        ctx->d_kp = n > 0 ? p : nullptr; ctx->kp_n = n; ctx->kp_set = true;
+        ctx->kp.list = n > 0 ? p : nullptr; ctx->kp.n = n; ctx->kp.set = true;
         return PSX_OK;
     }
     PSX_HIP(hipSetDevice(ctx->device));
     if (n > 0) {
-        int rc;
-        if ((size_t)n > ctx->kp_own_cap) {
-            PSX_HIP(hipStreamSynchronize(ctx->stream));       // a describe call in flight may still read the old copy
-            if ((rc = grow(ctx, &ctx->d_kp_own, &ctx->kp_own_cap, (size_t)n + (size_t)n / 4)) != PSX_OK) return rc;
-        }
-        if (!ctx->ev_kp) PSX_HIP(hipEventCreateWithFlags(&ctx->ev_kp, hipEventDisableTiming));
-        else PSX_HIP(hipEventSynchronize(ctx->ev_kp));        // previous DMA out of the staging buffer
-        if ((size_t)n > ctx->kp_stage_cap) {
-            if (ctx->h_kp_stage) PSX_HIP(hipHostFree(ctx->h_kp_stage));
-            ctx->h_kp_stage = nullptr; ctx->kp_stage_cap = 0;
-            PSX_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_kp_stage), ((size_t)n + (size_t)n / 4) * sizeof(psx_keypoint), hipHostMallocDefault));
-            ctx->kp_stage_cap = (size_t)n + (size_t)n / 4;
-        }
-        memcpy(ctx->h_kp_stage, p, (size_t)n * sizeof(psx_keypoint));
-        PSX_HIP(hipMemcpyAsync(ctx->d_kp_own, ctx->h_kp_stage, (size_t)n * sizeof(psx_keypoint), hipMemcpyHostToDevice, ctx->stream));
-        PSX_HIP(hipEventRecord(ctx->ev_kp, ctx->stream));
+        const size_t room = (size_t)n + (size_t)n / 4;
+        PSX_HIP(ctx->kp.own.push(p, (size_t)n, room, room, ctx->stream));
     }
-    ctx->d_kp = n > 0 ? ctx->d_kp_own : nullptr; ctx->kp_n = n; ctx->kp_set = true;
+    ctx->kp.list = n > 0 ? ctx->kp.own.dev.p : nullptr; ctx->kp.n = n; ctx->kp.set = true;
     return PSX_OK;
 }
 
@@ -1404,7 +1321,7 @@ int psx_describe(psx_ctx* ctx, int flags)
     if (!ctx) return PSX_ERR_INVALID;
     if ((flags & ~PSX_DESCRIBE_REUSE_PYRAMID) != 0) return fail(ctx, PSX_ERR_INVALID, "psx_describe: unknown flag");
     if (!ctx->d_input || !ctx->d_pyr) return fail(ctx, PSX_ERR_STATE, "psx_describe: no input image");
-    if (!ctx->kp_set) return fail(ctx, PSX_ERR_STATE, "psx_describe: no keypoints set");
+    if (!ctx->kp.set) return fail(ctx, PSX_ERR_STATE, "psx_describe: no keypoints set");
     const bool reuse = (flags & PSX_DESCRIBE_REUSE_PYRAMID) != 0;
     if (reuse && !ctx->pyr_ready) return fail(ctx, PSX_ERR_STATE, "psx_describe: the context holds no pyramid of the current input");
     PSX_HIP(hipSetDevice(ctx->device));
@@ -1412,15 +1329,15 @@ int psx_describe(psx_ctx* ctx, int flags)
 
     // side arrays: one entry per extremum that can come out of this list
     int rc;
-    const size_t side = (size_t)imax(1, imin(ctx->kp_n, P.ext_capacity));
-    const size_t tbl_need = psx_kp_table_ints(P.num_octaves, ctx->kp_n);
-    if (side > ctx->kp_src_cap || tbl_need > ctx->kp_tbl_cap) {
+    const size_t side = (size_t)imax(1, imin(ctx->kp.n, P.ext_capacity));
+    const size_t tbl_need = psx_kp_table_ints(P.num_octaves, ctx->kp.n);
+    if (side > ctx->kp.src.cap || tbl_need > ctx->kp.tbl.cap) {
         PSX_HIP(hipStreamSynchronize(ctx->stream));
         const size_t room = side + side / 4;
-        if ((rc = grow(ctx, &ctx->d_kp_tbl, &ctx->kp_tbl_cap, tbl_need + tbl_need / 4)) != PSX_OK) return rc;
-        if ((rc = grow(ctx, &ctx->d_kp_src, &ctx->kp_src_cap, room)) != PSX_OK) return rc;
-        if ((rc = grow(ctx, &ctx->d_kp_gnori, &ctx->kp_gnori_cap, room)) != PSX_OK) return rc;
-        if ((rc = grow(ctx, &ctx->d_kp_gori, &ctx->kp_gori_cap, 4 * room)) != PSX_OK) return rc;
+        PSX_HIP(ctx->kp.tbl.grow(tbl_need + tbl_need / 4));
+        PSX_HIP(ctx->kp.src.grow(room));
+        PSX_HIP(ctx->kp.gnori.grow(room));
+        PSX_HIP(ctx->kp.gori.grow(4 * room));
     }
 
     if (!reuse) {
@@ -1428,7 +1345,7 @@ int psx_describe(psx_ctx* ctx, int flags)
         if ((rc = psx_build_pyramid(ctx)) != PSX_OK) return rc;
     } else {
         ctx->counts_valid = false;
-        if (ctx->timers) { PSX_HIP(hipEventRecord(ctx->ev[0], ctx->stream)); PSX_HIP(hipEventRecord(ctx->ev[1], ctx->stream)); }
+        if (ctx->tm.on) { PSX_HIP(hipEventRecord(ctx->tm.ev[0].h, ctx->stream)); PSX_HIP(hipEventRecord(ctx->tm.ev[1].h, ctx->stream)); }
     }
     ctx->ext_launched = false;
     ctx->filtered = false;
@@ -1439,18 +1356,18 @@ int psx_describe(psx_ctx* ctx, int flags)
     g.num_octaves = P.num_octaves;
     for (int o = 0; o < P.num_octaves; o++) { g.w[o] = P.oct[o].w; g.h[o] = P.oct[o].h; }
     PsxKpBuffers b;
-    b.kps = ctx->d_kp; b.n = ctx->kp_n;
-    b.tbl = ctx->d_kp_tbl; b.src = ctx->d_kp_src; b.gnori = ctx->d_kp_gnori; b.gori = ctx->d_kp_gori;
+    b.kps = ctx->kp.list; b.n = ctx->kp.n;
+    b.tbl = ctx->kp.tbl; b.src = ctx->kp.src; b.gnori = ctx->kp.gnori; b.gori = ctx->kp.gori;
     // every counter the later stages read is written by the injection (ext_ct of all octaves) or by the scan
     PSX_HIP(psx_launch_kp_inject(ctx->tune, ctx->d_params, ctx->d_cnt, g, b, ctx->stream));
-    if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+    if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[2].h, ctx->stream));
     PSX_HIP(psx_launch_orientation(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->stream));
     PSX_HIP(psx_launch_kp_adopt(ctx->tune, ctx->d_params, b, ctx->stream));
     snapshot_export(ctx);
-    PSX_HIP(psx_launch_scan(ctx->d_params, ctx->d_cnt, ctx->fx, ctx->stream));
-    if (ctx->timers) PSX_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+    PSX_HIP(psx_launch_scan(ctx->d_params, ctx->d_cnt, ctx->xp.fx, ctx->stream));
+    if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[3].h, ctx->stream));
     rc = psx_descriptors(ctx);
-    ctx->kp_results = rc == PSX_OK;
+    ctx->kp.results = rc == PSX_OK;
     return rc;
 }
 
@@ -1462,33 +1379,18 @@ static int set_mask_common(psx_ctx* ctx, const unsigned char* p, int w, int h, b
     const char* who = on_device ? "psx_set_mask_dev" : "psx_set_mask";
     if (!p) {
         if (w != 0 || h != 0) return fail(ctx, PSX_ERR_INVALID, std::string(who) + ": a null mask with a non-zero size");
-        ctx->d_mask = nullptr; ctx->mask_w = 0; ctx->mask_h = 0;         // cleared
+        ctx->mask.data = nullptr; ctx->mask.w = 0; ctx->mask.h = 0;         // cleared
         return PSX_OK;
     }
     if (w <= 0 || h <= 0) return fail(ctx, PSX_ERR_INVALID, std::string(who) + ": non-positive mask size");
     if (on_device) {
-        ctx->d_mask = p; ctx->mask_w = w; ctx->mask_h = h;
+        ctx->mask.data = p; ctx->mask.w = w; ctx->mask.h = h;
         return PSX_OK;
     }
     PSX_HIP(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)w * (size_t)h;
-    if (bytes > ctx->mask_own_cap) {
-        PSX_HIP(hipStreamSynchronize(ctx->stream));           // an extraction in flight may still read the old plane
-        int rc;
-        if ((rc = grow(ctx, &ctx->d_mask_own, &ctx->mask_own_cap, bytes)) != PSX_OK) return rc;
-    }
-    if (!ctx->ev_mask) PSX_HIP(hipEventCreateWithFlags(&ctx->ev_mask, hipEventDisableTiming));
-    else PSX_HIP(hipEventSynchronize(ctx->ev_mask));          // previous DMA out of the staging buffer
-    if (bytes > ctx->mask_stage_cap) {
-        if (ctx->h_mask_stage) PSX_HIP(hipHostFree(ctx->h_mask_stage));
-        ctx->h_mask_stage = nullptr; ctx->mask_stage_cap = 0;
-        PSX_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_mask_stage), bytes, hipHostMallocDefault));
-        ctx->mask_stage_cap = bytes;
-    }
-    memcpy(ctx->h_mask_stage, p, bytes);
-    PSX_HIP(hipMemcpyAsync(ctx->d_mask_own, ctx->h_mask_stage, bytes, hipMemcpyHostToDevice, ctx->stream));
-    PSX_HIP(hipEventRecord(ctx->ev_mask, ctx->stream));
-    ctx->d_mask = ctx->d_mask_own; ctx->mask_w = w; ctx->mask_h = h;
+    PSX_HIP(ctx->mask.own.push(p, bytes, bytes, bytes, ctx->stream));
+    ctx->mask.data = ctx->mask.own.dev; ctx->mask.w = w; ctx->mask.h = h;
     return PSX_OK;
 }
 
@@ -1506,14 +1408,14 @@ int psx_mask_keep(const unsigned char* mask, int w, int h, const float* xpos, co
 int psx_keypoint_map(psx_ctx* ctx, int* host_src, int capacity, int* count)
 {
     if (!ctx) return PSX_ERR_INVALID;
-    if (!ctx->kp_results) return fail(ctx, PSX_ERR_STATE, "psx_keypoint_map: the last results are not a psx_describe call's");
+    if (!ctx->kp.results) return fail(ctx, PSX_ERR_STATE, "psx_keypoint_map: the last results are not a psx_describe call's");
     int rc = fetch_counts(ctx);
     if (rc != PSX_OK) return rc;
     const int n = ctx->h_cnt->ext_total;
     if (count) *count = n;
     if (host_src) {
         if (n > capacity) return fail(ctx, PSX_ERR_INVALID, "psx_keypoint_map: output capacity too small");
-        if (n > 0) PSX_HIP(hipMemcpy(host_src, ctx->d_kp_src, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        if (n > 0) PSX_HIP(hipMemcpy(host_src, ctx->kp.src, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
     }
     return PSX_OK;
 }
@@ -1526,7 +1428,6 @@ int psx_sync(psx_ctx* ctx)
     return PSX_OK;
 }
 
-static int fetch_counts(psx_ctx* ctx);
 static int fetch_counts_full(psx_ctx* ctx)
 {
     if (ctx->counts_valid && !ctx->counts_partial) return PSX_OK;
@@ -1548,28 +1449,23 @@ static int regrow_descriptors(psx_ctx* ctx, int ori_raw)
 {
     PsxParams& P = ctx->hp;
     const size_t need = (size_t)ori_raw + (size_t)ori_raw / 4 + 1024;
-    int rc;
     PSX_HIP(hipStreamSynchronize(ctx->stream));
-    if ((rc = grow(ctx, &ctx->d_desc, &ctx->desc_cap, need * 128)) != PSX_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_feat_to_ext, &ctx->f2e_cap, need)) != PSX_OK) return rc;
+    PSX_HIP(ctx->d_desc.grow(need * 128));
+    PSX_HIP(ctx->d_feat_to_ext.grow(need));
     // the byte array of a frame launched in byte mode grows with the floats (it is a kernel argument: the repeat carries the new one)
-    if (ctx->fx.desc_u8 != nullptr) {
-        if ((rc = grow(ctx, &ctx->d_desc_u8, &ctx->desc_u8_cap, ctx->desc_cap)) != PSX_OK) return rc;
-        ctx->fx.desc_u8 = ctx->d_desc_u8;
+    if (ctx->xp.fx.desc_u8 != nullptr) {
+        PSX_HIP(ctx->d_desc_u8.grow(ctx->d_desc.cap));
+        ctx->xp.fx.desc_u8 = ctx->d_desc_u8;
     }
     P.desc = ctx->d_desc;
     P.feat_to_ext = ctx->d_feat_to_ext;
     P.ori_capacity = (int)need;
     *ctx->h_params_pin = P;
     PSX_HIP(hipMemcpyAsync(ctx->d_params, ctx->h_params_pin, sizeof(P), hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->graph) { (void)hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
+    drop_graph(ctx);
     // same targets as the launch being repeated
-    PSX_HIP(psx_launch_scan(ctx->d_params, ctx->d_cnt, ctx->fx, ctx->stream));
-    if (ctx->cfg.desc_mode == PSX_DESC_LOOP)
-        PSX_HIP(psx_launch_descriptors(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->fx, ctx->stream));
-    else
-        PSX_HIP(psx_launch_descriptors_alt(ctx->tune, ctx->d_params, ctx->d_cnt, ctx->cfg.desc_mode, ctx->fx, ctx->stream));
-    return PSX_OK;
+    PSX_HIP(psx_launch_scan(ctx->d_params, ctx->d_cnt, ctx->xp.fx, ctx->stream));
+    return launch_descriptor_stage(ctx);
 }
 
 static int fetch_counts(psx_ctx* ctx)
@@ -1578,13 +1474,13 @@ static int fetch_counts(psx_ctx* ctx)
     PSX_HIP(hipSetDevice(ctx->device));
     for (int attempt = 0; attempt < 2; attempt++) {
         int raw;
-        if (ctx->fx_on) {
+        if (ctx->xp.fx_on) {
             // the frame was launched with export targets: its scan kernel deposited the counters in pinned memory
             { int wrc = wait_stream(ctx); if (wrc != PSX_OK) return wrc; }
-            ctx->h_cnt->ext_total = ctx->h_xcnt[0];
-            ctx->h_cnt->ori_total = ctx->h_xcnt[1];
-            raw = ctx->h_xcnt[2];
-            ctx->h_cnt->flow_error = ctx->h_xcnt[3];
+            ctx->h_cnt->ext_total = ctx->xp.counts[0];
+            ctx->h_cnt->ori_total = ctx->xp.counts[1];
+            raw = ctx->xp.counts[2];
+            ctx->h_cnt->flow_error = ctx->xp.counts[3];
             ctx->counts_partial = true;
         } else {
             PSX_HIP(hipMemcpyAsync(ctx->h_cnt, ctx->d_cnt, sizeof(PsxCounters), hipMemcpyDeviceToHost, ctx->stream));
@@ -1613,53 +1509,53 @@ int psx_counts(psx_ctx* ctx, int* num_features, int* num_descriptors)
     return PSX_OK;
 }
 
+// both download calls.  who: the caller's name in the error strings; dev_desc: the descriptor array (elem_bytes per value);
+// exported_host_desc: the export target of that array the frame in flight was launched with
+static int download_results(psx_ctx* ctx, const char* who, psx_feature* features, int feature_capacity, void* descriptors,
+                            int descriptor_capacity, size_t elem_bytes, const void* dev_desc, const void* exported_host_desc)
+{
+    const int ne = ctx->h_cnt->ext_total, no = ctx->h_cnt->ori_total;
+    if (ne > feature_capacity || no > descriptor_capacity)
+        return fail(ctx, PSX_ERR_INVALID, std::string(who) + ": output capacity too small");
+    if (ne > 0 && !features) return fail(ctx, PSX_ERR_INVALID, std::string(who) + ": null feature buffer");
+    if (no > 0 && !descriptors) return fail(ctx, PSX_ERR_INVALID, std::string(who) + ": null descriptor buffer");
+    const bool feat_exported = (ctx->xp.fx_on && features == ctx->xp.fx_host_feat && ne <= ctx->xp.fx.feat_capacity);
+    const bool desc_exported = (ctx->xp.fx_on && descriptors == exported_host_desc && no <= ctx->xp.fx.desc_capacity);
+    if (elem_bytes == sizeof(float)) {
+        // PSX_NULL_DEVICE_WORK=2: one real download per CONTEXT keeps its host records well formed (a process-wide flag was a
+        // data race between the workers and left every context but the first with uninitialised host buffers)
+        if (ctx->tune.null_device_work == 2 && ctx->nulldev.primed && ctx->nulldev.dl_done) return PSX_OK;
+        if (ctx->tune.null_device_work == 2 && ctx->nulldev.primed) ctx->nulldev.dl_done = true;
+    }
+    if (ne > 0 && !feat_exported)
+        PSX_HIP(hipMemcpyAsync(features, ctx->d_features, (size_t)ne * sizeof(psx_feature),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    if (no > 0 && !desc_exported)
+        PSX_HIP(hipMemcpyAsync(descriptors, dev_desc, (size_t)no * 128 * elem_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    // sleep on an event when the context is in blocking mode (the C++ pipeline's workers): hipStreamSynchronize spins, and
+    // the ~0.3 ms of a frame's result DMA -- several ms when replicas share a GPU -- were a busy core per worker
+    return wait_stream(ctx);
+}
+
 int psx_download(psx_ctx* ctx, psx_feature* features, int feature_capacity, float* descriptors,
                  int descriptor_capacity)
 {
     if (!ctx) return PSX_ERR_INVALID;
     int rc = fetch_counts(ctx);
     if (rc != PSX_OK) return rc;
-    const int ne = ctx->h_cnt->ext_total, no = ctx->h_cnt->ori_total;
-    if (ne > feature_capacity || no > descriptor_capacity)
-        return fail(ctx, PSX_ERR_INVALID, "psx_download: output capacity too small");
-    if (ne > 0 && !features) return fail(ctx, PSX_ERR_INVALID, "psx_download: null feature buffer");
-    if (no > 0 && !descriptors) return fail(ctx, PSX_ERR_INVALID, "psx_download: null descriptor buffer");
-    const bool feat_exported = (ctx->fx_on && features == ctx->fx_host_feat && ne <= ctx->fx.feat_capacity);
-    const bool desc_exported = (ctx->fx_on && descriptors == ctx->fx_host_desc && no <= ctx->fx.desc_capacity);
-    // PSX_NULL_DEVICE_WORK=2: one real download per CONTEXT keeps its host records well formed (a process-wide flag was a
-    // data race between the workers and left every context but the first with uninitialised host buffers)
-    if (ctx->tune.null_device_work == 2 && ctx->null_primed && ctx->null_dl_done) return PSX_OK;
-    if (ctx->tune.null_device_work == 2 && ctx->null_primed) ctx->null_dl_done = true;
-    if (ne > 0 && !feat_exported)
-        PSX_HIP(hipMemcpyAsync(features, ctx->d_features, (size_t)ne * sizeof(psx_feature),
-                               hipMemcpyDeviceToHost, ctx->stream));
-    if (no > 0 && !desc_exported)
-        PSX_HIP(hipMemcpyAsync(descriptors, ctx->d_desc, (size_t)no * 128 * sizeof(float),
-                               hipMemcpyDeviceToHost, ctx->stream));
-    // sleep on an event when the context is in blocking mode (the C++ pipeline's workers): hipStreamSynchronize spins, and
-    // the ~0.3 ms of a frame's result DMA -- several ms when replicas share a GPU -- were a busy core per worker
-    return wait_stream(ctx);
+    return download_results(ctx, "psx_download", features, feature_capacity, descriptors, descriptor_capacity, sizeof(float),
+                            ctx->d_desc, ctx->xp.fx_host_desc);
 }
 
-// the byte export is detached by every attach call (float or byte); the caller has waited for the stream if it was registered
-static void detach_u8(psx_ctx* ctx)
+// Detach everything exported; both attach calls start here.  Memory an earlier psx_attach_export had to register is a
+// reason to wait first: the frame in flight may still be storing into it.  Without any, no HIP call.
+static int detach_exports(psx_ctx* ctx, bool always_wait)
 {
-    if (ctx->x_registered_u8) { (void)hipHostUnregister(ctx->x_host_u8); ctx->x_registered_u8 = false; }
-    ctx->x_host_u8 = ctx->x_dev_u8 = nullptr;
-}
-
-static int map_host(psx_ctx* ctx, void* host, size_t bytes, void** dev, bool* registered)
-{
-    *registered = false;
-    *dev = nullptr;
-    hipPointerAttribute_t attr;
-    hipError_t e = hipPointerGetAttributes(&attr, host);
-    if (e != hipSuccess || attr.type == hipMemoryTypeUnregistered) {
-        (void)hipGetLastError();
-        PSX_HIP(hipHostRegister(host, bytes, hipHostRegisterMapped));
-        *registered = true;
+    if (always_wait || ctx->xp.feat.registered || ctx->xp.desc.registered || ctx->xp.u8.registered) {
+        PSX_HIP(hipSetDevice(ctx->device));
+        PSX_HIP(hipStreamSynchronize(ctx->stream));
     }
-    PSX_HIP(hipHostGetDevicePointer(dev, host, 0));
+    ctx->xp.feat.reset(); ctx->xp.desc.reset(); ctx->xp.u8.reset();
     return PSX_OK;
 }
 
@@ -1667,29 +1563,12 @@ int psx_attach_export(psx_ctx* ctx, psx_feature* host_features, int feature_capa
                       float* host_descriptors, int descriptor_capacity)
 {
     if (!ctx) return PSX_ERR_INVALID;
-    PSX_HIP(hipSetDevice(ctx->device));
-    PSX_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->x_registered_feat) { (void)hipHostUnregister(ctx->x_host_feat); ctx->x_registered_feat = false; }
-    if (ctx->x_registered_desc) { (void)hipHostUnregister(ctx->x_host_desc); ctx->x_registered_desc = false; }
-    detach_u8(ctx);
-    ctx->x_host_feat = nullptr; ctx->x_host_desc = nullptr;
-    ctx->x_dev_feat = nullptr; ctx->x_dev_desc = nullptr;
-    ctx->x_feat_cap = ctx->x_desc_cap = 0;
-    if (host_features && feature_capacity > 0) {
-        void* d = nullptr;
-        int rc = map_host(ctx, host_features, (size_t)feature_capacity * sizeof(psx_feature), &d, &ctx->x_registered_feat);
-        if (rc != PSX_OK) return rc;
-        ctx->x_host_feat = host_features; ctx->x_dev_feat = static_cast<psx_feature*>(d);
-        ctx->x_feat_cap = feature_capacity;
-    }
-    if (host_descriptors && descriptor_capacity > 0) {
-        void* d = nullptr;
-        int rc = map_host(ctx, host_descriptors, (size_t)descriptor_capacity * 128 * sizeof(float), &d, &ctx->x_registered_desc);
-        if (rc != PSX_OK) return rc;
-        ctx->x_host_desc = host_descriptors; ctx->x_dev_desc = static_cast<float*>(d);
-        ctx->x_desc_cap = descriptor_capacity;
-    }
-    if (ctx->graph) { (void)hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }      // the targets are kernel arguments
+    { const int rc = detach_exports(ctx, true); if (rc != PSX_OK) return rc; }
+    if (host_features && feature_capacity > 0)
+        PSX_HIP(ctx->xp.feat.attach(host_features, (size_t)feature_capacity * sizeof(psx_feature), feature_capacity));
+    if (host_descriptors && descriptor_capacity > 0)
+        PSX_HIP(ctx->xp.desc.attach(host_descriptors, (size_t)descriptor_capacity * 128 * sizeof(float), descriptor_capacity));
+    drop_graph(ctx);      // the targets are kernel arguments
     return PSX_OK;
 }
 
@@ -1699,21 +1578,12 @@ int psx_attach_export_mapped(psx_ctx* ctx, psx_feature* host_features, int featu
     if (!ctx) return PSX_ERR_INVALID;
     // Normally no HIP call: the targets travel as kernel arguments of the NEXT extraction; the frame in flight (if
     // any) keeps the targets it was launched with, and its counters / results are still fetched from those
-    // (psx_ctx::fx).  Only buffers an earlier psx_attach_export had to register are a reason to wait: the frame
-    // in flight may still be storing into them.
-    if (ctx->x_registered_feat || ctx->x_registered_desc || ctx->x_registered_u8) {
-        PSX_HIP(hipSetDevice(ctx->device));
-        PSX_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    if (ctx->x_registered_feat) { (void)hipHostUnregister(ctx->x_host_feat); ctx->x_registered_feat = false; }
-    if (ctx->x_registered_desc) { (void)hipHostUnregister(ctx->x_host_desc); ctx->x_registered_desc = false; }
-    detach_u8(ctx);
+    // (psx_ctx::xp.fx).
+    { const int rc = detach_exports(ctx, false); if (rc != PSX_OK) return rc; }
     // psx_host_alloc memory: mapped, and its device address is its host address (checked at allocation)
-    ctx->x_host_feat = ctx->x_dev_feat = (host_features && feature_capacity > 0) ? host_features : nullptr;
-    ctx->x_host_desc = ctx->x_dev_desc = (host_descriptors && descriptor_capacity > 0) ? host_descriptors : nullptr;
-    ctx->x_feat_cap = ctx->x_dev_feat ? feature_capacity : 0;
-    ctx->x_desc_cap = ctx->x_dev_desc ? descriptor_capacity : 0;
-    if (ctx->graph) { (void)hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }
+    ctx->xp.feat.adopt(feature_capacity > 0 ? host_features : nullptr, feature_capacity);
+    ctx->xp.desc.adopt(descriptor_capacity > 0 ? host_descriptors : nullptr, descriptor_capacity);
+    drop_graph(ctx);
     return PSX_OK;
 }
 
@@ -1731,17 +1601,15 @@ int psx_set_descriptor_format(psx_ctx* ctx, int fmt)
     // switching back to float mode keeps the byte array (a frame in flight may still be storing into it).  grow() replaces
     // it only when the float array has grown since it was sized; hipFree waits for the device to be idle, so no frame in
     // flight still stores into the old one -- the same rule as every other buffer grow() replaces
-    if (fmt == PSX_DESCFMT_U8 && ctx->desc_cap > 0) {
-        const int rc = grow(ctx, &ctx->d_desc_u8, &ctx->desc_u8_cap, ctx->desc_cap);
-        if (rc != PSX_OK) return rc;
+    if (fmt == PSX_DESCFMT_U8 && ctx->d_desc.cap > 0) {
+        PSX_HIP(ctx->d_desc_u8.grow(ctx->d_desc.cap));
     }
-    if (fmt == PSX_DESCFMT_F32 && ctx->x_dev_u8) {
-        if (ctx->x_registered_u8) PSX_HIP(hipStreamSynchronize(ctx->stream));
-        detach_u8(ctx);
-        ctx->x_desc_cap = 0;
+    if (fmt == PSX_DESCFMT_F32 && ctx->xp.u8.dev) {
+        if (ctx->xp.u8.registered) PSX_HIP(hipStreamSynchronize(ctx->stream));
+        ctx->xp.u8.reset();
     }
     ctx->desc_fmt = fmt;
-    if (ctx->graph) { (void)hipGraphExecDestroy(ctx->graph); ctx->graph = nullptr; }      // the byte array is a kernel argument
+    drop_graph(ctx);      // the byte array is a kernel argument
     return PSX_OK;
 }
 
@@ -1753,20 +1621,9 @@ int psx_download_u8(psx_ctx* ctx, psx_feature* features, int feature_capacity, u
     int rc = fetch_counts(ctx);
     if (rc != PSX_OK) return rc;
     // the frame must have been launched in byte mode (the format switched after its launch leaves no bytes of it)
-    if (ctx->fx.desc_u8 == nullptr) return fail(ctx, PSX_ERR_STATE, "psx_download_u8: the last extraction ran in float mode");
-    const int ne = ctx->h_cnt->ext_total, no = ctx->h_cnt->ori_total;
-    if (ne > feature_capacity || no > descriptor_capacity)
-        return fail(ctx, PSX_ERR_INVALID, "psx_download_u8: output capacity too small");
-    if (ne > 0 && !features) return fail(ctx, PSX_ERR_INVALID, "psx_download_u8: null feature buffer");
-    if (no > 0 && !descriptors) return fail(ctx, PSX_ERR_INVALID, "psx_download_u8: null descriptor buffer");
-    const bool feat_exported = (ctx->fx_on && features == ctx->fx_host_feat && ne <= ctx->fx.feat_capacity);
-    const bool desc_exported = (ctx->fx_on && descriptors == ctx->fx_host_u8 && no <= ctx->fx.desc_capacity);
-    if (ne > 0 && !feat_exported)
-        PSX_HIP(hipMemcpyAsync(features, ctx->d_features, (size_t)ne * sizeof(psx_feature),
-                               hipMemcpyDeviceToHost, ctx->stream));
-    if (no > 0 && !desc_exported)
-        PSX_HIP(hipMemcpyAsync(descriptors, ctx->d_desc_u8, (size_t)no * 128, hipMemcpyDeviceToHost, ctx->stream));
-    return wait_stream(ctx);
+    if (ctx->xp.fx.desc_u8 == nullptr) return fail(ctx, PSX_ERR_STATE, "psx_download_u8: the last extraction ran in float mode");
+    return download_results(ctx, "psx_download_u8", features, feature_capacity, descriptors, descriptor_capacity, 1,
+                            ctx->d_desc_u8, ctx->xp.fx_host_u8);
 }
 
 // both byte attach calls: the float descriptor export is detached, the feature export is replaced
@@ -1780,15 +1637,8 @@ static int attach_u8_common(psx_ctx* ctx, psx_feature* host_features, int featur
                     : psx_attach_export(ctx, host_features, feature_capacity, nullptr, 0);
     if (rc != PSX_OK) return rc;
     if (host_descriptors && descriptor_capacity > 0) {
-        if (mapped) {
-            ctx->x_host_u8 = ctx->x_dev_u8 = host_descriptors;
-        } else {
-            void* d = nullptr;
-            rc = map_host(ctx, host_descriptors, (size_t)descriptor_capacity * 128, &d, &ctx->x_registered_u8);
-            if (rc != PSX_OK) return rc;
-            ctx->x_host_u8 = host_descriptors; ctx->x_dev_u8 = static_cast<unsigned char*>(d);
-        }
-        ctx->x_desc_cap = descriptor_capacity;
+        if (mapped) ctx->xp.u8.adopt(host_descriptors, descriptor_capacity);
+        else PSX_HIP(ctx->xp.u8.attach(host_descriptors, (size_t)descriptor_capacity * 128, descriptor_capacity));
     }
     return PSX_OK;
 }
@@ -1999,17 +1849,17 @@ int psx_set_wait_mode(psx_ctx* ctx, int blocking)
 int psx_enable_timers(psx_ctx* ctx, int on)
 {
     if (!ctx) return PSX_ERR_INVALID;
-    ctx->timers = on != 0;
+    ctx->tm.on = on != 0;
     return PSX_OK;
 }
 
 int psx_stage_times(psx_ctx* ctx, float ms[4])
 {
     if (!ctx || !ms) return PSX_ERR_INVALID;
-    if (!ctx->timers) return fail(ctx, PSX_ERR_STATE, "timers are not enabled");
+    if (!ctx->tm.on) return fail(ctx, PSX_ERR_STATE, "timers are not enabled");
     PSX_HIP(hipSetDevice(ctx->device));
     PSX_HIP(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 4; i++) PSX_HIP(hipEventElapsedTime(&ms[i], ctx->ev[i], ctx->ev[i + 1]));
+    for (int i = 0; i < 4; i++) PSX_HIP(hipEventElapsedTime(&ms[i], ctx->tm.ev[i].h, ctx->tm.ev[i + 1].h));
     return PSX_OK;
 }
 
@@ -2020,15 +1870,15 @@ int psx_time_blur(psx_ctx* ctx, int octave, int level, int reps, float* avg_ms, 
     if (!ctx->d_pyr || octave < 0 || octave >= P.num_octaves || level < 1 || level >= P.L || reps < 1)
         return fail(ctx, PSX_ERR_INVALID, "psx_time_blur: bad arguments");
     PSX_HIP(hipSetDevice(ctx->device));
-    PSX_HIP(hipEventRecord(ctx->ev_t0, ctx->stream));
+    PSX_HIP(hipEventRecord(ctx->tm.t0, ctx->stream));
     for (int r = 0; r < reps; r++) {
         int rc = launch_blur_level(ctx, octave, level);
         if (rc != PSX_OK) return rc;
     }
-    PSX_HIP(hipEventRecord(ctx->ev_t1, ctx->stream));
+    PSX_HIP(hipEventRecord(ctx->tm.t1, ctx->stream));
     PSX_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0.0f;
-    PSX_HIP(hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1));
+    PSX_HIP(hipEventElapsedTime(&ms, ctx->tm.t0, ctx->tm.t1));
     *avg_ms = ms / reps;
     if (bytes) *bytes = 8.0 * (double)P.oct[octave].w * (double)P.oct[octave].h;
     return PSX_OK;
@@ -2048,28 +1898,24 @@ int psx_enable_blur_probe(psx_ctx* ctx, int on)
 {
     if (!ctx) return PSX_ERR_INVALID;
     PSX_HIP(hipSetDevice(ctx->device));
-    if (on)
-        for (int i = 0; i < 2 * PSX_GAUSS_LEVELS; i++)
-            if (!ctx->ev_blur[i]) PSX_HIP(hipEventCreate(&ctx->ev_blur[i]));
-    if (on)
-        for (int i = 0; i < 4; i++)
-            if (!ctx->ev_x[i]) PSX_HIP(hipEventCreate(&ctx->ev_x[i]));
-    ctx->blur_probe = on != 0;
-    ctx->probe_ext0 = false;
-    ctx->blur_probe_n = 0;
+    for (int i = 0; on && i < 2 * PSX_GAUSS_LEVELS; i++) PSX_HIP(ctx->tm.ev_blur[i].get(hipEventDefault));
+    for (int i = 0; on && i < 4; i++) PSX_HIP(ctx->tm.ev_x[i].get(hipEventDefault));
+    ctx->tm.probe = on != 0;
+    ctx->tm.probe_ext0 = false;
+    ctx->tm.probe_n = 0;
     return PSX_OK;
 }
 
 int psx_blur_probe_times(psx_ctx* ctx, float* ms, int capacity, int* n, double* bytes_per_launch)
 {
     if (!ctx || !ms || !n) return PSX_ERR_INVALID;
-    if (!ctx->blur_probe) return fail(ctx, PSX_ERR_STATE, "the blur probe is not enabled");
+    if (!ctx->tm.probe) return fail(ctx, PSX_ERR_STATE, "the blur probe is not enabled");
     PSX_HIP(hipSetDevice(ctx->device));
     PSX_HIP(hipStreamSynchronize(ctx->stream));
-    *n = ctx->blur_probe_n;
-    for (int i = 0; i < ctx->blur_probe_n && i < capacity; i++)
-        PSX_HIP(hipEventElapsedTime(&ms[i], ctx->ev_blur[2 * i], ctx->ev_blur[2 * i + 1]));
-    if (bytes_per_launch) *bytes_per_launch = ctx->blur_probe_bytes;
+    *n = ctx->tm.probe_n;
+    for (int i = 0; i < ctx->tm.probe_n && i < capacity; i++)
+        PSX_HIP(hipEventElapsedTime(&ms[i], ctx->tm.ev_blur[2 * i].h, ctx->tm.ev_blur[2 * i + 1].h));
+    if (bytes_per_launch) *bytes_per_launch = ctx->tm.probe_bytes;
     return PSX_OK;
 }
 
@@ -2079,18 +1925,19 @@ int psx_blur_probe_times(psx_ctx* ctx, float* ms, int capacity, int* n, double* 
 int psx_flow_trace(psx_ctx* ctx, long long* host_out, int capacity_items, int* nitems)
 {
     if (!ctx || !nitems) return PSX_ERR_INVALID;
-    *nitems = ctx->flow_on ? ctx->flow_nitems : 0;
-    if (!ctx->flow_on || host_out == nullptr || capacity_items < ctx->flow_nitems) return PSX_OK;
+    *nitems = ctx->flow.on ? ctx->flow.nitems : 0;
+    if (!ctx->flow.on || host_out == nullptr || capacity_items < ctx->flow.nitems) return PSX_OK;
     PSX_HIP(hipSetDevice(ctx->device));
     PSX_HIP(hipStreamSynchronize(ctx->stream));
-    const size_t bytes = sizeof(long long) * 6 * (size_t)ctx->flow_nitems;
-    PSX_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_flow_trace), bytes));
-    (void)hipMemset(ctx->d_flow_trace, 0, bytes);
+    const size_t bytes = sizeof(long long) * 6 * (size_t)ctx->flow.nitems;
+    DevBuf<long long> trace;
+    PSX_HIP(trace.grow(6 * (size_t)ctx->flow.nitems));
+    (void)hipMemset(trace, 0, bytes);
+    ctx->flow.trace = trace;
     int rc = psx_build_pyramid(ctx);
+    ctx->flow.trace = nullptr;
     hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(host_out, ctx->d_flow_trace, bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(ctx->d_flow_trace);
-    ctx->d_flow_trace = nullptr;
+    if (e == hipSuccess) e = hipMemcpy(host_out, trace, bytes, hipMemcpyDeviceToHost);
     if (rc != PSX_OK) return rc;
     PSX_HIP(e);
     return PSX_OK;
@@ -2103,13 +1950,13 @@ int psx_flow_trace(psx_ctx* ctx, long long* host_out, int capacity_items, int* n
 int psx_probe_extra_times(psx_ctx* ctx, float* level0_ms, double* level0_bytes, float* extrema_ms, double* extrema_bytes)
 {
     if (!ctx || !level0_ms || !extrema_ms) return PSX_ERR_INVALID;
-    if (!ctx->blur_probe) return fail(ctx, PSX_ERR_STATE, "the blur probe is not enabled");
+    if (!ctx->tm.probe) return fail(ctx, PSX_ERR_STATE, "the blur probe is not enabled");
     PSX_HIP(hipSetDevice(ctx->device));
     PSX_HIP(hipStreamSynchronize(ctx->stream));
     const PsxParams& P = ctx->hp;
     *level0_ms = 0.0f; *extrema_ms = 0.0f;
-    if (!ctx->alt_pyramid) PSX_HIP(hipEventElapsedTime(level0_ms, ctx->ev_x[0], ctx->ev_x[1]));
-    if (ctx->probe_ext0) PSX_HIP(hipEventElapsedTime(extrema_ms, ctx->ev_x[2], ctx->ev_x[3]));
+    if (!ctx->alt_pyramid) PSX_HIP(hipEventElapsedTime(level0_ms, ctx->tm.ev_x[0].h, ctx->tm.ev_x[1].h));
+    if (ctx->tm.probe_ext0) PSX_HIP(hipEventElapsedTime(extrema_ms, ctx->tm.ev_x[2].h, ctx->tm.ev_x[3].h));
     const double n0 = (double)P.oct[0].w * P.oct[0].h;
     if (level0_bytes) *level0_bytes = 4.0 * n0 + (double)ctx->in_w * ctx->in_h * (ctx->input_is_float ? 4.0 : 1.0);
     if (extrema_bytes) *extrema_bytes = 4.0 * (double)P.L * n0;

@@ -99,6 +99,18 @@ struct PsxCounters {
 
 struct PsxTaps { float g[PSX_GAUSS_ALIGN]; };
 
+// The Gauss tables of a configuration (host arithmetic of gauss_filter.cu:127-410): per table a row of PSX_GAUSS_ALIGN
+// taps, the span and the sigma of every level (dd: of every octave)
+struct PsxGaussTables {
+    float inc_filter[PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN];  int inc_span[PSX_GAUSS_LEVELS];  float inc_sigma[PSX_GAUSS_LEVELS];
+    float dd_filter[PSX_MAX_OCTAVES * PSX_GAUSS_ALIGN];    int dd_span[PSX_MAX_OCTAVES];    float dd_sigma[PSX_MAX_OCTAVES];
+    // tables of the alternative pyramid modes (gauss_filter.cu:188-214, 373-410): absolute filters of octave 0 and of the
+    // other octaves, and the interpolated (ratio, multiplier) form of the inc table, whose sigmas are inc_sigma
+    float abs0_filter[PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN]; int abs0_span[PSX_GAUSS_LEVELS]; float abs0_sigma[PSX_GAUSS_LEVELS];
+    float absN_filter[PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN]; int absN_span[PSX_GAUSS_LEVELS]; float absN_sigma[PSX_GAUSS_LEVELS];
+    float inc_ifilter[PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN]; int inc_ispan[PSX_GAUSS_LEVELS];
+};
+
 // ---- host-side launch helpers implemented in the .hip files ---------------------------------
 // t: the context's snapshot of the environment switches and its device's CU count (psx_tuning.h); nothing below api.hip
 // asks the environment or the current device
@@ -179,8 +191,7 @@ struct PsxAltArgs {
     const void* img; int w, h, is_float;
     int gauss_mode, scaling_mode, sift_mode;
     float upscale_factor;
-    const float *inc_filter, *inc_ifilter, *dd_filter, *abs0_filter, *absN_filter;      // host tables
-    const int *inc_span, *inc_ispan, *dd_span, *abs0_span;
+    const PsxGaussTables* tab;   // host tables
     float* up; int up_pitch;     // scratch of psx_launch_level0 (the resampled, padded input: PsxLevel0Args::tmp)
     float* intm;                 // scratch: one plane of octave 0 (pitch x height)
     float* vbuf; int vbuf_pitch; // scratch of the fixed-span modes: pitch + 2*7 columns

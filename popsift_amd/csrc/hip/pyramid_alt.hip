@@ -250,7 +250,7 @@ static PsxInterpJob interp_job(const PsxAltArgs& a, int o, int l, bool feeds)
     j.src = oc.data + (size_t)(l - 1) * oc.plane; j.dst = oc.data + (size_t)l * oc.plane;
     j.half_dst = feeds ? P.oct[o + 1].data : nullptr; j.half_pitch = feeds ? P.oct[o + 1].pitch : 0;
     j.W = oc.w; j.H = oc.h; j.pitch = oc.pitch;
-    j.fi = a.inc_ifilter + l * PSX_GAUSS_ALIGN; j.ispan = a.inc_ispan[l];
+    j.fi = a.tab->inc_ifilter + l * PSX_GAUSS_ALIGN; j.ispan = a.tab->inc_ispan[l];
     return j;
 }
 
@@ -276,7 +276,7 @@ static hipError_t relative_diagonal(const PsxAltArgs& a, hipStream_t s)
             hipError_t e;
             if (i + 1 < n) {
                 const int o2 = os[i + 1], l2 = t - D * o2;
-                if (psx_blur_interp_pair_ok(tune, P.oct[o1].w, P.oct[o1].h, a.inc_ispan[l1], P.oct[o2].w, P.oct[o2].h, a.inc_ispan[l2])) {
+                if (psx_blur_interp_pair_ok(tune, P.oct[o1].w, P.oct[o1].h, a.tab->inc_ispan[l1], P.oct[o2].w, P.oct[o2].h, a.tab->inc_ispan[l2])) {
                     e = psx_launch_blur_interp2(tune, job(o1, l1), job(o2, l2), s);
                     if (e != hipSuccess) return e;
                     i += 2;
@@ -307,8 +307,8 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
     if (fixed && P.L != 6) return hipErrorInvalidValue;
     const AltImg img{a.img, a.w, a.h, a.is_float};
     auto taps = [](const float* row) { PsxTaps t; for (int i = 0; i < PSX_GAUSS_ALIGN; i++) t.g[i] = row[i]; return t; };
-    auto inc = [&](int l) { return taps(a.inc_filter + l * PSX_GAUSS_ALIGN); };
-    auto inci = [&](int l) { return taps(a.inc_ifilter + l * PSX_GAUSS_ALIGN); };
+    auto inc = [&](int l) { return taps(a.tab->inc_filter + l * PSX_GAUSS_ALIGN); };
+    auto inci = [&](int l) { return taps(a.tab->inc_ifilter + l * PSX_GAUSS_ALIGN); };
     bool next_l0_done = false;          // level 0 of this octave was written by the previous octave's fused launch
     for (int o = 0; o < P.num_octaves; o++) {
         const PsxOctave& oc = P.oct[o];
@@ -343,7 +343,7 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
             const int vpitch = a.vbuf_pitch;
             const dim3 gv((W + 2 * SHIFT + ANT - 1) / ANT, H);
             for (int level = first; level < P.L; level++) {
-                const PsxTaps f = taps((from_input ? a.abs0_filter : a.absN_filter) + level * PSX_GAUSS_ALIGN);
+                const PsxTaps f = taps((from_input ? a.tab->abs0_filter : a.tab->absN_filter) + level * PSX_GAUSS_ALIGN);
                 if (from_input) {
                     const float tshift = 0.5f * powf(2.0f, a.upscale_factor);
                     if (SHIFT == 4) hipLaunchKernelGGL(k_fixed_v_input<4>, gv, b, 0, s, img, a.vbuf, W, H, vpitch, f, tshift);
@@ -367,7 +367,7 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
             if (o == 0) {
                 if (fused && psx_fixed_octave0_ok(t, a.w, a.h, W, H) && a.upscale_factor == 1.0f) {
                     fo.src = a.img; fo.from_input = 1; fo.nlev = 6; fo.dst = plane(0); fo.half_level = P.L - 3;
-                    fo.scale = 255.0f; fo.taps = a.abs0_filter;
+                    fo.scale = 255.0f; fo.taps = a.tab->abs0_filter;
                     fo.ev0 = a.probe_ev0; fo.ev1 = a.probe_ev1;
                     if (a.probe_hit) *a.probe_hit = 1;
                     const hipError_t e2 = psx_launch_fixed_octave(t, fo, s);
@@ -377,12 +377,12 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
                 } else { fixed_levels(0, true); next_l0_done = false; }
             } else {
                 if (direct) {
-                    hipLaunchKernelGGL(k_alt_h_input, g, b, 0, s, img, a.intm, W, H, pitch, taps(a.dd_filter + o * PSX_GAUSS_ALIGN), a.dd_span[o], shift);
-                    hipLaunchKernelGGL(k_alt_v_plain, g, b, 0, s, a.intm, plane(0), W, H, pitch, inc(0), a.inc_span[0]);
+                    hipLaunchKernelGGL(k_alt_h_input, g, b, 0, s, img, a.intm, W, H, pitch, taps(a.tab->dd_filter + o * PSX_GAUSS_ALIGN), a.tab->dd_span[o], shift);
+                    hipLaunchKernelGGL(k_alt_v_plain, g, b, 0, s, a.intm, plane(0), W, H, pitch, inc(0), a.tab->inc_span[0]);
                 } else if (!next_l0_done) downscale();
                 if (fused) {
                     fo.src = plane(0); fo.from_input = 0; fo.nlev = 5; fo.dst = plane(1); fo.half_level = P.L - 3 - 1;
-                    fo.scale = 1.0f; fo.taps = a.absN_filter + PSX_GAUSS_ALIGN;
+                    fo.scale = 1.0f; fo.taps = a.tab->absN_filter + PSX_GAUSS_ALIGN;
                     const hipError_t e2 = psx_launch_fixed_octave(t, fo, s);
                     if (e2 != hipSuccess) return e2;
                     next_l0_done = fo.half_dst != nullptr;
@@ -394,24 +394,24 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
                 if (!interp) {
                     // ScaleDirect with the plain tables: level 0 of every octave straight from the input image, the other
                     // levels absoluteSource::horiz + vert -- the default path's fused kernels
-                    const hipError_t e2 = level == 0 ? level_from_input(plane(0), taps(a.dd_filter + o * PSX_GAUSS_ALIGN), a.dd_span[o], inc(0), a.inc_span[0])
-                                                     : psx_launch_blur(t, plane(level - 1), plane(level), W, H, pitch, inc(level), a.inc_span[level], nullptr, 0, s);
+                    const hipError_t e2 = level == 0 ? level_from_input(plane(0), taps(a.tab->dd_filter + o * PSX_GAUSS_ALIGN), a.tab->dd_span[o], inc(0), a.tab->inc_span[0])
+                                                     : psx_launch_blur(t, plane(level - 1), plane(level), W, H, pitch, inc(level), a.tab->inc_span[level], nullptr, 0, s);
                     if (e2 != hipSuccess) return e2;
                     continue;
                 }
-                if (level > 0 && psx_blur_interp_ok(t, a.inc_ispan[level])) {
+                if (level > 0 && psx_blur_interp_ok(t, a.tab->inc_ispan[level])) {
                     // the fused kernel of pyramid_interp.hip (no decimation: ScaleDirect takes level 0 of every octave from the input)
                     const hipError_t e2 = psx_launch_blur_interp(t, interp_job(a, o, level, false), s);
                     if (e2 != hipSuccess) return e2;
                     continue;
                 }
-                if (level == 0) hipLaunchKernelGGL(k_alt_h_input, g, b, 0, s, img, a.intm, W, H, pitch, taps(a.dd_filter + o * PSX_GAUSS_ALIGN), a.dd_span[o], shift);
-                else hipLaunchKernelGGL(k_alt_interp<false>, g, b, 0, s, plane(level - 1), a.intm, W, H, pitch, inci(level), a.inc_ispan[level]);
-                hipLaunchKernelGGL(k_alt_interp<true>, g, b, 0, s, a.intm, plane(level), W, H, pitch, inci(level), a.inc_ispan[level]);
+                if (level == 0) hipLaunchKernelGGL(k_alt_h_input, g, b, 0, s, img, a.intm, W, H, pitch, taps(a.tab->dd_filter + o * PSX_GAUSS_ALIGN), a.tab->dd_span[o], shift);
+                else hipLaunchKernelGGL(k_alt_interp<false>, g, b, 0, s, plane(level - 1), a.intm, W, H, pitch, inci(level), a.tab->inc_ispan[level]);
+                hipLaunchKernelGGL(k_alt_interp<true>, g, b, 0, s, a.intm, plane(level), W, H, pitch, inci(level), a.tab->inc_ispan[level]);
             }
         } else if (gm == PSX_GAUSS_VLFEAT_RELATIVE) {
             bool all_fused = P.L >= 4;
-            for (int level = 1; level < P.L; level++) all_fused = all_fused && psx_blur_interp_ok(t, a.inc_ispan[level]);
+            for (int level = 1; level < P.L; level++) all_fused = all_fused && psx_blur_interp_ok(t, a.tab->inc_ispan[level]);
             for (int level = 0; level < P.L; level++) {
                 if (level == 1 && o == 0 && all_fused && t.interp_diagonal) {
                     // every remaining level of the frame (and the extrema scans behind the octaves' last levels): diagonal schedule
@@ -420,33 +420,33 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
                 if (level == 0) {
                     if (o == 0) {
                         // the x2 level-0 kernel of pyramid.hip with the interpolated vertical pass where it applies
-                        PsxLevel0Args l0 = level0_args(plane(0), taps(a.dd_filter), a.dd_span[0], inc(0), a.inc_span[0]);
-                        l0.v_ifilter = a.inc_ifilter; l0.v_ispan = a.inc_ispan[0];
+                        PsxLevel0Args l0 = level0_args(plane(0), taps(a.tab->dd_filter), a.tab->dd_span[0], inc(0), a.tab->inc_span[0]);
+                        l0.v_ifilter = a.tab->inc_ifilter; l0.v_ispan = a.tab->inc_ispan[0];
                         if (psx_level0_interp_ok(t, l0)) {
                             const hipError_t e2 = psx_launch_level0(t, l0, s);
                             if (e2 != hipSuccess) return e2;
                         } else {
-                            hipLaunchKernelGGL(k_alt_h_input, g, b, 0, s, img, a.intm, W, H, pitch, taps(a.dd_filter), a.dd_span[0], shift);
-                            hipLaunchKernelGGL(k_alt_interp<true>, g, b, 0, s, a.intm, plane(0), W, H, pitch, inci(0), a.inc_ispan[0]);
+                            hipLaunchKernelGGL(k_alt_h_input, g, b, 0, s, img, a.intm, W, H, pitch, taps(a.tab->dd_filter), a.tab->dd_span[0], shift);
+                            hipLaunchKernelGGL(k_alt_interp<true>, g, b, 0, s, a.intm, plane(0), W, H, pitch, inci(0), a.tab->inc_ispan[0]);
                         }
                     } else if (!next_l0_done) downscale();
                     next_l0_done = false;
-                } else if (psx_blur_interp_ok(t, a.inc_ispan[level])) {
+                } else if (psx_blur_interp_ok(t, a.tab->inc_ispan[level])) {
                     // one fused launch per level (pyramid_interp.hip); level L - 3 also writes level 0 of the next octave
                     const bool feeds = level == P.L - 3 && o + 1 < P.num_octaves;
                     const hipError_t e2 = psx_launch_blur_interp(t, interp_job(a, o, level, feeds), s);
                     if (e2 != hipSuccess) return e2;
                     if (feeds) next_l0_done = true;
                 } else {
-                    hipLaunchKernelGGL(k_alt_interp<false>, g, b, 0, s, plane(level - 1), a.intm, W, H, pitch, inci(level), a.inc_ispan[level]);
-                    hipLaunchKernelGGL(k_alt_interp<true>, g, b, 0, s, a.intm, plane(level), W, H, pitch, inci(level), a.inc_ispan[level]);
+                    hipLaunchKernelGGL(k_alt_interp<false>, g, b, 0, s, plane(level - 1), a.intm, W, H, pitch, inci(level), a.tab->inc_ispan[level]);
+                    hipLaunchKernelGGL(k_alt_interp<true>, g, b, 0, s, a.intm, plane(level), W, H, pitch, inci(level), a.tab->inc_ispan[level]);
                 }
             }
         } else if (o == 0 && gm == PSX_GAUSS_VLFEAT_RELATIVE_ALL) {
             for (int level = 0; level < P.L; level++) {
                 // every level of octave 0 from the input image with its absolute sigma: level-0 kernels, the level's table
-                const PsxTaps f = taps(a.abs0_filter + level * PSX_GAUSS_ALIGN);
-                const hipError_t e2 = level_from_input(plane(level), f, a.abs0_span[level], f, a.abs0_span[level]);
+                const PsxTaps f = taps(a.tab->abs0_filter + level * PSX_GAUSS_ALIGN);
+                const hipError_t e2 = level_from_input(plane(level), f, a.tab->abs0_span[level], f, a.tab->abs0_span[level]);
                 if (e2 != hipSuccess) return e2;
             }
         } else {
@@ -454,7 +454,7 @@ hipError_t psx_launch_pyramid_alt(const PsxAltArgs& a, hipStream_t s)
             if (o == 0) return hipErrorInvalidValue;       // not reached: the default branch is psx_build_pyramid's own
             downscale();
             for (int level = 1; level < P.L; level++) {
-                hipError_t e = psx_launch_blur(t, plane(level - 1), plane(level), W, H, pitch, inc(level), a.inc_span[level], nullptr, 0, s);
+                hipError_t e = psx_launch_blur(t, plane(level - 1), plane(level), W, H, pitch, inc(level), a.tab->inc_span[level], nullptr, 0, s);
                 if (e != hipSuccess) return e;
             }
         }

@@ -3,6 +3,7 @@ descriptor-buffer growth, the flat C binding of PopSift / SiftJob (include/popsi
 automatic octave count."""
 import numpy as np
 import pytest
+import torch        # before the HIP library is loaded: torch brings a HIP runtime of its own and must initialise first
 
 from popsift_amd.synth import synth
 from tests.parity import assert_parity, budget, match_features
@@ -195,6 +196,54 @@ def test_zero_copy_export_of_two_contexts_on_two_streams_stays_separate(oracle, 
     for c in ctxs:
         c.attach_export(None, None)
         c.close()
+
+
+def test_contexts_give_their_memory_back(capi):
+    """Everything a context allocates goes when it is destroyed.  One warm-up cycle, then six cycles of create ->
+    host upload, host mask, extract, download -> host keypoints, describe -> byte mode, byte export into ordinary
+    (registered) host memory, extract, download_u8 -> destroy, on a 1024 x 768 frame.  The device's free memory may drop
+    by less than three pyramids of that size (4 * sum_o pitch_o * h_o * L bytes each, about 100 MB): three of six
+    leaked pyramids already fail.  Buffers of a few kilobytes are below what the device reports."""
+    w, h = 1024, 768
+    img = synth(w, h, 5)
+    mask = np.ones((h, w), np.uint8)
+    mask[: h // 4] = 0
+    pyramid = [0]
+
+    def cycle():
+        ctx = capi.Context(capi.default_config())
+        ctx.upload(img)
+        ctx.set_mask(mask)
+        ctx.extract()
+        F, _ = ctx.download()
+        assert len(F) > 100
+        pyramid[0] = 4 * ctx.num_levels * sum(((ow + 63) & ~63) * oh for ow, oh in map(ctx.octave_dims, range(ctx.num_octaves)))
+        k = np.zeros(len(F), capi.KEYPOINT_DTYPE)
+        for name in ("xpos", "ypos", "sigma"):
+            k[name] = F[name]
+        k["octave"] = capi.KP_AUTO
+        ctx.set_keypoints(k)
+        ctx.describe()
+        assert ctx.counts()[0] > 100
+        ctx.set_descriptor_format(capi.DESCFMT_U8)
+        fbuf = np.zeros(2 * len(F) * capi.FEATURE_DTYPE.itemsize, np.uint8)
+        dbuf = np.zeros(8 * len(F) * 128, np.uint8)
+        ctx.attach_export_u8(fbuf, dbuf)
+        ctx.extract()
+        F8, D8 = ctx.download_u8()
+        assert len(F8) == len(F) and len(D8) == int(F8["num_ori"].sum())
+        ctx.close()                                    # with the registered export still attached
+
+    cycle()
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info(0)[0]
+    for _ in range(6):
+        cycle()
+    torch.cuda.synchronize()
+    drop = free0 - torch.cuda.mem_get_info(0)[0]
+    print("six context cycles: free device memory dropped by %.1f MB, one pyramid is %.1f MB" % (drop / 1e6, pyramid[0] / 1e6))
+    assert 90e6 < pyramid[0] < 110e6
+    assert drop < 3 * pyramid[0], (drop, pyramid[0])
 
 
 def test_cross_stream_hand_over_of_plain_stores_under_pcie_load(capi):
