@@ -313,6 +313,54 @@ int psx_quantize_desc(int device, const float* d_src, int n, unsigned char* d_ds
 int psx_match_u8(int device, const unsigned char* d_left, int l_len, const unsigned char* d_right, int r_len,
                  int* host_match, int* host_dist);
 
+/* ---- matches as data ---------------------------------------------------------------------
+ * The directed matchers above answer per LEFT DESCRIPTOR; these answer with a compact list of PAIRS, filtered by a
+ * caller-chosen ratio and optionally cross-checked (what OpenCV's BFMatcher(crossCheck=True) plus the ratio test, or
+ * VLFeat's vl_ubcmatch(..., thresh), give).  One rule, shared by host and device (csrc/hip/match_rule.h); INTEGRATION.md
+ * ("Matches as data") states it in words.  With F = psx_match(L, R) and B = psx_match(R, L) (psx_match_u8 for bytes), bit
+ * for bit, left descriptor i yields the pair (i, j = F[i].best) iff
+ *   1. r_len >= 1,
+ *   2. (float)F[i].d1 / (float)F[i].d2 < ratio -- a float32 IEEE division and comparison (0/0 is NaN and fails, d2 = +inf
+ *      gives 0 and passes; INT_MAX stands for +inf),
+ *   3. with PSX_PAIRS_MUTUAL: B[j].best == i.
+ * Pairs come out in ascending `left`: a stable, deterministic compaction.  {0.8f, 0} gives exactly the rows whose accept
+ * flag is 1; ratio = INFINITY switches the ratio test off (except for NaN); with PSX_PAIRS_MUTUAL every left and every
+ * right occurs at most once.
+ * *count is always the TOTAL number of pairs that pass; the first min(*count, capacity) are written; capacity = 0 with a
+ * NULL output asks "how many?".  l_len = 0 or r_len = 0 gives *count = 0 and PSX_OK.  PSX_ERR_INVALID, with nothing
+ * touched: opts == NULL, a ratio that is NaN or <= 0, unknown flag bits, negative sizes, NULL data with a non-zero size,
+ * count == NULL.  Descriptor pointers, alignment, scratch (psx_match_release) and thread safety as for psx_match /
+ * psx_match_u8; a device output buffer is 16-byte aligned (one 16-byte store per record).  Synchronous. */
+#define PSX_PAIRS_MUTUAL 1
+typedef struct psx_match_opts    { float ratio; int flags; } psx_match_opts;           /* {0.8f, 0} = today's accept */
+typedef struct psx_match_pair    { int left, right; float d1, d2; } psx_match_pair;    /* 16 bytes */
+typedef struct psx_match_pair_u8 { int left, right; int   d1, d2; } psx_match_pair_u8; /* 16 bytes, INT_MAX = none */
+
+/* *o = {0.8f, 0} */
+int psx_match_opts_default(psx_match_opts* o);
+
+/* host output: 16 bytes per PAIR come back instead of 20 per descriptor of both sides */
+int psx_match_pairs(int device, const float* d_left, int l_len, const float* d_right, int r_len,
+                    const psx_match_opts* opts, psx_match_pair* host_pairs, int capacity, int* count);
+int psx_match_pairs_u8(int device, const unsigned char* d_left, int l_len, const unsigned char* d_right, int r_len,
+                       const psx_match_opts* opts, psx_match_pair_u8* host_pairs, int capacity, int* count);
+/* device output: the list stays in HBM (d_pairs: DEVICE pointer) for the caller's own kernels / a torch tensor; only
+ * the count comes back */
+int psx_match_pairs_dev(int device, const float* d_left, int l_len, const float* d_right, int r_len,
+                        const psx_match_opts* opts, psx_match_pair* d_pairs, int capacity, int* count);
+int psx_match_pairs_u8_dev(int device, const unsigned char* d_left, int l_len, const unsigned char* d_right, int r_len,
+                           const psx_match_opts* opts, psx_match_pair_u8* d_pairs, int capacity, int* count);
+
+/* The join alone, on HOST arrays: no device, no context (what the join kernel computes -- for tests and for callers
+ * that already hold directed results).  fwd_match / fwd_dist: l_len rows as psx_match(L, R) returns them (3 ints, 2
+ * distances); bwd_match: r_len rows of psx_match(R, L), may be NULL when PSX_PAIRS_MUTUAL is not set.  Additionally
+ * PSX_ERR_INVALID when a best index lies outside [0, r_len), or a backward best outside [0, l_len), while that side is
+ * non-empty: nothing is read out of bounds, nothing is written. */
+int psx_pairs_join(const int* fwd_match, const float* fwd_dist, int l_len, const int* bwd_match, int r_len,
+                   const psx_match_opts* opts, psx_match_pair* pairs, int capacity, int* count);
+int psx_pairs_join_u8(const int* fwd_match, const int* fwd_dist, int l_len, const int* bwd_match, int r_len,
+                      const psx_match_opts* opts, psx_match_pair_u8* pairs, int capacity, int* count);
+
 /* ---- caller-supplied keypoints ------------------------------------------------------------
  * Describing points the caller brings along instead of the ones the DoG detector finds (what OpenCV calls
  * useProvidedKeypoints and VLFeat calls frames; the reference has no counterpart).  A record carries what a

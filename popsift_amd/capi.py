@@ -95,7 +95,20 @@ SYMBOLS = [
     "psx_keypoint_bounds", "psx_place_keypoints", "psx_set_keypoints", "psx_set_keypoints_dev", "psx_describe",
     "psx_keypoint_map",
     "psx_set_mask", "psx_set_mask_dev", "psx_mask_keep",
+    "psx_match_opts_default", "psx_match_pairs", "psx_match_pairs_u8", "psx_match_pairs_dev", "psx_match_pairs_u8_dev",
+    "psx_pairs_join", "psx_pairs_join_u8",
 ]
+
+PAIRS_MUTUAL = 1     # PSX_PAIRS_MUTUAL
+# psx_match_pair / psx_match_pair_u8 (16 bytes): one correspondence; byte distances are integers, INT_MAX = none
+PAIR_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4"), ("d1", "<f4"), ("d2", "<f4")])
+PAIR_U8_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4"), ("d1", "<i4"), ("d2", "<i4")])
+
+
+class MatchOpts(C.Structure):
+    """psx_match_opts: {0.8, 0} is the accept flag of psx_match."""
+    _fields_ = [("ratio", C.c_float), ("flags", C.c_int)]
+
 
 DESCFMT_F32 = 0      # PSX_DESCFMT_F32
 DESCFMT_U8 = 1       # PSX_DESCFMT_U8
@@ -160,6 +173,11 @@ def lib():
         L.psx_set_mask.argtypes = [vp, vp, C.c_int, C.c_int]
         L.psx_set_mask_dev.argtypes = [vp, vp, C.c_int, C.c_int]
         L.psx_mask_keep.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]
+        L.psx_match_opts_default.argtypes = [C.POINTER(MatchOpts)]
+        for n in ("psx_match_pairs", "psx_match_pairs_u8", "psx_match_pairs_dev", "psx_match_pairs_u8_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(MatchOpts), vp, C.c_int, ip]
+        for n in ("psx_pairs_join", "psx_pairs_join_u8"):
+            getattr(L, n).argtypes = [vp, vp, C.c_int, vp, C.c_int, C.POINTER(MatchOpts), vp, C.c_int, ip]
         _LIB = L
     return _LIB
 
@@ -329,6 +347,93 @@ def match_u8(left, right, device=0):
             L.psx_dev_free(device, p)
 
 
+def match_opts(ratio=0.8, mutual=False):
+    """psx_match_opts from the two keywords every pairs function takes"""
+    return MatchOpts(ratio, PAIRS_MUTUAL if mutual else 0)
+
+
+def _pairs_call(fn, name, device, pl, nl, pr, nr, ratio, mutual, dtype, capacity):
+    """One host-output pairs call; capacity None: room for every left descriptor.  Returns (pairs, total count)."""
+    cap = nl if capacity is None else capacity
+    out = np.zeros((cap,), dtype)
+    n = C.c_int(-1)
+    o = match_opts(ratio, mutual)
+    rc = fn(device, pl, nl, pr, nr, C.byref(o), out.ctypes.data_as(C.c_void_p) if cap else None, cap, C.byref(n))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    return out[:min(n.value, cap)], n.value
+
+
+def match_pairs(left, right, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs on host arrays of (n,128) / (m,128) float32 descriptors (through device buffers): the PAIR_DTYPE
+    records of the pairs that pass the ratio test (and the cross-check, with mutual), in ascending left.  With a
+    capacity: (the first min(count, capacity) records, count)."""
+    L = lib()
+    left = np.ascontiguousarray(left, dtype=np.float32).reshape(-1, 128)
+    right = np.ascontiguousarray(right, dtype=np.float32).reshape(-1, 128)
+    bufs = []
+    try:
+        pl, pr = _to_device(L, device, [left, right], bufs)
+        got = _pairs_call(L.psx_match_pairs, "psx_match_pairs", device, pl, len(left), pr, len(right), ratio, mutual, PAIR_DTYPE, capacity)
+        return got[0] if capacity is None else got
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def match_pairs_u8(left, right, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs_u8 on host arrays of (n,128) / (m,128) uint8 descriptors: PAIR_U8_DTYPE records, as match_pairs."""
+    L = lib()
+    left = np.ascontiguousarray(left, dtype=np.uint8).reshape(-1, 128)
+    right = np.ascontiguousarray(right, dtype=np.uint8).reshape(-1, 128)
+    bufs = []
+    try:
+        pl, pr = _to_device(L, device, [left, right], bufs)
+        got = _pairs_call(L.psx_match_pairs_u8, "psx_match_pairs_u8", device, pl, len(left), pr, len(right), ratio, mutual, PAIR_U8_DTYPE, capacity)
+        return got[0] if capacity is None else got
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def match_pairs_dev(left_ptr, l_len, right_ptr, r_len, out_ptr, capacity, ratio=0.8, mutual=False, device=0, u8=False):
+    """psx_match_pairs_dev / psx_match_pairs_u8_dev on DEVICE pointers (e.g. tensor.data_ptr()): the records go into
+    the caller's device buffer at out_ptr (16-byte aligned, `capacity` records); returns the total count."""
+    L = lib()
+    fn = L.psx_match_pairs_u8_dev if u8 else L.psx_match_pairs_dev
+    n = C.c_int(-1)
+    o = match_opts(ratio, mutual)
+    rc = fn(device, C.c_void_p(left_ptr), l_len, C.c_void_p(right_ptr), r_len, C.byref(o), C.c_void_p(out_ptr), capacity, C.byref(n))
+    if rc != 0:
+        raise PopSiftError("psx_match_pairs%s_dev failed (%d)" % ("_u8" if u8 else "", rc))
+    return n.value
+
+
+def pairs_join(fwd_match, fwd_dist, bwd_match, r_len, ratio=0.8, mutual=False, capacity=None):
+    """psx_pairs_join / psx_pairs_join_u8 (chosen by fwd_dist.dtype: float32 or int32): the join alone, on directed
+    results held on the host -- fwd_* = match(L, R), bwd_match = match(R, L)[0] or None without mutual.  No device.
+    Returns the pair records; with a capacity (records, count)."""
+    L = lib()
+    fwd_dist = np.asarray(fwd_dist)
+    if fwd_dist.dtype == np.float32:
+        fn, name, dtype = L.psx_pairs_join, "psx_pairs_join", PAIR_DTYPE
+    elif fwd_dist.dtype == np.int32:
+        fn, name, dtype = L.psx_pairs_join_u8, "psx_pairs_join_u8", PAIR_U8_DTYPE
+    else:
+        raise TypeError("fwd_dist must be float32 (psx_match) or int32 (psx_match_u8)")
+    fm = np.ascontiguousarray(fwd_match, dtype=np.int32).reshape(-1, 3)
+    fd = np.ascontiguousarray(fwd_dist).reshape(-1, 2)
+    if len(fm) != len(fd):
+        raise ValueError("fwd_match and fwd_dist differ in length")
+    bm = None if bwd_match is None else np.ascontiguousarray(bwd_match, dtype=np.int32).reshape(-1, 3)
+    if bm is not None and len(bm) != r_len:
+        raise ValueError("bwd_match must have r_len rows")
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    join = lambda dev, pm, nl, pb, nr, *rest: fn(pm, ptr(fd), nl, pb, nr, *rest)
+    got = _pairs_call(join, name, 0, ptr(fm), len(fm), ptr(bm), r_len, ratio, mutual, dtype, capacity)
+    return got[0] if capacity is None else got
+
+
 class DeviceDescriptors:
     """Descriptor sets resident on the device (what FeaturesDev holds, popsift.cpp:346-383): upload once, match many times."""
 
@@ -355,6 +460,12 @@ class DeviceDescriptors:
         if rc != 0:
             raise PopSiftError("psx_match failed (%d)" % rc)
         return mm, dd
+
+    def match_pairs(self, right, ratio=0.8, mutual=False, capacity=None):
+        """psx_match_pairs(self as left, right: DeviceDescriptors): PAIR_DTYPE records; with a capacity (records, count)"""
+        got = _pairs_call(lib().psx_match_pairs, "psx_match_pairs", self.device, self.ptr, self.n, right.ptr, right.n,
+                          ratio, mutual, PAIR_DTYPE, capacity)
+        return got[0] if capacity is None else got
 
     def close(self):
         if self.ptr:

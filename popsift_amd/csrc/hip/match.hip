@@ -22,6 +22,7 @@
 // k_match_merge combines the per-chunk top-2 with the (distance, index) order that the sequential scan
 // of the reference produces.
 #include "psx_internal.h"
+#include "match_join.h"
 
 #include <climits>
 #include <cstdio>
@@ -537,7 +538,9 @@ __global__ __launch_bounds__(256) void k_match_exact(const float* __restrict__ l
 // the device is synchronised) and buffers that only ever grow.  Freed when the thread exits.
 namespace {
 struct MatchScratch {
-    static constexpr int NBUF = 13;      // 0-9: psx_match, 10-12: psx_match_u8
+    // 0-9: psx_match, 10-12: psx_match_u8; the pair search: 13 the backward direction's results of psx_match_pairs,
+    // 14 those of psx_match_pairs_u8, 15 the join's per-workgroup totals
+    static constexpr int NBUF = 16;
     int device = -1;
     hipStream_t stream = nullptr;
     void* buf[NBUF] = {};
@@ -598,7 +601,7 @@ struct MatchScratch {
 thread_local MatchScratch t_scratch;
 } // namespace
 
-// frees the calling thread's matcher scratch (stream + up to 13 device buffers); an explicit user call -- PopSift::uninit
+// frees the calling thread's matcher scratch (stream + up to 16 device buffers); an explicit user call -- PopSift::uninit
 // does NOT call it: the scratch belongs to the thread, not to one PopSift object (another replica may be using it)
 extern "C" int psx_match_release(void)
 {
@@ -606,15 +609,12 @@ extern "C" int psx_match_release(void)
     return PSX_OK;
 }
 
-extern "C" int psx_match(int device, const float* d_left, int l_len, const float* d_right, int r_len,
-                         int* host_match, float* host_dist)
+// The launch sequence of the directed float matcher, l_len >= 1: leaves out[3 l_len] (best, second, accept), dist[2 l_len]
+// and the prefilter's flag in sc.buf[ob], in this order.  to_host: the same bytes are in sc.hpin on return (psx_match);
+// otherwise only the flag crosses (the pair search joins on the device).  Synchronised on return either way: the
+// prefilter's flag is read here, and the exact scan of every pair follows when it is up.
+static int match_f32_run(MatchScratch& sc, const float* d_left, int l_len, const float* d_right, int r_len, int ob, bool to_host)
 {
-    if (l_len < 0 || r_len < 0 || (l_len > 0 && (!d_left || !host_match)) || (r_len > 0 && !d_right))
-        return PSX_ERR_INVALID;
-    if (l_len == 0) return PSX_OK;
-    if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
-    MatchScratch& sc = t_scratch;
-    if (!sc.bind(device)) return PSX_ERR_HIP;
     // enough (left group, chunk) waves to fill the chip: 256 CUs x 4 SIMDs x 2 waves
     const int lgroups = (l_len + 63) / 64;
     int nchunks = (2048 + lgroups - 1) / lgroups;
@@ -625,11 +625,11 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
 
     if (!sc.need(0, sizeof(Top2) * (size_t)nchunks * l_len) ||
         !sc.need(1, sizeof(float) * 128 * (size_t)(r_len > 0 ? r_len : 1)) ||
-        !sc.need(2, (sizeof(int) * 3 + sizeof(float) * 2) * (size_t)l_len + 64))
+        !sc.need(ob, (sizeof(int) * 3 + sizeof(float) * 2) * (size_t)l_len + 64))
         return PSX_ERR_NOMEM;
     Top2* d_partial = static_cast<Top2*>(sc.buf[0]);
     float* d_rperm = static_cast<float*>(sc.buf[1]);
-    int* d_out = static_cast<int*>(sc.buf[2]);
+    int* d_out = static_cast<int*>(sc.buf[ob]);
     // matches, distances and the prefilter's flag in ONE buffer: one copy back per call (three cost ~5 us each)
     float* d_dist = reinterpret_cast<float*>(d_out + 3 * (size_t)l_len);
     int* d_flag = reinterpret_cast<int*>(d_dist + 2 * (size_t)l_len);
@@ -709,14 +709,18 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
         d_flag_used = d_flag; d_cct_used = d_cct;
     }
     const size_t mb = sizeof(int) * 3 * (size_t)l_len, db = sizeof(float) * 2 * (size_t)l_len;
-    if (!sc.need_pinned(mb + db + 64)) return PSX_ERR_NOMEM;
+    if (!sc.need_pinned(to_host ? mb + db + 64 : 64)) return PSX_ERR_NOMEM;
     char* hp = static_cast<char*>(sc.hpin);
-    int* h_flagp = reinterpret_cast<int*>(hp + mb + db);
+    int* h_flagp = reinterpret_cast<int*>(to_host ? hp + mb + db : hp);
     *h_flagp = 0;
     auto fetch = [&]() -> bool {
-        return hipGetLastError() == hipSuccess &&
-               hipMemcpyAsync(hp, d_out, mb + db + (d_flag_used ? sizeof(int) : 0), hipMemcpyDeviceToHost, st) == hipSuccess &&
-               hipStreamSynchronize(st) == hipSuccess;
+        if (hipGetLastError() != hipSuccess) return false;
+        if (to_host) {
+            if (hipMemcpyAsync(hp, d_out, mb + db + (d_flag_used ? sizeof(int) : 0), hipMemcpyDeviceToHost, st) != hipSuccess) return false;
+        } else if (d_flag_used) {
+            if (hipMemcpyAsync(h_flagp, d_flag_used, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return false;
+        }
+        return hipStreamSynchronize(st) == hipSuccess;
     };
     if (!exact_scan) {
         if (!fetch()) return PSX_ERR_HIP;
@@ -744,6 +748,22 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
                        r_len, d_out, d_dist);
     if (!fetch()) return PSX_ERR_HIP;
     }
+    return PSX_OK;
+}
+
+extern "C" int psx_match(int device, const float* d_left, int l_len, const float* d_right, int r_len,
+                         int* host_match, float* host_dist)
+{
+    if (l_len < 0 || r_len < 0 || (l_len > 0 && (!d_left || !host_match)) || (r_len > 0 && !d_right))
+        return PSX_ERR_INVALID;
+    if (l_len == 0) return PSX_OK;
+    if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
+    MatchScratch& sc = t_scratch;
+    if (!sc.bind(device)) return PSX_ERR_HIP;
+    const int rc = match_f32_run(sc, d_left, l_len, d_right, r_len, 2, true);
+    if (rc != PSX_OK) return rc;
+    const size_t mb = sizeof(int) * 3 * (size_t)l_len, db = sizeof(float) * 2 * (size_t)l_len;
+    const char* hp = static_cast<const char*>(sc.hpin);
     memcpy(host_match, hp, mb);
     if (host_dist) memcpy(host_dist, hp + mb, db);
     return PSX_OK;
@@ -918,6 +938,44 @@ __global__ void k_match_u8_merge(const uint2* __restrict__ partial, int l_len, i
 
 } // namespace
 
+// ---- the directed byte matcher's launch sequence, shared by psx_match_u8 and the pair search ----
+namespace {
+struct U8Plan { int lblocks, nchunks, chunk_len; };
+
+// chunks of at most U8_CHUNK_MAX right descriptors (the key's index bits), whole tiles, enough workgroups for the chip
+U8Plan u8_plan(int l_len, int r_len)
+{
+    const int lblocks = (l_len + 255) / 256;
+    int nchunks = (2048 + lblocks - 1) / lblocks;
+    const int min_chunks = (r_len + U8_CHUNK_MAX - 1) / U8_CHUNK_MAX;
+    if (nchunks < min_chunks) nchunks = min_chunks;
+    if (nchunks > (r_len + U8_TILE - 1) / U8_TILE) nchunks = (r_len + U8_TILE - 1) / U8_TILE;
+    int chunk_len = (r_len + nchunks - 1) / nchunks;
+    chunk_len = ((chunk_len + U8_TILE - 1) / U8_TILE) * U8_TILE;
+    nchunks = (r_len + chunk_len - 1) / chunk_len;
+    return U8Plan{lblocks, nchunks, chunk_len};
+}
+
+// entries of a set's norm array: whole tiles plus one tile of zeros (either set may be the one the matcher reads by tiles)
+size_t u8_pad(int n) { return ((size_t)(n + U8_TILE - 1) / U8_TILE + 1) * U8_TILE; }
+
+// the norms of both sets in one launch
+void u8_queue_norms(hipStream_t st, const unsigned char* d_left, int l_len, int* d_ln2, const unsigned char* d_right, int r_len, int* d_rn2)
+{
+    const int rnb = (int)((u8_pad(r_len) * 8 + 255) / 256), lnb = (int)((u8_pad(l_len) * 8 + 255) / 256);
+    hipLaunchKernelGGL(k_u8_norms, dim3(rnb + lnb), dim3(256), 0, st, d_right, r_len, d_rn2, rnb, d_left, l_len, d_ln2);
+}
+
+// one direction: the per-chunk top-2 into d_partial, merged into d_out (3 l_len indices / flags, 2 l_len distances)
+void u8_queue_match(hipStream_t st, const U8Plan& pl, const unsigned char* d_left, const int* d_ln2, int l_len,
+                    const unsigned char* d_right, const int* d_rn2, int r_len, uint2* d_partial, int* d_out)
+{
+    hipLaunchKernelGGL(k_match_u8, dim3(pl.lblocks, pl.nchunks), dim3(256), 0, st, d_left, d_ln2, l_len, d_right, d_rn2, r_len,
+                       pl.chunk_len, d_partial);
+    hipLaunchKernelGGL(k_match_u8_merge, dim3((l_len + 255) / 256), dim3(256), 0, st, d_partial, l_len, pl.nchunks, pl.chunk_len, d_out);
+}
+} // namespace
+
 extern "C" int psx_quantize_desc(int device, const float* d_src, int n, unsigned char* d_dst)
 {
     if (n < 0 || (n > 0 && (!d_src || !d_dst))) return PSX_ERR_INVALID;
@@ -949,31 +1007,18 @@ extern "C" int psx_match_u8(int device, const unsigned char* d_left, int l_len, 
     if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
     MatchScratch& sc = t_scratch;
     if (!sc.bind(device)) return PSX_ERR_HIP;
-    // chunks of at most U8_CHUNK_MAX right descriptors (the key's index bits), whole tiles, enough workgroups for the chip
-    const int lblocks = (l_len + 255) / 256;
-    int nchunks = (2048 + lblocks - 1) / lblocks;
-    const int min_chunks = (r_len + U8_CHUNK_MAX - 1) / U8_CHUNK_MAX;
-    if (nchunks < min_chunks) nchunks = min_chunks;
-    if (nchunks > (r_len + U8_TILE - 1) / U8_TILE) nchunks = (r_len + U8_TILE - 1) / U8_TILE;
-    int chunk_len = (r_len + nchunks - 1) / nchunks;
-    chunk_len = ((chunk_len + U8_TILE - 1) / U8_TILE) * U8_TILE;
-    nchunks = (r_len + chunk_len - 1) / chunk_len;
-
-    const size_t lpad = ((size_t)(l_len + U8_TILE - 1) / U8_TILE + 1) * U8_TILE;
-    const size_t rpad = ((size_t)(r_len + U8_TILE - 1) / U8_TILE + 1) * U8_TILE;
+    const U8Plan pl = u8_plan(l_len, r_len);
+    const size_t lpad = u8_pad(l_len), rpad = u8_pad(r_len);
     const size_t ob = sizeof(int) * 5 * (size_t)l_len;
-    if (!sc.need(10, sizeof(uint2) * (size_t)nchunks * l_len) || !sc.need(11, sizeof(int) * (lpad + rpad)) || !sc.need(12, ob))
+    if (!sc.need(10, sizeof(uint2) * (size_t)pl.nchunks * l_len) || !sc.need(11, sizeof(int) * (lpad + rpad)) || !sc.need(12, ob))
         return PSX_ERR_NOMEM;
     uint2* d_partial = static_cast<uint2*>(sc.buf[10]);
     int* d_ln2 = static_cast<int*>(sc.buf[11]);
     int* d_rn2 = d_ln2 + lpad;                   // lpad is a multiple of U8_TILE: 16-byte aligned
     int* d_out = static_cast<int*>(sc.buf[12]);
     hipStream_t st = sc.stream;
-    const int rnb = (int)((rpad * 8 + 255) / 256), lnb = (int)((lpad * 8 + 255) / 256);
-    hipLaunchKernelGGL(k_u8_norms, dim3(rnb + lnb), dim3(256), 0, st, d_right, r_len, d_rn2, rnb, d_left, l_len, d_ln2);
-    hipLaunchKernelGGL(k_match_u8, dim3(lblocks, nchunks), dim3(256), 0, st, d_left, d_ln2, l_len, d_right, d_rn2, r_len,
-                       chunk_len, d_partial);
-    hipLaunchKernelGGL(k_match_u8_merge, dim3((l_len + 255) / 256), dim3(256), 0, st, d_partial, l_len, nchunks, chunk_len, d_out);
+    u8_queue_norms(st, d_left, l_len, d_ln2, d_right, r_len, d_rn2);
+    u8_queue_match(st, pl, d_left, d_ln2, l_len, d_right, d_rn2, r_len, d_partial, d_out);
     if (!sc.need_pinned(ob)) return PSX_ERR_NOMEM;
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(sc.hpin, d_out, ob, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
@@ -982,4 +1027,217 @@ extern "C" int psx_match_u8(int device, const unsigned char* d_left, int l_len, 
     memcpy(host_match, hp, sizeof(int) * 3 * (size_t)l_len);
     if (host_dist) memcpy(host_dist, hp + 3 * (size_t)l_len, sizeof(int) * 2 * (size_t)l_len);
     return PSX_OK;
+}
+
+
+// =====================================================================================================================
+// Matches as data: psx_match_pairs / psx_match_pairs_u8 (+ _dev), psx_pairs_join (+ _u8)
+//
+// Two directed passes over the kernels above -- L -> R into one scratch buffer, with PSX_PAIRS_MUTUAL also R -> L into
+// another -- then a join on the device: per left descriptor i the rule of match_rule.h on F[i]'s distances and the gather
+// B[F[i].best].best == i, and a STABLE compaction of the survivors in ascending i.  Nothing depends on arrival order: a lane's
+// slot is (pairs of the workgroups before its own) + (pairs of the waves before its own) + (set ballot bits below its lane).
+//   k_pairs_count  evaluates the rule, one lane per left descriptor; wave64 ballot, the waves' counts summed in LDS: one
+//                  total per workgroup
+//   k_pairs_write  evaluates it again (three loads and a division: cheaper than parking the verdicts in memory), sums the
+//                  totals of the workgroups before its own (the exclusive scan across workgroups: every workgroup reads
+//                  at most gridDim.x ints), ranks its lanes with mbcnt and writes each surviving record with ONE 16-byte
+//                  store, never at or past `capacity`; the last workgroup writes the total
+// The host forms let k_pairs_write store straight into the thread's pinned staging buffer (mapped host memory): the
+// count and 16 bytes per PAIR cross PCIe, nothing else, and the byte path synchronises once per call.
+// =====================================================================================================================
+namespace {
+
+__device__ __forceinline__ int pair_bits(float d) { return __float_as_int(d); }
+__device__ __forceinline__ int pair_bits(int d) { return d; }
+
+__device__ __forceinline__ int lane_rank(unsigned long long m)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+// fwd: the forward direction's buffer (3 l_len ints, then 2 l_len distances); bwd: the backward direction's (r_len rows;
+// read only with `mutual`).  The directed kernels only ever write indices in [0, r_len) / [0, l_len), and r_len >= 1 here.
+template <class Dist>
+__device__ __forceinline__ bool pair_rule(const int* __restrict__ fwd, int l_len, const int* __restrict__ bwd, int i,
+                                          float ratio, int mutual, int4& rec)
+{
+    const Dist* dist = reinterpret_cast<const Dist*>(fwd + 3 * (size_t)l_len);
+    const int j = fwd[3 * (size_t)i];
+    const Dist d1 = dist[2 * (size_t)i], d2 = dist[2 * (size_t)i + 1];
+    bool keep = psx_match_keep(psx_match_dist(d1), psx_match_dist(d2), ratio);
+    if (keep && mutual) keep = bwd[3 * (size_t)j] == i;
+    rec = make_int4(i, j, pair_bits(d1), pair_bits(d2));
+    return keep;
+}
+
+template <class Dist>
+__global__ __launch_bounds__(256) void k_pairs_count(const int* __restrict__ fwd, int l_len, const int* __restrict__ bwd,
+                                                     float ratio, int mutual, int* __restrict__ wg_tot)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int4 rec;
+    const bool keep = i < l_len && pair_rule<Dist>(fwd, l_len, bwd, i, ratio, mutual, rec);
+    const unsigned long long m = __ballot(keep);
+    __shared__ int s_cnt[4];
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) wg_tot[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+template <class Dist>
+__global__ __launch_bounds__(256) void k_pairs_write(const int* __restrict__ fwd, int l_len, const int* __restrict__ bwd,
+                                                     float ratio, int mutual, const int* __restrict__ wg_tot,
+                                                     int4* __restrict__ out, int capacity, int* __restrict__ total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int4 rec = make_int4(0, 0, 0, 0);
+    const bool keep = i < l_len && pair_rule<Dist>(fwd, l_len, bwd, i, ratio, mutual, rec);
+    const unsigned long long m = __ballot(keep);
+    // pairs of the workgroups before this one
+    int part = 0;
+    for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) part += wg_tot[b];
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) part += __shfl_xor(part, k);
+    __shared__ int s_part[4], s_cnt[4];
+    if (lane == 0) { s_part[wave] = part; s_cnt[wave] = __popcll(m); }
+    __syncthreads();
+    const int base = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    int woff = 0;
+    for (int w = 0; w < wave; w++) woff += s_cnt[w];
+    const int pos = base + woff + lane_rank(m);
+    if (keep && pos < capacity) out[pos] = rec;
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = base + s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// Queues the join behind the directed passes and finishes the call: d_fwd / d_bwd as pair_rule reads them.  host_pairs:
+// the records go through the pinned staging buffer into it; d_pairs: into the caller's device buffer.  One
+// synchronisation.
+template <class Dist>
+int pairs_finish(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
+                 void* host_pairs, void* d_pairs, int capacity, int* count)
+{
+    const int nb = (l_len + 255) / 256;
+    if (!sc.need(15, sizeof(int) * (size_t)nb)) return PSX_ERR_NOMEM;
+    const int nrec = host_pairs ? (capacity < l_len ? capacity : l_len) : 0;       // at most l_len pairs exist
+    if (!sc.need_pinned(16 + 16 * (size_t)nrec)) return PSX_ERR_NOMEM;
+    void* dev_pin = nullptr;
+    if (hipHostGetDevicePointer(&dev_pin, sc.hpin, 0) != hipSuccess || dev_pin == nullptr) return PSX_ERR_HIP;
+    int* h_total = static_cast<int*>(sc.hpin);
+    *h_total = -1;
+    int* d_total = static_cast<int*>(dev_pin);
+    // the kernel's capacity for the host form is the staging buffer's (nrec <= capacity)
+    int4* out = host_pairs ? reinterpret_cast<int4*>(static_cast<char*>(dev_pin) + 16) : static_cast<int4*>(d_pairs);
+    const int cap = host_pairs ? nrec : capacity;
+    int* d_tot = static_cast<int*>(sc.buf[15]);
+    const int mutual = (opts->flags & PSX_PAIRS_MUTUAL) ? 1 : 0;
+    hipStream_t st = sc.stream;
+    hipLaunchKernelGGL((k_pairs_count<Dist>), dim3(nb), dim3(256), 0, st, d_fwd, l_len, d_bwd, opts->ratio, mutual, d_tot);
+    hipLaunchKernelGGL((k_pairs_write<Dist>), dim3(nb), dim3(256), 0, st, d_fwd, l_len, d_bwd, opts->ratio, mutual, d_tot, out, cap, d_total);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return PSX_ERR_HIP;
+    const int n = *h_total;
+    if (n < 0 || n > l_len) return PSX_ERR_HIP;
+    if (host_pairs && n > 0 && nrec > 0) memcpy(host_pairs, static_cast<const char*>(sc.hpin) + 16, 16 * (size_t)(n < nrec ? n : nrec));
+    *count = n;
+    return PSX_OK;
+}
+
+// host_pairs or d_pairs (the other is NULL; both NULL with capacity 0)
+int match_pairs_f32(int device, const float* d_left, int l_len, const float* d_right, int r_len, const psx_match_opts* opts,
+                    void* host_pairs, void* d_pairs, int capacity, int* count)
+{
+    if (!psx_pairs_args_ok(l_len, r_len, opts, host_pairs ? host_pairs : d_pairs, capacity, count) ||
+        (l_len > 0 && !d_left) || (r_len > 0 && !d_right))
+        return PSX_ERR_INVALID;
+    if (l_len == 0 || r_len == 0) { *count = 0; return PSX_OK; }
+    if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
+    MatchScratch& sc = t_scratch;
+    if (!sc.bind(device)) return PSX_ERR_HIP;
+    const bool mutual = (opts->flags & PSX_PAIRS_MUTUAL) != 0;
+    // each direction is a whole directed call (its own size rule, its own flag and fallback); the results stay in HBM
+    int rc = match_f32_run(sc, d_left, l_len, d_right, r_len, 2, false);
+    if (rc == PSX_OK && mutual) rc = match_f32_run(sc, d_right, r_len, d_left, l_len, 13, false);
+    if (rc != PSX_OK) return rc;
+    return pairs_finish<float>(sc, static_cast<const int*>(sc.buf[2]), l_len, mutual ? static_cast<const int*>(sc.buf[13]) : nullptr,
+                               opts, host_pairs, d_pairs, capacity, count);
+}
+
+int match_pairs_u8(int device, const unsigned char* d_left, int l_len, const unsigned char* d_right, int r_len,
+                   const psx_match_opts* opts, void* host_pairs, void* d_pairs, int capacity, int* count)
+{
+    if (!psx_pairs_args_ok(l_len, r_len, opts, host_pairs ? host_pairs : d_pairs, capacity, count) ||
+        (l_len > 0 && !d_left) || (r_len > 0 && !d_right))
+        return PSX_ERR_INVALID;
+    if (l_len == 0 || r_len == 0) { *count = 0; return PSX_OK; }
+    if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
+    MatchScratch& sc = t_scratch;
+    if (!sc.bind(device)) return PSX_ERR_HIP;
+    const bool mutual = (opts->flags & PSX_PAIRS_MUTUAL) != 0;
+    const U8Plan fw = u8_plan(l_len, r_len), bw = u8_plan(r_len, l_len);
+    const size_t lpad = u8_pad(l_len), rpad = u8_pad(r_len);
+    // every buffer of both directions before the first launch: nothing is reallocated under queued work
+    size_t pb = sizeof(uint2) * (size_t)fw.nchunks * l_len;
+    if (mutual && sizeof(uint2) * (size_t)bw.nchunks * r_len > pb) pb = sizeof(uint2) * (size_t)bw.nchunks * r_len;
+    if (!sc.need(10, pb) || !sc.need(11, sizeof(int) * (lpad + rpad)) || !sc.need(12, sizeof(int) * 5 * (size_t)l_len) ||
+        (mutual && !sc.need(14, sizeof(int) * 5 * (size_t)r_len)))
+        return PSX_ERR_NOMEM;
+    uint2* d_partial = static_cast<uint2*>(sc.buf[10]);
+    int* d_ln2 = static_cast<int*>(sc.buf[11]);
+    int* d_rn2 = d_ln2 + lpad;
+    int* d_fwd = static_cast<int*>(sc.buf[12]);
+    int* d_bwd = mutual ? static_cast<int*>(sc.buf[14]) : nullptr;
+    hipStream_t st = sc.stream;
+    // one norms launch serves both directions; the second direction's partials reuse the first's buffer (stream order)
+    u8_queue_norms(st, d_left, l_len, d_ln2, d_right, r_len, d_rn2);
+    u8_queue_match(st, fw, d_left, d_ln2, l_len, d_right, d_rn2, r_len, d_partial, d_fwd);
+    if (mutual) u8_queue_match(st, bw, d_right, d_rn2, r_len, d_left, d_ln2, l_len, d_partial, d_bwd);
+    return pairs_finish<int>(sc, d_fwd, l_len, d_bwd, opts, host_pairs, d_pairs, capacity, count);
+}
+
+} // namespace
+
+extern "C" int psx_match_opts_default(psx_match_opts* o)
+{
+    if (!o) return PSX_ERR_INVALID;
+    o->ratio = 0.8f; o->flags = 0;
+    return PSX_OK;
+}
+
+extern "C" int psx_match_pairs(int device, const float* d_left, int l_len, const float* d_right, int r_len,
+                               const psx_match_opts* opts, psx_match_pair* host_pairs, int capacity, int* count)
+{
+    return match_pairs_f32(device, d_left, l_len, d_right, r_len, opts, host_pairs, nullptr, capacity, count);
+}
+
+extern "C" int psx_match_pairs_dev(int device, const float* d_left, int l_len, const float* d_right, int r_len,
+                                   const psx_match_opts* opts, psx_match_pair* d_pairs, int capacity, int* count)
+{
+    return match_pairs_f32(device, d_left, l_len, d_right, r_len, opts, nullptr, d_pairs, capacity, count);
+}
+
+extern "C" int psx_match_pairs_u8(int device, const unsigned char* d_left, int l_len, const unsigned char* d_right, int r_len,
+                                  const psx_match_opts* opts, psx_match_pair_u8* host_pairs, int capacity, int* count)
+{
+    return match_pairs_u8(device, d_left, l_len, d_right, r_len, opts, host_pairs, nullptr, capacity, count);
+}
+
+extern "C" int psx_match_pairs_u8_dev(int device, const unsigned char* d_left, int l_len, const unsigned char* d_right, int r_len,
+                                      const psx_match_opts* opts, psx_match_pair_u8* d_pairs, int capacity, int* count)
+{
+    return match_pairs_u8(device, d_left, l_len, d_right, r_len, opts, nullptr, d_pairs, capacity, count);
+}
+
+static_assert(sizeof(psx_match_pair) == 16 && sizeof(psx_match_pair_u8) == 16, "a pair record is one 16-byte store");
+
+extern "C" int psx_pairs_join(const int* fwd_match, const float* fwd_dist, int l_len, const int* bwd_match, int r_len,
+                              const psx_match_opts* opts, psx_match_pair* pairs, int capacity, int* count)
+{
+    return psx_pairs_join_host<float, psx_match_pair>(fwd_match, fwd_dist, l_len, bwd_match, r_len, opts, pairs, capacity, count);
+}
+
+extern "C" int psx_pairs_join_u8(const int* fwd_match, const int* fwd_dist, int l_len, const int* bwd_match, int r_len,
+                                 const psx_match_opts* opts, psx_match_pair_u8* pairs, int capacity, int* count)
+{
+    return psx_pairs_join_host<int, psx_match_pair_u8>(fwd_match, fwd_dist, l_len, bwd_match, r_len, opts, pairs, capacity, count);
 }

@@ -1,6 +1,7 @@
 // popsift-match -- MatchingMode tool with the reference's option surface (src/application/match.cpp:49-300):
 // extracts two images into FeaturesDev objects and prints one accept / reject line per left descriptor
-// (FeaturesDev::match, features.cu:227-304).
+// (FeaturesDev::match, features.cu:227-304).  Not in the reference tool: --pairs FILE writes the matches as data
+// (FeaturesDev::matchPairs) instead of the accept / reject lines; --ratio and --mutual refine it.
 #include "options.h"
 #include "pgmread.h"
 
@@ -12,13 +13,19 @@
 
 #include <sys/stat.h>
 
+#include <cmath>
+#include <cstdio>
 #include <iostream>
 #include <string>
+#include <vector>
 
 using namespace std;
 
 static bool print_dev_info = false;
 static bool uchar_desc = false;
+static string pairs_file;
+static bool  have_ratio = false, mutual = false;
+static float pair_ratio = 0.8f;
 
 static bool is_file( const string& p ) { struct stat st; return stat( p.c_str(), &st ) == 0 && S_ISREG( st.st_mode ); }
 
@@ -53,11 +60,18 @@ int main( int argc, char** argv )
     all.flag( "dont-write", 0, "accepted for compatibility", []() {} );
     // not in the reference tool: quantise both descriptor sets to bytes and run the exact integer matcher
     all.flag( "uchar-descriptors", 0, "Match byte descriptors (FeaturesDev::matchBytes)", [&]() { uchar_desc = true; } );
+    all.add( "pairs", 0, true, "Write the matches to this file, one line per pair: left_feature left_descriptor right_feature "
+             "right_descriptor distance second_distance (instead of the accept / reject lines)", [&]( const string& s ) { pairs_file = s; } );
+    all.add( "ratio", 0, true, "Keep a pair iff distance / second_distance < ratio; 'inf' switches the test off. Default is 0.8 (needs --pairs)",
+             [&]( const string& s ) { pair_ratio = app::to_float( s ); have_ratio = true; } );
+    all.flag( "mutual", 0, "Keep a pair only if each descriptor is the other's nearest neighbour (needs --pairs)", [&]() { mutual = true; } );
     all.flag( "pgmread-loading", 0, "Use the PGM/PPM loader (the only loader of this build)", []() {} );
     try {
         all.parse( argc, argv );
         if( help ) { all.usage( cout ); return EXIT_SUCCESS; }
         if( lFile.empty() || rFile.empty() ) throw runtime_error( "the options '--left' and '--right' are required" );
+        if( ( have_ratio || mutual ) && pairs_file.empty() ) throw runtime_error( "the options '--ratio' and '--mutual' need '--pairs'" );
+        if( have_ratio && !( pair_ratio > 0.0f ) ) throw runtime_error( "the ratio must be positive" );
     } catch( const std::exception& e ) {
         cerr << "Error: " << e.what() << endl << endl << "Usage:" << endl << endl;
         all.usage( cerr );
@@ -82,8 +96,20 @@ int main( int argc, char** argv )
         cout << "Number of features:    " << rFeatures->getFeatureCount() << endl;
         cout << "Number of descriptors: " << rFeatures->getDescriptorCount() << endl;
         cout.flush();
-        if( uchar_desc ) lFeatures->matchBytes( rFeatures );
-        else             lFeatures->match( rFeatures );
+        if( !pairs_file.empty() ) {
+            popsift::MatchOptions mo;
+            mo.ratio = pair_ratio; mo.mutual = mutual; mo.bytes = uchar_desc;
+            const std::vector<popsift::Match> mm = lFeatures->matchPairs( rFeatures, mo );
+            FILE* f = fopen( pairs_file.c_str(), "w" );
+            if( f == nullptr ) throw runtime_error( "cannot write " + pairs_file );
+            for( const popsift::Match& m : mm )
+                fprintf( f, "%d %d %d %d %.3f %.3f\n", m.left_feature, m.left_descriptor, m.right_feature, m.right_descriptor,
+                         m.distance, m.second_distance );
+            fclose( f );
+            cout << "Number of matches: " << mm.size() << endl;
+        }
+        else if( uchar_desc ) lFeatures->matchBytes( rFeatures );
+        else                  lFeatures->match( rFeatures );
         fflush( stdout );
         delete lFeatures; delete rFeatures; delete lJob; delete rJob;
         sift.uninit();

@@ -495,4 +495,65 @@ void FeaturesDev::matchBytes( FeaturesDev* other )
     }
 }
 
+// FeaturesDev::matchPairs: psx_match_pairs / psx_match_pairs_u8 on the two descriptor arrays; the pair list (16 bytes
+// per pair) and the two reverse maps come back, nothing per descriptor
+std::vector<Match> FeaturesDev::matchPairs( FeaturesDev* other, const MatchOptions& opts )
+{
+    if( other == nullptr ) fatal( __FILE__, __LINE__, "FeaturesDev::matchPairs: null argument" );
+    if( other->_device != _device ) {
+        std::ostringstream ss;
+        ss << "FeaturesDev::matchPairs: the two objects live on different devices (" << _device << " and " << other->_device << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    const int l_len = getDescriptorCount();
+    const int r_len = other->getDescriptorCount();
+    std::vector<Match> out;
+    if( l_len <= 0 || r_len <= 0 ) return out;
+    psx_match_opts po;
+    po.ratio = opts.ratio;
+    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
+    int count = 0;
+    std::vector<psx_match_pair>    pf;
+    std::vector<psx_match_pair_u8> pb;
+    int rc;
+    if( opts.bytes ) {
+        pb.resize( l_len );
+        void *lb = nullptr, *rb = nullptr;
+        rc = psx_dev_alloc( _device, (size_t)l_len * 128, &lb );
+        if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)r_len * 128, &rb );
+        if( rc == PSX_OK ) rc = psx_quantize_desc( _device, (const float*)_ori, l_len, (unsigned char*)lb );
+        if( rc == PSX_OK ) rc = psx_quantize_desc( _device, (const float*)other->_ori, r_len, (unsigned char*)rb );
+        if( rc == PSX_OK ) rc = psx_match_pairs_u8( _device, (const unsigned char*)lb, l_len, (const unsigned char*)rb, r_len, &po, pb.data(), l_len, &count );
+        psx_dev_free( _device, lb );
+        psx_dev_free( _device, rb );
+    } else {
+        pf.resize( l_len );
+        rc = psx_match_pairs( _device, (const float*)_ori, l_len, (const float*)other->_ori, r_len, &po, pf.data(), l_len, &count );
+    }
+    if( rc != PSX_OK ) {
+        std::ostringstream ss;
+        ss << "FeaturesDev::matchPairs failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    std::vector<int> l_fem( l_len ), r_fem( r_len );
+    if( psx_dev_read( _device, l_fem.data(), _rev, (size_t)l_len * sizeof(int) ) != PSX_OK ||
+        psx_dev_read( other->_device, r_fem.data(), other->_rev, (size_t)r_len * sizeof(int) ) != PSX_OK )
+        fatal( __FILE__, __LINE__, "FeaturesDev::matchPairs: reading the reverse maps failed" );
+    out.resize( count );
+    for( int k = 0; k < count; k++ ) {
+        Match& m = out[k];
+        if( opts.bytes ) {
+            m.left_descriptor = pb[k].left; m.right_descriptor = pb[k].right;
+            m.distance        = pb[k].d1 == INT32_MAX ? INFINITY : (float)pb[k].d1;
+            m.second_distance = pb[k].d2 == INT32_MAX ? INFINITY : (float)pb[k].d2;
+        } else {
+            m.left_descriptor = pf[k].left; m.right_descriptor = pf[k].right;
+            m.distance = pf[k].d1; m.second_distance = pf[k].d2;
+        }
+        m.left_feature  = l_fem[m.left_descriptor];
+        m.right_feature = r_fem[m.right_descriptor];
+    }
+    return out;
+}
+
 } // namespace popsift

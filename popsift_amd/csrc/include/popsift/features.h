@@ -118,6 +118,22 @@ using Features = FeaturesHost;
 
 std::ostream& operator<<( std::ostream& ostr, const FeaturesHost& feature );
 
+/// How FeaturesDev::matchPairs filters: the pair rule of psx_match_pairs (include/popsift_hip.h, "matches as data")
+struct MatchOptions
+{
+    float ratio  = 0.8f;    ///< keep a pair iff distance / second_distance < ratio (float32); INFINITY: no ratio test
+    bool  mutual = false;   ///< cross-check: the right descriptor's best left descriptor must be this one
+    bool  bytes  = false;   ///< quantise both sides (psx_quantize_desc) and run the exact integer matcher, as matchBytes
+};
+
+/// One correspondence of FeaturesDev::matchPairs
+struct Match
+{
+    int   left_feature, right_feature;          ///< indices into the two feature arrays (via the reverse maps)
+    int   left_descriptor, right_descriptor;    ///< indices into the two descriptor arrays
+    float distance, second_distance;            ///< squared; byte distances converted (exact), +inf: no second neighbour
+};
+
 /// Device-resident result (MatchingMode): arrays live in HBM of the extracting device.
 class FeaturesDev : public FeaturesBase
 {
@@ -139,6 +155,10 @@ public:
     /// the same on bytes: both float arrays quantised on the device (psx_quantize_desc), then the exact integer
     /// matcher psx_match_u8; prints the same accept / reject lines as match()
     void matchBytes( FeaturesDev* other );
+    /// the matches as data: the pairs (descriptor of *this, its best descriptor of *other) that pass the ratio test
+    /// and, with MatchOptions::mutual, the cross-check, in ascending left descriptor; prints nothing.  Throws
+    /// std::runtime_error for a null argument, objects on different devices, or a failing call.
+    std::vector<Match> matchPairs( FeaturesDev* other, const MatchOptions& opts = MatchOptions() );
 
     inline Feature*    getFeatures()    { return _ext; }
     inline Descriptor* getDescriptors() { return _ori; }
