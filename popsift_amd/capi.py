@@ -800,6 +800,17 @@ class Context:
         return lib().psx_stream(self._h)
 
 
+def device_info(device=0):
+    """psx_device_info: dict(name, total_mem, compute_units, clock_khz) of a device."""
+    L = lib()
+    L.psx_device_info.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    name = C.create_string_buffer(256)
+    mem, cus, khz = C.c_size_t(), C.c_int(), C.c_int()
+    if L.psx_device_info(device, name, 256, C.byref(mem), C.byref(cus), C.byref(khz)) != 0:
+        raise PopSiftError("psx_device_info failed")
+    return dict(name=name.value.decode(), total_mem=mem.value, compute_units=cus.value, clock_khz=khz.value)
+
+
 def copy_bench(device=0, nbytes=0, reps=10):
     """Measured HBM roofline: (GB/s, ms per launch) of the 16 B/lane streaming copy kernel (psx_copy_bench)."""
     ms, by = C.c_float(), C.c_double()
