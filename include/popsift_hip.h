@@ -361,6 +361,71 @@ int psx_pairs_join(const int* fwd_match, const float* fwd_dist, int l_len, const
 int psx_pairs_join_u8(const int* fwd_match, const int* fwd_dist, int l_len, const int* bwd_match, int r_len,
                       const psx_match_opts* opts, psx_match_pair_u8* pairs, int capacity, int* count);
 
+/* ---- guided matching ---------------------------------------------------------------------
+ * The 2-NN search restricted by what the caller knows about where a match can lie (AliceVision's guidedMatching, a
+ * stereo search window, a tracker's prediction; the reference has no counterpart): a homography -- identity H is a plain
+ * search window of radius tol -- or a fundamental matrix.  Every left descriptor ranks only its ADMISSIBLE right
+ * descriptors; filtering the unguided matcher's pairs afterwards is not the same result (a left descriptor whose globally
+ * nearest right one is inadmissible is lost there, and its ratio test ran against a neighbour the geometry excludes).
+ * One rule, shared by host and device (csrc/hip/guide_rule.h); INTEGRATION.md ("Guided matching") states it in words.
+ * Positions are in INPUT-IMAGE units, as psx_feature reports them.  With left position (xl, yl), right position
+ * (xr, yr), float32 arithmetic only, every operation rounded on its own in exactly this order (no fused multiply-add,
+ * no division, no square root):
+ *     a = (m0*xl + m1*yl) + m2;   b = (m3*xl + m4*yl) + m5;   c = (m6*xl + m7*yl) + m8
+ *     HOMOGRAPHY: allowed iff  c > 0  and  (dx*dx + dy*dy) <= (tol*c)*(tol*c),   dx = a - c*xr,  dy = b - c*yr
+ *     EPIPOLAR:   e = (a*xr + b*yr) + c;   allowed iff  e*e <= (tol*tol) * (a*a + b*b)
+ * The IEEE result of the comparison is the rule: any NaN makes a pair inadmissible.  The relation is defined on (left i,
+ * right j) and is NOT symmetric in its roles: the backward pass of a cross-check evaluates the SAME relation with the
+ * loops exchanged and never a transposed or inverted matrix.
+ * A guide is valid iff kind is 1 or 2, all nine entries are finite and tol is finite and >= 0; anything else is
+ * PSX_ERR_INVALID, with nothing touched. */
+#define PSX_GUIDE_HOMOGRAPHY 1   /* m = H, row major: right point within tol of H * left point            */
+#define PSX_GUIDE_EPIPOLAR   2   /* m = F, row major: right point within tol of the line F * left point   */
+typedef struct psx_guide { int kind; float m[9]; float tol; } psx_guide;   /* positions in INPUT-IMAGE units, as psx_feature reports them */
+
+/* The rule on the host, no device and no context: allowed[i * nr + j] = 1 where (left i, right j) is admissible, else 0.
+ * left_xy / right_xy: nl / nr (x, y) pairs.  PSX_ERR_INVALID for an invalid guide, negative sizes, or a NULL array with
+ * a non-zero size (allowed is needed when nl * nr > 0). */
+int psx_guide_allows(const psx_guide* guide, const float* left_xy, int nl, const float* right_xy, int nr,
+                     unsigned char* allowed);
+
+/* d_xy[2k], d_xy[2k+1] = xpos, ypos of the feature that descriptor k belongs to: a gather over what psx_clone_results
+ * leaves (d_features: its psx_feature_dev records, d_reverse_map: its descriptor -> feature map; every entry must index
+ * a record).  All three are DEVICE pointers, d_xy to 2 n_desc floats, 8-byte aligned.  Synchronous. */
+int psx_desc_positions(int device, const psx_feature_dev* d_features, const int* d_reverse_map, int n_desc, float* d_xy);
+
+/* psx_match / psx_match_u8 with every left descriptor's search restricted to its admissible right descriptors: the two
+ * smallest under (distance, index) order among them.  Output layout and conventions are exactly those of psx_match /
+ * psx_match_u8: float distances from the reference's operation tree, bit for bit, byte distances exact integers; a
+ * missing neighbour is +inf / INT_MAX with index 0 -- which now also arises with zero or one admissible right
+ * descriptor; accept = (d1 / d2 < 0.8f).  d_left_xy / d_right_xy: DEVICE pointers to l_len / r_len (x, y) pairs, 8-byte
+ * aligned (psx_desc_positions writes them).  Additionally PSX_ERR_INVALID for an invalid guide or a NULL position array
+ * with a non-zero length.  Scratch as psx_match (psx_match_release).  Synchronous. */
+int psx_match_guided(int device, const float* d_left, const float* d_left_xy, int l_len,
+                     const float* d_right, const float* d_right_xy, int r_len, const psx_guide* guide,
+                     int* host_match, float* host_dist);
+int psx_match_guided_u8(int device, const unsigned char* d_left, const float* d_left_xy, int l_len,
+                        const unsigned char* d_right, const float* d_right_xy, int r_len, const psx_guide* guide,
+                        int* host_match, int* host_dist);
+
+/* psx_match_pairs and its three siblings on guided directed passes: F = the guided L -> R pass; with PSX_PAIRS_MUTUAL
+ * B = the guided R -> L pass on the SAME relation (right descriptor j ranks the left descriptors i with (i, j)
+ * admissible); then the join and compaction of psx_match_pairs, unchanged.  Record types, ordering, capacity and "how
+ * many?" semantics, empty sides, argument errors and scratch are as documented there; additionally PSX_ERR_INVALID for
+ * an invalid guide or a NULL position array with a non-zero length. */
+int psx_match_pairs_guided(int device, const float* d_left, const float* d_left_xy, int l_len,
+                           const float* d_right, const float* d_right_xy, int r_len, const psx_guide* guide,
+                           const psx_match_opts* opts, psx_match_pair* host_pairs, int capacity, int* count);
+int psx_match_pairs_guided_u8(int device, const unsigned char* d_left, const float* d_left_xy, int l_len,
+                              const unsigned char* d_right, const float* d_right_xy, int r_len, const psx_guide* guide,
+                              const psx_match_opts* opts, psx_match_pair_u8* host_pairs, int capacity, int* count);
+int psx_match_pairs_guided_dev(int device, const float* d_left, const float* d_left_xy, int l_len,
+                               const float* d_right, const float* d_right_xy, int r_len, const psx_guide* guide,
+                               const psx_match_opts* opts, psx_match_pair* d_pairs, int capacity, int* count);
+int psx_match_pairs_guided_u8_dev(int device, const unsigned char* d_left, const float* d_left_xy, int l_len,
+                                  const unsigned char* d_right, const float* d_right_xy, int r_len, const psx_guide* guide,
+                                  const psx_match_opts* opts, psx_match_pair_u8* d_pairs, int capacity, int* count);
+
 /* ---- caller-supplied keypoints ------------------------------------------------------------
  * Describing points the caller brings along instead of the ones the DoG detector finds (what OpenCV calls
  * useProvidedKeypoints and VLFeat calls frames; the reference has no counterpart).  A record carries what a

@@ -97,6 +97,8 @@ SYMBOLS = [
     "psx_set_mask", "psx_set_mask_dev", "psx_mask_keep",
     "psx_match_opts_default", "psx_match_pairs", "psx_match_pairs_u8", "psx_match_pairs_dev", "psx_match_pairs_u8_dev",
     "psx_pairs_join", "psx_pairs_join_u8",
+    "psx_guide_allows", "psx_desc_positions", "psx_match_guided", "psx_match_guided_u8",
+    "psx_match_pairs_guided", "psx_match_pairs_guided_u8", "psx_match_pairs_guided_dev", "psx_match_pairs_guided_u8_dev",
 ]
 
 PAIRS_MUTUAL = 1     # PSX_PAIRS_MUTUAL
@@ -108,6 +110,30 @@ PAIR_U8_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4"), ("d1", "<i4"), ("d2
 class MatchOpts(C.Structure):
     """psx_match_opts: {0.8, 0} is the accept flag of psx_match."""
     _fields_ = [("ratio", C.c_float), ("flags", C.c_int)]
+
+
+GUIDE_HOMOGRAPHY = 1     # PSX_GUIDE_HOMOGRAPHY
+GUIDE_EPIPOLAR = 2       # PSX_GUIDE_EPIPOLAR
+
+
+class Guide(C.Structure):
+    """psx_guide: which (left, right) pairs guided matching may form, from their positions in input-image units.
+    Guide.homography(H, tol): the right point lies within tol of H * left point (identity H: a search window);
+    Guide.epipolar(F, tol): the right point lies within tol of the line F * left point.  Matrices row major."""
+    _fields_ = [("kind", C.c_int), ("m", C.c_float * 9), ("tol", C.c_float)]
+
+    @classmethod
+    def make(cls, kind, m, tol):
+        m = np.asarray(m, dtype=np.float32).reshape(9)
+        return cls(kind, (C.c_float * 9)(*[float(v) for v in m]), float(np.float32(tol)))
+
+    @classmethod
+    def homography(cls, H, tol):
+        return cls.make(GUIDE_HOMOGRAPHY, H, tol)
+
+    @classmethod
+    def epipolar(cls, F, tol):
+        return cls.make(GUIDE_EPIPOLAR, F, tol)
 
 
 DESCFMT_F32 = 0      # PSX_DESCFMT_F32
@@ -178,6 +204,12 @@ def lib():
             getattr(L, n).argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(MatchOpts), vp, C.c_int, ip]
         for n in ("psx_pairs_join", "psx_pairs_join_u8"):
             getattr(L, n).argtypes = [vp, vp, C.c_int, vp, C.c_int, C.POINTER(MatchOpts), vp, C.c_int, ip]
+        L.psx_guide_allows.argtypes = [C.POINTER(Guide), vp, C.c_int, vp, C.c_int, vp]
+        L.psx_desc_positions.argtypes = [C.c_int, vp, vp, C.c_int, vp]
+        for n in ("psx_match_guided", "psx_match_guided_u8"):
+            getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(Guide), vp, vp]
+        for n in ("psx_match_pairs_guided", "psx_match_pairs_guided_u8", "psx_match_pairs_guided_dev", "psx_match_pairs_guided_u8_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(Guide), C.POINTER(MatchOpts), vp, C.c_int, ip]
         _LIB = L
     return _LIB
 
@@ -434,21 +466,141 @@ def pairs_join(fwd_match, fwd_dist, bwd_match, r_len, ratio=0.8, mutual=False, c
     return got[0] if capacity is None else got
 
 
+def _xy(xy):
+    """(n, 2) float32 positions, C-contiguous"""
+    return np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+
+
+def guide_allows(guide, left_xy, right_xy):
+    """psx_guide_allows: the guide's rule on the host.  left_xy (nl, 2), right_xy (nr, 2): positions in input-image units.
+    Returns the (nl, nr) bool relation, [i, j] True where (left i, right j) is admissible.  No device."""
+    lx, rx = _xy(left_xy), _xy(right_xy)
+    out = np.zeros((len(lx), len(rx)), np.uint8)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    rc = lib().psx_guide_allows(C.byref(guide), ptr(lx), len(lx), ptr(rx), len(rx), ptr(out))
+    if rc != 0:
+        raise PopSiftError("psx_guide_allows failed (%d)" % rc)
+    return out.astype(bool)
+
+
+def desc_positions(features_ptr, reverse_map_ptr, n_desc, xy_ptr, device=0):
+    """psx_desc_positions on DEVICE pointers: xy[k] = (xpos, ypos) of the feature descriptor k belongs to, gathered from
+    what psx_clone_results leaves; xy_ptr: 2 n_desc floats, 8-byte aligned."""
+    rc = lib().psx_desc_positions(device, C.c_void_p(features_ptr), C.c_void_p(reverse_map_ptr), n_desc, C.c_void_p(xy_ptr))
+    if rc != 0:
+        raise PopSiftError("psx_desc_positions failed (%d)" % rc)
+
+
+def _guided_sides(left, left_xy, right, right_xy, dtype):
+    left = np.ascontiguousarray(left, dtype=dtype).reshape(-1, 128)
+    right = np.ascontiguousarray(right, dtype=dtype).reshape(-1, 128)
+    lx, rx = _xy(left_xy), _xy(right_xy)
+    if len(lx) != len(left) or len(rx) != len(right):
+        raise ValueError("one position per descriptor")
+    return left, lx, right, rx
+
+
+def _match_guided(name, dtype, ddtype, left, left_xy, right, right_xy, guide, device):
+    L = lib()
+    left, lx, right, rx = _guided_sides(left, left_xy, right, right_xy, dtype)
+    bufs = []
+    try:
+        pl, plx, pr, prx = _to_device(L, device, [left, lx, right, rx], bufs)
+        mm = np.zeros((len(left), 3), np.int32)
+        dd = np.zeros((len(left), 2), ddtype)
+        rc = getattr(L, name)(device, pl, plx, len(left), pr, prx, len(right), C.byref(guide),
+                              mm.ctypes.data_as(C.c_void_p), dd.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise PopSiftError("%s failed (%d)" % (name, rc))
+        return mm, dd
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def match_guided(left, left_xy, right, right_xy, guide, device=0):
+    """psx_match_guided on host arrays (through device buffers): as match(), every left descriptor's search restricted to
+    the right descriptors the guide admits.  left_xy / right_xy: (n, 2) / (m, 2) float32 positions."""
+    return _match_guided("psx_match_guided", np.float32, np.float32, left, left_xy, right, right_xy, guide, device)
+
+
+def match_guided_u8(left, left_xy, right, right_xy, guide, device=0):
+    """psx_match_guided_u8 on host arrays of uint8 descriptors: as match_u8(), restricted by the guide."""
+    return _match_guided("psx_match_guided_u8", np.uint8, np.int32, left, left_xy, right, right_xy, guide, device)
+
+
+def _guided_fn(fn, plx, prx, guide):
+    """a guided pairs entry point with the argument order _pairs_call uses"""
+    return lambda dev, pl, nl, pr, nr, *rest: fn(dev, pl, plx, nl, pr, prx, nr, C.byref(guide), *rest)
+
+
+def _match_pairs_guided(name, dtype, pair_dtype, left, left_xy, right, right_xy, guide, ratio, mutual, device, capacity):
+    L = lib()
+    left, lx, right, rx = _guided_sides(left, left_xy, right, right_xy, dtype)
+    bufs = []
+    try:
+        pl, plx, pr, prx = _to_device(L, device, [left, lx, right, rx], bufs)
+        got = _pairs_call(_guided_fn(getattr(L, name), plx, prx, guide), name, device, pl, len(left), pr, len(right), ratio, mutual,
+                          pair_dtype, capacity)
+        return got[0] if capacity is None else got
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def match_pairs_guided(left, left_xy, right, right_xy, guide, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs_guided on host arrays (through device buffers): PAIR_DTYPE records as match_pairs(), from guided
+    directed passes.  With a capacity: (the first min(count, capacity) records, count)."""
+    return _match_pairs_guided("psx_match_pairs_guided", np.float32, PAIR_DTYPE, left, left_xy, right, right_xy, guide, ratio, mutual,
+                               device, capacity)
+
+
+def match_pairs_guided_u8(left, left_xy, right, right_xy, guide, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs_guided_u8 on host arrays of uint8 descriptors: PAIR_U8_DTYPE records, as match_pairs_guided."""
+    return _match_pairs_guided("psx_match_pairs_guided_u8", np.uint8, PAIR_U8_DTYPE, left, left_xy, right, right_xy, guide, ratio, mutual,
+                               device, capacity)
+
+
+def match_pairs_guided_dev(left_ptr, left_xy_ptr, l_len, right_ptr, right_xy_ptr, r_len, guide, out_ptr, capacity, ratio=0.8,
+                           mutual=False, device=0, u8=False):
+    """psx_match_pairs_guided_dev / psx_match_pairs_guided_u8_dev on DEVICE pointers: the records go into the caller's
+    device buffer at out_ptr (16-byte aligned, `capacity` records); returns the total count."""
+    L = lib()
+    fn = L.psx_match_pairs_guided_u8_dev if u8 else L.psx_match_pairs_guided_dev
+    n = C.c_int(-1)
+    o = match_opts(ratio, mutual)
+    rc = fn(device, C.c_void_p(left_ptr), C.c_void_p(left_xy_ptr), l_len, C.c_void_p(right_ptr), C.c_void_p(right_xy_ptr), r_len,
+            C.byref(guide), C.byref(o), C.c_void_p(out_ptr), capacity, C.byref(n))
+    if rc != 0:
+        raise PopSiftError("psx_match_pairs_guided%s_dev failed (%d)" % ("_u8" if u8 else "", rc))
+    return n.value
+
+
 class DeviceDescriptors:
     """Descriptor sets resident on the device (what FeaturesDev holds, popsift.cpp:346-383): upload once, match many times."""
 
-    def __init__(self, arr, device=0):
+    def __init__(self, arr, device=0, xy=None):
+        """xy: None, or one (x, y) position per descriptor in input-image units (needed by match_pairs_guided)"""
         L = lib()
         L.psx_dev_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
         L.psx_dev_free.argtypes = [C.c_int, C.c_void_p]
         L.psx_dev_write.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
         arr = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1, 128)
-        self.n, self.device, self.ptr = len(arr), device, C.c_void_p()
+        self.n, self.device, self.ptr, self.xy_ptr = len(arr), device, C.c_void_p(), C.c_void_p()
         if self.n:
             if L.psx_dev_alloc(device, arr.nbytes, C.byref(self.ptr)) != 0:
                 raise PopSiftError("psx_dev_alloc failed")
             if L.psx_dev_write(device, self.ptr, arr.ctypes.data_as(C.c_void_p), arr.nbytes) != 0:
                 raise PopSiftError("psx_dev_write failed")
+        if xy is not None:
+            xy = _xy(xy)
+            if len(xy) != self.n:
+                raise ValueError("one position per descriptor")
+            if self.n:
+                if L.psx_dev_alloc(device, xy.nbytes, C.byref(self.xy_ptr)) != 0:
+                    raise PopSiftError("psx_dev_alloc failed")
+                if L.psx_dev_write(device, self.xy_ptr, xy.ctypes.data_as(C.c_void_p), xy.nbytes) != 0:
+                    raise PopSiftError("psx_dev_write failed")
 
     def match(self, right):
         """psx_match(self as left, right: DeviceDescriptors): (n,3) int32 and (n,2) float32 host arrays"""
@@ -467,10 +619,22 @@ class DeviceDescriptors:
                           ratio, mutual, PAIR_DTYPE, capacity)
         return got[0] if capacity is None else got
 
+    def match_pairs_guided(self, right, guide, ratio=0.8, mutual=False, capacity=None):
+        """psx_match_pairs_guided(self as left, right: DeviceDescriptors, both built with positions): PAIR_DTYPE records;
+        with a capacity (records, count)"""
+        if (self.n and not self.xy_ptr) or (right.n and not right.xy_ptr):
+            raise ValueError("both sides need positions (DeviceDescriptors(arr, xy=...))")
+        fn = _guided_fn(lib().psx_match_pairs_guided, self.xy_ptr, right.xy_ptr, guide)
+        got = _pairs_call(fn, "psx_match_pairs_guided", self.device, self.ptr, self.n, right.ptr, right.n, ratio, mutual, PAIR_DTYPE, capacity)
+        return got[0] if capacity is None else got
+
     def close(self):
         if self.ptr:
             lib().psx_dev_free(self.device, self.ptr)
             self.ptr = C.c_void_p()
+        if self.xy_ptr:
+            lib().psx_dev_free(self.device, self.xy_ptr)
+            self.xy_ptr = C.c_void_p()
 
     def __del__(self):
         try:

@@ -23,6 +23,7 @@
 // of the reference produces.
 #include "psx_internal.h"
 #include "match_join.h"
+#include "match_scratch.h"
 
 #include <climits>
 #include <cstdio>
@@ -534,74 +535,12 @@ __global__ __launch_bounds__(256) void k_match_exact(const float* __restrict__ l
 
 } // namespace
 
-// Scratch of one calling thread: a private non-blocking stream (no null-stream launch, so nothing else on
-// the device is synchronised) and buffers that only ever grow.  Freed when the thread exits.
+// the calling thread's scratch (MatchScratch: match_scratch.h, shared with match_guided.hip through psx_match_scratch)
 namespace {
-struct MatchScratch {
-    // 0-9: psx_match, 10-12: psx_match_u8; the pair search: 13 the backward direction's results of psx_match_pairs,
-    // 14 those of psx_match_pairs_u8, 15 the join's per-workgroup totals
-    static constexpr int NBUF = 16;
-    int device = -1;
-    hipStream_t stream = nullptr;
-    void* buf[NBUF] = {};
-    size_t cap[NBUF] = {};
-    void* hpin = nullptr;                // pinned staging of the results: a DMA into pageable caller memory goes through the
-    size_t hpin_cap = 0;                 // runtime's own bounce buffers, ~0.5 ms per call on this stack
-    bool tidy = false;                   // the prefilter's counters are zero (left so by the previous call's last kernel)
-    PsxTuning tune;                      // the POPSIFT_MATCH_* switches and the CU count of `device`: taken in bind()
-    int mfma_per_cu = 0;                 // workgroups of the prefilter kernel resident per CU on `device` (0: not asked yet)
-    void release()
-    {
-        if (device < 0) return;
-        int cur = -1;                                        // the caller's current device is left as it was
-        if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-        (void)hipSetDevice(device);
-        for (int i = 0; i < NBUF; i++) { (void)hipFree(buf[i]); buf[i] = nullptr; cap[i] = 0; }
-        tidy = false;
-        if (hpin) (void)hipHostFree(hpin);
-        hpin = nullptr; hpin_cap = 0;
-        if (stream) (void)hipStreamDestroy(stream);
-        stream = nullptr; device = -1;
-        if (cur >= 0) (void)hipSetDevice(cur);
-    }
-    // the scratch of `device` (a call for another device releases the previous one's first)
-    bool bind(int dev)
-    {
-        if (device == dev) return true;
-        release();
-        if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return false;
-        device = dev;
-        tune = psx_tuning_from_env();
-        if (hipDeviceGetAttribute(&tune.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || tune.cus <= 0) tune.cus = 256;
-        mfma_per_cu = 0;
-        return true;
-    }
-    bool need_pinned(size_t bytes)
-    {
-        if (bytes <= hpin_cap && hpin) return true;
-        if (hpin) (void)hipHostFree(hpin);
-        hpin = nullptr; hpin_cap = 0;
-        if (hipHostMalloc(&hpin, bytes, hipHostMallocDefault) != hipSuccess) return false;
-        hpin_cap = bytes;
-        return true;
-    }
-    bool need(int i, size_t bytes)
-    {
-        if (bytes <= cap[i] && buf[i]) return true;
-        (void)hipFree(buf[i]); buf[i] = nullptr; cap[i] = 0;
-        tidy = false;
-        if (hipMalloc(&buf[i], bytes) != hipSuccess) return false;
-        cap[i] = bytes;
-        return true;
-    }
-    // Thread exit.  For the main thread that is process teardown, where the HIP runtime may already be gone: ask it
-    // first (a finalised runtime answers with an error) and then leave the buffers to the process exit.
-    ~MatchScratch() { int n = 0; if (device >= 0 && hipGetDeviceCount(&n) == hipSuccess && n > 0) release(); }
-};
 thread_local MatchScratch t_scratch;
 } // namespace
 
-// frees the calling thread's matcher scratch (stream + up to 16 device buffers); an explicit user call -- PopSift::uninit
+// frees the calling thread's matcher scratch (stream + up to 19 device buffers); an explicit user call -- PopSift::uninit
 // does NOT call it: the scratch belongs to the thread, not to one PopSift object (another replica may be using it)
 extern "C" int psx_match_release(void)
 {
@@ -1196,6 +1135,21 @@ int match_pairs_u8(int device, const unsigned char* d_left, int l_len, const uns
 }
 
 } // namespace
+
+// what match_guided.hip shares (match_scratch.h)
+MatchScratch& psx_match_scratch() { return t_scratch; }
+
+int psx_pairs_finish_f32(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
+                         void* host_pairs, void* d_pairs, int capacity, int* count)
+{
+    return pairs_finish<float>(sc, d_fwd, l_len, d_bwd, opts, host_pairs, d_pairs, capacity, count);
+}
+
+int psx_pairs_finish_u8(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
+                        void* host_pairs, void* d_pairs, int capacity, int* count)
+{
+    return pairs_finish<int>(sc, d_fwd, l_len, d_bwd, opts, host_pairs, d_pairs, capacity, count);
+}
 
 extern "C" int psx_match_opts_default(psx_match_opts* o)
 {

@@ -1,7 +1,8 @@
 // popsift-match -- MatchingMode tool with the reference's option surface (src/application/match.cpp:49-300):
 // extracts two images into FeaturesDev objects and prints one accept / reject line per left descriptor
 // (FeaturesDev::match, features.cu:227-304).  Not in the reference tool: --pairs FILE writes the matches as data
-// (FeaturesDev::matchPairs) instead of the accept / reject lines; --ratio and --mutual refine it.
+// (FeaturesDev::matchPairs) instead of the accept / reject lines; --ratio and --mutual refine it; --homography or
+// --fundamental with --guide-tol restrict the search to the pairs a guide admits (FeaturesDev::matchPairsGuided).
 #include "options.h"
 #include "pgmread.h"
 
@@ -26,6 +27,22 @@ static bool uchar_desc = false;
 static string pairs_file;
 static bool  have_ratio = false, mutual = false;
 static float pair_ratio = 0.8f;
+static bool  have_h = false, have_f = false, have_tol = false;
+static popsift::MatchGuide guide;
+
+// "m0,...,m8": nine numbers, row major
+static void parse_matrix( const string& opt, const string& s, float* m )
+{
+    size_t pos = 0;
+    for( int k = 0; k < 9; k++ ) {
+        const size_t end = k < 8 ? s.find( ',', pos ) : s.size();
+        if( end == string::npos ) throw runtime_error( "the option '--" + opt + "' takes nine numbers m0,...,m8" );
+        const string v = s.substr( pos, end - pos );
+        try { m[k] = app::to_float( v ); }
+        catch( const std::logic_error& ) { throw runtime_error( "bad number '" + v + "' in the option '--" + opt + "'" ); }
+        pos = end + 1;
+    }
+}
 
 static bool is_file( const string& p ) { struct stat st; return stat( p.c_str(), &st ) == 0 && S_ISREG( st.st_mode ); }
 
@@ -65,6 +82,12 @@ int main( int argc, char** argv )
     all.add( "ratio", 0, true, "Keep a pair iff distance / second_distance < ratio; 'inf' switches the test off. Default is 0.8 (needs --pairs)",
              [&]( const string& s ) { pair_ratio = app::to_float( s ); have_ratio = true; } );
     all.flag( "mutual", 0, "Keep a pair only if each descriptor is the other's nearest neighbour (needs --pairs)", [&]() { mutual = true; } );
+    all.add( "homography", 0, true, "Guided matching: m0,...,m8 = H, row major; keep a right point only within --guide-tol pixels of "
+             "H * left point (needs --pairs and --guide-tol)", [&]( const string& s ) { parse_matrix( "homography", s, guide.m ); have_h = true; } );
+    all.add( "fundamental", 0, true, "Guided matching: m0,...,m8 = F, row major; keep a right point only within --guide-tol pixels of "
+             "the line F * left point (needs --pairs and --guide-tol)", [&]( const string& s ) { parse_matrix( "fundamental", s, guide.m ); have_f = true; } );
+    all.add( "guide-tol", 0, true, "Guided matching: the tolerance in pixels (needs --homography or --fundamental)",
+             [&]( const string& s ) { guide.tol = app::to_float( s ); have_tol = true; } );
     all.flag( "pgmread-loading", 0, "Use the PGM/PPM loader (the only loader of this build)", []() {} );
     try {
         all.parse( argc, argv );
@@ -72,6 +95,12 @@ int main( int argc, char** argv )
         if( lFile.empty() || rFile.empty() ) throw runtime_error( "the options '--left' and '--right' are required" );
         if( ( have_ratio || mutual ) && pairs_file.empty() ) throw runtime_error( "the options '--ratio' and '--mutual' need '--pairs'" );
         if( have_ratio && !( pair_ratio > 0.0f ) ) throw runtime_error( "the ratio must be positive" );
+        if( have_h && have_f ) throw runtime_error( "at most one of the options '--homography' and '--fundamental' may be given" );
+        if( ( have_h || have_f ) && pairs_file.empty() ) throw runtime_error( "the options '--homography' and '--fundamental' need '--pairs'" );
+        if( have_tol && !( have_h || have_f ) ) throw runtime_error( "the option '--guide-tol' needs '--homography' or '--fundamental'" );
+        if( ( have_h || have_f ) && !have_tol ) throw runtime_error( "the options '--homography' and '--fundamental' need '--guide-tol'" );
+        if( have_tol && !( guide.tol >= 0.0f && std::isfinite( guide.tol ) ) ) throw runtime_error( "the guide tolerance must be finite and not negative" );
+        guide.kind = have_f ? popsift::MatchGuide::Epipolar : popsift::MatchGuide::Homography;
     } catch( const std::exception& e ) {
         cerr << "Error: " << e.what() << endl << endl << "Usage:" << endl << endl;
         all.usage( cerr );
@@ -99,7 +128,8 @@ int main( int argc, char** argv )
         if( !pairs_file.empty() ) {
             popsift::MatchOptions mo;
             mo.ratio = pair_ratio; mo.mutual = mutual; mo.bytes = uchar_desc;
-            const std::vector<popsift::Match> mm = lFeatures->matchPairs( rFeatures, mo );
+            const std::vector<popsift::Match> mm = ( have_h || have_f ) ? lFeatures->matchPairsGuided( rFeatures, guide, mo )
+                                                                        : lFeatures->matchPairs( rFeatures, mo );
             FILE* f = fopen( pairs_file.c_str(), "w" );
             if( f == nullptr ) throw runtime_error( "cannot write " + pairs_file );
             for( const popsift::Match& m : mm )

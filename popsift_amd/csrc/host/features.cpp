@@ -495,19 +495,24 @@ void FeaturesDev::matchBytes( FeaturesDev* other )
     }
 }
 
-// FeaturesDev::matchPairs: psx_match_pairs / psx_match_pairs_u8 on the two descriptor arrays; the pair list (16 bytes
-// per pair) and the two reverse maps come back, nothing per descriptor
-std::vector<Match> FeaturesDev::matchPairs( FeaturesDev* other, const MatchOptions& opts )
+// FeaturesDev::matchPairs / matchPairsGuided: psx_match_pairs* / psx_match_pairs_guided* on the two descriptor arrays; the
+// pair list (16 bytes per pair) and the two reverse maps come back, nothing per descriptor.  guide == nullptr: unguided.
+static std::vector<Match> match_pairs_impl( const char* who, int device, int other_device,
+                                            Feature* l_ext, Descriptor* l_ori, int* l_rev, int l_len,
+                                            Feature* r_ext, Descriptor* r_ori, int* r_rev, int r_len,
+                                            const MatchGuide* guide, const MatchOptions& opts )
 {
-    if( other == nullptr ) fatal( __FILE__, __LINE__, "FeaturesDev::matchPairs: null argument" );
-    if( other->_device != _device ) {
-        std::ostringstream ss;
-        ss << "FeaturesDev::matchPairs: the two objects live on different devices (" << _device << " and " << other->_device << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    const int l_len = getDescriptorCount();
-    const int r_len = other->getDescriptorCount();
     std::vector<Match> out;
+    psx_guide pg;
+    if( guide != nullptr ) {
+        pg.kind = (int)guide->kind;
+        for( int k = 0; k < 9; k++ ) pg.m[k] = guide->m[k];
+        pg.tol = guide->tol;
+        // refused here, before any device is touched (and for empty sides too): what psx_match_pairs_guided refuses
+        bool ok = ( pg.kind == PSX_GUIDE_HOMOGRAPHY || pg.kind == PSX_GUIDE_EPIPOLAR ) && std::isfinite( pg.tol ) && pg.tol >= 0.0f;
+        for( int k = 0; k < 9; k++ ) ok = ok && std::isfinite( pg.m[k] );
+        if( !ok ) fatal( __FILE__, __LINE__, std::string( who ) + ": invalid guide (kind 1 or 2, finite entries, finite tolerance >= 0)" );
+    }
     if( l_len <= 0 || r_len <= 0 ) return out;
     psx_match_opts po;
     po.ratio = opts.ratio;
@@ -515,30 +520,46 @@ std::vector<Match> FeaturesDev::matchPairs( FeaturesDev* other, const MatchOptio
     int count = 0;
     std::vector<psx_match_pair>    pf;
     std::vector<psx_match_pair_u8> pb;
-    int rc;
+    int rc = PSX_OK;
+    void *lb = nullptr, *rb = nullptr, *lxy = nullptr, *rxy = nullptr;
+    if( guide != nullptr ) {
+        rc = psx_dev_alloc( device, (size_t)l_len * 2 * sizeof(float), &lxy );
+        if( rc == PSX_OK ) rc = psx_dev_alloc( device, (size_t)r_len * 2 * sizeof(float), &rxy );
+        if( rc == PSX_OK ) rc = psx_desc_positions( device, (const psx_feature_dev*)l_ext, l_rev, l_len, (float*)lxy );
+        if( rc == PSX_OK ) rc = psx_desc_positions( device, (const psx_feature_dev*)r_ext, r_rev, r_len, (float*)rxy );
+    }
     if( opts.bytes ) {
         pb.resize( l_len );
-        void *lb = nullptr, *rb = nullptr;
-        rc = psx_dev_alloc( _device, (size_t)l_len * 128, &lb );
-        if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)r_len * 128, &rb );
-        if( rc == PSX_OK ) rc = psx_quantize_desc( _device, (const float*)_ori, l_len, (unsigned char*)lb );
-        if( rc == PSX_OK ) rc = psx_quantize_desc( _device, (const float*)other->_ori, r_len, (unsigned char*)rb );
-        if( rc == PSX_OK ) rc = psx_match_pairs_u8( _device, (const unsigned char*)lb, l_len, (const unsigned char*)rb, r_len, &po, pb.data(), l_len, &count );
-        psx_dev_free( _device, lb );
-        psx_dev_free( _device, rb );
+        if( rc == PSX_OK ) rc = psx_dev_alloc( device, (size_t)l_len * 128, &lb );
+        if( rc == PSX_OK ) rc = psx_dev_alloc( device, (size_t)r_len * 128, &rb );
+        if( rc == PSX_OK ) rc = psx_quantize_desc( device, (const float*)l_ori, l_len, (unsigned char*)lb );
+        if( rc == PSX_OK ) rc = psx_quantize_desc( device, (const float*)r_ori, r_len, (unsigned char*)rb );
+        if( rc == PSX_OK && guide == nullptr )
+            rc = psx_match_pairs_u8( device, (const unsigned char*)lb, l_len, (const unsigned char*)rb, r_len, &po, pb.data(), l_len, &count );
+        else if( rc == PSX_OK )
+            rc = psx_match_pairs_guided_u8( device, (const unsigned char*)lb, (const float*)lxy, l_len, (const unsigned char*)rb, (const float*)rxy, r_len,
+                                            &pg, &po, pb.data(), l_len, &count );
     } else {
         pf.resize( l_len );
-        rc = psx_match_pairs( _device, (const float*)_ori, l_len, (const float*)other->_ori, r_len, &po, pf.data(), l_len, &count );
+        if( rc == PSX_OK && guide == nullptr )
+            rc = psx_match_pairs( device, (const float*)l_ori, l_len, (const float*)r_ori, r_len, &po, pf.data(), l_len, &count );
+        else if( rc == PSX_OK )
+            rc = psx_match_pairs_guided( device, (const float*)l_ori, (const float*)lxy, l_len, (const float*)r_ori, (const float*)rxy, r_len,
+                                         &pg, &po, pf.data(), l_len, &count );
     }
+    psx_dev_free( device, lb );
+    psx_dev_free( device, rb );
+    psx_dev_free( device, lxy );
+    psx_dev_free( device, rxy );
     if( rc != PSX_OK ) {
         std::ostringstream ss;
-        ss << "FeaturesDev::matchPairs failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
+        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
         fatal( __FILE__, __LINE__, ss.str() );
     }
     std::vector<int> l_fem( l_len ), r_fem( r_len );
-    if( psx_dev_read( _device, l_fem.data(), _rev, (size_t)l_len * sizeof(int) ) != PSX_OK ||
-        psx_dev_read( other->_device, r_fem.data(), other->_rev, (size_t)r_len * sizeof(int) ) != PSX_OK )
-        fatal( __FILE__, __LINE__, "FeaturesDev::matchPairs: reading the reverse maps failed" );
+    if( psx_dev_read( device, l_fem.data(), l_rev, (size_t)l_len * sizeof(int) ) != PSX_OK ||
+        psx_dev_read( other_device, r_fem.data(), r_rev, (size_t)r_len * sizeof(int) ) != PSX_OK )
+        fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
     out.resize( count );
     for( int k = 0; k < count; k++ ) {
         Match& m = out[k];
@@ -554,6 +575,30 @@ std::vector<Match> FeaturesDev::matchPairs( FeaturesDev* other, const MatchOptio
         m.right_feature = r_fem[m.right_descriptor];
     }
     return out;
+}
+
+std::vector<Match> FeaturesDev::matchPairs( FeaturesDev* other, const MatchOptions& opts )
+{
+    if( other == nullptr ) fatal( __FILE__, __LINE__, "FeaturesDev::matchPairs: null argument" );
+    if( other->_device != _device ) {
+        std::ostringstream ss;
+        ss << "FeaturesDev::matchPairs: the two objects live on different devices (" << _device << " and " << other->_device << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    return match_pairs_impl( "FeaturesDev::matchPairs", _device, other->_device, _ext, _ori, _rev, getDescriptorCount(),
+                             other->_ext, other->_ori, other->_rev, other->getDescriptorCount(), nullptr, opts );
+}
+
+std::vector<Match> FeaturesDev::matchPairsGuided( FeaturesDev* other, const MatchGuide& guide, const MatchOptions& opts )
+{
+    if( other == nullptr ) fatal( __FILE__, __LINE__, "FeaturesDev::matchPairsGuided: null argument" );
+    if( other->_device != _device ) {
+        std::ostringstream ss;
+        ss << "FeaturesDev::matchPairsGuided: the two objects live on different devices (" << _device << " and " << other->_device << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    return match_pairs_impl( "FeaturesDev::matchPairsGuided", _device, other->_device, _ext, _ori, _rev, getDescriptorCount(),
+                             other->_ext, other->_ori, other->_rev, other->getDescriptorCount(), &guide, opts );
 }
 
 } // namespace popsift

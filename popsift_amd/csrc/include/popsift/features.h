@@ -126,7 +126,17 @@ struct MatchOptions
     bool  bytes  = false;   ///< quantise both sides (psx_quantize_desc) and run the exact integer matcher, as matchBytes
 };
 
-/// One correspondence of FeaturesDev::matchPairs
+/// What FeaturesDev::matchPairsGuided knows about where a match can lie: the guide of psx_match_pairs_guided
+/// (include/popsift_hip.h, "guided matching").  Positions are Feature::xpos / ypos, in input-image units.
+struct MatchGuide
+{
+    enum Kind { Homography = 1, Epipolar = 2 } kind;   ///< m = H: right point within tol of H * left point (identity H: a
+                                                       ///< search window); m = F: within tol of the line F * left point
+    float m[9];                                        ///< row major
+    float tol;                                         ///< pixels, finite and >= 0
+};
+
+/// One correspondence of FeaturesDev::matchPairs / matchPairsGuided
 struct Match
 {
     int   left_feature, right_feature;          ///< indices into the two feature arrays (via the reverse maps)
@@ -159,6 +169,11 @@ public:
     /// and, with MatchOptions::mutual, the cross-check, in ascending left descriptor; prints nothing.  Throws
     /// std::runtime_error for a null argument, objects on different devices, or a failing call.
     std::vector<Match> matchPairs( FeaturesDev* other, const MatchOptions& opts = MatchOptions() );
+    /// matchPairs with every descriptor's search restricted to the descriptors of the other side that the guide admits
+    /// (this = left, other = right; the cross-check runs on the same relation).  The positions are those of the
+    /// features the descriptors belong to (psx_desc_positions on each object's own arrays).  Throws as matchPairs,
+    /// and for an invalid guide.
+    std::vector<Match> matchPairsGuided( FeaturesDev* other, const MatchGuide& guide, const MatchOptions& opts = MatchOptions() );
 
     inline Feature*    getFeatures()    { return _ext; }
     inline Descriptor* getDescriptors() { return _ori; }
