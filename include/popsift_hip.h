@@ -398,8 +398,10 @@ int psx_desc_positions(int device, const psx_feature_dev* d_features, const int*
  * smallest under (distance, index) order among them.  Output layout and conventions are exactly those of psx_match /
  * psx_match_u8: float distances from the reference's operation tree, bit for bit, byte distances exact integers; a
  * missing neighbour is +inf / INT_MAX with index 0 -- which now also arises with zero or one admissible right
- * descriptor; accept = (d1 / d2 < 0.8f).  d_left_xy / d_right_xy: DEVICE pointers to l_len / r_len (x, y) pairs, 8-byte
- * aligned (psx_desc_positions writes them).  Additionally PSX_ERR_INVALID for an invalid guide or a NULL position array
+ * descriptor; accept = (d1 / d2 < 0.8f).  An admissible right descriptor whose distance is NaN (a NaN value in either
+ * row) or overflows to +inf is never a neighbour: the reference's scan keeps a candidate only on a strict '<' against
+ * +inf, which neither passes, so such a row is skipped as if it were inadmissible.
+ * d_left_xy / d_right_xy: DEVICE pointers to l_len / r_len (x, y) pairs, 8-byte aligned (psx_desc_positions writes them).  Additionally PSX_ERR_INVALID for an invalid guide or a NULL position array
  * with a non-zero length.  Scratch as psx_match (psx_match_release).  Synchronous. */
 int psx_match_guided(int device, const float* d_left, const float* d_left_xy, int l_len,
                      const float* d_right, const float* d_right_xy, int r_len, const psx_guide* guide,

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from popsift_amd.synth import synth
+from tests.rule_edge_cases import boundary_records
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -109,29 +110,7 @@ def test_placement_equals_the_restatement(capi, kw, size):
     itself and its two float neighbours (and the two ends of the accepted sigma range with theirs)."""
     w, h = size
     cfg = capi.default_config(**kw)
-    rng = np.random.default_rng(11)
-    b = capi.keypoint_bounds(cfg)
-    up = int(cfg.upscale_factor)
-    L = cfg.levels + 3
-    ends = [np.float32(cfg.sigma), np.float32(np.float64(np.float32(cfg.sigma)) * 2.0 ** ((L - 1) / cfg.levels))]
-    sig = []
-    for o in range(-1, cfg.octaves + 1):
-        for v in list(b) + ends:
-            v = np.float32(v) * np.float32(2.0 ** (o - up))
-            sig += [np.nextafter(v, np.float32(0)), v, np.nextafter(v, np.float32(np.inf))]
-    sig = np.array(sig + list(np.exp2(rng.uniform(-2, 8, 3000))), np.float32)
-    kps = np.zeros(len(sig), capi.KEYPOINT_DTYPE)
-    kps["sigma"] = sig
-    kps["xpos"] = rng.uniform(-2, w + 2, len(sig)).astype(np.float32)
-    kps["ypos"] = rng.uniform(-2, h + 2, len(sig)).astype(np.float32)
-    kps["octave"] = capi.KP_AUTO
-    edge = rng.integers(0, len(sig), 60)                                  # positions on and next to the borders
-    kps["xpos"][edge[:20]] = 0.0
-    kps["xpos"][edge[20:40]] = np.float32(w - 1)
-    kps["ypos"][edge[40:]] = np.nextafter(np.float32(h - 1), np.float32(np.inf))
-    explicit = kps.copy()
-    explicit["octave"] = rng.integers(-1, cfg.octaves + 1, len(sig))     # -1 is PSX_KP_AUTO: both kinds mixed
-    explicit["lpos"] = rng.integers(-1, L + 1, len(sig))
+    kps, explicit = boundary_records(capi, cfg, w, h)                    # tests/rule_edge_cases.py: the GPU tests use them too
     for recs in (kps, explicit):
         o_lib, l_lib = capi.place_keypoints(cfg, w, h, recs)
         o_np, l_np = restate(capi, cfg, w, h, recs, cfg.octaves)

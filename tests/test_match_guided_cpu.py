@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from tests import guided_cases as gc
+from tests import rule_edge_cases as rc
 from tests.match_pairs_cases import INT_MAX, dist_as_int
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,21 +45,8 @@ def test_guide_allows_equals_the_restatement(capi, nl, nr, seed, guide):
 
 
 def test_guide_allows_on_edge_inputs(capi):
-    nan, inf = np.float32(np.nan), np.float32(np.inf)
-    rng = np.random.default_rng(5)
-    base = rng.uniform(-50, 50, (40, 2)).astype(np.float32)
-    special = np.array([[nan, 1], [1, nan], [inf, 1], [1, -inf], [inf, inf], [0, 0], [1e30, 1e30], [-1e38, 3e38], [1e-40, -1e-40]], np.float32)
-    lxy = np.concatenate([base[:20], special])
-    rxy = np.concatenate([base[10:], special, base[:5]])                  # some points on both sides: distance 0
-    guides = []
-    for tol in (0.0, 2.0, 1e30, 3e38):                                     # 1e30 and up: the squared tolerance overflows to +inf
-        guides += [(gc.HOMOGRAPHY, gc.IDENTITY, tol), (gc.HOMOGRAPHY, gc.H_ASYM, tol), (gc.EPIPOLAR, gc.F_EPI, tol)]
-    guides += [(gc.HOMOGRAPHY, [1, 0, 0, 0, 1, 0, 0, 0, -1], 2.0),        # c < 0 everywhere
-               (gc.HOMOGRAPHY, [1, 0, 0, 0, 1, 0, 0, 0, 0], 2.0),         # c = 0 everywhere
-               (gc.HOMOGRAPHY, [1, 0, 0, 0, 1, 0, 0.05, 0, 1], 2.0),      # c changes sign over the points
-               (gc.EPIPOLAR, [0, 0, 0, 0, 0, 0, 0, 0, 1], 2.0),           # a degenerate line a = b = 0, c != 0: nothing
-               (gc.EPIPOLAR, [0] * 9, 2.0),                               # a = b = c = 0: 0 <= 0, everything without a NaN
-               (gc.EPIPOLAR, [0, 0, 0, 0, 0, 0, 1, 0, 0], 0.0)]           # degenerate, c = xl
+    lxy, rxy = rc.edge_points()                                           # the lists live in tests/rule_edge_cases.py: the GPU tests use them too
+    guides = rc.edge_guides()
     seen = set()
     for kind, m, tol in guides:
         want = gc.restate(kind, m, tol, lxy, rxy)
