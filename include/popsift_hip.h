@@ -428,6 +428,63 @@ int psx_match_pairs_guided_u8_dev(int device, const unsigned char* d_left, const
                                   const unsigned char* d_right, const float* d_right_xy, int r_len, const psx_guide* guide,
                                   const psx_match_opts* opts, psx_match_pair_u8* d_pairs, int capacity, int* count);
 
+/* ---- geometric verification ---------------------------------------------------------------
+ * The step between a match and a guided re-match: a homography estimated from the pair list by RANSAC on the device
+ * (OpenCV's findHomography(RANSAC), the model AliceVision's guidedMatching starts from; the reference has no
+ * counterpart).  match -> verify -> re-match guided by the verified model, without the pairs leaving HBM.  Every step
+ * is a stated rule, shared by host and device (csrc/hip/ransac_rule.h states it operation by operation;
+ * INTEGRATION.md, "Geometric verification", in words), so the device result equals psx_ransac_homography_ref bit for bit:
+ *   1. samples:  hypothesis h draws four distinct pair indices from an integer hash of (seed, h);
+ *   2. fit:      the four correspondences (and, for the refit, any n >= 4) give a 3 x 3 matrix by normalised DLT --
+ *                normal equations, LDL^T without pivoting, in double, rounded once to float32; a degenerate sample gives
+ *                NaN / inf entries, there is no special case;
+ *   3. score:    count[h] = number of pairs that pass the HOMOGRAPHY rule of guided matching (psx_guide) under model h
+ *                and opts->tol; a model with a non-finite entry scores 0;
+ *   4. select:   the largest count, ties to the lowest h;
+ *   5. refit (PSX_RANSAC_REFIT), one round: fit the winner's inliers (when there are at least 4) in pair order; that
+ *                model is kept iff it is finite and its count is >= the winner's;
+ *   6. inliers:  the input records that pass the rule under the kept model, compacted stably in input order.
+ * Pair records are 16 bytes (psx_match_pair or psx_match_pair_u8: only left and right are read, the record is copied
+ * whole); pair p is the correspondence left_xy[pairs[p].left] -> right_xy[pairs[p].right], positions in INPUT-IMAGE units
+ * as psx_desc_positions writes them.  The result's m is a valid psx_guide matrix for PSX_GUIDE_HOMOGRAPHY (left -> right).
+ * result->best = winning hypothesis, sample_inliers = its count, inliers = the count under the kept model (== *count),
+ * refit_kept = 1 when the refit model replaced the sample model.  n < 4, or a kept model with a non-finite entry (every
+ * sample degenerate), gives PSX_OK with best = -1, a zero matrix, *count = 0 and no record written.
+ * *count, capacity and the "how many?" form are as in psx_match_pairs.  PSX_ERR_INVALID, with nothing touched: opts, result
+ * or count NULL, a tol that is NaN, negative or infinite, hypotheses outside [1, 65536], unknown flag bits, negative
+ * sizes, NULL data with a non-zero size, a pair index outside its position array.  A fundamental-matrix estimator is
+ * not part of the library. */
+#define PSX_RANSAC_REFIT 1
+typedef struct psx_ransac_opts   { float tol; int hypotheses; unsigned seed; int flags; } psx_ransac_opts;
+typedef struct psx_ransac_result { float m[9]; int best; int sample_inliers; int inliers; int refit_kept; } psx_ransac_result;
+
+/* *o = {2.0f, 1024, 0, PSX_RANSAC_REFIT} */
+int psx_ransac_opts_default(psx_ransac_opts* o);
+
+/* Host only, no device and no context (as psx_pairs_join). */
+/* step 1: idx[4 * i .. 4 * i + 3] = the four pair indices of hypothesis first + i, in draw order, for i in [0, count);
+ * PSX_ERR_INVALID for n < 4, first < 0, count < 0, first + count > 65536 or a NULL idx with count > 0 */
+int psx_ransac_samples(unsigned seed, int first, int count, int n, int* idx);
+/* step 2 on n >= 4 correspondences left_xy[i] -> right_xy[i] ((x, y) pairs), in the given order; m: 9 floats, row major */
+int psx_homography_fit(const float* left_xy, const float* right_xy, int n, float* m);
+/* the whole rule on host arrays: left_xy / right_xy hold nl / nr positions; models (N x 9 floats) and counts (N ints)
+ * receive every hypothesis' model and count, either may be NULL */
+int psx_ransac_homography_ref(const void* pairs, int n, const float* left_xy, int nl, const float* right_xy, int nr,
+                              const psx_ransac_opts* opts, psx_ransac_result* result, void* inliers, int capacity, int* count,
+                              float* models, int* counts);
+
+/* On the device.  d_left_xy / d_right_xy: DEVICE pointers to l_len / r_len (x, y) pairs, 8-byte aligned.  The host form
+ * uploads n records from host memory and returns the inliers to a host buffer; the _dev form reads the records from and
+ * writes the inliers to DEVICE memory (16-byte aligned; d_inliers must not overlap d_pairs), so the list psx_match_pairs*_dev left
+ * never leaves HBM.  The result struct always comes back to the host; host_models (N x 9 floats) and host_counts (N
+ * ints) expose the per-hypothesis layers, either may be NULL.  Scratch as psx_match (psx_match_release).  Synchronous. */
+int psx_ransac_homography(int device, const void* host_pairs, int n, const float* d_left_xy, int l_len,
+                          const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                          void* host_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_homography_dev(int device, const void* d_pairs, int n, const float* d_left_xy, int l_len,
+                              const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                              void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
+
 /* ---- caller-supplied keypoints ------------------------------------------------------------
  * Describing points the caller brings along instead of the ones the DoG detector finds (what OpenCV calls
  * useProvidedKeypoints and VLFeat calls frames; the reference has no counterpart).  A record carries what a

@@ -99,6 +99,8 @@ SYMBOLS = [
     "psx_pairs_join", "psx_pairs_join_u8",
     "psx_guide_allows", "psx_desc_positions", "psx_match_guided", "psx_match_guided_u8",
     "psx_match_pairs_guided", "psx_match_pairs_guided_u8", "psx_match_pairs_guided_dev", "psx_match_pairs_guided_u8_dev",
+    "psx_ransac_opts_default", "psx_ransac_samples", "psx_homography_fit", "psx_ransac_homography_ref",
+    "psx_ransac_homography", "psx_ransac_homography_dev",
 ]
 
 PAIRS_MUTUAL = 1     # PSX_PAIRS_MUTUAL
@@ -134,6 +136,27 @@ class Guide(C.Structure):
     @classmethod
     def epipolar(cls, F, tol):
         return cls.make(GUIDE_EPIPOLAR, F, tol)
+
+
+RANSAC_REFIT = 1         # PSX_RANSAC_REFIT
+
+
+class RansacOpts(C.Structure):
+    """psx_ransac_opts: inlier tolerance in pixels, number of hypotheses (1..65536), seed, flags (RANSAC_REFIT)."""
+    _fields_ = [("tol", C.c_float), ("hypotheses", C.c_int), ("seed", C.c_uint), ("flags", C.c_int)]
+
+
+class RansacResult(C.Structure):
+    """psx_ransac_result: the kept model (row major, left -> right), the winning hypothesis (-1: no model), its inlier
+    count, the inlier count under the kept model, and whether the refit replaced the sample model."""
+    _fields_ = [("m", C.c_float * 9), ("best", C.c_int), ("sample_inliers", C.c_int), ("inliers", C.c_int), ("refit_kept", C.c_int)]
+
+    def matrix(self):
+        return np.array(list(self.m), np.float32)
+
+    def guide(self, tol):
+        """the kept model as the psx_guide of a guided re-match"""
+        return Guide.homography(self.matrix(), tol)
 
 
 DESCFMT_F32 = 0      # PSX_DESCFMT_F32
@@ -210,6 +233,14 @@ def lib():
             getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(Guide), vp, vp]
         for n in ("psx_match_pairs_guided", "psx_match_pairs_guided_u8", "psx_match_pairs_guided_dev", "psx_match_pairs_guided_u8_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(Guide), C.POINTER(MatchOpts), vp, C.c_int, ip]
+        L.psx_ransac_opts_default.argtypes = [C.POINTER(RansacOpts)]
+        L.psx_ransac_samples.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_int, vp]
+        L.psx_homography_fit.argtypes = [vp, vp, C.c_int, vp]
+        L.psx_ransac_homography_ref.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(RansacOpts), C.POINTER(RansacResult),
+                                                vp, C.c_int, ip, vp, vp]
+        for n in ("psx_ransac_homography", "psx_ransac_homography_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(RansacOpts), C.POINTER(RansacResult),
+                                      vp, C.c_int, ip, vp, vp]
         _LIB = L
     return _LIB
 
@@ -576,6 +607,104 @@ def match_pairs_guided_dev(left_ptr, left_xy_ptr, l_len, right_ptr, right_xy_ptr
     return n.value
 
 
+def ransac_opts(tol=2.0, hypotheses=1024, seed=0, refit=True):
+    """psx_ransac_opts from keywords"""
+    return RansacOpts(float(np.float32(tol)), int(hypotheses), int(seed) & 0xffffffff, RANSAC_REFIT if refit else 0)
+
+
+def ransac_samples(seed, first, count, n):
+    """psx_ransac_samples: the (count, 4) int32 pair indices of hypotheses first .. first + count - 1 among n pairs.  No device."""
+    out = np.zeros((count, 4), np.int32)
+    rc = lib().psx_ransac_samples(int(seed) & 0xffffffff, first, count, n, out.ctypes.data_as(C.c_void_p) if count else None)
+    if rc != 0:
+        raise PopSiftError("psx_ransac_samples failed (%d)" % rc)
+    return out
+
+
+def homography_fit(left_xy, right_xy):
+    """psx_homography_fit: the 9 float32 entries (row major) of the model fitted to left_xy[i] -> right_xy[i], in the given
+    order; a degenerate input gives non-finite entries.  No device."""
+    lx, rx = _xy(left_xy), _xy(right_xy)
+    if len(lx) != len(rx):
+        raise ValueError("one right position per left position")
+    m = np.zeros(9, np.float32)
+    rc = lib().psx_homography_fit(lx.ctypes.data_as(C.c_void_p), rx.ctypes.data_as(C.c_void_p), len(lx), m.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PopSiftError("psx_homography_fit failed (%d)" % rc)
+    return m
+
+
+def _pair_records(pairs):
+    """16-byte pair records (PAIR_DTYPE or PAIR_U8_DTYPE), C-contiguous"""
+    pairs = np.ascontiguousarray(pairs).reshape(-1)
+    if pairs.dtype.itemsize != 16:
+        raise TypeError("pairs must be PAIR_DTYPE or PAIR_U8_DTYPE records")
+    return pairs
+
+
+def _ransac_call(fn, name, pairs_ptr, n, dtype, plx, nl, prx, nr, opts, capacity, layers, out_ptr=None):
+    """One RANSAC call.  out_ptr None: the inliers come back in a host array.  Returns a dict: result (RansacResult), count,
+    inliers (host forms), and with layers models (N, 9) and counts (N)."""
+    cap = n if capacity is None else capacity
+    N = max(int(opts.hypotheses), 0)
+    res, cnt = RansacResult(), C.c_int(-1)
+    out = np.zeros((cap,), dtype) if out_ptr is None else None
+    models = np.zeros((N, 9), np.float32) if layers else None
+    counts = np.zeros((N,), np.int32) if layers else None
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    po = ptr(out) if out_ptr is None else (C.c_void_p(out_ptr) if cap else None)
+    rc = fn(pairs_ptr, n, plx, nl, prx, nr, C.byref(opts), C.byref(res), po, cap, C.byref(cnt), ptr(models), ptr(counts))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    got = dict(result=res, count=cnt.value)
+    if out is not None:
+        got["inliers"] = out[:min(cnt.value, cap)]
+    if layers:
+        got["models"], got["counts"] = models, counts
+    return got
+
+
+def ransac_homography_ref(pairs, left_xy, right_xy, opts=None, capacity=None, layers=False):
+    """psx_ransac_homography_ref: the whole rule on host arrays, no device.  pairs: PAIR_DTYPE / PAIR_U8_DTYPE records;
+    left_xy / right_xy: (nl, 2) / (nr, 2) positions.  Returns a dict: result, count, inliers, and with layers the
+    per-hypothesis models and counts."""
+    L = lib()
+    pairs, lx, rx = _pair_records(pairs), _xy(left_xy), _xy(right_xy)
+    opts = opts or ransac_opts()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    return _ransac_call(L.psx_ransac_homography_ref, "psx_ransac_homography_ref", ptr(pairs), len(pairs), pairs.dtype, ptr(lx), len(lx),
+                        ptr(rx), len(rx), opts, capacity, layers)
+
+
+def ransac_homography(pairs, left_xy, right_xy, opts=None, device=0, capacity=None, layers=False):
+    """psx_ransac_homography on host arrays (the positions go through device buffers): as ransac_homography_ref, on the
+    device."""
+    L = lib()
+    pairs, lx, rx = _pair_records(pairs), _xy(left_xy), _xy(right_xy)
+    opts = opts or ransac_opts()
+    bufs = []
+    try:
+        plx, prx = _to_device(L, device, [lx, rx], bufs)
+        fn = lambda *a: L.psx_ransac_homography(device, *a)
+        return _ransac_call(fn, "psx_ransac_homography", pairs.ctypes.data_as(C.c_void_p) if pairs.size else None, len(pairs), pairs.dtype,
+                            plx, len(lx), prx, len(rx), opts, capacity, layers)
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def ransac_homography_dev(pairs_ptr, n, left_xy_ptr, l_len, right_xy_ptr, r_len, out_ptr, capacity, opts=None, device=0, layers=False):
+    """psx_ransac_homography_dev on DEVICE pointers: the records at pairs_ptr (e.g. what match_pairs_dev left) are read and
+    the inlier records written in device memory (16-byte aligned, `capacity` records).  Returns a dict: result, count, and
+    with layers the per-hypothesis models and counts."""
+    L = lib()
+    opts = opts or ransac_opts()
+    vp = lambda p: C.c_void_p(p) if p else None
+    fn = lambda *a: L.psx_ransac_homography_dev(device, *a)
+    return _ransac_call(fn, "psx_ransac_homography_dev", vp(pairs_ptr), n, None, vp(left_xy_ptr), l_len, vp(right_xy_ptr), r_len, opts,
+                        capacity, layers, out_ptr=out_ptr or 0)
+
+
 class DeviceDescriptors:
     """Descriptor sets resident on the device (what FeaturesDev holds, popsift.cpp:346-383): upload once, match many times."""
 
@@ -627,6 +756,16 @@ class DeviceDescriptors:
         fn = _guided_fn(lib().psx_match_pairs_guided, self.xy_ptr, right.xy_ptr, guide)
         got = _pairs_call(fn, "psx_match_pairs_guided", self.device, self.ptr, self.n, right.ptr, right.n, ratio, mutual, PAIR_DTYPE, capacity)
         return got[0] if capacity is None else got
+
+    def ransac_homography(self, right, pairs, opts=None, capacity=None, layers=False):
+        """psx_ransac_homography(pairs of self as left and right: DeviceDescriptors, both built with positions): the dict
+        of capi.ransac_homography"""
+        if (self.n and not self.xy_ptr) or (right.n and not right.xy_ptr):
+            raise ValueError("both sides need positions (DeviceDescriptors(arr, xy=...))")
+        pairs = _pair_records(pairs)
+        fn = lambda *a: lib().psx_ransac_homography(self.device, *a)
+        return _ransac_call(fn, "psx_ransac_homography", pairs.ctypes.data_as(C.c_void_p) if pairs.size else None, len(pairs), pairs.dtype,
+                            self.xy_ptr, self.n, right.xy_ptr, right.n, opts or ransac_opts(), capacity, layers)
 
     def close(self):
         if self.ptr:

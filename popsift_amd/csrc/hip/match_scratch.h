@@ -9,8 +9,10 @@
 struct MatchScratch {
     // 0-9: psx_match, 10-12: psx_match_u8; the pair search: 13 the backward direction's results of psx_match_pairs,
     // 14 those of psx_match_pairs_u8, 15 the join's per-workgroup totals; guided matching (match_guided.hip): 16 the forward
-    // direction's results, 17 the backward direction's, 18 the left side's lines for the backward direction
-    static constexpr int NBUF = 19;
+    // direction's results, 17 the backward direction's, 18 the left side's lines for the backward direction; the homography
+    // RANSAC (ransac.hip): 19 the uploaded pair records, 20 the packed correspondences, 21 the hypotheses' models, 22 their
+    // counts, 23 the state block, 24 the compaction's per-workgroup totals
+    static constexpr int NBUF = 25;
     int device = -1;
     hipStream_t stream = nullptr;
     void* buf[NBUF] = {};

@@ -2,7 +2,9 @@
 // extracts two images into FeaturesDev objects and prints one accept / reject line per left descriptor
 // (FeaturesDev::match, features.cu:227-304).  Not in the reference tool: --pairs FILE writes the matches as data
 // (FeaturesDev::matchPairs) instead of the accept / reject lines; --ratio and --mutual refine it; --homography or
-// --fundamental with --guide-tol restrict the search to the pairs a guide admits (FeaturesDev::matchPairsGuided).
+// --fundamental with --guide-tol restrict the search to the pairs a guide admits (FeaturesDev::matchPairsGuided);
+// --verify-homography TOL estimates a homography from the pairs (FeaturesDev::estimateHomography) and writes its inliers,
+// --rematch then writes the list guided by that model instead.
 #include "options.h"
 #include "pgmread.h"
 
@@ -29,6 +31,8 @@ static bool  have_ratio = false, mutual = false;
 static float pair_ratio = 0.8f;
 static bool  have_h = false, have_f = false, have_tol = false;
 static popsift::MatchGuide guide;
+static bool  have_verify = false, have_ransac_opt = false, rematch = false;
+static popsift::RansacOptions ransac;
 
 // "m0,...,m8": nine numbers, row major
 static void parse_matrix( const string& opt, const string& s, float* m )
@@ -63,6 +67,7 @@ int main( int argc, char** argv )
     string lFile, rFile;
     cout << "PopSift version: " << POPSIFT_VERSION_STRING << endl;
 
+    ransac.refit = false;                   // the tool refits on request (--ransac-refit)
     app::Options all;
     bool help = false;
     all.flag( "help", 'h', "Print usage", [&]() { help = true; } );
@@ -88,6 +93,16 @@ int main( int argc, char** argv )
              "the line F * left point (needs --pairs and --guide-tol)", [&]( const string& s ) { parse_matrix( "fundamental", s, guide.m ); have_f = true; } );
     all.add( "guide-tol", 0, true, "Guided matching: the tolerance in pixels (needs --homography or --fundamental)",
              [&]( const string& s ) { guide.tol = app::to_float( s ); have_tol = true; } );
+    all.add( "verify-homography", 0, true, "Geometric verification: estimate a homography from the pairs by RANSAC with this inlier "
+             "tolerance in pixels, print it and write only its inliers (needs --pairs)",
+             [&]( const string& s ) { ransac.tol = app::to_float( s ); have_verify = true; } );
+    all.add( "ransac-hypotheses", 0, true, "Geometric verification: the number of hypotheses, 1 to 65536. Default is 1024",
+             [&]( const string& s ) { ransac.hypotheses = (int)app::to_float( s ); have_ransac_opt = true; } );
+    all.add( "ransac-seed", 0, true, "Geometric verification: the seed of the samples. Default is 0",
+             [&]( const string& s ) { ransac.seed = (unsigned)std::strtoul( s.c_str(), nullptr, 10 ); have_ransac_opt = true; } );
+    all.flag( "ransac-refit", 0, "Geometric verification: refit the best hypothesis over its inliers", [&]() { ransac.refit = true; have_ransac_opt = true; } );
+    all.flag( "rematch", 0, "After --verify-homography: match again, guided by the estimated homography and the same tolerance, and "
+              "write that list instead", [&]() { rematch = true; } );
     all.flag( "pgmread-loading", 0, "Use the PGM/PPM loader (the only loader of this build)", []() {} );
     try {
         all.parse( argc, argv );
@@ -101,6 +116,12 @@ int main( int argc, char** argv )
         if( ( have_h || have_f ) && !have_tol ) throw runtime_error( "the options '--homography' and '--fundamental' need '--guide-tol'" );
         if( have_tol && !( guide.tol >= 0.0f && std::isfinite( guide.tol ) ) ) throw runtime_error( "the guide tolerance must be finite and not negative" );
         guide.kind = have_f ? popsift::MatchGuide::Epipolar : popsift::MatchGuide::Homography;
+        if( have_verify && pairs_file.empty() ) throw runtime_error( "the option '--verify-homography' needs '--pairs'" );
+        if( have_ransac_opt && !have_verify ) throw runtime_error( "the options '--ransac-hypotheses', '--ransac-seed' and '--ransac-refit' need '--verify-homography'" );
+        if( rematch && !have_verify ) throw runtime_error( "the option '--rematch' needs '--verify-homography'" );
+        if( have_verify && ( have_h || have_f ) ) throw runtime_error( "the option '--verify-homography' cannot be combined with '--homography' or '--fundamental'" );
+        if( have_verify && !( ransac.tol >= 0.0f && std::isfinite( ransac.tol ) ) ) throw runtime_error( "the verification tolerance must be finite and not negative" );
+        if( have_verify && ( ransac.hypotheses < 1 || ransac.hypotheses > 65536 ) ) throw runtime_error( "the number of hypotheses must lie in 1 .. 65536" );
     } catch( const std::exception& e ) {
         cerr << "Error: " << e.what() << endl << endl << "Usage:" << endl << endl;
         all.usage( cerr );
@@ -128,8 +149,16 @@ int main( int argc, char** argv )
         if( !pairs_file.empty() ) {
             popsift::MatchOptions mo;
             mo.ratio = pair_ratio; mo.mutual = mutual; mo.bytes = uchar_desc;
-            const std::vector<popsift::Match> mm = ( have_h || have_f ) ? lFeatures->matchPairsGuided( rFeatures, guide, mo )
-                                                                        : lFeatures->matchPairs( rFeatures, mo );
+            std::vector<popsift::Match> mm = ( have_h || have_f ) ? lFeatures->matchPairsGuided( rFeatures, guide, mo )
+                                                                  : lFeatures->matchPairs( rFeatures, mo );
+            if( have_verify ) {
+                const popsift::HomographyEstimate est = lFeatures->estimateHomography( rFeatures, mm, ransac );
+                printf( "Homography:" );
+                for( int k = 0; k < 9; k++ ) printf( " %.9g", est.guide.m[k] );
+                printf( "\nHomography inliers: %d of %d\n", (int)est.inliers.size(), (int)mm.size() );
+                if( est.best < 0 ) throw runtime_error( "no homography could be estimated from the pairs" );
+                mm = rematch ? lFeatures->matchPairsGuided( rFeatures, est.guide, mo ) : est.inliers;
+            }
             FILE* f = fopen( pairs_file.c_str(), "w" );
             if( f == nullptr ) throw runtime_error( "cannot write " + pairs_file );
             for( const popsift::Match& m : mm )

@@ -601,4 +601,53 @@ std::vector<Match> FeaturesDev::matchPairsGuided( FeaturesDev* other, const Matc
                              other->_ext, other->_ori, other->_rev, other->getDescriptorCount(), &guide, opts );
 }
 
+HomographyEstimate FeaturesDev::estimateHomography( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts )
+{
+    const char* who = "FeaturesDev::estimateHomography";
+    if( other == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
+    if( other->_device != _device ) {
+        std::ostringstream ss;
+        ss << who << ": the two objects live on different devices (" << _device << " and " << other->_device << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    // refused here, before any device is touched: what psx_ransac_homography refuses
+    if( !( std::isfinite( opts.tol ) && opts.tol >= 0.0f ) || opts.hypotheses < 1 || opts.hypotheses > 65536 )
+        fatal( __FILE__, __LINE__, std::string( who ) + ": invalid options (finite tolerance >= 0, 1 to 65536 hypotheses)" );
+    HomographyEstimate est;
+    est.guide.kind = MatchGuide::Homography;
+    for( int k = 0; k < 9; k++ ) est.guide.m[k] = 0.0f;
+    est.guide.tol = opts.tol;
+    est.best = -1; est.sample_inliers = 0; est.refit_kept = false;
+    const int n = (int)matches.size();
+    const int l_len = getDescriptorCount(), r_len = other->getDescriptorCount();
+    if( n < 4 ) return est;
+    // the record is copied whole: its distance slots carry the index of the match
+    std::vector<psx_match_pair_u8> rec( n ), inl( n );
+    for( int k = 0; k < n; k++ ) { rec[k].left = matches[k].left_descriptor; rec[k].right = matches[k].right_descriptor; rec[k].d1 = k; rec[k].d2 = 0; }
+    psx_ransac_opts po;
+    po.tol = opts.tol; po.hypotheses = opts.hypotheses; po.seed = opts.seed; po.flags = opts.refit ? PSX_RANSAC_REFIT : 0;
+    psx_ransac_result res;
+    int count = 0;
+    void *lxy = nullptr, *rxy = nullptr;
+    int rc = ( l_len > 0 && r_len > 0 ) ? PSX_OK : PSX_ERR_INVALID;
+    if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)l_len * 2 * sizeof(float), &lxy );
+    if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)r_len * 2 * sizeof(float), &rxy );
+    if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)_ext, _rev, l_len, (float*)lxy );
+    if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)other->_ext, other->_rev, r_len, (float*)rxy );
+    if( rc == PSX_OK ) rc = psx_ransac_homography( _device, rec.data(), n, (const float*)lxy, l_len, (const float*)rxy, r_len, &po, &res,
+                                                   inl.data(), n, &count, nullptr, nullptr );
+    psx_dev_free( _device, lxy );
+    psx_dev_free( _device, rxy );
+    if( rc != PSX_OK ) {
+        std::ostringstream ss;
+        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options or a descriptor index outside its object" : "" ) << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    for( int k = 0; k < 9; k++ ) est.guide.m[k] = res.m[k];
+    est.best = res.best; est.sample_inliers = res.sample_inliers; est.refit_kept = res.refit_kept != 0;
+    est.inliers.reserve( count );
+    for( int k = 0; k < count; k++ ) est.inliers.push_back( matches[inl[k].d1] );
+    return est;
+}
+
 } // namespace popsift

@@ -144,6 +144,27 @@ struct Match
     float distance, second_distance;            ///< squared; byte distances converted (exact), +inf: no second neighbour
 };
 
+/// How FeaturesDev::estimateHomography runs: the options of psx_ransac_homography (include/popsift_hip.h, "geometric
+/// verification")
+struct RansacOptions
+{
+    float    tol        = 2.0f;   ///< inlier tolerance in pixels, finite and >= 0
+    int      hypotheses = 1024;   ///< 1 .. 65536
+    unsigned seed       = 0;      ///< the same seed on the same matches gives the same result, bit for bit
+    bool     refit      = true;   ///< refit the winner over its inliers (kept iff it does not lose inliers)
+};
+
+/// What FeaturesDev::estimateHomography returns
+struct HomographyEstimate
+{
+    MatchGuide         guide;            ///< Homography, the estimated matrix (this -> other), tol = RansacOptions::tol:
+                                         ///< ready for matchPairsGuided
+    std::vector<Match> inliers;          ///< the matches that pass under the matrix, in input order
+    int                best;             ///< the winning hypothesis; -1: no model (fewer than 4 matches, or all degenerate)
+    int                sample_inliers;   ///< inliers of the winning 4-point model
+    bool               refit_kept;       ///< the refit model replaced it
+};
+
 /// Device-resident result (MatchingMode): arrays live in HBM of the extracting device.
 class FeaturesDev : public FeaturesBase
 {
@@ -174,6 +195,10 @@ public:
     /// features the descriptors belong to (psx_desc_positions on each object's own arrays).  Throws as matchPairs,
     /// and for an invalid guide.
     std::vector<Match> matchPairsGuided( FeaturesDev* other, const MatchGuide& guide, const MatchOptions& opts = MatchOptions() );
+    /// geometric verification: a homography (this = left -> other = right) estimated from `matches` (what matchPairs
+    /// returned for the same two objects) by RANSAC on the device, psx_ransac_homography.  Throws as matchPairs, and for
+    /// invalid options or a descriptor index outside its object.
+    HomographyEstimate estimateHomography( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts = RansacOptions() );
 
     inline Feature*    getFeatures()    { return _ext; }
     inline Descriptor* getDescriptors() { return _ori; }
