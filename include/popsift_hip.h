@@ -452,8 +452,7 @@ int psx_match_pairs_guided_u8_dev(int device, const unsigned char* d_left, const
  * sample degenerate), gives PSX_OK with best = -1, a zero matrix, *count = 0 and no record written.
  * *count, capacity and the "how many?" form are as in psx_match_pairs.  PSX_ERR_INVALID, with nothing touched: opts, result
  * or count NULL, a tol that is NaN, negative or infinite, hypotheses outside [1, 65536], unknown flag bits, negative
- * sizes, NULL data with a non-zero size, a pair index outside its position array.  A fundamental-matrix estimator is
- * not part of the library. */
+ * sizes, NULL data with a non-zero size, a pair index outside its position array. */
 #define PSX_RANSAC_REFIT 1
 typedef struct psx_ransac_opts   { float tol; int hypotheses; unsigned seed; int flags; } psx_ransac_opts;
 typedef struct psx_ransac_result { float m[9]; int best; int sample_inliers; int inliers; int refit_kept; } psx_ransac_result;
@@ -484,6 +483,35 @@ int psx_ransac_homography(int device, const void* host_pairs, int n, const float
 int psx_ransac_homography_dev(int device, const void* d_pairs, int n, const float* d_left_xy, int l_len,
                               const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
                               void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
+
+/* The same for the general two-view case, a scene with depth: a FUNDAMENTAL MATRIX (OpenCV's findFundamentalMat(RANSAC)),
+ * the producer of guided matching's other guide.  The result's m is a valid psx_guide matrix for PSX_GUIDE_EPIPOLAR
+ * (left -> right: (xr yr 1) m (xl yl 1)^T = 0), ready for psx_match_pairs_guided*.  The rule has the same six steps, stated
+ * operation by operation in csrc/hip/fundamental_rule.h ("Geometric verification", in words), and the
+ * device result equals psx_ransac_fundamental_ref bit for bit:
+ *   1. samples:  EIGHT distinct pair indices per hypothesis, by the same hash;
+ *   2. fit:      the normalised 8-point algorithm for n >= 8 correspondences -- the 9 x 9 moment matrix, LDL^T with
+ *                diagonal pivoting (the entry fixed at 1 is whichever the pivoting leaves over), four Newton steps on the
+ *                determinant for rank 2 -- in double, rounded once to float32; no special case for a degenerate sample;
+ *   3. score:    the EPIPOLAR rule of guided matching under opts->tol (one-sided: what is verified is what will guide); a
+ *                model with a non-finite entry, or with all nine entries zero, scores 0;
+ *   4 - 6.       as above with 8 in place of 4; the refit model is kept iff it may score and its count is >= the winner's.
+ * n < 8, or a kept model that may not score, gives PSX_OK with best = -1, a zero matrix, *count = 0.  Arguments, opts,
+ * result, capacity and errors are those of the homography calls. */
+/* Host only.  step 1 with k draws per hypothesis, k = 4 (== psx_ransac_samples) or 8: idx[k * i ..]; PSX_ERR_INVALID for
+ * another k, n < k, and as psx_ransac_samples */
+int psx_ransac_samples_k(unsigned seed, int first, int count, int n, int k, int* idx);
+/* step 2 on n >= 8 correspondences left_xy[i] -> right_xy[i], in the given order; m: 9 floats, row major */
+int psx_fundamental_fit(const float* left_xy, const float* right_xy, int n, float* m);
+int psx_ransac_fundamental_ref(const void* pairs, int n, const float* left_xy, int nl, const float* right_xy, int nr,
+                               const psx_ransac_opts* opts, psx_ransac_result* result, void* inliers, int capacity, int* count,
+                               float* models, int* counts);
+int psx_ransac_fundamental(int device, const void* host_pairs, int n, const float* d_left_xy, int l_len,
+                           const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                           void* host_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_fundamental_dev(int device, const void* d_pairs, int n, const float* d_left_xy, int l_len,
+                               const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                               void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
 
 /* ---- caller-supplied keypoints ------------------------------------------------------------
  * Describing points the caller brings along instead of the ones the DoG detector finds (what OpenCV calls

@@ -101,6 +101,7 @@ SYMBOLS = [
     "psx_match_pairs_guided", "psx_match_pairs_guided_u8", "psx_match_pairs_guided_dev", "psx_match_pairs_guided_u8_dev",
     "psx_ransac_opts_default", "psx_ransac_samples", "psx_homography_fit", "psx_ransac_homography_ref",
     "psx_ransac_homography", "psx_ransac_homography_dev",
+    "psx_ransac_samples_k", "psx_fundamental_fit", "psx_ransac_fundamental_ref", "psx_ransac_fundamental", "psx_ransac_fundamental_dev",
 ]
 
 PAIRS_MUTUAL = 1     # PSX_PAIRS_MUTUAL
@@ -154,9 +155,12 @@ class RansacResult(C.Structure):
     def matrix(self):
         return np.array(list(self.m), np.float32)
 
+    kind = GUIDE_HOMOGRAPHY      # the ransac_fundamental* wrappers set GUIDE_EPIPOLAR on the results they return
+
     def guide(self, tol):
-        """the kept model as the psx_guide of a guided re-match"""
-        return Guide.homography(self.matrix(), tol)
+        """the kept model as the psx_guide of a guided re-match: a homography guide from ransac_homography*, an epipolar
+        one from ransac_fundamental*"""
+        return Guide.make(self.kind, self.matrix(), tol)
 
 
 DESCFMT_F32 = 0      # PSX_DESCFMT_F32
@@ -236,9 +240,11 @@ def lib():
         L.psx_ransac_opts_default.argtypes = [C.POINTER(RansacOpts)]
         L.psx_ransac_samples.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_int, vp]
         L.psx_homography_fit.argtypes = [vp, vp, C.c_int, vp]
-        L.psx_ransac_homography_ref.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(RansacOpts), C.POINTER(RansacResult),
+        L.psx_ransac_samples_k.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.psx_fundamental_fit.argtypes = [vp, vp, C.c_int, vp]
+        L.psx_ransac_fundamental_ref.argtypes = L.psx_ransac_homography_ref.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(RansacOpts), C.POINTER(RansacResult),
                                                 vp, C.c_int, ip, vp, vp]
-        for n in ("psx_ransac_homography", "psx_ransac_homography_dev"):
+        for n in ("psx_ransac_homography", "psx_ransac_homography_dev", "psx_ransac_fundamental", "psx_ransac_fundamental_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(RansacOpts), C.POINTER(RansacResult),
                                       vp, C.c_int, ip, vp, vp]
         _LIB = L
@@ -612,12 +618,17 @@ def ransac_opts(tol=2.0, hypotheses=1024, seed=0, refit=True):
     return RansacOpts(float(np.float32(tol)), int(hypotheses), int(seed) & 0xffffffff, RANSAC_REFIT if refit else 0)
 
 
-def ransac_samples(seed, first, count, n):
-    """psx_ransac_samples: the (count, 4) int32 pair indices of hypotheses first .. first + count - 1 among n pairs.  No device."""
-    out = np.zeros((count, 4), np.int32)
-    rc = lib().psx_ransac_samples(int(seed) & 0xffffffff, first, count, n, out.ctypes.data_as(C.c_void_p) if count else None)
+def ransac_samples(seed, first, count, n, k=4):
+    """psx_ransac_samples (k = 4, the homography's) / psx_ransac_samples_k (any other k; the fundamental matrix draws 8): the
+    (count, k) int32 pair indices of hypotheses first .. first + count - 1 among n pairs.  No device."""
+    out = np.zeros((count, max(int(k), 0)), np.int32)
+    po = out.ctypes.data_as(C.c_void_p) if out.size else None
+    if k == 4:
+        rc = lib().psx_ransac_samples(int(seed) & 0xffffffff, first, count, n, po)
+    else:
+        rc = lib().psx_ransac_samples_k(int(seed) & 0xffffffff, first, count, n, k, po)
     if rc != 0:
-        raise PopSiftError("psx_ransac_samples failed (%d)" % rc)
+        raise PopSiftError("psx_ransac_samples%s failed (%d)" % ("" if k == 4 else "_k", rc))
     return out
 
 
@@ -634,6 +645,19 @@ def homography_fit(left_xy, right_xy):
     return m
 
 
+def fundamental_fit(left_xy, right_xy):
+    """psx_fundamental_fit: the 9 float32 entries (row major, (xr yr 1) F (xl yl 1)^T = 0) of the fundamental matrix fitted to
+    n >= 8 correspondences left_xy[i] -> right_xy[i], in the given order.  No device."""
+    lx, rx = _xy(left_xy), _xy(right_xy)
+    if len(lx) != len(rx):
+        raise ValueError("one right position per left position")
+    m = np.zeros(9, np.float32)
+    rc = lib().psx_fundamental_fit(lx.ctypes.data_as(C.c_void_p), rx.ctypes.data_as(C.c_void_p), len(lx), m.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PopSiftError("psx_fundamental_fit failed (%d)" % rc)
+    return m
+
+
 def _pair_records(pairs):
     """16-byte pair records (PAIR_DTYPE or PAIR_U8_DTYPE), C-contiguous"""
     pairs = np.ascontiguousarray(pairs).reshape(-1)
@@ -642,9 +666,9 @@ def _pair_records(pairs):
     return pairs
 
 
-def _ransac_call(fn, name, pairs_ptr, n, dtype, plx, nl, prx, nr, opts, capacity, layers, out_ptr=None):
+def _ransac_call(fn, name, pairs_ptr, n, dtype, plx, nl, prx, nr, opts, capacity, layers, out_ptr=None, kind=GUIDE_HOMOGRAPHY):
     """One RANSAC call.  out_ptr None: the inliers come back in a host array.  Returns a dict: result (RansacResult), count,
-    inliers (host forms), and with layers models (N, 9) and counts (N)."""
+    inliers (host forms), and with layers models (N, 9) and counts (N).  kind: the guide the result's model is."""
     cap = n if capacity is None else capacity
     N = max(int(opts.hypotheses), 0)
     res, cnt = RansacResult(), C.c_int(-1)
@@ -656,6 +680,7 @@ def _ransac_call(fn, name, pairs_ptr, n, dtype, plx, nl, prx, nr, opts, capacity
     rc = fn(pairs_ptr, n, plx, nl, prx, nr, C.byref(opts), C.byref(res), po, cap, C.byref(cnt), ptr(models), ptr(counts))
     if rc != 0:
         raise PopSiftError("%s failed (%d)" % (name, rc))
+    res.kind = kind
     got = dict(result=res, count=cnt.value)
     if out is not None:
         got["inliers"] = out[:min(cnt.value, cap)]
@@ -664,7 +689,12 @@ def _ransac_call(fn, name, pairs_ptr, n, dtype, plx, nl, prx, nr, opts, capacity
     return got
 
 
-def ransac_homography_ref(pairs, left_xy, right_xy, opts=None, capacity=None, layers=False):
+def _ransac_names(model):
+    """(C name stem, guide kind) of the model "homography" or "fundamental" that a ransac_* wrapper estimates"""
+    return "psx_ransac_" + model, {"homography": GUIDE_HOMOGRAPHY, "fundamental": GUIDE_EPIPOLAR}[model]
+
+
+def ransac_homography_ref(pairs, left_xy, right_xy, opts=None, capacity=None, layers=False, model="homography"):
     """psx_ransac_homography_ref: the whole rule on host arrays, no device.  pairs: PAIR_DTYPE / PAIR_U8_DTYPE records;
     left_xy / right_xy: (nl, 2) / (nr, 2) positions.  Returns a dict: result, count, inliers, and with layers the
     per-hypothesis models and counts."""
@@ -672,11 +702,12 @@ def ransac_homography_ref(pairs, left_xy, right_xy, opts=None, capacity=None, la
     pairs, lx, rx = _pair_records(pairs), _xy(left_xy), _xy(right_xy)
     opts = opts or ransac_opts()
     ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
-    return _ransac_call(L.psx_ransac_homography_ref, "psx_ransac_homography_ref", ptr(pairs), len(pairs), pairs.dtype, ptr(lx), len(lx),
-                        ptr(rx), len(rx), opts, capacity, layers)
+    name, kind = _ransac_names(model)
+    return _ransac_call(getattr(L, name + "_ref"), name + "_ref", ptr(pairs), len(pairs), pairs.dtype, ptr(lx), len(lx),
+                        ptr(rx), len(rx), opts, capacity, layers, kind=kind)
 
 
-def ransac_homography(pairs, left_xy, right_xy, opts=None, device=0, capacity=None, layers=False):
+def ransac_homography(pairs, left_xy, right_xy, opts=None, device=0, capacity=None, layers=False, model="homography"):
     """psx_ransac_homography on host arrays (the positions go through device buffers): as ransac_homography_ref, on the
     device."""
     L = lib()
@@ -685,24 +716,44 @@ def ransac_homography(pairs, left_xy, right_xy, opts=None, device=0, capacity=No
     bufs = []
     try:
         plx, prx = _to_device(L, device, [lx, rx], bufs)
-        fn = lambda *a: L.psx_ransac_homography(device, *a)
-        return _ransac_call(fn, "psx_ransac_homography", pairs.ctypes.data_as(C.c_void_p) if pairs.size else None, len(pairs), pairs.dtype,
-                            plx, len(lx), prx, len(rx), opts, capacity, layers)
+        name, kind = _ransac_names(model)
+        fn = lambda *a: getattr(L, name)(device, *a)
+        return _ransac_call(fn, name, pairs.ctypes.data_as(C.c_void_p) if pairs.size else None, len(pairs), pairs.dtype,
+                            plx, len(lx), prx, len(rx), opts, capacity, layers, kind=kind)
     finally:
         for p in bufs:
             L.psx_dev_free(device, p)
 
 
-def ransac_homography_dev(pairs_ptr, n, left_xy_ptr, l_len, right_xy_ptr, r_len, out_ptr, capacity, opts=None, device=0, layers=False):
+def ransac_homography_dev(pairs_ptr, n, left_xy_ptr, l_len, right_xy_ptr, r_len, out_ptr, capacity, opts=None, device=0, layers=False,
+                          model="homography"):
     """psx_ransac_homography_dev on DEVICE pointers: the records at pairs_ptr (e.g. what match_pairs_dev left) are read and
     the inlier records written in device memory (16-byte aligned, `capacity` records).  Returns a dict: result, count, and
     with layers the per-hypothesis models and counts."""
     L = lib()
     opts = opts or ransac_opts()
     vp = lambda p: C.c_void_p(p) if p else None
-    fn = lambda *a: L.psx_ransac_homography_dev(device, *a)
-    return _ransac_call(fn, "psx_ransac_homography_dev", vp(pairs_ptr), n, None, vp(left_xy_ptr), l_len, vp(right_xy_ptr), r_len, opts,
-                        capacity, layers, out_ptr=out_ptr or 0)
+    name, kind = _ransac_names(model)
+    fn = lambda *a: getattr(L, name + "_dev")(device, *a)
+    return _ransac_call(fn, name + "_dev", vp(pairs_ptr), n, None, vp(left_xy_ptr), l_len, vp(right_xy_ptr), r_len, opts,
+                        capacity, layers, out_ptr=out_ptr or 0, kind=kind)
+
+
+def ransac_fundamental_ref(pairs, left_xy, right_xy, opts=None, capacity=None, layers=False):
+    """psx_ransac_fundamental_ref: as ransac_homography_ref for a fundamental matrix (n >= 8 pairs); result.guide(tol) is an
+    epipolar Guide"""
+    return ransac_homography_ref(pairs, left_xy, right_xy, opts, capacity, layers, model="fundamental")
+
+
+def ransac_fundamental(pairs, left_xy, right_xy, opts=None, device=0, capacity=None, layers=False):
+    """psx_ransac_fundamental on host arrays: as ransac_fundamental_ref, on the device"""
+    return ransac_homography(pairs, left_xy, right_xy, opts, device, capacity, layers, model="fundamental")
+
+
+def ransac_fundamental_dev(pairs_ptr, n, left_xy_ptr, l_len, right_xy_ptr, r_len, out_ptr, capacity, opts=None, device=0, layers=False):
+    """psx_ransac_fundamental_dev on DEVICE pointers: as ransac_homography_dev"""
+    return ransac_homography_dev(pairs_ptr, n, left_xy_ptr, l_len, right_xy_ptr, r_len, out_ptr, capacity, opts, device, layers,
+                                 model="fundamental")
 
 
 class DeviceDescriptors:
@@ -757,15 +808,20 @@ class DeviceDescriptors:
         got = _pairs_call(fn, "psx_match_pairs_guided", self.device, self.ptr, self.n, right.ptr, right.n, ratio, mutual, PAIR_DTYPE, capacity)
         return got[0] if capacity is None else got
 
-    def ransac_homography(self, right, pairs, opts=None, capacity=None, layers=False):
+    def ransac_homography(self, right, pairs, opts=None, capacity=None, layers=False, model="homography"):
         """psx_ransac_homography(pairs of self as left and right: DeviceDescriptors, both built with positions): the dict
         of capi.ransac_homography"""
         if (self.n and not self.xy_ptr) or (right.n and not right.xy_ptr):
             raise ValueError("both sides need positions (DeviceDescriptors(arr, xy=...))")
         pairs = _pair_records(pairs)
-        fn = lambda *a: lib().psx_ransac_homography(self.device, *a)
-        return _ransac_call(fn, "psx_ransac_homography", pairs.ctypes.data_as(C.c_void_p) if pairs.size else None, len(pairs), pairs.dtype,
-                            self.xy_ptr, self.n, right.xy_ptr, right.n, opts or ransac_opts(), capacity, layers)
+        name, kind = _ransac_names(model)
+        fn = lambda *a: getattr(lib(), name)(self.device, *a)
+        return _ransac_call(fn, name, pairs.ctypes.data_as(C.c_void_p) if pairs.size else None, len(pairs), pairs.dtype,
+                            self.xy_ptr, self.n, right.xy_ptr, right.n, opts or ransac_opts(), capacity, layers, kind=kind)
+
+    def ransac_fundamental(self, right, pairs, opts=None, capacity=None, layers=False):
+        """psx_ransac_fundamental(pairs of self as left and right): the dict of capi.ransac_fundamental"""
+        return self.ransac_homography(right, pairs, opts, capacity, layers, model="fundamental")
 
     def close(self):
         if self.ptr:

@@ -1,12 +1,15 @@
-// ransac.hip -- geometric verification: a homography from matched pairs by RANSAC on the device
-// (psx_ransac_homography*, psx_ransac_samples, psx_homography_fit, psx_ransac_homography_ref; include/popsift_hip.h).
+// ransac.hip -- geometric verification: a homography or a fundamental matrix from matched pairs by RANSAC on the device
+// (psx_ransac_homography*, psx_ransac_samples, psx_homography_fit, psx_ransac_homography_ref; psx_ransac_fundamental*,
+// psx_ransac_samples_k, psx_fundamental_fit, psx_ransac_fundamental_ref; include/popsift_hip.h).
 //
-// The rule -- samples, fit, score, select, refit, inliers -- is ransac_rule.h, shared with the host reference; this file is
-// the estimator around it.
+// The rule -- samples, fit, score, select, refit, inliers -- is ransac_rule.h (homography) and fundamental_rule.h
+// (fundamental matrix), shared with the host references; this file is the estimator around them.  Kernels that evaluate
+// the inlier test are templates on the model kind (RModel), everything else serves both.
 //   k_ransac_gather  the four floats of every pair, once, into a packed float4 array (out-of-range indices raise a flag and
 //                    read nothing); everything after it streams 16 B per lane, coalesced
 //   k_ransac_hyp     one lane per hypothesis: the sample's four indices, their float4s and the double-precision fit, all
 //                    loops of constant trip count (registers); writes the model, clears the count
+//   k_ransac_hyp_fund  the same for the fundamental matrix: eight indices, the pivoted 8-point fit, still in registers
 //   k_ransac_score   the hot kernel, N x n rule evaluations.  Lanes own pairs: R_PPL float4 stay in VGPRs; the workgroup
 //                    walks a block of R_HB hypotheses whose nine floats sit at a wave-uniform address (scalar loads); per
 //                    hypothesis one wave64 ballot + popcount per resident pair and ONE integer atomic per wave -- integer
@@ -14,11 +17,11 @@
 //   k_ransac_select  single workgroup arg-max on (count descending, index ascending); copies the winner's model
 //   k_ransac_inl_count / _write   the stable compaction of the pair join (match.hip): ballot + mbcnt, exclusive scan across
 //                    workgroups; the payload is any 16-byte record array (the float4s for the refit, the pair records at the end)
-//   k_ransac_decide  keeps the refit model iff it is finite and its count is not below the winner's
+//   k_ransac_decide  keeps the refit model iff it may score and its count is not below the winner's
 // The refit's fit is serial by definition: the winner's float4s come to the host through the pinned staging buffer, the
 // model goes back and is scored by the score kernel with N = 1.  One synchronisation without the refit, two with it.
 #include "psx_internal.h"
-#include "ransac_rule.h"
+#include "fundamental_rule.h"
 #include "match_scratch.h"
 
 #include <cstring>
@@ -34,6 +37,20 @@ struct RState {                              // device resident, copied to the h
     int best, sample_inliers, refit_kept, bad, total;
     int refit_count, pad;                    // from here: uploaded before the refit's score launch (11 words)
     float refit[9];
+};
+
+// What differs between the two estimators, by the kind of guide the model is (PSX_GUIDE_HOMOGRAPHY: ransac_rule.h;
+// PSX_GUIDE_EPIPOLAR: fundamental_rule.h): the sample size, which models may score, the serial fit of the refit.
+template <int KIND> struct RModel;
+template <> struct RModel<PSX_GUIDE_HOMOGRAPHY> {
+    static constexpr int MIN = 4;
+    static __host__ __device__ __forceinline__ bool usable(const float* m) { return psx_ransac_model_finite(m); }
+    static void fit(const psx_ransac_pt* pt, int n, float* m) { psx_homography_fit_rule<0>(pt, n, m); }
+};
+template <> struct RModel<PSX_GUIDE_EPIPOLAR> {
+    static constexpr int MIN = PSX_FUND_MIN;
+    static __host__ __device__ __forceinline__ bool usable(const float* m) { return psx_fund_model_usable(m); }
+    static void fit(const psx_ransac_pt* pt, int n, float* m) { psx_fundamental_fit_rule<0>(pt, n, m); }
 };
 
 __device__ __forceinline__ psx_ransac_pt r_pt(const float4& v) { psx_ransac_pt p = {v.x, v.y, v.z, v.w}; return p; }
@@ -75,7 +92,26 @@ __global__ __launch_bounds__(64) void k_ransac_hyp(const float4* __restrict__ pt
     counts[h] = 0;
 }
 
+// the same for a fundamental matrix: eight indices, their float4s, the fit of fundamental_rule.h
+__global__ __launch_bounds__(64) void k_ransac_hyp_fund(const float4* __restrict__ pts, int n, unsigned seed, int N,
+                                                        float* __restrict__ models, int* __restrict__ counts)
+{
+    const int h = blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= N) return;
+    int idx[PSX_FUND_MIN];
+    psx_ransac_sample_k<PSX_FUND_MIN>(seed, h, n, idx);
+    psx_ransac_pt q[PSX_FUND_MIN];
+#pragma unroll
+    for (int k = 0; k < PSX_FUND_MIN; k++) q[k] = r_pt(pts[idx[k]]);
+    float m[9];
+    psx_fundamental_fit_rule<PSX_FUND_MIN>(q, PSX_FUND_MIN, m);
+#pragma unroll
+    for (int k = 0; k < 9; k++) models[9 * (size_t)h + k] = m[k];
+    counts[h] = 0;
+}
+
 // grid (ceil(n / (256 R_PPL)), ceil(N / R_HB)), 256 threads
+template <int KIND>
 __global__ __launch_bounds__(256) void k_ransac_score(const float4* __restrict__ pts, int n, const float* __restrict__ models, int N,
                                                       float tol, int* __restrict__ counts)
 {
@@ -95,12 +131,12 @@ __global__ __launch_bounds__(256) void k_ransac_score(const float4* __restrict__
         float m[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) m[k] = models[9 * (size_t)h + k];       // wave-uniform address
-        if (!psx_ransac_model_finite(m)) continue;                        // wave uniform
+        if (!RModel<KIND>::usable(m)) continue;                           // wave uniform
         int c = 0;
 #pragma unroll
         for (int k = 0; k < R_PPL; k++) {
-            const psx_guide_line l = psx_guide_left(PSX_GUIDE_HOMOGRAPHY, m, tol, q[k].xl, q[k].yl);
-            c += __popcll(__ballot(in[k] && psx_guide_right(PSX_GUIDE_HOMOGRAPHY, l, q[k].xr, q[k].yr)));
+            const psx_guide_line l = psx_guide_left(KIND, m, tol, q[k].xl, q[k].yl);
+            c += __popcll(__ballot(in[k] && psx_guide_right(KIND, l, q[k].xr, q[k].yr)));
         }
         if (lane == 0 && c > 0) atomicAdd(counts + h, c);
     }
@@ -132,30 +168,34 @@ __global__ __launch_bounds__(256) void k_ransac_select(const int* __restrict__ c
     }
 }
 
+template <int KIND>
 __global__ void k_ransac_decide(RState* __restrict__ st)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (psx_ransac_model_finite(st->refit) && st->refit_count >= st->sample_inliers) {
+    if (RModel<KIND>::usable(st->refit) && st->refit_count >= st->sample_inliers) {
         for (int k = 0; k < 9; k++) st->kept[k] = st->refit[k];
         st->refit_kept = 1;
     }
 }
 
-// keep: pair i passes under the state's kept model (no pair does under a non-finite one, or after a bad index)
+// keep: pair i passes under the state's kept model (no pair does under one that may not score, or after a bad index)
+template <int KIND>
 __device__ __forceinline__ bool r_keep(const float4* __restrict__ pts, int n, const RState* __restrict__ st, float tol, int i)
 {
     float m[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) m[k] = st->kept[k];
-    if (st->bad != 0 || !psx_ransac_model_finite(m) || i >= n) return false;
-    return psx_ransac_inlier(m, tol, r_pt(pts[i]));
+    if (st->bad != 0 || !RModel<KIND>::usable(m) || i >= n) return false;
+    const psx_ransac_pt p = r_pt(pts[i]);
+    return psx_guide_right(KIND, psx_guide_left(KIND, m, tol, p.xl, p.yl), p.xr, p.yr);
 }
 
+template <int KIND>
 __global__ __launch_bounds__(256) void k_ransac_inl_count(const float4* __restrict__ pts, int n, const RState* __restrict__ st, float tol,
                                                           int* __restrict__ wg_tot)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long m = __ballot(r_keep(pts, n, st, tol, i));
+    const unsigned long long m = __ballot(r_keep<KIND>(pts, n, st, tol, i));
     __shared__ int s_cnt[4];
     if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(m);
     __syncthreads();
@@ -163,13 +203,14 @@ __global__ __launch_bounds__(256) void k_ransac_inl_count(const float4* __restri
 }
 
 // src: n 16-byte records (the correspondences themselves, or the pair records); out: never written at or past `capacity`
+template <int KIND>
 __global__ __launch_bounds__(256) void k_ransac_inl_write(const float4* __restrict__ pts, int n, const RState* __restrict__ st, float tol,
                                                           const int* __restrict__ wg_tot, const int4* __restrict__ src,
                                                           int4* __restrict__ out, int capacity, int* __restrict__ total)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool keep = r_keep(pts, n, st, tol, i);
+    const bool keep = r_keep<KIND>(pts, n, st, tol, i);
     const unsigned long long m = __ballot(keep);
     int part = 0;
     for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) part += wg_tot[b];
@@ -189,21 +230,24 @@ __global__ __launch_bounds__(256) void k_ransac_inl_write(const float4* __restri
 constexpr size_t R_PIN_STATE = 0, R_PIN_REFIT = 128, R_PIN_REC = 256;      // layout of the pinned staging buffer
 static_assert(sizeof(RState) <= R_PIN_REFIT, "RState layout");
 
+template <int KIND>
 void queue_score(hipStream_t st, const float4* d_pts, int n, const float* d_models, int N, float tol, int* d_counts)
 {
     const dim3 grid((unsigned)((n + 256 * R_PPL - 1) / (256 * R_PPL)), (unsigned)((N + R_HB - 1) / R_HB));
-    hipLaunchKernelGGL(k_ransac_score, grid, dim3(256), 0, st, d_pts, n, d_models, N, tol, d_counts);
+    hipLaunchKernelGGL(k_ransac_score<KIND>, grid, dim3(256), 0, st, d_pts, n, d_models, N, tol, d_counts);
 }
 
+template <int KIND>
 void queue_compact(hipStream_t st, const float4* d_pts, int n, RState* d_state, float tol, int* d_tot, const void* src, void* out, int cap)
 {
     const int nb = (n + 255) / 256;
-    hipLaunchKernelGGL(k_ransac_inl_count, dim3(nb), dim3(256), 0, st, d_pts, n, d_state, tol, d_tot);
-    hipLaunchKernelGGL(k_ransac_inl_write, dim3(nb), dim3(256), 0, st, d_pts, n, d_state, tol, d_tot, static_cast<const int4*>(src),
+    hipLaunchKernelGGL(k_ransac_inl_count<KIND>, dim3(nb), dim3(256), 0, st, d_pts, n, d_state, tol, d_tot);
+    hipLaunchKernelGGL(k_ransac_inl_write<KIND>, dim3(nb), dim3(256), 0, st, d_pts, n, d_state, tol, d_tot, static_cast<const int4*>(src),
                        static_cast<int4*>(out), cap, &d_state->total);
 }
 
 // host_pairs or d_pairs_in; host_inl or d_inl (the other is NULL; both NULL with capacity 0)
+template <int KIND>
 int ransac_run(int device, const void* host_pairs, const void* d_pairs_in, int n, const float* d_lxy, int l_len, const float* d_rxy, int r_len,
                const psx_ransac_opts* opts, psx_ransac_result* result, void* host_inl, void* d_inl, int capacity, int* count,
                float* host_models, int* host_counts)
@@ -213,7 +257,8 @@ int ransac_run(int device, const void* host_pairs, const void* d_pairs_in, int n
     if (!psx_ransac_opts_ok(opts) || !result || !count || n < 0 || n > 0x3fffffff || l_len < 0 || r_len < 0 || capacity < 0 ||
         (n > 0 && !in) || (l_len > 0 && !d_lxy) || (r_len > 0 && !d_rxy) || (capacity > 0 && !outp))
         return PSX_ERR_INVALID;
-    if (n < 4) { psx_ransac_no_model(result); *count = 0; return PSX_OK; }
+    constexpr int MIN = RModel<KIND>::MIN;
+    if (n < MIN) { psx_ransac_no_model(result); *count = 0; return PSX_OK; }
     if (l_len == 0 || r_len == 0) return PSX_ERR_INVALID;                 // no index can lie inside an empty array
     if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
     MatchScratch& sc = psx_match_scratch();
@@ -250,12 +295,15 @@ int ransac_run(int device, const void* host_pairs, const void* d_pairs_in, int n
     if (hipMemsetAsync(d_state, 0, sizeof(RState), st) != hipSuccess) return PSX_ERR_HIP;
     hipLaunchKernelGGL(k_ransac_gather, dim3(nb), dim3(256), 0, st, static_cast<const int4*>(d_pairs), n, reinterpret_cast<const float2*>(d_lxy),
                        l_len, reinterpret_cast<const float2*>(d_rxy), r_len, d_pts, &d_state->bad);
-    hipLaunchKernelGGL(k_ransac_hyp, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, d_pts, n, opts->seed, N, d_models, d_counts);
-    queue_score(st, d_pts, n, d_models, N, tol, d_counts);
+    if (KIND == PSX_GUIDE_HOMOGRAPHY)
+        hipLaunchKernelGGL(k_ransac_hyp, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, d_pts, n, opts->seed, N, d_models, d_counts);
+    else
+        hipLaunchKernelGGL(k_ransac_hyp_fund, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, d_pts, n, opts->seed, N, d_models, d_counts);
+    queue_score<KIND>(st, d_pts, n, d_models, N, tol, d_counts);
     hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(256), 0, st, d_counts, N, d_models, d_state);
     // with the refit: the winner's correspondences to the host; without: the inlier records, and the call is complete
-    if (refit) queue_compact(st, d_pts, n, d_state, tol, d_tot, d_pts, pin_rec, n);
-    else queue_compact(st, d_pts, n, d_state, tol, d_tot, d_pairs, final_out, final_cap);
+    if (refit) queue_compact<KIND>(st, d_pts, n, d_state, tol, d_tot, d_pts, pin_rec, n);
+    else queue_compact<KIND>(st, d_pts, n, d_state, tol, d_tot, d_pairs, final_out, final_cap);
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hpin + R_PIN_STATE, d_state, sizeof(RState), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
         return PSX_ERR_HIP;
@@ -263,17 +311,17 @@ int ransac_run(int device, const void* host_pairs, const void* d_pairs_in, int n
     if (hs->best < 0 || hs->best >= N || hs->total < 0 || hs->total > n) return PSX_ERR_HIP;
     if (refit) {
         const int k = hs->sample_inliers;
-        if (k >= 4 && hs->total == k) {
+        if (k >= MIN && hs->total == k) {
             int* up = reinterpret_cast<int*>(hpin + R_PIN_REFIT);           // refit_count, pad, refit[9]
             up[0] = 0; up[1] = 0;
-            psx_homography_fit_rule<0>(reinterpret_cast<const psx_ransac_pt*>(hpin + R_PIN_REC), k, reinterpret_cast<float*>(up + 2));
-            if (psx_ransac_model_finite(reinterpret_cast<const float*>(up + 2))) {
+            RModel<KIND>::fit(reinterpret_cast<const psx_ransac_pt*>(hpin + R_PIN_REC), k, reinterpret_cast<float*>(up + 2));
+            if (RModel<KIND>::usable(reinterpret_cast<const float*>(up + 2))) {
                 if (hipMemcpyAsync(&d_state->refit_count, up, sizeof(int) * 11, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
-                queue_score(st, d_pts, n, d_state->refit, 1, tol, &d_state->refit_count);
-                hipLaunchKernelGGL(k_ransac_decide, dim3(1), dim3(64), 0, st, d_state);
+                queue_score<KIND>(st, d_pts, n, d_state->refit, 1, tol, &d_state->refit_count);
+                hipLaunchKernelGGL(k_ransac_decide<KIND>, dim3(1), dim3(64), 0, st, d_state);
             }
         }
-        queue_compact(st, d_pts, n, d_state, tol, d_tot, d_pairs, final_out, final_cap);
+        queue_compact<KIND>(st, d_pts, n, d_state, tol, d_tot, d_pairs, final_out, final_cap);
         if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hpin + R_PIN_STATE, d_state, sizeof(RState), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
             return PSX_ERR_HIP;
@@ -282,7 +330,7 @@ int ransac_run(int device, const void* host_pairs, const void* d_pairs_in, int n
     if (host_models && (hipMemcpyAsync(host_models, d_models, sizeof(float) * 9 * (size_t)N, hipMemcpyDeviceToHost, st) != hipSuccess)) return PSX_ERR_HIP;
     if (host_counts && (hipMemcpyAsync(host_counts, d_counts, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost, st) != hipSuccess)) return PSX_ERR_HIP;
     if ((host_models || host_counts) && hipStreamSynchronize(st) != hipSuccess) return PSX_ERR_HIP;
-    if (!psx_ransac_model_finite(hs->kept)) { psx_ransac_no_model(result); *count = 0; return PSX_OK; }
+    if (!RModel<KIND>::usable(hs->kept)) { psx_ransac_no_model(result); *count = 0; return PSX_OK; }
     const int total = hs->total;
     if (host_inl && total > 0 && nrec > 0) memcpy(host_inl, hpin + R_PIN_REC, 16 * (size_t)(total < nrec ? total : nrec));
     for (int k = 0; k < 9; k++) result->m[k] = hs->kept[k];
@@ -336,7 +384,7 @@ extern "C" int psx_ransac_homography(int device, const void* host_pairs, int n, 
                                      const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
                                      void* host_inliers, int capacity, int* count, float* host_models, int* host_counts)
 {
-    return ransac_run(device, host_pairs, nullptr, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, host_inliers, nullptr, capacity, count,
+    return ransac_run<PSX_GUIDE_HOMOGRAPHY>(device, host_pairs, nullptr, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, host_inliers, nullptr, capacity, count,
                       host_models, host_counts);
 }
 
@@ -344,6 +392,58 @@ extern "C" int psx_ransac_homography_dev(int device, const void* d_pairs, int n,
                                          const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
                                          void* d_inliers, int capacity, int* count, float* host_models, int* host_counts)
 {
-    return ransac_run(device, nullptr, d_pairs, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, nullptr, d_inliers, capacity, count,
+    return ransac_run<PSX_GUIDE_HOMOGRAPHY>(device, nullptr, d_pairs, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, nullptr, d_inliers, capacity, count,
                       host_models, host_counts);
+}
+
+extern "C" int psx_ransac_samples_k(unsigned seed, int first, int count, int n, int k, int* idx)
+{
+    if ((k != 4 && k != PSX_FUND_MIN) || n < k || first < 0 || count < 0 || first > PSX_RANSAC_MAX_HYPOTHESES - count || (count > 0 && !idx))
+        return PSX_ERR_INVALID;
+    for (int i = 0; i < count; i++) {
+        if (k == 4) psx_ransac_sample_k<4>(seed, first + i, n, idx + 4 * (size_t)i);
+        else psx_ransac_sample_k<PSX_FUND_MIN>(seed, first + i, n, idx + PSX_FUND_MIN * (size_t)i);
+    }
+    return PSX_OK;
+}
+
+extern "C" int psx_fundamental_fit(const float* left_xy, const float* right_xy, int n, float* m)
+{
+    if (n < PSX_FUND_MIN || !left_xy || !right_xy || !m) return PSX_ERR_INVALID;
+    psx_ransac_pt* pt = new (std::nothrow) psx_ransac_pt[(size_t)n];
+    if (!pt) return PSX_ERR_NOMEM;
+    for (int i = 0; i < n; i++) {
+        pt[i].xl = left_xy[2 * (size_t)i]; pt[i].yl = left_xy[2 * (size_t)i + 1];
+        pt[i].xr = right_xy[2 * (size_t)i]; pt[i].yr = right_xy[2 * (size_t)i + 1];
+    }
+    psx_fundamental_fit_rule<0>(pt, n, m);
+    delete[] pt;
+    return PSX_OK;
+}
+
+extern "C" int psx_ransac_fundamental_ref(const void* pairs, int n, const float* left_xy, int nl, const float* right_xy, int nr,
+                                          const psx_ransac_opts* opts, psx_ransac_result* result, void* inliers, int capacity, int* count,
+                                          float* models, int* counts)
+{
+    psx_ransac_pt* scratch = n >= PSX_FUND_MIN ? new (std::nothrow) psx_ransac_pt[(size_t)n] : nullptr;
+    if (n >= PSX_FUND_MIN && !scratch) return PSX_ERR_NOMEM;
+    const int rc = psx_ransac_fundamental_host(pairs, n, left_xy, nl, right_xy, nr, opts, result, inliers, capacity, count, models, counts, scratch);
+    delete[] scratch;
+    return rc;
+}
+
+extern "C" int psx_ransac_fundamental(int device, const void* host_pairs, int n, const float* d_left_xy, int l_len,
+                                      const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                                      void* host_inliers, int capacity, int* count, float* host_models, int* host_counts)
+{
+    return ransac_run<PSX_GUIDE_EPIPOLAR>(device, host_pairs, nullptr, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, host_inliers, nullptr,
+                                          capacity, count, host_models, host_counts);
+}
+
+extern "C" int psx_ransac_fundamental_dev(int device, const void* d_pairs, int n, const float* d_left_xy, int l_len,
+                                          const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                                          void* d_inliers, int capacity, int* count, float* host_models, int* host_counts)
+{
+    return ransac_run<PSX_GUIDE_EPIPOLAR>(device, nullptr, d_pairs, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, nullptr, d_inliers,
+                                          capacity, count, host_models, host_counts);
 }

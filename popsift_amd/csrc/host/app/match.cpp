@@ -4,7 +4,8 @@
 // (FeaturesDev::matchPairs) instead of the accept / reject lines; --ratio and --mutual refine it; --homography or
 // --fundamental with --guide-tol restrict the search to the pairs a guide admits (FeaturesDev::matchPairsGuided);
 // --verify-homography TOL estimates a homography from the pairs (FeaturesDev::estimateHomography) and writes its inliers,
-// --rematch then writes the list guided by that model instead.
+// --verify-fundamental TOL a fundamental matrix (FeaturesDev::estimateFundamental); --rematch then writes the list guided
+// by that model instead.
 #include "options.h"
 #include "pgmread.h"
 
@@ -31,7 +32,7 @@ static bool  have_ratio = false, mutual = false;
 static float pair_ratio = 0.8f;
 static bool  have_h = false, have_f = false, have_tol = false;
 static popsift::MatchGuide guide;
-static bool  have_verify = false, have_ransac_opt = false, rematch = false;
+static bool  have_verify = false, have_verify_f = false, have_ransac_opt = false, rematch = false;
 static popsift::RansacOptions ransac;
 
 // "m0,...,m8": nine numbers, row major
@@ -96,13 +97,16 @@ int main( int argc, char** argv )
     all.add( "verify-homography", 0, true, "Geometric verification: estimate a homography from the pairs by RANSAC with this inlier "
              "tolerance in pixels, print it and write only its inliers (needs --pairs)",
              [&]( const string& s ) { ransac.tol = app::to_float( s ); have_verify = true; } );
+    all.add( "verify-fundamental", 0, true, "Geometric verification: estimate a fundamental matrix from the pairs by RANSAC with this "
+             "inlier tolerance in pixels (distance from the epipolar line), print it and write only its inliers (needs --pairs)",
+             [&]( const string& s ) { ransac.tol = app::to_float( s ); have_verify_f = true; } );
     all.add( "ransac-hypotheses", 0, true, "Geometric verification: the number of hypotheses, 1 to 65536. Default is 1024",
              [&]( const string& s ) { ransac.hypotheses = (int)app::to_float( s ); have_ransac_opt = true; } );
     all.add( "ransac-seed", 0, true, "Geometric verification: the seed of the samples. Default is 0",
              [&]( const string& s ) { ransac.seed = (unsigned)std::strtoul( s.c_str(), nullptr, 10 ); have_ransac_opt = true; } );
     all.flag( "ransac-refit", 0, "Geometric verification: refit the best hypothesis over its inliers", [&]() { ransac.refit = true; have_ransac_opt = true; } );
-    all.flag( "rematch", 0, "After --verify-homography: match again, guided by the estimated homography and the same tolerance, and "
-              "write that list instead", [&]() { rematch = true; } );
+    all.flag( "rematch", 0, "After --verify-homography or --verify-fundamental: match again, guided by the estimated model and the "
+              "same tolerance, and write that list instead", [&]() { rematch = true; } );
     all.flag( "pgmread-loading", 0, "Use the PGM/PPM loader (the only loader of this build)", []() {} );
     try {
         all.parse( argc, argv );
@@ -116,10 +120,13 @@ int main( int argc, char** argv )
         if( ( have_h || have_f ) && !have_tol ) throw runtime_error( "the options '--homography' and '--fundamental' need '--guide-tol'" );
         if( have_tol && !( guide.tol >= 0.0f && std::isfinite( guide.tol ) ) ) throw runtime_error( "the guide tolerance must be finite and not negative" );
         guide.kind = have_f ? popsift::MatchGuide::Epipolar : popsift::MatchGuide::Homography;
-        if( have_verify && pairs_file.empty() ) throw runtime_error( "the option '--verify-homography' needs '--pairs'" );
-        if( have_ransac_opt && !have_verify ) throw runtime_error( "the options '--ransac-hypotheses', '--ransac-seed' and '--ransac-refit' need '--verify-homography'" );
-        if( rematch && !have_verify ) throw runtime_error( "the option '--rematch' needs '--verify-homography'" );
-        if( have_verify && ( have_h || have_f ) ) throw runtime_error( "the option '--verify-homography' cannot be combined with '--homography' or '--fundamental'" );
+        if( have_verify && have_verify_f ) throw runtime_error( "the options '--verify-homography' and '--verify-fundamental' cannot be combined" );
+        const string verify_opt = have_verify_f ? "'--verify-fundamental'" : "'--verify-homography'";
+        have_verify = have_verify || have_verify_f;
+        if( have_verify && pairs_file.empty() ) throw runtime_error( "the option " + verify_opt + " needs '--pairs'" );
+        if( have_ransac_opt && !have_verify ) throw runtime_error( "the options '--ransac-hypotheses', '--ransac-seed' and '--ransac-refit' need '--verify-homography' or '--verify-fundamental'" );
+        if( rematch && !have_verify ) throw runtime_error( "the option '--rematch' needs '--verify-homography' or '--verify-fundamental'" );
+        if( have_verify && ( have_h || have_f ) ) throw runtime_error( "the option " + verify_opt + " cannot be combined with '--homography' or '--fundamental'" );
         if( have_verify && !( ransac.tol >= 0.0f && std::isfinite( ransac.tol ) ) ) throw runtime_error( "the verification tolerance must be finite and not negative" );
         if( have_verify && ( ransac.hypotheses < 1 || ransac.hypotheses > 65536 ) ) throw runtime_error( "the number of hypotheses must lie in 1 .. 65536" );
     } catch( const std::exception& e ) {
@@ -152,11 +159,14 @@ int main( int argc, char** argv )
             std::vector<popsift::Match> mm = ( have_h || have_f ) ? lFeatures->matchPairsGuided( rFeatures, guide, mo )
                                                                   : lFeatures->matchPairs( rFeatures, mo );
             if( have_verify ) {
-                const popsift::HomographyEstimate est = lFeatures->estimateHomography( rFeatures, mm, ransac );
-                printf( "Homography:" );
+                const char* model = have_verify_f ? "Fundamental" : "Homography";
+                const popsift::HomographyEstimate est = have_verify_f ? lFeatures->estimateFundamental( rFeatures, mm, ransac )
+                                                                      : lFeatures->estimateHomography( rFeatures, mm, ransac );
+                printf( "%s:", model );
                 for( int k = 0; k < 9; k++ ) printf( " %.9g", est.guide.m[k] );
-                printf( "\nHomography inliers: %d of %d\n", (int)est.inliers.size(), (int)mm.size() );
-                if( est.best < 0 ) throw runtime_error( "no homography could be estimated from the pairs" );
+                printf( "\n%s inliers: %d of %d\n", model, (int)est.inliers.size(), (int)mm.size() );
+                if( est.best < 0 ) throw runtime_error( have_verify_f ? "no fundamental matrix could be estimated from the pairs"
+                                                                      : "no homography could be estimated from the pairs" );
                 mm = rematch ? lFeatures->matchPairsGuided( rFeatures, est.guide, mo ) : est.inliers;
             }
             FILE* f = fopen( pairs_file.c_str(), "w" );

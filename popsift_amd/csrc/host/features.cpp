@@ -603,24 +603,34 @@ std::vector<Match> FeaturesDev::matchPairsGuided( FeaturesDev* other, const Matc
 
 HomographyEstimate FeaturesDev::estimateHomography( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts )
 {
-    const char* who = "FeaturesDev::estimateHomography";
+    return estimate( "FeaturesDev::estimateHomography", false, other, matches, opts );
+}
+
+FundamentalEstimate FeaturesDev::estimateFundamental( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts )
+{
+    return estimate( "FeaturesDev::estimateFundamental", true, other, matches, opts );
+}
+
+HomographyEstimate FeaturesDev::estimate( const char* who, bool fundamental, FeaturesDev* other, const std::vector<Match>& matches,
+                                          const RansacOptions& opts )
+{
     if( other == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
     if( other->_device != _device ) {
         std::ostringstream ss;
         ss << who << ": the two objects live on different devices (" << _device << " and " << other->_device << ")";
         fatal( __FILE__, __LINE__, ss.str() );
     }
-    // refused here, before any device is touched: what psx_ransac_homography refuses
+    // refused here, before any device is touched: what psx_ransac_homography and psx_ransac_fundamental refuse
     if( !( std::isfinite( opts.tol ) && opts.tol >= 0.0f ) || opts.hypotheses < 1 || opts.hypotheses > 65536 )
         fatal( __FILE__, __LINE__, std::string( who ) + ": invalid options (finite tolerance >= 0, 1 to 65536 hypotheses)" );
     HomographyEstimate est;
-    est.guide.kind = MatchGuide::Homography;
+    est.guide.kind = fundamental ? MatchGuide::Epipolar : MatchGuide::Homography;
     for( int k = 0; k < 9; k++ ) est.guide.m[k] = 0.0f;
     est.guide.tol = opts.tol;
     est.best = -1; est.sample_inliers = 0; est.refit_kept = false;
     const int n = (int)matches.size();
     const int l_len = getDescriptorCount(), r_len = other->getDescriptorCount();
-    if( n < 4 ) return est;
+    if( n < ( fundamental ? 8 : 4 ) ) return est;
     // the record is copied whole: its distance slots carry the index of the match
     std::vector<psx_match_pair_u8> rec( n ), inl( n );
     for( int k = 0; k < n; k++ ) { rec[k].left = matches[k].left_descriptor; rec[k].right = matches[k].right_descriptor; rec[k].d1 = k; rec[k].d2 = 0; }
@@ -634,8 +644,9 @@ HomographyEstimate FeaturesDev::estimateHomography( FeaturesDev* other, const st
     if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)r_len * 2 * sizeof(float), &rxy );
     if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)_ext, _rev, l_len, (float*)lxy );
     if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)other->_ext, other->_rev, r_len, (float*)rxy );
-    if( rc == PSX_OK ) rc = psx_ransac_homography( _device, rec.data(), n, (const float*)lxy, l_len, (const float*)rxy, r_len, &po, &res,
-                                                   inl.data(), n, &count, nullptr, nullptr );
+    if( rc == PSX_OK ) rc = ( fundamental ? psx_ransac_fundamental : psx_ransac_homography )( _device, rec.data(), n, (const float*)lxy, l_len,
+                                                                                              (const float*)rxy, r_len, &po, &res, inl.data(), n,
+                                                                                              &count, nullptr, nullptr );
     psx_dev_free( _device, lxy );
     psx_dev_free( _device, rxy );
     if( rc != PSX_OK ) {

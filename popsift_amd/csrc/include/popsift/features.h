@@ -144,8 +144,8 @@ struct Match
     float distance, second_distance;            ///< squared; byte distances converted (exact), +inf: no second neighbour
 };
 
-/// How FeaturesDev::estimateHomography runs: the options of psx_ransac_homography (include/popsift_hip.h, "geometric
-/// verification")
+/// How FeaturesDev::estimateHomography and estimateFundamental run: the options of psx_ransac_homography and
+/// psx_ransac_fundamental (include/popsift_hip.h, "geometric verification")
 struct RansacOptions
 {
     float    tol        = 2.0f;   ///< inlier tolerance in pixels, finite and >= 0
@@ -165,6 +165,10 @@ struct HomographyEstimate
     bool               refit_kept;       ///< the refit model replaced it
 };
 
+/// What FeaturesDev::estimateFundamental returns: the same fields; guide is Epipolar, the estimated fundamental matrix
+/// (this -> other); the sample has 8 points and best = -1 stands for fewer than 8 matches or no usable model
+typedef HomographyEstimate FundamentalEstimate;
+
 /// Device-resident result (MatchingMode): arrays live in HBM of the extracting device.
 class FeaturesDev : public FeaturesBase
 {
@@ -172,6 +176,8 @@ class FeaturesDev : public FeaturesBase
     Descriptor*  _ori;   // device
     int*         _rev;   // device: descriptor -> extremum
     int          _device;
+
+    HomographyEstimate estimate( const char* who, bool fundamental, FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts );
 
 public:
     FeaturesDev( );
@@ -199,6 +205,9 @@ public:
     /// returned for the same two objects) by RANSAC on the device, psx_ransac_homography.  Throws as matchPairs, and for
     /// invalid options or a descriptor index outside its object.
     HomographyEstimate estimateHomography( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts = RansacOptions() );
+    /// the same for a scene with depth: a fundamental matrix from at least 8 matches, psx_ransac_fundamental; its guide
+    /// restricts matchPairsGuided to the epipolar band
+    FundamentalEstimate estimateFundamental( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts = RansacOptions() );
 
     inline Feature*    getFeatures()    { return _ext; }
     inline Descriptor* getDescriptors() { return _ori; }
