@@ -361,6 +361,50 @@ int psx_pairs_join(const int* fwd_match, const float* fwd_dist, int l_len, const
 int psx_pairs_join_u8(const int* fwd_match, const int* fwd_dist, int l_len, const int* bwd_match, int r_len,
                       const psx_match_opts* opts, psx_match_pair_u8* pairs, int capacity, int* count);
 
+/* ---- one descriptor set against many (byte descriptors) --------------------------------------
+ * A view matched against dozens of others, a query against a shortlist, a frame against several keyframes: one left set
+ * against n_sets right sets in ONE call -- one synchronisation and a number of kernel launches that does not grow with
+ * n_sets, where a loop over psx_match_pairs_u8 pays both per set.  INTEGRATION.md ("One set against many") states the
+ * rule in words.  d_left: DEVICE pointer to l_len descriptors of 128 bytes; d_rights / r_lens: HOST arrays of n_sets
+ * entries, d_rights[k] a DEVICE pointer to r_lens[k] descriptors of 128 bytes.  Every device pointer is 16-byte aligned;
+ * the sets may be separate allocations, slices of one buffer, or the same pointer more than once.
+ * With P_k = the list psx_match_pairs_u8 returns for (L, R_k, opts) at unlimited capacity, bit for bit:
+ *   - the result is the concatenation P_0, P_1, ..., P_{n_sets-1}: sets ascending, `left` ascending within a set;
+ *   - `right` is the index WITHIN ITS SET;
+ *   - set_counts[k] = |P_k| (HOST array of n_sets ints), always the set's total: set k starts at the sum of the counts
+ *     before it;
+ *   - *count = the sum of the |P_k|; the first min(*count, capacity) records of the concatenation are written, nothing at
+ *     or past capacity; capacity = 0 with a NULL output asks "how many?".
+ * n_sets = 0, l_len = 0 or an empty set give zero counts and PSX_OK; no device is touched when no pair can exist.
+ * PSX_ERR_INVALID, with nothing touched and before any device call: everything psx_match_pairs_u8 refuses; n_sets < 0;
+ * d_rights, r_lens or set_counts NULL with n_sets > 0; a negative r_lens[k]; a NULL d_rights[k] with r_lens[k] > 0;
+ * n_sets * l_len or the sum of r_lens above INT_MAX.  Scratch (psx_match_release) and thread safety as for psx_match_u8.
+ * Synchronous, with exactly one stream synchronisation per call.  Only the byte form exists. */
+int psx_match_pairs_many_u8(int device, const unsigned char* d_left, int l_len,
+                            const unsigned char* const* d_rights, const int* r_lens, int n_sets,
+                            const psx_match_opts* opts, psx_match_pair_u8* host_pairs, int capacity,
+                            int* set_counts, int* count);
+/* the list stays in HBM: d_pairs is a DEVICE pointer, 16-byte aligned; set_counts and count are still HOST memory */
+int psx_match_pairs_many_u8_dev(int device, const unsigned char* d_left, int l_len,
+                                const unsigned char* const* d_rights, const int* r_lens, int n_sets,
+                                const psx_match_opts* opts, psx_match_pair_u8* d_pairs, int capacity,
+                                int* set_counts, int* count);
+
+/* How the one-to-many search cuts its sides, on the HOST: no device, no context (csrc/hip/match_many_plan.h, the
+ * function the library itself plans with -- for tests and for callers who want to see the launch shape).
+ * backward = 0: the forward direction -- `chunks` cut the n_sets right sets (set = k), `blocks` cut L (set = 0);
+ * backward = 1: the cross-check's direction -- `chunks` cut L (set = 0), `blocks` cut the right sets (set = k).
+ * A chunk is rows [r0, r1) of one set, r0 a multiple of 32 and r1 - r0 <= 512, a set's chunks ascending and contiguous;
+ * a block is rows [row0, row0 + 256) of one set, cut at the set's end.  Either table covers every row of every non-empty
+ * set exactly once; nothing spans two sets; empty sets contribute nothing.  *chunk_count / *block_count are always the
+ * totals; the first min(total, capacity) entries are written (capacity 0 with NULL: "how many?").  PSX_ERR_INVALID as
+ * above for the sets, for a NULL count, a negative capacity, a NULL table with a capacity, backward not 0 or 1. */
+typedef struct psx_many_chunk { int set, r0, r1; } psx_many_chunk;
+typedef struct psx_many_block { int set, row0; } psx_many_block;
+int psx_match_many_plan(int l_len, const int* r_lens, int n_sets, int backward,
+                        psx_many_chunk* chunks, int chunk_capacity, int* chunk_count,
+                        psx_many_block* blocks, int block_capacity, int* block_count);
+
 /* ---- guided matching ---------------------------------------------------------------------
  * The 2-NN search restricted by what the caller knows about where a match can lie (AliceVision's guidedMatching, a
  * stereo search window, a tracker's prediction; the reference has no counterpart): a homography -- identity H is a plain

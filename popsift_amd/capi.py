@@ -97,6 +97,7 @@ SYMBOLS = [
     "psx_set_mask", "psx_set_mask_dev", "psx_mask_keep",
     "psx_match_opts_default", "psx_match_pairs", "psx_match_pairs_u8", "psx_match_pairs_dev", "psx_match_pairs_u8_dev",
     "psx_pairs_join", "psx_pairs_join_u8",
+    "psx_match_pairs_many_u8", "psx_match_pairs_many_u8_dev", "psx_match_many_plan",
     "psx_guide_allows", "psx_desc_positions", "psx_match_guided", "psx_match_guided_u8",
     "psx_match_pairs_guided", "psx_match_pairs_guided_u8", "psx_match_pairs_guided_dev", "psx_match_pairs_guided_u8_dev",
     "psx_ransac_opts_default", "psx_ransac_samples", "psx_homography_fit", "psx_ransac_homography_ref",
@@ -231,6 +232,9 @@ def lib():
             getattr(L, n).argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(MatchOpts), vp, C.c_int, ip]
         for n in ("psx_pairs_join", "psx_pairs_join_u8"):
             getattr(L, n).argtypes = [vp, vp, C.c_int, vp, C.c_int, C.POINTER(MatchOpts), vp, C.c_int, ip]
+        for n in ("psx_match_pairs_many_u8", "psx_match_pairs_many_u8_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, C.c_int, vp, vp, C.c_int, C.POINTER(MatchOpts), vp, C.c_int, vp, ip]
+        L.psx_match_many_plan.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, ip, vp, C.c_int, ip]
         L.psx_guide_allows.argtypes = [C.POINTER(Guide), vp, C.c_int, vp, C.c_int, vp]
         L.psx_desc_positions.argtypes = [C.c_int, vp, vp, C.c_int, vp]
         for n in ("psx_match_guided", "psx_match_guided_u8"):
@@ -476,6 +480,75 @@ def match_pairs_dev(left_ptr, l_len, right_ptr, r_len, out_ptr, capacity, ratio=
     if rc != 0:
         raise PopSiftError("psx_match_pairs%s_dev failed (%d)" % ("_u8" if u8 else "", rc))
     return n.value
+
+
+def _many_call(fn, name, device, left_ptr, l_len, right_ptrs, r_lens, out_ptr, capacity, ratio, mutual):
+    """One one-to-many call on device pointers: (per-set counts (n_sets,) int32, total count)"""
+    k = len(r_lens)
+    ptrs = (C.c_void_p * max(k, 1))(*[p.value if isinstance(p, C.c_void_p) else p for p in right_ptrs])
+    lens = np.ascontiguousarray(r_lens, dtype=np.int32)
+    counts = np.full((k,), -1, np.int32)
+    n = C.c_int(-1)
+    o = match_opts(ratio, mutual)
+    rc = fn(device, left_ptr, l_len, ptrs if k else None, lens.ctypes.data_as(C.c_void_p) if k else None, k, C.byref(o),
+            out_ptr, capacity, counts.ctypes.data_as(C.c_void_p) if k else None, C.byref(n))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    return counts, n.value
+
+
+def split_sets(records, set_counts, capacity=None):
+    """The concatenated list of a one-to-many call as one array per set (a prefix sum of the counts); with a capacity
+    the sets behind it are cut as the call cut them."""
+    cap = len(records) if capacity is None else min(capacity, len(records))
+    ends = np.minimum(np.cumsum(np.asarray(set_counts, np.int64)), cap)
+    starts = np.concatenate([[0], ends[:-1]]) if len(ends) else ends
+    return [records[int(a):int(b)] for a, b in zip(starts, ends)]
+
+
+def match_pairs_many_u8(left, rights, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs_many_u8 on host arrays: left (n,128) uint8 against every (m_k,128) uint8 array of `rights` in ONE
+    call.  Returns (list of per-set PAIR_U8_DTYPE arrays -- set k's equals match_pairs_u8(left, rights[k]), `right`
+    indexing rights[k] -- , per-set counts); with a capacity the list holds the first `capacity` records of the
+    concatenation and the counts are still the totals."""
+    L = lib()
+    left = np.ascontiguousarray(left, dtype=np.uint8).reshape(-1, 128)
+    rights = [np.ascontiguousarray(r, dtype=np.uint8).reshape(-1, 128) for r in rights]
+    bufs = []
+    try:
+        ptrs = _to_device(L, device, [left] + rights, bufs)
+        cap = len(left) * len(rights) if capacity is None else capacity
+        out = np.zeros((cap,), PAIR_U8_DTYPE)
+        counts, n = _many_call(L.psx_match_pairs_many_u8, "psx_match_pairs_many_u8", device, ptrs[0], len(left), ptrs[1:],
+                               [len(r) for r in rights], out.ctypes.data_as(C.c_void_p) if cap else None, cap, ratio, mutual)
+        return split_sets(out[:min(n, cap)], counts), counts
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def match_pairs_many_dev(left_ptr, l_len, right_ptrs, r_lens, out_ptr, capacity, ratio=0.8, mutual=False, device=0):
+    """psx_match_pairs_many_u8_dev on DEVICE pointers (e.g. tensor.data_ptr()): the concatenated records go into the
+    caller's device buffer at out_ptr (16-byte aligned, `capacity` records); returns (per-set counts, total count)."""
+    return _many_call(lib().psx_match_pairs_many_u8_dev, "psx_match_pairs_many_u8_dev", device, C.c_void_p(left_ptr), l_len,
+                      list(right_ptrs), r_lens, C.c_void_p(out_ptr), capacity, ratio, mutual)
+
+
+def match_many_plan(l_len, r_lens, backward=False):
+    """psx_match_many_plan: (chunks (n,3) int32 = set, r0, r1; blocks (m,2) int32 = set, row0) of one direction.  No device."""
+    L = lib()
+    lens = np.ascontiguousarray(r_lens, dtype=np.int32)
+    nc, nb = C.c_int(-1), C.c_int(-1)
+    args = (l_len, lens.ctypes.data_as(C.c_void_p) if len(lens) else None, len(lens), 1 if backward else 0)
+    rc = L.psx_match_many_plan(*args, None, 0, C.byref(nc), None, 0, C.byref(nb))
+    if rc != 0:
+        raise PopSiftError("psx_match_many_plan failed (%d)" % rc)
+    chunks, blocks = np.zeros((nc.value, 3), np.int32), np.zeros((nb.value, 2), np.int32)
+    rc = L.psx_match_many_plan(*args, chunks.ctypes.data_as(C.c_void_p) if nc.value else None, nc.value, C.byref(nc),
+                               blocks.ctypes.data_as(C.c_void_p) if nb.value else None, nb.value, C.byref(nb))
+    if rc != 0:
+        raise PopSiftError("psx_match_many_plan failed (%d)" % rc)
+    return chunks, blocks
 
 
 def pairs_join(fwd_match, fwd_dist, bwd_match, r_len, ratio=0.8, mutual=False, capacity=None):

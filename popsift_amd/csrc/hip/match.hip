@@ -24,6 +24,7 @@
 #include "psx_internal.h"
 #include "match_join.h"
 #include "match_scratch.h"
+#include "match_u8_core.h"
 
 #include <climits>
 #include <cstdio>
@@ -730,12 +731,7 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
 // =====================================================================================================================
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int U8_TILE = 32;                  // right descriptors per MFMA tile
-constexpr int U8_CHUNK_MAX = 512;            // right descriptors per chunk: 9 index bits in the key
-constexpr unsigned U8_NONE = 0xffffffffu;    // empty key: larger than any real one (d << 9 | 511 < 2^32 - 1)
+// the key's constants (U8_*), u8_frag and key_insert: match_u8_core.h, shared with match_many.hip
 
 __global__ void k_quantize_desc(const float* __restrict__ src, size_t n4, unsigned* __restrict__ dst)
 {
@@ -769,18 +765,6 @@ __global__ void k_u8_norms(const unsigned char* __restrict__ src_a, int n_a, int
     }
     ss += __shfl_xor(ss, 4, 8); ss += __shfl_xor(ss, 2, 8); ss += __shfl_xor(ss, 1, 8);
     if (q == 0) norm[d] = ss;
-}
-
-__device__ __forceinline__ i32x4 u8_frag(const unsigned char* __restrict__ p)
-{
-    const uint4 v = *reinterpret_cast<const uint4*>(p);
-    return (i32x4){(int)(v.x ^ 0x80808080u), (int)(v.y ^ 0x80808080u), (int)(v.z ^ 0x80808080u), (int)(v.w ^ 0x80808080u)};
-}
-
-__device__ __forceinline__ void key_insert(unsigned& m1, unsigned& m2, unsigned k)
-{
-    m2 = min(m2, max(m1, k));                // m1 <= m2: the median of (m1, m2, k)
-    m1 = min(m1, k);
 }
 
 // grid (ceil(l_len / 256), nchunks), 256 threads: wave w owns left descriptors [256 bx + 64 w, + 64) as two B fragment sets

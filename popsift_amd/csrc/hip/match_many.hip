@@ -1,0 +1,483 @@
+// match_many.hip -- one byte descriptor set against many in one call: psx_match_pairs_many_u8 (+ _dev), psx_match_many_plan.
+//
+// psx_match_pairs_u8 (match.hip) is two directed passes of the exact i8-MFMA matcher and a join: per call a fixed launch
+// sequence, one synchronisation and one count read-back.  An image has 2k-4k descriptors: at that size the MFMA work is
+// microseconds and the call is launch latency and the synchronisation, paid again for every right set.  The byte matcher
+// already walks the right side in chunks of <= 512 rows that leave a per-left top-2 key each, merged in index order; the
+// (distance, index) order is total, so the result does not depend on where the chunks are cut.  "One left set against K
+// right sets" is that dataflow driven by tables in which no chunk crosses a set boundary (match_many_plan.h):
+//   k_u8_norms_many        |x - 128|^2 of every row of all K + 1 sets, padded per set as k_u8_norms pads
+//   k_match_u8_many        the tile loop of k_match_u8; its outer rows come from a block table, its inner rows from a chunk
+//                          table.  Forward: blocks of L x chunks of the K right sets; backward (PSX_PAIRS_MUTUAL only): blocks
+//                          of the K right sets x chunks of L -- the same kernel on the other pair of tables
+//   k_match_u8_many_merge  per (outer row, inner set) the chunks of that set in index order, strict '<': the directed layout
+//                          (3 ints, 2 distances per row) the join reads -- K results per left row forward, one per right row
+//                          backward
+//   k_many_count / k_many_scan / k_many_write   the join of match.hip, segmented: the rule of match_rule.h per (set, left)
+//                          with the gather into set k's backward rows; one total per workgroup in set-major order, an exclusive
+//                          scan of the totals by one workgroup (K x blocks totals: every workgroup summing all earlier ones, as
+//                          k_pairs_write does, would be quadratic), then one 16-byte store per survivor at its global rank.
+//                          No atomics: a record's slot is (offset of its workgroup) + (pairs of the waves before its own) +
+//                          (ballot bits below its lane).
+// Launches per call, whatever K is: the table copy, the norms, 2 per direction, 3 for the join -- 8 kernels with the
+// cross-check, 6 without; one stream synchronisation.  The per-chunk partials are the one buffer that grows with
+// (chunks x outer rows): above MANY_PARTIAL_BUDGET the sets are processed in groups of whole sets, each group its own
+// match + merge on the same stream (2 more launches per extra group, no synchronisation).
+#include "psx_internal.h"
+#include "match_join.h"
+#include "match_many_plan.h"
+#include "match_scratch.h"
+#include "match_u8_core.h"
+
+#include <climits>
+#include <cstring>
+#include <vector>
+
+namespace {
+
+constexpr size_t MANY_PARTIAL_BUDGET = (size_t)256 << 20;    // bytes of per-chunk partials one group of sets may take
+
+// one entry per set: 0 .. K-1 the right sets, K the left set
+struct ManySet {
+    const unsigned char* desc;   // the set's descriptors
+    int len;                     // rows
+    int noff;                    // first entry of its norms in the norm array (a multiple of U8_TILE: 16-byte aligned)
+    int roff;                    // its first row among the rows of its side (the right sets: prefix sum of the lengths; L: 0)
+    int c0, c1;                  // its chunks in the chunk table
+    int pad;
+};
+static_assert(sizeof(ManySet) == 32, "two 16-byte scalar loads per entry");
+
+// which part of the tables a launch walks, and where its rows lie in the partials
+struct ManyPass {
+    int nblocks, block_base;     // outer blocks [block_base, block_base + nblocks)
+    int chunk_base;              // the partials' first chunk
+    int row_base, outer_rows;    // the partials hold outer rows [row_base, row_base + outer_rows) of the outer side
+};
+
+__device__ __forceinline__ int many_pad(int n) { return ((n + U8_TILE - 1) / U8_TILE + 1) * U8_TILE; }
+
+// grid: every block of both sides, 256 threads, 8 lanes per descriptor (16 bytes each).  A set's norms are written up to a
+// multiple of U8_TILE plus one tile with zeros (the matcher reads whole tiles): the set's last block writes the padding.
+__global__ __launch_bounds__(256) void k_u8_norms_many(const ManySet* __restrict__ sets, const int2* __restrict__ blocks,
+                                                       int* __restrict__ norms)
+{
+    const int2 blk = blocks[blockIdx.x];
+    const ManySet s = sets[blk.x];
+    const int end = blk.y + PSX_MANY_BLOCK >= s.len ? many_pad(s.len) : blk.y + PSX_MANY_BLOCK;
+    const int q = threadIdx.x & 7;
+    for (int d = blk.y + (threadIdx.x >> 3); d < end; d += 32) {
+        int ss = 0;
+        if (d < s.len) {
+            const uint4 v = reinterpret_cast<const uint4*>(s.desc + (size_t)d * 128)[q];
+            const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+#pragma unroll
+                for (int b = 0; b < 4; b++) { const int x = (int)((w[k] >> (8 * b)) & 0xffu) - 128; ss += x * x; }
+        }
+        ss += __shfl_xor(ss, 4, 8); ss += __shfl_xor(ss, 2, 8); ss += __shfl_xor(ss, 1, 8);
+        if (q == 0) norms[s.noff + d] = ss;
+    }
+}
+
+// grid nblocks x (chunks of the launch), 256 threads; workgroup (ob, ch) = (blockIdx.x % nblocks, blockIdx.x / nblocks).
+// k_match_u8 with both sides taken from tables: wave w owns outer rows [row0 + 64 w, + 64) of ITS block's set as two B
+// fragment sets, and walks rows [r0, r1) of ITS chunk's set in tiles of 32.  The two table entries are read at
+// wave-uniform addresses (scalar loads).  Row reads are clamped to the set's own last row, idle outer columns repeat the
+// last row of their own set, keys of rows past the chunk's end are U8_NONE: nothing of a neighbouring set is ever ranked.
+// partial[ch * outer_rows + (row among the launch's outer rows)] = (smallest, second smallest key).
+__global__ __launch_bounds__(256) void k_match_u8_many(const ManySet* __restrict__ sets, const int4* __restrict__ chunks,
+                                                       const int2* __restrict__ blocks, const int* __restrict__ norms,
+                                                       ManyPass ps, uint2* __restrict__ partial)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = lane & 31, half = lane >> 5;
+    const int ob = (int)(blockIdx.x % (unsigned)ps.nblocks), ch = (int)(blockIdx.x / (unsigned)ps.nblocks);
+    const int2 blk = blocks[ps.block_base + ob];
+    const int4 chk = chunks[ps.chunk_base + ch];
+    const ManySet os = sets[blk.x], is = sets[chk.x];
+    const unsigned char* __restrict__ left = os.desc;
+    const unsigned char* __restrict__ right = is.desc;
+    const int* __restrict__ ln2 = norms + os.noff;
+    const int* __restrict__ rn2 = norms + is.noff;
+    const int l_len = os.len, r_len = is.len;
+    const int r0 = chk.y, r1 = chk.z;
+    i32x4 bfrag[2][4];
+    int nl[2], lidx[2];
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        const int li = blk.y + wave * 64 + c * 32 + col;
+        lidx[c] = li;
+        const int lq = min(li, l_len - 1);                  // idle columns repeat the last descriptor of their own set
+        const unsigned char* lp = left + (size_t)lq * 128 + half * 16;
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) bfrag[c][kk] = u8_frag(lp + kk * 32);
+        nl[c] = ln2[lq];
+    }
+    unsigned m1[2] = {U8_NONE, U8_NONE}, m2[2] = {U8_NONE, U8_NONE};
+    for (int base = r0; base < r1; base += U8_TILE) {
+        const unsigned char* rp = right + (size_t)min(base + col, r_len - 1) * 128 + half * 16;
+        i32x4 a[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) a[kk] = u8_frag(rp + kk * 32);
+        // this lane's 16 rows: base + 8 g + 4 half + e (the set's norms are padded by a tile of zeros)
+        int nr[16];
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const int4 v = *reinterpret_cast<const int4*>(rn2 + base + 8 * g + 4 * half);
+            nr[4 * g] = v.x; nr[4 * g + 1] = v.y; nr[4 * g + 2] = v.z; nr[4 * g + 3] = v.w;
+        }
+        i32x16 acc[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            acc[c] = (i32x16){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int kk = 0; kk < 4; kk++) acc[c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[kk], bfrag[c][kk], acc[c], 0, 0, 0);
+        }
+        const unsigned loc0 = (unsigned)(base - r0 + 4 * half);
+        const bool full = base + U8_TILE <= r1;             // wave uniform: only a chunk's last tile can be partial
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+#pragma unroll
+            for (int reg = 0; reg < 16; reg++) {
+                const int roff = 8 * (reg >> 2) + (reg & 3);
+                const unsigned d = (unsigned)(nl[c] + nr[reg] - 2 * acc[c][reg]);
+                unsigned key = (d << 9) | (loc0 + (unsigned)roff);
+                if (!full && base + 4 * half + roff >= r1) key = U8_NONE;
+                key_insert(m1[c], m2[c], key);
+            }
+        }
+    }
+    const size_t prow = (size_t)ch * ps.outer_rows + (size_t)(os.roff - ps.row_base);
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        const unsigned o1 = __shfl_xor(m1[c], 32), o2 = __shfl_xor(m2[c], 32);
+        key_insert(m1[c], m2[c], o1);
+        key_insert(m1[c], m2[c], o2);
+        if (half == 0 && lidx[c] < l_len) partial[prow + lidx[c]] = make_uint2(m1[c], m2[c]);
+    }
+}
+
+// grid nblocks x ngroups, 256 threads: one thread per (outer row of block ob, inner set group_base + g).  The set's chunks
+// in table order = index order; a chunk's two keys are in (distance, index) order, so strict '<' on the distance reproduces
+// the sequential scan (k_match_u8_merge).  The result goes where the join expects the directed result of (outer set, inner
+// set): out + out_stride * (inner set) + 5 * (outer set's first row), 3 len ints (best, second, accept) then 2 len distances.
+// out_stride = 5 l_len forward (K results per left row), 0 backward (the one inner set is L).
+__global__ __launch_bounds__(256) void k_match_u8_many_merge(const ManySet* __restrict__ sets, const int4* __restrict__ chunks,
+                                                             const int2* __restrict__ blocks, ManyPass ps, int group_base,
+                                                             size_t out_stride, const uint2* __restrict__ partial, int* __restrict__ out)
+{
+    const int ob = (int)(blockIdx.x % (unsigned)ps.nblocks), g = group_base + (int)(blockIdx.x / (unsigned)ps.nblocks);
+    const int2 blk = blocks[ps.block_base + ob];
+    const ManySet os = sets[blk.x], is = sets[g];
+    const int row = blk.y + (int)threadIdx.x;
+    if (row >= os.len) return;
+    const size_t prow = (size_t)(os.roff - ps.row_base) + row;
+    int d1 = INT_MAX, d2 = INT_MAX, i1 = 0, i2 = 0;
+    for (int c = is.c0; c < is.c1; c++) {
+        const uint2 p = partial[(size_t)(c - ps.chunk_base) * ps.outer_rows + prow];
+        const int r0 = chunks[c].y;
+        const unsigned k[2] = {p.x, p.y};
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            if (k[e] == U8_NONE) continue;
+            const int d = (int)(k[e] >> 9), i = r0 + (int)(k[e] & 511u);
+            if (d < d1) { d2 = d1; i2 = i1; d1 = d; i1 = i; }
+            else if (d < d2) { d2 = d; i2 = i; }
+        }
+    }
+    // IEEE division (no v_rcp): the integers are exact in float; a missing neighbour is +inf, as in psx_match
+    const float f1 = d1 == INT_MAX ? INFINITY : (float)d1, f2 = d2 == INT_MAX ? INFINITY : (float)d2;
+    const bool accept = (f1 / f2 < 0.8f);
+    int* o = out + out_stride * (size_t)g + 5 * (size_t)os.roff;
+    o[3 * (size_t)row + 0] = i1; o[3 * (size_t)row + 1] = i2; o[3 * (size_t)row + 2] = accept ? 1 : 0;
+    o[3 * (size_t)os.len + 2 * (size_t)row + 0] = d1; o[3 * (size_t)os.len + 2 * (size_t)row + 1] = d2;
+}
+
+__device__ __forceinline__ int many_lane_rank(unsigned long long m)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+// The rule of match_rule.h for left row i against set k: fwd holds K directed results of 5 l_len ints each, bwd the K sets'
+// backward results at 5 * (the set's first row).  An empty set has no pairs (and no results: nothing of it is read).
+__device__ __forceinline__ bool many_rule(const ManySet* __restrict__ sets, const int* __restrict__ fwd, int l_len,
+                                          const int* __restrict__ bwd, int k, int i, float ratio, int mutual, int4& rec)
+{
+    const ManySet s = sets[k];
+    if (i >= l_len || s.len == 0) return false;
+    const int* f = fwd + 5 * (size_t)l_len * k;
+    const int j = f[3 * (size_t)i];
+    const int d1 = f[3 * (size_t)l_len + 2 * (size_t)i], d2 = f[3 * (size_t)l_len + 2 * (size_t)i + 1];
+    bool keep = psx_match_keep(psx_match_dist(d1), psx_match_dist(d2), ratio);
+    if (keep && mutual) keep = bwd[5 * (size_t)s.roff + 3 * (size_t)j] == i;
+    rec = make_int4(i, j, d1, d2);
+    return keep;
+}
+
+// grid K * nb (nb = blocks of 256 left rows), workgroup k * nb + b: set-major, so the offsets are the concatenation's
+__global__ __launch_bounds__(256) void k_many_count(const ManySet* __restrict__ sets, const int* __restrict__ fwd, int l_len,
+                                                    const int* __restrict__ bwd, int nb, float ratio, int mutual,
+                                                    int* __restrict__ wg_tot)
+{
+    const int k = (int)(blockIdx.x / (unsigned)nb), b = (int)(blockIdx.x % (unsigned)nb);
+    int4 rec;
+    const bool keep = many_rule(sets, fwd, l_len, bwd, k, b * 256 + (int)threadIdx.x, ratio, mutual, rec);
+    const unsigned long long m = __ballot(keep);
+    __shared__ int s_cnt[4];
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) wg_tot[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// ONE workgroup of 1024 threads: offs[w] = the totals before workgroup w, offs[n] = all of them.  1024 totals per round:
+// a wave scan (shuffles), the 16 wave sums through LDS, the carry of the rounds before.
+__global__ __launch_bounds__(1024) void k_many_scan(const int* __restrict__ wg_tot, int n, int* __restrict__ offs)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int s_wave[16];
+    int carry = 0;
+    for (int base = 0; base < n; base += 1024) {
+        const int w = base + (int)threadIdx.x;
+        const int v = w < n ? wg_tot[w] : 0;
+        int incl = v;
+#pragma unroll
+        for (int k = 1; k < 64; k <<= 1) { const int o = __shfl_up(incl, k); if (lane >= k) incl += o; }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int before = 0, all = 0;
+#pragma unroll
+        for (int q = 0; q < 16; q++) { const int t = s_wave[q]; all += t; if (q < wave) before += t; }
+        if (w < n) offs[w] = carry + before + incl - v;
+        carry += all;
+        __syncthreads();                                     // s_wave is rewritten in the next round
+    }
+    if (threadIdx.x == 0) offs[n] = carry;
+}
+
+// grid as k_many_count.  Evaluates the rule again (k_pairs_write: cheaper than parking the verdicts), ranks its lanes and
+// writes each surviving record with ONE 16-byte store at offs[workgroup] + rank, never at or past capacity; a set's first
+// workgroup writes the set's count, workgroup 0 the total.
+__global__ __launch_bounds__(256) void k_many_write(const ManySet* __restrict__ sets, const int* __restrict__ fwd, int l_len,
+                                                    const int* __restrict__ bwd, int nb, float ratio, int mutual,
+                                                    const int* __restrict__ offs, int4* __restrict__ out, int capacity,
+                                                    int* __restrict__ set_counts, int* __restrict__ total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k = (int)(blockIdx.x / (unsigned)nb), b = (int)(blockIdx.x % (unsigned)nb);
+    int4 rec = make_int4(0, 0, 0, 0);
+    const bool keep = many_rule(sets, fwd, l_len, bwd, k, b * 256 + (int)threadIdx.x, ratio, mutual, rec);
+    const unsigned long long m = __ballot(keep);
+    __shared__ int s_cnt[4];
+    if (lane == 0) s_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int woff = 0;
+    for (int w = 0; w < wave; w++) woff += s_cnt[w];
+    const int pos = offs[blockIdx.x] + woff + many_lane_rank(m);
+    if (keep && pos < capacity) out[pos] = rec;
+    if (threadIdx.x == 0) {
+        if (b == 0) set_counts[k] = offs[(size_t)(k + 1) * nb] - offs[(size_t)k * nb];
+        if (blockIdx.x == 0) *total = offs[gridDim.x];
+    }
+}
+
+// a run of whole sets whose partials fit the budget: what one match + merge pair of launches takes
+struct ManyGroup { int block0, nblocks, chunk0, nchunks, set0, nsets, row0, rows; };
+
+size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// host_pairs or d_pairs (the other is NULL; both NULL with capacity 0)
+int match_pairs_many(int device, const unsigned char* d_left, int l_len, const unsigned char* const* d_rights, const int* r_lens,
+                     int n_sets, const psx_match_opts* opts, void* host_pairs, void* d_pairs, int capacity, int* set_counts, int* count)
+{
+    if (!psx_pairs_args_ok(l_len, 0, opts, host_pairs ? host_pairs : d_pairs, capacity, count) || (l_len > 0 && !d_left) ||
+        n_sets < 0 || (n_sets > 0 && (!d_rights || !r_lens || !set_counts)) || !psx_many_sets_ok(l_len, r_lens, n_sets))
+        return PSX_ERR_INVALID;
+    long long r_total = 0;
+    for (int k = 0; k < n_sets; k++) {
+        if (r_lens[k] > 0 && !d_rights[k]) return PSX_ERR_INVALID;
+        r_total += r_lens[k];
+    }
+    if (l_len == 0 || r_total == 0) {
+        for (int k = 0; k < n_sets; k++) set_counts[k] = 0;
+        *count = 0;
+        return PSX_OK;
+    }
+    const bool mutual = (opts->flags & PSX_PAIRS_MUTUAL) != 0;
+    const int K = n_sets;
+
+    // ---- the plan: blocks and chunks of both sides (match_many_plan.h), on the host ----
+    thread_local std::vector<psx_many_block> rblk, lblk;
+    thread_local std::vector<psx_many_chunk> rchk, lchk;
+    const long long BR = psx_many_blocks(r_lens, K, nullptr, 0), BL = psx_many_blocks(&l_len, 1, nullptr, 0);
+    const long long CR = psx_many_chunks(r_lens, K, BL, nullptr, 0);
+    const long long CL = mutual ? psx_many_chunks(&l_len, 1, BR, nullptr, 0) : 0;
+    const long long nb = BL, ntot = (long long)K * nb;               // the join's workgroups
+    if (ntot + 1 > INT_MAX) return PSX_ERR_NOMEM;
+    rblk.resize((size_t)BR); lblk.resize((size_t)BL); rchk.resize((size_t)CR); lchk.resize((size_t)CL);
+    psx_many_blocks(r_lens, K, rblk.data(), BR);
+    psx_many_blocks(&l_len, 1, lblk.data(), BL);
+    psx_many_chunks(r_lens, K, BL, rchk.data(), CR);
+    if (mutual) psx_many_chunks(&l_len, 1, BR, lchk.data(), CL);
+
+    // groups of whole sets within the partials' budget: forward over the right sets' chunks, backward over their blocks
+    std::vector<ManyGroup> fgroups, bgroups;
+    size_t partial_bytes = 0;
+    for (long long c = 0; c < CR;) {
+        ManyGroup g = {(int)BR, (int)BL, (int)c, 0, rchk[(size_t)c].set, 0, 0, l_len};
+        while (c < CR) {
+            long long e = c;                                         // the end of the next set's chunks
+            while (e < CR && rchk[(size_t)e].set == rchk[(size_t)c].set) e++;
+            if (g.nchunks > 0 && sizeof(uint2) * (size_t)(e - g.chunk0) * l_len > MANY_PARTIAL_BUDGET) break;
+            g.nchunks = (int)(e - g.chunk0);
+            g.nsets = rchk[(size_t)e - 1].set + 1 - g.set0;
+            c = e;
+        }
+        if ((long long)g.nblocks * g.nchunks > INT_MAX || (long long)g.nblocks * g.nsets > INT_MAX) return PSX_ERR_NOMEM;
+        const size_t b = sizeof(uint2) * (size_t)g.nchunks * l_len;
+        if (b > partial_bytes) partial_bytes = b;
+        fgroups.push_back(g);
+    }
+    std::vector<long long> roff((size_t)K + 1, 0);
+    for (int k = 0; k < K; k++) roff[(size_t)k + 1] = roff[(size_t)k] + r_lens[k];
+    if (mutual)
+        for (long long b = 0; b < BR;) {
+            const int s0 = rblk[(size_t)b].set;
+            ManyGroup g = {(int)b, 0, (int)CR, (int)CL, s0, 0, (int)roff[(size_t)s0], 0};
+            while (b < BR) {
+                long long e = b;
+                while (e < BR && rblk[(size_t)e].set == rblk[(size_t)b].set) e++;
+                const int s = rblk[(size_t)b].set;
+                const long long rows = roff[(size_t)s + 1] - g.row0;
+                if (g.nblocks > 0 && sizeof(uint2) * (size_t)CL * (size_t)rows > MANY_PARTIAL_BUDGET) break;
+                g.nblocks = (int)(e - g.block0);
+                g.nsets = s + 1 - g.set0;
+                g.rows = (int)rows;
+                b = e;
+            }
+            if ((long long)g.nblocks * g.nchunks > INT_MAX) return PSX_ERR_NOMEM;
+            const size_t bytes = sizeof(uint2) * (size_t)g.nchunks * (size_t)g.rows;
+            if (bytes > partial_bytes) partial_bytes = bytes;
+            bgroups.push_back(g);
+        }
+
+    // ---- sizes: the norms of all sets, the tables, the results ----
+    long long npad = 0;
+    for (int k = 0; k < K; k++) npad += r_lens[k] > 0 ? ((long long)(r_lens[k] + U8_TILE - 1) / U8_TILE + 1) * U8_TILE : 0;
+    const long long l_noff = npad;
+    npad += ((long long)(l_len + U8_TILE - 1) / U8_TILE + 1) * U8_TILE;
+    if (npad > INT_MAX) return PSX_ERR_NOMEM;
+    const size_t sets_b = pad16(sizeof(ManySet) * ((size_t)K + 1));
+    const size_t chunks_b = pad16(sizeof(int4) * (size_t)(CR + CL));
+    const size_t blocks_b = pad16(sizeof(int2) * (size_t)(BR + BL));
+    const size_t blob_b = sets_b + chunks_b + blocks_b;
+    const long long all_pairs = (long long)K * l_len;                 // at most l_len pairs per set exist
+    const size_t nrec = host_pairs ? (size_t)(capacity < all_pairs ? capacity : all_pairs) : 0;
+    const size_t off_counts = 16, off_rec = off_counts + pad16(sizeof(int) * (size_t)K), off_blob = off_rec + 16 * nrec;
+
+    if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
+    MatchScratch& sc = psx_match_scratch();
+    if (!sc.bind(device)) return PSX_ERR_HIP;
+    // every buffer before the first launch: nothing is reallocated under queued work
+    if (!sc.need(25, blob_b) || !sc.need(26, sizeof(int) * (size_t)npad) || !sc.need(27, partial_bytes) ||
+        !sc.need(28, sizeof(int) * 5 * (size_t)all_pairs) || (mutual && !sc.need(29, sizeof(int) * 5 * (size_t)r_total)) ||
+        !sc.need(30, sizeof(int) * (2 * (size_t)ntot + 1)) || !sc.need_pinned(off_blob + blob_b))
+        return PSX_ERR_NOMEM;
+    void* dev_pin = nullptr;
+    if (hipHostGetDevicePointer(&dev_pin, sc.hpin, 0) != hipSuccess || dev_pin == nullptr) return PSX_ERR_HIP;
+    char* hp = static_cast<char*>(sc.hpin);
+
+    // ---- the tables, written into the pinned staging buffer and copied on the stream ----
+    {
+        ManySet* hs = reinterpret_cast<ManySet*>(hp + off_blob);
+        int4* hc = reinterpret_cast<int4*>(hp + off_blob + sets_b);
+        int2* hb = reinterpret_cast<int2*>(hp + off_blob + sets_b + chunks_b);
+        long long noff = 0;
+        for (int k = 0; k < K; k++) {
+            hs[k] = ManySet{d_rights[k], r_lens[k], (int)noff, (int)roff[(size_t)k], 0, 0, 0};
+            noff += r_lens[k] > 0 ? ((long long)(r_lens[k] + U8_TILE - 1) / U8_TILE + 1) * U8_TILE : 0;
+        }
+        hs[K] = ManySet{d_left, l_len, (int)l_noff, 0, (int)CR, (int)(CR + CL), 0};
+        for (long long c = 0; c < CR; c++) {
+            const psx_many_chunk& q = rchk[(size_t)c];
+            hc[c] = make_int4(q.set, q.r0, q.r1, 0);
+            if (hs[q.set].c1 == 0) hs[q.set].c0 = (int)c;            // a set's chunks are contiguous: first and last + 1
+            hs[q.set].c1 = (int)c + 1;
+        }
+        for (long long c = 0; c < CL; c++) hc[CR + c] = make_int4(K, lchk[(size_t)c].r0, lchk[(size_t)c].r1, 0);
+        for (long long b = 0; b < BR; b++) hb[b] = make_int2(rblk[(size_t)b].set, rblk[(size_t)b].row0);
+        for (long long b = 0; b < BL; b++) hb[BR + b] = make_int2(K, lblk[(size_t)b].row0);
+    }
+    int* h_total = reinterpret_cast<int*>(hp);
+    *h_total = -1;
+    const ManySet* d_sets = static_cast<const ManySet*>(sc.buf[25]);
+    const int4* d_chunks = reinterpret_cast<const int4*>(static_cast<const char*>(sc.buf[25]) + sets_b);
+    const int2* d_blocks = reinterpret_cast<const int2*>(static_cast<const char*>(sc.buf[25]) + sets_b + chunks_b);
+    int* d_norms = static_cast<int*>(sc.buf[26]);
+    uint2* d_partial = static_cast<uint2*>(sc.buf[27]);
+    int* d_fwd = static_cast<int*>(sc.buf[28]);
+    int* d_bwd = mutual ? static_cast<int*>(sc.buf[29]) : nullptr;
+    int* d_tot = static_cast<int*>(sc.buf[30]);
+    int* d_offs = d_tot + ntot;
+    int* d_total = static_cast<int*>(dev_pin);
+    int* d_counts = reinterpret_cast<int*>(static_cast<char*>(dev_pin) + off_counts);
+    // the kernel's capacity for the host form is the staging buffer's (nrec <= capacity)
+    int4* out = host_pairs ? reinterpret_cast<int4*>(static_cast<char*>(dev_pin) + off_rec) : static_cast<int4*>(d_pairs);
+    const int cap = host_pairs ? (int)nrec : capacity;
+    hipStream_t st = sc.stream;
+
+    if (hipMemcpyAsync(sc.buf[25], hp + off_blob, blob_b, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
+    hipLaunchKernelGGL(k_u8_norms_many, dim3((unsigned)(BR + BL)), dim3(256), 0, st, d_sets, d_blocks, d_norms);
+    for (const ManyGroup& g : fgroups) {
+        const ManyPass ps = {g.nblocks, g.block0, g.chunk0, g.row0, g.rows};
+        hipLaunchKernelGGL(k_match_u8_many, dim3((unsigned)g.nblocks * (unsigned)g.nchunks), dim3(256), 0, st, d_sets, d_chunks, d_blocks,
+                           d_norms, ps, d_partial);
+        hipLaunchKernelGGL(k_match_u8_many_merge, dim3((unsigned)g.nblocks * (unsigned)g.nsets), dim3(256), 0, st, d_sets, d_chunks,
+                           d_blocks, ps, g.set0, 5 * (size_t)l_len, d_partial, d_fwd);
+    }
+    for (const ManyGroup& g : bgroups) {
+        const ManyPass ps = {g.nblocks, g.block0, g.chunk0, g.row0, g.rows};
+        hipLaunchKernelGGL(k_match_u8_many, dim3((unsigned)g.nblocks * (unsigned)g.nchunks), dim3(256), 0, st, d_sets, d_chunks, d_blocks,
+                           d_norms, ps, d_partial);
+        hipLaunchKernelGGL(k_match_u8_many_merge, dim3((unsigned)g.nblocks), dim3(256), 0, st, d_sets, d_chunks, d_blocks, ps, K,
+                           (size_t)0, d_partial, d_bwd);
+    }
+    const int mflag = mutual ? 1 : 0;
+    hipLaunchKernelGGL(k_many_count, dim3((unsigned)ntot), dim3(256), 0, st, d_sets, d_fwd, l_len, d_bwd, (int)nb, opts->ratio, mflag, d_tot);
+    hipLaunchKernelGGL(k_many_scan, dim3(1), dim3(1024), 0, st, d_tot, (int)ntot, d_offs);
+    hipLaunchKernelGGL(k_many_write, dim3((unsigned)ntot), dim3(256), 0, st, d_sets, d_fwd, l_len, d_bwd, (int)nb, opts->ratio, mflag,
+                       d_offs, out, cap, d_counts, d_total);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return PSX_ERR_HIP;
+    const int n = *h_total;
+    if (n < 0 || n > all_pairs) return PSX_ERR_HIP;
+    memcpy(set_counts, hp + off_counts, sizeof(int) * (size_t)K);
+    if (host_pairs && n > 0 && nrec > 0) memcpy(host_pairs, hp + off_rec, 16 * ((size_t)n < nrec ? (size_t)n : nrec));
+    *count = n;
+    return PSX_OK;
+}
+
+} // namespace
+
+extern "C" int psx_match_pairs_many_u8(int device, const unsigned char* d_left, int l_len,
+                                       const unsigned char* const* d_rights, const int* r_lens, int n_sets,
+                                       const psx_match_opts* opts, psx_match_pair_u8* host_pairs, int capacity,
+                                       int* set_counts, int* count)
+{
+    return match_pairs_many(device, d_left, l_len, d_rights, r_lens, n_sets, opts, host_pairs, nullptr, capacity, set_counts, count);
+}
+
+extern "C" int psx_match_pairs_many_u8_dev(int device, const unsigned char* d_left, int l_len,
+                                           const unsigned char* const* d_rights, const int* r_lens, int n_sets,
+                                           const psx_match_opts* opts, psx_match_pair_u8* d_pairs, int capacity,
+                                           int* set_counts, int* count)
+{
+    return match_pairs_many(device, d_left, l_len, d_rights, r_lens, n_sets, opts, nullptr, d_pairs, capacity, set_counts, count);
+}
+
+extern "C" int psx_match_many_plan(int l_len, const int* r_lens, int n_sets, int backward,
+                                   psx_many_chunk* chunks, int chunk_capacity, int* chunk_count,
+                                   psx_many_block* blocks, int block_capacity, int* block_count)
+{
+    return psx_many_plan_host(l_len, r_lens, n_sets, backward, chunks, chunk_capacity, chunk_count, blocks, block_capacity, block_count);
+}

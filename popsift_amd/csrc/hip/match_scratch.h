@@ -11,8 +11,10 @@ struct MatchScratch {
     // 14 those of psx_match_pairs_u8, 15 the join's per-workgroup totals; guided matching (match_guided.hip): 16 the forward
     // direction's results, 17 the backward direction's, 18 the left side's lines for the backward direction; the homography
     // RANSAC (ransac.hip): 19 the uploaded pair records, 20 the packed correspondences, 21 the hypotheses' models, 22 their
-    // counts, 23 the state block, 24 the compaction's per-workgroup totals
-    static constexpr int NBUF = 25;
+    // counts, 23 the state block, 24 the compaction's per-workgroup totals; the one-to-many byte pair search
+    // (match_many.hip): 25 the set / chunk / block tables, 26 the norms of all sets, 27 the per-chunk partials, 28 the forward
+    // direction's results of all sets, 29 the backward direction's, 30 the join's per-workgroup totals and their offsets
+    static constexpr int NBUF = 31;
     int device = -1;
     hipStream_t stream = nullptr;
     void* buf[NBUF] = {};

@@ -601,6 +601,78 @@ std::vector<Match> FeaturesDev::matchPairsGuided( FeaturesDev* other, const Matc
                              other->_ext, other->_ori, other->_rev, other->getDescriptorCount(), &guide, opts );
 }
 
+// FeaturesDev::matchPairsMany: psx_match_pairs_many_u8 on this object's bytes and every other object's -- each side
+// quantised once, ONE matching call for all of them; the concatenated list is cut at the per-set counts and mapped through
+// the reverse maps as matchPairs does
+std::vector<std::vector<Match>> FeaturesDev::matchPairsMany( const std::vector<FeaturesDev*>& others, const MatchOptions& opts )
+{
+    const char* who = "FeaturesDev::matchPairsMany";
+    for( FeaturesDev* o : others ) {
+        if( o == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
+        if( o->_device != _device ) {
+            std::ostringstream ss;
+            ss << who << ": the objects live on different devices (" << _device << " and " << o->_device << ")";
+            fatal( __FILE__, __LINE__, ss.str() );
+        }
+    }
+    if( !opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": the one-to-many form is byte-only (set MatchOptions::bytes)" );
+    const int K = (int)others.size();
+    const int l_len = getDescriptorCount();
+    std::vector<std::vector<Match>> out( others.size() );
+    bool any = false;
+    for( FeaturesDev* o : others ) any = any || o->getDescriptorCount() > 0;
+    if( l_len <= 0 || !any ) return out;
+    psx_match_opts po;
+    po.ratio = opts.ratio;
+    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
+    std::vector<void*> bufs( (size_t)K + 1, nullptr );
+    std::vector<const unsigned char*> ptrs( K, nullptr );
+    std::vector<int> lens( K, 0 ), counts( K, 0 );
+    int rc = psx_dev_alloc( _device, (size_t)l_len * 128, &bufs[K] );
+    if( rc == PSX_OK ) rc = psx_quantize_desc( _device, (const float*)_ori, l_len, (unsigned char*)bufs[K] );
+    for( int k = 0; k < K && rc == PSX_OK; k++ ) {
+        const int r_len = others[k]->getDescriptorCount();
+        if( r_len <= 0 ) continue;
+        lens[k] = r_len;
+        rc = psx_dev_alloc( _device, (size_t)r_len * 128, &bufs[k] );
+        if( rc == PSX_OK ) rc = psx_quantize_desc( _device, (const float*)others[k]->_ori, r_len, (unsigned char*)bufs[k] );
+        ptrs[k] = (const unsigned char*)bufs[k];
+    }
+    // at most l_len pairs per set exist (a product above INT_MAX is the call's to refuse)
+    const long long room = (long long)K * l_len;
+    std::vector<psx_match_pair_u8> pb( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
+    int count = 0;
+    if( rc == PSX_OK )
+        rc = psx_match_pairs_many_u8( _device, (const unsigned char*)bufs[K], l_len, ptrs.data(), lens.data(), K, &po,
+                                      pb.data(), (int)pb.size(), counts.data(), &count );
+    for( void* b : bufs ) psx_dev_free( _device, b );
+    if( rc != PSX_OK ) {
+        std::ostringstream ss;
+        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    std::vector<int> l_fem( l_len );
+    if( psx_dev_read( _device, l_fem.data(), _rev, (size_t)l_len * sizeof(int) ) != PSX_OK )
+        fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
+    size_t at = 0;
+    for( int k = 0; k < K; k++ ) {
+        if( counts[k] <= 0 ) continue;
+        std::vector<int> r_fem( lens[k] );
+        if( psx_dev_read( _device, r_fem.data(), others[k]->_rev, (size_t)lens[k] * sizeof(int) ) != PSX_OK )
+            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
+        out[k].resize( counts[k] );
+        for( int q = 0; q < counts[k]; q++, at++ ) {
+            Match& m = out[k][q];
+            m.left_descriptor = pb[at].left; m.right_descriptor = pb[at].right;
+            m.distance        = pb[at].d1 == INT32_MAX ? INFINITY : (float)pb[at].d1;
+            m.second_distance = pb[at].d2 == INT32_MAX ? INFINITY : (float)pb[at].d2;
+            m.left_feature  = l_fem[m.left_descriptor];
+            m.right_feature = r_fem[m.right_descriptor];
+        }
+    }
+    return out;
+}
+
 HomographyEstimate FeaturesDev::estimateHomography( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts )
 {
     return estimate( "FeaturesDev::estimateHomography", false, other, matches, opts );

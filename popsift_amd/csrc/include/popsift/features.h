@@ -201,6 +201,11 @@ public:
     /// features the descriptors belong to (psx_desc_positions on each object's own arrays).  Throws as matchPairs,
     /// and for an invalid guide.
     std::vector<Match> matchPairsGuided( FeaturesDev* other, const MatchGuide& guide, const MatchOptions& opts = MatchOptions() );
+    /// matchPairs against many objects in ONE device call (psx_match_pairs_many_u8: one synchronisation, a number of
+    /// launches that does not grow with others.size()): element k equals matchPairs( others[k], opts ).  Byte
+    /// descriptors only -- every side is quantised once on the device, as matchPairs does with MatchOptions::bytes.
+    /// Throws as matchPairs for a null entry or an object on another device, and for opts.bytes == false.
+    std::vector<std::vector<Match>> matchPairsMany( const std::vector<FeaturesDev*>& others, const MatchOptions& opts );
     /// geometric verification: a homography (this = left -> other = right) estimated from `matches` (what matchPairs
     /// returned for the same two objects) by RANSAC on the device, psx_ransac_homography.  Throws as matchPairs, and for
     /// invalid options or a descriptor index outside its object.
