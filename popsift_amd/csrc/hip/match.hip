@@ -21,10 +21,13 @@
 // No LDS, no shuffles.  The right side is split into chunks so that ~18k x 18k descriptors fill the chip;
 // k_match_merge combines the per-chunk top-2 with the (distance, index) order that the sequential scan
 // of the reference produces.
+// Further down: the exact byte matcher for one pair of sets (its device pieces: match_u8_core.h, shared with match_many.hip)
+// and the pair join (its compaction: wg_compact.h); the directed result's layout and the scratch buffers: match_scratch.h.
 #include "psx_internal.h"
 #include "match_join.h"
 #include "match_scratch.h"
 #include "match_u8_core.h"
+#include "wg_compact.h"
 
 #include <climits>
 #include <cstdio>
@@ -110,9 +113,9 @@ __global__ __launch_bounds__(64) void k_match_partial(const float* __restrict__ 
     if (li < l_len) partial[(size_t)blockIdx.y * l_len + li] = t;
 }
 
-// out[3*l + 0..2] = (best, second, accept) (int3 match_matrix, features.cu:218-222), dist[2*l + 0..1]
-__global__ void k_match_merge(const Top2* __restrict__ partial, int l_len, int nchunks, int r_len,
-                              int* __restrict__ out, float* __restrict__ dist)
+// out: the directed result of match_scratch.h -- (best, second, accept) is the reference's int3 match_matrix
+// (features.cu:218-222)
+__global__ void k_match_merge(const Top2* __restrict__ partial, int l_len, int nchunks, int r_len, int* __restrict__ out)
 {
     const int li = blockIdx.x * blockDim.x + threadIdx.x;
     if (li >= l_len) return;
@@ -121,16 +124,11 @@ __global__ void k_match_merge(const Top2* __restrict__ partial, int l_len, int n
     // order, so strict '<' insertion reproduces the sequential scan: ties keep the smaller index
     for (int c = 0; c < nchunks; c++) {
         const Top2 p = partial[(size_t)c * l_len + li];
-        if (p.d1 < t.d1) { t.d2 = t.d1; t.i2 = t.i1; t.d1 = p.d1; t.i1 = p.i1; }
-        else if (p.d1 < t.d2) { t.d2 = p.d1; t.i2 = p.i1; }
-        if (p.d2 < t.d1) { t.d2 = t.d1; t.i2 = t.i1; t.d1 = p.d2; t.i1 = p.i2; }
-        else if (p.d2 < t.d2) { t.d2 = p.d2; t.i2 = p.i2; }
+        top2_insert(t, p.d1, p.i1);
+        top2_insert(t, p.d2, p.i2);
     }
-    const bool accept = (t.d1 / t.d2 < 0.8f);
-    out[3 * li + 0] = t.i1; out[3 * li + 1] = t.i2; out[3 * li + 2] = accept ? 1 : 0;
-    if (dist) { dist[2 * li + 0] = t.d1; dist[2 * li + 1] = t.d2; }
+    psx_directed_store<float>(out, l_len, li, t.i1, t.i2, t.d1 / t.d2 < 0.8f, t.d1, t.d2);
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // MFMA prefilter (round 5).  The exact scan above costs 165 lane instructions per pair and runs at ~1/3 of the VALU issue
@@ -541,7 +539,7 @@ namespace {
 thread_local MatchScratch t_scratch;
 } // namespace
 
-// frees the calling thread's matcher scratch (stream + up to 19 device buffers); an explicit user call -- PopSift::uninit
+// frees the calling thread's matcher scratch (its stream and every device buffer); an explicit user call -- PopSift::uninit
 // does NOT call it: the scratch belongs to the thread, not to one PopSift object (another replica may be using it)
 extern "C" int psx_match_release(void)
 {
@@ -553,7 +551,7 @@ extern "C" int psx_match_release(void)
 // and the prefilter's flag in sc.buf[ob], in this order.  to_host: the same bytes are in sc.hpin on return (psx_match);
 // otherwise only the flag crosses (the pair search joins on the device).  Synchronised on return either way: the
 // prefilter's flag is read here, and the exact scan of every pair follows when it is up.
-static int match_f32_run(MatchScratch& sc, const float* d_left, int l_len, const float* d_right, int r_len, int ob, bool to_host)
+static int match_f32_run(MatchScratch& sc, const float* d_left, int l_len, const float* d_right, int r_len, MatchSlot ob, bool to_host)
 {
     // enough (left group, chunk) waves to fill the chip: 256 CUs x 4 SIMDs x 2 waves
     const int lgroups = (l_len + 63) / 64;
@@ -563,12 +561,12 @@ static int match_f32_run(MatchScratch& sc, const float* d_left, int l_len, const
     const int chunk_len = r_len > 0 ? (r_len + nchunks - 1) / nchunks : 1;
     if (r_len > 0) nchunks = (r_len + chunk_len - 1) / chunk_len;
 
-    if (!sc.need(0, sizeof(Top2) * (size_t)nchunks * l_len) ||
-        !sc.need(1, sizeof(float) * 128 * (size_t)(r_len > 0 ? r_len : 1)) ||
+    if (!sc.need(MS_F32_PARTIAL, sizeof(Top2) * (size_t)nchunks * l_len) ||
+        !sc.need(MS_F32_RPERM, sizeof(float) * 128 * (size_t)(r_len > 0 ? r_len : 1)) ||
         !sc.need(ob, (sizeof(int) * 3 + sizeof(float) * 2) * (size_t)l_len + 64))
         return PSX_ERR_NOMEM;
-    Top2* d_partial = static_cast<Top2*>(sc.buf[0]);
-    float* d_rperm = static_cast<float*>(sc.buf[1]);
+    Top2* d_partial = static_cast<Top2*>(sc.buf[MS_F32_PARTIAL]);
+    float* d_rperm = static_cast<float*>(sc.buf[MS_F32_RPERM]);
     int* d_out = static_cast<int*>(sc.buf[ob]);
     // matches, distances and the prefilter's flag in ONE buffer: one copy back per call (three cost ~5 us each)
     float* d_dist = reinterpret_cast<float*>(d_out + 3 * (size_t)l_len);
@@ -582,21 +580,21 @@ static int match_f32_run(MatchScratch& sc, const float* d_left, int l_len, const
     int* d_cct_used = nullptr;
     // (a failed allocation of the prefilter's scratch -- 4 KB of candidate slots per left descriptor -- leaves the exact scan)
     if (use_mfma && r_len >= 2 * MF_SEED && l_len >= 256 &&
-        sc.need(4, sizeof(unsigned short) * 128 * (size_t)l_len) && sc.need(5, sizeof(unsigned short) * 128 * (size_t)r_len) &&
-        sc.need(6, sizeof(float) * (1 + 2 * MF_SEEDCH) * (size_t)l_len) && sc.need(7, sizeof(float) * (size_t)r_len + 1024) &&
-        sc.need(8, sizeof(int) * (size_t)MF_SEGS * l_len) && sc.need(9, sizeof(int) * (size_t)MF_CAP * l_len)) {
-        unsigned short* d_lf16 = static_cast<unsigned short*>(sc.buf[4]);
-        unsigned short* d_rf16 = static_cast<unsigned short*>(sc.buf[5]);
-        float* d_ln2 = static_cast<float*>(sc.buf[6]);
+        sc.need(MS_F32_LF16, sizeof(unsigned short) * 128 * (size_t)l_len) && sc.need(MS_F32_RF16, sizeof(unsigned short) * 128 * (size_t)r_len) &&
+        sc.need(MS_F32_LNORM, sizeof(float) * (1 + 2 * MF_SEEDCH) * (size_t)l_len) && sc.need(MS_F32_RNORM, sizeof(float) * (size_t)r_len + 1024) &&
+        sc.need(MS_F32_CAND_CT, sizeof(int) * (size_t)MF_SEGS * l_len) && sc.need(MS_F32_CAND, sizeof(int) * (size_t)MF_CAP * l_len)) {
+        unsigned short* d_lf16 = static_cast<unsigned short*>(sc.buf[MS_F32_LF16]);
+        unsigned short* d_rf16 = static_cast<unsigned short*>(sc.buf[MS_F32_RF16]);
+        float* d_ln2 = static_cast<float*>(sc.buf[MS_F32_LNORM]);
         float* d_seed = d_ln2 + l_len;
         // in front of the right norms, at an address that does not move with r_len (the slots are zeroed by the previous call):
         // 2 x MF_MAXSLOTS maximum slots, 4 parameters
-        unsigned* d_rmax = static_cast<unsigned*>(sc.buf[7]);
+        unsigned* d_rmax = static_cast<unsigned*>(sc.buf[MS_F32_RNORM]);
         unsigned* d_lmax = d_rmax + MF_MAXSLOTS;
         float* d_par = reinterpret_cast<float*>(d_lmax + MF_MAXSLOTS);
         float* d_rn2 = reinterpret_cast<float*>(d_rmax + 256);
-        int* d_cct = static_cast<int*>(sc.buf[8]);
-        int* d_cand = static_cast<int*>(sc.buf[9]);
+        int* d_cct = static_cast<int*>(sc.buf[MS_F32_CAND_CT]);
+        int* d_cand = static_cast<int*>(sc.buf[MS_F32_CAND]);
         // workgroups the prefilter kernel keeps resident (the occupancy the runtime computes from its registers and LDS: 3 per CU)
         const int cus = sc.tune.cus;
         if (sc.mfma_per_cu == 0) {
@@ -616,7 +614,7 @@ static int match_f32_run(MatchScratch& sc, const float* d_left, int l_len, const
         const bool stats = sc.tune.match_stats;               // measurement: candidates per left descriptor
         // the candidate counts and the maximum slots: zeroed here after an allocation or a call that did not finish the usual
         // way, otherwise left at zero by the previous call's k_match_exact
-        if (!sc.tidy && (hipMemsetAsync(d_cct, 0, sc.cap[8], st) != hipSuccess ||
+        if (!sc.tidy && (hipMemsetAsync(d_cct, 0, sc.cap[MS_F32_CAND_CT], st) != hipSuccess ||
                          hipMemsetAsync(d_rmax, 0, sizeof(unsigned) * 2 * MF_MAXSLOTS, st) != hipSuccess))
             return PSX_ERR_HIP;
         sc.tidy = false;                                       // until this call's results are back with the flag down
@@ -684,8 +682,7 @@ static int match_f32_run(MatchScratch& sc, const float* d_left, int l_len, const
         hipLaunchKernelGGL(k_match_permute, dim3((r_len * 64 + 255) / 256), dim3(256), 0, st, d_right, r_len, d_rperm);
     hipLaunchKernelGGL(k_match_partial, dim3(lgroups, nchunks), dim3(64), 0, st, d_left, l_len, d_rperm, r_len,
                        chunk_len, d_partial);
-    hipLaunchKernelGGL(k_match_merge, dim3((l_len + 255) / 256), dim3(256), 0, st, d_partial, l_len, nchunks,
-                       r_len, d_out, d_dist);
+    hipLaunchKernelGGL(k_match_merge, dim3((l_len + 255) / 256), dim3(256), 0, st, d_partial, l_len, nchunks, r_len, d_out);
     if (!fetch()) return PSX_ERR_HIP;
     }
     return PSX_OK;
@@ -700,7 +697,7 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
     if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
     MatchScratch& sc = t_scratch;
     if (!sc.bind(device)) return PSX_ERR_HIP;
-    const int rc = match_f32_run(sc, d_left, l_len, d_right, r_len, 2, true);
+    const int rc = match_f32_run(sc, d_left, l_len, d_right, r_len, MS_F32_FWD, true);
     if (rc != PSX_OK) return rc;
     const size_t mb = sizeof(int) * 3 * (size_t)l_len, db = sizeof(float) * 2 * (size_t)l_len;
     const char* hp = static_cast<const char*>(sc.hpin);
@@ -731,7 +728,8 @@ extern "C" int psx_match(int device, const float* d_left, int l_len, const float
 // =====================================================================================================================
 namespace {
 
-// the key's constants (U8_*), u8_frag and key_insert: match_u8_core.h, shared with match_many.hip
+// the padding rule, the row norm, the key, the tile walk, the chunk merge and the accept decision: match_u8_core.h, shared with
+// match_many.hip
 
 __global__ void k_quantize_desc(const float* __restrict__ src, size_t n4, unsigned* __restrict__ dst)
 {
@@ -741,8 +739,8 @@ __global__ void k_quantize_desc(const float* __restrict__ src, size_t n4, unsign
     dst[i] = psx_quantize_u8(v.x) | (psx_quantize_u8(v.y) << 8) | (psx_quantize_u8(v.z) << 16) | (psx_quantize_u8(v.w) << 24);
 }
 
-// |x - 128|^2 of every descriptor of both sets (blocks [0, blocks_a): the first set); 8 lanes per descriptor (16 bytes
-// each).  The norm arrays are written up to a multiple of U8_TILE plus one tile with zeros: the matcher reads whole tiles.
+// |x - 128|^2 of every descriptor of both sets (blocks [0, blocks_a): the first set); 8 lanes per descriptor.  The norm
+// arrays are written up to u8_pad(n), the padding with zeros.
 __global__ void k_u8_norms(const unsigned char* __restrict__ src_a, int n_a, int* __restrict__ norm_a, int blocks_a,
                            const unsigned char* __restrict__ src_b, int n_b, int* __restrict__ norm_b)
 {
@@ -752,111 +750,33 @@ __global__ void k_u8_norms(const unsigned char* __restrict__ src_a, int n_a, int
     int* norm = second ? norm_b : norm_a;
     const int g = ((int)blockIdx.x - (second ? blocks_a : 0)) * blockDim.x + threadIdx.x;
     const int d = g >> 3, q = g & 7;
-    const int npad = ((n + U8_TILE - 1) / U8_TILE + 1) * U8_TILE;
-    if (d >= npad) return;
-    int ss = 0;
-    if (d < n) {
-        const uint4 v = reinterpret_cast<const uint4*>(src + (size_t)d * 128)[q];
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-#pragma unroll
-            for (int b = 0; b < 4; b++) { const int x = (int)((w[k] >> (8 * b)) & 0xffu) - 128; ss += x * x; }
-    }
-    ss += __shfl_xor(ss, 4, 8); ss += __shfl_xor(ss, 2, 8); ss += __shfl_xor(ss, 1, 8);
+    if (d >= (int)u8_pad(n)) return;
+    const int ss = u8_row_norm(src, n, d, q);
     if (q == 0) norm[d] = ss;
 }
 
-// grid (ceil(l_len / 256), nchunks), 256 threads: wave w owns left descriptors [256 bx + 64 w, + 64) as two B fragment sets
-// of 32 columns; every wave walks the chunk's right descriptors in tiles of 32 (A fragments straight from global memory:
-// the four waves of a workgroup read the same rows, the L1 serves the other three).  partial[chunk * l_len + left] =
-// (smallest, second smallest key).
+// grid (ceil(l_len / 256), nchunks), 256 threads: wave w owns left descriptors [256 bx + 64 w, + 64) and walks the chunk's
+// right descriptors (match_u8_core.h; the four waves of a workgroup read the same rows, the L1 serves the other three).
+// partial[chunk * l_len + left] = (smallest, second smallest key).
 __global__ __launch_bounds__(256) void k_match_u8(const unsigned char* __restrict__ left, const int* __restrict__ ln2, int l_len,
                                                   const unsigned char* __restrict__ right, const int* __restrict__ rn2, int r_len,
                                                   int chunk_len, uint2* __restrict__ partial)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = lane & 31, half = lane >> 5;
     const int r0 = blockIdx.y * chunk_len, r1 = min(r0 + chunk_len, r_len);
-    i32x4 bfrag[2][4];
-    int nl[2], lidx[2];
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        const int li = blockIdx.x * 256 + wave * 64 + c * 32 + col;
-        lidx[c] = li;
-        const int lq = min(li, l_len - 1);                  // idle columns repeat the last descriptor
-        const unsigned char* lp = left + (size_t)lq * 128 + half * 16;
-#pragma unroll
-        for (int kk = 0; kk < 4; kk++) bfrag[c][kk] = u8_frag(lp + kk * 32);
-        nl[c] = ln2[lq];
-    }
-    unsigned m1[2] = {U8_NONE, U8_NONE}, m2[2] = {U8_NONE, U8_NONE};
-    for (int base = r0; base < r1; base += U8_TILE) {
-        const unsigned char* rp = right + (size_t)min(base + col, r_len - 1) * 128 + half * 16;
-        i32x4 a[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; kk++) a[kk] = u8_frag(rp + kk * 32);
-        // this lane's 16 rows: base + 8 g + 4 half + e (the norm arrays are padded by a tile of zeros)
-        int nr[16];
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const int4 v = *reinterpret_cast<const int4*>(rn2 + base + 8 * g + 4 * half);
-            nr[4 * g] = v.x; nr[4 * g + 1] = v.y; nr[4 * g + 2] = v.z; nr[4 * g + 3] = v.w;
-        }
-        i32x16 acc[2];
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            acc[c] = (i32x16){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int kk = 0; kk < 4; kk++) acc[c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[kk], bfrag[c][kk], acc[c], 0, 0, 0);
-        }
-        const unsigned loc0 = (unsigned)(base - r0 + 4 * half);
-        const bool full = base + U8_TILE <= r1;             // wave uniform: only a chunk's last tile can be partial
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++) {
-                const int roff = 8 * (reg >> 2) + (reg & 3);
-                const unsigned d = (unsigned)(nl[c] + nr[reg] - 2 * acc[c][reg]);
-                unsigned key = (d << 9) | (loc0 + (unsigned)roff);
-                if (!full && base + 4 * half + roff >= r1) key = U8_NONE;
-                key_insert(m1[c], m2[c], key);
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        const unsigned o1 = __shfl_xor(m1[c], 32), o2 = __shfl_xor(m2[c], 32);
-        key_insert(m1[c], m2[c], o1);
-        key_insert(m1[c], m2[c], o2);
-        if (half == 0 && lidx[c] < l_len) partial[(size_t)blockIdx.y * l_len + lidx[c]] = make_uint2(m1[c], m2[c]);
-    }
+    U8Wave w;
+    u8_load_cols(w, left, ln2, l_len, blockIdx.x * 256 + (threadIdx.x >> 6) * 64);
+    u8_walk(w, right, rn2, r_len, r0, r1);
+    u8_store_keys(w, l_len, partial + (size_t)blockIdx.y * l_len);
 }
 
-// out[3 l .. 3 l + 2] = (best, second, accept), out[3 l_len + 2 l ..] = the two distances (INT_MAX: none)
+// the chunks in index order (u8_merge_chunk) into the directed result of match_scratch.h; distances INT_MAX: none
 __global__ void k_match_u8_merge(const uint2* __restrict__ partial, int l_len, int nchunks, int chunk_len, int* __restrict__ out)
 {
     const int li = blockIdx.x * blockDim.x + threadIdx.x;
     if (li >= l_len) return;
-    // the reference starts from (inf, inf, index 0, index 0); chunks are visited in index order and a chunk's two entries
-    // are in (distance, index) order, so strict '<' on the distance reproduces the sequential scan
-    int d1 = INT_MAX, d2 = INT_MAX, i1 = 0, i2 = 0;
-    for (int c = 0; c < nchunks; c++) {
-        const uint2 p = partial[(size_t)c * l_len + li];
-        const unsigned k[2] = {p.x, p.y};
-#pragma unroll
-        for (int e = 0; e < 2; e++) {
-            if (k[e] == U8_NONE) continue;
-            const int d = (int)(k[e] >> 9), i = c * chunk_len + (int)(k[e] & 511u);
-            if (d < d1) { d2 = d1; i2 = i1; d1 = d; i1 = i; }
-            else if (d < d2) { d2 = d; i2 = i; }
-        }
-    }
-    // IEEE division (no v_rcp): the integers are exact in float; a missing neighbour is +inf, as in psx_match
-    const float f1 = d1 == INT_MAX ? INFINITY : (float)d1, f2 = d2 == INT_MAX ? INFINITY : (float)d2;
-    const bool accept = (f1 / f2 < 0.8f);
-    out[3 * li + 0] = i1; out[3 * li + 1] = i2; out[3 * li + 2] = accept ? 1 : 0;
-    out[3 * (size_t)l_len + 2 * li + 0] = d1; out[3 * (size_t)l_len + 2 * li + 1] = d2;
+    U8Best t;
+    for (int c = 0; c < nchunks; c++) u8_merge_chunk(t, partial[(size_t)c * l_len + li], c * chunk_len);
+    psx_directed_store<int>(out, l_len, li, t.i1, t.i2, u8_accept(t.d1, t.d2), t.d1, t.d2);
 }
 
 } // namespace
@@ -879,13 +799,10 @@ U8Plan u8_plan(int l_len, int r_len)
     return U8Plan{lblocks, nchunks, chunk_len};
 }
 
-// entries of a set's norm array: whole tiles plus one tile of zeros (either set may be the one the matcher reads by tiles)
-size_t u8_pad(int n) { return ((size_t)(n + U8_TILE - 1) / U8_TILE + 1) * U8_TILE; }
-
 // the norms of both sets in one launch
 void u8_queue_norms(hipStream_t st, const unsigned char* d_left, int l_len, int* d_ln2, const unsigned char* d_right, int r_len, int* d_rn2)
 {
-    const int rnb = (int)((u8_pad(r_len) * 8 + 255) / 256), lnb = (int)((u8_pad(l_len) * 8 + 255) / 256);
+    const int rnb = (int)(((size_t)u8_pad(r_len) * 8 + 255) / 256), lnb = (int)(((size_t)u8_pad(l_len) * 8 + 255) / 256);
     hipLaunchKernelGGL(k_u8_norms, dim3(rnb + lnb), dim3(256), 0, st, d_right, r_len, d_rn2, rnb, d_left, l_len, d_ln2);
 }
 
@@ -933,12 +850,12 @@ extern "C" int psx_match_u8(int device, const unsigned char* d_left, int l_len, 
     const U8Plan pl = u8_plan(l_len, r_len);
     const size_t lpad = u8_pad(l_len), rpad = u8_pad(r_len);
     const size_t ob = sizeof(int) * 5 * (size_t)l_len;
-    if (!sc.need(10, sizeof(uint2) * (size_t)pl.nchunks * l_len) || !sc.need(11, sizeof(int) * (lpad + rpad)) || !sc.need(12, ob))
+    if (!sc.need(MS_U8_PARTIAL, sizeof(uint2) * (size_t)pl.nchunks * l_len) || !sc.need(MS_U8_NORMS, sizeof(int) * (lpad + rpad)) || !sc.need(MS_U8_FWD, ob))
         return PSX_ERR_NOMEM;
-    uint2* d_partial = static_cast<uint2*>(sc.buf[10]);
-    int* d_ln2 = static_cast<int*>(sc.buf[11]);
+    uint2* d_partial = static_cast<uint2*>(sc.buf[MS_U8_PARTIAL]);
+    int* d_ln2 = static_cast<int*>(sc.buf[MS_U8_NORMS]);
     int* d_rn2 = d_ln2 + lpad;                   // lpad is a multiple of U8_TILE: 16-byte aligned
-    int* d_out = static_cast<int*>(sc.buf[12]);
+    int* d_out = static_cast<int*>(sc.buf[MS_U8_FWD]);
     hipStream_t st = sc.stream;
     u8_queue_norms(st, d_left, l_len, d_ln2, d_right, r_len, d_rn2);
     u8_queue_match(st, pl, d_left, d_ln2, l_len, d_right, d_rn2, r_len, d_partial, d_out);
@@ -958,14 +875,12 @@ extern "C" int psx_match_u8(int device, const unsigned char* d_left, int l_len, 
 //
 // Two directed passes over the kernels above -- L -> R into one scratch buffer, with PSX_PAIRS_MUTUAL also R -> L into
 // another -- then a join on the device: per left descriptor i the rule of match_rule.h on F[i]'s distances and the gather
-// B[F[i].best].best == i, and a STABLE compaction of the survivors in ascending i.  Nothing depends on arrival order: a lane's
-// slot is (pairs of the workgroups before its own) + (pairs of the waves before its own) + (set ballot bits below its lane).
-//   k_pairs_count  evaluates the rule, one lane per left descriptor; wave64 ballot, the waves' counts summed in LDS: one
-//                  total per workgroup
-//   k_pairs_write  evaluates it again (three loads and a division: cheaper than parking the verdicts in memory), sums the
-//                  totals of the workgroups before its own (the exclusive scan across workgroups: every workgroup reads
-//                  at most gridDim.x ints), ranks its lanes with mbcnt and writes each surviving record with ONE 16-byte
-//                  store, never at or past `capacity`; the last workgroup writes the total
+// B[F[i].best].best == i, and the STABLE compaction of wg_compact.h of the survivors in ascending i (shared with
+// match_many.hip and ransac.hip).
+//   k_pairs_count  evaluates the rule, one lane per left descriptor: one total per workgroup
+//   k_pairs_write  evaluates it again (three loads and a division: cheaper than parking the verdicts in memory) and writes
+//                  each surviving record with ONE 16-byte store at its slot, never at or past `capacity`; the last
+//                  workgroup writes the total
 // The host forms let k_pairs_write store straight into the thread's pinned staging buffer (mapped host memory): the
 // count and 16 bytes per PAIR cross PCIe, nothing else, and the byte path synchronises once per call.
 // =====================================================================================================================
@@ -974,22 +889,17 @@ namespace {
 __device__ __forceinline__ int pair_bits(float d) { return __float_as_int(d); }
 __device__ __forceinline__ int pair_bits(int d) { return d; }
 
-__device__ __forceinline__ int lane_rank(unsigned long long m)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
-// fwd: the forward direction's buffer (3 l_len ints, then 2 l_len distances); bwd: the backward direction's (r_len rows;
-// read only with `mutual`).  The directed kernels only ever write indices in [0, r_len) / [0, l_len), and r_len >= 1 here.
+// fwd: the forward direction's directed result (l_len rows); bwd: the backward direction's (r_len rows; read only with
+// `mutual`).  The directed kernels only ever write indices in [0, r_len) / [0, l_len), and r_len >= 1 here.
 template <class Dist>
 __device__ __forceinline__ bool pair_rule(const int* __restrict__ fwd, int l_len, const int* __restrict__ bwd, int i,
                                           float ratio, int mutual, int4& rec)
 {
-    const Dist* dist = reinterpret_cast<const Dist*>(fwd + 3 * (size_t)l_len);
-    const int j = fwd[3 * (size_t)i];
-    const Dist d1 = dist[2 * (size_t)i], d2 = dist[2 * (size_t)i + 1];
+    int j;
+    Dist d1, d2;
+    psx_directed_load<Dist>(fwd, l_len, i, j, d1, d2);
     bool keep = psx_match_keep(psx_match_dist(d1), psx_match_dist(d2), ratio);
-    if (keep && mutual) keep = bwd[3 * (size_t)j] == i;
+    if (keep && mutual) keep = psx_directed_best(bwd, j) == i;
     rec = make_int4(i, j, pair_bits(d1), pair_bits(d2));
     return keep;
 }
@@ -1001,11 +911,9 @@ __global__ __launch_bounds__(256) void k_pairs_count(const int* __restrict__ fwd
     const int i = blockIdx.x * 256 + threadIdx.x;
     int4 rec;
     const bool keep = i < l_len && pair_rule<Dist>(fwd, l_len, bwd, i, ratio, mutual, rec);
-    const unsigned long long m = __ballot(keep);
     __shared__ int s_cnt[4];
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) wg_tot[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    wg_count(__ballot(keep), s_cnt);
+    if (threadIdx.x == 0) wg_tot[blockIdx.x] = wg_total(s_cnt);
 }
 
 template <class Dist>
@@ -1013,36 +921,24 @@ __global__ __launch_bounds__(256) void k_pairs_write(const int* __restrict__ fwd
                                                      float ratio, int mutual, const int* __restrict__ wg_tot,
                                                      int4* __restrict__ out, int capacity, int* __restrict__ total)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blockIdx.x * 256 + threadIdx.x;
     int4 rec = make_int4(0, 0, 0, 0);
     const bool keep = i < l_len && pair_rule<Dist>(fwd, l_len, bwd, i, ratio, mutual, rec);
-    const unsigned long long m = __ballot(keep);
-    // pairs of the workgroups before this one
-    int part = 0;
-    for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) part += wg_tot[b];
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) part += __shfl_xor(part, k);
-    __shared__ int s_part[4], s_cnt[4];
-    if (lane == 0) { s_part[wave] = part; s_cnt[wave] = __popcll(m); }
-    __syncthreads();
-    const int base = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-    int woff = 0;
-    for (int w = 0; w < wave; w++) woff += s_cnt[w];
-    const int pos = base + woff + lane_rank(m);
+    const int pos = wg_slot(__ballot(keep), wg_tot, total);
     if (keep && pos < capacity) out[pos] = rec;
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = base + s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
-// Queues the join behind the directed passes and finishes the call: d_fwd / d_bwd as pair_rule reads them.  host_pairs:
-// the records go through the pinned staging buffer into it; d_pairs: into the caller's device buffer.  One
-// synchronisation.
+} // namespace
+
+// Queues the join behind the directed passes and finishes the call (match_scratch.h; match_guided.hip calls it too): d_fwd /
+// d_bwd as pair_rule reads them.  host_pairs: the records go through the pinned staging buffer into it; d_pairs: into the
+// caller's device buffer.  One synchronisation.
 template <class Dist>
-int pairs_finish(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
-                 void* host_pairs, void* d_pairs, int capacity, int* count)
+int psx_pairs_finish(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
+                     void* host_pairs, void* d_pairs, int capacity, int* count)
 {
     const int nb = (l_len + 255) / 256;
-    if (!sc.need(15, sizeof(int) * (size_t)nb)) return PSX_ERR_NOMEM;
+    if (!sc.need(MS_PAIRS_TOT, sizeof(int) * (size_t)nb)) return PSX_ERR_NOMEM;
     const int nrec = host_pairs ? (capacity < l_len ? capacity : l_len) : 0;       // at most l_len pairs exist
     if (!sc.need_pinned(16 + 16 * (size_t)nrec)) return PSX_ERR_NOMEM;
     void* dev_pin = nullptr;
@@ -1053,7 +949,7 @@ int pairs_finish(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd
     // the kernel's capacity for the host form is the staging buffer's (nrec <= capacity)
     int4* out = host_pairs ? reinterpret_cast<int4*>(static_cast<char*>(dev_pin) + 16) : static_cast<int4*>(d_pairs);
     const int cap = host_pairs ? nrec : capacity;
-    int* d_tot = static_cast<int*>(sc.buf[15]);
+    int* d_tot = static_cast<int*>(sc.buf[MS_PAIRS_TOT]);
     const int mutual = (opts->flags & PSX_PAIRS_MUTUAL) ? 1 : 0;
     hipStream_t st = sc.stream;
     hipLaunchKernelGGL((k_pairs_count<Dist>), dim3(nb), dim3(256), 0, st, d_fwd, l_len, d_bwd, opts->ratio, mutual, d_tot);
@@ -1065,6 +961,10 @@ int pairs_finish(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd
     *count = n;
     return PSX_OK;
 }
+template int psx_pairs_finish<float>(MatchScratch&, const int*, int, const int*, const psx_match_opts*, void*, void*, int, int*);
+template int psx_pairs_finish<int>(MatchScratch&, const int*, int, const int*, const psx_match_opts*, void*, void*, int, int*);
+
+namespace {
 
 // host_pairs or d_pairs (the other is NULL; both NULL with capacity 0)
 int match_pairs_f32(int device, const float* d_left, int l_len, const float* d_right, int r_len, const psx_match_opts* opts,
@@ -1079,11 +979,11 @@ int match_pairs_f32(int device, const float* d_left, int l_len, const float* d_r
     if (!sc.bind(device)) return PSX_ERR_HIP;
     const bool mutual = (opts->flags & PSX_PAIRS_MUTUAL) != 0;
     // each direction is a whole directed call (its own size rule, its own flag and fallback); the results stay in HBM
-    int rc = match_f32_run(sc, d_left, l_len, d_right, r_len, 2, false);
-    if (rc == PSX_OK && mutual) rc = match_f32_run(sc, d_right, r_len, d_left, l_len, 13, false);
+    int rc = match_f32_run(sc, d_left, l_len, d_right, r_len, MS_F32_FWD, false);
+    if (rc == PSX_OK && mutual) rc = match_f32_run(sc, d_right, r_len, d_left, l_len, MS_F32_BWD, false);
     if (rc != PSX_OK) return rc;
-    return pairs_finish<float>(sc, static_cast<const int*>(sc.buf[2]), l_len, mutual ? static_cast<const int*>(sc.buf[13]) : nullptr,
-                               opts, host_pairs, d_pairs, capacity, count);
+    return psx_pairs_finish<float>(sc, static_cast<const int*>(sc.buf[MS_F32_FWD]), l_len, mutual ? static_cast<const int*>(sc.buf[MS_F32_BWD]) : nullptr,
+                                   opts, host_pairs, d_pairs, capacity, count);
 }
 
 int match_pairs_u8(int device, const unsigned char* d_left, int l_len, const unsigned char* d_right, int r_len,
@@ -1102,38 +1002,26 @@ int match_pairs_u8(int device, const unsigned char* d_left, int l_len, const uns
     // every buffer of both directions before the first launch: nothing is reallocated under queued work
     size_t pb = sizeof(uint2) * (size_t)fw.nchunks * l_len;
     if (mutual && sizeof(uint2) * (size_t)bw.nchunks * r_len > pb) pb = sizeof(uint2) * (size_t)bw.nchunks * r_len;
-    if (!sc.need(10, pb) || !sc.need(11, sizeof(int) * (lpad + rpad)) || !sc.need(12, sizeof(int) * 5 * (size_t)l_len) ||
-        (mutual && !sc.need(14, sizeof(int) * 5 * (size_t)r_len)))
+    if (!sc.need(MS_U8_PARTIAL, pb) || !sc.need(MS_U8_NORMS, sizeof(int) * (lpad + rpad)) || !sc.need(MS_U8_FWD, sizeof(int) * 5 * (size_t)l_len) ||
+        (mutual && !sc.need(MS_U8_BWD, sizeof(int) * 5 * (size_t)r_len)))
         return PSX_ERR_NOMEM;
-    uint2* d_partial = static_cast<uint2*>(sc.buf[10]);
-    int* d_ln2 = static_cast<int*>(sc.buf[11]);
+    uint2* d_partial = static_cast<uint2*>(sc.buf[MS_U8_PARTIAL]);
+    int* d_ln2 = static_cast<int*>(sc.buf[MS_U8_NORMS]);
     int* d_rn2 = d_ln2 + lpad;
-    int* d_fwd = static_cast<int*>(sc.buf[12]);
-    int* d_bwd = mutual ? static_cast<int*>(sc.buf[14]) : nullptr;
+    int* d_fwd = static_cast<int*>(sc.buf[MS_U8_FWD]);
+    int* d_bwd = mutual ? static_cast<int*>(sc.buf[MS_U8_BWD]) : nullptr;
     hipStream_t st = sc.stream;
     // one norms launch serves both directions; the second direction's partials reuse the first's buffer (stream order)
     u8_queue_norms(st, d_left, l_len, d_ln2, d_right, r_len, d_rn2);
     u8_queue_match(st, fw, d_left, d_ln2, l_len, d_right, d_rn2, r_len, d_partial, d_fwd);
     if (mutual) u8_queue_match(st, bw, d_right, d_rn2, r_len, d_left, d_ln2, l_len, d_partial, d_bwd);
-    return pairs_finish<int>(sc, d_fwd, l_len, d_bwd, opts, host_pairs, d_pairs, capacity, count);
+    return psx_pairs_finish<int>(sc, d_fwd, l_len, d_bwd, opts, host_pairs, d_pairs, capacity, count);
 }
 
 } // namespace
 
 // what match_guided.hip shares (match_scratch.h)
 MatchScratch& psx_match_scratch() { return t_scratch; }
-
-int psx_pairs_finish_f32(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
-                         void* host_pairs, void* d_pairs, int capacity, int* count)
-{
-    return pairs_finish<float>(sc, d_fwd, l_len, d_bwd, opts, host_pairs, d_pairs, capacity, count);
-}
-
-int psx_pairs_finish_u8(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
-                        void* host_pairs, void* d_pairs, int capacity, int* count)
-{
-    return pairs_finish<int>(sc, d_fwd, l_len, d_bwd, opts, host_pairs, d_pairs, capacity, count);
-}
 
 extern "C" int psx_match_opts_default(psx_match_opts* o)
 {

@@ -163,9 +163,7 @@ __global__ __launch_bounds__(256) void k_match_guided(const T* __restrict__ oute
         // the reference starts from (inf, inf, index 0, index 0): zero or one admissible inner descriptor leaves them
         const int i1 = t.i1 == G_NOIDX ? 0 : t.i1, i2 = t.i2 == G_NOIDX ? 0 : t.i2;
         const bool accept = psx_match_keep(psx_match_dist(t.d1), psx_match_dist(t.d2), 0.8f);
-        out[3 * (size_t)oi + 0] = i1; out[3 * (size_t)oi + 1] = i2; out[3 * (size_t)oi + 2] = accept ? 1 : 0;
-        D* dist = reinterpret_cast<D*>(out + 3 * (size_t)o_len);
-        dist[2 * (size_t)oi + 0] = t.d1; dist[2 * (size_t)oi + 1] = t.d2;
+        psx_directed_store<D>(out, o_len, (size_t)oi, i1, i2, accept, t.d1, t.d2);
     }
 }
 
@@ -211,8 +209,8 @@ int match_guided(int device, const T* d_left, const float* d_left_xy, int l_len,
     MatchScratch& sc = psx_match_scratch();
     if (!sc.bind(device)) return PSX_ERR_HIP;
     const size_t ob = sizeof(int) * 5 * (size_t)l_len;
-    if (!sc.need(16, ob) || !sc.need_pinned(ob)) return PSX_ERR_NOMEM;
-    int* d_out = static_cast<int*>(sc.buf[16]);
+    if (!sc.need(MS_GUIDED_FWD, ob) || !sc.need_pinned(ob)) return PSX_ERR_NOMEM;
+    int* d_out = static_cast<int*>(sc.buf[MS_GUIDED_FWD]);
     hipStream_t st = sc.stream;
     queue_directed<T, D>(st, false, d_left, d_left_xy, l_len, d_right, d_right_xy, r_len, *guide, nullptr, d_out);
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(sc.hpin, d_out, ob, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -222,17 +220,6 @@ int match_guided(int device, const T* d_left, const float* d_left_xy, int l_len,
     memcpy(host_match, hp, sizeof(int) * 3 * (size_t)l_len);
     if (host_dist) memcpy(host_dist, hp + 3 * (size_t)l_len, sizeof(D) * 2 * (size_t)l_len);
     return PSX_OK;
-}
-
-int pairs_finish(float, MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
-                 void* host_pairs, void* d_pairs, int capacity, int* count)
-{
-    return psx_pairs_finish_f32(sc, d_fwd, l_len, d_bwd, opts, host_pairs, d_pairs, capacity, count);
-}
-int pairs_finish(int, MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
-                 void* host_pairs, void* d_pairs, int capacity, int* count)
-{
-    return psx_pairs_finish_u8(sc, d_fwd, l_len, d_bwd, opts, host_pairs, d_pairs, capacity, count);
 }
 
 // host_pairs or d_pairs (the other is NULL; both NULL with capacity 0)
@@ -249,14 +236,14 @@ int match_pairs_guided(int device, const T* d_left, const float* d_left_xy, int 
     if (!sc.bind(device)) return PSX_ERR_HIP;
     const bool mutual = (opts->flags & PSX_PAIRS_MUTUAL) != 0;
     // both directions' buffers before the first launch: nothing is reallocated under queued work
-    if (!sc.need(16, sizeof(int) * 5 * (size_t)l_len) ||
-        (mutual && (!sc.need(17, sizeof(int) * 5 * (size_t)r_len) || !sc.need(18, sizeof(float4) * (size_t)l_len))))
+    if (!sc.need(MS_GUIDED_FWD, sizeof(int) * 5 * (size_t)l_len) ||
+        (mutual && (!sc.need(MS_GUIDED_BWD, sizeof(int) * 5 * (size_t)r_len) || !sc.need(MS_GUIDED_LINES, sizeof(float4) * (size_t)l_len))))
         return PSX_ERR_NOMEM;
-    int* d_fwd = static_cast<int*>(sc.buf[16]);
-    int* d_bwd = mutual ? static_cast<int*>(sc.buf[17]) : nullptr;
+    int* d_fwd = static_cast<int*>(sc.buf[MS_GUIDED_FWD]);
+    int* d_bwd = mutual ? static_cast<int*>(sc.buf[MS_GUIDED_BWD]) : nullptr;
     queue_directed<T, D>(sc.stream, false, d_left, d_left_xy, l_len, d_right, d_right_xy, r_len, *guide, nullptr, d_fwd);
-    if (mutual) queue_directed<T, D>(sc.stream, true, d_right, d_right_xy, r_len, d_left, d_left_xy, l_len, *guide, static_cast<float4*>(sc.buf[18]), d_bwd);
-    return pairs_finish(D(), sc, d_fwd, l_len, d_bwd, opts, host_pairs, d_pairs, capacity, count);
+    if (mutual) queue_directed<T, D>(sc.stream, true, d_right, d_right_xy, r_len, d_left, d_left_xy, l_len, *guide, static_cast<float4*>(sc.buf[MS_GUIDED_LINES]), d_bwd);
+    return psx_pairs_finish<D>(sc, d_fwd, l_len, d_bwd, opts, host_pairs, d_pairs, capacity, count);
 }
 
 } // namespace

@@ -6,19 +6,19 @@
 // already walks the right side in chunks of <= 512 rows that leave a per-left top-2 key each, merged in index order; the
 // (distance, index) order is total, so the result does not depend on where the chunks are cut.  "One left set against K
 // right sets" is that dataflow driven by tables in which no chunk crosses a set boundary (match_many_plan.h):
-//   k_u8_norms_many        |x - 128|^2 of every row of all K + 1 sets, padded per set as k_u8_norms pads
-//   k_match_u8_many        the tile loop of k_match_u8; its outer rows come from a block table, its inner rows from a chunk
+// The matcher's device pieces -- row norm, padding, tile walk, chunk merge, accept -- are those of k_match_u8, stated once in
+// match_u8_core.h; the kernels here only say where the operands live:
+//   k_u8_norms_many        |x - 128|^2 of every row of all K + 1 sets, each set padded to u8_pad(len)
+//   k_match_u8_many        the walk of k_match_u8; its outer rows come from a block table, its inner rows from a chunk
 //                          table.  Forward: blocks of L x chunks of the K right sets; backward (PSX_PAIRS_MUTUAL only): blocks
 //                          of the K right sets x chunks of L -- the same kernel on the other pair of tables
-//   k_match_u8_many_merge  per (outer row, inner set) the chunks of that set in index order, strict '<': the directed layout
-//                          (3 ints, 2 distances per row) the join reads -- K results per left row forward, one per right row
-//                          backward
+//   k_match_u8_many_merge  per (outer row, inner set) the chunks of that set in index order: the directed result
+//                          (match_scratch.h) the join reads -- K results per left row forward, one per right row backward
 //   k_many_count / k_many_scan / k_many_write   the join of match.hip, segmented: the rule of match_rule.h per (set, left)
-//                          with the gather into set k's backward rows; one total per workgroup in set-major order, an exclusive
-//                          scan of the totals by one workgroup (K x blocks totals: every workgroup summing all earlier ones, as
-//                          k_pairs_write does, would be quadratic), then one 16-byte store per survivor at its global rank.
-//                          No atomics: a record's slot is (offset of its workgroup) + (pairs of the waves before its own) +
-//                          (ballot bits below its lane).
+//                          with the gather into set k's backward rows and the compaction of wg_compact.h; one total per
+//                          workgroup in set-major order, an exclusive scan of the totals by one workgroup (K x blocks totals:
+//                          every workgroup summing all earlier ones, as k_pairs_write does, would be quadratic), then one
+//                          16-byte store per survivor at (offset of its workgroup) + (its offset within the workgroup).
 // Launches per call, whatever K is: the table copy, the norms, 2 per direction, 3 for the join -- 8 kernels with the
 // cross-check, 6 without; one stream synchronisation.  The per-chunk partials are the one buffer that grows with
 // (chunks x outer rows): above MANY_PARTIAL_BUDGET the sets are processed in groups of whole sets, each group its own
@@ -28,6 +28,7 @@
 #include "match_many_plan.h"
 #include "match_scratch.h"
 #include "match_u8_core.h"
+#include "wg_compact.h"
 
 #include <climits>
 #include <cstring>
@@ -55,114 +56,44 @@ struct ManyPass {
     int row_base, outer_rows;    // the partials hold outer rows [row_base, row_base + outer_rows) of the outer side
 };
 
-__device__ __forceinline__ int many_pad(int n) { return ((n + U8_TILE - 1) / U8_TILE + 1) * U8_TILE; }
-
-// grid: every block of both sides, 256 threads, 8 lanes per descriptor (16 bytes each).  A set's norms are written up to a
-// multiple of U8_TILE plus one tile with zeros (the matcher reads whole tiles): the set's last block writes the padding.
+// grid: every block of both sides, 256 threads, 8 lanes per descriptor.  A set's norms are written up to u8_pad(len), the
+// padding with zeros: the set's last block writes it.
 __global__ __launch_bounds__(256) void k_u8_norms_many(const ManySet* __restrict__ sets, const int2* __restrict__ blocks,
                                                        int* __restrict__ norms)
 {
     const int2 blk = blocks[blockIdx.x];
     const ManySet s = sets[blk.x];
-    const int end = blk.y + PSX_MANY_BLOCK >= s.len ? many_pad(s.len) : blk.y + PSX_MANY_BLOCK;
+    const int end = blk.y + PSX_MANY_BLOCK >= s.len ? (int)u8_pad(s.len) : blk.y + PSX_MANY_BLOCK;
     const int q = threadIdx.x & 7;
     for (int d = blk.y + (threadIdx.x >> 3); d < end; d += 32) {
-        int ss = 0;
-        if (d < s.len) {
-            const uint4 v = reinterpret_cast<const uint4*>(s.desc + (size_t)d * 128)[q];
-            const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-#pragma unroll
-                for (int b = 0; b < 4; b++) { const int x = (int)((w[k] >> (8 * b)) & 0xffu) - 128; ss += x * x; }
-        }
-        ss += __shfl_xor(ss, 4, 8); ss += __shfl_xor(ss, 2, 8); ss += __shfl_xor(ss, 1, 8);
+        const int ss = u8_row_norm(s.desc, s.len, d, q);
         if (q == 0) norms[s.noff + d] = ss;
     }
 }
 
 // grid nblocks x (chunks of the launch), 256 threads; workgroup (ob, ch) = (blockIdx.x % nblocks, blockIdx.x / nblocks).
-// k_match_u8 with both sides taken from tables: wave w owns outer rows [row0 + 64 w, + 64) of ITS block's set as two B
-// fragment sets, and walks rows [r0, r1) of ITS chunk's set in tiles of 32.  The two table entries are read at
-// wave-uniform addresses (scalar loads).  Row reads are clamped to the set's own last row, idle outer columns repeat the
-// last row of their own set, keys of rows past the chunk's end are U8_NONE: nothing of a neighbouring set is ever ranked.
+// k_match_u8 with both sides taken from tables: wave w owns outer rows [row0 + 64 w, + 64) of ITS block's set and walks
+// rows [r0, r1) of ITS chunk's set (match_u8_core.h).  The two table entries are read at wave-uniform addresses (scalar
+// loads).  Row reads are clamped to the set's own last row, idle outer columns repeat the last row of their own set, keys
+// of rows past the chunk's end are U8_NONE: nothing of a neighbouring set is ever ranked.
 // partial[ch * outer_rows + (row among the launch's outer rows)] = (smallest, second smallest key).
 __global__ __launch_bounds__(256) void k_match_u8_many(const ManySet* __restrict__ sets, const int4* __restrict__ chunks,
                                                        const int2* __restrict__ blocks, const int* __restrict__ norms,
                                                        ManyPass ps, uint2* __restrict__ partial)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = lane & 31, half = lane >> 5;
     const int ob = (int)(blockIdx.x % (unsigned)ps.nblocks), ch = (int)(blockIdx.x / (unsigned)ps.nblocks);
     const int2 blk = blocks[ps.block_base + ob];
     const int4 chk = chunks[ps.chunk_base + ch];
     const ManySet os = sets[blk.x], is = sets[chk.x];
-    const unsigned char* __restrict__ left = os.desc;
-    const unsigned char* __restrict__ right = is.desc;
-    const int* __restrict__ ln2 = norms + os.noff;
-    const int* __restrict__ rn2 = norms + is.noff;
-    const int l_len = os.len, r_len = is.len;
-    const int r0 = chk.y, r1 = chk.z;
-    i32x4 bfrag[2][4];
-    int nl[2], lidx[2];
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        const int li = blk.y + wave * 64 + c * 32 + col;
-        lidx[c] = li;
-        const int lq = min(li, l_len - 1);                  // idle columns repeat the last descriptor of their own set
-        const unsigned char* lp = left + (size_t)lq * 128 + half * 16;
-#pragma unroll
-        for (int kk = 0; kk < 4; kk++) bfrag[c][kk] = u8_frag(lp + kk * 32);
-        nl[c] = ln2[lq];
-    }
-    unsigned m1[2] = {U8_NONE, U8_NONE}, m2[2] = {U8_NONE, U8_NONE};
-    for (int base = r0; base < r1; base += U8_TILE) {
-        const unsigned char* rp = right + (size_t)min(base + col, r_len - 1) * 128 + half * 16;
-        i32x4 a[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; kk++) a[kk] = u8_frag(rp + kk * 32);
-        // this lane's 16 rows: base + 8 g + 4 half + e (the set's norms are padded by a tile of zeros)
-        int nr[16];
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const int4 v = *reinterpret_cast<const int4*>(rn2 + base + 8 * g + 4 * half);
-            nr[4 * g] = v.x; nr[4 * g + 1] = v.y; nr[4 * g + 2] = v.z; nr[4 * g + 3] = v.w;
-        }
-        i32x16 acc[2];
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            acc[c] = (i32x16){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int kk = 0; kk < 4; kk++) acc[c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[kk], bfrag[c][kk], acc[c], 0, 0, 0);
-        }
-        const unsigned loc0 = (unsigned)(base - r0 + 4 * half);
-        const bool full = base + U8_TILE <= r1;             // wave uniform: only a chunk's last tile can be partial
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++) {
-                const int roff = 8 * (reg >> 2) + (reg & 3);
-                const unsigned d = (unsigned)(nl[c] + nr[reg] - 2 * acc[c][reg]);
-                unsigned key = (d << 9) | (loc0 + (unsigned)roff);
-                if (!full && base + 4 * half + roff >= r1) key = U8_NONE;
-                key_insert(m1[c], m2[c], key);
-            }
-        }
-    }
-    const size_t prow = (size_t)ch * ps.outer_rows + (size_t)(os.roff - ps.row_base);
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        const unsigned o1 = __shfl_xor(m1[c], 32), o2 = __shfl_xor(m2[c], 32);
-        key_insert(m1[c], m2[c], o1);
-        key_insert(m1[c], m2[c], o2);
-        if (half == 0 && lidx[c] < l_len) partial[prow + lidx[c]] = make_uint2(m1[c], m2[c]);
-    }
+    U8Wave w;
+    u8_load_cols(w, os.desc, norms + os.noff, os.len, blk.y + (threadIdx.x >> 6) * 64);
+    u8_walk(w, is.desc, norms + is.noff, is.len, chk.y, chk.z);
+    u8_store_keys(w, os.len, partial + (size_t)ch * ps.outer_rows + (size_t)(os.roff - ps.row_base));
 }
 
 // grid nblocks x ngroups, 256 threads: one thread per (outer row of block ob, inner set group_base + g).  The set's chunks
-// in table order = index order; a chunk's two keys are in (distance, index) order, so strict '<' on the distance reproduces
-// the sequential scan (k_match_u8_merge).  The result goes where the join expects the directed result of (outer set, inner
-// set): out + out_stride * (inner set) + 5 * (outer set's first row), 3 len ints (best, second, accept) then 2 len distances.
+// in table order = index order, merged as k_match_u8_merge merges them (u8_merge_chunk).  The result goes where the join
+// expects the directed result of (outer set, inner set): at out + out_stride * (inner set) + 5 * (outer set's first row).
 // out_stride = 5 l_len forward (K results per left row), 0 backward (the one inner set is L).
 __global__ __launch_bounds__(256) void k_match_u8_many_merge(const ManySet* __restrict__ sets, const int4* __restrict__ chunks,
                                                              const int2* __restrict__ blocks, ManyPass ps, int group_base,
@@ -174,30 +105,10 @@ __global__ __launch_bounds__(256) void k_match_u8_many_merge(const ManySet* __re
     const int row = blk.y + (int)threadIdx.x;
     if (row >= os.len) return;
     const size_t prow = (size_t)(os.roff - ps.row_base) + row;
-    int d1 = INT_MAX, d2 = INT_MAX, i1 = 0, i2 = 0;
-    for (int c = is.c0; c < is.c1; c++) {
-        const uint2 p = partial[(size_t)(c - ps.chunk_base) * ps.outer_rows + prow];
-        const int r0 = chunks[c].y;
-        const unsigned k[2] = {p.x, p.y};
-#pragma unroll
-        for (int e = 0; e < 2; e++) {
-            if (k[e] == U8_NONE) continue;
-            const int d = (int)(k[e] >> 9), i = r0 + (int)(k[e] & 511u);
-            if (d < d1) { d2 = d1; i2 = i1; d1 = d; i1 = i; }
-            else if (d < d2) { d2 = d; i2 = i; }
-        }
-    }
-    // IEEE division (no v_rcp): the integers are exact in float; a missing neighbour is +inf, as in psx_match
-    const float f1 = d1 == INT_MAX ? INFINITY : (float)d1, f2 = d2 == INT_MAX ? INFINITY : (float)d2;
-    const bool accept = (f1 / f2 < 0.8f);
-    int* o = out + out_stride * (size_t)g + 5 * (size_t)os.roff;
-    o[3 * (size_t)row + 0] = i1; o[3 * (size_t)row + 1] = i2; o[3 * (size_t)row + 2] = accept ? 1 : 0;
-    o[3 * (size_t)os.len + 2 * (size_t)row + 0] = d1; o[3 * (size_t)os.len + 2 * (size_t)row + 1] = d2;
-}
-
-__device__ __forceinline__ int many_lane_rank(unsigned long long m)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    U8Best t;
+    for (int c = is.c0; c < is.c1; c++)
+        u8_merge_chunk(t, partial[(size_t)(c - ps.chunk_base) * ps.outer_rows + prow], chunks[c].y);
+    psx_directed_store<int>(out + out_stride * (size_t)g + 5 * (size_t)os.roff, os.len, (size_t)row, t.i1, t.i2, u8_accept(t.d1, t.d2), t.d1, t.d2);
 }
 
 // The rule of match_rule.h for left row i against set k: fwd holds K directed results of 5 l_len ints each, bwd the K sets'
@@ -207,11 +118,10 @@ __device__ __forceinline__ bool many_rule(const ManySet* __restrict__ sets, cons
 {
     const ManySet s = sets[k];
     if (i >= l_len || s.len == 0) return false;
-    const int* f = fwd + 5 * (size_t)l_len * k;
-    const int j = f[3 * (size_t)i];
-    const int d1 = f[3 * (size_t)l_len + 2 * (size_t)i], d2 = f[3 * (size_t)l_len + 2 * (size_t)i + 1];
+    int j, d1, d2;
+    psx_directed_load<int>(fwd + 5 * (size_t)l_len * k, l_len, i, j, d1, d2);
     bool keep = psx_match_keep(psx_match_dist(d1), psx_match_dist(d2), ratio);
-    if (keep && mutual) keep = bwd[5 * (size_t)s.roff + 3 * (size_t)j] == i;
+    if (keep && mutual) keep = psx_directed_best(bwd + 5 * (size_t)s.roff, j) == i;
     rec = make_int4(i, j, d1, d2);
     return keep;
 }
@@ -224,11 +134,9 @@ __global__ __launch_bounds__(256) void k_many_count(const ManySet* __restrict__ 
     const int k = (int)(blockIdx.x / (unsigned)nb), b = (int)(blockIdx.x % (unsigned)nb);
     int4 rec;
     const bool keep = many_rule(sets, fwd, l_len, bwd, k, b * 256 + (int)threadIdx.x, ratio, mutual, rec);
-    const unsigned long long m = __ballot(keep);
     __shared__ int s_cnt[4];
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) wg_tot[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    wg_count(__ballot(keep), s_cnt);
+    if (threadIdx.x == 0) wg_tot[blockIdx.x] = wg_total(s_cnt);
 }
 
 // ONE workgroup of 1024 threads: offs[w] = the totals before workgroup w, offs[n] = all of them.  1024 totals per round:
@@ -264,17 +172,13 @@ __global__ __launch_bounds__(256) void k_many_write(const ManySet* __restrict__ 
                                                     const int* __restrict__ offs, int4* __restrict__ out, int capacity,
                                                     int* __restrict__ set_counts, int* __restrict__ total)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int k = (int)(blockIdx.x / (unsigned)nb), b = (int)(blockIdx.x % (unsigned)nb);
     int4 rec = make_int4(0, 0, 0, 0);
     const bool keep = many_rule(sets, fwd, l_len, bwd, k, b * 256 + (int)threadIdx.x, ratio, mutual, rec);
     const unsigned long long m = __ballot(keep);
     __shared__ int s_cnt[4];
-    if (lane == 0) s_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wave; w++) woff += s_cnt[w];
-    const int pos = offs[blockIdx.x] + woff + many_lane_rank(m);
+    wg_count(m, s_cnt);
+    const int pos = offs[blockIdx.x] + wg_offset(m, s_cnt);
     if (keep && pos < capacity) out[pos] = rec;
     if (threadIdx.x == 0) {
         if (b == 0) set_counts[k] = offs[(size_t)(k + 1) * nb] - offs[(size_t)k * nb];
@@ -364,9 +268,9 @@ int match_pairs_many(int device, const unsigned char* d_left, int l_len, const u
 
     // ---- sizes: the norms of all sets, the tables, the results ----
     long long npad = 0;
-    for (int k = 0; k < K; k++) npad += r_lens[k] > 0 ? ((long long)(r_lens[k] + U8_TILE - 1) / U8_TILE + 1) * U8_TILE : 0;
+    for (int k = 0; k < K; k++) npad += r_lens[k] > 0 ? u8_pad(r_lens[k]) : 0;
     const long long l_noff = npad;
-    npad += ((long long)(l_len + U8_TILE - 1) / U8_TILE + 1) * U8_TILE;
+    npad += u8_pad(l_len);
     if (npad > INT_MAX) return PSX_ERR_NOMEM;
     const size_t sets_b = pad16(sizeof(ManySet) * ((size_t)K + 1));
     const size_t chunks_b = pad16(sizeof(int4) * (size_t)(CR + CL));
@@ -380,9 +284,9 @@ int match_pairs_many(int device, const unsigned char* d_left, int l_len, const u
     MatchScratch& sc = psx_match_scratch();
     if (!sc.bind(device)) return PSX_ERR_HIP;
     // every buffer before the first launch: nothing is reallocated under queued work
-    if (!sc.need(25, blob_b) || !sc.need(26, sizeof(int) * (size_t)npad) || !sc.need(27, partial_bytes) ||
-        !sc.need(28, sizeof(int) * 5 * (size_t)all_pairs) || (mutual && !sc.need(29, sizeof(int) * 5 * (size_t)r_total)) ||
-        !sc.need(30, sizeof(int) * (2 * (size_t)ntot + 1)) || !sc.need_pinned(off_blob + blob_b))
+    if (!sc.need(MS_MANY_TABLES, blob_b) || !sc.need(MS_MANY_NORMS, sizeof(int) * (size_t)npad) || !sc.need(MS_MANY_PARTIAL, partial_bytes) ||
+        !sc.need(MS_MANY_FWD, sizeof(int) * 5 * (size_t)all_pairs) || (mutual && !sc.need(MS_MANY_BWD, sizeof(int) * 5 * (size_t)r_total)) ||
+        !sc.need(MS_MANY_TOT, sizeof(int) * (2 * (size_t)ntot + 1)) || !sc.need_pinned(off_blob + blob_b))
         return PSX_ERR_NOMEM;
     void* dev_pin = nullptr;
     if (hipHostGetDevicePointer(&dev_pin, sc.hpin, 0) != hipSuccess || dev_pin == nullptr) return PSX_ERR_HIP;
@@ -396,7 +300,7 @@ int match_pairs_many(int device, const unsigned char* d_left, int l_len, const u
         long long noff = 0;
         for (int k = 0; k < K; k++) {
             hs[k] = ManySet{d_rights[k], r_lens[k], (int)noff, (int)roff[(size_t)k], 0, 0, 0};
-            noff += r_lens[k] > 0 ? ((long long)(r_lens[k] + U8_TILE - 1) / U8_TILE + 1) * U8_TILE : 0;
+            noff += r_lens[k] > 0 ? u8_pad(r_lens[k]) : 0;
         }
         hs[K] = ManySet{d_left, l_len, (int)l_noff, 0, (int)CR, (int)(CR + CL), 0};
         for (long long c = 0; c < CR; c++) {
@@ -411,14 +315,14 @@ int match_pairs_many(int device, const unsigned char* d_left, int l_len, const u
     }
     int* h_total = reinterpret_cast<int*>(hp);
     *h_total = -1;
-    const ManySet* d_sets = static_cast<const ManySet*>(sc.buf[25]);
-    const int4* d_chunks = reinterpret_cast<const int4*>(static_cast<const char*>(sc.buf[25]) + sets_b);
-    const int2* d_blocks = reinterpret_cast<const int2*>(static_cast<const char*>(sc.buf[25]) + sets_b + chunks_b);
-    int* d_norms = static_cast<int*>(sc.buf[26]);
-    uint2* d_partial = static_cast<uint2*>(sc.buf[27]);
-    int* d_fwd = static_cast<int*>(sc.buf[28]);
-    int* d_bwd = mutual ? static_cast<int*>(sc.buf[29]) : nullptr;
-    int* d_tot = static_cast<int*>(sc.buf[30]);
+    const ManySet* d_sets = static_cast<const ManySet*>(sc.buf[MS_MANY_TABLES]);
+    const int4* d_chunks = reinterpret_cast<const int4*>(static_cast<const char*>(sc.buf[MS_MANY_TABLES]) + sets_b);
+    const int2* d_blocks = reinterpret_cast<const int2*>(static_cast<const char*>(sc.buf[MS_MANY_TABLES]) + sets_b + chunks_b);
+    int* d_norms = static_cast<int*>(sc.buf[MS_MANY_NORMS]);
+    uint2* d_partial = static_cast<uint2*>(sc.buf[MS_MANY_PARTIAL]);
+    int* d_fwd = static_cast<int*>(sc.buf[MS_MANY_FWD]);
+    int* d_bwd = mutual ? static_cast<int*>(sc.buf[MS_MANY_BWD]) : nullptr;
+    int* d_tot = static_cast<int*>(sc.buf[MS_MANY_TOT]);
     int* d_offs = d_tot + ntot;
     int* d_total = static_cast<int*>(dev_pin);
     int* d_counts = reinterpret_cast<int*>(static_cast<char*>(dev_pin) + off_counts);
@@ -427,7 +331,7 @@ int match_pairs_many(int device, const unsigned char* d_left, int l_len, const u
     const int cap = host_pairs ? (int)nrec : capacity;
     hipStream_t st = sc.stream;
 
-    if (hipMemcpyAsync(sc.buf[25], hp + off_blob, blob_b, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
+    if (hipMemcpyAsync(sc.buf[MS_MANY_TABLES], hp + off_blob, blob_b, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
     hipLaunchKernelGGL(k_u8_norms_many, dim3((unsigned)(BR + BL)), dim3(256), 0, st, d_sets, d_blocks, d_norms);
     for (const ManyGroup& g : fgroups) {
         const ManyPass ps = {g.nblocks, g.block0, g.chunk0, g.row0, g.rows};

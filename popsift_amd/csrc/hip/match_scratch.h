@@ -1,20 +1,75 @@
-// match_scratch.h -- what the matcher's translation units share (match.hip, match_guided.hip): the per-thread scratch and
-// the runner of the pair join.  Internal to the HIP library.
+// match_scratch.h -- what the matcher's translation units share (match.hip, match_guided.hip, match_many.hip, ransac.hip):
+// the layout of a directed result, the per-thread scratch with its named buffers, and the runner of the pair join.
+// Internal to the HIP library.
 #pragma once
 
 #include "psx_internal.h"
 
+// A DIRECTED RESULT of `len` rows, as every directed matcher leaves it on the device and the joins read it: 3 len ints
+// (best, second, accept per row), then 2 len distances (float, or int for the byte matchers) -- 5 len words in all.
+// The row offsets are formed in the caller's Row type.  k_match_merge and k_match_u8_merge pass int, as they always did:
+// with size_t the row's 64-bit offset stays live across k_match_u8_merge's chunk loop, and psx_match_pairs_u8 at
+// 2048 x 2048 measured 2.7 % slower on one MI355X.
+template <class Dist, class Row>
+__device__ __forceinline__ void psx_directed_store(int* __restrict__ res, size_t len, Row row, int best, int second, bool accept,
+                                                   Dist d1, Dist d2)
+{
+    res[3 * row + 0] = best; res[3 * row + 1] = second; res[3 * row + 2] = accept ? 1 : 0;
+    Dist* dist = reinterpret_cast<Dist*>(res + 3 * len);
+    dist[2 * row + 0] = d1; dist[2 * row + 1] = d2;
+}
+
+// what a join reads of a row: the best index and the two distances; for the cross-check the best index alone
+template <class Dist>
+__device__ __forceinline__ void psx_directed_load(const int* __restrict__ res, size_t len, size_t row, int& best, Dist& d1, Dist& d2)
+{
+    const Dist* dist = reinterpret_cast<const Dist*>(res + 3 * len);
+    best = res[3 * row];
+    d1 = dist[2 * row]; d2 = dist[2 * row + 1];
+}
+__device__ __forceinline__ int psx_directed_best(const int* __restrict__ res, size_t row) { return res[3 * row]; }
+
+// The buffers of a MatchScratch.  A buffer belongs to ONE use: calls queue work without waiting for the stream, so two
+// features sharing a buffer would alias under queued work.  F32: psx_match / psx_match_pairs, U8: psx_match_u8 /
+// psx_match_pairs_u8 (match.hip); GUIDED: match_guided.hip; RANSAC: ransac.hip; MANY: the one-to-many search (match_many.hip)
+enum MatchSlot {
+    MS_F32_PARTIAL,      // the exact scan's per-chunk top-2
+    MS_F32_RPERM,        // the exact scan's permuted right side
+    MS_F32_FWD,          // the directed result (and the prefilter's flag behind it)
+    MS_F32_BWD,          // the backward direction's, psx_match_pairs with the cross-check
+    MS_F32_LF16,         // the prefilter: the left side as f16 ...
+    MS_F32_RF16,         // ... the right side
+    MS_F32_LNORM,        // the left norms, then the seeding pass' minima
+    MS_F32_RNORM,        // the maximum slots and the parameters, then the right norms
+    MS_F32_CAND_CT,      // the candidate counts per (left, segment)
+    MS_F32_CAND,         // the candidates
+    MS_U8_PARTIAL,       // the per-chunk key pairs (both directions, one after the other)
+    MS_U8_NORMS,         // the norms of both sets
+    MS_U8_FWD,           // the directed result
+    MS_U8_BWD,           // the backward direction's
+    MS_PAIRS_TOT,        // the pair join's per-workgroup totals (float and bytes)
+    MS_GUIDED_FWD,       // the forward direction's result
+    MS_GUIDED_BWD,       // the backward direction's
+    MS_GUIDED_LINES,     // the left side's lines for the backward direction
+    MS_RANSAC_PAIRS,     // the uploaded pair records
+    MS_RANSAC_PTS,       // the packed correspondences
+    MS_RANSAC_MODELS,    // the hypotheses' models
+    MS_RANSAC_COUNTS,    // their counts
+    MS_RANSAC_STATE,     // the state block
+    MS_RANSAC_TOT,       // the compaction's per-workgroup totals
+    MS_MANY_TABLES,      // the set / chunk / block tables
+    MS_MANY_NORMS,       // the norms of all sets
+    MS_MANY_PARTIAL,     // the per-chunk key pairs
+    MS_MANY_FWD,         // the forward direction's results of all sets
+    MS_MANY_BWD,         // the backward direction's
+    MS_MANY_TOT,         // the join's per-workgroup totals and their offsets
+    MS_NBUF
+};
+
 // Scratch of one calling thread: a private non-blocking stream (no null-stream launch, so nothing else on
 // the device is synchronised) and buffers that only ever grow.  Freed when the thread exits.
 struct MatchScratch {
-    // 0-9: psx_match, 10-12: psx_match_u8; the pair search: 13 the backward direction's results of psx_match_pairs,
-    // 14 those of psx_match_pairs_u8, 15 the join's per-workgroup totals; guided matching (match_guided.hip): 16 the forward
-    // direction's results, 17 the backward direction's, 18 the left side's lines for the backward direction; the homography
-    // RANSAC (ransac.hip): 19 the uploaded pair records, 20 the packed correspondences, 21 the hypotheses' models, 22 their
-    // counts, 23 the state block, 24 the compaction's per-workgroup totals; the one-to-many byte pair search
-    // (match_many.hip): 25 the set / chunk / block tables, 26 the norms of all sets, 27 the per-chunk partials, 28 the forward
-    // direction's results of all sets, 29 the backward direction's, 30 the join's per-workgroup totals and their offsets
-    static constexpr int NBUF = 31;
+    static constexpr int NBUF = MS_NBUF;
     int device = -1;
     hipStream_t stream = nullptr;
     void* buf[NBUF] = {};
@@ -59,7 +114,7 @@ struct MatchScratch {
         hpin_cap = bytes;
         return true;
     }
-    bool need(int i, size_t bytes)
+    bool need(MatchSlot i, size_t bytes)
     {
         if (bytes <= cap[i] && buf[i]) return true;
         (void)hipFree(buf[i]); buf[i] = nullptr; cap[i] = 0;
@@ -77,10 +132,9 @@ struct MatchScratch {
 MatchScratch& psx_match_scratch();
 
 // Queues the join (k_pairs_count / k_pairs_write, match.hip) behind the directed passes already queued on sc.stream and
-// finishes the call.  d_fwd / d_bwd: a directed pass' device results -- 3 len ints (best, second, accept), then 2 len
-// distances (float / int); d_bwd is read only with PSX_PAIRS_MUTUAL.  host_pairs or d_pairs (the other is NULL; both
-// NULL with capacity 0).  One synchronisation.
-int psx_pairs_finish_f32(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
-                         void* host_pairs, void* d_pairs, int capacity, int* count);
-int psx_pairs_finish_u8(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
-                        void* host_pairs, void* d_pairs, int capacity, int* count);
+// finishes the call.  d_fwd / d_bwd: a directed pass' device results (float / int distances); d_bwd is read only with
+// PSX_PAIRS_MUTUAL.  host_pairs or d_pairs (the other is NULL; both NULL with capacity 0).  One synchronisation.
+// Dist = float or int: defined and instantiated for both in match.hip.
+template <class Dist>
+int psx_pairs_finish(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
+                     void* host_pairs, void* d_pairs, int capacity, int* count);

@@ -15,14 +15,15 @@
 //                    hypothesis one wave64 ballot + popcount per resident pair and ONE integer atomic per wave -- integer
 //                    atomics are order-free, the counts are deterministic
 //   k_ransac_select  single workgroup arg-max on (count descending, index ascending); copies the winner's model
-//   k_ransac_inl_count / _write   the stable compaction of the pair join (match.hip): ballot + mbcnt, exclusive scan across
-//                    workgroups; the payload is any 16-byte record array (the float4s for the refit, the pair records at the end)
+//   k_ransac_inl_count / _write   the stable compaction of wg_compact.h, as the pair join (match.hip) runs it; the payload is
+//                    any 16-byte record array (the float4s for the refit, the pair records at the end)
 //   k_ransac_decide  keeps the refit model iff it may score and its count is not below the winner's
 // The refit's fit is serial by definition: the winner's float4s come to the host through the pinned staging buffer, the
 // model goes back and is scored by the score kernel with N = 1.  One synchronisation without the refit, two with it.
 #include "psx_internal.h"
 #include "fundamental_rule.h"
 #include "match_scratch.h"
+#include "wg_compact.h"
 
 #include <cstring>
 #include <new>
@@ -54,11 +55,6 @@ template <> struct RModel<PSX_GUIDE_EPIPOLAR> {
 };
 
 __device__ __forceinline__ psx_ransac_pt r_pt(const float4& v) { psx_ransac_pt p = {v.x, v.y, v.z, v.w}; return p; }
-
-__device__ __forceinline__ int r_lane_rank(unsigned long long m)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
 
 __global__ void k_ransac_gather(const int4* __restrict__ pairs, int n, const float2* __restrict__ lxy, int l_len,
                                 const float2* __restrict__ rxy, int r_len, float4* __restrict__ pts, int* __restrict__ bad)
@@ -195,11 +191,9 @@ __global__ __launch_bounds__(256) void k_ransac_inl_count(const float4* __restri
                                                           int* __restrict__ wg_tot)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long m = __ballot(r_keep<KIND>(pts, n, st, tol, i));
     __shared__ int s_cnt[4];
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) wg_tot[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    wg_count(__ballot(r_keep<KIND>(pts, n, st, tol, i)), s_cnt);
+    if (threadIdx.x == 0) wg_tot[blockIdx.x] = wg_total(s_cnt);
 }
 
 // src: n 16-byte records (the correspondences themselves, or the pair records); out: never written at or past `capacity`
@@ -208,23 +202,10 @@ __global__ __launch_bounds__(256) void k_ransac_inl_write(const float4* __restri
                                                           const int* __restrict__ wg_tot, const int4* __restrict__ src,
                                                           int4* __restrict__ out, int capacity, int* __restrict__ total)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool keep = r_keep<KIND>(pts, n, st, tol, i);
-    const unsigned long long m = __ballot(keep);
-    int part = 0;
-    for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) part += wg_tot[b];
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) part += __shfl_xor(part, k);
-    __shared__ int s_part[4], s_cnt[4];
-    if (lane == 0) { s_part[wave] = part; s_cnt[wave] = __popcll(m); }
-    __syncthreads();
-    const int base = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-    int woff = 0;
-    for (int w = 0; w < wave; w++) woff += s_cnt[w];
-    const int pos = base + woff + r_lane_rank(m);
+    const int pos = wg_slot(__ballot(keep), wg_tot, total);
     if (keep && pos < capacity) out[pos] = src[i];
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = base + s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
 constexpr size_t R_PIN_STATE = 0, R_PIN_REFIT = 128, R_PIN_REC = 256;      // layout of the pinned staging buffer
@@ -269,8 +250,8 @@ int ransac_run(int device, const void* host_pairs, const void* d_pairs_in, int n
     const int nb = (n + 255) / 256;
     const int nrec = host_inl ? (capacity < n ? capacity : n) : 0;
     // every buffer before the first launch: nothing is reallocated under queued work
-    if ((host_pairs && !sc.need(19, 16 * (size_t)n)) || !sc.need(20, 16 * (size_t)n) || !sc.need(21, sizeof(float) * 9 * (size_t)N) ||
-        !sc.need(22, sizeof(int) * (size_t)N) || !sc.need(23, sizeof(RState)) || !sc.need(24, sizeof(int) * (size_t)nb) ||
+    if ((host_pairs && !sc.need(MS_RANSAC_PAIRS, 16 * (size_t)n)) || !sc.need(MS_RANSAC_PTS, 16 * (size_t)n) || !sc.need(MS_RANSAC_MODELS, sizeof(float) * 9 * (size_t)N) ||
+        !sc.need(MS_RANSAC_COUNTS, sizeof(int) * (size_t)N) || !sc.need(MS_RANSAC_STATE, sizeof(RState)) || !sc.need(MS_RANSAC_TOT, sizeof(int) * (size_t)nb) ||
         !sc.need_pinned(R_PIN_REC + 16 * (size_t)(refit ? n : nrec)))
         return PSX_ERR_NOMEM;
     void* dev_pin = nullptr;
@@ -280,14 +261,14 @@ int ransac_run(int device, const void* host_pairs, const void* d_pairs_in, int n
     hipStream_t st = sc.stream;
     const void* d_pairs = d_pairs_in;
     if (host_pairs) {
-        if (hipMemcpyAsync(sc.buf[19], host_pairs, 16 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
-        d_pairs = sc.buf[19];
+        if (hipMemcpyAsync(sc.buf[MS_RANSAC_PAIRS], host_pairs, 16 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
+        d_pairs = sc.buf[MS_RANSAC_PAIRS];
     }
-    float4* d_pts = static_cast<float4*>(sc.buf[20]);
-    float* d_models = static_cast<float*>(sc.buf[21]);
-    int* d_counts = static_cast<int*>(sc.buf[22]);
-    RState* d_state = static_cast<RState*>(sc.buf[23]);
-    int* d_tot = static_cast<int*>(sc.buf[24]);
+    float4* d_pts = static_cast<float4*>(sc.buf[MS_RANSAC_PTS]);
+    float* d_models = static_cast<float*>(sc.buf[MS_RANSAC_MODELS]);
+    int* d_counts = static_cast<int*>(sc.buf[MS_RANSAC_COUNTS]);
+    RState* d_state = static_cast<RState*>(sc.buf[MS_RANSAC_STATE]);
+    int* d_tot = static_cast<int*>(sc.buf[MS_RANSAC_TOT]);
     const RState* hs = reinterpret_cast<const RState*>(hpin + R_PIN_STATE);
     void* final_out = host_inl ? pin_rec : d_inl;
     const int final_cap = host_inl ? nrec : capacity;

@@ -12,7 +12,7 @@ import pytest
 import torch        # before the HIP library is loaded: torch brings a HIP runtime of its own and must initialise first (_dev forms)
 
 from popsift_amd.synth import synth
-from tests.match_pairs_cases import (INT_MAX, RATIOS, assert_premise, directed, dist_as_int, planted, restate, same_records)
+from tests.match_pairs_cases import (AMPS, INT_MAX, RATIOS, assert_premise, directed, dist_as_int, planted, restate, same_records)
 
 pytestmark = pytest.mark.gpu
 
@@ -137,6 +137,53 @@ def test_compaction_edges(oracle, capi, n):
             assert cnt == 0 and len(part) == 0
     finally:
         other.close()
+
+
+def test_compaction_past_256_workgroups(oracle, capi):
+    """65 793 = 256 * 257 + 1 left rows against 40 right rows: 258 join workgroups, the smallest size at which the last
+    workgroup's sum over the totals of the workgroups before it takes a second trip (it reads totals 0 .. 256 with 256
+    threads).  Left rows are noisy copies of right rows (the amplitudes of the planted sets) with a density that differs
+    from workgroup to workgroup -- none, 5 %, half, all -- so a wrong prefix moves records, not only the total; the only
+    exact copies lie in workgroup 256 and in the last row, so the cross-check keeps rows there and the total depends on
+    workgroup 256's count.  Every ratio, with and without the cross-check, host and device form, all records and the count
+    against the host join of the oracle's directed results."""
+    n, nr = 256 * 257 + 1, 40
+    rng = np.random.default_rng(65793)
+    right = rng.integers(0, 64, (nr, 128), dtype=np.uint8)
+    left = rng.integers(0, 64, (n, 128), dtype=np.uint8)
+    density = rng.choice([0.0, 0.05, 0.5, 1.0], 258)
+    density[256] = 0.5
+    rows = np.nonzero(rng.random(n) < density[np.arange(n) // 256])[0]
+    amp = np.array(AMPS)[rows % len(AMPS)]
+    noise = np.rint((rng.random((len(rows), 128)) * 2 - 1) * amp[:, None]).astype(np.int64)
+    noise[np.arange(len(rows)), rows % 128] += 1                           # never an exact copy
+    left[rows] = np.clip(right[rows % nr].astype(np.int64) + noise, 0, 255).astype(np.uint8)
+    exact = 65536 + 5 * np.arange(nr - 1)
+    left[exact] = right[:nr - 1]
+    left[n - 1] = right[nr - 1]
+    fm, fd, bm, bd = directed(oracle, ("past 256 workgroups",), left, right, True)
+    dev = _OnDevice(capi, left, right)
+    try:
+        for ratio in RATIOS:
+            for mutual in (False, True):
+                want = capi.pairs_join(fm, fd, bm if mutual else None, nr, ratio, mutual)
+                wg = want["left"] // 256
+                assert (wg == 256).any() and want["left"][-1] == n - 1, (ratio, mutual)
+                if not mutual and ratio < 1.0:                             # (from 1.0 on nearly every row survives)
+                    per_wg = np.bincount(wg, minlength=258)
+                    assert (per_wg[:256] == 0).any() and (per_wg[:256] > 100).any(), ratio
+                if ratio == float("inf") and not mutual:
+                    assert len(want) == n and np.array_equal(want["left"], np.arange(n))
+                got = dev.pairs(ratio, mutual)
+                assert same_records(got, want), (ratio, mutual, len(got), len(want))
+                dbuf = torch.full(((n + 1) * 16,), 0xA5, dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()
+                cnt = capi.match_pairs_dev(dev.pl.value, n, dev.pr.value, nr, dbuf.data_ptr(), n, ratio, mutual, u8=True)
+                back = dbuf.cpu().numpy()
+                assert cnt == len(want), (ratio, mutual, cnt, len(want))
+                assert same_records(back[:cnt * 16].view(capi.PAIR_U8_DTYPE), want) and np.all(back[cnt * 16:] == 0xA5), (ratio, mutual)
+    finally:
+        dev.close()
 
 
 # ---- floats -------------------------------------------------------------------------------------------------------------

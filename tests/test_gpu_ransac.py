@@ -86,6 +86,34 @@ def test_device_equals_reference_and_restatement(capi, n, N, seed, refit):
         pos.close()
 
 
+@pytest.mark.parametrize("refit", [False, True], ids=["sample", "refit"])
+def test_inlier_compaction_past_256_workgroups(capi, refit):
+    """65 793 = 256 * 257 + 1 planted pairs, 8 hypotheses: 258 compaction workgroups, the smallest size at which the last
+    workgroup's sum over the totals of the workgroups before it takes a second trip.  Seed 19: the host reference's
+    winning sample keeps 15 793 pairs (36 849 after the refit), 67 (143) of them in workgroup 256 and the last pair in
+    workgroup 257, so both the total and the last record's slot depend on that second trip.  The device result equals
+    psx_ransac_homography_ref: model bits, best, the three counts, every inlier record.  The pure-Python restatement
+    (ransac_cases.expect) is not run at this size: its fit and score are loops in Python."""
+    n, N, seed = 256 * 257 + 1, 8, 19
+    pairs, lxy, rxy, _ = rc.planted(n, seed)
+    opts = capi.ransac_opts(rc.TOL, N, seed, refit)
+    ref = capi.ransac_homography_ref(pairs, lxy, rxy, opts, layers=True)
+    want = rc_dict(ref)
+    assert want["inliers"] == ref["count"] > 5000 and want["refit_kept"] == int(refit)
+    at = np.searchsorted(pairs["d1"], ref["inliers"]["d1"])                 # planted: d1 = the record's index + 1, ascending
+    assert (at // 256 == 256).any() and at[-1] == n - 1
+    pos = _Positions(capi, lxy, rxy)
+    try:
+        rv, res, cnt, out, models, counts = _raw(capi, pos, pairs, opts, n)
+        assert rv == 0
+        assert np.array_equal(rc.bits(models), rc.bits(ref["models"])) and np.array_equal(counts, ref["counts"])
+        assert rc.same_result(res, want), (res.best, res.sample_inliers, res.inliers, res.refit_kept, want)
+        assert cnt == ref["count"]
+        assert rc.same_records(out[:4 * cnt].view(rc.PAIR_DTYPE), ref["inliers"]) and np.all(out[4 * cnt:] == -7)
+    finally:
+        pos.close()
+
+
 def rc_dict(ref):
     r = ref["result"]
     return dict(m=r.matrix(), best=r.best, sample_inliers=r.sample_inliers, inliers=r.inliers, refit_kept=r.refit_kept)
