@@ -557,6 +557,68 @@ int psx_ransac_fundamental_dev(int device, const void* d_pairs, int n, const flo
                                const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
                                void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
 
+/* MANY LISTS IN ONE CALL.  psx_match_pairs_many_u8* leaves the concatenation P_0 .. P_{K-1} of K pair lists and their
+ * counts; these verify all K in one call -- a number of kernel launches that does not grow with n_sets (7 without the
+ * refit, 12 with it) and 1 stream synchronisation without PSX_RANSAC_REFIT, 2 with it, where a loop over psx_ransac_*_dev
+ * pays 6 / 11 launches and 1 / 2 synchronisations per list.  INTEGRATION.md ("Many lists in one call") has the words and
+ * the measured cost.  The arguments are the outputs of psx_match_pairs_many_u8*, unchanged:
+ *   pairs       the concatenation, 16-byte records (host_pairs: HOST; d_pairs: DEVICE, 16-byte aligned);
+ *   set_counts  HOST array of n_sets counts; set k's records start at the sum of the counts before it, and their `right`
+ *               indexes set k's own position array;
+ *   d_left_xy   one left position array of l_len (x, y) pairs;  d_right_xys / r_lens: HOST arrays of n_sets DEVICE
+ *               pointers / lengths -- separate allocations, slices of one buffer, or the same pointer more than once;
+ *   opts        one tol, hypotheses = N, seed and flags for all sets: hypothesis h of set k draws from its own n_k
+ *               exactly as the single call does;
+ *   results     HOST array of n_sets results.
+ * With (result_k, I_k) = what the single call returns at unlimited capacity for (P_k, left_xy, right_xys[k], opts), bit
+ * for bit: results[k] = result_k; the inlier output is the concatenation I_0 .. I_{K-1}, set k's inliers starting at the
+ * sum of results[j].inliers for j < k; *count = the sum over all sets; the first min(*count, capacity) records are
+ * written, nothing at or past capacity; capacity = 0 with a NULL output asks "how many?".  host_models (n_sets x N x 9
+ * floats) and host_counts (n_sets x N ints) receive every set's layers, either may be NULL.
+ * A set with fewer than 4 (homography) / 8 (fundamental) pairs yields the "no model" result, contributes nothing to the
+ * output and has zeros in its rows of host_models / host_counts.  n_sets = 0, or all sets below the minimum, gives
+ * PSX_OK without touching a device.
+ * PSX_ERR_INVALID, with nothing touched and before any device call: everything the single call refuses; n_sets < 0;
+ * set_counts, d_right_xys, r_lens or results NULL with n_sets > 0; a negative count or length; a NULL right array whose
+ * set has pairs or a length; a sum of counts, or n_sets * hypotheses, above 0x3fffffff.  A pair index outside its position
+ * array, in any set that has a model to estimate, gives PSX_ERR_INVALID for the whole call and no inlier record is written.
+ * Scratch (psx_match_release) and thread safety as psx_ransac_*.  Synchronous. */
+int psx_ransac_homography_many(int device, const void* host_pairs, const int* set_counts, int n_sets,
+                               const float* d_left_xy, int l_len, const float* const* d_right_xys, const int* r_lens,
+                               const psx_ransac_opts* opts, psx_ransac_result* results,
+                               void* host_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_homography_many_dev(int device, const void* d_pairs, const int* set_counts, int n_sets,
+                                   const float* d_left_xy, int l_len, const float* const* d_right_xys, const int* r_lens,
+                                   const psx_ransac_opts* opts, psx_ransac_result* results,
+                                   void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_fundamental_many(int device, const void* host_pairs, const int* set_counts, int n_sets,
+                                const float* d_left_xy, int l_len, const float* const* d_right_xys, const int* r_lens,
+                                const psx_ransac_opts* opts, psx_ransac_result* results,
+                                void* host_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_fundamental_many_dev(int device, const void* d_pairs, const int* set_counts, int n_sets,
+                                    const float* d_left_xy, int l_len, const float* const* d_right_xys, const int* r_lens,
+                                    const psx_ransac_opts* opts, psx_ransac_result* results,
+                                    void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
+/* Host only, no device and no context: the loop over the single-list rule on host arrays (right_xys: n_sets HOST pointers),
+ * with the same argument checks; every pair index of every set is checked before anything is written. */
+int psx_ransac_homography_many_ref(const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
+                                   const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                   psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts);
+int psx_ransac_fundamental_many_ref(const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
+                                    const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                    psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts);
+
+/* How the batched calls cut the concatenated list, on the HOST: no device, no context (csrc/hip/ransac_many_plan.h, the
+ * function the library itself plans with: block_rows = 512 for the score kernel, 256 for the gather and the compaction).
+ * A block is pairs [first, end) of the CONCATENATION, all of one set, end - first <= block_rows; a set's blocks are
+ * ascending and contiguous and cover it exactly once; a set with fewer than min_pairs pairs contributes no block.
+ * *block_count is always the total; the first min(total, capacity) entries are written (capacity 0 with NULL: "how
+ * many?").  PSX_ERR_INVALID for n_sets < 0, a NULL set_counts with n_sets > 0, a negative count, a sum of counts above
+ * 0x3fffffff, min_pairs < 1, block_rows < 1, a NULL block_count, a negative capacity, a NULL table with a capacity. */
+typedef struct psx_ransac_block { int set, first, end; } psx_ransac_block;
+int psx_ransac_many_plan(const int* set_counts, int n_sets, int min_pairs, int block_rows,
+                         psx_ransac_block* blocks, int capacity, int* block_count);
+
 /* ---- caller-supplied keypoints ------------------------------------------------------------
  * Describing points the caller brings along instead of the ones the DoG detector finds (what OpenCV calls
  * useProvidedKeypoints and VLFeat calls frames; the reference has no counterpart).  A record carries what a

@@ -103,6 +103,8 @@ SYMBOLS = [
     "psx_ransac_opts_default", "psx_ransac_samples", "psx_homography_fit", "psx_ransac_homography_ref",
     "psx_ransac_homography", "psx_ransac_homography_dev",
     "psx_ransac_samples_k", "psx_fundamental_fit", "psx_ransac_fundamental_ref", "psx_ransac_fundamental", "psx_ransac_fundamental_dev",
+    "psx_ransac_homography_many", "psx_ransac_homography_many_dev", "psx_ransac_homography_many_ref",
+    "psx_ransac_fundamental_many", "psx_ransac_fundamental_many_dev", "psx_ransac_fundamental_many_ref", "psx_ransac_many_plan",
 ]
 
 PAIRS_MUTUAL = 1     # PSX_PAIRS_MUTUAL
@@ -251,6 +253,11 @@ def lib():
         for n in ("psx_ransac_homography", "psx_ransac_homography_dev", "psx_ransac_fundamental", "psx_ransac_fundamental_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(RansacOpts), C.POINTER(RansacResult),
                                       vp, C.c_int, ip, vp, vp]
+        for n in ("psx_ransac_homography_many", "psx_ransac_homography_many_dev", "psx_ransac_fundamental_many", "psx_ransac_fundamental_many_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(RansacOpts), vp, vp, C.c_int, ip, vp, vp]
+        for n in ("psx_ransac_homography_many_ref", "psx_ransac_fundamental_many_ref"):
+            getattr(L, n).argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(RansacOpts), vp, vp, C.c_int, ip, vp, vp]
+        L.psx_ransac_many_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, ip]
         _LIB = L
     return _LIB
 
@@ -827,6 +834,129 @@ def ransac_fundamental_dev(pairs_ptr, n, left_xy_ptr, l_len, right_xy_ptr, r_len
     """psx_ransac_fundamental_dev on DEVICE pointers: as ransac_homography_dev"""
     return ransac_homography_dev(pairs_ptr, n, left_xy_ptr, l_len, right_xy_ptr, r_len, out_ptr, capacity, opts, device, layers,
                                  model="fundamental")
+
+
+def _ransac_many_call(fn, name, pairs_ptr, set_counts, dtype, plx, nl, right_ptrs, r_lens, opts, capacity, layers, out_ptr=None,
+                      kind=GUIDE_HOMOGRAPHY):
+    """One batched RANSAC call on K pair lists behind one another.  out_ptr None: the inliers come back in a host array.
+    Returns a dict: results (K RansacResult), count (all inliers), and for the host forms records (the concatenated inlier
+    records) and inliers (one array per set, cut by split_sets); with layers models (K, N, 9) and counts (K, N)."""
+    k = len(set_counts)
+    sc = np.ascontiguousarray(set_counts, dtype=np.int32)
+    lens = np.ascontiguousarray(r_lens, dtype=np.int32)
+    ptrs = (C.c_void_p * max(k, 1))(*[p.value if isinstance(p, C.c_void_p) else p for p in right_ptrs])
+    n = int(sc.sum())
+    cap = n if capacity is None else capacity
+    N = max(int(opts.hypotheses), 0)
+    res, cnt = (RansacResult * max(k, 1))(), C.c_int(-1)
+    out = np.zeros((cap,), dtype) if out_ptr is None else None
+    models = np.zeros((k, N, 9), np.float32) if layers else None
+    counts = np.zeros((k, N), np.int32) if layers else None
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    po = ptr(out) if out_ptr is None else (C.c_void_p(out_ptr) if cap else None)
+    rc = fn(pairs_ptr, ptr(sc), k, plx, nl, ptrs if k else None, ptr(lens), C.byref(opts), res if k else None, po, cap, C.byref(cnt),
+            ptr(models), ptr(counts))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    results = []
+    for i in range(k):
+        r = RansacResult.from_buffer_copy(res[i])
+        r.kind = kind
+        results.append(r)
+    got = dict(results=results, count=cnt.value)
+    if out is not None:
+        got["records"] = out[:min(cnt.value, cap)]
+        got["inliers"] = split_sets(got["records"], [r.inliers for r in results])
+    if layers:
+        got["models"], got["counts"] = models, counts
+    return got
+
+
+def _pair_lists(pair_lists):
+    """per-set record arrays -> (the concatenation, the counts)"""
+    lists = [_pair_records(p) for p in pair_lists]
+    dtype = lists[0].dtype if lists else PAIR_DTYPE
+    return (np.concatenate(lists) if lists else np.zeros((0,), dtype)), [len(p) for p in lists]
+
+
+def ransac_homography_many_ref(pair_lists, left_xy, right_xys, opts=None, capacity=None, layers=False, model="homography"):
+    """psx_ransac_homography_many_ref: the loop over the single-list rule on host arrays, no device.  pair_lists: one
+    PAIR_DTYPE / PAIR_U8_DTYPE array per set (what match_pairs_many_u8 returns), `right` indexing right_xys[k]; left_xy: one
+    (nl, 2) array.  Returns the dict of _ransac_many_call."""
+    L = lib()
+    pairs, set_counts = _pair_lists(pair_lists)
+    lx, rxs = _xy(left_xy), [_xy(r) for r in right_xys]
+    opts = opts or ransac_opts()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    name, kind = _ransac_names(model)
+    return _ransac_many_call(getattr(L, name + "_many_ref"), name + "_many_ref", ptr(pairs), set_counts, pairs.dtype, ptr(lx), len(lx),
+                             [r.ctypes.data if r.size else None for r in rxs], [len(r) for r in rxs], opts, capacity, layers, kind=kind)
+
+
+def ransac_homography_many(pair_lists, left_xy, right_xys, opts=None, device=0, capacity=None, layers=False, model="homography"):
+    """psx_ransac_homography_many on host arrays (the positions go through device buffers): K pair lists verified in ONE
+    call; set k's result and inliers equal ransac_homography(pair_lists[k], left_xy, right_xys[k], opts)."""
+    L = lib()
+    pairs, set_counts = _pair_lists(pair_lists)
+    lx, rxs = _xy(left_xy), [_xy(r) for r in right_xys]
+    opts = opts or ransac_opts()
+    bufs = []
+    try:
+        ptrs = _to_device(L, device, [lx] + rxs, bufs)
+        name, kind = _ransac_names(model)
+        fn = lambda *a: getattr(L, name + "_many")(device, *a)
+        return _ransac_many_call(fn, name + "_many", pairs.ctypes.data_as(C.c_void_p) if pairs.size else None, set_counts, pairs.dtype,
+                                 ptrs[0], len(lx), ptrs[1:], [len(r) for r in rxs], opts, capacity, layers, kind=kind)
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def ransac_homography_many_dev(pairs_ptr, set_counts, left_xy_ptr, l_len, right_xy_ptrs, r_lens, out_ptr, capacity, opts=None, device=0,
+                               layers=False, model="homography"):
+    """psx_ransac_homography_many_dev on DEVICE pointers: pairs_ptr and set_counts are what match_pairs_many_dev left and
+    returned; the concatenated inlier records are written in device memory (16-byte aligned, `capacity` records).  Returns
+    a dict: results, count, and with layers the per-set models and counts."""
+    L = lib()
+    opts = opts or ransac_opts()
+    vp = lambda p: C.c_void_p(p) if p else None
+    name, kind = _ransac_names(model)
+    fn = lambda *a: getattr(L, name + "_many_dev")(device, *a)
+    return _ransac_many_call(fn, name + "_many_dev", vp(pairs_ptr), set_counts, None, vp(left_xy_ptr), l_len, list(right_xy_ptrs), r_lens,
+                             opts, capacity, layers, out_ptr=out_ptr or 0, kind=kind)
+
+
+def ransac_fundamental_many_ref(pair_lists, left_xy, right_xys, opts=None, capacity=None, layers=False):
+    """psx_ransac_fundamental_many_ref: as ransac_homography_many_ref for fundamental matrices"""
+    return ransac_homography_many_ref(pair_lists, left_xy, right_xys, opts, capacity, layers, model="fundamental")
+
+
+def ransac_fundamental_many(pair_lists, left_xy, right_xys, opts=None, device=0, capacity=None, layers=False):
+    """psx_ransac_fundamental_many on host arrays: as ransac_homography_many; every result's guide is an epipolar one"""
+    return ransac_homography_many(pair_lists, left_xy, right_xys, opts, device, capacity, layers, model="fundamental")
+
+
+def ransac_fundamental_many_dev(pairs_ptr, set_counts, left_xy_ptr, l_len, right_xy_ptrs, r_lens, out_ptr, capacity, opts=None, device=0,
+                                layers=False):
+    """psx_ransac_fundamental_many_dev on DEVICE pointers: as ransac_homography_many_dev"""
+    return ransac_homography_many_dev(pairs_ptr, set_counts, left_xy_ptr, l_len, right_xy_ptrs, r_lens, out_ptr, capacity, opts, device,
+                                      layers, model="fundamental")
+
+
+def ransac_many_plan(set_counts, min_pairs, block_rows):
+    """psx_ransac_many_plan: the (n, 3) int32 blocks = set, first, end of the concatenated list.  No device."""
+    L = lib()
+    sc = np.ascontiguousarray(set_counts, dtype=np.int32)
+    nb = C.c_int(-1)
+    args = (sc.ctypes.data_as(C.c_void_p) if len(sc) else None, len(sc), min_pairs, block_rows)
+    rc = L.psx_ransac_many_plan(*args, None, 0, C.byref(nb))
+    if rc != 0:
+        raise PopSiftError("psx_ransac_many_plan failed (%d)" % rc)
+    blocks = np.zeros((nb.value, 3), np.int32)
+    rc = L.psx_ransac_many_plan(*args, blocks.ctypes.data_as(C.c_void_p) if nb.value else None, nb.value, C.byref(nb))
+    if rc != 0:
+        raise PopSiftError("psx_ransac_many_plan failed (%d)" % rc)
+    return blocks
 
 
 class DeviceDescriptors:

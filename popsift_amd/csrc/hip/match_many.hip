@@ -139,29 +139,10 @@ __global__ __launch_bounds__(256) void k_many_count(const ManySet* __restrict__ 
     if (threadIdx.x == 0) wg_tot[blockIdx.x] = wg_total(s_cnt);
 }
 
-// ONE workgroup of 1024 threads: offs[w] = the totals before workgroup w, offs[n] = all of them.  1024 totals per round:
-// a wave scan (shuffles), the 16 wave sums through LDS, the carry of the rounds before.
+// ONE workgroup of 1024 threads: offs[w] = the totals before workgroup w, offs[n] = all of them (wg_compact.h)
 __global__ __launch_bounds__(1024) void k_many_scan(const int* __restrict__ wg_tot, int n, int* __restrict__ offs)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __shared__ int s_wave[16];
-    int carry = 0;
-    for (int base = 0; base < n; base += 1024) {
-        const int w = base + (int)threadIdx.x;
-        const int v = w < n ? wg_tot[w] : 0;
-        int incl = v;
-#pragma unroll
-        for (int k = 1; k < 64; k <<= 1) { const int o = __shfl_up(incl, k); if (lane >= k) incl += o; }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int q = 0; q < 16; q++) { const int t = s_wave[q]; all += t; if (q < wave) before += t; }
-        if (w < n) offs[w] = carry + before + incl - v;
-        carry += all;
-        __syncthreads();                                     // s_wave is rewritten in the next round
-    }
-    if (threadIdx.x == 0) offs[n] = carry;
+    wg_scan_totals(wg_tot, n, offs);
 }
 
 // grid as k_many_count.  Evaluates the rule again (k_pairs_write: cheaper than parking the verdicts), ranks its lanes and

@@ -21,8 +21,8 @@
 // The refit's fit is serial by definition: the winner's float4s come to the host through the pinned staging buffer, the
 // model goes back and is scored by the score kernel with N = 1.  One synchronisation without the refit, two with it.
 #include "psx_internal.h"
-#include "fundamental_rule.h"
 #include "match_scratch.h"
+#include "ransac_model.h"
 #include "wg_compact.h"
 
 #include <cstring>
@@ -40,21 +40,7 @@ struct RState {                              // device resident, copied to the h
     float refit[9];
 };
 
-// What differs between the two estimators, by the kind of guide the model is (PSX_GUIDE_HOMOGRAPHY: ransac_rule.h;
-// PSX_GUIDE_EPIPOLAR: fundamental_rule.h): the sample size, which models may score, the serial fit of the refit.
-template <int KIND> struct RModel;
-template <> struct RModel<PSX_GUIDE_HOMOGRAPHY> {
-    static constexpr int MIN = 4;
-    static __host__ __device__ __forceinline__ bool usable(const float* m) { return psx_ransac_model_finite(m); }
-    static void fit(const psx_ransac_pt* pt, int n, float* m) { psx_homography_fit_rule<0>(pt, n, m); }
-};
-template <> struct RModel<PSX_GUIDE_EPIPOLAR> {
-    static constexpr int MIN = PSX_FUND_MIN;
-    static __host__ __device__ __forceinline__ bool usable(const float* m) { return psx_fund_model_usable(m); }
-    static void fit(const psx_ransac_pt* pt, int n, float* m) { psx_fundamental_fit_rule<0>(pt, n, m); }
-};
-
-__device__ __forceinline__ psx_ransac_pt r_pt(const float4& v) { psx_ransac_pt p = {v.x, v.y, v.z, v.w}; return p; }
+// RModel<KIND> -- what differs between the two estimators -- , r_pt and r_better: ransac_model.h
 
 __global__ void k_ransac_gather(const int4* __restrict__ pairs, int n, const float2* __restrict__ lxy, int l_len,
                                 const float2* __restrict__ rxy, int r_len, float4* __restrict__ pts, int* __restrict__ bad)
@@ -136,11 +122,6 @@ __global__ __launch_bounds__(256) void k_ransac_score(const float4* __restrict__
         }
         if (lane == 0 && c > 0) atomicAdd(counts + h, c);
     }
-}
-
-__device__ __forceinline__ void r_better(int& bc, int& bh, int c, int h)
-{
-    if (c > bc || (c == bc && h < bh)) { bc = c; bh = h; }
 }
 
 // one workgroup of 256 threads

@@ -1,0 +1,527 @@
+// ransac_many.hip -- geometric verification of many pair lists in one call: psx_ransac_homography_many (+ _dev, _ref),
+// psx_ransac_fundamental_many (+ _dev, _ref), psx_ransac_many_plan (include/popsift_hip.h).
+//
+// psx_ransac_*_dev (ransac.hip) is a fixed sequence of launches and one or two synchronisations per pair list.  A list
+// has a few hundred to a few thousand pairs: at that size the kernels are nearly empty and the call is launch latency and
+// round trips, paid again for every list.  Here the K lists that psx_match_pairs_many_u8* left behind one another are
+// verified by the SAME sequence, every kernel one grid over all sets, driven by tables in which no block crosses a set
+// boundary (ransac_many_plan.h).  The rule -- samples, fit, score, select, refit, inliers -- is ransac_rule.h and
+// fundamental_rule.h, used as they are: set k's result is the single call's, bit for bit.
+//   k_rmany_gather  the four floats of every pair of every set that has a model to estimate, into ONE packed float4 array
+//                   indexed as the concatenation; set k's right positions through the set table (out-of-range indices
+//                   raise the one flag and write NaNs)
+//   k_rmany_hyp     one lane per (set, hypothesis): the sample drawn from the set's own n_k, the fixed-size fit in
+//                   registers; a set below the minimum gets zeros
+//   k_rmany_score   the hot kernel.  As k_ransac_score: lanes own pairs in VGPRs, the workgroup walks a block of M_HB
+//                   hypotheses; the block-table entry and with it the model address models[(set N + h) 9] are workgroup
+//                   uniform (scalar loads); one ballot + popcount per resident pair, ONE integer atomic per wave into
+//                   counts[set N + h] -- integer atomics are order-free, the counts are deterministic.  A wave owns M_PPL x 64
+//                   CONSECUTIVE pairs of its block, and a wave without a resident pair leaves before the loop: a short
+//                   set's last block is mostly such waves
+//   k_rmany_select  one workgroup per set: arg-max on (count descending, index ascending), copies the winner's model
+//   k_rmany_count / k_rmany_scan / k_rmany_write   the stable compaction of wg_compact.h, segmented as the one-to-many
+//                   join (match_many.hip) runs it: one total per 256-pair workgroup in set-major order, an exclusive scan
+//                   of the totals by one workgroup, one 16-byte store per survivor; a set's total is the difference of the
+//                   scan at its boundaries.  No atomics.  The payload is any 16-byte record array
+//   k_rmany_decide  one lane per set: keeps the refit model iff it was tried, may score and does not lose inliers
+// The refit's fit is serial by definition: every set's winner correspondences come to the host through the pinned
+// staging buffer in ONE compaction, the host fits the sets whose refit is due, ONE upload carries all refit models with a
+// per-set "tried" word, and the score kernel runs once more with one model per set.
+// Launches per call, whatever K is: the table copy and a memset, then gather, hyp, score, select and the compaction's 3 --
+// 7 kernels and 1 synchronisation without the refit; with it 5 more (score, decide, the compaction's 3) -- 12 kernels and
+// 2 synchronisations.
+#include "psx_internal.h"
+#include "match_scratch.h"
+#include "ransac_many_plan.h"
+#include "ransac_model.h"
+#include "wg_compact.h"
+
+#include <cmath>
+#include <cstring>
+#include <new>
+
+namespace {
+
+constexpr int M_PPL = PSX_RANSAC_MANY_SCORE_ROWS / 256;    // pairs resident per lane of the score kernel
+constexpr int M_HB = 64;                                    // hypotheses per workgroup of the score kernel
+static_assert(M_PPL * 256 == PSX_RANSAC_MANY_SCORE_ROWS && PSX_RANSAC_MANY_ROWS == 256, "block sizes");
+
+struct RMSet {                               // one entry per set
+    const float2* rxy;                       // its right positions
+    int r_len;
+    int n;                                   // its pairs
+    int off;                                 // its first pair in the concatenation
+    int b0, b1;                              // its blocks in the 256-pair table (b0 == b1: below the minimum)
+    int pad;
+};
+static_assert(sizeof(RMSet) == 32, "two 16-byte scalar loads per entry");
+
+struct RMHead { int bad, total, pad[2]; };   // device resident, in front of the states: the one flag, the sum of the totals
+struct RMState {                             // per set; copied to the host with the head at the end of a stage
+    float kept[9];
+    int best, sample_inliers, refit_kept, total, pad[3];
+};
+struct RMRefit {                             // per set; uploaded in one copy before the refit's score launch
+    int tried, count;
+    float m[9];
+    int pad;
+};
+static_assert(sizeof(RMHead) == 16 && sizeof(RMState) == 64 && sizeof(RMRefit) == 48, "state layout");
+constexpr int RM_REFIT_WORDS = sizeof(RMRefit) / 4;
+
+// grid: the 256-pair blocks
+__global__ __launch_bounds__(256) void k_rmany_gather(const int4* __restrict__ pairs, const RMSet* __restrict__ sets,
+                                                      const int4* __restrict__ blocks, const float2* __restrict__ lxy, int l_len,
+                                                      float4* __restrict__ pts, int* __restrict__ bad)
+{
+    const int4 blk = blocks[blockIdx.x];
+    const RMSet s = sets[blk.x];
+    const int p = blk.y + (int)threadIdx.x;
+    if (p >= blk.z) return;
+    const int4 rec = pairs[p];
+    if (rec.x < 0 || rec.x >= l_len || rec.y < 0 || rec.y >= s.r_len) {
+        atomicOr(bad, 1);
+        pts[p] = make_float4(NAN, NAN, NAN, NAN);
+        return;
+    }
+    const float2 a = lxy[rec.x], b = s.rxy[rec.y];
+    pts[p] = make_float4(a.x, a.y, b.x, b.y);
+}
+
+// the sample and the fixed-size fit of a model kind: the bodies of k_ransac_hyp / k_ransac_hyp_fund
+template <int KIND> __device__ __forceinline__ void rmany_fit(const float4* __restrict__ pts, int n, unsigned seed, int h, float m[9]);
+template <> __device__ __forceinline__ void rmany_fit<PSX_GUIDE_HOMOGRAPHY>(const float4* __restrict__ pts, int n, unsigned seed, int h, float m[9])
+{
+    int idx[4];
+    psx_ransac_sample(seed, h, n, idx);
+    psx_ransac_pt q[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) q[k] = r_pt(pts[idx[k]]);
+    psx_homography_fit_rule<4>(q, 4, m);
+}
+template <> __device__ __forceinline__ void rmany_fit<PSX_GUIDE_EPIPOLAR>(const float4* __restrict__ pts, int n, unsigned seed, int h, float m[9])
+{
+    int idx[PSX_FUND_MIN];
+    psx_ransac_sample_k<PSX_FUND_MIN>(seed, h, n, idx);
+    psx_ransac_pt q[PSX_FUND_MIN];
+#pragma unroll
+    for (int k = 0; k < PSX_FUND_MIN; k++) q[k] = r_pt(pts[idx[k]]);
+    psx_fundamental_fit_rule<PSX_FUND_MIN>(q, PSX_FUND_MIN, m);
+}
+
+// grid K * hw (hw = ceil(N / 64)) waves, workgroup k * hw + w: one lane per (set, hypothesis)
+template <int KIND>
+__global__ __launch_bounds__(64) void k_rmany_hyp(const float4* __restrict__ pts, const RMSet* __restrict__ sets, int hw, unsigned seed, int N,
+                                                  float* __restrict__ models, int* __restrict__ counts)
+{
+    const int k = (int)(blockIdx.x / (unsigned)hw);
+    const int h = (int)(blockIdx.x % (unsigned)hw) * 64 + (int)threadIdx.x;
+    if (h >= N) return;
+    const RMSet s = sets[k];
+    float m[9];
+    if (s.n >= RModel<KIND>::MIN) rmany_fit<KIND>(pts + s.off, s.n, seed, h, m);          // workgroup uniform
+    else {
+#pragma unroll
+        for (int j = 0; j < 9; j++) m[j] = 0.0f;
+    }
+    const size_t at = (size_t)k * (size_t)N + (size_t)h;
+#pragma unroll
+    for (int j = 0; j < 9; j++) models[9 * at + j] = m[j];
+    counts[at] = 0;
+}
+
+// grid nsb * ceil(N / M_HB), workgroup hb * nsb + b: block b of the score table x hypotheses [hb M_HB, + M_HB) of ITS set.
+// Model (set, h) lies at models + (set N + h) mstride, its count at counts + (set N + h) cstride: 9 and 1 for the
+// hypotheses, the RMRefit array (N = 1) for the refit.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_rmany_score(const float4* __restrict__ pts, const int4* __restrict__ blocks, int nsb,
+                                                     const float* __restrict__ models, int N, int mstride, float tol,
+                                                     int* __restrict__ counts, int cstride)
+{
+    const int4 blk = blocks[blockIdx.x % (unsigned)nsb];
+    const int lane = threadIdx.x & 63;
+    const int wave0 = blk.y + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * (64 * M_PPL);
+    if (wave0 >= blk.z) return;                                            // no resident pair in this wave
+    psx_ransac_pt q[M_PPL];
+    bool in[M_PPL];
+#pragma unroll
+    for (int k = 0; k < M_PPL; k++) {
+        const int p = wave0 + k * 64 + lane;
+        in[k] = p < blk.z;
+        q[k] = r_pt(in[k] ? pts[p] : make_float4(0.f, 0.f, 0.f, 0.f));
+    }
+    const int h0 = (int)(blockIdx.x / (unsigned)nsb) * M_HB;
+    const int h1 = h0 + M_HB < N ? h0 + M_HB : N;
+    const size_t row = (size_t)blk.x * (size_t)N;
+    for (int h = h0; h < h1; h++) {
+        float m[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) m[k] = models[(row + h) * mstride + k];    // workgroup-uniform address
+        if (!RModel<KIND>::usable(m)) continue;                           // workgroup uniform
+        int c = 0;
+#pragma unroll
+        for (int k = 0; k < M_PPL; k++) {
+            const psx_guide_line l = psx_guide_left(KIND, m, tol, q[k].xl, q[k].yl);
+            c += __popcll(__ballot(in[k] && psx_guide_right(KIND, l, q[k].xr, q[k].yr)));
+        }
+        if (lane == 0 && c > 0) atomicAdd(counts + (row + h) * cstride, c);
+    }
+}
+
+// one workgroup of 256 threads per set
+__global__ __launch_bounds__(256) void k_rmany_select(const RMSet* __restrict__ sets, const int* __restrict__ counts, int N,
+                                                      const float* __restrict__ models, RMState* __restrict__ st)
+{
+    const int set = blockIdx.x;
+    if (sets[set].b0 == sets[set].b1) return;                              // below the minimum: its state stays zero
+    const size_t row = (size_t)set * (size_t)N;
+    int bc = -1, bh = 0x7fffffff;
+    for (int h = threadIdx.x; h < N; h += 256) r_better(bc, bh, counts[row + h], h);
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+        const int oc = __shfl_xor(bc, k), oh = __shfl_xor(bh, k);
+        r_better(bc, bh, oc, oh);
+    }
+    __shared__ int s_c[4], s_h[4];
+    if ((threadIdx.x & 63) == 0) { s_c[threadIdx.x >> 6] = bc; s_h[threadIdx.x >> 6] = bh; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) r_better(bc, bh, s_c[w], s_h[w]);
+        st[set].best = bh; st[set].sample_inliers = bc;                    // N >= 1: thread 0 saw hypothesis 0
+        for (int k = 0; k < 9; k++) st[set].kept[k] = models[9 * (row + bh) + k];
+    }
+}
+
+// one lane per set
+template <int KIND>
+__global__ __launch_bounds__(256) void k_rmany_decide(RMState* __restrict__ st, const RMRefit* __restrict__ rf, int n_sets)
+{
+    const int set = blockIdx.x * 256 + threadIdx.x;
+    if (set >= n_sets || rf[set].tried == 0) return;
+    float m[9];
+    for (int k = 0; k < 9; k++) m[k] = rf[set].m[k];
+    if (RModel<KIND>::usable(m) && rf[set].count >= st[set].sample_inliers) {
+        for (int k = 0; k < 9; k++) st[set].kept[k] = m[k];
+        st[set].refit_kept = 1;
+    }
+}
+
+// keep: pair i of block blk passes under its set's kept model (no pair does under one that may not score, or after a bad
+// index).  The state is read at a workgroup-uniform address.
+template <int KIND>
+__device__ __forceinline__ bool rmany_keep(const float4* __restrict__ pts, const int4 blk, const RMHead* __restrict__ head,
+                                           const RMState* __restrict__ st, float tol, int i)
+{
+    float m[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) m[k] = st[blk.x].kept[k];
+    if (head->bad != 0 || !RModel<KIND>::usable(m) || i >= blk.z) return false;
+    const psx_ransac_pt p = r_pt(pts[i]);
+    return psx_guide_right(KIND, psx_guide_left(KIND, m, tol, p.xl, p.yl), p.xr, p.yr);
+}
+
+// grid: the 256-pair blocks, set-major as the table is
+template <int KIND>
+__global__ __launch_bounds__(256) void k_rmany_count(const float4* __restrict__ pts, const int4* __restrict__ blocks,
+                                                     const RMHead* __restrict__ head, const RMState* __restrict__ st, float tol,
+                                                     int* __restrict__ wg_tot)
+{
+    const int4 blk = blocks[blockIdx.x];
+    __shared__ int s_cnt[4];
+    wg_count(__ballot(rmany_keep<KIND>(pts, blk, head, st, tol, blk.y + (int)threadIdx.x)), s_cnt);
+    if (threadIdx.x == 0) wg_tot[blockIdx.x] = wg_total(s_cnt);
+}
+
+// ONE workgroup of 1024 threads (wg_compact.h)
+__global__ __launch_bounds__(1024) void k_rmany_scan(const int* __restrict__ wg_tot, int n, int* __restrict__ offs)
+{
+    wg_scan_totals(wg_tot, n, offs);
+}
+
+// grid as k_rmany_count.  src: the concatenation's 16-byte records (the correspondences themselves, or the pair records);
+// out: never written at or past `capacity`.  A set's first workgroup writes the set's total, workgroup 0 the sum.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_rmany_write(const float4* __restrict__ pts, const RMSet* __restrict__ sets,
+                                                     const int4* __restrict__ blocks, RMHead* __restrict__ head, RMState* __restrict__ st,
+                                                     float tol, const int* __restrict__ offs, const int4* __restrict__ src,
+                                                     int4* __restrict__ out, int capacity)
+{
+    const int4 blk = blocks[blockIdx.x];
+    const int i = blk.y + (int)threadIdx.x;
+    const bool keep = rmany_keep<KIND>(pts, blk, head, st, tol, i);
+    const unsigned long long m = __ballot(keep);
+    __shared__ int s_cnt[4];
+    wg_count(m, s_cnt);
+    const int pos = offs[blockIdx.x] + wg_offset(m, s_cnt);
+    if (keep && pos < capacity) out[pos] = src[i];
+    if (threadIdx.x == 0) {
+        const RMSet s = sets[blk.x];
+        if ((int)blockIdx.x == s.b0) st[blk.x].total = offs[s.b1] - offs[s.b0];
+        if (blockIdx.x == 0) head->total = offs[gridDim.x];
+    }
+}
+
+size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// what a call holds while it queues: the device arrays and the launch shapes
+struct RMQueue {
+    hipStream_t st;
+    const RMSet* d_sets;
+    const int4 *d_sblk, *d_cblk;
+    int nsb, ncb, K;
+    float4* d_pts;
+    RMHead* d_head;
+    RMState* d_state;
+    int *d_tot, *d_offs;
+    float tol;
+};
+
+template <int KIND>
+void queue_score(const RMQueue& q, const float* d_models, int N, int mstride, int* d_counts, int cstride)
+{
+    const unsigned hb = (unsigned)((N + M_HB - 1) / M_HB);
+    hipLaunchKernelGGL(k_rmany_score<KIND>, dim3((unsigned)q.nsb * hb), dim3(256), 0, q.st, q.d_pts, q.d_sblk, q.nsb, d_models, N, mstride, q.tol,
+                       d_counts, cstride);
+}
+
+template <int KIND>
+void queue_compact(const RMQueue& q, const void* src, void* out, int cap)
+{
+    hipLaunchKernelGGL(k_rmany_count<KIND>, dim3((unsigned)q.ncb), dim3(256), 0, q.st, q.d_pts, q.d_cblk, q.d_head, q.d_state, q.tol, q.d_tot);
+    hipLaunchKernelGGL(k_rmany_scan, dim3(1), dim3(1024), 0, q.st, q.d_tot, q.ncb, q.d_offs);
+    hipLaunchKernelGGL(k_rmany_write<KIND>, dim3((unsigned)q.ncb), dim3(256), 0, q.st, q.d_pts, q.d_sets, q.d_cblk, q.d_head, q.d_state, q.tol,
+                       q.d_offs, static_cast<const int4*>(src), static_cast<int4*>(out), cap);
+}
+
+// host_pairs or d_pairs_in; host_inl or d_inl (the other is NULL; both NULL with capacity 0)
+template <int KIND>
+int ransac_many_run(int device, const void* host_pairs, const void* d_pairs_in, const int* set_counts, int n_sets, const float* d_lxy, int l_len,
+                    const float* const* d_rxys, const int* r_lens, const psx_ransac_opts* opts, psx_ransac_result* results, void* host_inl,
+                    void* d_inl, int capacity, int* count, float* host_models, int* host_counts)
+{
+    long long total_pairs = 0;
+    if (!psx_ransac_many_args_ok(host_pairs ? host_pairs : d_pairs_in, set_counts, n_sets, d_lxy, l_len, d_rxys, r_lens, opts, results,
+                                 host_inl ? host_inl : d_inl, capacity, count, &total_pairs))
+        return PSX_ERR_INVALID;
+    constexpr int MIN = RModel<KIND>::MIN;
+    const int K = n_sets, N = opts->hypotheses, n = (int)total_pairs;
+    const long long nsb = psx_ransac_many_blocks(set_counts, K, MIN, PSX_RANSAC_MANY_SCORE_ROWS, nullptr, 0);
+    const long long ncb = psx_ransac_many_blocks(set_counts, K, MIN, PSX_RANSAC_MANY_ROWS, nullptr, 0);
+    if (ncb == 0) { psx_ransac_many_none(K, N, results, count, host_models, host_counts); return PSX_OK; }
+    for (int k = 0; k < K; k++)
+        if (set_counts[k] >= MIN && (l_len == 0 || r_lens[k] == 0)) return PSX_ERR_INVALID;     // no index can lie inside an empty array
+    const long long score_wgs = nsb * ((N + M_HB - 1) / M_HB), hyp_wgs = (long long)K * ((N + 63) / 64);
+    if (score_wgs > 0x7fffffffLL || hyp_wgs > 0x7fffffffLL) return PSX_ERR_NOMEM;
+    if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
+    MatchScratch& sc = psx_match_scratch();
+    if (!sc.bind(device)) return PSX_ERR_HIP;
+    const float tol = opts->tol;
+    const bool refit = (opts->flags & PSX_RANSAC_REFIT) != 0;
+    const int nrec = host_inl ? (capacity < n ? capacity : n) : 0;
+    // the device blob: set table, score blocks, compaction blocks; the pinned buffer: states, refit models, blob, records
+    const size_t sets_b = pad16(sizeof(RMSet) * (size_t)K), sblk_b = sizeof(int4) * (size_t)nsb, cblk_b = sizeof(int4) * (size_t)ncb;
+    const size_t blob_b = sets_b + sblk_b + cblk_b;
+    const size_t state_b = sizeof(RMHead) + sizeof(RMState) * (size_t)K, refit_b = sizeof(RMRefit) * (size_t)K;
+    const size_t pin_state = 0, pin_refit = pad16(state_b), pin_blob = pin_refit + refit_b, pin_rec = pin_blob + blob_b;
+    // every buffer before the first launch: nothing is reallocated under queued work
+    if ((host_pairs && !sc.need(MS_RMANY_PAIRS, 16 * (size_t)n)) || !sc.need(MS_RMANY_TABLES, blob_b) || !sc.need(MS_RMANY_PTS, 16 * (size_t)n) ||
+        !sc.need(MS_RMANY_MODELS, sizeof(float) * 9 * (size_t)K * (size_t)N) || !sc.need(MS_RMANY_COUNTS, sizeof(int) * (size_t)K * (size_t)N) ||
+        !sc.need(MS_RMANY_STATE, pin_refit + refit_b) || !sc.need(MS_RMANY_TOT, sizeof(int) * (2 * (size_t)ncb + 1)) ||
+        !sc.need_pinned(pin_rec + 16 * (size_t)(refit ? n : nrec)))
+        return PSX_ERR_NOMEM;
+    void* dev_pin = nullptr;
+    if (hipHostGetDevicePointer(&dev_pin, sc.hpin, 0) != hipSuccess || dev_pin == nullptr) return PSX_ERR_HIP;
+    char* hpin = static_cast<char*>(sc.hpin);
+    void* d_pin_rec = static_cast<char*>(dev_pin) + pin_rec;
+
+    // ---- the tables, written into the pinned staging buffer and copied on the stream in ONE copy ----
+    {
+        RMSet* hs = reinterpret_cast<RMSet*>(hpin + pin_blob);
+        psx_ransac_block* tmp = new (std::nothrow) psx_ransac_block[(size_t)ncb];          // nsb <= ncb
+        if (!tmp) return PSX_ERR_NOMEM;
+        int4* hb = reinterpret_cast<int4*>(hpin + pin_blob + sets_b);
+        psx_ransac_many_blocks(set_counts, K, MIN, PSX_RANSAC_MANY_SCORE_ROWS, tmp, nsb);
+        for (long long b = 0; b < nsb; b++) hb[b] = make_int4(tmp[b].set, tmp[b].first, tmp[b].end, 0);
+        hb += nsb;
+        psx_ransac_many_blocks(set_counts, K, MIN, PSX_RANSAC_MANY_ROWS, tmp, ncb);
+        long long off = 0;
+        for (int k = 0; k < K; k++) {
+            hs[k] = RMSet{reinterpret_cast<const float2*>(d_rxys[k]), r_lens[k], set_counts[k], (int)off, 0, 0, 0};
+            off += set_counts[k];
+        }
+        for (long long b = 0; b < ncb; b++) {
+            hb[b] = make_int4(tmp[b].set, tmp[b].first, tmp[b].end, 0);
+            RMSet& s = hs[tmp[b].set];
+            if (s.b1 == 0) s.b0 = (int)b;                                  // a set's blocks are contiguous: first and last + 1
+            s.b1 = (int)b + 1;
+        }
+        delete[] tmp;
+    }
+    hipStream_t st = sc.stream;
+    const void* d_pairs = d_pairs_in;
+    if (host_pairs) {
+        if (hipMemcpyAsync(sc.buf[MS_RMANY_PAIRS], host_pairs, 16 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
+        d_pairs = sc.buf[MS_RMANY_PAIRS];
+    }
+    char* d_blob = static_cast<char*>(sc.buf[MS_RMANY_TABLES]);
+    char* d_st = static_cast<char*>(sc.buf[MS_RMANY_STATE]);
+    RMQueue q;
+    q.st = st; q.K = K; q.nsb = (int)nsb; q.ncb = (int)ncb; q.tol = tol;
+    q.d_sets = reinterpret_cast<const RMSet*>(d_blob);
+    q.d_sblk = reinterpret_cast<const int4*>(d_blob + sets_b);
+    q.d_cblk = reinterpret_cast<const int4*>(d_blob + sets_b + sblk_b);
+    q.d_pts = static_cast<float4*>(sc.buf[MS_RMANY_PTS]);
+    q.d_head = reinterpret_cast<RMHead*>(d_st);
+    q.d_state = reinterpret_cast<RMState*>(d_st + sizeof(RMHead));
+    q.d_tot = static_cast<int*>(sc.buf[MS_RMANY_TOT]);
+    q.d_offs = q.d_tot + ncb;
+    RMRefit* d_refit = reinterpret_cast<RMRefit*>(d_st + pin_refit);
+    float* d_models = static_cast<float*>(sc.buf[MS_RMANY_MODELS]);
+    int* d_counts = static_cast<int*>(sc.buf[MS_RMANY_COUNTS]);
+    const RMHead* hh = reinterpret_cast<const RMHead*>(hpin + pin_state);
+    const RMState* hs = reinterpret_cast<const RMState*>(hpin + pin_state + sizeof(RMHead));
+    void* final_out = host_inl ? d_pin_rec : d_inl;
+    const int final_cap = host_inl ? nrec : capacity;
+    const unsigned hw = (unsigned)((N + 63) / 64);
+
+    if (hipMemcpyAsync(d_blob, hpin + pin_blob, blob_b, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(d_st, 0, state_b, st) != hipSuccess)
+        return PSX_ERR_HIP;
+    hipLaunchKernelGGL(k_rmany_gather, dim3((unsigned)ncb), dim3(256), 0, st, static_cast<const int4*>(d_pairs), q.d_sets, q.d_cblk,
+                       reinterpret_cast<const float2*>(d_lxy), l_len, q.d_pts, &q.d_head->bad);
+    hipLaunchKernelGGL(k_rmany_hyp<KIND>, dim3((unsigned)K * hw), dim3(64), 0, st, q.d_pts, q.d_sets, (int)hw, opts->seed, N, d_models, d_counts);
+    queue_score<KIND>(q, d_models, N, 9, d_counts, 1);
+    hipLaunchKernelGGL(k_rmany_select, dim3((unsigned)K), dim3(256), 0, st, q.d_sets, d_counts, N, d_models, q.d_state);
+    // with the refit: every set's winner correspondences to the host; without: the inlier records, and the call is complete
+    if (refit) queue_compact<KIND>(q, q.d_pts, d_pin_rec, n);
+    else queue_compact<KIND>(q, d_pairs, final_out, final_cap);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hpin + pin_state, d_st, state_b, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return PSX_ERR_HIP;
+    if (hh->bad != 0) return PSX_ERR_INVALID;
+    auto sane = [&]() {
+        long long sum = 0;
+        for (int k = 0; k < K; k++) {
+            if (hs[k].total < 0 || hs[k].total > set_counts[k]) return false;
+            if (set_counts[k] >= MIN && (hs[k].best < 0 || hs[k].best >= N)) return false;
+            sum += hs[k].total;
+        }
+        return sum == hh->total;
+    };
+    if (!sane()) return PSX_ERR_HIP;
+    if (refit) {
+        // set k's winner correspondences lie behind those of the sets before it, in pair order
+        RMRefit* up = reinterpret_cast<RMRefit*>(hpin + pin_refit);
+        const psx_ransac_pt* rec = reinterpret_cast<const psx_ransac_pt*>(hpin + pin_rec);
+        bool any = false;
+        size_t at = 0;
+        for (int k = 0; k < K; at += (size_t)hs[k].total, k++) {
+            up[k].tried = 0; up[k].count = 0; up[k].pad = 0;
+            for (int j = 0; j < 9; j++) up[k].m[j] = NAN;                   // a model no rule lets score
+            const int c = hs[k].sample_inliers;
+            if (set_counts[k] < MIN || c < MIN || hs[k].total != c) continue;
+            float m[9];
+            RModel<KIND>::fit(rec + at, c, m);
+            if (!RModel<KIND>::usable(m)) continue;
+            for (int j = 0; j < 9; j++) up[k].m[j] = m[j];
+            up[k].tried = 1;
+            any = true;
+        }
+        if (any) {
+            if (hipMemcpyAsync(d_refit, up, refit_b, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
+            queue_score<KIND>(q, d_refit->m, 1, RM_REFIT_WORDS, &d_refit->count, RM_REFIT_WORDS);
+            hipLaunchKernelGGL(k_rmany_decide<KIND>, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, q.d_state, d_refit, K);
+        }
+        queue_compact<KIND>(q, d_pairs, final_out, final_cap);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hpin + pin_state, d_st, state_b, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return PSX_ERR_HIP;
+        if (!sane()) return PSX_ERR_HIP;
+    }
+    if (host_models && (hipMemcpyAsync(host_models, d_models, sizeof(float) * 9 * (size_t)K * (size_t)N, hipMemcpyDeviceToHost, st) != hipSuccess)) return PSX_ERR_HIP;
+    if (host_counts && (hipMemcpyAsync(host_counts, d_counts, sizeof(int) * (size_t)K * (size_t)N, hipMemcpyDeviceToHost, st) != hipSuccess)) return PSX_ERR_HIP;
+    if ((host_models || host_counts) && hipStreamSynchronize(st) != hipSuccess) return PSX_ERR_HIP;
+    const int total = hh->total;
+    if (host_inl && total > 0 && nrec > 0) memcpy(host_inl, hpin + pin_rec, 16 * (size_t)(total < nrec ? total : nrec));
+    for (int k = 0; k < K; k++) {
+        psx_ransac_result* r = results + k;
+        if (set_counts[k] < MIN || !RModel<KIND>::usable(hs[k].kept)) { psx_ransac_no_model(r); continue; }   // its total is 0: no pair passes
+        for (int j = 0; j < 9; j++) r->m[j] = hs[k].kept[j];
+        r->best = hs[k].best; r->sample_inliers = hs[k].sample_inliers; r->inliers = hs[k].total; r->refit_kept = hs[k].refit_kept;
+    }
+    *count = total;
+    return PSX_OK;
+}
+
+int many_ref(int kind, const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl, const float* const* right_xys,
+             const int* r_lens, const psx_ransac_opts* opts, psx_ransac_result* results, void* inliers, int capacity, int* count, float* models,
+             int* counts)
+{
+    int longest = 0;
+    if (n_sets > 0 && set_counts != nullptr)
+        for (int k = 0; k < n_sets; k++) longest = set_counts[k] > longest ? set_counts[k] : longest;
+    psx_ransac_pt* scratch = longest > 0 ? new (std::nothrow) psx_ransac_pt[(size_t)longest] : nullptr;
+    if (longest > 0 && !scratch) return PSX_ERR_NOMEM;
+    const int rc = psx_ransac_many_host(kind, pairs, set_counts, n_sets, left_xy, nl, right_xys, r_lens, opts, results, inliers, capacity, count,
+                                        models, counts, scratch);
+    delete[] scratch;
+    return rc;
+}
+
+} // namespace
+
+extern "C" int psx_ransac_many_plan(const int* set_counts, int n_sets, int min_pairs, int block_rows, psx_ransac_block* blocks, int capacity,
+                                    int* block_count)
+{
+    return psx_ransac_many_plan_host(set_counts, n_sets, min_pairs, block_rows, blocks, capacity, block_count);
+}
+
+extern "C" int psx_ransac_homography_many_ref(const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
+                                              const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                              psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts)
+{
+    return many_ref(PSX_GUIDE_HOMOGRAPHY, pairs, set_counts, n_sets, left_xy, nl, right_xys, r_lens, opts, results, inliers, capacity, count, models, counts);
+}
+
+extern "C" int psx_ransac_fundamental_many_ref(const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
+                                               const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                               psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts)
+{
+    return many_ref(PSX_GUIDE_EPIPOLAR, pairs, set_counts, n_sets, left_xy, nl, right_xys, r_lens, opts, results, inliers, capacity, count, models, counts);
+}
+
+extern "C" int psx_ransac_homography_many(int device, const void* host_pairs, const int* set_counts, int n_sets, const float* d_left_xy, int l_len,
+                                          const float* const* d_right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                          psx_ransac_result* results, void* host_inliers, int capacity, int* count, float* host_models,
+                                          int* host_counts)
+{
+    return ransac_many_run<PSX_GUIDE_HOMOGRAPHY>(device, host_pairs, nullptr, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
+                                                 host_inliers, nullptr, capacity, count, host_models, host_counts);
+}
+
+extern "C" int psx_ransac_homography_many_dev(int device, const void* d_pairs, const int* set_counts, int n_sets, const float* d_left_xy, int l_len,
+                                              const float* const* d_right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                              psx_ransac_result* results, void* d_inliers, int capacity, int* count, float* host_models,
+                                              int* host_counts)
+{
+    return ransac_many_run<PSX_GUIDE_HOMOGRAPHY>(device, nullptr, d_pairs, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
+                                                 nullptr, d_inliers, capacity, count, host_models, host_counts);
+}
+
+extern "C" int psx_ransac_fundamental_many(int device, const void* host_pairs, const int* set_counts, int n_sets, const float* d_left_xy, int l_len,
+                                           const float* const* d_right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                           psx_ransac_result* results, void* host_inliers, int capacity, int* count, float* host_models,
+                                           int* host_counts)
+{
+    return ransac_many_run<PSX_GUIDE_EPIPOLAR>(device, host_pairs, nullptr, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
+                                               host_inliers, nullptr, capacity, count, host_models, host_counts);
+}
+
+extern "C" int psx_ransac_fundamental_many_dev(int device, const void* d_pairs, const int* set_counts, int n_sets, const float* d_left_xy, int l_len,
+                                               const float* const* d_right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                               psx_ransac_result* results, void* d_inliers, int capacity, int* count, float* host_models,
+                                               int* host_counts)
+{
+    return ransac_many_run<PSX_GUIDE_EPIPOLAR>(device, nullptr, d_pairs, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
+                                               nullptr, d_inliers, capacity, count, host_models, host_counts);
+}

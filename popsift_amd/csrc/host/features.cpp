@@ -733,4 +733,98 @@ HomographyEstimate FeaturesDev::estimate( const char* who, bool fundamental, Fea
     return est;
 }
 
+std::vector<HomographyEstimate> FeaturesDev::estimateHomographyMany( const std::vector<FeaturesDev*>& others,
+                                                                     const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
+{
+    return estimateMany( "FeaturesDev::estimateHomographyMany", false, others, matches, opts );
+}
+
+std::vector<FundamentalEstimate> FeaturesDev::estimateFundamentalMany( const std::vector<FeaturesDev*>& others,
+                                                                       const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
+{
+    return estimateMany( "FeaturesDev::estimateFundamentalMany", true, others, matches, opts );
+}
+
+// psx_ransac_homography_many / psx_ransac_fundamental_many on the lists matchPairsMany returned: the lists that can have
+// a model go behind one another into ONE call (a shorter list is "no model" without a device, as estimate() has it), the
+// left positions are gathered once, every other object's once
+std::vector<HomographyEstimate> FeaturesDev::estimateMany( const char* who, bool fundamental, const std::vector<FeaturesDev*>& others,
+                                                           const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
+{
+    if( others.size() != matches.size() ) {
+        std::ostringstream ss;
+        ss << who << ": " << others.size() << " objects but " << matches.size() << " match lists";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    for( FeaturesDev* o : others ) {
+        if( o == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
+        if( o->_device != _device ) {
+            std::ostringstream ss;
+            ss << who << ": the objects live on different devices (" << _device << " and " << o->_device << ")";
+            fatal( __FILE__, __LINE__, ss.str() );
+        }
+    }
+    if( !( std::isfinite( opts.tol ) && opts.tol >= 0.0f ) || opts.hypotheses < 1 || opts.hypotheses > 65536 )
+        fatal( __FILE__, __LINE__, std::string( who ) + ": invalid options (finite tolerance >= 0, 1 to 65536 hypotheses)" );
+    const int K = (int)others.size();
+    const int min_pairs = fundamental ? 8 : 4;
+    HomographyEstimate none;
+    none.guide.kind = fundamental ? MatchGuide::Epipolar : MatchGuide::Homography;
+    for( int k = 0; k < 9; k++ ) none.guide.m[k] = 0.0f;
+    none.guide.tol = opts.tol;
+    none.best = -1; none.sample_inliers = 0; none.refit_kept = false;
+    std::vector<HomographyEstimate> out( others.size(), none );
+    std::vector<int> counts( K, 0 ), lens( K, 0 );
+    size_t total = 0;
+    for( int k = 0; k < K; k++ )
+        if( (int)matches[k].size() >= min_pairs ) { counts[k] = (int)matches[k].size(); total += matches[k].size(); }
+    if( total == 0 ) return out;
+    // the record is copied whole: its distance slots carry the index of the match within its list
+    std::vector<psx_match_pair_u8> rec( total ), inl( total );
+    size_t at = 0;
+    for( int k = 0; k < K; k++ )
+        for( int q = 0; q < counts[k]; q++, at++ ) {
+            rec[at].left = matches[k][q].left_descriptor; rec[at].right = matches[k][q].right_descriptor; rec[at].d1 = q; rec[at].d2 = 0;
+        }
+    psx_ransac_opts po;
+    po.tol = opts.tol; po.hypotheses = opts.hypotheses; po.seed = opts.seed; po.flags = opts.refit ? PSX_RANSAC_REFIT : 0;
+    std::vector<psx_ransac_result> res( K );
+    std::vector<void*> bufs( (size_t)K + 1, nullptr );
+    std::vector<const float*> rxys( K, nullptr );
+    const int l_len = getDescriptorCount();
+    int count = 0;
+    int rc = l_len > 0 ? PSX_OK : PSX_ERR_INVALID;
+    if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)l_len * 2 * sizeof(float), &bufs[K] );
+    if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)_ext, _rev, l_len, (float*)bufs[K] );
+    for( int k = 0; k < K && rc == PSX_OK; k++ ) {
+        const int r_len = others[k]->getDescriptorCount();
+        if( counts[k] == 0 ) continue;
+        if( r_len <= 0 ) { rc = PSX_ERR_INVALID; break; }
+        lens[k] = r_len;
+        rc = psx_dev_alloc( _device, (size_t)r_len * 2 * sizeof(float), &bufs[k] );
+        if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)others[k]->_ext, others[k]->_rev, r_len, (float*)bufs[k] );
+        rxys[k] = (const float*)bufs[k];
+    }
+    if( rc == PSX_OK )
+        rc = ( fundamental ? psx_ransac_fundamental_many : psx_ransac_homography_many )( _device, rec.data(), counts.data(), K, (const float*)bufs[K], l_len,
+                                                                                          rxys.data(), lens.data(), &po, res.data(), inl.data(),
+                                                                                          (int)total, &count, nullptr, nullptr );
+    for( void* b : bufs ) psx_dev_free( _device, b );
+    if( rc != PSX_OK ) {
+        std::ostringstream ss;
+        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options or a descriptor index outside its object" : "" ) << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    at = 0;
+    for( int k = 0; k < K; k++ ) {
+        if( counts[k] == 0 ) continue;
+        HomographyEstimate& est = out[k];
+        for( int j = 0; j < 9; j++ ) est.guide.m[j] = res[k].m[j];
+        est.best = res[k].best; est.sample_inliers = res[k].sample_inliers; est.refit_kept = res[k].refit_kept != 0;
+        est.inliers.reserve( res[k].inliers );
+        for( int q = 0; q < res[k].inliers; q++, at++ ) est.inliers.push_back( matches[k][inl[at].d1] );
+    }
+    return out;
+}
+
 } // namespace popsift

@@ -178,6 +178,8 @@ class FeaturesDev : public FeaturesBase
     int          _device;
 
     HomographyEstimate estimate( const char* who, bool fundamental, FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts );
+    std::vector<HomographyEstimate> estimateMany( const char* who, bool fundamental, const std::vector<FeaturesDev*>& others,
+                                                  const std::vector<std::vector<Match>>& matches, const RansacOptions& opts );
 
 public:
     FeaturesDev( );
@@ -213,8 +215,17 @@ public:
     /// the same for a scene with depth: a fundamental matrix from at least 8 matches, psx_ransac_fundamental; its guide
     /// restricts matchPairsGuided to the epipolar band
     FundamentalEstimate estimateFundamental( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts = RansacOptions() );
+    /// estimateHomography against many objects in ONE device call (psx_ransac_homography_many: one or two
+    /// synchronisations and a number of launches that does not grow with others.size()): `matches` is what
+    /// matchPairsMany( others ) returned, element k equals estimateHomography( others[k], matches[k], opts ).  Throws as
+    /// estimateHomography, and when others and matches differ in size.
+    std::vector<HomographyEstimate> estimateHomographyMany( const std::vector<FeaturesDev*>& others, const std::vector<std::vector<Match>>& matches,
+                                                            const RansacOptions& opts = RansacOptions() );
+    /// the same for fundamental matrices (psx_ransac_fundamental_many)
+    std::vector<FundamentalEstimate> estimateFundamentalMany( const std::vector<FeaturesDev*>& others, const std::vector<std::vector<Match>>& matches,
+                                                              const RansacOptions& opts = RansacOptions() );
 
-    inline Feature*    getFeatures()    { return _ext; }
+    inline Feature*   getFeatures()    { return _ext; }
     inline Descriptor* getDescriptors() { return _ori; }
     inline int*        getReverseMap()  { return _rev; }
     inline void        setDevice( int d ) { _device = d; }
