@@ -472,6 +472,47 @@ int psx_match_pairs_guided_u8_dev(int device, const unsigned char* d_left, const
                                   const unsigned char* d_right, const float* d_right_xy, int r_len, const psx_guide* guide,
                                   const psx_match_opts* opts, psx_match_pair_u8* d_pairs, int capacity, int* count);
 
+/* GUIDED RE-MATCH OF MANY SETS IN ONE CALL (byte descriptors).  The third link of match -> verify -> re-match for one
+ * view against n_sets others: psx_match_pairs_many_u8* leaves K pair lists, psx_ransac_*_many* K models,
+ * psx_guides_from_ransac (below, after the batched RANSAC) turns them into K guides, and this call re-matches all K sets,
+ * each under its OWN guide -- one stream synchronisation and a number of kernel launches that does not grow with n_sets
+ * (4 without the cross-check, 6 with it), where a loop over psx_match_pairs_guided_u8_dev pays 3 / 5 launches, a
+ * synchronisation and a count read-back per set.  INTEGRATION.md ("Guided re-match of many sets") has the words and the
+ * measured cost.  d_left / d_left_xy: DEVICE pointers to l_len descriptors of 128 bytes / l_len (x, y) pairs; d_rights,
+ * d_right_xys, r_lens: HOST arrays of n_sets entries, d_rights[k] / d_right_xys[k] DEVICE pointers to r_lens[k]
+ * descriptors / positions; guides: HOST array of n_sets guides, guides[k] for set k.  Descriptor pointers are 16-byte
+ * aligned, position pointers 8-byte aligned; the sets may be separate allocations, slices of one buffer, or the same
+ * pointer more than once, possibly under different guides.
+ * With G_k = the list psx_match_pairs_guided_u8 returns for (L, L_xy, R_k, R_xy_k, guides[k], opts) at unlimited capacity,
+ * bit for bit:
+ *   - the result is the concatenation G_0, G_1, ..., G_{n_sets-1}: sets ascending, `left` ascending within a set;
+ *   - `right` is the index WITHIN ITS SET;
+ *   - set_counts[k] = |G_k| (HOST array of n_sets ints), always the set's total;
+ *   - *count = the sum of the |G_k|; the first min(*count, capacity) records of the concatenation are written, nothing at
+ *     or past capacity; capacity = 0 with a NULL output asks "how many?".
+ * A set whose guide has kind == PSX_GUIDE_NONE is SKIPPED: it contributes nothing, its count is 0, none of its arrays is
+ * read and its d_rights[k] / d_right_xys[k] may be NULL (the rest of that guide is not looked at).  This is how "no model"
+ * is said: psx_ransac_*_many reports a set it could not verify with best = -1 and a ZERO matrix, and a zero matrix is a
+ * valid guide -- it admits nothing as a homography and EVERYTHING as an epipolar guide.  psx_guides_from_ransac maps such a
+ * result to kind 0.  The single-set calls keep refusing kind 0.
+ * n_sets = 0, l_len = 0, and a call whose sets are all empty or all skipped give zero counts and PSX_OK without touching
+ * a device.  PSX_ERR_INVALID, with nothing touched and before any device call: everything psx_match_pairs_guided_u8 and
+ * psx_match_pairs_many_u8 refuse; guides, d_rights, d_right_xys, r_lens or set_counts NULL with n_sets > 0; d_left or
+ * d_left_xy NULL with l_len > 0; any guide that is neither valid nor of kind 0 -- EVERY guide is checked before anything
+ * runs; a NULL d_rights[k] or d_right_xys[k] for a set that is not skipped and has rows.  Scratch (psx_match_release) and
+ * thread safety as for psx_match_u8.  Synchronous, with exactly one stream synchronisation per call.  Only the byte form
+ * exists, as for the unguided one-to-many call. */
+#define PSX_GUIDE_NONE 0         /* in the *_many call only: this set is skipped */
+int psx_match_pairs_guided_many_u8(int device, const unsigned char* d_left, const float* d_left_xy, int l_len,
+                                   const unsigned char* const* d_rights, const float* const* d_right_xys, const int* r_lens,
+                                   int n_sets, const psx_guide* guides, const psx_match_opts* opts,
+                                   psx_match_pair_u8* host_pairs, int capacity, int* set_counts, int* count);
+/* the list stays in HBM: d_pairs is a DEVICE pointer, 16-byte aligned; set_counts and count are still HOST memory */
+int psx_match_pairs_guided_many_u8_dev(int device, const unsigned char* d_left, const float* d_left_xy, int l_len,
+                                       const unsigned char* const* d_rights, const float* const* d_right_xys, const int* r_lens,
+                                       int n_sets, const psx_guide* guides, const psx_match_opts* opts,
+                                       psx_match_pair_u8* d_pairs, int capacity, int* set_counts, int* count);
+
 /* ---- geometric verification ---------------------------------------------------------------
  * The step between a match and a guided re-match: a homography estimated from the pair list by RANSAC on the device
  * (OpenCV's findHomography(RANSAC), the model AliceVision's guidedMatching starts from; the reference has no
@@ -607,6 +648,13 @@ int psx_ransac_homography_many_ref(const void* pairs, const int* set_counts, int
 int psx_ransac_fundamental_many_ref(const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
                                     const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts,
                                     psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts);
+
+/* From the K results of psx_ransac_*_many* to the K guides of psx_match_pairs_guided_many_u8*, on the HOST: no device, no
+ * context.  guides[k] = { results[k].best < 0 ? PSX_GUIDE_NONE : kind, results[k].m, tol }: a set without a model is
+ * skipped by the re-match instead of being matched under its zero matrix.  kind: PSX_GUIDE_HOMOGRAPHY for the results of
+ * psx_ransac_homography_many*, PSX_GUIDE_EPIPOLAR for those of psx_ransac_fundamental_many*.  PSX_ERR_INVALID, with
+ * nothing written: n_sets < 0, a NULL array with n_sets > 0, a kind other than 1 or 2, a tol that is not finite and >= 0. */
+int psx_guides_from_ransac(const psx_ransac_result* results, int n_sets, int kind, float tol, psx_guide* guides);
 
 /* How the batched calls cut the concatenated list, on the HOST: no device, no context (csrc/hip/ransac_many_plan.h, the
  * function the library itself plans with: block_rows = 512 for the score kernel, 256 for the gather and the compaction).

@@ -100,6 +100,7 @@ SYMBOLS = [
     "psx_match_pairs_many_u8", "psx_match_pairs_many_u8_dev", "psx_match_many_plan",
     "psx_guide_allows", "psx_desc_positions", "psx_match_guided", "psx_match_guided_u8",
     "psx_match_pairs_guided", "psx_match_pairs_guided_u8", "psx_match_pairs_guided_dev", "psx_match_pairs_guided_u8_dev",
+    "psx_match_pairs_guided_many_u8", "psx_match_pairs_guided_many_u8_dev", "psx_guides_from_ransac",
     "psx_ransac_opts_default", "psx_ransac_samples", "psx_homography_fit", "psx_ransac_homography_ref",
     "psx_ransac_homography", "psx_ransac_homography_dev",
     "psx_ransac_samples_k", "psx_fundamental_fit", "psx_ransac_fundamental_ref", "psx_ransac_fundamental", "psx_ransac_fundamental_dev",
@@ -120,6 +121,7 @@ class MatchOpts(C.Structure):
 
 GUIDE_HOMOGRAPHY = 1     # PSX_GUIDE_HOMOGRAPHY
 GUIDE_EPIPOLAR = 2       # PSX_GUIDE_EPIPOLAR
+GUIDE_NONE = 0           # PSX_GUIDE_NONE: in the *_many call only, this set is skipped
 
 
 class Guide(C.Structure):
@@ -140,6 +142,11 @@ class Guide(C.Structure):
     @classmethod
     def epipolar(cls, F, tol):
         return cls.make(GUIDE_EPIPOLAR, F, tol)
+
+    @classmethod
+    def none(cls):
+        """the guide of a set that match_pairs_guided_many_* skips (kind 0); the single-set calls refuse it"""
+        return cls.make(GUIDE_NONE, np.zeros(9, np.float32), 0.0)
 
 
 RANSAC_REFIT = 1         # PSX_RANSAC_REFIT
@@ -243,6 +250,9 @@ def lib():
             getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(Guide), vp, vp]
         for n in ("psx_match_pairs_guided", "psx_match_pairs_guided_u8", "psx_match_pairs_guided_dev", "psx_match_pairs_guided_u8_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(Guide), C.POINTER(MatchOpts), vp, C.c_int, ip]
+        for n in ("psx_match_pairs_guided_many_u8", "psx_match_pairs_guided_many_u8_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.POINTER(MatchOpts), vp, C.c_int, vp, ip]
+        L.psx_guides_from_ransac.argtypes = [vp, C.c_int, C.c_int, C.c_float, vp]
         L.psx_ransac_opts_default.argtypes = [C.POINTER(RansacOpts)]
         L.psx_ransac_samples.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_int, vp]
         L.psx_homography_fit.argtypes = [vp, vp, C.c_int, vp]
@@ -691,6 +701,83 @@ def match_pairs_guided_dev(left_ptr, left_xy_ptr, l_len, right_ptr, right_xy_ptr
     if rc != 0:
         raise PopSiftError("psx_match_pairs_guided%s_dev failed (%d)" % ("_u8" if u8 else "", rc))
     return n.value
+
+
+def _guide_array(guides):
+    """a HOST array of psx_guide from a sequence of Guide (None stands for Guide.none())"""
+    gs = [Guide.none() if g is None else g for g in guides]
+    return (Guide * max(len(gs), 1))(*gs)
+
+
+def _guided_many_call(fn, name, device, left_ptr, left_xy_ptr, l_len, right_ptrs, right_xy_ptrs, r_lens, guides, out_ptr, capacity,
+                      ratio, mutual):
+    """One guided one-to-many call on device pointers: (per-set counts (n_sets,) int32, total count)"""
+    k = len(r_lens)
+    if not (len(right_ptrs) == len(right_xy_ptrs) == len(guides) == k):
+        raise ValueError("one descriptor pointer, one position pointer and one guide per set")
+    val = lambda p: p.value if isinstance(p, C.c_void_p) else p
+    ptrs = (C.c_void_p * max(k, 1))(*[val(p) for p in right_ptrs])
+    xptrs = (C.c_void_p * max(k, 1))(*[val(p) for p in right_xy_ptrs])
+    lens = np.ascontiguousarray(r_lens, dtype=np.int32)
+    garr = _guide_array(guides)
+    counts = np.full((k,), -1, np.int32)
+    n = C.c_int(-1)
+    o = match_opts(ratio, mutual)
+    rc = fn(device, left_ptr, left_xy_ptr, l_len, ptrs if k else None, xptrs if k else None, lens.ctypes.data_as(C.c_void_p) if k else None,
+            k, garr if k else None, C.byref(o), out_ptr, capacity, counts.ctypes.data_as(C.c_void_p) if k else None, C.byref(n))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    return counts, n.value
+
+
+def match_pairs_guided_many_u8(left, left_xy, rights, right_xys, guides, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs_guided_many_u8 on host arrays: left (n,128) uint8 with positions left_xy (n,2) against every
+    (m_k,128) uint8 array of `rights` with positions right_xys[k], set k under guides[k], in ONE call.  A guide of kind
+    GUIDE_NONE (Guide.none(), or None) skips its set; that set's arrays may be None.  Returns (list of per-set
+    PAIR_U8_DTYPE arrays -- set k's equals match_pairs_guided_u8(left, left_xy, rights[k], right_xys[k], guides[k]) --,
+    per-set counts); with a capacity the list holds the first `capacity` records of the concatenation and the counts are
+    still the totals."""
+    L = lib()
+    if not (len(rights) == len(right_xys) == len(guides)):
+        raise ValueError("one descriptor array, one position array and one guide per set")
+    empty, empty_xy = np.zeros((0, 128), np.uint8), np.zeros((0, 2), np.float32)
+    sides = [_guided_sides(left, left_xy, empty if r is None else r, empty_xy if x is None else x, np.uint8) for r, x in zip(rights, right_xys)]
+    left, lx = _guided_sides(left, left_xy, empty, empty_xy, np.uint8)[:2]
+    bufs = []
+    try:
+        ptrs = _to_device(L, device, [left, lx] + [s[2] for s in sides] + [s[3] for s in sides], bufs)
+        k = len(sides)
+        cap = len(left) * k if capacity is None else capacity
+        out = np.zeros((cap,), PAIR_U8_DTYPE)
+        counts, n = _guided_many_call(L.psx_match_pairs_guided_many_u8, "psx_match_pairs_guided_many_u8", device, ptrs[0], ptrs[1], len(left),
+                                      ptrs[2:2 + k], ptrs[2 + k:], [len(s[2]) for s in sides], guides,
+                                      out.ctypes.data_as(C.c_void_p) if cap else None, cap, ratio, mutual)
+        return split_sets(out[:min(n, cap)], counts), counts
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def match_pairs_guided_many_dev(left_ptr, left_xy_ptr, l_len, right_ptrs, right_xy_ptrs, r_lens, guides, out_ptr, capacity, ratio=0.8,
+                                mutual=False, device=0):
+    """psx_match_pairs_guided_many_u8_dev on DEVICE pointers (e.g. tensor.data_ptr()): the concatenated records go into
+    the caller's device buffer at out_ptr (16-byte aligned, `capacity` records); returns (per-set counts, total count)."""
+    return _guided_many_call(lib().psx_match_pairs_guided_many_u8_dev, "psx_match_pairs_guided_many_u8_dev", device, C.c_void_p(left_ptr),
+                             C.c_void_p(left_xy_ptr), l_len, list(right_ptrs), list(right_xy_ptrs), r_lens, guides, C.c_void_p(out_ptr),
+                             capacity, ratio, mutual)
+
+
+def guides_from_ransac(results, kind, tol):
+    """psx_guides_from_ransac: the results of ransac_*_many* (RansacResult objects) as the guides of
+    match_pairs_guided_many_*: a result without a model (best < 0) becomes Guide.none(), every other one
+    Guide(kind, its matrix, tol).  kind: GUIDE_HOMOGRAPHY or GUIDE_EPIPOLAR.  No device."""
+    k = len(results)
+    res = (RansacResult * max(k, 1))(*results)
+    out = (Guide * max(k, 1))()
+    rc = lib().psx_guides_from_ransac(res if k else None, k, kind, float(np.float32(tol)), out if k else None)
+    if rc != 0:
+        raise PopSiftError("psx_guides_from_ransac failed (%d)" % rc)
+    return [Guide(g.kind, g.m, g.tol) for g in out[:k]]
 
 
 def ransac_opts(tol=2.0, hypotheses=1024, seed=0, refit=True):

@@ -14,21 +14,19 @@
 //                          of the K right sets x chunks of L -- the same kernel on the other pair of tables
 //   k_match_u8_many_merge  per (outer row, inner set) the chunks of that set in index order: the directed result
 //                          (match_scratch.h) the join reads -- K results per left row forward, one per right row backward
-//   k_many_count / k_many_scan / k_many_write   the join of match.hip, segmented: the rule of match_rule.h per (set, left)
-//                          with the gather into set k's backward rows and the compaction of wg_compact.h; one total per
-//                          workgroup in set-major order, an exclusive scan of the totals by one workgroup (K x blocks totals:
-//                          every workgroup summing all earlier ones, as k_pairs_write does, would be quadratic), then one
-//                          16-byte store per survivor at (offset of its workgroup) + (its offset within the workgroup).
+//   k_many_count / k_many_scan / k_many_write   the join of match.hip, segmented (match_many_join.h, shared with the
+//                          guided one-to-many call): the rule of match_rule.h (psx_match_keep) per (set, left) counted per
+//                          workgroup, a scan of the totals, one 16-byte store per survivor
 // Launches per call, whatever K is: the table copy, the norms, 2 per direction, 3 for the join -- 8 kernels with the
 // cross-check, 6 without; one stream synchronisation.  The per-chunk partials are the one buffer that grows with
 // (chunks x outer rows): above MANY_PARTIAL_BUDGET the sets are processed in groups of whole sets, each group its own
 // match + merge on the same stream (2 more launches per extra group, no synchronisation).
 #include "psx_internal.h"
 #include "match_join.h"
+#include "match_many_join.h"
 #include "match_many_plan.h"
 #include "match_scratch.h"
 #include "match_u8_core.h"
-#include "wg_compact.h"
 
 #include <climits>
 #include <cstring>
@@ -109,62 +107,6 @@ __global__ __launch_bounds__(256) void k_match_u8_many_merge(const ManySet* __re
     for (int c = is.c0; c < is.c1; c++)
         u8_merge_chunk(t, partial[(size_t)(c - ps.chunk_base) * ps.outer_rows + prow], chunks[c].y);
     psx_directed_store<int>(out + out_stride * (size_t)g + 5 * (size_t)os.roff, os.len, (size_t)row, t.i1, t.i2, u8_accept(t.d1, t.d2), t.d1, t.d2);
-}
-
-// The rule of match_rule.h for left row i against set k: fwd holds K directed results of 5 l_len ints each, bwd the K sets'
-// backward results at 5 * (the set's first row).  An empty set has no pairs (and no results: nothing of it is read).
-__device__ __forceinline__ bool many_rule(const ManySet* __restrict__ sets, const int* __restrict__ fwd, int l_len,
-                                          const int* __restrict__ bwd, int k, int i, float ratio, int mutual, int4& rec)
-{
-    const ManySet s = sets[k];
-    if (i >= l_len || s.len == 0) return false;
-    int j, d1, d2;
-    psx_directed_load<int>(fwd + 5 * (size_t)l_len * k, l_len, i, j, d1, d2);
-    bool keep = psx_match_keep(psx_match_dist(d1), psx_match_dist(d2), ratio);
-    if (keep && mutual) keep = psx_directed_best(bwd + 5 * (size_t)s.roff, j) == i;
-    rec = make_int4(i, j, d1, d2);
-    return keep;
-}
-
-// grid K * nb (nb = blocks of 256 left rows), workgroup k * nb + b: set-major, so the offsets are the concatenation's
-__global__ __launch_bounds__(256) void k_many_count(const ManySet* __restrict__ sets, const int* __restrict__ fwd, int l_len,
-                                                    const int* __restrict__ bwd, int nb, float ratio, int mutual,
-                                                    int* __restrict__ wg_tot)
-{
-    const int k = (int)(blockIdx.x / (unsigned)nb), b = (int)(blockIdx.x % (unsigned)nb);
-    int4 rec;
-    const bool keep = many_rule(sets, fwd, l_len, bwd, k, b * 256 + (int)threadIdx.x, ratio, mutual, rec);
-    __shared__ int s_cnt[4];
-    wg_count(__ballot(keep), s_cnt);
-    if (threadIdx.x == 0) wg_tot[blockIdx.x] = wg_total(s_cnt);
-}
-
-// ONE workgroup of 1024 threads: offs[w] = the totals before workgroup w, offs[n] = all of them (wg_compact.h)
-__global__ __launch_bounds__(1024) void k_many_scan(const int* __restrict__ wg_tot, int n, int* __restrict__ offs)
-{
-    wg_scan_totals(wg_tot, n, offs);
-}
-
-// grid as k_many_count.  Evaluates the rule again (k_pairs_write: cheaper than parking the verdicts), ranks its lanes and
-// writes each surviving record with ONE 16-byte store at offs[workgroup] + rank, never at or past capacity; a set's first
-// workgroup writes the set's count, workgroup 0 the total.
-__global__ __launch_bounds__(256) void k_many_write(const ManySet* __restrict__ sets, const int* __restrict__ fwd, int l_len,
-                                                    const int* __restrict__ bwd, int nb, float ratio, int mutual,
-                                                    const int* __restrict__ offs, int4* __restrict__ out, int capacity,
-                                                    int* __restrict__ set_counts, int* __restrict__ total)
-{
-    const int k = (int)(blockIdx.x / (unsigned)nb), b = (int)(blockIdx.x % (unsigned)nb);
-    int4 rec = make_int4(0, 0, 0, 0);
-    const bool keep = many_rule(sets, fwd, l_len, bwd, k, b * 256 + (int)threadIdx.x, ratio, mutual, rec);
-    const unsigned long long m = __ballot(keep);
-    __shared__ int s_cnt[4];
-    wg_count(m, s_cnt);
-    const int pos = offs[blockIdx.x] + wg_offset(m, s_cnt);
-    if (keep && pos < capacity) out[pos] = rec;
-    if (threadIdx.x == 0) {
-        if (b == 0) set_counts[k] = offs[(size_t)(k + 1) * nb] - offs[(size_t)k * nb];
-        if (blockIdx.x == 0) *total = offs[gridDim.x];
-    }
 }
 
 // a run of whole sets whose partials fit the budget: what one match + merge pair of launches takes
@@ -304,7 +246,6 @@ int match_pairs_many(int device, const unsigned char* d_left, int l_len, const u
     int* d_fwd = static_cast<int*>(sc.buf[MS_MANY_FWD]);
     int* d_bwd = mutual ? static_cast<int*>(sc.buf[MS_MANY_BWD]) : nullptr;
     int* d_tot = static_cast<int*>(sc.buf[MS_MANY_TOT]);
-    int* d_offs = d_tot + ntot;
     int* d_total = static_cast<int*>(dev_pin);
     int* d_counts = reinterpret_cast<int*>(static_cast<char*>(dev_pin) + off_counts);
     // the kernel's capacity for the host form is the staging buffer's (nrec <= capacity)
@@ -328,11 +269,7 @@ int match_pairs_many(int device, const unsigned char* d_left, int l_len, const u
         hipLaunchKernelGGL(k_match_u8_many_merge, dim3((unsigned)g.nblocks), dim3(256), 0, st, d_sets, d_chunks, d_blocks, ps, K,
                            (size_t)0, d_partial, d_bwd);
     }
-    const int mflag = mutual ? 1 : 0;
-    hipLaunchKernelGGL(k_many_count, dim3((unsigned)ntot), dim3(256), 0, st, d_sets, d_fwd, l_len, d_bwd, (int)nb, opts->ratio, mflag, d_tot);
-    hipLaunchKernelGGL(k_many_scan, dim3(1), dim3(1024), 0, st, d_tot, (int)ntot, d_offs);
-    hipLaunchKernelGGL(k_many_write, dim3((unsigned)ntot), dim3(256), 0, st, d_sets, d_fwd, l_len, d_bwd, (int)nb, opts->ratio, mflag,
-                       d_offs, out, cap, d_counts, d_total);
+    psx_many_join_queue(st, d_sets, d_fwd, l_len, d_bwd, (int)nb, (int)ntot, opts->ratio, mutual, d_tot, out, cap, d_counts, d_total);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return PSX_ERR_HIP;
     const int n = *h_total;
     if (n < 0 || n > all_pairs) return PSX_ERR_HIP;

@@ -1,5 +1,5 @@
-// match_scratch.h -- what the matcher's translation units share (match.hip, match_guided.hip, match_many.hip, ransac.hip,
-// ransac_many.hip):
+// match_scratch.h -- what the matcher's translation units share (match.hip, match_guided.hip, match_many.hip,
+// match_guided_many.hip, ransac.hip, ransac_many.hip):
 // the layout of a directed result, the per-thread scratch with its named buffers, and the runner of the pair join.
 // Internal to the HIP library.
 #pragma once
@@ -33,7 +33,7 @@ __device__ __forceinline__ int psx_directed_best(const int* __restrict__ res, si
 // The buffers of a MatchScratch.  A buffer belongs to ONE use: calls queue work without waiting for the stream, so two
 // features sharing a buffer would alias under queued work.  F32: psx_match / psx_match_pairs, U8: psx_match_u8 /
 // psx_match_pairs_u8 (match.hip); GUIDED: match_guided.hip; RANSAC: ransac.hip; MANY: the one-to-many search (match_many.hip);
-// RMANY: the batched RANSAC (ransac_many.hip)
+// RMANY: the batched RANSAC (ransac_many.hip); GMANY: the guided one-to-many search (match_guided_many.hip)
 enum MatchSlot {
     MS_F32_PARTIAL,      // the exact scan's per-chunk top-2
     MS_F32_RPERM,        // the exact scan's permuted right side
@@ -72,6 +72,11 @@ enum MatchSlot {
     MS_RMANY_COUNTS,     // their counts
     MS_RMANY_STATE,      // the head, the per-set states and the per-set refit models
     MS_RMANY_TOT,        // the compaction's per-workgroup totals and their offsets
+    MS_GMANY_TABLES,     // the guided one-to-many search (match_guided_many.hip): the set table and the backward block table
+    MS_GMANY_LINES,      // the left side's lines under every set's guide, for the backward direction
+    MS_GMANY_FWD,        // the forward direction's results of all sets
+    MS_GMANY_BWD,        // the backward direction's
+    MS_GMANY_TOT,        // the join's per-workgroup totals and their offsets
     MS_NBUF
 };
 

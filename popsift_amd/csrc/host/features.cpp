@@ -673,6 +673,104 @@ std::vector<std::vector<Match>> FeaturesDev::matchPairsMany( const std::vector<F
     return out;
 }
 
+// FeaturesDev::matchPairsGuidedMany: psx_match_pairs_guided_many_u8 on this object's bytes and positions and every other
+// object's that is neither empty nor skipped -- each side quantised and its positions gathered once, ONE matching call for
+// all of them; the concatenated list is cut at the per-set counts and mapped through the reverse maps as matchPairs does
+std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedMany( const std::vector<FeaturesDev*>& others, const std::vector<MatchGuide>& guides,
+                                                                   const MatchOptions& opts )
+{
+    const char* who = "FeaturesDev::matchPairsGuidedMany";
+    for( FeaturesDev* o : others ) {
+        if( o == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
+        if( o->_device != _device ) {
+            std::ostringstream ss;
+            ss << who << ": the objects live on different devices (" << _device << " and " << o->_device << ")";
+            fatal( __FILE__, __LINE__, ss.str() );
+        }
+    }
+    if( !opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": the one-to-many form is byte-only (set MatchOptions::bytes)" );
+    if( guides.size() != others.size() ) {
+        std::ostringstream ss;
+        ss << who << ": " << others.size() << " objects but " << guides.size() << " guides";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    const int K = (int)others.size();
+    std::vector<psx_guide> pg( others.size() );
+    for( int k = 0; k < K; k++ ) {
+        pg[k].kind = (int)guides[k].kind;
+        for( int q = 0; q < 9; q++ ) pg[k].m[q] = guides[k].m[q];
+        pg[k].tol = guides[k].tol;
+        if( pg[k].kind == PSX_GUIDE_NONE ) continue;
+        // refused here, before any device is touched (and for empty sides too): what the call refuses
+        bool ok = ( pg[k].kind == PSX_GUIDE_HOMOGRAPHY || pg[k].kind == PSX_GUIDE_EPIPOLAR ) && std::isfinite( pg[k].tol ) && pg[k].tol >= 0.0f;
+        for( int q = 0; q < 9; q++ ) ok = ok && std::isfinite( pg[k].m[q] );
+        if( !ok ) fatal( __FILE__, __LINE__, std::string( who ) + ": invalid guide (kind 0, 1 or 2, finite entries, finite tolerance >= 0)" );
+    }
+    const int l_len = getDescriptorCount();
+    std::vector<std::vector<Match>> out( others.size() );
+    std::vector<int> lens( K, 0 ), counts( K, 0 );
+    bool any = false;
+    for( int k = 0; k < K; k++ ) {
+        if( pg[k].kind != PSX_GUIDE_NONE && others[k]->getDescriptorCount() > 0 ) lens[k] = others[k]->getDescriptorCount();
+        any = any || lens[k] > 0;
+    }
+    if( l_len <= 0 || !any ) return out;
+    psx_match_opts po;
+    po.ratio = opts.ratio;
+    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
+    // descriptors of set k at [k], its positions at [K + 1 + k]; this object's at [K] and [2 K + 1]
+    std::vector<void*> bufs( 2 * (size_t)K + 2, nullptr );
+    std::vector<const unsigned char*> ptrs( K, nullptr );
+    std::vector<const float*> xys( K, nullptr );
+    int rc = psx_dev_alloc( _device, (size_t)l_len * 128, &bufs[K] );
+    if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)l_len * 2 * sizeof(float), &bufs[2 * K + 1] );
+    if( rc == PSX_OK ) rc = psx_quantize_desc( _device, (const float*)_ori, l_len, (unsigned char*)bufs[K] );
+    if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)_ext, _rev, l_len, (float*)bufs[2 * K + 1] );
+    for( int k = 0; k < K && rc == PSX_OK; k++ ) {
+        const int r_len = lens[k];
+        if( r_len <= 0 ) continue;
+        rc = psx_dev_alloc( _device, (size_t)r_len * 128, &bufs[k] );
+        if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)r_len * 2 * sizeof(float), &bufs[K + 1 + k] );
+        if( rc == PSX_OK ) rc = psx_quantize_desc( _device, (const float*)others[k]->_ori, r_len, (unsigned char*)bufs[k] );
+        if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)others[k]->_ext, others[k]->_rev, r_len, (float*)bufs[K + 1 + k] );
+        ptrs[k] = (const unsigned char*)bufs[k];
+        xys[k] = (const float*)bufs[K + 1 + k];
+    }
+    // at most l_len pairs per set exist (a product above INT_MAX is the call's to refuse)
+    const long long room = (long long)K * l_len;
+    std::vector<psx_match_pair_u8> pb( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
+    int count = 0;
+    if( rc == PSX_OK )
+        rc = psx_match_pairs_guided_many_u8( _device, (const unsigned char*)bufs[K], (const float*)bufs[2 * K + 1], l_len, ptrs.data(), xys.data(),
+                                             lens.data(), K, pg.data(), &po, pb.data(), (int)pb.size(), counts.data(), &count );
+    for( void* b : bufs ) psx_dev_free( _device, b );
+    if( rc != PSX_OK ) {
+        std::ostringstream ss;
+        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    std::vector<int> l_fem( l_len );
+    if( psx_dev_read( _device, l_fem.data(), _rev, (size_t)l_len * sizeof(int) ) != PSX_OK )
+        fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
+    size_t at = 0;
+    for( int k = 0; k < K; k++ ) {
+        if( counts[k] <= 0 ) continue;
+        std::vector<int> r_fem( lens[k] );
+        if( psx_dev_read( _device, r_fem.data(), others[k]->_rev, (size_t)lens[k] * sizeof(int) ) != PSX_OK )
+            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
+        out[k].resize( counts[k] );
+        for( int q = 0; q < counts[k]; q++, at++ ) {
+            Match& m = out[k][q];
+            m.left_descriptor = pb[at].left; m.right_descriptor = pb[at].right;
+            m.distance        = pb[at].d1 == INT32_MAX ? INFINITY : (float)pb[at].d1;
+            m.second_distance = pb[at].d2 == INT32_MAX ? INFINITY : (float)pb[at].d2;
+            m.left_feature  = l_fem[m.left_descriptor];
+            m.right_feature = r_fem[m.right_descriptor];
+        }
+    }
+    return out;
+}
+
 HomographyEstimate FeaturesDev::estimateHomography( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts )
 {
     return estimate( "FeaturesDev::estimateHomography", false, other, matches, opts );

@@ -130,10 +130,15 @@ struct MatchOptions
 /// (include/popsift_hip.h, "guided matching").  Positions are Feature::xpos / ypos, in input-image units.
 struct MatchGuide
 {
-    enum Kind { Homography = 1, Epipolar = 2 } kind;   ///< m = H: right point within tol of H * left point (identity H: a
-                                                       ///< search window); m = F: within tol of the line F * left point
+    enum Kind { None = 0, Homography = 1, Epipolar = 2 } kind;   ///< m = H: right point within tol of H * left point
+                                                       ///< (identity H: a search window); m = F: within tol of the line
+                                                       ///< F * left point; None: matchPairsGuidedMany skips the set
+                                                       ///< (matchPairsGuided refuses it)
     float m[9];                                        ///< row major
     float tol;                                         ///< pixels, finite and >= 0
+
+    /// the guide of a set that FeaturesDev::matchPairsGuidedMany skips: kind None, a zero matrix, tol 0
+    static MatchGuide none() { MatchGuide g; g.kind = None; for( int k = 0; k < 9; k++ ) g.m[k] = 0.0f; g.tol = 0.0f; return g; }
 };
 
 /// One correspondence of FeaturesDev::matchPairs / matchPairsGuided
@@ -208,6 +213,13 @@ public:
     /// descriptors only -- every side is quantised once on the device, as matchPairs does with MatchOptions::bytes.
     /// Throws as matchPairs for a null entry or an object on another device, and for opts.bytes == false.
     std::vector<std::vector<Match>> matchPairsMany( const std::vector<FeaturesDev*>& others, const MatchOptions& opts );
+    /// matchPairsGuided against many objects in ONE device call (psx_match_pairs_guided_many_u8: one synchronisation, a
+    /// number of launches that does not grow with others.size()), others[k] under guides[k]: element k equals
+    /// matchPairsGuided( others[k], guides[k], opts ) with opts.bytes.  A guide of kind MatchGuide::None
+    /// (MatchGuide::none()) skips its set: element k is empty.  Byte descriptors only.  Throws as matchPairsMany, for
+    /// guides.size() != others.size(), and for a guide that is neither valid nor of kind None.
+    std::vector<std::vector<Match>> matchPairsGuidedMany( const std::vector<FeaturesDev*>& others, const std::vector<MatchGuide>& guides,
+                                                          const MatchOptions& opts );
     /// geometric verification: a homography (this = left -> other = right) estimated from `matches` (what matchPairs
     /// returned for the same two objects) by RANSAC on the device, psx_ransac_homography.  Throws as matchPairs, and for
     /// invalid options or a descriptor index outside its object.
@@ -219,6 +231,9 @@ public:
     /// synchronisations and a number of launches that does not grow with others.size()): `matches` is what
     /// matchPairsMany( others ) returned, element k equals estimateHomography( others[k], matches[k], opts ).  Throws as
     /// estimateHomography, and when others and matches differ in size.
+    /// From the result vector to the guides of matchPairsGuidedMany: guides[k] = est[k].best < 0 ? MatchGuide::none()
+    /// : est[k].guide.  An estimate without a model carries a ZERO matrix, which as an Epipolar guide would admit every
+    /// pair: it must become MatchGuide::none(), not be forwarded.
     std::vector<HomographyEstimate> estimateHomographyMany( const std::vector<FeaturesDev*>& others, const std::vector<std::vector<Match>>& matches,
                                                             const RansacOptions& opts = RansacOptions() );
     /// the same for fundamental matrices (psx_ransac_fundamental_many)
