@@ -32,8 +32,9 @@ __device__ __forceinline__ int psx_directed_best(const int* __restrict__ res, si
 
 // The buffers of a MatchScratch.  A buffer belongs to ONE use: calls queue work without waiting for the stream, so two
 // features sharing a buffer would alias under queued work.  F32: psx_match / psx_match_pairs, U8: psx_match_u8 /
-// psx_match_pairs_u8 (match.hip); GUIDED: match_guided.hip; RANSAC: ransac.hip; MANY: the one-to-many search (match_many.hip);
-// RMANY: the batched RANSAC (ransac_many.hip); GMANY: the guided one-to-many search (match_guided_many.hip)
+// psx_match_pairs_u8 (match.hip); GUIDED: match_guided.hip; MANY: the one-to-many search (match_many.hip); GMANY: the guided
+// one-to-many search (match_guided_many.hip).  RANSAC: ransac.hip AND the batched ransac_many.hip, which adds RMANY for its
+// tables: every call of either ends synchronised, so the two never have work queued on a thread's scratch at once.
 enum MatchSlot {
     MS_F32_PARTIAL,      // the exact scan's per-chunk top-2
     MS_F32_RPERM,        // the exact scan's permuted right side
@@ -53,25 +54,19 @@ enum MatchSlot {
     MS_GUIDED_FWD,       // the forward direction's result
     MS_GUIDED_BWD,       // the backward direction's
     MS_GUIDED_LINES,     // the left side's lines for the backward direction
-    MS_RANSAC_PAIRS,     // the uploaded pair records
+    MS_RANSAC_PAIRS,     // the uploaded pair records (of all sets)
     MS_RANSAC_PTS,       // the packed correspondences
-    MS_RANSAC_MODELS,    // the hypotheses' models
+    MS_RANSAC_MODELS,    // the hypotheses' models, every set's
     MS_RANSAC_COUNTS,    // their counts
-    MS_RANSAC_STATE,     // the state block
-    MS_RANSAC_TOT,       // the compaction's per-workgroup totals
+    MS_RANSAC_STATE,     // the head, the per-set states and the per-set refit models (ransac_core.h)
+    MS_RANSAC_TOT,       // the compaction's per-workgroup totals (the batched call: and their offsets)
     MS_MANY_TABLES,      // the set / chunk / block tables
     MS_MANY_NORMS,       // the norms of all sets
     MS_MANY_PARTIAL,     // the per-chunk key pairs
     MS_MANY_FWD,         // the forward direction's results of all sets
     MS_MANY_BWD,         // the backward direction's
     MS_MANY_TOT,         // the join's per-workgroup totals and their offsets
-    MS_RMANY_TABLES,     // the batched RANSAC (ransac_many.hip): the set table and the two block tables
-    MS_RMANY_PAIRS,      // the uploaded pair records of all sets
-    MS_RMANY_PTS,        // the packed correspondences of all sets
-    MS_RMANY_MODELS,     // every set's hypotheses' models
-    MS_RMANY_COUNTS,     // their counts
-    MS_RMANY_STATE,      // the head, the per-set states and the per-set refit models
-    MS_RMANY_TOT,        // the compaction's per-workgroup totals and their offsets
+    MS_RMANY_TABLES,     // the batched RANSAC's set table and its two block tables
     MS_GMANY_TABLES,     // the guided one-to-many search (match_guided_many.hip): the set table and the backward block table
     MS_GMANY_LINES,      // the left side's lines under every set's guide, for the backward direction
     MS_GMANY_FWD,        // the forward direction's results of all sets

@@ -6,24 +6,21 @@
 // round trips, paid again for every list.  Here the K lists that psx_match_pairs_many_u8* left behind one another are
 // verified by the SAME sequence, every kernel one grid over all sets, driven by tables in which no block crosses a set
 // boundary (ransac_many_plan.h).  The rule -- samples, fit, score, select, refit, inliers -- is ransac_rule.h and
-// fundamental_rule.h, used as they are: set k's result is the single call's, bit for bit.
-//   k_rmany_gather  the four floats of every pair of every set that has a model to estimate, into ONE packed float4 array
-//                   indexed as the concatenation; set k's right positions through the set table (out-of-range indices
-//                   raise the one flag and write NaNs)
-//   k_rmany_hyp     one lane per (set, hypothesis): the sample drawn from the set's own n_k, the fixed-size fit in
-//                   registers; a set below the minimum gets zeros
-//   k_rmany_score   the hot kernel.  As k_ransac_score: lanes own pairs in VGPRs, the workgroup walks a block of M_HB
-//                   hypotheses; the block-table entry and with it the model address models[(set N + h) 9] are workgroup
-//                   uniform (scalar loads); one ballot + popcount per resident pair, ONE integer atomic per wave into
-//                   counts[set N + h] -- integer atomics are order-free, the counts are deterministic.  A wave owns M_PPL x 64
-//                   CONSECUTIVE pairs of its block, and a wave without a resident pair leaves before the loop: a short
-//                   set's last block is mostly such waves
-//   k_rmany_select  one workgroup per set: arg-max on (count descending, index ascending), copies the winner's model
-//   k_rmany_count / k_rmany_scan / k_rmany_write   the stable compaction of wg_compact.h, segmented as the one-to-many
-//                   join (match_many.hip) runs it: one total per 256-pair workgroup in set-major order, an exclusive scan
-//                   of the totals by one workgroup, one 16-byte store per survivor; a set's total is the difference of the
-//                   scan at its boundaries.  No atomics.  The payload is any 16-byte record array
-//   k_rmany_decide  one lane per set: keeps the refit model iff it was tried, may score and does not lose inliers
+// fundamental_rule.h, and every step of the estimator around it is the ONE statement of ransac_core.h that the single call
+// runs too: set k's result is the single call's, bit for bit.  The kernels here say where a step's operands live:
+//   k_rmany_gather  r_gather per pair of every set that has a model to estimate, into ONE packed float4 array indexed as
+//                   the concatenation; set k's right positions through the set table
+//   k_rmany_hyp     one lane per (set, hypothesis): r_sample_fit on the set's own n_k; a set below the minimum gets zeros
+//   k_rmany_score   the hot kernel: r_score_walk over a block of M_HB hypotheses.  The block-table entry and with it the
+//                   model address models[(set N + h) mstride] are workgroup uniform (scalar loads), the counts go to
+//                   counts[(set N + h) cstride].  A wave owns M_PPL x 64 CONSECUTIVE pairs of its block, and a wave without
+//                   a resident pair leaves before the walk: a short set's last block is mostly such waves
+//   k_rmany_select  r_select, one workgroup per set
+//   k_rmany_count / k_rmany_scan / k_rmany_write   r_keep into the stable compaction of wg_compact.h, segmented as the
+//                   one-to-many join (match_many.hip) runs it: one total per 256-pair workgroup in set-major order, an
+//                   exclusive scan of the totals by one workgroup, one 16-byte store per survivor; a set's total is the
+//                   difference of the scan at its boundaries.  No atomics.  The payload is any 16-byte record array
+//   k_rmany_decide  r_decide, one lane per set
 // The refit's fit is serial by definition: every set's winner correspondences come to the host through the pinned
 // staging buffer in ONE compaction, the host fits the sets whose refit is due, ONE upload carries all refit models with a
 // per-set "tried" word, and the score kernel runs once more with one model per set.
@@ -31,12 +28,10 @@
 // 7 kernels and 1 synchronisation without the refit; with it 5 more (score, decide, the compaction's 3) -- 12 kernels and
 // 2 synchronisations.
 #include "psx_internal.h"
-#include "match_scratch.h"
+#include "ransac_core.h"
 #include "ransac_many_plan.h"
-#include "ransac_model.h"
 #include "wg_compact.h"
 
-#include <cmath>
 #include <cstring>
 #include <new>
 
@@ -56,19 +51,6 @@ struct RMSet {                               // one entry per set
 };
 static_assert(sizeof(RMSet) == 32, "two 16-byte scalar loads per entry");
 
-struct RMHead { int bad, total, pad[2]; };   // device resident, in front of the states: the one flag, the sum of the totals
-struct RMState {                             // per set; copied to the host with the head at the end of a stage
-    float kept[9];
-    int best, sample_inliers, refit_kept, total, pad[3];
-};
-struct RMRefit {                             // per set; uploaded in one copy before the refit's score launch
-    int tried, count;
-    float m[9];
-    int pad;
-};
-static_assert(sizeof(RMHead) == 16 && sizeof(RMState) == 64 && sizeof(RMRefit) == 48, "state layout");
-constexpr int RM_REFIT_WORDS = sizeof(RMRefit) / 4;
-
 // grid: the 256-pair blocks
 __global__ __launch_bounds__(256) void k_rmany_gather(const int4* __restrict__ pairs, const RMSet* __restrict__ sets,
                                                       const int4* __restrict__ blocks, const float2* __restrict__ lxy, int l_len,
@@ -78,35 +60,7 @@ __global__ __launch_bounds__(256) void k_rmany_gather(const int4* __restrict__ p
     const RMSet s = sets[blk.x];
     const int p = blk.y + (int)threadIdx.x;
     if (p >= blk.z) return;
-    const int4 rec = pairs[p];
-    if (rec.x < 0 || rec.x >= l_len || rec.y < 0 || rec.y >= s.r_len) {
-        atomicOr(bad, 1);
-        pts[p] = make_float4(NAN, NAN, NAN, NAN);
-        return;
-    }
-    const float2 a = lxy[rec.x], b = s.rxy[rec.y];
-    pts[p] = make_float4(a.x, a.y, b.x, b.y);
-}
-
-// the sample and the fixed-size fit of a model kind: the bodies of k_ransac_hyp / k_ransac_hyp_fund
-template <int KIND> __device__ __forceinline__ void rmany_fit(const float4* __restrict__ pts, int n, unsigned seed, int h, float m[9]);
-template <> __device__ __forceinline__ void rmany_fit<PSX_GUIDE_HOMOGRAPHY>(const float4* __restrict__ pts, int n, unsigned seed, int h, float m[9])
-{
-    int idx[4];
-    psx_ransac_sample(seed, h, n, idx);
-    psx_ransac_pt q[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) q[k] = r_pt(pts[idx[k]]);
-    psx_homography_fit_rule<4>(q, 4, m);
-}
-template <> __device__ __forceinline__ void rmany_fit<PSX_GUIDE_EPIPOLAR>(const float4* __restrict__ pts, int n, unsigned seed, int h, float m[9])
-{
-    int idx[PSX_FUND_MIN];
-    psx_ransac_sample_k<PSX_FUND_MIN>(seed, h, n, idx);
-    psx_ransac_pt q[PSX_FUND_MIN];
-#pragma unroll
-    for (int k = 0; k < PSX_FUND_MIN; k++) q[k] = r_pt(pts[idx[k]]);
-    psx_fundamental_fit_rule<PSX_FUND_MIN>(q, PSX_FUND_MIN, m);
+    r_gather(pairs[p], lxy, l_len, s.rxy, s.r_len, pts + p, bad);
 }
 
 // grid K * hw (hw = ceil(N / 64)) waves, workgroup k * hw + w: one lane per (set, hypothesis)
@@ -119,7 +73,7 @@ __global__ __launch_bounds__(64) void k_rmany_hyp(const float4* __restrict__ pts
     if (h >= N) return;
     const RMSet s = sets[k];
     float m[9];
-    if (s.n >= RModel<KIND>::MIN) rmany_fit<KIND>(pts + s.off, s.n, seed, h, m);          // workgroup uniform
+    if (s.n >= RModel<KIND>::MIN) r_sample_fit<KIND>(pts + s.off, s.n, seed, h, m);       // workgroup uniform
     else {
 #pragma unroll
         for (int j = 0; j < 9; j++) m[j] = 0.0f;
@@ -132,7 +86,7 @@ __global__ __launch_bounds__(64) void k_rmany_hyp(const float4* __restrict__ pts
 
 // grid nsb * ceil(N / M_HB), workgroup hb * nsb + b: block b of the score table x hypotheses [hb M_HB, + M_HB) of ITS set.
 // Model (set, h) lies at models + (set N + h) mstride, its count at counts + (set N + h) cstride: 9 and 1 for the
-// hypotheses, the RMRefit array (N = 1) for the refit.
+// hypotheses, the RRefit array (N = 1) for the refit.  A wave owns M_PPL x 64 consecutive pairs of its block.
 template <int KIND>
 __global__ __launch_bounds__(256) void k_rmany_score(const float4* __restrict__ pts, const int4* __restrict__ blocks, int nsb,
                                                      const float* __restrict__ models, int N, int mstride, float tol,
@@ -151,84 +105,37 @@ __global__ __launch_bounds__(256) void k_rmany_score(const float4* __restrict__ 
         q[k] = r_pt(in[k] ? pts[p] : make_float4(0.f, 0.f, 0.f, 0.f));
     }
     const int h0 = (int)(blockIdx.x / (unsigned)nsb) * M_HB;
-    const int h1 = h0 + M_HB < N ? h0 + M_HB : N;
-    const size_t row = (size_t)blk.x * (size_t)N;
-    for (int h = h0; h < h1; h++) {
-        float m[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) m[k] = models[(row + h) * mstride + k];    // workgroup-uniform address
-        if (!RModel<KIND>::usable(m)) continue;                           // workgroup uniform
-        int c = 0;
-#pragma unroll
-        for (int k = 0; k < M_PPL; k++) {
-            const psx_guide_line l = psx_guide_left(KIND, m, tol, q[k].xl, q[k].yl);
-            c += __popcll(__ballot(in[k] && psx_guide_right(KIND, l, q[k].xr, q[k].yr)));
-        }
-        if (lane == 0 && c > 0) atomicAdd(counts + (row + h) * cstride, c);
-    }
+    r_score_walk<KIND, M_PPL>(q, in, models, counts, (size_t)blk.x * (size_t)N, mstride, cstride, h0, h0 + M_HB < N ? h0 + M_HB : N, tol);
 }
 
 // one workgroup of 256 threads per set
 __global__ __launch_bounds__(256) void k_rmany_select(const RMSet* __restrict__ sets, const int* __restrict__ counts, int N,
-                                                      const float* __restrict__ models, RMState* __restrict__ st)
+                                                      const float* __restrict__ models, RState* __restrict__ st)
 {
     const int set = blockIdx.x;
     if (sets[set].b0 == sets[set].b1) return;                              // below the minimum: its state stays zero
     const size_t row = (size_t)set * (size_t)N;
-    int bc = -1, bh = 0x7fffffff;
-    for (int h = threadIdx.x; h < N; h += 256) r_better(bc, bh, counts[row + h], h);
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) {
-        const int oc = __shfl_xor(bc, k), oh = __shfl_xor(bh, k);
-        r_better(bc, bh, oc, oh);
-    }
-    __shared__ int s_c[4], s_h[4];
-    if ((threadIdx.x & 63) == 0) { s_c[threadIdx.x >> 6] = bc; s_h[threadIdx.x >> 6] = bh; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) r_better(bc, bh, s_c[w], s_h[w]);
-        st[set].best = bh; st[set].sample_inliers = bc;                    // N >= 1: thread 0 saw hypothesis 0
-        for (int k = 0; k < 9; k++) st[set].kept[k] = models[9 * (row + bh) + k];
-    }
+    r_select(counts + row, N, models + 9 * row, st + set);
 }
 
 // one lane per set
 template <int KIND>
-__global__ __launch_bounds__(256) void k_rmany_decide(RMState* __restrict__ st, const RMRefit* __restrict__ rf, int n_sets)
+__global__ __launch_bounds__(256) void k_rmany_decide(RState* __restrict__ st, const RRefit* __restrict__ rf, int n_sets)
 {
     const int set = blockIdx.x * 256 + threadIdx.x;
-    if (set >= n_sets || rf[set].tried == 0) return;
-    float m[9];
-    for (int k = 0; k < 9; k++) m[k] = rf[set].m[k];
-    if (RModel<KIND>::usable(m) && rf[set].count >= st[set].sample_inliers) {
-        for (int k = 0; k < 9; k++) st[set].kept[k] = m[k];
-        st[set].refit_kept = 1;
-    }
-}
-
-// keep: pair i of block blk passes under its set's kept model (no pair does under one that may not score, or after a bad
-// index).  The state is read at a workgroup-uniform address.
-template <int KIND>
-__device__ __forceinline__ bool rmany_keep(const float4* __restrict__ pts, const int4 blk, const RMHead* __restrict__ head,
-                                           const RMState* __restrict__ st, float tol, int i)
-{
-    float m[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) m[k] = st[blk.x].kept[k];
-    if (head->bad != 0 || !RModel<KIND>::usable(m) || i >= blk.z) return false;
-    const psx_ransac_pt p = r_pt(pts[i]);
-    return psx_guide_right(KIND, psx_guide_left(KIND, m, tol, p.xl, p.yl), p.xr, p.yr);
+    if (set < n_sets) r_decide<KIND>(st, rf, set);
 }
 
 // grid: the 256-pair blocks, set-major as the table is
 template <int KIND>
 __global__ __launch_bounds__(256) void k_rmany_count(const float4* __restrict__ pts, const int4* __restrict__ blocks,
-                                                     const RMHead* __restrict__ head, const RMState* __restrict__ st, float tol,
+                                                     const RHead* __restrict__ head, const RState* __restrict__ st, float tol,
                                                      int* __restrict__ wg_tot)
 {
     const int4 blk = blocks[blockIdx.x];
+    const int i = blk.y + (int)threadIdx.x;
     __shared__ int s_cnt[4];
-    wg_count(__ballot(rmany_keep<KIND>(pts, blk, head, st, tol, blk.y + (int)threadIdx.x)), s_cnt);
+    wg_count(__ballot(r_keep<KIND>(head, st + blk.x, i < blk.z, pts, i, tol)), s_cnt);
     if (threadIdx.x == 0) wg_tot[blockIdx.x] = wg_total(s_cnt);
 }
 
@@ -242,13 +149,13 @@ __global__ __launch_bounds__(1024) void k_rmany_scan(const int* __restrict__ wg_
 // out: never written at or past `capacity`.  A set's first workgroup writes the set's total, workgroup 0 the sum.
 template <int KIND>
 __global__ __launch_bounds__(256) void k_rmany_write(const float4* __restrict__ pts, const RMSet* __restrict__ sets,
-                                                     const int4* __restrict__ blocks, RMHead* __restrict__ head, RMState* __restrict__ st,
+                                                     const int4* __restrict__ blocks, RHead* __restrict__ head, RState* __restrict__ st,
                                                      float tol, const int* __restrict__ offs, const int4* __restrict__ src,
                                                      int4* __restrict__ out, int capacity)
 {
     const int4 blk = blocks[blockIdx.x];
     const int i = blk.y + (int)threadIdx.x;
-    const bool keep = rmany_keep<KIND>(pts, blk, head, st, tol, i);
+    const bool keep = r_keep<KIND>(head, st + blk.x, i < blk.z, pts, i, tol);
     const unsigned long long m = __ballot(keep);
     __shared__ int s_cnt[4];
     wg_count(m, s_cnt);
@@ -270,8 +177,8 @@ struct RMQueue {
     const int4 *d_sblk, *d_cblk;
     int nsb, ncb, K;
     float4* d_pts;
-    RMHead* d_head;
-    RMState* d_state;
+    RHead* d_head;
+    RState* d_state;
     int *d_tot, *d_offs;
     float tol;
 };
@@ -321,16 +228,16 @@ int ransac_many_run(int device, const void* host_pairs, const void* d_pairs_in, 
     // the device blob: set table, score blocks, compaction blocks; the pinned buffer: states, refit models, blob, records
     const size_t sets_b = pad16(sizeof(RMSet) * (size_t)K), sblk_b = sizeof(int4) * (size_t)nsb, cblk_b = sizeof(int4) * (size_t)ncb;
     const size_t blob_b = sets_b + sblk_b + cblk_b;
-    const size_t state_b = sizeof(RMHead) + sizeof(RMState) * (size_t)K, refit_b = sizeof(RMRefit) * (size_t)K;
+    const size_t state_b = sizeof(RHead) + sizeof(RState) * (size_t)K, refit_b = sizeof(RRefit) * (size_t)K;
     const size_t pin_state = 0, pin_refit = pad16(state_b), pin_blob = pin_refit + refit_b, pin_rec = pin_blob + blob_b;
     // every buffer before the first launch: nothing is reallocated under queued work
-    if ((host_pairs && !sc.need(MS_RMANY_PAIRS, 16 * (size_t)n)) || !sc.need(MS_RMANY_TABLES, blob_b) || !sc.need(MS_RMANY_PTS, 16 * (size_t)n) ||
-        !sc.need(MS_RMANY_MODELS, sizeof(float) * 9 * (size_t)K * (size_t)N) || !sc.need(MS_RMANY_COUNTS, sizeof(int) * (size_t)K * (size_t)N) ||
-        !sc.need(MS_RMANY_STATE, pin_refit + refit_b) || !sc.need(MS_RMANY_TOT, sizeof(int) * (2 * (size_t)ncb + 1)) ||
+    if ((host_pairs && !sc.need(MS_RANSAC_PAIRS, 16 * (size_t)n)) || !sc.need(MS_RMANY_TABLES, blob_b) || !sc.need(MS_RANSAC_PTS, 16 * (size_t)n) ||
+        !sc.need(MS_RANSAC_MODELS, sizeof(float) * 9 * (size_t)K * (size_t)N) || !sc.need(MS_RANSAC_COUNTS, sizeof(int) * (size_t)K * (size_t)N) ||
+        !sc.need(MS_RANSAC_STATE, pin_refit + refit_b) || !sc.need(MS_RANSAC_TOT, sizeof(int) * (2 * (size_t)ncb + 1)) ||
         !sc.need_pinned(pin_rec + 16 * (size_t)(refit ? n : nrec)))
         return PSX_ERR_NOMEM;
-    void* dev_pin = nullptr;
-    if (hipHostGetDevicePointer(&dev_pin, sc.hpin, 0) != hipSuccess || dev_pin == nullptr) return PSX_ERR_HIP;
+    void* dev_pin = r_pinned_dev(sc);
+    if (dev_pin == nullptr) return PSX_ERR_HIP;
     char* hpin = static_cast<char*>(sc.hpin);
     void* d_pin_rec = static_cast<char*>(dev_pin) + pin_rec;
 
@@ -360,26 +267,26 @@ int ransac_many_run(int device, const void* host_pairs, const void* d_pairs_in, 
     hipStream_t st = sc.stream;
     const void* d_pairs = d_pairs_in;
     if (host_pairs) {
-        if (hipMemcpyAsync(sc.buf[MS_RMANY_PAIRS], host_pairs, 16 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
-        d_pairs = sc.buf[MS_RMANY_PAIRS];
+        if (hipMemcpyAsync(sc.buf[MS_RANSAC_PAIRS], host_pairs, 16 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
+        d_pairs = sc.buf[MS_RANSAC_PAIRS];
     }
     char* d_blob = static_cast<char*>(sc.buf[MS_RMANY_TABLES]);
-    char* d_st = static_cast<char*>(sc.buf[MS_RMANY_STATE]);
+    char* d_st = static_cast<char*>(sc.buf[MS_RANSAC_STATE]);
     RMQueue q;
     q.st = st; q.K = K; q.nsb = (int)nsb; q.ncb = (int)ncb; q.tol = tol;
     q.d_sets = reinterpret_cast<const RMSet*>(d_blob);
     q.d_sblk = reinterpret_cast<const int4*>(d_blob + sets_b);
     q.d_cblk = reinterpret_cast<const int4*>(d_blob + sets_b + sblk_b);
-    q.d_pts = static_cast<float4*>(sc.buf[MS_RMANY_PTS]);
-    q.d_head = reinterpret_cast<RMHead*>(d_st);
-    q.d_state = reinterpret_cast<RMState*>(d_st + sizeof(RMHead));
-    q.d_tot = static_cast<int*>(sc.buf[MS_RMANY_TOT]);
+    q.d_pts = static_cast<float4*>(sc.buf[MS_RANSAC_PTS]);
+    q.d_head = reinterpret_cast<RHead*>(d_st);
+    q.d_state = reinterpret_cast<RState*>(d_st + sizeof(RHead));
+    q.d_tot = static_cast<int*>(sc.buf[MS_RANSAC_TOT]);
     q.d_offs = q.d_tot + ncb;
-    RMRefit* d_refit = reinterpret_cast<RMRefit*>(d_st + pin_refit);
-    float* d_models = static_cast<float*>(sc.buf[MS_RMANY_MODELS]);
-    int* d_counts = static_cast<int*>(sc.buf[MS_RMANY_COUNTS]);
-    const RMHead* hh = reinterpret_cast<const RMHead*>(hpin + pin_state);
-    const RMState* hs = reinterpret_cast<const RMState*>(hpin + pin_state + sizeof(RMHead));
+    RRefit* d_refit = reinterpret_cast<RRefit*>(d_st + pin_refit);
+    float* d_models = static_cast<float*>(sc.buf[MS_RANSAC_MODELS]);
+    int* d_counts = static_cast<int*>(sc.buf[MS_RANSAC_COUNTS]);
+    const RHead* hh = reinterpret_cast<const RHead*>(hpin + pin_state);
+    const RState* hs = reinterpret_cast<const RState*>(hpin + pin_state + sizeof(RHead));
     void* final_out = host_inl ? d_pin_rec : d_inl;
     const int final_cap = host_inl ? nrec : capacity;
     const unsigned hw = (unsigned)((N + 63) / 64);
@@ -395,9 +302,7 @@ int ransac_many_run(int device, const void* host_pairs, const void* d_pairs_in, 
     // with the refit: every set's winner correspondences to the host; without: the inlier records, and the call is complete
     if (refit) queue_compact<KIND>(q, q.d_pts, d_pin_rec, n);
     else queue_compact<KIND>(q, d_pairs, final_out, final_cap);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hpin + pin_state, d_st, state_b, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return PSX_ERR_HIP;
+    if (!r_stage_end(st, hpin + pin_state, d_st, state_b)) return PSX_ERR_HIP;
     if (hh->bad != 0) return PSX_ERR_INVALID;
     auto sane = [&]() {
         long long sum = 0;
@@ -410,44 +315,27 @@ int ransac_many_run(int device, const void* host_pairs, const void* d_pairs_in, 
     };
     if (!sane()) return PSX_ERR_HIP;
     if (refit) {
-        // set k's winner correspondences lie behind those of the sets before it, in pair order
-        RMRefit* up = reinterpret_cast<RMRefit*>(hpin + pin_refit);
+        // set k's winner correspondences lie behind those of the sets before it, in pair order; a set below the minimum
+        // has a zero state, which is never due
+        RRefit* up = reinterpret_cast<RRefit*>(hpin + pin_refit);
         const psx_ransac_pt* rec = reinterpret_cast<const psx_ransac_pt*>(hpin + pin_rec);
         bool any = false;
         size_t at = 0;
-        for (int k = 0; k < K; at += (size_t)hs[k].total, k++) {
-            up[k].tried = 0; up[k].count = 0; up[k].pad = 0;
-            for (int j = 0; j < 9; j++) up[k].m[j] = NAN;                   // a model no rule lets score
-            const int c = hs[k].sample_inliers;
-            if (set_counts[k] < MIN || c < MIN || hs[k].total != c) continue;
-            float m[9];
-            RModel<KIND>::fit(rec + at, c, m);
-            if (!RModel<KIND>::usable(m)) continue;
-            for (int j = 0; j < 9; j++) up[k].m[j] = m[j];
-            up[k].tried = 1;
-            any = true;
-        }
+        for (int k = 0; k < K; at += (size_t)hs[k].total, k++) any |= r_refit_model<KIND>(hs[k], rec + at, up + k);
         if (any) {
             if (hipMemcpyAsync(d_refit, up, refit_b, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
-            queue_score<KIND>(q, d_refit->m, 1, RM_REFIT_WORDS, &d_refit->count, RM_REFIT_WORDS);
+            queue_score<KIND>(q, d_refit->m, 1, R_REFIT_WORDS, &d_refit->count, R_REFIT_WORDS);
             hipLaunchKernelGGL(k_rmany_decide<KIND>, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, q.d_state, d_refit, K);
         }
         queue_compact<KIND>(q, d_pairs, final_out, final_cap);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hpin + pin_state, d_st, state_b, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return PSX_ERR_HIP;
-        if (!sane()) return PSX_ERR_HIP;
+        if (!r_stage_end(st, hpin + pin_state, d_st, state_b) || !sane()) return PSX_ERR_HIP;
     }
-    if (host_models && (hipMemcpyAsync(host_models, d_models, sizeof(float) * 9 * (size_t)K * (size_t)N, hipMemcpyDeviceToHost, st) != hipSuccess)) return PSX_ERR_HIP;
-    if (host_counts && (hipMemcpyAsync(host_counts, d_counts, sizeof(int) * (size_t)K * (size_t)N, hipMemcpyDeviceToHost, st) != hipSuccess)) return PSX_ERR_HIP;
-    if ((host_models || host_counts) && hipStreamSynchronize(st) != hipSuccess) return PSX_ERR_HIP;
+    if (!r_download_layers(st, host_models, d_models, host_counts, d_counts, (size_t)K * (size_t)N)) return PSX_ERR_HIP;
     const int total = hh->total;
     if (host_inl && total > 0 && nrec > 0) memcpy(host_inl, hpin + pin_rec, 16 * (size_t)(total < nrec ? total : nrec));
-    for (int k = 0; k < K; k++) {
-        psx_ransac_result* r = results + k;
-        if (set_counts[k] < MIN || !RModel<KIND>::usable(hs[k].kept)) { psx_ransac_no_model(r); continue; }   // its total is 0: no pair passes
-        for (int j = 0; j < 9; j++) r->m[j] = hs[k].kept[j];
-        r->best = hs[k].best; r->sample_inliers = hs[k].sample_inliers; r->inliers = hs[k].total; r->refit_kept = hs[k].refit_kept;
+    for (int k = 0; k < K; k++) {                                          // a set below the minimum has a zero state, which a
+        if (set_counts[k] < MIN) psx_ransac_no_model(results + k);         // homography may take for a model
+        else r_result<KIND>(hs[k], results + k);
     }
     *count = total;
     return PSX_OK;

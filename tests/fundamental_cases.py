@@ -23,9 +23,11 @@ from tests.ransac_cases import (M32, PAIR_DTYPE, PAIR_U8_DTYPE, _div, _side, bit
 TOL = 2.0
 KINDS = ("general", "rectified")
 # (n, N, seed): the ballot (64) and workgroup (256 pairs; 64 hypotheses per score workgroup, 256 per select pass)
-# boundaries on both axes, below-minimum n, and one case of several workgroups
+# boundaries on both axes, below-minimum n, one case of several workgroups, the single call's score block of 1024 pairs
+# (256 threads x 4 resident pairs) from both sides -- under (1025, 8, 32) the one pair of the second block passes under a
+# hypothesis of either scene -- and N = 1, the hypothesis count of the refit's own score launch
 SHAPES = [(0, 8, 0), (7, 8, 0), (8, 8, 1), (9, 64, 2), (63, 64, 3), (64, 65, 4), (65, 64, 5), (129, 128, 6), (300, 256, 7),
-          (2500, 512, 8)]
+          (2500, 512, 8), (1023, 8, 9), (1024, 8, 9), (1025, 8, 32), (65, 1, 56)]
 SHAPE_IDS = ["n%d_N%d" % (n, N) for n, N, _ in SHAPES]
 TIE_SHAPES = [(8, 8, 1), (9, 64, 2)]
 

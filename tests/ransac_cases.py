@@ -18,9 +18,10 @@ from tests.guided_cases import H_ASYM
 TOL = 2.0
 RADII = (0.0, 0.5, 1.5)
 # (n, N, seed): the ballot (64) and workgroup (256 pairs; 64 hypotheses per score workgroup, 256 per select pass)
-# boundaries on both axes, below-minimum n, and one case of several workgroups
+# boundaries on both axes, below-minimum n, one case of several workgroups, the single call's score block of 1024 pairs
+# (256 threads x 4 resident pairs) from both sides, and N = 1, the hypothesis count of the refit's own score launch
 SHAPES = [(0, 8, 0), (3, 8, 0), (4, 8, 1), (5, 64, 2), (63, 64, 3), (64, 65, 4), (65, 64, 5), (129, 128, 6), (300, 256, 7),
-          (2500, 512, 8)]
+          (2500, 512, 8), (1023, 8, 9), (1024, 8, 9), (1025, 8, 32), (65, 1, 10)]
 SHAPE_IDS = ["n%d_N%d" % (n, N) for n, N, _ in SHAPES]
 TIE_SHAPES = [(4, 8, 1), (5, 64, 2)]
 PAIR_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4"), ("d1", "<f4"), ("d2", "<f4")])

@@ -7,7 +7,8 @@ The premises (asserted in test_premises_of_the_planted_inputs, from the restatem
 shape has a non-finite model; (4, 8, 1) has all eight hypotheses tied at 4 inliers and (5, 64, 2) has 17 tied at 4, the
 lowest of them h = 1; every other shape has a unique winner; the refit is kept everywhere; and the refit model recovers
 (63, 64, 3): 38 of 39 planted pairs, (64, 65, 4): 37 of 39, (65, 64, 5): 39 of 39, (129, 128, 6): 77 of 78, (300, 256, 7): 180
-of 180, (2500, 512, 8): 1500 of 1500."""
+of 180, (2500, 512, 8): 1500 of 1500, (1023, 8, 9): 595 of 615, (1024, 8, 9): 615 of 615, (1025, 8, 32): 590 of 615 and, from
+its one hypothesis of 5 inliers, (65, 1, 10): 15 of 39."""
 import ctypes as C
 import os
 import shutil
@@ -23,7 +24,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (n, N, seed) -> (best, its count, hypotheses at that count, inliers after the refit, planted pairs among them, planted pairs)
 PREMISES = {(4, 8, 1): (0, 4, 8, 4, 4, 4), (5, 64, 2): (1, 4, 17, 4, 3, 3), (63, 64, 3): (49, 31, 1, 38, 38, 39),
             (64, 65, 4): (14, 37, 1, 37, 37, 39), (65, 64, 5): (40, 39, 1, 39, 39, 39), (129, 128, 6): (27, 66, 1, 77, 77, 78),
-            (300, 256, 7): (229, 170, 1, 180, 180, 180), (2500, 512, 8): (361, 1500, 1, 1500, 1500, 1500)}
+            (300, 256, 7): (229, 170, 1, 180, 180, 180), (2500, 512, 8): (361, 1500, 1, 1500, 1500, 1500),
+            (1023, 8, 9): (0, 401, 1, 595, 595, 615), (1024, 8, 9): (7, 538, 1, 615, 615, 615),
+            (1025, 8, 32): (1, 268, 1, 590, 590, 615), (65, 1, 10): (0, 5, 1, 15, 15, 39)}
 
 
 @pytest.mark.parametrize("n,N,seed", rc.SHAPES, ids=rc.SHAPE_IDS)

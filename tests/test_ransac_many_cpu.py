@@ -35,10 +35,20 @@ def test_entry_points_declared_and_bound(capi):
     plan = open(os.path.join(hip, "ransac_many_plan.h")).read()
     assert "hip/hip_runtime.h" not in plan and "__global__" not in plan and "__device__" not in plan      # plain C++
     src = open(os.path.join(hip, "ransac_many.hip")).read()
-    # the rule headers are used as they are: the kernels call them, nothing is restated
-    for piece in ('#include "ransac_many_plan.h"', "psx_ransac_sample(", "psx_ransac_sample_k<PSX_FUND_MIN>(", "psx_homography_fit_rule<4>(",
-                  "psx_fundamental_fit_rule<PSX_FUND_MIN>(", "psx_guide_left(", "psx_guide_right(", "wg_scan_totals("):
+    one = open(os.path.join(hip, "ransac.hip")).read()
+    core = open(os.path.join(hip, "ransac_core.h")).read()
+    for piece in ('#include "ransac_many_plan.h"', '#include "ransac_core.h"', "wg_scan_totals("):
         assert piece in src, piece
+    # the rule headers are used as they are: the device pieces call them, nothing is restated -- and the pieces stand once,
+    # in the header that the single call's kernels use too
+    assert '#include "ransac_core.h"' in one
+    for piece in ("psx_ransac_sample(", "psx_ransac_sample_k<PSX_FUND_MIN>(", "psx_homography_fit_rule<4>(",
+                  "psx_fundamental_fit_rule<PSX_FUND_MIN>(", "psx_guide_left(", "psx_guide_right("):
+        assert core.count(piece) >= 1, piece
+    for piece in ("psx_homography_fit_rule<4>(", "psx_fundamental_fit_rule<PSX_FUND_MIN>(", "psx_guide_left(", "psx_guide_right("):
+        assert piece not in src and piece not in one, piece
+    for piece in ("r_gather(", "r_sample_fit<KIND>(", "r_score_walk<KIND, ", "r_select(", "r_keep<KIND>(", "r_decide<KIND>("):
+        assert piece in src and piece in one, piece
     fh = open(os.path.join(ROOT, "popsift_amd", "csrc", "include", "popsift", "features.h")).read()
     assert "estimateHomographyMany(" in fh and "estimateFundamentalMany(" in fh
 
