@@ -583,8 +583,8 @@ int psx_ransac_homography_dev(int device, const void* d_pairs, int n, const floa
  *   4 - 6.       as above with 8 in place of 4; the refit model is kept iff it may score and its count is >= the winner's.
  * n < 8, or a kept model that may not score, gives PSX_OK with best = -1, a zero matrix, *count = 0.  Arguments, opts,
  * result, capacity and errors are those of the homography calls. */
-/* Host only.  step 1 with k draws per hypothesis, k = 4 (== psx_ransac_samples) or 8: idx[k * i ..]; PSX_ERR_INVALID for
- * another k, n < k, and as psx_ransac_samples */
+/* Host only.  step 1 with k draws per hypothesis, k = 2, 3, 4 (== psx_ransac_samples) or 8: idx[k * i ..]; the draws of a
+ * smaller k are the first k of a larger one's.  PSX_ERR_INVALID for another k, n < k, and as psx_ransac_samples */
 int psx_ransac_samples_k(unsigned seed, int first, int count, int n, int k, int* idx);
 /* step 2 on n >= 8 correspondences left_xy[i] -> right_xy[i], in the given order; m: 9 floats, row major */
 int psx_fundamental_fit(const float* left_xy, const float* right_xy, int n, float* m);
@@ -597,6 +597,46 @@ int psx_ransac_fundamental(int device, const void* host_pairs, int n, const floa
 int psx_ransac_fundamental_dev(int device, const void* d_pairs, int n, const float* d_left_xy, int l_len,
                                const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
                                void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
+
+/* The same for the two registration models below a homography: a 2-D AFFINE transform (3 pairs; OpenCV's
+ * estimateAffine2D) and a 2-D SIMILARITY (rotation, uniform scale, translation; 2 pairs; OpenCV's
+ * estimateAffinePartial2D).  A pair list too short for a homography -- 2 or 3 correct pairs -- still gives a model, fewer
+ * hypotheses are needed at the same outlier rate, and no degree of freedom is spent on perspective the scene does not
+ * have.  The result's m is a valid psx_guide matrix for PSX_GUIDE_HOMOGRAPHY (left -> right) whose last row is EXACTLY
+ * (0, 0, 1): psx_guides_from_ransac(..., PSX_GUIDE_HOMOGRAPHY, ...) and psx_match_pairs_guided* take it as it is.  A
+ * similarity has m[0] == m[4] and m[1] == -m[3] up to the final rounding: it cannot represent a reflection (a mirrored
+ * scene needs the affine model).  The rule has the same six steps, stated operation by operation in
+ * csrc/hip/affine_rule.h ("Geometric verification", in words), and the device result equals
+ * psx_ransac_affine_ref / psx_ransac_similarity_ref bit for bit:
+ *   1. samples:  the first THREE (affine) or TWO (similarity) of the homography's four draws, by the same hash;
+ *   2. fit:      both sides normalised as for the homography; affine: the 3 x 3 normal equations with two right-hand
+ *                sides, LDL^T without pivoting; similarity: the closed form p = sum(x*u + y*v) / sum(x*x + y*y),
+ *                q = sum(x*v - y*u) / sum(x*x + y*y), rows (p, -q, 0), (q, p, 0) -- in double, rounded once to float32;
+ *                no special case for a degenerate sample (a repeated or collinear left point gives non-finite entries);
+ *   3 - 6.       as for the homography, the HOMOGRAPHY rule of guided matching, with 3 / 2 in place of 4.
+ * n < 3 / n < 2, or a kept model with a non-finite entry, gives PSX_OK with best = -1, a zero matrix, *count = 0.
+ * Arguments, opts, result, capacity, the host_models / host_counts layers and errors are those of the homography calls;
+ * psx_affine_fit needs n >= 3 and psx_similarity_fit n >= 2 (PSX_ERR_INVALID otherwise). */
+int psx_affine_fit(const float* left_xy, const float* right_xy, int n, float* m);
+int psx_ransac_affine_ref(const void* pairs, int n, const float* left_xy, int nl, const float* right_xy, int nr,
+                          const psx_ransac_opts* opts, psx_ransac_result* result, void* inliers, int capacity, int* count,
+                          float* models, int* counts);
+int psx_ransac_affine(int device, const void* host_pairs, int n, const float* d_left_xy, int l_len,
+                      const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                      void* host_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_affine_dev(int device, const void* d_pairs, int n, const float* d_left_xy, int l_len,
+                          const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                          void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_similarity_fit(const float* left_xy, const float* right_xy, int n, float* m);
+int psx_ransac_similarity_ref(const void* pairs, int n, const float* left_xy, int nl, const float* right_xy, int nr,
+                              const psx_ransac_opts* opts, psx_ransac_result* result, void* inliers, int capacity, int* count,
+                              float* models, int* counts);
+int psx_ransac_similarity(int device, const void* host_pairs, int n, const float* d_left_xy, int l_len,
+                          const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                          void* host_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_similarity_dev(int device, const void* d_pairs, int n, const float* d_left_xy, int l_len,
+                              const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                              void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
 
 /* MANY LISTS IN ONE CALL.  psx_match_pairs_many_u8* leaves the concatenation P_0 .. P_{K-1} of K pair lists and their
  * counts; these verify all K in one call -- a number of kernel launches that does not grow with n_sets (7 without the
@@ -616,7 +656,7 @@ int psx_ransac_fundamental_dev(int device, const void* d_pairs, int n, const flo
  * sum of results[j].inliers for j < k; *count = the sum over all sets; the first min(*count, capacity) records are
  * written, nothing at or past capacity; capacity = 0 with a NULL output asks "how many?".  host_models (n_sets x N x 9
  * floats) and host_counts (n_sets x N ints) receive every set's layers, either may be NULL.
- * A set with fewer than 4 (homography) / 8 (fundamental) pairs yields the "no model" result, contributes nothing to the
+ * A set with fewer than 4 (homography) / 8 (fundamental) / 3 (affine) / 2 (similarity) pairs yields the "no model" result, contributes nothing to the
  * output and has zeros in its rows of host_models / host_counts.  n_sets = 0, or all sets below the minimum, gives
  * PSX_OK without touching a device.
  * PSX_ERR_INVALID, with nothing touched and before any device call: everything the single call refuses; n_sets < 0;
@@ -640,6 +680,22 @@ int psx_ransac_fundamental_many_dev(int device, const void* d_pairs, const int* 
                                     const float* d_left_xy, int l_len, const float* const* d_right_xys, const int* r_lens,
                                     const psx_ransac_opts* opts, psx_ransac_result* results,
                                     void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_affine_many(int device, const void* host_pairs, const int* set_counts, int n_sets,
+                         const float* d_left_xy, int l_len, const float* const* d_right_xys, const int* r_lens,
+                         const psx_ransac_opts* opts, psx_ransac_result* results,
+                         void* host_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_affine_many_dev(int device, const void* d_pairs, const int* set_counts, int n_sets,
+                             const float* d_left_xy, int l_len, const float* const* d_right_xys, const int* r_lens,
+                             const psx_ransac_opts* opts, psx_ransac_result* results,
+                             void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_similarity_many(int device, const void* host_pairs, const int* set_counts, int n_sets,
+                         const float* d_left_xy, int l_len, const float* const* d_right_xys, const int* r_lens,
+                         const psx_ransac_opts* opts, psx_ransac_result* results,
+                         void* host_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_similarity_many_dev(int device, const void* d_pairs, const int* set_counts, int n_sets,
+                             const float* d_left_xy, int l_len, const float* const* d_right_xys, const int* r_lens,
+                             const psx_ransac_opts* opts, psx_ransac_result* results,
+                             void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
 /* Host only, no device and no context: the loop over the single-list rule on host arrays (right_xys: n_sets HOST pointers),
  * with the same argument checks; every pair index of every set is checked before anything is written. */
 int psx_ransac_homography_many_ref(const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
@@ -648,11 +704,17 @@ int psx_ransac_homography_many_ref(const void* pairs, const int* set_counts, int
 int psx_ransac_fundamental_many_ref(const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
                                     const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts,
                                     psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts);
+int psx_ransac_affine_many_ref(const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
+                             const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                             psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts);
+int psx_ransac_similarity_many_ref(const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
+                             const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                             psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts);
 
 /* From the K results of psx_ransac_*_many* to the K guides of psx_match_pairs_guided_many_u8*, on the HOST: no device, no
  * context.  guides[k] = { results[k].best < 0 ? PSX_GUIDE_NONE : kind, results[k].m, tol }: a set without a model is
  * skipped by the re-match instead of being matched under its zero matrix.  kind: PSX_GUIDE_HOMOGRAPHY for the results of
- * psx_ransac_homography_many*, PSX_GUIDE_EPIPOLAR for those of psx_ransac_fundamental_many*.  PSX_ERR_INVALID, with
+ * psx_ransac_homography_many*, psx_ransac_affine_many* and psx_ransac_similarity_many*, PSX_GUIDE_EPIPOLAR for those of psx_ransac_fundamental_many*.  PSX_ERR_INVALID, with
  * nothing written: n_sets < 0, a NULL array with n_sets > 0, a kind other than 1 or 2, a tol that is not finite and >= 0. */
 int psx_guides_from_ransac(const psx_ransac_result* results, int n_sets, int kind, float tol, psx_guide* guides);
 

@@ -106,6 +106,10 @@ SYMBOLS = [
     "psx_ransac_samples_k", "psx_fundamental_fit", "psx_ransac_fundamental_ref", "psx_ransac_fundamental", "psx_ransac_fundamental_dev",
     "psx_ransac_homography_many", "psx_ransac_homography_many_dev", "psx_ransac_homography_many_ref",
     "psx_ransac_fundamental_many", "psx_ransac_fundamental_many_dev", "psx_ransac_fundamental_many_ref", "psx_ransac_many_plan",
+    "psx_affine_fit", "psx_ransac_affine_ref", "psx_ransac_affine", "psx_ransac_affine_dev",
+    "psx_similarity_fit", "psx_ransac_similarity_ref", "psx_ransac_similarity", "psx_ransac_similarity_dev",
+    "psx_ransac_affine_many", "psx_ransac_affine_many_dev", "psx_ransac_affine_many_ref",
+    "psx_ransac_similarity_many", "psx_ransac_similarity_many_dev", "psx_ransac_similarity_many_ref",
 ]
 
 PAIRS_MUTUAL = 1     # PSX_PAIRS_MUTUAL
@@ -257,15 +261,17 @@ def lib():
         L.psx_ransac_samples.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_int, vp]
         L.psx_homography_fit.argtypes = [vp, vp, C.c_int, vp]
         L.psx_ransac_samples_k.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-        L.psx_fundamental_fit.argtypes = [vp, vp, C.c_int, vp]
-        L.psx_ransac_fundamental_ref.argtypes = L.psx_ransac_homography_ref.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(RansacOpts), C.POINTER(RansacResult),
+        L.psx_fundamental_fit.argtypes = L.psx_affine_fit.argtypes = L.psx_similarity_fit.argtypes = [vp, vp, C.c_int, vp]
+        L.psx_ransac_affine_ref.argtypes = L.psx_ransac_similarity_ref.argtypes = L.psx_ransac_fundamental_ref.argtypes = L.psx_ransac_homography_ref.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(RansacOpts), C.POINTER(RansacResult),
                                                 vp, C.c_int, ip, vp, vp]
-        for n in ("psx_ransac_homography", "psx_ransac_homography_dev", "psx_ransac_fundamental", "psx_ransac_fundamental_dev"):
+        for n in ("psx_ransac_homography", "psx_ransac_homography_dev", "psx_ransac_fundamental", "psx_ransac_fundamental_dev",
+                  "psx_ransac_affine", "psx_ransac_affine_dev", "psx_ransac_similarity", "psx_ransac_similarity_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(RansacOpts), C.POINTER(RansacResult),
                                       vp, C.c_int, ip, vp, vp]
-        for n in ("psx_ransac_homography_many", "psx_ransac_homography_many_dev", "psx_ransac_fundamental_many", "psx_ransac_fundamental_many_dev"):
+        for n in ("psx_ransac_homography_many", "psx_ransac_homography_many_dev", "psx_ransac_fundamental_many", "psx_ransac_fundamental_many_dev",
+                  "psx_ransac_affine_many", "psx_ransac_affine_many_dev", "psx_ransac_similarity_many", "psx_ransac_similarity_many_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(RansacOpts), vp, vp, C.c_int, ip, vp, vp]
-        for n in ("psx_ransac_homography_many_ref", "psx_ransac_fundamental_many_ref"):
+        for n in ("psx_ransac_homography_many_ref", "psx_ransac_fundamental_many_ref", "psx_ransac_affine_many_ref", "psx_ransac_similarity_many_ref"):
             getattr(L, n).argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(RansacOpts), vp, vp, C.c_int, ip, vp, vp]
         L.psx_ransac_many_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, ip]
         _LIB = L
@@ -786,7 +792,8 @@ def ransac_opts(tol=2.0, hypotheses=1024, seed=0, refit=True):
 
 
 def ransac_samples(seed, first, count, n, k=4):
-    """psx_ransac_samples (k = 4, the homography's) / psx_ransac_samples_k (any other k; the fundamental matrix draws 8): the
+    """psx_ransac_samples (k = 4, the homography's) / psx_ransac_samples_k (any other k; the fundamental matrix draws 8, the
+    affine transform 3, the similarity 2): the
     (count, k) int32 pair indices of hypotheses first .. first + count - 1 among n pairs.  No device."""
     out = np.zeros((count, max(int(k), 0)), np.int32)
     po = out.ctypes.data_as(C.c_void_p) if out.size else None
@@ -825,6 +832,28 @@ def fundamental_fit(left_xy, right_xy):
     return m
 
 
+def _fit_xy(name, left_xy, right_xy):
+    lx, rx = _xy(left_xy), _xy(right_xy)
+    if len(lx) != len(rx):
+        raise ValueError("one right position per left position")
+    m = np.zeros(9, np.float32)
+    rc = getattr(lib(), name)(lx.ctypes.data_as(C.c_void_p), rx.ctypes.data_as(C.c_void_p), len(lx), m.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    return m
+
+
+def affine_fit(left_xy, right_xy):
+    """psx_affine_fit: the 9 float32 entries (row major, last row exactly 0 0 1) of the 2-D affine transform fitted to n >= 3
+    correspondences left_xy[i] -> right_xy[i], in the given order.  No device."""
+    return _fit_xy("psx_affine_fit", left_xy, right_xy)
+
+
+def similarity_fit(left_xy, right_xy):
+    """psx_similarity_fit: as affine_fit for a similarity (rotation, uniform scale, translation) and n >= 2.  No device."""
+    return _fit_xy("psx_similarity_fit", left_xy, right_xy)
+
+
 def _pair_records(pairs):
     """16-byte pair records (PAIR_DTYPE or PAIR_U8_DTYPE), C-contiguous"""
     pairs = np.ascontiguousarray(pairs).reshape(-1)
@@ -857,8 +886,10 @@ def _ransac_call(fn, name, pairs_ptr, n, dtype, plx, nl, prx, nr, opts, capacity
 
 
 def _ransac_names(model):
-    """(C name stem, guide kind) of the model "homography" or "fundamental" that a ransac_* wrapper estimates"""
-    return "psx_ransac_" + model, {"homography": GUIDE_HOMOGRAPHY, "fundamental": GUIDE_EPIPOLAR}[model]
+    """(C name stem, guide kind) of the model "homography", "fundamental", "affine" or "similarity" that a ransac_* wrapper
+    estimates"""
+    return "psx_ransac_" + model, {"homography": GUIDE_HOMOGRAPHY, "fundamental": GUIDE_EPIPOLAR, "affine": GUIDE_HOMOGRAPHY,
+                                   "similarity": GUIDE_HOMOGRAPHY}[model]
 
 
 def ransac_homography_ref(pairs, left_xy, right_xy, opts=None, capacity=None, layers=False, model="homography"):
@@ -1030,6 +1061,72 @@ def ransac_fundamental_many_dev(pairs_ptr, set_counts, left_xy_ptr, l_len, right
                                       layers, model="fundamental")
 
 
+def ransac_affine_ref(pairs, left_xy, right_xy, opts=None, capacity=None, layers=False):
+    """psx_ransac_affine_ref: as ransac_homography_ref for the affine model; result.guide(tol) is a homography Guide"""
+    return ransac_homography_ref(pairs, left_xy, right_xy, opts, capacity, layers, model="affine")
+
+
+def ransac_affine(pairs, left_xy, right_xy, opts=None, device=0, capacity=None, layers=False):
+    """psx_ransac_affine on host arrays: as ransac_affine_ref, on the device"""
+    return ransac_homography(pairs, left_xy, right_xy, opts, device, capacity, layers, model="affine")
+
+
+def ransac_affine_dev(pairs_ptr, n, left_xy_ptr, l_len, right_xy_ptr, r_len, out_ptr, capacity, opts=None, device=0, layers=False):
+    """psx_ransac_affine_dev on DEVICE pointers: as ransac_homography_dev"""
+    return ransac_homography_dev(pairs_ptr, n, left_xy_ptr, l_len, right_xy_ptr, r_len, out_ptr, capacity, opts, device, layers,
+                                 model="affine")
+
+
+def ransac_affine_many_ref(pair_lists, left_xy, right_xys, opts=None, capacity=None, layers=False):
+    """psx_ransac_affine_many_ref: as ransac_homography_many_ref for the affine model"""
+    return ransac_homography_many_ref(pair_lists, left_xy, right_xys, opts, capacity, layers, model="affine")
+
+
+def ransac_affine_many(pair_lists, left_xy, right_xys, opts=None, device=0, capacity=None, layers=False):
+    """psx_ransac_affine_many on host arrays: as ransac_homography_many"""
+    return ransac_homography_many(pair_lists, left_xy, right_xys, opts, device, capacity, layers, model="affine")
+
+
+def ransac_affine_many_dev(pairs_ptr, set_counts, left_xy_ptr, l_len, right_xy_ptrs, r_lens, out_ptr, capacity, opts=None, device=0,
+                          layers=False):
+    """psx_ransac_affine_many_dev on DEVICE pointers: as ransac_homography_many_dev"""
+    return ransac_homography_many_dev(pairs_ptr, set_counts, left_xy_ptr, l_len, right_xy_ptrs, r_lens, out_ptr, capacity, opts, device,
+                                      layers, model="affine")
+
+
+def ransac_similarity_ref(pairs, left_xy, right_xy, opts=None, capacity=None, layers=False):
+    """psx_ransac_similarity_ref: as ransac_homography_ref for the similarity model; result.guide(tol) is a homography Guide"""
+    return ransac_homography_ref(pairs, left_xy, right_xy, opts, capacity, layers, model="similarity")
+
+
+def ransac_similarity(pairs, left_xy, right_xy, opts=None, device=0, capacity=None, layers=False):
+    """psx_ransac_similarity on host arrays: as ransac_similarity_ref, on the device"""
+    return ransac_homography(pairs, left_xy, right_xy, opts, device, capacity, layers, model="similarity")
+
+
+def ransac_similarity_dev(pairs_ptr, n, left_xy_ptr, l_len, right_xy_ptr, r_len, out_ptr, capacity, opts=None, device=0, layers=False):
+    """psx_ransac_similarity_dev on DEVICE pointers: as ransac_homography_dev"""
+    return ransac_homography_dev(pairs_ptr, n, left_xy_ptr, l_len, right_xy_ptr, r_len, out_ptr, capacity, opts, device, layers,
+                                 model="similarity")
+
+
+def ransac_similarity_many_ref(pair_lists, left_xy, right_xys, opts=None, capacity=None, layers=False):
+    """psx_ransac_similarity_many_ref: as ransac_homography_many_ref for the similarity model"""
+    return ransac_homography_many_ref(pair_lists, left_xy, right_xys, opts, capacity, layers, model="similarity")
+
+
+def ransac_similarity_many(pair_lists, left_xy, right_xys, opts=None, device=0, capacity=None, layers=False):
+    """psx_ransac_similarity_many on host arrays: as ransac_homography_many"""
+    return ransac_homography_many(pair_lists, left_xy, right_xys, opts, device, capacity, layers, model="similarity")
+
+
+def ransac_similarity_many_dev(pairs_ptr, set_counts, left_xy_ptr, l_len, right_xy_ptrs, r_lens, out_ptr, capacity, opts=None, device=0,
+                          layers=False):
+    """psx_ransac_similarity_many_dev on DEVICE pointers: as ransac_homography_many_dev"""
+    return ransac_homography_many_dev(pairs_ptr, set_counts, left_xy_ptr, l_len, right_xy_ptrs, r_lens, out_ptr, capacity, opts, device,
+                                      layers, model="similarity")
+
+
 def ransac_many_plan(set_counts, min_pairs, block_rows):
     """psx_ransac_many_plan: the (n, 3) int32 blocks = set, first, end of the concatenated list.  No device."""
     L = lib()
@@ -1112,6 +1209,14 @@ class DeviceDescriptors:
     def ransac_fundamental(self, right, pairs, opts=None, capacity=None, layers=False):
         """psx_ransac_fundamental(pairs of self as left and right): the dict of capi.ransac_fundamental"""
         return self.ransac_homography(right, pairs, opts, capacity, layers, model="fundamental")
+
+    def ransac_affine(self, right, pairs, opts=None, capacity=None, layers=False):
+        """psx_ransac_affine(pairs of self as left and right): the dict of capi.ransac_affine"""
+        return self.ransac_homography(right, pairs, opts, capacity, layers, model="affine")
+
+    def ransac_similarity(self, right, pairs, opts=None, capacity=None, layers=False):
+        """psx_ransac_similarity(pairs of self as left and right): the dict of capi.ransac_similarity"""
+        return self.ransac_homography(right, pairs, opts, capacity, layers, model="similarity")
 
     def close(self):
         if self.ptr:

@@ -1,15 +1,17 @@
-// ransac.hip -- geometric verification: a homography or a fundamental matrix from matched pairs by RANSAC on the device
-// (psx_ransac_homography*, psx_ransac_samples, psx_homography_fit, psx_ransac_homography_ref; psx_ransac_fundamental*,
-// psx_ransac_samples_k, psx_fundamental_fit, psx_ransac_fundamental_ref; include/popsift_hip.h).
+// ransac.hip -- geometric verification: a homography, a fundamental matrix, a 2-D affine transform or a similarity from
+// matched pairs by RANSAC on the device (psx_ransac_homography*, psx_ransac_samples, psx_homography_fit,
+// psx_ransac_homography_ref; psx_ransac_fundamental*, psx_ransac_samples_k, psx_fundamental_fit,
+// psx_ransac_fundamental_ref; psx_ransac_affine*, psx_affine_fit, psx_ransac_similarity*, psx_similarity_fit;
+// include/popsift_hip.h).
 //
-// The rule -- samples, fit, score, select, refit, inliers -- is ransac_rule.h (homography) and fundamental_rule.h
-// (fundamental matrix), shared with the host references; the steps of the estimator around them are ransac_core.h, shared
+// The rule -- samples, fit, score, select, refit, inliers -- is ransac_rule.h (homography), fundamental_rule.h
+// (fundamental matrix) and affine_rule.h (affine, similarity), shared with the host references; the steps of the estimator around them are ransac_core.h, shared
 // with the batched call (ransac_many.hip).  This file is the call for ONE pair list: kernels that say where a step's
-// operands live, and the sequence.  Kernels that evaluate the rule are templates on the model kind (RModel).
+// operands live, and the sequence.  Kernels that evaluate the rule are templates on the model id (RModel).
 //   k_ransac_gather  r_gather per pair: the four floats, once, into a packed float4 array; everything after it streams 16 B
 //                    per lane, coalesced
-//   k_ransac_hyp     one lane per hypothesis: r_sample_fit (four indices and the 4-point fit, or eight and the pivoted
-//                    8-point fit, in registers); writes the model, clears the count
+//   k_ransac_hyp     one lane per hypothesis: r_sample_fit (four indices and the 4-point fit, eight and the pivoted
+//                    8-point fit, or two / three and the similarity / affine fit, in registers); writes the model, clears the count
 //   k_ransac_score   the hot kernel, N x n rule evaluations.  Lanes own pairs: R_PPL float4, strided over the workgroup,
 //                    stay in VGPRs; r_score_walk over a block of R_HB hypotheses with the strides 9 and 1 as literals
 //   k_ransac_select  r_select by a single workgroup
@@ -210,7 +212,7 @@ int ransac_run(int device, const void* host_pairs, const void* d_pairs_in, int n
     return PSX_OK;
 }
 
-// psx_homography_fit / psx_fundamental_fit: the xy arrays packed into correspondences, then the kind's serial fit
+// psx_*_fit: the xy arrays packed into correspondences, then the model's serial fit
 template <int KIND>
 int fit_xy(const float* left_xy, const float* right_xy, int n, float* m)
 {
@@ -226,15 +228,14 @@ int fit_xy(const float* left_xy, const float* right_xy, int n, float* m)
     return PSX_OK;
 }
 
-// psx_ransac_*_ref: the kind's host rule on a scratch of n correspondences
+// psx_ransac_*_ref: the model's host rule on a scratch of n correspondences
 template <int KIND>
 int ransac_ref(const void* pairs, int n, const float* left_xy, int nl, const float* right_xy, int nr, const psx_ransac_opts* opts,
                psx_ransac_result* result, void* inliers, int capacity, int* count, float* models, int* counts)
 {
     psx_ransac_pt* scratch = n >= RModel<KIND>::MIN ? new (std::nothrow) psx_ransac_pt[(size_t)n] : nullptr;
     if (n >= RModel<KIND>::MIN && !scratch) return PSX_ERR_NOMEM;
-    const auto rule = KIND == PSX_GUIDE_EPIPOLAR ? psx_ransac_fundamental_host : psx_ransac_homography_host;
-    const int rc = rule(pairs, n, left_xy, nl, right_xy, nr, opts, result, inliers, capacity, count, models, counts, scratch);
+    const int rc = psx_ransac_host_rule(KIND)(pairs, n, left_xy, nl, right_xy, nr, opts, result, inliers, capacity, count, models, counts, scratch);
     delete[] scratch;
     return rc;
 }
@@ -257,21 +258,21 @@ extern "C" int psx_ransac_samples(unsigned seed, int first, int count, int n, in
 
 extern "C" int psx_homography_fit(const float* left_xy, const float* right_xy, int n, float* m)
 {
-    return fit_xy<PSX_GUIDE_HOMOGRAPHY>(left_xy, right_xy, n, m);
+    return fit_xy<PSX_RANSAC_MODEL_HOMOGRAPHY>(left_xy, right_xy, n, m);
 }
 
 extern "C" int psx_ransac_homography_ref(const void* pairs, int n, const float* left_xy, int nl, const float* right_xy, int nr,
                                          const psx_ransac_opts* opts, psx_ransac_result* result, void* inliers, int capacity, int* count,
                                          float* models, int* counts)
 {
-    return ransac_ref<PSX_GUIDE_HOMOGRAPHY>(pairs, n, left_xy, nl, right_xy, nr, opts, result, inliers, capacity, count, models, counts);
+    return ransac_ref<PSX_RANSAC_MODEL_HOMOGRAPHY>(pairs, n, left_xy, nl, right_xy, nr, opts, result, inliers, capacity, count, models, counts);
 }
 
 extern "C" int psx_ransac_homography(int device, const void* host_pairs, int n, const float* d_left_xy, int l_len,
                                      const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
                                      void* host_inliers, int capacity, int* count, float* host_models, int* host_counts)
 {
-    return ransac_run<PSX_GUIDE_HOMOGRAPHY>(device, host_pairs, nullptr, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, host_inliers, nullptr, capacity, count,
+    return ransac_run<PSX_RANSAC_MODEL_HOMOGRAPHY>(device, host_pairs, nullptr, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, host_inliers, nullptr, capacity, count,
                       host_models, host_counts);
 }
 
@@ -279,16 +280,18 @@ extern "C" int psx_ransac_homography_dev(int device, const void* d_pairs, int n,
                                          const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
                                          void* d_inliers, int capacity, int* count, float* host_models, int* host_counts)
 {
-    return ransac_run<PSX_GUIDE_HOMOGRAPHY>(device, nullptr, d_pairs, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, nullptr, d_inliers, capacity, count,
+    return ransac_run<PSX_RANSAC_MODEL_HOMOGRAPHY>(device, nullptr, d_pairs, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, nullptr, d_inliers, capacity, count,
                       host_models, host_counts);
 }
 
 extern "C" int psx_ransac_samples_k(unsigned seed, int first, int count, int n, int k, int* idx)
 {
-    if ((k != 4 && k != PSX_FUND_MIN) || n < k || first < 0 || count < 0 || first > PSX_RANSAC_MAX_HYPOTHESES - count || (count > 0 && !idx))
+    if ((k != PSX_SIMILARITY_MIN && k != PSX_AFFINE_MIN && k != 4 && k != PSX_FUND_MIN) || n < k || first < 0 || count < 0 || first > PSX_RANSAC_MAX_HYPOTHESES - count || (count > 0 && !idx))
         return PSX_ERR_INVALID;
     for (int i = 0; i < count; i++) {
-        if (k == 4) psx_ransac_sample_k<4>(seed, first + i, n, idx + 4 * (size_t)i);
+        if (k == PSX_SIMILARITY_MIN) psx_ransac_sample_k<PSX_SIMILARITY_MIN>(seed, first + i, n, idx + PSX_SIMILARITY_MIN * (size_t)i);
+        else if (k == PSX_AFFINE_MIN) psx_ransac_sample_k<PSX_AFFINE_MIN>(seed, first + i, n, idx + PSX_AFFINE_MIN * (size_t)i);
+        else if (k == 4) psx_ransac_sample_k<4>(seed, first + i, n, idx + 4 * (size_t)i);
         else psx_ransac_sample_k<PSX_FUND_MIN>(seed, first + i, n, idx + PSX_FUND_MIN * (size_t)i);
     }
     return PSX_OK;
@@ -296,21 +299,21 @@ extern "C" int psx_ransac_samples_k(unsigned seed, int first, int count, int n, 
 
 extern "C" int psx_fundamental_fit(const float* left_xy, const float* right_xy, int n, float* m)
 {
-    return fit_xy<PSX_GUIDE_EPIPOLAR>(left_xy, right_xy, n, m);
+    return fit_xy<PSX_RANSAC_MODEL_FUNDAMENTAL>(left_xy, right_xy, n, m);
 }
 
 extern "C" int psx_ransac_fundamental_ref(const void* pairs, int n, const float* left_xy, int nl, const float* right_xy, int nr,
                                           const psx_ransac_opts* opts, psx_ransac_result* result, void* inliers, int capacity, int* count,
                                           float* models, int* counts)
 {
-    return ransac_ref<PSX_GUIDE_EPIPOLAR>(pairs, n, left_xy, nl, right_xy, nr, opts, result, inliers, capacity, count, models, counts);
+    return ransac_ref<PSX_RANSAC_MODEL_FUNDAMENTAL>(pairs, n, left_xy, nl, right_xy, nr, opts, result, inliers, capacity, count, models, counts);
 }
 
 extern "C" int psx_ransac_fundamental(int device, const void* host_pairs, int n, const float* d_left_xy, int l_len,
                                       const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
                                       void* host_inliers, int capacity, int* count, float* host_models, int* host_counts)
 {
-    return ransac_run<PSX_GUIDE_EPIPOLAR>(device, host_pairs, nullptr, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, host_inliers, nullptr,
+    return ransac_run<PSX_RANSAC_MODEL_FUNDAMENTAL>(device, host_pairs, nullptr, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, host_inliers, nullptr,
                                           capacity, count, host_models, host_counts);
 }
 
@@ -318,6 +321,62 @@ extern "C" int psx_ransac_fundamental_dev(int device, const void* d_pairs, int n
                                           const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
                                           void* d_inliers, int capacity, int* count, float* host_models, int* host_counts)
 {
-    return ransac_run<PSX_GUIDE_EPIPOLAR>(device, nullptr, d_pairs, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, nullptr, d_inliers,
+    return ransac_run<PSX_RANSAC_MODEL_FUNDAMENTAL>(device, nullptr, d_pairs, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, nullptr, d_inliers,
                                           capacity, count, host_models, host_counts);
+}
+
+extern "C" int psx_affine_fit(const float* left_xy, const float* right_xy, int n, float* m)
+{
+    return fit_xy<PSX_RANSAC_MODEL_AFFINE>(left_xy, right_xy, n, m);
+}
+
+extern "C" int psx_ransac_affine_ref(const void* pairs, int n, const float* left_xy, int nl, const float* right_xy, int nr,
+                                   const psx_ransac_opts* opts, psx_ransac_result* result, void* inliers, int capacity, int* count,
+                                   float* models, int* counts)
+{
+    return ransac_ref<PSX_RANSAC_MODEL_AFFINE>(pairs, n, left_xy, nl, right_xy, nr, opts, result, inliers, capacity, count, models, counts);
+}
+
+extern "C" int psx_ransac_affine(int device, const void* host_pairs, int n, const float* d_left_xy, int l_len,
+                               const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                               void* host_inliers, int capacity, int* count, float* host_models, int* host_counts)
+{
+    return ransac_run<PSX_RANSAC_MODEL_AFFINE>(device, host_pairs, nullptr, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, host_inliers, nullptr,
+                          capacity, count, host_models, host_counts);
+}
+
+extern "C" int psx_ransac_affine_dev(int device, const void* d_pairs, int n, const float* d_left_xy, int l_len,
+                                   const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                                   void* d_inliers, int capacity, int* count, float* host_models, int* host_counts)
+{
+    return ransac_run<PSX_RANSAC_MODEL_AFFINE>(device, nullptr, d_pairs, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, nullptr, d_inliers,
+                          capacity, count, host_models, host_counts);
+}
+
+extern "C" int psx_similarity_fit(const float* left_xy, const float* right_xy, int n, float* m)
+{
+    return fit_xy<PSX_RANSAC_MODEL_SIMILARITY>(left_xy, right_xy, n, m);
+}
+
+extern "C" int psx_ransac_similarity_ref(const void* pairs, int n, const float* left_xy, int nl, const float* right_xy, int nr,
+                                   const psx_ransac_opts* opts, psx_ransac_result* result, void* inliers, int capacity, int* count,
+                                   float* models, int* counts)
+{
+    return ransac_ref<PSX_RANSAC_MODEL_SIMILARITY>(pairs, n, left_xy, nl, right_xy, nr, opts, result, inliers, capacity, count, models, counts);
+}
+
+extern "C" int psx_ransac_similarity(int device, const void* host_pairs, int n, const float* d_left_xy, int l_len,
+                               const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                               void* host_inliers, int capacity, int* count, float* host_models, int* host_counts)
+{
+    return ransac_run<PSX_RANSAC_MODEL_SIMILARITY>(device, host_pairs, nullptr, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, host_inliers, nullptr,
+                          capacity, count, host_models, host_counts);
+}
+
+extern "C" int psx_ransac_similarity_dev(int device, const void* d_pairs, int n, const float* d_left_xy, int l_len,
+                                   const float* d_right_xy, int r_len, const psx_ransac_opts* opts, psx_ransac_result* result,
+                                   void* d_inliers, int capacity, int* count, float* host_models, int* host_counts)
+{
+    return ransac_run<PSX_RANSAC_MODEL_SIMILARITY>(device, nullptr, d_pairs, n, d_left_xy, l_len, d_right_xy, r_len, opts, result, nullptr, d_inliers,
+                          capacity, count, host_models, host_counts);
 }

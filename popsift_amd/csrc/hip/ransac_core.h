@@ -4,28 +4,51 @@
 // (r_score_walk), the workgroup arg-max (r_select), the keep test (r_keep), the refit decision (r_decide) -- and the host
 // steps that both call sequences take (r_pinned_dev, r_stage_end, r_refit_model, r_download_layers, r_result).  The
 // kernels only say where their operands live; the sequences and the argument checks stay in the two files.  The rule
-// itself is ransac_rule.h and fundamental_rule.h.  Internal to the HIP library.
+// itself is ransac_rule.h, fundamental_rule.h and affine_rule.h.  Internal to the HIP library.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
-#include "fundamental_rule.h"
+#include "affine_rule.h"
 #include "match_scratch.h"
 
-// What differs between the two estimators, by the kind of guide the model is (PSX_GUIDE_HOMOGRAPHY: ransac_rule.h;
-// PSX_GUIDE_EPIPOLAR: fundamental_rule.h): the sample size, which models may score, the serial fit of the refit.
-template <int KIND> struct RModel;
-template <> struct RModel<PSX_GUIDE_HOMOGRAPHY> {
+// What differs between the estimators, by the id of the model (PSX_RANSAC_MODEL_HOMOGRAPHY: ransac_rule.h; _FUNDAMENTAL:
+// fundamental_rule.h; _AFFINE and _SIMILARITY: affine_rule.h; the first two ids are their guide kinds): the kind of guide
+// the model is, the sample size, which models may score, the serial fit of the refit and the fixed-size fit of a sample.
+template <int KIND> struct RModel;      // KIND: the model id
+template <> struct RModel<PSX_RANSAC_MODEL_HOMOGRAPHY> {
+    static constexpr int GUIDE = PSX_GUIDE_HOMOGRAPHY;
     static constexpr int MIN = 4;
     static __host__ __device__ __forceinline__ bool usable(const float* m) { return psx_ransac_model_finite(m); }
     static void fit(const psx_ransac_pt* pt, int n, float* m) { psx_homography_fit_rule<0>(pt, n, m); }
+    static __device__ __forceinline__ void sample(unsigned seed, int h, int n, int* idx) { psx_ransac_sample(seed, h, n, idx); }
+    static __device__ __forceinline__ void fit_sample(const psx_ransac_pt* q, float* m) { psx_homography_fit_rule<4>(q, 4, m); }
 };
-template <> struct RModel<PSX_GUIDE_EPIPOLAR> {
+template <> struct RModel<PSX_RANSAC_MODEL_FUNDAMENTAL> {
+    static constexpr int GUIDE = PSX_GUIDE_EPIPOLAR;
     static constexpr int MIN = PSX_FUND_MIN;
     static __host__ __device__ __forceinline__ bool usable(const float* m) { return psx_fund_model_usable(m); }
     static void fit(const psx_ransac_pt* pt, int n, float* m) { psx_fundamental_fit_rule<0>(pt, n, m); }
+    static __device__ __forceinline__ void sample(unsigned seed, int h, int n, int* idx) { psx_ransac_sample_k<PSX_FUND_MIN>(seed, h, n, idx); }
+    static __device__ __forceinline__ void fit_sample(const psx_ransac_pt* q, float* m) { psx_fundamental_fit_rule<PSX_FUND_MIN>(q, PSX_FUND_MIN, m); }
+};
+template <> struct RModel<PSX_RANSAC_MODEL_AFFINE> {
+    static constexpr int GUIDE = PSX_GUIDE_HOMOGRAPHY;
+    static constexpr int MIN = PSX_AFFINE_MIN;
+    static __host__ __device__ __forceinline__ bool usable(const float* m) { return psx_ransac_model_finite(m); }
+    static void fit(const psx_ransac_pt* pt, int n, float* m) { psx_affine_fit_rule<0>(pt, n, m); }
+    static __device__ __forceinline__ void sample(unsigned seed, int h, int n, int* idx) { psx_ransac_sample_k<PSX_AFFINE_MIN>(seed, h, n, idx); }
+    static __device__ __forceinline__ void fit_sample(const psx_ransac_pt* q, float* m) { psx_affine_fit_rule<PSX_AFFINE_MIN>(q, PSX_AFFINE_MIN, m); }
+};
+template <> struct RModel<PSX_RANSAC_MODEL_SIMILARITY> {
+    static constexpr int GUIDE = PSX_GUIDE_HOMOGRAPHY;
+    static constexpr int MIN = PSX_SIMILARITY_MIN;
+    static __host__ __device__ __forceinline__ bool usable(const float* m) { return psx_ransac_model_finite(m); }
+    static void fit(const psx_ransac_pt* pt, int n, float* m) { psx_similarity_fit_rule<0>(pt, n, m); }
+    static __device__ __forceinline__ void sample(unsigned seed, int h, int n, int* idx) { psx_ransac_sample_k<PSX_SIMILARITY_MIN>(seed, h, n, idx); }
+    static __device__ __forceinline__ void fit_sample(const psx_ransac_pt* q, float* m) { psx_similarity_fit_rule<PSX_SIMILARITY_MIN>(q, PSX_SIMILARITY_MIN, m); }
 };
 
 // The state of a call on the device: RHead, K x RState (the single call: K = 1), then from a 16-byte boundary K x RRefit.
@@ -71,13 +94,11 @@ __device__ __forceinline__ void r_sample_fit(const float4* __restrict__ pts, int
 {
     constexpr int S = RModel<KIND>::MIN;
     int idx[S];
-    if constexpr (KIND == PSX_GUIDE_HOMOGRAPHY) psx_ransac_sample(seed, h, n, idx);
-    else psx_ransac_sample_k<PSX_FUND_MIN>(seed, h, n, idx);
+    RModel<KIND>::sample(seed, h, n, idx);
     psx_ransac_pt q[S];
 #pragma unroll
     for (int k = 0; k < S; k++) q[k] = r_pt(pts[idx[k]]);
-    if constexpr (KIND == PSX_GUIDE_HOMOGRAPHY) psx_homography_fit_rule<4>(q, 4, m);
-    else psx_fundamental_fit_rule<PSX_FUND_MIN>(q, PSX_FUND_MIN, m);
+    RModel<KIND>::fit_sample(q, m);
 }
 
 // The score walk of one wave: its lanes hold PPL resident pairs each (q, with in[] false past the list's end).  Per
@@ -89,6 +110,7 @@ template <int KIND, int PPL>
 __device__ __forceinline__ void r_score_walk(const psx_ransac_pt (&q)[PPL], const bool (&in)[PPL], const float* __restrict__ models,
                                              int* __restrict__ counts, size_t row, int mstride, int cstride, int h0, int h1, float tol)
 {
+    constexpr int GUIDE = RModel<KIND>::GUIDE;
     const int lane = threadIdx.x & 63;
     for (int h = h0; h < h1; h++) {
         float m[9];
@@ -98,8 +120,8 @@ __device__ __forceinline__ void r_score_walk(const psx_ransac_pt (&q)[PPL], cons
         int c = 0;
 #pragma unroll
         for (int k = 0; k < PPL; k++) {
-            const psx_guide_line l = psx_guide_left(KIND, m, tol, q[k].xl, q[k].yl);
-            c += __popcll(__ballot(in[k] && psx_guide_right(KIND, l, q[k].xr, q[k].yr)));
+            const psx_guide_line l = psx_guide_left(GUIDE, m, tol, q[k].xl, q[k].yl);
+            c += __popcll(__ballot(in[k] && psx_guide_right(GUIDE, l, q[k].xr, q[k].yr)));
         }
         if (lane == 0 && c > 0) atomicAdd(counts + (row + h) * cstride, c);
     }
@@ -136,8 +158,9 @@ __device__ __forceinline__ bool r_keep(const RHead* __restrict__ head, const RSt
 #pragma unroll
     for (int k = 0; k < 9; k++) m[k] = st->kept[k];
     if (head->bad != 0 || !RModel<KIND>::usable(m) || !inside) return false;
+    constexpr int GUIDE = RModel<KIND>::GUIDE;
     const psx_ransac_pt p = r_pt(pts[i]);
-    return psx_guide_right(KIND, psx_guide_left(KIND, m, tol, p.xl, p.yl), p.xr, p.yr);
+    return psx_guide_right(GUIDE, psx_guide_left(GUIDE, m, tol, p.xl, p.yl), p.xr, p.yr);
 }
 
 // set `set` of the state and refit arrays: the refit model replaces the kept one iff it was tried, may score and has not

@@ -1,12 +1,13 @@
 // ransac_many.hip -- geometric verification of many pair lists in one call: psx_ransac_homography_many (+ _dev, _ref),
-// psx_ransac_fundamental_many (+ _dev, _ref), psx_ransac_many_plan (include/popsift_hip.h).
+// psx_ransac_fundamental_many, psx_ransac_affine_many, psx_ransac_similarity_many (+ _dev, _ref each),
+// psx_ransac_many_plan (include/popsift_hip.h).
 //
 // psx_ransac_*_dev (ransac.hip) is a fixed sequence of launches and one or two synchronisations per pair list.  A list
 // has a few hundred to a few thousand pairs: at that size the kernels are nearly empty and the call is launch latency and
 // round trips, paid again for every list.  Here the K lists that psx_match_pairs_many_u8* left behind one another are
 // verified by the SAME sequence, every kernel one grid over all sets, driven by tables in which no block crosses a set
-// boundary (ransac_many_plan.h).  The rule -- samples, fit, score, select, refit, inliers -- is ransac_rule.h and
-// fundamental_rule.h, and every step of the estimator around it is the ONE statement of ransac_core.h that the single call
+// boundary (ransac_many_plan.h).  The rule -- samples, fit, score, select, refit, inliers -- is ransac_rule.h,
+// fundamental_rule.h and affine_rule.h, and every step of the estimator around it is the ONE statement of ransac_core.h that the single call
 // runs too: set k's result is the single call's, bit for bit.  The kernels here say where a step's operands live:
 //   k_rmany_gather  r_gather per pair of every set that has a model to estimate, into ONE packed float4 array indexed as
 //                   the concatenation; set k's right positions through the set table
@@ -341,7 +342,7 @@ int ransac_many_run(int device, const void* host_pairs, const void* d_pairs_in, 
     return PSX_OK;
 }
 
-int many_ref(int kind, const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl, const float* const* right_xys,
+int many_ref(int model, const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl, const float* const* right_xys,
              const int* r_lens, const psx_ransac_opts* opts, psx_ransac_result* results, void* inliers, int capacity, int* count, float* models,
              int* counts)
 {
@@ -350,7 +351,7 @@ int many_ref(int kind, const void* pairs, const int* set_counts, int n_sets, con
         for (int k = 0; k < n_sets; k++) longest = set_counts[k] > longest ? set_counts[k] : longest;
     psx_ransac_pt* scratch = longest > 0 ? new (std::nothrow) psx_ransac_pt[(size_t)longest] : nullptr;
     if (longest > 0 && !scratch) return PSX_ERR_NOMEM;
-    const int rc = psx_ransac_many_host(kind, pairs, set_counts, n_sets, left_xy, nl, right_xys, r_lens, opts, results, inliers, capacity, count,
+    const int rc = psx_ransac_many_host(model, pairs, set_counts, n_sets, left_xy, nl, right_xys, r_lens, opts, results, inliers, capacity, count,
                                         models, counts, scratch);
     delete[] scratch;
     return rc;
@@ -368,14 +369,14 @@ extern "C" int psx_ransac_homography_many_ref(const void* pairs, const int* set_
                                               const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts,
                                               psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts)
 {
-    return many_ref(PSX_GUIDE_HOMOGRAPHY, pairs, set_counts, n_sets, left_xy, nl, right_xys, r_lens, opts, results, inliers, capacity, count, models, counts);
+    return many_ref(PSX_RANSAC_MODEL_HOMOGRAPHY, pairs, set_counts, n_sets, left_xy, nl, right_xys, r_lens, opts, results, inliers, capacity, count, models, counts);
 }
 
 extern "C" int psx_ransac_fundamental_many_ref(const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
                                                const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts,
                                                psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts)
 {
-    return many_ref(PSX_GUIDE_EPIPOLAR, pairs, set_counts, n_sets, left_xy, nl, right_xys, r_lens, opts, results, inliers, capacity, count, models, counts);
+    return many_ref(PSX_RANSAC_MODEL_FUNDAMENTAL, pairs, set_counts, n_sets, left_xy, nl, right_xys, r_lens, opts, results, inliers, capacity, count, models, counts);
 }
 
 extern "C" int psx_ransac_homography_many(int device, const void* host_pairs, const int* set_counts, int n_sets, const float* d_left_xy, int l_len,
@@ -383,7 +384,7 @@ extern "C" int psx_ransac_homography_many(int device, const void* host_pairs, co
                                           psx_ransac_result* results, void* host_inliers, int capacity, int* count, float* host_models,
                                           int* host_counts)
 {
-    return ransac_many_run<PSX_GUIDE_HOMOGRAPHY>(device, host_pairs, nullptr, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
+    return ransac_many_run<PSX_RANSAC_MODEL_HOMOGRAPHY>(device, host_pairs, nullptr, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
                                                  host_inliers, nullptr, capacity, count, host_models, host_counts);
 }
 
@@ -392,7 +393,7 @@ extern "C" int psx_ransac_homography_many_dev(int device, const void* d_pairs, c
                                               psx_ransac_result* results, void* d_inliers, int capacity, int* count, float* host_models,
                                               int* host_counts)
 {
-    return ransac_many_run<PSX_GUIDE_HOMOGRAPHY>(device, nullptr, d_pairs, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
+    return ransac_many_run<PSX_RANSAC_MODEL_HOMOGRAPHY>(device, nullptr, d_pairs, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
                                                  nullptr, d_inliers, capacity, count, host_models, host_counts);
 }
 
@@ -401,7 +402,7 @@ extern "C" int psx_ransac_fundamental_many(int device, const void* host_pairs, c
                                            psx_ransac_result* results, void* host_inliers, int capacity, int* count, float* host_models,
                                            int* host_counts)
 {
-    return ransac_many_run<PSX_GUIDE_EPIPOLAR>(device, host_pairs, nullptr, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
+    return ransac_many_run<PSX_RANSAC_MODEL_FUNDAMENTAL>(device, host_pairs, nullptr, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
                                                host_inliers, nullptr, capacity, count, host_models, host_counts);
 }
 
@@ -410,6 +411,56 @@ extern "C" int psx_ransac_fundamental_many_dev(int device, const void* d_pairs, 
                                                psx_ransac_result* results, void* d_inliers, int capacity, int* count, float* host_models,
                                                int* host_counts)
 {
-    return ransac_many_run<PSX_GUIDE_EPIPOLAR>(device, nullptr, d_pairs, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
+    return ransac_many_run<PSX_RANSAC_MODEL_FUNDAMENTAL>(device, nullptr, d_pairs, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
                                                nullptr, d_inliers, capacity, count, host_models, host_counts);
+}
+
+extern "C" int psx_ransac_affine_many_ref(const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
+                                        const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                        psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts)
+{
+    return many_ref(PSX_RANSAC_MODEL_AFFINE, pairs, set_counts, n_sets, left_xy, nl, right_xys, r_lens, opts, results, inliers, capacity, count, models, counts);
+}
+
+extern "C" int psx_ransac_affine_many(int device, const void* host_pairs, const int* set_counts, int n_sets, const float* d_left_xy, int l_len,
+                                    const float* const* d_right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                    psx_ransac_result* results, void* host_inliers, int capacity, int* count, float* host_models,
+                                    int* host_counts)
+{
+    return ransac_many_run<PSX_RANSAC_MODEL_AFFINE>(device, host_pairs, nullptr, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
+                               host_inliers, nullptr, capacity, count, host_models, host_counts);
+}
+
+extern "C" int psx_ransac_affine_many_dev(int device, const void* d_pairs, const int* set_counts, int n_sets, const float* d_left_xy, int l_len,
+                                        const float* const* d_right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                        psx_ransac_result* results, void* d_inliers, int capacity, int* count, float* host_models,
+                                        int* host_counts)
+{
+    return ransac_many_run<PSX_RANSAC_MODEL_AFFINE>(device, nullptr, d_pairs, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
+                               nullptr, d_inliers, capacity, count, host_models, host_counts);
+}
+
+extern "C" int psx_ransac_similarity_many_ref(const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
+                                        const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                        psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts)
+{
+    return many_ref(PSX_RANSAC_MODEL_SIMILARITY, pairs, set_counts, n_sets, left_xy, nl, right_xys, r_lens, opts, results, inliers, capacity, count, models, counts);
+}
+
+extern "C" int psx_ransac_similarity_many(int device, const void* host_pairs, const int* set_counts, int n_sets, const float* d_left_xy, int l_len,
+                                    const float* const* d_right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                    psx_ransac_result* results, void* host_inliers, int capacity, int* count, float* host_models,
+                                    int* host_counts)
+{
+    return ransac_many_run<PSX_RANSAC_MODEL_SIMILARITY>(device, host_pairs, nullptr, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
+                               host_inliers, nullptr, capacity, count, host_models, host_counts);
+}
+
+extern "C" int psx_ransac_similarity_many_dev(int device, const void* d_pairs, const int* set_counts, int n_sets, const float* d_left_xy, int l_len,
+                                        const float* const* d_right_xys, const int* r_lens, const psx_ransac_opts* opts,
+                                        psx_ransac_result* results, void* d_inliers, int capacity, int* count, float* host_models,
+                                        int* host_counts)
+{
+    return ransac_many_run<PSX_RANSAC_MODEL_SIMILARITY>(device, nullptr, d_pairs, set_counts, n_sets, d_left_xy, l_len, d_right_xys, r_lens, opts, results,
+                               nullptr, d_inliers, capacity, count, host_models, host_counts);
 }

@@ -8,14 +8,15 @@
 // The input is the concatenation P_0 .. P_{K-1} of K pair lists, set_counts[k] = |P_k|.  It is cut into
 //   blocks {set, first, end}: pairs [first, end) OF THE CONCATENATION, all of one set, end - first <= block_rows
 // A set's blocks are ascending and contiguous in the table and cover it exactly once; nothing spans two sets; a set with
-// fewer than min_pairs pairs (4 for a homography, 8 for a fundamental matrix: it has no model) contributes no block.
+// fewer than min_pairs pairs (4 for a homography, 8 for a fundamental matrix, 3 affine, 2 similarity: it has no model) contributes no block.
 // The library plans twice: at PSX_RANSAC_MANY_SCORE_ROWS for the score kernel, at 256 for the gather and the compaction.
 //
-// The host reference is the loop over the single-list rule (psx_ransac_homography_host, psx_ransac_fundamental_host:
-// ransac_rule.h, fundamental_rule.h), nothing of which is restated here.
+// The host reference is the loop over the single-list rule (psx_ransac_homography_host, psx_ransac_fundamental_host,
+// psx_ransac_affine_host, psx_ransac_similarity_host: ransac_rule.h, fundamental_rule.h, affine_rule.h), nothing of which
+// is restated here.
 #pragma once
 
-#include "fundamental_rule.h"
+#include "affine_rule.h"
 #include "popsift_hip.h"
 
 constexpr int PSX_RANSAC_MANY_SCORE_ROWS = 512;      // pairs per workgroup of the score kernel (256 lanes x 2 resident pairs)
@@ -86,11 +87,9 @@ inline void psx_ransac_many_none(int n_sets, int N, psx_ransac_result* results, 
     *count = 0;
 }
 
-// the single-list host rule of a model kind (PSX_GUIDE_HOMOGRAPHY / PSX_GUIDE_EPIPOLAR) and its sample size
-typedef int (*psx_ransac_host_fn)(const void*, int, const float*, int, const float*, int, const psx_ransac_opts*, psx_ransac_result*, void*, int,
-                                  int*, float*, int*, psx_ransac_pt*);
-inline psx_ransac_host_fn psx_ransac_many_rule(int kind) { return kind == PSX_GUIDE_EPIPOLAR ? psx_ransac_fundamental_host : psx_ransac_homography_host; }
-inline int psx_ransac_many_min(int kind) { return kind == PSX_GUIDE_EPIPOLAR ? PSX_FUND_MIN : 4; }
+// the single-list host rule of a model (its id, affine_rule.h; the first two ids are guide kinds) and its sample size
+inline psx_ransac_host_fn psx_ransac_many_rule(int model) { return psx_ransac_host_rule(model); }
+inline int psx_ransac_many_min(int model) { return psx_ransac_host_min(model); }
 
 // The host reference (psx_ransac_*_many_ref): the loop over the single-list rule.  Two passes: every argument and every
 // pair index of every set is checked before anything is written.  `scratch` holds as many psx_ransac_pt as the longest

@@ -4,8 +4,9 @@
 // (FeaturesDev::matchPairs) instead of the accept / reject lines; --ratio and --mutual refine it; --homography or
 // --fundamental with --guide-tol restrict the search to the pairs a guide admits (FeaturesDev::matchPairsGuided);
 // --verify-homography TOL estimates a homography from the pairs (FeaturesDev::estimateHomography) and writes its inliers,
-// --verify-fundamental TOL a fundamental matrix (FeaturesDev::estimateFundamental); --rematch then writes the list guided
-// by that model instead.
+// --verify-fundamental TOL a fundamental matrix (FeaturesDev::estimateFundamental), --verify-affine TOL a 2-D affine
+// transform (estimateAffine), --verify-similarity TOL a similarity (estimateSimilarity); --rematch then writes the list
+// guided by that model instead.
 #include "options.h"
 #include "pgmread.h"
 
@@ -32,7 +33,15 @@ static bool  have_ratio = false, mutual = false;
 static float pair_ratio = 0.8f;
 static bool  have_h = false, have_f = false, have_tol = false;
 static popsift::MatchGuide guide;
-static bool  have_verify = false, have_verify_f = false, have_ransac_opt = false, rematch = false;
+static bool  have_verify = false, have_ransac_opt = false, rematch = false;
+// the models of --verify-*: option name, the name printed, the model in an error message
+enum { VerifyHomography, VerifyFundamental, VerifyAffine, VerifySimilarity, VerifyModels };
+static const char* const verify_names[VerifyModels][3] = { { "verify-homography", "Homography", "homography" },
+                                                            { "verify-fundamental", "Fundamental", "fundamental matrix" },
+                                                            { "verify-affine", "Affine", "affine transform" },
+                                                            { "verify-similarity", "Similarity", "similarity" } };
+static const char* const verify_list = "'--verify-homography', '--verify-fundamental', '--verify-affine' or '--verify-similarity'";
+static bool  verify_given[VerifyModels] = { false, false, false, false };
 static popsift::RansacOptions ransac;
 
 // "m0,...,m8": nine numbers, row major
@@ -96,18 +105,25 @@ int main( int argc, char** argv )
              [&]( const string& s ) { guide.tol = app::to_float( s ); have_tol = true; } );
     all.add( "verify-homography", 0, true, "Geometric verification: estimate a homography from the pairs by RANSAC with this inlier "
              "tolerance in pixels, print it and write only its inliers (needs --pairs)",
-             [&]( const string& s ) { ransac.tol = app::to_float( s ); have_verify = true; } );
+             [&]( const string& s ) { ransac.tol = app::to_float( s ); verify_given[VerifyHomography] = true; } );
     all.add( "verify-fundamental", 0, true, "Geometric verification: estimate a fundamental matrix from the pairs by RANSAC with this "
              "inlier tolerance in pixels (distance from the epipolar line), print it and write only its inliers (needs --pairs)",
-             [&]( const string& s ) { ransac.tol = app::to_float( s ); have_verify_f = true; } );
+             [&]( const string& s ) { ransac.tol = app::to_float( s ); verify_given[VerifyFundamental] = true; } );
+    all.add( "verify-affine", 0, true, "Geometric verification: estimate a 2-D affine transform (3-point samples) from the pairs by RANSAC "
+             "with this inlier tolerance in pixels, print it and write only its inliers (needs --pairs)",
+             [&]( const string& s ) { ransac.tol = app::to_float( s ); verify_given[VerifyAffine] = true; } );
+    all.add( "verify-similarity", 0, true, "Geometric verification: estimate a similarity -- rotation, uniform scale, translation; 2-point "
+             "samples -- from the pairs by RANSAC with this inlier tolerance in pixels, print it and write only its inliers (needs --pairs)",
+             [&]( const string& s ) { ransac.tol = app::to_float( s ); verify_given[VerifySimilarity] = true; } );
     all.add( "ransac-hypotheses", 0, true, "Geometric verification: the number of hypotheses, 1 to 65536. Default is 1024",
              [&]( const string& s ) { ransac.hypotheses = (int)app::to_float( s ); have_ransac_opt = true; } );
     all.add( "ransac-seed", 0, true, "Geometric verification: the seed of the samples. Default is 0",
              [&]( const string& s ) { ransac.seed = (unsigned)std::strtoul( s.c_str(), nullptr, 10 ); have_ransac_opt = true; } );
     all.flag( "ransac-refit", 0, "Geometric verification: refit the best hypothesis over its inliers", [&]() { ransac.refit = true; have_ransac_opt = true; } );
-    all.flag( "rematch", 0, "After --verify-homography or --verify-fundamental: match again, guided by the estimated model and the "
+    all.flag( "rematch", 0, "After --verify-homography, --verify-fundamental, --verify-affine or --verify-similarity: match again, guided by the estimated model and the "
               "same tolerance, and write that list instead", [&]() { rematch = true; } );
     all.flag( "pgmread-loading", 0, "Use the PGM/PPM loader (the only loader of this build)", []() {} );
+    int verify_model = VerifyHomography;
     try {
         all.parse( argc, argv );
         if( help ) { all.usage( cout ); return EXIT_SUCCESS; }
@@ -120,12 +136,15 @@ int main( int argc, char** argv )
         if( ( have_h || have_f ) && !have_tol ) throw runtime_error( "the options '--homography' and '--fundamental' need '--guide-tol'" );
         if( have_tol && !( guide.tol >= 0.0f && std::isfinite( guide.tol ) ) ) throw runtime_error( "the guide tolerance must be finite and not negative" );
         guide.kind = have_f ? popsift::MatchGuide::Epipolar : popsift::MatchGuide::Homography;
-        if( have_verify && have_verify_f ) throw runtime_error( "the options '--verify-homography' and '--verify-fundamental' cannot be combined" );
-        const string verify_opt = have_verify_f ? "'--verify-fundamental'" : "'--verify-homography'";
-        have_verify = have_verify || have_verify_f;
+        for( int k = 0; k < VerifyModels; k++ ) {
+            if( !verify_given[k] ) continue;
+            if( have_verify ) throw runtime_error( string( "the options '--" ) + verify_names[verify_model][0] + "' and '--" + verify_names[k][0] + "' cannot be combined" );
+            have_verify = true; verify_model = k;
+        }
+        const string verify_opt = string( "'--" ) + verify_names[verify_model][0] + "'";
         if( have_verify && pairs_file.empty() ) throw runtime_error( "the option " + verify_opt + " needs '--pairs'" );
-        if( have_ransac_opt && !have_verify ) throw runtime_error( "the options '--ransac-hypotheses', '--ransac-seed' and '--ransac-refit' need '--verify-homography' or '--verify-fundamental'" );
-        if( rematch && !have_verify ) throw runtime_error( "the option '--rematch' needs '--verify-homography' or '--verify-fundamental'" );
+        if( have_ransac_opt && !have_verify ) throw runtime_error( string( "the options '--ransac-hypotheses', '--ransac-seed' and '--ransac-refit' need " ) + verify_list );
+        if( rematch && !have_verify ) throw runtime_error( string( "the option '--rematch' needs " ) + verify_list );
         if( have_verify && ( have_h || have_f ) ) throw runtime_error( "the option " + verify_opt + " cannot be combined with '--homography' or '--fundamental'" );
         if( have_verify && !( ransac.tol >= 0.0f && std::isfinite( ransac.tol ) ) ) throw runtime_error( "the verification tolerance must be finite and not negative" );
         if( have_verify && ( ransac.hypotheses < 1 || ransac.hypotheses > 65536 ) ) throw runtime_error( "the number of hypotheses must lie in 1 .. 65536" );
@@ -159,14 +178,15 @@ int main( int argc, char** argv )
             std::vector<popsift::Match> mm = ( have_h || have_f ) ? lFeatures->matchPairsGuided( rFeatures, guide, mo )
                                                                   : lFeatures->matchPairs( rFeatures, mo );
             if( have_verify ) {
-                const char* model = have_verify_f ? "Fundamental" : "Homography";
-                const popsift::HomographyEstimate est = have_verify_f ? lFeatures->estimateFundamental( rFeatures, mm, ransac )
-                                                                      : lFeatures->estimateHomography( rFeatures, mm, ransac );
+                const char* model = verify_names[verify_model][1];
+                const popsift::HomographyEstimate est = verify_model == VerifyFundamental ? lFeatures->estimateFundamental( rFeatures, mm, ransac )
+                                                      : verify_model == VerifyAffine      ? lFeatures->estimateAffine( rFeatures, mm, ransac )
+                                                      : verify_model == VerifySimilarity  ? lFeatures->estimateSimilarity( rFeatures, mm, ransac )
+                                                                                          : lFeatures->estimateHomography( rFeatures, mm, ransac );
                 printf( "%s:", model );
                 for( int k = 0; k < 9; k++ ) printf( " %.9g", est.guide.m[k] );
                 printf( "\n%s inliers: %d of %d\n", model, (int)est.inliers.size(), (int)mm.size() );
-                if( est.best < 0 ) throw runtime_error( have_verify_f ? "no fundamental matrix could be estimated from the pairs"
-                                                                      : "no homography could be estimated from the pairs" );
+                if( est.best < 0 ) throw runtime_error( string( "no " ) + verify_names[verify_model][2] + " could be estimated from the pairs" );
                 mm = rematch ? lFeatures->matchPairsGuided( rFeatures, est.guide, mo ) : est.inliers;
             }
             FILE* f = fopen( pairs_file.c_str(), "w" );

@@ -773,15 +773,39 @@ std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedMany( const std::ve
 
 HomographyEstimate FeaturesDev::estimateHomography( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts )
 {
-    return estimate( "FeaturesDev::estimateHomography", false, other, matches, opts );
+    return estimate( "FeaturesDev::estimateHomography", ModelHomography, other, matches, opts );
 }
 
 FundamentalEstimate FeaturesDev::estimateFundamental( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts )
 {
-    return estimate( "FeaturesDev::estimateFundamental", true, other, matches, opts );
+    return estimate( "FeaturesDev::estimateFundamental", ModelFundamental, other, matches, opts );
 }
 
-HomographyEstimate FeaturesDev::estimate( const char* who, bool fundamental, FeaturesDev* other, const std::vector<Match>& matches,
+HomographyEstimate FeaturesDev::estimateAffine( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts )
+{
+    return estimate( "FeaturesDev::estimateAffine", ModelAffine, other, matches, opts );
+}
+
+HomographyEstimate FeaturesDev::estimateSimilarity( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts )
+{
+    return estimate( "FeaturesDev::estimateSimilarity", ModelSimilarity, other, matches, opts );
+}
+
+// what differs between the models of estimate() and estimateMany(), in the order of FeaturesDev::RansacModel
+namespace {
+typedef int (*RansacOneFn)( int, const void*, int, const float*, int, const float*, int, const psx_ransac_opts*, psx_ransac_result*, void*, int, int*,
+                            float*, int* );
+typedef int (*RansacManyFn)( int, const void*, const int*, int, const float*, int, const float* const*, const int*, const psx_ransac_opts*,
+                             psx_ransac_result*, void*, int, int*, float*, int* );
+const struct { int min_pairs; RansacOneFn one; RansacManyFn many; } ransac_models[4] = {
+    { 4, psx_ransac_homography,  psx_ransac_homography_many },
+    { 8, psx_ransac_fundamental, psx_ransac_fundamental_many },
+    { 3, psx_ransac_affine,      psx_ransac_affine_many },
+    { 2, psx_ransac_similarity,  psx_ransac_similarity_many },
+};
+}
+
+HomographyEstimate FeaturesDev::estimate( const char* who, RansacModel model, FeaturesDev* other, const std::vector<Match>& matches,
                                           const RansacOptions& opts )
 {
     if( other == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
@@ -790,17 +814,17 @@ HomographyEstimate FeaturesDev::estimate( const char* who, bool fundamental, Fea
         ss << who << ": the two objects live on different devices (" << _device << " and " << other->_device << ")";
         fatal( __FILE__, __LINE__, ss.str() );
     }
-    // refused here, before any device is touched: what psx_ransac_homography and psx_ransac_fundamental refuse
+    // refused here, before any device is touched: what the psx_ransac_* calls refuse
     if( !( std::isfinite( opts.tol ) && opts.tol >= 0.0f ) || opts.hypotheses < 1 || opts.hypotheses > 65536 )
         fatal( __FILE__, __LINE__, std::string( who ) + ": invalid options (finite tolerance >= 0, 1 to 65536 hypotheses)" );
     HomographyEstimate est;
-    est.guide.kind = fundamental ? MatchGuide::Epipolar : MatchGuide::Homography;
+    est.guide.kind = model == ModelFundamental ? MatchGuide::Epipolar : MatchGuide::Homography;
     for( int k = 0; k < 9; k++ ) est.guide.m[k] = 0.0f;
     est.guide.tol = opts.tol;
     est.best = -1; est.sample_inliers = 0; est.refit_kept = false;
     const int n = (int)matches.size();
     const int l_len = getDescriptorCount(), r_len = other->getDescriptorCount();
-    if( n < ( fundamental ? 8 : 4 ) ) return est;
+    if( n < ransac_models[model].min_pairs ) return est;
     // the record is copied whole: its distance slots carry the index of the match
     std::vector<psx_match_pair_u8> rec( n ), inl( n );
     for( int k = 0; k < n; k++ ) { rec[k].left = matches[k].left_descriptor; rec[k].right = matches[k].right_descriptor; rec[k].d1 = k; rec[k].d2 = 0; }
@@ -814,9 +838,8 @@ HomographyEstimate FeaturesDev::estimate( const char* who, bool fundamental, Fea
     if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)r_len * 2 * sizeof(float), &rxy );
     if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)_ext, _rev, l_len, (float*)lxy );
     if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)other->_ext, other->_rev, r_len, (float*)rxy );
-    if( rc == PSX_OK ) rc = ( fundamental ? psx_ransac_fundamental : psx_ransac_homography )( _device, rec.data(), n, (const float*)lxy, l_len,
-                                                                                              (const float*)rxy, r_len, &po, &res, inl.data(), n,
-                                                                                              &count, nullptr, nullptr );
+    if( rc == PSX_OK ) rc = ransac_models[model].one( _device, rec.data(), n, (const float*)lxy, l_len, (const float*)rxy, r_len, &po, &res,
+                                                      inl.data(), n, &count, nullptr, nullptr );
     psx_dev_free( _device, lxy );
     psx_dev_free( _device, rxy );
     if( rc != PSX_OK ) {
@@ -834,19 +857,31 @@ HomographyEstimate FeaturesDev::estimate( const char* who, bool fundamental, Fea
 std::vector<HomographyEstimate> FeaturesDev::estimateHomographyMany( const std::vector<FeaturesDev*>& others,
                                                                      const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
 {
-    return estimateMany( "FeaturesDev::estimateHomographyMany", false, others, matches, opts );
+    return estimateMany( "FeaturesDev::estimateHomographyMany", ModelHomography, others, matches, opts );
 }
 
 std::vector<FundamentalEstimate> FeaturesDev::estimateFundamentalMany( const std::vector<FeaturesDev*>& others,
                                                                        const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
 {
-    return estimateMany( "FeaturesDev::estimateFundamentalMany", true, others, matches, opts );
+    return estimateMany( "FeaturesDev::estimateFundamentalMany", ModelFundamental, others, matches, opts );
 }
 
-// psx_ransac_homography_many / psx_ransac_fundamental_many on the lists matchPairsMany returned: the lists that can have
+std::vector<HomographyEstimate> FeaturesDev::estimateAffineMany( const std::vector<FeaturesDev*>& others,
+                                                                 const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
+{
+    return estimateMany( "FeaturesDev::estimateAffineMany", ModelAffine, others, matches, opts );
+}
+
+std::vector<HomographyEstimate> FeaturesDev::estimateSimilarityMany( const std::vector<FeaturesDev*>& others,
+                                                                     const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
+{
+    return estimateMany( "FeaturesDev::estimateSimilarityMany", ModelSimilarity, others, matches, opts );
+}
+
+// psx_ransac_homography_many / _fundamental_many / _affine_many / _similarity_many on the lists matchPairsMany returned: the lists that can have
 // a model go behind one another into ONE call (a shorter list is "no model" without a device, as estimate() has it), the
 // left positions are gathered once, every other object's once
-std::vector<HomographyEstimate> FeaturesDev::estimateMany( const char* who, bool fundamental, const std::vector<FeaturesDev*>& others,
+std::vector<HomographyEstimate> FeaturesDev::estimateMany( const char* who, RansacModel model, const std::vector<FeaturesDev*>& others,
                                                            const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
 {
     if( others.size() != matches.size() ) {
@@ -865,9 +900,9 @@ std::vector<HomographyEstimate> FeaturesDev::estimateMany( const char* who, bool
     if( !( std::isfinite( opts.tol ) && opts.tol >= 0.0f ) || opts.hypotheses < 1 || opts.hypotheses > 65536 )
         fatal( __FILE__, __LINE__, std::string( who ) + ": invalid options (finite tolerance >= 0, 1 to 65536 hypotheses)" );
     const int K = (int)others.size();
-    const int min_pairs = fundamental ? 8 : 4;
+    const int min_pairs = ransac_models[model].min_pairs;
     HomographyEstimate none;
-    none.guide.kind = fundamental ? MatchGuide::Epipolar : MatchGuide::Homography;
+    none.guide.kind = model == ModelFundamental ? MatchGuide::Epipolar : MatchGuide::Homography;
     for( int k = 0; k < 9; k++ ) none.guide.m[k] = 0.0f;
     none.guide.tol = opts.tol;
     none.best = -1; none.sample_inliers = 0; none.refit_kept = false;
@@ -904,9 +939,8 @@ std::vector<HomographyEstimate> FeaturesDev::estimateMany( const char* who, bool
         rxys[k] = (const float*)bufs[k];
     }
     if( rc == PSX_OK )
-        rc = ( fundamental ? psx_ransac_fundamental_many : psx_ransac_homography_many )( _device, rec.data(), counts.data(), K, (const float*)bufs[K], l_len,
-                                                                                          rxys.data(), lens.data(), &po, res.data(), inl.data(),
-                                                                                          (int)total, &count, nullptr, nullptr );
+        rc = ransac_models[model].many( _device, rec.data(), counts.data(), K, (const float*)bufs[K], l_len, rxys.data(), lens.data(), &po, res.data(),
+                                        inl.data(), (int)total, &count, nullptr, nullptr );
     for( void* b : bufs ) psx_dev_free( _device, b );
     if( rc != PSX_OK ) {
         std::ostringstream ss;

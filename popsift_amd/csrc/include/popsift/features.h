@@ -149,8 +149,9 @@ struct Match
     float distance, second_distance;            ///< squared; byte distances converted (exact), +inf: no second neighbour
 };
 
-/// How FeaturesDev::estimateHomography and estimateFundamental run: the options of psx_ransac_homography and
-/// psx_ransac_fundamental (include/popsift_hip.h, "geometric verification")
+/// How FeaturesDev::estimateHomography, estimateFundamental, estimateAffine and estimateSimilarity run: the options of
+/// psx_ransac_homography, psx_ransac_fundamental, psx_ransac_affine and psx_ransac_similarity (include/popsift_hip.h,
+/// "geometric verification")
 struct RansacOptions
 {
     float    tol        = 2.0f;   ///< inlier tolerance in pixels, finite and >= 0
@@ -173,6 +174,8 @@ struct HomographyEstimate
 /// What FeaturesDev::estimateFundamental returns: the same fields; guide is Epipolar, the estimated fundamental matrix
 /// (this -> other); the sample has 8 points and best = -1 stands for fewer than 8 matches or no usable model
 typedef HomographyEstimate FundamentalEstimate;
+/// FeaturesDev::estimateAffine and estimateSimilarity return a HomographyEstimate: guide is Homography, a matrix whose last
+/// row is exactly (0, 0, 1); the sample has 3 / 2 points and best = -1 stands for fewer matches than that or no finite model
 
 /// Device-resident result (MatchingMode): arrays live in HBM of the extracting device.
 class FeaturesDev : public FeaturesBase
@@ -182,8 +185,9 @@ class FeaturesDev : public FeaturesBase
     int*         _rev;   // device: descriptor -> extremum
     int          _device;
 
-    HomographyEstimate estimate( const char* who, bool fundamental, FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts );
-    std::vector<HomographyEstimate> estimateMany( const char* who, bool fundamental, const std::vector<FeaturesDev*>& others,
+    enum RansacModel { ModelHomography, ModelFundamental, ModelAffine, ModelSimilarity };   // what estimate() fits
+    HomographyEstimate estimate( const char* who, RansacModel model, FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts );
+    std::vector<HomographyEstimate> estimateMany( const char* who, RansacModel model, const std::vector<FeaturesDev*>& others,
                                                   const std::vector<std::vector<Match>>& matches, const RansacOptions& opts );
 
 public:
@@ -227,6 +231,12 @@ public:
     /// the same for a scene with depth: a fundamental matrix from at least 8 matches, psx_ransac_fundamental; its guide
     /// restricts matchPairsGuided to the epipolar band
     FundamentalEstimate estimateFundamental( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts = RansacOptions() );
+    /// the registration models below a homography, for a scene that is one (video stabilisation, mosaics, a tracker's
+    /// re-initialisation) or a match list too short for four points: a 2-D affine transform from at least 3 matches
+    /// (psx_ransac_affine) and a similarity -- rotation, uniform scale, translation, no reflection -- from at least 2
+    /// (psx_ransac_similarity).  The guide is a Homography whose last row is exactly (0, 0, 1)
+    HomographyEstimate estimateAffine( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts = RansacOptions() );
+    HomographyEstimate estimateSimilarity( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts = RansacOptions() );
     /// estimateHomography against many objects in ONE device call (psx_ransac_homography_many: one or two
     /// synchronisations and a number of launches that does not grow with others.size()): `matches` is what
     /// matchPairsMany( others ) returned, element k equals estimateHomography( others[k], matches[k], opts ).  Throws as
@@ -239,6 +249,11 @@ public:
     /// the same for fundamental matrices (psx_ransac_fundamental_many)
     std::vector<FundamentalEstimate> estimateFundamentalMany( const std::vector<FeaturesDev*>& others, const std::vector<std::vector<Match>>& matches,
                                                               const RansacOptions& opts = RansacOptions() );
+    /// the same for affine transforms and similarities (psx_ransac_affine_many, psx_ransac_similarity_many)
+    std::vector<HomographyEstimate> estimateAffineMany( const std::vector<FeaturesDev*>& others, const std::vector<std::vector<Match>>& matches,
+                                                        const RansacOptions& opts = RansacOptions() );
+    std::vector<HomographyEstimate> estimateSimilarityMany( const std::vector<FeaturesDev*>& others, const std::vector<std::vector<Match>>& matches,
+                                                            const RansacOptions& opts = RansacOptions() );
 
     inline Feature*   getFeatures()    { return _ext; }
     inline Descriptor* getDescriptors() { return _ori; }
