@@ -844,6 +844,41 @@ int psx_probe_extra_times(psx_ctx* ctx, float* level0_ms, double* level0_bytes, 
  * an event carries plain stores between kernels; the assumption every multi-stream use of this library rests on). */
 int psx_debug_cross_stream(int device, int rounds, int pcie_words_per_thread, int* stale);
 
+/* The launch schedule of a frame, on the HOST: no device, no context (csrc/hip/pyramid_plan.h, the function psx_resize
+ * itself plans with).  Behind the level-0 launch of octave 0, psx_build_pyramid issues the steps of a plan in order, and
+ * psx_find_extrema the scan steps when they did not go out with the pyramid.  A step is a kind and four ints, unused
+ * ones 0:
+ *   PSX_STEP_BLUR      level b of octave a in one launch
+ *   PSX_STEP_BLUR2     levels (a, b) and (c, d) in one launch
+ *   PSX_STEP_TILE      launch a of the tile schedule
+ *   PSX_STEP_FLOW      the one-launch flow kernel
+ *   PSX_STEP_SCAN      the extrema scan of octave a as a launch of its own
+ *   PSX_STEP_SCAN_SET  one batched scan of the n <= 4 octaves a, b, c, d
+ * The frame is w0 x h0 at octave 0 and halves, rounding up, per octave; spans: the levels + 3 one-sided tap counts of the
+ * inc table (psx_gauss_tables); resident_blocks: 4 x the device's compute units (1024 on an MI355X).  The tuning is the
+ * environment's, as a context created now would read it.  schedule: PSX_PLAN_DIAGONAL (the default), PSX_PLAN_TILE
+ * (POPSIFT_TILE=1: `first` is ignored, the tile schedule decides it; PSX_ERR_STATE where no tile schedule exists and a
+ * context keeps the diagonal one) or PSX_PLAN_FLOW (POPSIFT_FLOW=1 / 2: first = 0 / 1, the first octave on the flow
+ * kernel).  *count is always the total; the first min(total, capacity) steps are written (capacity 0 with NULL: "how
+ * many?").  PSX_ERR_INVALID for a NULL spans or count, a NULL steps with a capacity, a negative capacity, a size, level
+ * count or resident_blocks below 1, an octave or level count above the library's limits, an unknown schedule, a flow
+ * `first` outside 0, 1 or not below num_octaves. */
+#define PSX_STEP_BLUR     1
+#define PSX_STEP_BLUR2    2
+#define PSX_STEP_TILE     3
+#define PSX_STEP_FLOW     4
+#define PSX_STEP_SCAN     5
+#define PSX_STEP_SCAN_SET 6
+#define PSX_PLAN_DIAGONAL 0
+#define PSX_PLAN_TILE     1
+#define PSX_PLAN_FLOW     2
+typedef struct psx_step { int kind, n, a, b, c, d; } psx_step;
+int psx_pyramid_plan(int w0, int h0, int num_octaves, int levels, const int* spans, int resident_blocks, int schedule,
+                     int first, psx_step* steps, int capacity, int* count);
+/* Workgroups a plane-to-plane blur of a W x H plane is launched with at this span, under the environment's tuning: the
+ * pairing rule of the diagonal schedule is grid(plane 1) + grid(plane 2) <= resident_blocks at the larger span. */
+int psx_blur_grid_of(int W, int H, int span);
+
 /* Measurement: one pyramid build with the whole-pyramid kernel (k_pyramid_flow) recording, per work item and in ticket
  * order, six int64: the 100 MHz wall clock at dequeue / dependencies met / arithmetic done / published, a word
  * (octave << 40 | level << 32 | chunk << 16 | strip) and the workgroup index.  *nitems = items of the current plan

@@ -110,6 +110,7 @@ SYMBOLS = [
     "psx_similarity_fit", "psx_ransac_similarity_ref", "psx_ransac_similarity", "psx_ransac_similarity_dev",
     "psx_ransac_affine_many", "psx_ransac_affine_many_dev", "psx_ransac_affine_many_ref",
     "psx_ransac_similarity_many", "psx_ransac_similarity_many_dev", "psx_ransac_similarity_many_ref",
+    "psx_pyramid_plan", "psx_blur_grid_of",
 ]
 
 PAIRS_MUTUAL = 1     # PSX_PAIRS_MUTUAL
@@ -274,6 +275,8 @@ def lib():
         for n in ("psx_ransac_homography_many_ref", "psx_ransac_fundamental_many_ref", "psx_ransac_affine_many_ref", "psx_ransac_similarity_many_ref"):
             getattr(L, n).argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(RansacOpts), vp, vp, C.c_int, ip, vp, vp]
         L.psx_ransac_many_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, ip]
+        L.psx_pyramid_plan.argtypes = [C.c_int] * 4 + [vp] + [C.c_int] * 3 + [vp, C.c_int, ip]
+        L.psx_blur_grid_of.argtypes = [C.c_int] * 3
         _LIB = L
     return _LIB
 
@@ -1141,6 +1144,39 @@ def ransac_many_plan(set_counts, min_pairs, block_rows):
     if rc != 0:
         raise PopSiftError("psx_ransac_many_plan failed (%d)" % rc)
     return blocks
+
+
+# psx_step kinds and the schedules of psx_pyramid_plan
+STEP_BLUR, STEP_BLUR2, STEP_TILE, STEP_FLOW, STEP_SCAN, STEP_SCAN_SET = 1, 2, 3, 4, 5, 6
+PLAN_DIAGONAL, PLAN_TILE, PLAN_FLOW = 0, 1, 2
+EXT_BATCH = 4                    # PSX_EXT_BATCH: octaves per batched extrema scan
+
+
+def pyramid_plan(w0, h0, num_octaves, levels, spans, resident_blocks=1024, schedule=PLAN_DIAGONAL, first=0):
+    """psx_pyramid_plan: the (n, 6) int32 steps = kind, n, a, b, c, d a context of this size issues per frame behind the
+    level-0 launch.  No device.  None where the tile schedule is asked for and none exists."""
+    L = lib()
+    sp = np.ascontiguousarray(spans, dtype=np.int32)
+    args = (w0, h0, num_octaves, levels, sp.ctypes.data_as(C.c_void_p), resident_blocks, schedule, first)
+    n = C.c_int(-1)
+    rc = L.psx_pyramid_plan(*args, None, 0, C.byref(n))
+    if rc == -4 and schedule == PLAN_TILE:
+        return None
+    if rc != 0:
+        raise PopSiftError("psx_pyramid_plan failed (%d)" % rc)
+    steps = np.zeros((n.value, 6), np.int32)
+    rc = L.psx_pyramid_plan(*args, steps.ctypes.data_as(C.c_void_p) if n.value else None, n.value, C.byref(n))
+    if rc != 0:
+        raise PopSiftError("psx_pyramid_plan failed (%d)" % rc)
+    return steps
+
+
+def blur_grid(w, h, span):
+    """psx_blur_grid_of: workgroups of a plane-to-plane blur of a w x h plane at this span.  No device."""
+    n = lib().psx_blur_grid_of(w, h, span)
+    if n < 0:
+        raise PopSiftError("psx_blur_grid_of failed (%d)" % n)
+    return n
 
 
 class DeviceDescriptors:

@@ -7,7 +7,8 @@
 // device; the batch dispatcher uses that to keep several frames in flight per GPU.
 //
 // Stream model: every context owns one HIP stream; a frame is one stream-ordered chain
-//   memset(counters) -> k_level0_fused -> k_blur / k_blur2 in the diagonal schedule of psx_build_pyramid, a large octave's
+//   memset(counters) -> k_level0_fused -> k_blur / k_blur2 in the diagonal schedule (the frame's plan, pyramid_plan.h, built
+//   in psx_resize and issued by psx_build_pyramid), a large octave's
 //   k_extrema right behind its last level and one batched k_extrema for the small octaves -> k_refine
 //   -> k_orientation -> k_scan -> k_descriptors
 // (default configuration; the other Gauss and scaling modes build their pyramid in pyramid_alt.hip, POPSIFT_FLOW and
@@ -18,6 +19,7 @@
 #include "blur_tile_core.h"
 #include "kp_place.h"
 #include "mask_rule.h"
+#include "pyramid_plan.h"
 
 #include <atomic>
 #include <cmath>
@@ -212,6 +214,12 @@ struct psx_ctx {
         std::vector<TileLaunch> launches;
         DevBuf<PsxTileJob> jobs;
     } tile;
+
+    // The frame's blur and scan launches in issue order (pyramid_plan.h), rebuilt where sizes or tuning change: in
+    // psx_resize.  plan_own: the flow or tile schedule in force, empty when there is none; plan_diagonal: the default
+    // schedule, which also serves where the tile schedule steps aside for the blur probe (frame_plan) and, through its
+    // scan steps alone, the alternative modes.
+    PsxPlan plan_diagonal, plan_own;
 
     // caller-supplied keypoints (psx_set_keypoints / psx_describe, keypoints.hip)
     struct {
@@ -463,18 +471,7 @@ extern "C" int psx_tile_selfcheck(int w0, int h0, int num_octaves, int levels, c
                                   long long maxpx, int* stats)
 {
     PsxParams P;
-    memset(&P, 0, sizeof(P));
-    P.num_octaves = num_octaves; P.levels = levels; P.L = levels + 3;
-    if (num_octaves < 1 || num_octaves > PSX_MAX_OCTAVES || P.L > PSX_GAUSS_LEVELS) return -1;
-    size_t off = 4096;
-    int w = w0, h = h0;
-    for (int o = 0; o < num_octaves; o++) {
-        PsxOctave& oc = P.oct[o];
-        oc.w = w; oc.h = h; oc.pitch = (w + 63) & ~63; oc.plane = (size_t)oc.pitch * h;
-        oc.data = reinterpret_cast<float*>(off * 4);
-        off += oc.plane * P.L;
-        w = (w + 1) / 2; h = (h + 1) / 2;
-    }
+    if (!psx_plan_params(w0, h0, num_octaves, levels, &P)) return -1;
     std::vector<float> filt((size_t)PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN, 0.0f);
     TileSched sc;
     if (!tile_schedule(P, spans, filt.data(), tile_ty, tile_nt, maxpx, psx_tuning_from_env().tile_small, sc)) return 0;
@@ -522,6 +519,31 @@ extern "C" int psx_tile_selfcheck(int w0, int h0, int num_octaves, int levels, c
     if (stats) { stats[0] = sc.first; stats[1] = (int)sc.launches.size(); stats[2] = (int)maxlds; stats[3] = maxgrid; }
     return (int)sc.jobs.size();
 }
+
+// psx_pyramid_plan, psx_blur_grid_of (include/popsift_hip.h): the step list a context of this size would issue, no device
+extern "C" int psx_pyramid_plan(int w0, int h0, int num_octaves, int levels, const int* spans, int resident_blocks, int schedule,
+                                int first, psx_step* steps, int capacity, int* count)
+{
+    PsxParams P;
+    if (!spans || !count || capacity < 0 || (capacity > 0 && !steps) || w0 < 1 || h0 < 1 || levels < 1 || resident_blocks < 1 ||
+        schedule < PSX_PLAN_DIAGONAL || schedule > PSX_PLAN_FLOW || !psx_plan_params(w0, h0, num_octaves, levels, &P))
+        return PSX_ERR_INVALID;
+    const PsxTuning t = psx_tuning_from_env();
+    int ntile = 0;
+    if (schedule == PSX_PLAN_TILE) {
+        std::vector<float> filt((size_t)PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN, 0.0f);
+        TileSched sc;
+        if (!tile_schedule(P, spans, filt.data(), t.tile_ty, t.tile_nt, t.tile_maxpx, t.tile_small, sc)) return PSX_ERR_STATE;
+        first = sc.first; ntile = (int)sc.launches.size();
+    } else if (schedule == PSX_PLAN_FLOW && (first < 0 || first > 1 || first >= num_octaves)) return PSX_ERR_INVALID;
+    PsxPlan plan;
+    psx_pyramid_steps(P, spans, t, resident_blocks, schedule, first, ntile, plan);
+    *count = (int)plan.size();
+    for (int i = 0; i < *count && i < capacity; i++) steps[i] = plan[(size_t)i];
+    return PSX_OK;
+}
+
+extern "C" int psx_blur_grid_of(int W, int H, int span) { return W < 1 || H < 1 || span < 1 ? PSX_ERR_INVALID : psx_blur_grid(psx_tuning_from_env(), W, H, span); }
 
 extern "C" {
 
@@ -818,6 +840,11 @@ int psx_resize(psx_ctx* ctx, int w, int h)
         }
     }
     { const int trc = plan_tiles(ctx); if (trc != PSX_OK) return trc; }
+    psx_pyramid_steps(P, ctx->tab.inc_span, ctx->tune, ctx->resident_blocks, PSX_PLAN_DIAGONAL, 0, 0, ctx->plan_diagonal);
+    ctx->plan_own.clear();
+    if (ctx->flow.on) psx_pyramid_steps(P, ctx->tab.inc_span, ctx->tune, ctx->resident_blocks, PSX_PLAN_FLOW, ctx->flow.first, 0, ctx->plan_own);
+    else if (ctx->tile.on)
+        psx_pyramid_steps(P, ctx->tab.inc_span, ctx->tune, ctx->resident_blocks, PSX_PLAN_TILE, ctx->tile.first, (int)ctx->tile.launches.size(), ctx->plan_own);
     ctx->d_cand_ct = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->d_cnt) + CNT_BLOCK + ctx->flow.bytes);
     P.cand_capacity = (4 * c.max_extrema + PSX_CAND_SUB - 1) / PSX_CAND_SUB;
     PSX_HIP(ctx->d_cand.grow((size_t)P.num_octaves * PSX_CAND_SUB * P.cand_capacity));
@@ -927,27 +954,58 @@ static int launch_blur_level(psx_ctx* ctx, int o, int level, hipEvent_t ev0 = nu
     return PSX_OK;
 }
 
-// extrema scans of a set of octaves, PSX_EXT_BATCH per launch
-static int launch_extrema_set(psx_ctx* ctx, const int* octaves, int n)
+// the plan of the schedule in force: with the blur probe on, a tile schedule that would take octave 0 steps aside for the
+// diagonal one (the probe times octave 0's launches level by level)
+static const PsxPlan& frame_plan(const psx_ctx* ctx)
 {
-    for (int i = 0; i < n; i += PSX_EXT_BATCH) {
-        const int m = n - i < PSX_EXT_BATCH ? n - i : PSX_EXT_BATCH;
-        PSX_HIP(psx_launch_extrema_batch(ctx->d_params, ctx->hp, ctx->d_cnt, octaves + i, m, mask_of(ctx), ctx->stream));
-    }
-    return PSX_OK;
+    const bool own = ctx->flow.on || (ctx->tile.on && !(ctx->tm.probe && ctx->tile.first == 0));
+    return own ? ctx->plan_own : ctx->plan_diagonal;
 }
 
-// The extrema scan of octave o.  A large octave's scan goes out at once (right behind its last level its planes are as
-// cache-resident as they will ever be), bracketed by the probe events when it is octave 0; an octave whose tiles do not fill
-// the chip (a few hundred tiles, a latency-bound launch) is put on `deferred` and shares one launch with the others.
-static int scan_or_defer(psx_ctx* ctx, int o, int* deferred, int* ndef)
+// One step of the frame's plan.  With the blur probe on, a blur launch whose (first) plane is a level of octave 0 is
+// bracketed by that level's events and adds its algorithmic bytes (8 B per pixel of every plane it blurs) to *probe_bytes,
+// the flow launch is bracketed when it carries octave 0, and octave 0's own scan launch by ev_x[2] / ev_x[3].
+static int issue_step(psx_ctx* ctx, const psx_step& s, double* probe_bytes)
 {
-    if (psx_extrema_tiles(ctx->hp, o) < ctx->resident_blocks) { deferred[(*ndef)++] = o; return PSX_OK; }
-    const bool px = ctx->tm.probe && o == 0;
-    if (px) PSX_HIP(hipEventRecord(ctx->tm.ev_x[2].h, ctx->stream));
-    PSX_HIP(psx_launch_extrema(ctx->d_params, ctx->hp, ctx->d_cnt, o, mask_of(ctx), ctx->stream));
-    if (px) { PSX_HIP(hipEventRecord(ctx->tm.ev_x[3].h, ctx->stream)); ctx->tm.probe_ext0 = true; }
-    return PSX_OK;
+    const PsxParams& P = ctx->hp;
+    const bool probe = ctx->tm.probe;
+    switch (s.kind) {
+    case PSX_STEP_BLUR:
+    case PSX_STEP_BLUR2: {
+        const bool pl = probe && s.a == 0;
+        hipEvent_t e0 = pl ? ctx->tm.ev_blur[2 * (s.b - 1)].h : nullptr, e1 = pl ? ctx->tm.ev_blur[2 * (s.b - 1) + 1].h : nullptr;
+        if (s.kind == PSX_STEP_BLUR) { const int rc = launch_blur_level(ctx, s.a, s.b, e0, e1); if (rc != PSX_OK) return rc; }
+        else PSX_HIP(psx_launch_blur2(ctx->tune, blur_job(ctx, s.a, s.b), blur_job(ctx, s.c, s.d), ctx->stream, e0, e1));
+        if (pl) *probe_bytes += 8.0 * ((double)P.oct[s.a].w * P.oct[s.a].h + (s.kind == PSX_STEP_BLUR2 ? (double)P.oct[s.c].w * P.oct[s.c].h : 0.0));
+        return PSX_OK;
+    }
+    case PSX_STEP_TILE: {
+        const psx_ctx::TileLaunch& ln = ctx->tile.launches[(size_t)s.a];
+        PSX_HIP(psx_launch_blur_tile(ctx->tile.jobs + ln.job0, ln.njobs, ln.grid, ln.lds, ctx->tune.tile_nt, ctx->stream));
+        return PSX_OK;
+    }
+    case PSX_STEP_FLOW: {
+        const bool pf = probe && ctx->flow.first == 0;
+        int* state = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->d_cnt) + CNT_BLOCK);
+        PSX_HIP(psx_launch_flow(ctx->tune, ctx->flow.jobs, ctx->flow.items, ctx->flow.nitems, state, &ctx->d_cnt->flow_error,
+                                ctx->flow.grid, ctx->tune.flow_ld, ctx->stream, pf ? ctx->tm.ev_blur[0].h : nullptr, pf ? ctx->tm.ev_blur[1].h : nullptr,
+                                ctx->flow.trace));
+        return PSX_OK;
+    }
+    case PSX_STEP_SCAN: {
+        const bool px = probe && s.a == 0;
+        if (px) PSX_HIP(hipEventRecord(ctx->tm.ev_x[2].h, ctx->stream));
+        PSX_HIP(psx_launch_extrema(ctx->d_params, ctx->hp, ctx->d_cnt, s.a, mask_of(ctx), ctx->stream));
+        if (px) { PSX_HIP(hipEventRecord(ctx->tm.ev_x[3].h, ctx->stream)); ctx->tm.probe_ext0 = true; }
+        return PSX_OK;
+    }
+    case PSX_STEP_SCAN_SET: {
+        const int octaves[PSX_EXT_BATCH] = {s.a, s.b, s.c, s.d};
+        PSX_HIP(psx_launch_extrema_batch(ctx->d_params, ctx->hp, ctx->d_cnt, octaves, s.n, mask_of(ctx), ctx->stream));
+        return PSX_OK;
+    }
+    }
+    return fail(ctx, PSX_ERR_STATE, "issue_step: unknown step kind");
 }
 
 int psx_build_pyramid(psx_ctx* ctx)
@@ -957,12 +1015,16 @@ int psx_build_pyramid(psx_ctx* ctx)
     PSX_HIP(hipSetDevice(ctx->device));
     const PsxParams& P = ctx->hp;
     const psx_config& c = ctx->cfg;
+    const bool probe = ctx->tm.probe;
     ctx->counts_valid = false;
     ctx->pyr_ready = true; ctx->kp.results = false;
+    ctx->ext_launched = false;
     if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[0].h, ctx->stream));
     // Pyramid::reset_extrema_mgmt, sift_pyramid.cu:364-371
     PSX_HIP(hipMemsetAsync(ctx->d_cnt, 0, CNT_BLOCK + ctx->flow.bytes + sizeof(int) * (size_t)P.num_octaves * PSX_CAND_SUB * 32, ctx->stream));
 
+    // the scans go out with the pyramid in psx_extract, except behind the flow kernel: there psx_find_extrema issues them
+    const bool scans = ctx->interleave && !ctx->flow.on;
     if (ctx->alt_pyramid) {
         PsxAltArgs q;
         q.tune = &ctx->tune; q.hp = &ctx->hp;
@@ -973,13 +1035,12 @@ int psx_build_pyramid(psx_ctx* ctx)
         q.up = ctx->d_up; q.up_pitch = ctx->up_pitch;
         q.intm = ctx->d_intm; q.vbuf = ctx->d_vbuf; q.vbuf_pitch = P.oct[0].pitch + 64;
         q.user = ctx;
-        q.after_octave = ctx->interleave ? +[](void* u, int o) -> hipError_t {
+        q.after_octave = scans ? +[](void* u, int o) -> hipError_t {
             psx_ctx* cx = static_cast<psx_ctx*>(u);
             return psx_launch_extrema(cx->d_params, cx->hp, cx->d_cnt, o, mask_of(cx), cx->stream);
         } : nullptr;
-        ctx->ext_launched = false;
         int probe_hit = 0;
-        if (ctx->tm.probe) { q.probe_ev0 = ctx->tm.ev_blur[0].h; q.probe_ev1 = ctx->tm.ev_blur[1].h; q.probe_hit = &probe_hit; ctx->tm.probe_n = 0; }
+        if (probe) { q.probe_ev0 = ctx->tm.ev_blur[0].h; q.probe_ev1 = ctx->tm.ev_blur[1].h; q.probe_hit = &probe_hit; ctx->tm.probe_n = 0; }
         const hipError_t e = psx_launch_pyramid_alt(q, ctx->stream);
         if (probe_hit) {
             // Fixed9 / Fixed15: the one-kernel octave 0 (six planes written from the input image: 24 B per pixel + the image)
@@ -988,135 +1049,31 @@ int psx_build_pyramid(psx_ctx* ctx)
         }
         if (e == hipErrorInvalidValue) return fail(ctx, PSX_ERR_INVALID, "Unsupported number of levels for making all octaves at once");
         PSX_HIP(e);
-        ctx->ext_launched = ctx->interleave;
-        if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[1].h, ctx->stream));
-        return PSX_OK;
-    }
+    } else {
+        PsxLevel0Args a;
+        a.img = ctx->d_input; a.w = ctx->in_w; a.h = ctx->in_h; a.is_float = ctx->input_is_float;
+        a.dst = P.oct[0].data; a.W = P.oct[0].w; a.H = P.oct[0].h; a.pitch = P.oct[0].pitch;
+        a.tmp = ctx->d_up; a.tmp_pitch = ctx->up_pitch;
+        a.shift = 0.5f;                                                    // s_pyramid_build.cu:109-114
+        if (c.sift_mode == PSX_MODE_POPSIFT || c.sift_mode == PSX_MODE_VLFEAT)
+            a.shift = 0.5f * powf(2.0f, c.upscale_factor - 0);
+        a.taps_h = taps_from(ctx->tab.dd_filter); a.span_h = ctx->tab.dd_span[0];
+        a.taps_v = taps_from(ctx->tab.inc_filter); a.span_v = ctx->tab.inc_span[0];
+        if (probe) PSX_HIP(hipEventRecord(ctx->tm.ev_x[0].h, ctx->stream));
+        PSX_HIP(psx_launch_level0(ctx->tune, a, ctx->stream));
+        if (probe) PSX_HIP(hipEventRecord(ctx->tm.ev_x[1].h, ctx->stream));
 
-    PsxLevel0Args a;
-    a.img = ctx->d_input; a.w = ctx->in_w; a.h = ctx->in_h; a.is_float = ctx->input_is_float;
-    a.dst = P.oct[0].data; a.W = P.oct[0].w; a.H = P.oct[0].h; a.pitch = P.oct[0].pitch;
-    a.tmp = ctx->d_up; a.tmp_pitch = ctx->up_pitch;
-    a.shift = 0.5f;                                                    // s_pyramid_build.cu:109-114
-    if (c.sift_mode == PSX_MODE_POPSIFT || c.sift_mode == PSX_MODE_VLFEAT)
-        a.shift = 0.5f * powf(2.0f, c.upscale_factor - 0);
-    a.taps_h = taps_from(ctx->tab.dd_filter); a.span_h = ctx->tab.dd_span[0];
-    a.taps_v = taps_from(ctx->tab.inc_filter); a.span_v = ctx->tab.inc_span[0];
-    if (ctx->tm.probe) PSX_HIP(hipEventRecord(ctx->tm.ev_x[0].h, ctx->stream));
-    PSX_HIP(psx_launch_level0(ctx->tune, a, ctx->stream));
-    if (ctx->tm.probe) PSX_HIP(hipEventRecord(ctx->tm.ev_x[1].h, ctx->stream));
-
-    ctx->ext_launched = false;
-    const bool probe = ctx->tm.probe;
-    if (ctx->flow.on) {
-        // k_pyramid_flow: octave 0's levels by launches first when the plan starts at octave 1 (POPSIFT_FLOW=2), then every
-        // remaining blur level of the frame in ONE launch with device-side dependencies; the extrema scans follow in
-        // psx_find_extrema
-        for (int level = 1; ctx->flow.first > 0 && level < P.L; level++) {
-            hipEvent_t e0 = probe ? ctx->tm.ev_blur[2 * (level - 1)].h : nullptr, e1 = probe ? ctx->tm.ev_blur[2 * (level - 1) + 1].h : nullptr;
-            const int rc = launch_blur_level(ctx, 0, level, e0, e1);
-            if (rc != PSX_OK) return rc;
-        }
-        const bool pf = probe && ctx->flow.first == 0;
-        int* state = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->d_cnt) + CNT_BLOCK);
-        PSX_HIP(psx_launch_flow(ctx->tune, ctx->flow.jobs, ctx->flow.items, ctx->flow.nitems, state, &ctx->d_cnt->flow_error,
-                                ctx->flow.grid, ctx->tune.flow_ld, ctx->stream, pf ? ctx->tm.ev_blur[0].h : nullptr, pf ? ctx->tm.ev_blur[1].h : nullptr,
-                                ctx->flow.trace));
-        if (probe) {
-            if (pf) { ctx->tm.probe_n = 1; ctx->tm.probe_bytes = ctx->flow.algo_bytes; }
-            else    { ctx->tm.probe_n = P.L - 1; ctx->tm.probe_bytes = 8.0 * (double)P.oct[0].w * P.oct[0].h; }
-        }
-        if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[1].h, ctx->stream));
-        return PSX_OK;
-    }
-    if (ctx->tile.on && !(probe && ctx->tile.first == 0)) {
-        // octaves in front of tile_first: one launch per level, the octave's extrema scan right behind its last level;
-        // then the tile launches (several levels of up to two octaves each); then the scans of the small octaves
         double probe_bytes = 0.0;
-        int deferred[PSX_MAX_OCTAVES], ndef = 0;
-        auto scan_after = [&](int o) -> int { return ctx->interleave ? scan_or_defer(ctx, o, deferred, &ndef) : PSX_OK; };
-        for (int o = 0; o < ctx->tile.first; o++) {
-            for (int level = 1; level < P.L; level++) {
-                const bool pl = probe && o == 0;
-                hipEvent_t e0 = pl ? ctx->tm.ev_blur[2 * (level - 1)].h : nullptr, e1 = pl ? ctx->tm.ev_blur[2 * (level - 1) + 1].h : nullptr;
-                const int rc = launch_blur_level(ctx, o, level, e0, e1);
-                if (rc != PSX_OK) return rc;
-                if (pl) probe_bytes += 8.0 * (double)P.oct[o].w * P.oct[o].h;
-            }
-            const int rc = scan_after(o);
+        for (const psx_step& s : frame_plan(ctx)) {
+            if (psx_step_is_scan(s) && !scans) continue;
+            const int rc = issue_step(ctx, s, &probe_bytes);
             if (rc != PSX_OK) return rc;
         }
-        for (const psx_ctx::TileLaunch& ln : ctx->tile.launches)
-            PSX_HIP(psx_launch_blur_tile(ctx->tile.jobs + ln.job0, ln.njobs, ln.grid, ln.lds, ctx->tune.tile_nt, ctx->stream));
-        for (int o = ctx->tile.first; o < P.num_octaves; o++) { const int rc = scan_after(o); if (rc != PSX_OK) return rc; }
-        if (ndef > 0) { const int rc = launch_extrema_set(ctx, deferred, ndef); if (rc != PSX_OK) return rc; }
-        if (probe) { ctx->tm.probe_n = P.L - 1; ctx->tm.probe_bytes = probe_bytes / (P.L - 1); }
-        ctx->ext_launched = ctx->interleave;
-        if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[1].h, ctx->stream));
-        return PSX_OK;
+        // octave 0's L - 1 launches, timed one by one; or the one flow launch that carries octave 0
+        const bool pf = ctx->flow.on && ctx->flow.first == 0;
+        if (probe) { ctx->tm.probe_n = pf ? 1 : P.L - 1; ctx->tm.probe_bytes = pf ? ctx->flow.algo_bytes : probe_bytes / (P.L - 1); }
     }
-    // Diagonal schedule.  Level l of octave o only needs level l-1 of the same octave, and level 0 of octave o+1
-    // is written by the launch of level D = L-3 of octave o; so octave o+1 may start D launch slots after octave
-    // o, and (o+1, l) then shares ONE launch with (o, l+D) -- if the two planes fit one round of resident
-    // workgroups (4 per CU).  The small octaves, chains of ~5 us launches on their own, ride along with the octave
-    // above.  Where the pair does not fit (octave 0 / 1 of a 1080p frame) the smaller plane would only queue behind
-    // a full chip, run on the larger radius' kernel for nothing and push the larger octave's planes out of L2
-    // between its own levels: there octave o+1 starts after octave o's last level.
-    const int D = P.L - 3;
-    int t0[PSX_MAX_OCTAVES];                       // level l of octave o runs in launch slot t0[o] + l
-    t0[0] = 0;
-    for (int o = 0; o + 1 < P.num_octaves; o++) {
-        const int span = ctx->tab.inc_span[P.L - 1];
-        const bool fits = ctx->tune.batch_octaves &&
-            psx_blur_pair_ok(ctx->tune, P.oct[o].w, P.oct[o].h, P.oct[o + 1].w, P.oct[o + 1].h, span, ctx->resident_blocks);
-        t0[o + 1] = t0[o] + (fits ? D : P.L - 1);
-    }
-    const int T = t0[P.num_octaves - 1] + P.L - 1;
-    double probe_bytes = 0.0;
-    int deferred[PSX_MAX_OCTAVES], ndef = 0;
-    for (int t = 1; t <= T; t++) {
-        int jo[4], nj = 0;
-        for (int o = 0; o < P.num_octaves && nj < 4; o++) {
-            const int l = t - t0[o];
-            if (l >= 1 && l <= P.L - 1) jo[nj++] = o;
-        }
-        for (int q = 0; q < nj; q += 2) {
-            const int o = jo[q], level = t - t0[o];
-            const bool pl = probe && o == 0;
-            hipEvent_t e0 = pl ? ctx->tm.ev_blur[2 * (level - 1)].h : nullptr, e1 = pl ? ctx->tm.ev_blur[2 * (level - 1) + 1].h : nullptr;
-            // only when both fit into one round of resident workgroups (4 per CU): behind a launch that fills the
-            // chip the second plane would just queue, and it would run on the larger radius' kernel for nothing
-            bool pair = q + 1 < nj && ctx->tune.batch_octaves;
-            if (pair) {
-                const int o2 = jo[q + 1], level2 = t - t0[o2];
-                const int span = ctx->tab.inc_span[level] > ctx->tab.inc_span[level2] ? ctx->tab.inc_span[level] : ctx->tab.inc_span[level2];
-                pair = psx_blur_pair_ok(ctx->tune, P.oct[o].w, P.oct[o].h, P.oct[o2].w, P.oct[o2].h, span, ctx->resident_blocks);
-            }
-            if (pair) {
-                const int o2 = jo[q + 1], level2 = t - t0[o2];
-                PSX_HIP(psx_launch_blur2(ctx->tune, blur_job(ctx, o, level), blur_job(ctx, o2, level2), ctx->stream, e0, e1));
-                if (pl) probe_bytes += 8.0 * ((double)P.oct[o].w * P.oct[o].h + (double)P.oct[o2].w * P.oct[o2].h);
-            } else {
-                int rc = launch_blur_level(ctx, o, level, e0, e1);
-                if (rc != PSX_OK) return rc;
-                if (pl) probe_bytes += 8.0 * (double)P.oct[o].w * P.oct[o].h;
-                if (q + 1 < nj) {
-                    rc = launch_blur_level(ctx, jo[q + 1], t - t0[jo[q + 1]]);
-                    if (rc != PSX_OK) return rc;
-                }
-            }
-        }
-        // a large octave's scan right behind its last level: its planes are as cache-resident now as they will ever
-        // be.  The small octaves' scans (a few hundred tiles each, latency-bound launches) wait and share one launch.
-        for (int q = 0; q < nj; q++)
-            if (t - t0[jo[q]] == P.L - 1 && ctx->interleave) {
-                const int rc = scan_or_defer(ctx, jo[q], deferred, &ndef);
-                if (rc != PSX_OK) return rc;
-            }
-    }
-    if (ndef > 0) { int rc = launch_extrema_set(ctx, deferred, ndef); if (rc != PSX_OK) return rc; }
-    if (probe) { ctx->tm.probe_n = P.L - 1; ctx->tm.probe_bytes = probe_bytes / (P.L - 1); }
-    ctx->ext_launched = ctx->interleave;
+    ctx->ext_launched = scans;
     if (ctx->tm.on) PSX_HIP(hipEventRecord(ctx->tm.ev[1].h, ctx->stream));
     return PSX_OK;
 }
@@ -1177,14 +1134,12 @@ int psx_find_extrema(psx_ctx* ctx)
     if (!ctx->d_pyr) return fail(ctx, PSX_ERR_STATE, "psx_find_extrema: no pyramid");
     { const int mrc = check_mask(ctx, "psx_find_extrema"); if (mrc != PSX_OK) return mrc; }
     PSX_HIP(hipSetDevice(ctx->device));
-    if (!ctx->ext_launched) {
-        int small[PSX_MAX_OCTAVES], ns = 0;
-        for (int o = 0; o < ctx->hp.num_octaves; o++) {
-            const int rc = scan_or_defer(ctx, o, small, &ns);
+    if (!ctx->ext_launched)                              // the scans did not go out with the pyramid: the plan's scan steps, in its order
+        for (const psx_step& s : frame_plan(ctx)) {
+            if (!psx_step_is_scan(s)) continue;
+            const int rc = issue_step(ctx, s, nullptr);
             if (rc != PSX_OK) return rc;
         }
-        if (ns > 0) { int rc = launch_extrema_set(ctx, small, ns); if (rc != PSX_OK) return rc; }
-    }
     ctx->ext_launched = false;
     PSX_HIP(psx_launch_refine(ctx->d_params, ctx->hp, ctx->d_cnt, mask_of(ctx), ctx->stream));
     ctx->filtered = false;

@@ -61,6 +61,25 @@ struct PsxParams {
     int*          ext_nori;              // num_ori per extremum (SoA copy for the scan)
 };
 
+// The sizes, pitches and (never dereferenced) plane addresses of a w0 x h0 frame, for the entry points that plan without a
+// device (psx_tile_selfcheck, psx_flow_selfcheck, psx_pyramid_plan); false for counts outside the library's limits
+inline bool psx_plan_params(int w0, int h0, int num_octaves, int levels, PsxParams* P)
+{
+    *P = PsxParams{};
+    P->num_octaves = num_octaves; P->levels = levels; P->L = levels + 3;
+    if (num_octaves < 1 || num_octaves > PSX_MAX_OCTAVES || P->L > PSX_GAUSS_LEVELS) return false;
+    size_t off = 4096;
+    int w = w0, h = h0;
+    for (int o = 0; o < num_octaves; o++) {
+        PsxOctave& oc = P->oct[o];
+        oc.w = w; oc.h = h; oc.pitch = (w + 63) & ~63; oc.plane = (size_t)oc.pitch * h;
+        oc.data = reinterpret_cast<float*>(off * 4);
+        off += oc.plane * P->L;
+        w = (w + 1) / 2; h = (h + 1) / 2;
+    }
+    return true;
+}
+
 // Zero-copy export targets in mapped host memory (nullptr when detached).  Passed to the scan and descriptor
 // kernels BY VALUE as a kernel argument: attaching a fresh result buffer per frame then costs no HIP call at all
 // (a parameter-block update over PCIe per frame measured 0.9 ms of host time per worker).

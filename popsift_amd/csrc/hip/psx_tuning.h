@@ -3,7 +3,8 @@
 // Host only (no HIP header: tests/test_tuning_cpu.py builds it with the host compiler).  This is the only file of the
 // HIP library that calls getenv.  Lifetime: psx_create takes one snapshot per context and every launcher below api.hip
 // receives it; psx_match / psx_match_u8 (no context) keep one in the calling thread's scratch, refreshed when its device
-// changes; the planning self checks (psx_tile_selfcheck, psx_flow_selfcheck) take one per call.
+// changes; the no-device planning entries (psx_tile_selfcheck, psx_flow_selfcheck, psx_pyramid_plan, psx_blur_grid_of)
+// take one per call.
 //
 // A row: X(kind, type, field, environment name, default, accepted values as an expression in v, meaning).
 // Kinds -- a variable that is not set always leaves the default:

@@ -1859,18 +1859,7 @@ extern "C" int psx_flow_selfcheck(int w0, int h0, int num_octaves, int levels, c
                                   int resident_blocks, int order, int* stats)
 {
     PsxParams P;
-    memset(&P, 0, sizeof(P));
-    P.num_octaves = num_octaves; P.levels = levels; P.L = levels + 3;
-    if (num_octaves < 1 || num_octaves > PSX_MAX_OCTAVES || P.L > PSX_GAUSS_LEVELS) return -1;
-    size_t off = 4096;
-    int w = w0, h = h0;
-    for (int o = 0; o < num_octaves; o++) {
-        PsxOctave& oc = P.oct[o];
-        oc.w = w; oc.h = h; oc.pitch = (w + 63) & ~63; oc.plane = (size_t)oc.pitch * h;
-        oc.data = reinterpret_cast<float*>(off * 4);
-        off += oc.plane * P.L;
-        w = (w + 1) / 2; h = (h + 1) / 2;
-    }
+    if (!psx_plan_params(w0, h0, num_octaves, levels, &P)) return -1;
     std::vector<float> filt((size_t)PSX_GAUSS_LEVELS * PSX_GAUSS_ALIGN, 0.0f);
     PsxFlowPlan plan{};
     if (!psx_flow_plan(psx_tuning_from_env(), P, filt.data(), spans, first_octave, resident_blocks, order, &plan)) return -2;
