@@ -379,7 +379,8 @@ int psx_pairs_join_u8(const int* fwd_match, const int* fwd_dist, int l_len, cons
  * PSX_ERR_INVALID, with nothing touched and before any device call: everything psx_match_pairs_u8 refuses; n_sets < 0;
  * d_rights, r_lens or set_counts NULL with n_sets > 0; a negative r_lens[k]; a NULL d_rights[k] with r_lens[k] > 0;
  * n_sets * l_len or the sum of r_lens above INT_MAX.  Scratch (psx_match_release) and thread safety as for psx_match_u8.
- * Synchronous, with exactly one stream synchronisation per call.  Only the byte form exists. */
+ * Synchronous, with exactly one stream synchronisation per call.  The float form: psx_match_pairs_many, below ("one
+ * descriptor set against many, float descriptors"). */
 int psx_match_pairs_many_u8(int device, const unsigned char* d_left, int l_len,
                             const unsigned char* const* d_rights, const int* r_lens, int n_sets,
                             const psx_match_opts* opts, psx_match_pair_u8* host_pairs, int capacity,
@@ -404,6 +405,56 @@ typedef struct psx_many_block { int set, row0; } psx_many_block;
 int psx_match_many_plan(int l_len, const int* r_lens, int n_sets, int backward,
                         psx_many_chunk* chunks, int chunk_capacity, int* chunk_count,
                         psx_many_block* blocks, int block_capacity, int* block_count);
+
+/* ---- one descriptor set against many (float descriptors) -------------------------------------
+ * psx_match_pairs_many_u8's contract, word for word, with psx_match_pairs in place of psx_match_pairs_u8: d_left is a
+ * DEVICE pointer to l_len descriptors of 128 floats, d_rights[k] one to r_lens[k] descriptors (d_rights / r_lens: HOST
+ * arrays of n_sets entries); every device pointer is 16-byte aligned; the sets may be separate allocations, slices of one
+ * buffer, or the same pointer more than once.  With P_k = the list psx_match_pairs returns for (L, R_k, opts) at unlimited
+ * capacity, bit for bit (float distances compared as bit patterns):
+ *   - the result is the concatenation P_0, P_1, ..., P_{n_sets-1}: sets ascending, `left` ascending within a set;
+ *   - `right` is the index WITHIN ITS SET; ties keep the earlier index, a NaN distance never wins, 0/0 fails the ratio
+ *     test, a missing second neighbour is +inf;
+ *   - set_counts[k] = |P_k| (HOST array of n_sets ints), always the set's total;
+ *   - *count = the sum of the |P_k|; the first min(*count, capacity) records of the concatenation are written, nothing at
+ *     or past capacity; capacity = 0 with a NULL output asks "how many?".
+ * n_sets = 0, l_len = 0 or an empty set give zero counts and PSX_OK; no device is touched when no pair can exist.
+ * PSX_ERR_INVALID, with nothing touched and before any device call: everything psx_match_pairs refuses; n_sets < 0;
+ * d_rights, r_lens or set_counts NULL with n_sets > 0; a negative r_lens[k]; a NULL d_rights[k] with r_lens[k] > 0;
+ * n_sets * l_len or the sum of r_lens above INT_MAX.  Scratch (psx_match_release) and thread safety as for psx_match.
+ * Two paths, one result ("One set against many", the float subsection): the MFMA prefilter over all sets
+ * when POPSIFT_MATCH_MFMA is on, l_len >= 256 and the sum of r_lens >= 4096 -- the single call's two thresholds on the
+ * call's totals --, the exact scan of every pair otherwise.  Synchronous: ONE stream synchronisation per call; a second
+ * one only when the prefilter's flag comes back up (a candidate segment overflowed, or a norm is zero, infinite or NaN)
+ * and the whole call is repeated by the exact scan.  The number of kernel launches does not grow with n_sets. */
+int psx_match_pairs_many(int device, const float* d_left, int l_len,
+                         const float* const* d_rights, const int* r_lens, int n_sets,
+                         const psx_match_opts* opts, psx_match_pair* host_pairs, int capacity,
+                         int* set_counts, int* count);
+/* the list stays in HBM: d_pairs is a DEVICE pointer, 16-byte aligned; set_counts and count are still HOST memory */
+int psx_match_pairs_many_dev(int device, const float* d_left, int l_len,
+                             const float* const* d_rights, const int* r_lens, int n_sets,
+                             const psx_match_opts* opts, psx_match_pair* d_pairs, int capacity,
+                             int* set_counts, int* count);
+
+/* What psx_match_pairs_many decides for these sizes, on the HOST: no device, no context (csrc/hip/match_many_f32_plan.h,
+ * the function the library itself plans with).  flags: psx_match_opts.flags; mfma_enabled: 1 as POPSIFT_MATCH_MFMA's
+ * default, 0 as POPSIFT_MATCH_MFMA=0.  path: 1 the exact scan, 2 the prefilter (0: no pair can exist, nothing runs);
+ * fwd_groups / bwd_groups: the groups of whole sets each direction is walked in (bwd_groups = 0 without the
+ * cross-check); launches: the kernels queued when the flag stays down; scratch_bytes: the largest group's share of the
+ * one buffer that grows with (chunks x outer rows), at most 256 MiB unless a single set exceeds it.  PSX_ERR_INVALID as
+ * above for the sets, for unknown flag bits, mfma_enabled not 0 or 1, out == NULL. */
+typedef struct psx_many_f32_plan { int path;        /* 1 scan, 2 prefilter */
+                                   int fwd_groups, bwd_groups;
+                                   int launches;    /* kernels queued when the flag stays down */
+                                   long long scratch_bytes; } psx_many_f32_plan;
+int psx_match_many_f32_plan(int l_len, const int* r_lens, int n_sets, int flags, int mfma_enabled,
+                            psx_many_f32_plan* out);
+/* The calling thread's last psx_match_pairs_many / _dev call that passed its argument checks (zeros before any): the
+ * path it planned, whether the flag came back up and the scan repeated the call, and the kernels launched and stream
+ * synchronisations made, counted where the call launches and synchronises.  PSX_ERR_INVALID for out == NULL. */
+typedef struct psx_many_f32_info { int path, fell_back, launches, syncs; } psx_many_f32_info;
+int psx_match_many_f32_last(psx_many_f32_info* out);
 
 /* ---- guided matching ---------------------------------------------------------------------
  * The 2-NN search restricted by what the caller knows about where a match can lie (AliceVision's guidedMatching, a

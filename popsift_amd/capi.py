@@ -98,6 +98,7 @@ SYMBOLS = [
     "psx_match_opts_default", "psx_match_pairs", "psx_match_pairs_u8", "psx_match_pairs_dev", "psx_match_pairs_u8_dev",
     "psx_pairs_join", "psx_pairs_join_u8",
     "psx_match_pairs_many_u8", "psx_match_pairs_many_u8_dev", "psx_match_many_plan",
+    "psx_match_pairs_many", "psx_match_pairs_many_dev", "psx_match_many_f32_plan", "psx_match_many_f32_last",
     "psx_guide_allows", "psx_desc_positions", "psx_match_guided", "psx_match_guided_u8",
     "psx_match_pairs_guided", "psx_match_pairs_guided_u8", "psx_match_pairs_guided_dev", "psx_match_pairs_guided_u8_dev",
     "psx_match_pairs_guided_many_u8", "psx_match_pairs_guided_many_u8_dev", "psx_guides_from_ransac",
@@ -117,6 +118,16 @@ PAIRS_MUTUAL = 1     # PSX_PAIRS_MUTUAL
 # psx_match_pair / psx_match_pair_u8 (16 bytes): one correspondence; byte distances are integers, INT_MAX = none
 PAIR_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4"), ("d1", "<f4"), ("d2", "<f4")])
 PAIR_U8_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4"), ("d1", "<i4"), ("d2", "<i4")])
+
+
+class ManyF32Plan(C.Structure):
+    """psx_many_f32_plan: what psx_match_pairs_many decides for the sizes of a call (path 1 scan, 2 prefilter, 0 nothing)"""
+    _fields_ = [("path", C.c_int), ("fwd_groups", C.c_int), ("bwd_groups", C.c_int), ("launches", C.c_int), ("scratch_bytes", C.c_longlong)]
+
+
+class ManyF32Info(C.Structure):
+    """psx_many_f32_info: the calling thread's last psx_match_pairs_many call"""
+    _fields_ = [("path", C.c_int), ("fell_back", C.c_int), ("launches", C.c_int), ("syncs", C.c_int)]
 
 
 class MatchOpts(C.Structure):
@@ -246,8 +257,10 @@ def lib():
             getattr(L, n).argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(MatchOpts), vp, C.c_int, ip]
         for n in ("psx_pairs_join", "psx_pairs_join_u8"):
             getattr(L, n).argtypes = [vp, vp, C.c_int, vp, C.c_int, C.POINTER(MatchOpts), vp, C.c_int, ip]
-        for n in ("psx_match_pairs_many_u8", "psx_match_pairs_many_u8_dev"):
+        for n in ("psx_match_pairs_many_u8", "psx_match_pairs_many_u8_dev", "psx_match_pairs_many", "psx_match_pairs_many_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, C.c_int, vp, vp, C.c_int, C.POINTER(MatchOpts), vp, C.c_int, vp, ip]
+        L.psx_match_many_f32_plan.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(ManyF32Plan)]
+        L.psx_match_many_f32_last.argtypes = [C.POINTER(ManyF32Info)]
         L.psx_match_many_plan.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, ip, vp, C.c_int, ip]
         L.psx_guide_allows.argtypes = [C.POINTER(Guide), vp, C.c_int, vp, C.c_int, vp]
         L.psx_desc_positions.argtypes = [C.c_int, vp, vp, C.c_int, vp]
@@ -553,11 +566,56 @@ def match_pairs_many_u8(left, rights, ratio=0.8, mutual=False, device=0, capacit
             L.psx_dev_free(device, p)
 
 
-def match_pairs_many_dev(left_ptr, l_len, right_ptrs, r_lens, out_ptr, capacity, ratio=0.8, mutual=False, device=0):
-    """psx_match_pairs_many_u8_dev on DEVICE pointers (e.g. tensor.data_ptr()): the concatenated records go into the
-    caller's device buffer at out_ptr (16-byte aligned, `capacity` records); returns (per-set counts, total count)."""
-    return _many_call(lib().psx_match_pairs_many_u8_dev, "psx_match_pairs_many_u8_dev", device, C.c_void_p(left_ptr), l_len,
+def match_pairs_many(left, rights, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs_many on host arrays: left (n,128) float32 against every (m_k,128) float32 array of `rights` in ONE
+    call.  Returns (list of per-set PAIR_DTYPE arrays -- set k's equals match_pairs(left, rights[k]), `right` indexing
+    rights[k] -- , per-set counts); with a capacity the list holds the first `capacity` records of the concatenation and
+    the counts are still the totals."""
+    L = lib()
+    left = np.ascontiguousarray(left, dtype=np.float32).reshape(-1, 128)
+    rights = [np.ascontiguousarray(r, dtype=np.float32).reshape(-1, 128) for r in rights]
+    bufs = []
+    try:
+        ptrs = _to_device(L, device, [left] + rights, bufs)
+        cap = len(left) * len(rights) if capacity is None else capacity
+        out = np.zeros((cap,), PAIR_DTYPE)
+        counts, n = _many_call(L.psx_match_pairs_many, "psx_match_pairs_many", device, ptrs[0], len(left), ptrs[1:],
+                               [len(r) for r in rights], out.ctypes.data_as(C.c_void_p) if cap else None, cap, ratio, mutual)
+        return split_sets(out[:min(n, cap)], counts), counts
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def match_pairs_many_dev(left_ptr, l_len, right_ptrs, r_lens, out_ptr, capacity, ratio=0.8, mutual=False, device=0, u8=True):
+    """psx_match_pairs_many_u8_dev (u8=False: psx_match_pairs_many_dev, float descriptors) on DEVICE pointers (e.g.
+    tensor.data_ptr()): the concatenated records go into the caller's device buffer at out_ptr (16-byte aligned,
+    `capacity` records); returns (per-set counts, total count)."""
+    name = "psx_match_pairs_many_u8_dev" if u8 else "psx_match_pairs_many_dev"
+    return _many_call(getattr(lib(), name), name, device, C.c_void_p(left_ptr), l_len,
                       list(right_ptrs), r_lens, C.c_void_p(out_ptr), capacity, ratio, mutual)
+
+
+def match_many_f32_plan(l_len, r_lens, mutual=False, mfma_enabled=True):
+    """psx_match_many_f32_plan: what psx_match_pairs_many decides for these sizes, as a dict (path, fwd_groups, bwd_groups,
+    launches, scratch_bytes).  No device."""
+    lens = np.ascontiguousarray(r_lens, dtype=np.int32)
+    out = ManyF32Plan()
+    rc = lib().psx_match_many_f32_plan(l_len, lens.ctypes.data_as(C.c_void_p) if len(lens) else None, len(lens),
+                                       PAIRS_MUTUAL if mutual else 0, 1 if mfma_enabled else 0, C.byref(out))
+    if rc != 0:
+        raise PopSiftError("psx_match_many_f32_plan failed (%d)" % rc)
+    return {n: int(getattr(out, n)) for n, _ in ManyF32Plan._fields_}
+
+
+def match_many_f32_last():
+    """psx_match_many_f32_last: the calling thread's last match_pairs_many / match_pairs_many_dev(u8=False) call as a dict
+    (path, fell_back, launches, syncs); zeros before any"""
+    out = ManyF32Info()
+    rc = lib().psx_match_many_f32_last(C.byref(out))
+    if rc != 0:
+        raise PopSiftError("psx_match_many_f32_last failed (%d)" % rc)
+    return {n: int(getattr(out, n)) for n, _ in ManyF32Info._fields_}
 
 
 def match_many_plan(l_len, r_lens, backward=False):

@@ -24,6 +24,7 @@
 // Further down: the exact byte matcher for one pair of sets (its device pieces: match_u8_core.h, shared with match_many.hip)
 // and the pair join (its compaction: wg_compact.h); the directed result's layout and the scratch buffers: match_scratch.h.
 #include "psx_internal.h"
+#include "match_f32_core.h"
 #include "match_join.h"
 #include "match_scratch.h"
 #include "match_u8_core.h"
@@ -37,22 +38,7 @@
 
 namespace {
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-struct Top2 { float d1, d2; int i1, i2; };
-
-// two smallest under (distance, index) lexicographic order == result of the reference's sequential scan
-__device__ __forceinline__ void top2_insert(Top2& t, float d, int i)
-{
-    if (d < t.d1) { t.d2 = t.d1; t.i2 = t.i1; t.d1 = d; t.i1 = i; }
-    else if (d < t.d2) { t.d2 = d; t.i2 = i; }
-}
-
-__device__ __forceinline__ v2f pk_fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-
-// Descriptors are permuted once so that the two partial sums computed together sit in one register /
-// SGPR pair: pair k = c*16 + m (component c of float4 m and of float4 m+16) = (v[4m+c], v[4(m+16)+c]).
-__device__ __forceinline__ int perm_src(int k, int half) { return 4 * ((k & 15) + 16 * half) + (k >> 4); }
+// v2f, Top2 / top2_insert, pk_fma2, the permuted layout (perm_src) and the operation tree (l2_tree): match_f32_core.h
 
 __global__ void k_match_permute(const float* __restrict__ src, int n, float* __restrict__ dst)
 {
@@ -61,32 +47,6 @@ __global__ void k_match_permute(const float* __restrict__ src, int n, float* __r
     const int d = i >> 6, k = i & 63;
     const float* s = src + (size_t)d * 128;
     reinterpret_cast<float2*>(dst)[i] = make_float2(s[perm_src(k, 0)], s[perm_src(k, 1)]);
-}
-
-// distance of this lane's left descriptor (64 permuted pairs) to the wave-uniform, permuted right
-// descriptor r: P_m = (p_m, p_{m+16}) for m = 0..15, two partial sums per packed instruction
-__device__ __forceinline__ float l2_tree(const v2f* l, const float* __restrict__ r)
-{
-    float a[16];
-#pragma unroll
-    for (int m = 0; m < 16; m++) {
-        const v2f rx = {r[2 * m], r[2 * m + 1]},           ry = {r[32 + 2 * m], r[32 + 2 * m + 1]};
-        const v2f rz = {r[64 + 2 * m], r[64 + 2 * m + 1]}, rw = {r[96 + 2 * m], r[96 + 2 * m + 1]};
-        const v2f x = l[m] - rx, y = l[16 + m] - ry, z = l[32 + m] - rz, w = l[48 + m] - rw;
-        v2f p = y * y;
-        p = pk_fma2(x, x, p);
-        p = pk_fma2(z, z, p);
-        p = pk_fma2(w, w, p);
-        a[m] = p.x + p.y;                                  // a_m = p_m + p_{m+16}
-    }
-    float b[8], c[4], d[2];
-#pragma unroll
-    for (int i = 0; i < 8; i++) b[i] = a[i] + a[i + 8];
-#pragma unroll
-    for (int i = 0; i < 4; i++) c[i] = b[i] + b[i + 4];
-#pragma unroll
-    for (int i = 0; i < 2; i++) d[i] = c[i] + c[i + 2];
-    return d[0] + d[1];
 }
 
 // grid (ceil(l_len/64), nchunks), 64 threads.  left: original layout; right_p: permuted copy.
@@ -163,26 +123,7 @@ __global__ void k_match_merge(const Top2* __restrict__ partial, int l_len, int n
 // bytes of a descriptor go into the same operand slot on both sides, so whatever k the hardware assigns to a slot, the
 // products pair up (the sum over k is what matters); C/D: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
 // ---------------------------------------------------------------------------------------------------------------------
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int MF_SEGS = 32;                  // candidate segments per left descriptor: one per (chunk of the right side, half wave) ...
-constexpr int MF_SEGCAP = 32;                // ... of this many slots: private to one lane of one workgroup, so appending needs no atomic
-constexpr int MF_CAP = MF_SEGS * MF_SEGCAP;  // (a returned global atomic per candidate made the scan wait ~1 us per tile and column set)
-constexpr int MF_TILE = 32;                  // right descriptors per MFMA tile
-constexpr int MF_SUB = 2;                    // MFMA tiles per staged block (= per barrier)
-constexpr int MF_ROW = 272;                  // bytes per staged right descriptor: 256 + 16 (rows 4 banks apart: conflict-free b128 reads)
-constexpr int MF_SEED = 2048;                // right descriptors of the seeding pass ...
-constexpr int MF_SEEDCH = 8;                 // ... in this many chunks (workgroups per 256 left descriptors)
-constexpr int MF_MAXSLOTS = 64;              // the largest squared norm of the right side is kept in 64 slots (same-address atomics serialise)
-
-__device__ __forceinline__ unsigned short to_f16(float f)
-{
-    const _Float16 h = (_Float16)f;                                                // v_cvt_f16_f32: round to nearest even
-    unsigned short b; __builtin_memcpy(&b, &h, 2);
-    return b;
-}
+// the vector types, the MF_* constants, to_f16, match_scale and the margin E_l (match_margin): match_f32_core.h
 
 // squared norm of every descriptor and the largest one (bits of a non-negative float, 64 slots: same-address atomics serialise)
 // (both sides in one launch: blocks [0, blocks_a) take the first set, the others the second)
@@ -213,21 +154,6 @@ __global__ void k_match_norms(const float* __restrict__ src_a, int n_a, float* _
     if (q == 0) atomicMax(&s_max, __float_as_uint(mx));
     __syncthreads();
     if (threadIdx.x == 0) atomicMax(&maxbits[bid & (MF_MAXSLOTS - 1)], s_max);
-}
-
-// par[0] = 2^k, par[1] = -2 / 4^k, par[2] = Rmax^2, par[3] = M; *bad = 1 when the prefilter cannot be used
-__device__ __forceinline__ void match_scale(float l2, float r2, float* par, int* bad)
-{
-    const float m2 = fmaxf(l2, r2);
-    // finite, positive, and far enough from both ends of the float range for the squares below
-    if (!(l2 == l2) || !(r2 == r2) || !(m2 > 1e-30f) || !(m2 < 1e30f)) { *bad = 1; par[0] = 1.0f; par[1] = -2.0f; par[2] = 0.0f; par[3] = 0.0f; return; }
-    const float M = sqrtf(m2);
-    const int k = (int)floorf(log2f(16384.0f / M));
-    *bad = 0;
-    par[0] = ldexpf(1.0f, k);
-    par[1] = ldexpf(-2.0f, -2 * k);
-    par[2] = r2;
-    par[3] = M;
 }
 
 // f16 copy of every descriptor of both sides, scaled by 2^k (blocks [0, blocks_a): the first set).  Every block derives the
@@ -302,7 +228,7 @@ __global__ __launch_bounds__(256, 2) void k_match_mfma(const unsigned short* __r
 #pragma unroll
         for (int kk = 0; kk < 8; kk++) bfrag[c][kk] = *reinterpret_cast<const f16x8*>(lp + kk * 16);
         const float nl = ln2[lq];
-        const float E = 0.00197f * sqrtf(nl) * rmax + 2e-7f * bigM * (sqrtf(nl) + rmax) + 4e-5f * (nl + rmax2);
+        const float E = match_margin(nl, rmax, rmax2, bigM);
         twoE[c] = 2.0f * E * -inv;                      // the margin in D units (-inv > 0, a power of two: exact)
         // running LARGEST / second largest of D (= smallest / second smallest of s' = |r|^2 - 2 <l, r>; |l|^2 is the same for every
         // pair of a column).  The real pass starts both at the sample's second smallest s': "two values <= S exist" is all a
@@ -447,14 +373,7 @@ __global__ __launch_bounds__(256, 2) void k_match_mfma(const unsigned short* __r
 #undef MF_COMMIT
 #undef MF_LOAD_
 
-// (distance, index) lexicographic order: what the reference's sequential scan with strict '<' yields
-__device__ __forceinline__ bool lex_less(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
-__device__ __forceinline__ void top2_insert_lex(Top2& t, float d, int i)
-{
-    if (!(d == d)) return;                                   // NaN never passes the reference's '<'
-    if (lex_less(d, i, t.d1, t.i1)) { t.d2 = t.d1; t.i2 = t.i1; t.d1 = d; t.i1 = i; }
-    else if (lex_less(d, i, t.d2, t.i2)) { t.d2 = d; t.i2 = i; }
-}
+// lex_less / top2_insert_lex, the (distance, index) order of the reference's scan: match_f32_core.h
 
 // Exact distances of the candidates, one wave per left descriptor, one HALF WAVE per pair -- the reference's own shape
 // (l2_in_t0, features.cu:160-189: 32 threads, thread t takes floats 4t..4t+3, then shuffle_down 16, 8, 4, 2, 1): one

@@ -182,7 +182,7 @@ int match_pairs_guided_many(int device, const unsigned char* d_left, const float
     }
     hipLaunchKernelGGL(k_match_guided_many<false>, dim3((unsigned)(K * per_set)), dim3(256), 0, st, d_sets, d_blocks, d_left, lxy, l_len,
                        (int)per_set, static_cast<const float4*>(nullptr), d_fwd);
-    psx_many_join_queue(st, d_sets, d_fwd, l_len, d_bwd, (int)nb, (int)ntot, opts->ratio, mutual, static_cast<int*>(sc.buf[MS_GMANY_TOT]),
+    psx_many_join_queue<int>(st, d_sets, d_fwd, l_len, d_bwd, (int)nb, (int)ntot, opts->ratio, mutual, static_cast<int*>(sc.buf[MS_GMANY_TOT]),
                         out, cap, d_counts, d_total);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return PSX_ERR_HIP;
     const int n = *h_total;

@@ -269,7 +269,7 @@ int match_pairs_many(int device, const unsigned char* d_left, int l_len, const u
         hipLaunchKernelGGL(k_match_u8_many_merge, dim3((unsigned)g.nblocks), dim3(256), 0, st, d_sets, d_chunks, d_blocks, ps, K,
                            (size_t)0, d_partial, d_bwd);
     }
-    psx_many_join_queue(st, d_sets, d_fwd, l_len, d_bwd, (int)nb, (int)ntot, opts->ratio, mutual, d_tot, out, cap, d_counts, d_total);
+    psx_many_join_queue<int>(st, d_sets, d_fwd, l_len, d_bwd, (int)nb, (int)ntot, opts->ratio, mutual, d_tot, out, cap, d_counts, d_total);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return PSX_ERR_HIP;
     const int n = *h_total;
     if (n < 0 || n > all_pairs) return PSX_ERR_HIP;

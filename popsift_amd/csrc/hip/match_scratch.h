@@ -1,5 +1,5 @@
 // match_scratch.h -- what the matcher's translation units share (match.hip, match_guided.hip, match_many.hip,
-// match_guided_many.hip, ransac.hip, ransac_many.hip):
+// match_many_f32.hip, match_guided_many.hip, ransac.hip, ransac_many.hip):
 // the layout of a directed result, the per-thread scratch with its named buffers, and the runner of the pair join.
 // Internal to the HIP library.
 #pragma once
@@ -32,7 +32,8 @@ __device__ __forceinline__ int psx_directed_best(const int* __restrict__ res, si
 
 // The buffers of a MatchScratch.  A buffer belongs to ONE use: calls queue work without waiting for the stream, so two
 // features sharing a buffer would alias under queued work.  F32: psx_match / psx_match_pairs, U8: psx_match_u8 /
-// psx_match_pairs_u8 (match.hip); GUIDED: match_guided.hip; MANY: the one-to-many search (match_many.hip); GMANY: the guided
+// psx_match_pairs_u8 (match.hip); GUIDED: match_guided.hip; MANY: the one-to-many search (match_many.hip), MANYF: its float form
+// (match_many_f32.hip); GMANY: the guided
 // one-to-many search (match_guided_many.hip).  RANSAC: ransac.hip AND the batched ransac_many.hip, which adds RMANY for its
 // tables: every call of either ends synchronised, so the two never have work queued on a thread's scratch at once.
 enum MatchSlot {
@@ -72,6 +73,17 @@ enum MatchSlot {
     MS_GMANY_FWD,        // the forward direction's results of all sets
     MS_GMANY_BWD,        // the backward direction's
     MS_GMANY_TOT,        // the join's per-workgroup totals and their offsets
+    MS_MANYF_TABLES,     // the float one-to-many search (match_many_f32.hip): the set / chunk / block tables
+    MS_MANYF_STATE,      // the blocks' largest norms, the prefilter's parameters and its flag
+    MS_MANYF_PERM,       // the scan: the permuted copy of every inner row
+    MS_MANYF_PARTIAL,    // the scan: the per-chunk top-2
+    MS_MANYF_F16,        // the prefilter: the f16 copy of every row of all sets
+    MS_MANYF_NORMS,      // the prefilter: their squared norms
+    MS_MANYF_CAND_CT,    // the prefilter: the candidate counts per (outer row, chunk, half wave)
+    MS_MANYF_CAND,       // the prefilter: the candidates
+    MS_MANYF_FWD,        // the forward direction's results of all sets
+    MS_MANYF_BWD,        // the backward direction's
+    MS_MANYF_TOT,        // the join's per-workgroup totals and their offsets
     MS_NBUF
 };
 

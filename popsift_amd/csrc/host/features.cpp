@@ -673,6 +673,70 @@ std::vector<std::vector<Match>> FeaturesDev::matchPairsMany( const std::vector<F
     return out;
 }
 
+// FeaturesDev::matchPairsManyFloat: psx_match_pairs_many on the objects' own float descriptors -- nothing is quantised,
+// nothing is copied, ONE matching call for all of them; the concatenated list is cut at the per-set counts and mapped
+// through the reverse maps as matchPairs does
+std::vector<std::vector<Match>> FeaturesDev::matchPairsManyFloat( const std::vector<FeaturesDev*>& others, const MatchOptions& opts )
+{
+    const char* who = "FeaturesDev::matchPairsManyFloat";
+    for( FeaturesDev* o : others ) {
+        if( o == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
+        if( o->_device != _device ) {
+            std::ostringstream ss;
+            ss << who << ": the objects live on different devices (" << _device << " and " << o->_device << ")";
+            fatal( __FILE__, __LINE__, ss.str() );
+        }
+    }
+    if( opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": float descriptors only (use matchPairsMany for MatchOptions::bytes)" );
+    const int K = (int)others.size();
+    const int l_len = getDescriptorCount();
+    std::vector<std::vector<Match>> out( others.size() );
+    bool any = false;
+    for( FeaturesDev* o : others ) any = any || o->getDescriptorCount() > 0;
+    if( l_len <= 0 || !any ) return out;
+    psx_match_opts po;
+    po.ratio = opts.ratio;
+    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
+    std::vector<const float*> ptrs( K, nullptr );
+    std::vector<int> lens( K, 0 ), counts( K, 0 );
+    for( int k = 0; k < K; k++ ) {
+        const int r_len = others[k]->getDescriptorCount();
+        if( r_len <= 0 ) continue;
+        lens[k] = r_len;
+        ptrs[k] = (const float*)others[k]->_ori;
+    }
+    // at most l_len pairs per set exist (a product above INT_MAX is the call's to refuse)
+    const long long room = (long long)K * l_len;
+    std::vector<psx_match_pair> pf( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
+    int count = 0;
+    const int rc = psx_match_pairs_many( _device, (const float*)_ori, l_len, ptrs.data(), lens.data(), K, &po,
+                                         pf.data(), (int)pf.size(), counts.data(), &count );
+    if( rc != PSX_OK ) {
+        std::ostringstream ss;
+        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    std::vector<int> l_fem( l_len );
+    if( psx_dev_read( _device, l_fem.data(), _rev, (size_t)l_len * sizeof(int) ) != PSX_OK )
+        fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
+    size_t at = 0;
+    for( int k = 0; k < K; k++ ) {
+        if( counts[k] <= 0 ) continue;
+        std::vector<int> r_fem( lens[k] );
+        if( psx_dev_read( _device, r_fem.data(), others[k]->_rev, (size_t)lens[k] * sizeof(int) ) != PSX_OK )
+            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
+        out[k].resize( counts[k] );
+        for( int q = 0; q < counts[k]; q++, at++ ) {
+            Match& m = out[k][q];
+            m.left_descriptor = pf[at].left; m.right_descriptor = pf[at].right;
+            m.distance = pf[at].d1; m.second_distance = pf[at].d2;
+            m.left_feature  = l_fem[m.left_descriptor];
+            m.right_feature = r_fem[m.right_descriptor];
+        }
+    }
+    return out;
+}
+
 // FeaturesDev::matchPairsGuidedMany: psx_match_pairs_guided_many_u8 on this object's bytes and positions and every other
 // object's that is neither empty nor skipped -- each side quantised and its positions gathered once, ONE matching call for
 // all of them; the concatenated list is cut at the per-set counts and mapped through the reverse maps as matchPairs does

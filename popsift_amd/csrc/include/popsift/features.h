@@ -217,6 +217,11 @@ public:
     /// descriptors only -- every side is quantised once on the device, as matchPairs does with MatchOptions::bytes.
     /// Throws as matchPairs for a null entry or an object on another device, and for opts.bytes == false.
     std::vector<std::vector<Match>> matchPairsMany( const std::vector<FeaturesDev*>& others, const MatchOptions& opts );
+    /// matchPairsMany on the objects' FLOAT descriptors (psx_match_pairs_many): no quantisation, no copies; element k
+    /// equals matchPairs( others[k], opts ) field by field, and the estimate*Many functions accept the lists unchanged.
+    /// Throws as matchPairs for a null entry or an object on another device, and for opts.bytes == true (use
+    /// matchPairsMany).
+    std::vector<std::vector<Match>> matchPairsManyFloat( const std::vector<FeaturesDev*>& others, const MatchOptions& opts = MatchOptions() );
     /// matchPairsGuided against many objects in ONE device call (psx_match_pairs_guided_many_u8: one synchronisation, a
     /// number of launches that does not grow with others.size()), others[k] under guides[k]: element k equals
     /// matchPairsGuided( others[k], guides[k], opts ) with opts.bytes.  A guide of kind MatchGuide::None
