@@ -406,6 +406,62 @@ int psx_match_many_plan(int l_len, const int* r_lens, int n_sets, int backward,
                         psx_many_chunk* chunks, int chunk_capacity, int* chunk_count,
                         psx_many_block* blocks, int block_capacity, int* block_count);
 
+/* ---- a list of view pairs over N descriptor sets (byte descriptors) ---------------------------
+ * A structure-from-motion or loop-closure front end has N views and an EDGE LIST -- all pairs, a sliding window, a
+ * retrieval shortlist per view --, not one left view.  n_edges ordered pairs of sets matched in ONE call: one
+ * synchronisation and a number of kernel launches that grows neither with n_edges nor with n_sets; every set named by an
+ * edge gets its norms once.  INTEGRATION.md ("A list of view pairs") has the words and the measured cost.
+ * d_sets / lens: HOST arrays of n_sets entries, d_sets[s] a DEVICE pointer to lens[s] descriptors of 128 bytes, 16-byte
+ * aligned (separate allocations, slices of one buffer, or the same pointer more than once); edges: HOST array of n_edges
+ * {left, right} indices into the set array; edge_counts (n_edges ints) and count: HOST memory.
+ * With P_e = the list psx_match_pairs_u8 returns for (d_sets[edges[e].left], d_sets[edges[e].right], opts) at unlimited
+ * capacity, bit for bit:
+ *   - the result is the concatenation P_0, P_1, ..., P_{n_edges-1} in the order of the edge list, which is neither sorted
+ *     nor deduplicated: a duplicate edge returns the same list each time, (a, b) and (b, a) are two edges with two lists;
+ *   - `left` and `right` index the edge's own two sets;
+ *   - an edge with left == right is the single call with the same pointer on both sides (every row finds itself at
+ *     distance 0); nothing is special-cased;
+ *   - edge_counts[e] = |P_e|, *count their sum: always the totals.  The first min(*count, capacity) records are written --
+ *     the cut may fall inside an edge --, nothing at or past capacity; capacity = 0 with a NULL output asks "how many?";
+ *   - an edge with an empty side contributes nothing and has count 0.  Only sets named by an edge whose two sides are both
+ *     non-empty are read.
+ * When the edge list is grouped by `left`, the records of one left view's edges are contiguous: that slice, with its
+ * edge_counts, is exactly what psx_match_pairs_many_u8 returns for that star, and goes into psx_ransac_*_many_dev and
+ * psx_match_pairs_guided_many_u8_dev unchanged, offset into the device buffer.
+ * n_edges = 0, or a call whose every edge has an empty side, gives zero counts and PSX_OK without touching a device.
+ * PSX_ERR_INVALID, with nothing touched and before any device call: everything psx_match_pairs_u8 refuses about opts,
+ * output, capacity and count; n_sets < 0 or n_edges < 0; d_sets or lens NULL with n_sets > 0; edges or edge_counts NULL
+ * with n_edges > 0; a negative length; a NULL set pointer with a non-zero length; an edge index outside [0, n_sets) --
+ * every edge is checked before anything runs, so n_sets = 0 admits no edge --; the sum over the edges of lens[left] (the
+ * number of pairs that can exist) or of lens[right] (the backward rows) above INT_MAX.  PSX_ERR_NOMEM where a grid or a
+ * table would not fit an int.  Scratch (psx_match_release) and thread safety as for psx_match_u8.  Synchronous, with
+ * exactly one stream synchronisation per call.  There is no float form, and no guided or RANSAC call over an edge list
+ * with varying left views: the grouped-by-left slices above cover those. */
+typedef struct psx_view_edge { int left, right; } psx_view_edge;   /* indices into the set array */
+int psx_match_pairs_graph_u8(int device, const unsigned char* const* d_sets, const int* lens, int n_sets,
+                             const psx_view_edge* edges, int n_edges, const psx_match_opts* opts,
+                             psx_match_pair_u8* host_pairs, int capacity, int* edge_counts, int* count);
+/* the list stays in HBM: d_pairs is a DEVICE pointer, 16-byte aligned; edge_counts and count are still HOST memory */
+int psx_match_pairs_graph_u8_dev(int device, const unsigned char* const* d_sets, const int* lens, int n_sets,
+                                 const psx_view_edge* edges, int n_edges, const psx_match_opts* opts,
+                                 psx_match_pair_u8* d_pairs, int capacity, int* edge_counts, int* count);
+
+/* What the call above plans for these sizes, on the HOST: no device, no context (csrc/hip/match_graph_plan.h, the
+ * functions the library itself plans with).  flags: psx_match_opts.flags.  Every referenced set (named by an edge whose
+ * two sides are non-empty) is cut ONCE per call into outer blocks of 256 rows and inner chunks of whole tiles, at most
+ * chunk_len <= 512 rows; the forward work items of edge e are blocks(left_e) x chunks(right_e), the backward ones (with
+ * PSX_PAIRS_MUTUAL only) blocks(right_e) x chunks(left_e); one workgroup per item.  fwd_groups / bwd_groups: the runs of
+ * whole edges whose per-chunk partials fit 256 MiB (a single edge above it is a group of its own); join_workgroups: the sum
+ * over the edges of ceil(lens[left] / 256); launches: 1 (norms) + 2 per group + 3 (join), 0 when nothing runs;
+ * scratch_bytes: the partials of the largest group.  PSX_ERR_INVALID as above for the sets and the edges, for unknown
+ * flag bits, out == NULL. */
+typedef struct psx_graph_plan_info { int referenced_sets, blocks, chunks, chunk_len;
+                                     int fwd_items, bwd_items, fwd_groups, bwd_groups;
+                                     int join_workgroups, launches;
+                                     long long scratch_bytes; } psx_graph_plan_info;
+int psx_match_graph_plan(const int* lens, int n_sets, const psx_view_edge* edges, int n_edges, int flags,
+                         psx_graph_plan_info* out);
+
 /* ---- one descriptor set against many (float descriptors) -------------------------------------
  * psx_match_pairs_many_u8's contract, word for word, with psx_match_pairs in place of psx_match_pairs_u8: d_left is a
  * DEVICE pointer to l_len descriptors of 128 floats, d_rights[k] one to r_lens[k] descriptors (d_rights / r_lens: HOST

@@ -98,6 +98,7 @@ SYMBOLS = [
     "psx_match_opts_default", "psx_match_pairs", "psx_match_pairs_u8", "psx_match_pairs_dev", "psx_match_pairs_u8_dev",
     "psx_pairs_join", "psx_pairs_join_u8",
     "psx_match_pairs_many_u8", "psx_match_pairs_many_u8_dev", "psx_match_many_plan",
+    "psx_match_pairs_graph_u8", "psx_match_pairs_graph_u8_dev", "psx_match_graph_plan",
     "psx_match_pairs_many", "psx_match_pairs_many_dev", "psx_match_many_f32_plan", "psx_match_many_f32_last",
     "psx_guide_allows", "psx_desc_positions", "psx_match_guided", "psx_match_guided_u8",
     "psx_match_pairs_guided", "psx_match_pairs_guided_u8", "psx_match_pairs_guided_dev", "psx_match_pairs_guided_u8_dev",
@@ -123,6 +124,13 @@ PAIR_U8_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4"), ("d1", "<i4"), ("d2
 class ManyF32Plan(C.Structure):
     """psx_many_f32_plan: what psx_match_pairs_many decides for the sizes of a call (path 1 scan, 2 prefilter, 0 nothing)"""
     _fields_ = [("path", C.c_int), ("fwd_groups", C.c_int), ("bwd_groups", C.c_int), ("launches", C.c_int), ("scratch_bytes", C.c_longlong)]
+
+
+class GraphPlanInfo(C.Structure):
+    """psx_graph_plan_info: what psx_match_pairs_graph_u8 plans for the sizes of a call"""
+    _fields_ = [("referenced_sets", C.c_int), ("blocks", C.c_int), ("chunks", C.c_int), ("chunk_len", C.c_int),
+                ("fwd_items", C.c_int), ("bwd_items", C.c_int), ("fwd_groups", C.c_int), ("bwd_groups", C.c_int),
+                ("join_workgroups", C.c_int), ("launches", C.c_int), ("scratch_bytes", C.c_longlong)]
 
 
 class ManyF32Info(C.Structure):
@@ -262,6 +270,9 @@ def lib():
         L.psx_match_many_f32_plan.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(ManyF32Plan)]
         L.psx_match_many_f32_last.argtypes = [C.POINTER(ManyF32Info)]
         L.psx_match_many_plan.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, ip, vp, C.c_int, ip]
+        for n in ("psx_match_pairs_graph_u8", "psx_match_pairs_graph_u8_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, C.c_int, C.POINTER(MatchOpts), vp, C.c_int, vp, ip]
+        L.psx_match_graph_plan.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(GraphPlanInfo)]
         L.psx_guide_allows.argtypes = [C.POINTER(Guide), vp, C.c_int, vp, C.c_int, vp]
         L.psx_desc_positions.argtypes = [C.c_int, vp, vp, C.c_int, vp]
         for n in ("psx_match_guided", "psx_match_guided_u8"):
@@ -633,6 +644,74 @@ def match_many_plan(l_len, r_lens, backward=False):
     if rc != 0:
         raise PopSiftError("psx_match_many_plan failed (%d)" % rc)
     return chunks, blocks
+
+
+def _graph_edges(edges):
+    """an edge list as the (n, 2) int32 array of psx_view_edge records"""
+    e = np.ascontiguousarray(edges, dtype=np.int32)
+    return e.reshape(-1, 2)
+
+
+def _graph_call(fn, name, device, set_ptrs, lens, edges, out_ptr, capacity, ratio, mutual):
+    """One edge-list call on device pointers: (per-edge counts (n_edges,) int32, total count)"""
+    k = len(lens)
+    ptrs = (C.c_void_p * max(k, 1))(*[p.value if isinstance(p, C.c_void_p) else p for p in set_ptrs])
+    la = np.ascontiguousarray(lens, dtype=np.int32)
+    ea = _graph_edges(edges)
+    counts = np.full((len(ea),), -1, np.int32)
+    n = C.c_int(-1)
+    o = match_opts(ratio, mutual)
+    rc = fn(device, ptrs if k else None, la.ctypes.data_as(C.c_void_p) if k else None, k,
+            ea.ctypes.data_as(C.c_void_p) if len(ea) else None, len(ea), C.byref(o), out_ptr, capacity,
+            counts.ctypes.data_as(C.c_void_p) if len(ea) else None, C.byref(n))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    return counts, n.value
+
+
+def match_pairs_graph_u8(sets, edges, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs_graph_u8 on host arrays: `sets` are (n_s,128) uint8 arrays, `edges` (left, right) index pairs into
+    them, all matched in ONE call.  Returns (list of per-edge PAIR_U8_DTYPE arrays -- edge e's equals
+    match_pairs_u8(sets[left], sets[right]), in the order of the edge list --, per-edge counts); with a capacity the list
+    holds the first `capacity` records of the concatenation and the counts are still the totals."""
+    L = lib()
+    sets = [np.ascontiguousarray(s, dtype=np.uint8).reshape(-1, 128) for s in sets]
+    ea = _graph_edges(edges)
+    bufs = []
+    try:
+        ptrs = _to_device(L, device, sets, bufs) if sets else []
+        lens = [len(s) for s in sets]
+        ok = all(0 <= a < len(sets) and 0 <= b < len(sets) for a, b in ea)
+        cap = (sum(lens[a] for a, _ in ea) if ok else 0) if capacity is None else capacity
+        out = np.zeros((cap,), PAIR_U8_DTYPE)
+        counts, n = _graph_call(L.psx_match_pairs_graph_u8, "psx_match_pairs_graph_u8", device, ptrs, lens, ea,
+                                out.ctypes.data_as(C.c_void_p) if cap else None, cap, ratio, mutual)
+        return split_sets(out[:min(n, cap)], counts), counts
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def match_pairs_graph_dev(ptrs, lens, edges, out_ptr, capacity, ratio=0.8, mutual=False, device=0):
+    """psx_match_pairs_graph_u8_dev on DEVICE pointers (e.g. tensor.data_ptr()): the concatenated records go into the
+    caller's device buffer at out_ptr (16-byte aligned, `capacity` records); returns (per-edge counts, total count).  With
+    the edge list grouped by left, a left view's slice of the buffer and of the counts is what match_pairs_many_dev
+    leaves for that star: ransac_*_many_dev and match_pairs_guided_many_dev take it unchanged."""
+    return _graph_call(lib().psx_match_pairs_graph_u8_dev, "psx_match_pairs_graph_u8_dev", device, list(ptrs), lens, edges,
+                       C.c_void_p(out_ptr), capacity, ratio, mutual)
+
+
+def match_graph_plan(lens, edges, mutual=False):
+    """psx_match_graph_plan: what psx_match_pairs_graph_u8 plans for these sizes, as a dict (referenced_sets, blocks, chunks,
+    chunk_len, fwd_items, bwd_items, fwd_groups, bwd_groups, join_workgroups, launches, scratch_bytes).  No device."""
+    la = np.ascontiguousarray(lens, dtype=np.int32)
+    ea = _graph_edges(edges)
+    out = GraphPlanInfo()
+    rc = lib().psx_match_graph_plan(la.ctypes.data_as(C.c_void_p) if len(la) else None, len(la),
+                                    ea.ctypes.data_as(C.c_void_p) if len(ea) else None, len(ea), PAIRS_MUTUAL if mutual else 0, C.byref(out))
+    if rc != 0:
+        raise PopSiftError("psx_match_graph_plan failed (%d)" % rc)
+    return {n: int(getattr(out, n)) for n, _ in GraphPlanInfo._fields_}
 
 
 def pairs_join(fwd_match, fwd_dist, bwd_match, r_len, ratio=0.8, mutual=False, capacity=None):

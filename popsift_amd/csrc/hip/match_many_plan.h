@@ -45,11 +45,10 @@ inline int psx_many_chunk_len(const int* lens, int n, long long outer_blocks)
     return (int)len;
 }
 
-// chunks of a side: every set is cut into ceil(len / chunk_len) chunks of equal length (whole tiles), so a set slightly
-// longer than chunk_len gives two halves, not one full chunk and a sliver
-inline long long psx_many_chunks(const int* lens, int n, long long outer_blocks, psx_many_chunk* out, long long cap)
+// chunks of a side at a given chunk length (whole tiles, <= 512): every set is cut into ceil(len / target) chunks of equal
+// length (whole tiles), so a set slightly longer than target gives two halves, not one full chunk and a sliver
+inline long long psx_many_chunks_of(const int* lens, int n, int target, psx_many_chunk* out, long long cap)
 {
-    const int target = psx_many_chunk_len(lens, n, outer_blocks);
     long long c = 0;
     for (int s = 0; s < n; s++) {
         const long long len = lens[s];
@@ -63,6 +62,12 @@ inline long long psx_many_chunks(const int* lens, int n, long long outer_blocks,
             }
     }
     return c;
+}
+
+// chunks of a side whose other side has outer_blocks blocks: at the length psx_many_chunk_len chooses
+inline long long psx_many_chunks(const int* lens, int n, long long outer_blocks, psx_many_chunk* out, long long cap)
+{
+    return psx_many_chunks_of(lens, n, psx_many_chunk_len(lens, n, outer_blocks), out, cap);
 }
 
 // what every one-to-many entry point refuses about its sets, before anything else is looked at

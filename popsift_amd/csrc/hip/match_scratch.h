@@ -1,5 +1,5 @@
 // match_scratch.h -- what the matcher's translation units share (match.hip, match_guided.hip, match_many.hip,
-// match_many_f32.hip, match_guided_many.hip, ransac.hip, ransac_many.hip):
+// match_many_f32.hip, match_guided_many.hip, match_graph.hip, ransac.hip, ransac_many.hip):
 // the layout of a directed result, the per-thread scratch with its named buffers, and the runner of the pair join.
 // Internal to the HIP library.
 #pragma once
@@ -34,7 +34,7 @@ __device__ __forceinline__ int psx_directed_best(const int* __restrict__ res, si
 // features sharing a buffer would alias under queued work.  F32: psx_match / psx_match_pairs, U8: psx_match_u8 /
 // psx_match_pairs_u8 (match.hip); GUIDED: match_guided.hip; MANY: the one-to-many search (match_many.hip), MANYF: its float form
 // (match_many_f32.hip); GMANY: the guided
-// one-to-many search (match_guided_many.hip).  RANSAC: ransac.hip AND the batched ransac_many.hip, which adds RMANY for its
+// one-to-many search (match_guided_many.hip); GRAPH: the pair search over an edge list (match_graph.hip).  RANSAC: ransac.hip AND the batched ransac_many.hip, which adds RMANY for its
 // tables: every call of either ends synchronised, so the two never have work queued on a thread's scratch at once.
 enum MatchSlot {
     MS_F32_PARTIAL,      // the exact scan's per-chunk top-2
@@ -84,6 +84,12 @@ enum MatchSlot {
     MS_MANYF_FWD,        // the forward direction's results of all sets
     MS_MANYF_BWD,        // the backward direction's
     MS_MANYF_TOT,        // the join's per-workgroup totals and their offsets
+    MS_GRAPH_TABLES,     // the pair search over an edge list (match_graph.hip): the set / edge / chunk / item / block / {edge, row0} tables
+    MS_GRAPH_NORMS,      // the norms of the referenced sets
+    MS_GRAPH_PARTIAL,    // the per-chunk key pairs of one group of edges
+    MS_GRAPH_FWD,        // the forward direction's results of all edges
+    MS_GRAPH_BWD,        // the backward direction's
+    MS_GRAPH_TOT,        // the join's per-workgroup totals and their offsets
     MS_NBUF
 };
 

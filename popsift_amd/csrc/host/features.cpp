@@ -673,6 +673,93 @@ std::vector<std::vector<Match>> FeaturesDev::matchPairsMany( const std::vector<F
     return out;
 }
 
+// FeaturesDev::matchPairsGraph: psx_match_pairs_graph_u8 on the bytes of every view an edge names -- each quantised once
+// for the whole call, ONE matching call for all edges; the concatenated list is cut at the per-edge counts and mapped
+// through the two views' reverse maps as matchPairs does
+std::vector<std::vector<Match>> FeaturesDev::matchPairsGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                              const MatchOptions& opts )
+{
+    const char* who = "FeaturesDev::matchPairsGraph";
+    const int N = (int)views.size(), E = (int)edges.size();
+    std::vector<char> named( views.size(), 0 );
+    for( const std::pair<int,int>& e : edges ) {
+        if( e.first < 0 || e.first >= N || e.second < 0 || e.second >= N ) {
+            std::ostringstream ss;
+            ss << who << ": edge (" << e.first << ", " << e.second << ") out of range (" << N << " views)";
+            fatal( __FILE__, __LINE__, ss.str() );
+        }
+        named[e.first] = named[e.second] = 1;
+    }
+    int device = -1;
+    for( int v = 0; v < N; v++ ) {
+        if( !named[v] ) continue;
+        if( views[v] == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
+        if( device < 0 ) device = views[v]->_device;
+        if( views[v]->_device != device ) {
+            std::ostringstream ss;
+            ss << who << ": the objects live on different devices (" << device << " and " << views[v]->_device << ")";
+            fatal( __FILE__, __LINE__, ss.str() );
+        }
+    }
+    if( !opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": the edge-list form is byte-only (set MatchOptions::bytes)" );
+    std::vector<std::vector<Match>> out( edges.size() );
+    std::vector<int> lens( views.size(), 0 );
+    for( int v = 0; v < N; v++ ) if( named[v] && views[v]->getDescriptorCount() > 0 ) lens[v] = views[v]->getDescriptorCount();
+    long long room = 0;                                      // at most lens[left] pairs per edge exist
+    std::vector<char> used( views.size(), 0 );               // named by an edge with two non-empty sides: only these are quantised
+    for( const std::pair<int,int>& e : edges )
+        if( lens[e.first] > 0 && lens[e.second] > 0 ) { room += lens[e.first]; used[e.first] = used[e.second] = 1; }
+    if( room == 0 ) return out;
+    psx_match_opts po;
+    po.ratio = opts.ratio;
+    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
+    std::vector<void*> bufs( views.size(), nullptr );
+    std::vector<const unsigned char*> ptrs( views.size(), nullptr );
+    int rc = PSX_OK;
+    for( int v = 0; v < N && rc == PSX_OK; v++ ) {
+        if( !used[v] ) { lens[v] = 0; continue; }            // a view no live edge names is an empty set to the call
+        rc = psx_dev_alloc( device, (size_t)lens[v] * 128, &bufs[v] );
+        if( rc == PSX_OK ) rc = psx_quantize_desc( device, (const float*)views[v]->_ori, lens[v], (unsigned char*)bufs[v] );
+        ptrs[v] = (const unsigned char*)bufs[v];
+    }
+    std::vector<psx_view_edge> pe( edges.size() );
+    for( int e = 0; e < E; e++ ) { pe[e].left = edges[e].first; pe[e].right = edges[e].second; }
+    std::vector<psx_match_pair_u8> pb( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
+    std::vector<int> counts( edges.size(), 0 );
+    int count = 0;
+    if( rc == PSX_OK )
+        rc = psx_match_pairs_graph_u8( device, ptrs.data(), lens.data(), N, pe.data(), E, &po, pb.data(), (int)pb.size(), counts.data(), &count );
+    for( void* b : bufs ) psx_dev_free( device, b );
+    if( rc != PSX_OK ) {
+        std::ostringstream ss;
+        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    std::vector<std::vector<int>> fem( views.size() );       // every used view's reverse map, read once
+    for( int v = 0; v < N; v++ ) {
+        if( !used[v] ) continue;
+        fem[v].resize( lens[v] );
+        if( psx_dev_read( device, fem[v].data(), views[v]->_rev, (size_t)lens[v] * sizeof(int) ) != PSX_OK )
+            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
+    }
+    size_t at = 0;
+    for( int e = 0; e < E; e++ ) {
+        if( counts[e] <= 0 ) continue;
+        const std::vector<int>& l_fem = fem[pe[e].left];
+        const std::vector<int>& r_fem = fem[pe[e].right];
+        out[e].resize( counts[e] );
+        for( int q = 0; q < counts[e]; q++, at++ ) {
+            Match& m = out[e][q];
+            m.left_descriptor = pb[at].left; m.right_descriptor = pb[at].right;
+            m.distance        = pb[at].d1 == INT32_MAX ? INFINITY : (float)pb[at].d1;
+            m.second_distance = pb[at].d2 == INT32_MAX ? INFINITY : (float)pb[at].d2;
+            m.left_feature  = l_fem[m.left_descriptor];
+            m.right_feature = r_fem[m.right_descriptor];
+        }
+    }
+    return out;
+}
+
 // FeaturesDev::matchPairsManyFloat: psx_match_pairs_many on the objects' own float descriptors -- nothing is quantised,
 // nothing is copied, ONE matching call for all of them; the concatenated list is cut at the per-set counts and mapped
 // through the reverse maps as matchPairs does

@@ -8,6 +8,7 @@
 #include "sift_constants.h"
 
 #include <iostream>
+#include <utility>
 #include <vector>
 
 namespace popsift {
@@ -217,6 +218,14 @@ public:
     /// descriptors only -- every side is quantised once on the device, as matchPairs does with MatchOptions::bytes.
     /// Throws as matchPairs for a null entry or an object on another device, and for opts.bytes == false.
     std::vector<std::vector<Match>> matchPairsMany( const std::vector<FeaturesDev*>& others, const MatchOptions& opts );
+    /// matchPairs over a LIST OF VIEW PAIRS in ONE device call (psx_match_pairs_graph_u8: one synchronisation, a number of
+    /// launches that grows neither with edges.size() nor with views.size()): edges[e] = (left, right) indexes `views`,
+    /// element e equals views[left]->matchPairs( views[right], opts ) field by field, in the order of the list -- which
+    /// may name a pair twice, in both orders, or a view against itself.  Byte descriptors only; every referenced view is
+    /// quantised once for the whole call.  Throws as matchPairsMany (a null referenced entry, views on different devices,
+    /// opts.bytes == false), and for an edge index outside `views`.
+    static std::vector<std::vector<Match>> matchPairsGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                            const MatchOptions& opts );
     /// matchPairsMany on the objects' FLOAT descriptors (psx_match_pairs_many): no quantisation, no copies; element k
     /// equals matchPairs( others[k], opts ) field by field, and the estimate*Many functions accept the lists unchanged.
     /// Throws as matchPairs for a null entry or an object on another device, and for opts.bytes == true (use
