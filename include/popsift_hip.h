@@ -435,8 +435,8 @@ int psx_match_many_plan(int l_len, const int* r_lens, int n_sets, int backward,
  * every edge is checked before anything runs, so n_sets = 0 admits no edge --; the sum over the edges of lens[left] (the
  * number of pairs that can exist) or of lens[right] (the backward rows) above INT_MAX.  PSX_ERR_NOMEM where a grid or a
  * table would not fit an int.  Scratch (psx_match_release) and thread safety as for psx_match_u8.  Synchronous, with
- * exactly one stream synchronisation per call.  There is no float form, and no guided or RANSAC call over an edge list
- * with varying left views: the grouped-by-left slices above cover those. */
+ * exactly one stream synchronisation per call.  There is no float form.  The next two links over the same edge list,
+ * whatever its order: psx_ransac_*_graph* and psx_match_pairs_guided_graph_u8* ("A LIST OF VIEW PAIRS", below). */
 typedef struct psx_view_edge { int left, right; } psx_view_edge;   /* indices into the set array */
 int psx_match_pairs_graph_u8(int device, const unsigned char* const* d_sets, const int* lens, int n_sets,
                              const psx_view_edge* edges, int n_edges, const psx_match_opts* opts,
@@ -609,7 +609,7 @@ int psx_match_pairs_guided_u8_dev(int device, const unsigned char* d_left, const
  * runs; a NULL d_rights[k] or d_right_xys[k] for a set that is not skipped and has rows.  Scratch (psx_match_release) and
  * thread safety as for psx_match_u8.  Synchronous, with exactly one stream synchronisation per call.  Only the byte form
  * exists, as for the unguided one-to-many call. */
-#define PSX_GUIDE_NONE 0         /* in the *_many call only: this set is skipped */
+#define PSX_GUIDE_NONE 0         /* in the *_many and *_graph calls only: this set / edge is skipped */
 int psx_match_pairs_guided_many_u8(int device, const unsigned char* d_left, const float* d_left_xy, int l_len,
                                    const unsigned char* const* d_rights, const float* const* d_right_xys, const int* r_lens,
                                    int n_sets, const psx_guide* guides, const psx_match_opts* opts,
@@ -835,6 +835,116 @@ int psx_guides_from_ransac(const psx_ransac_result* results, int n_sets, int kin
 typedef struct psx_ransac_block { int set, first, end; } psx_ransac_block;
 int psx_ransac_many_plan(const int* set_counts, int n_sets, int min_pairs, int block_rows,
                          psx_ransac_block* blocks, int capacity, int* block_count);
+
+/* A LIST OF VIEW PAIRS IN ONE CALL: verify, then re-match.  psx_match_pairs_graph_u8* leaves the concatenation P_0 ..
+ * P_{E-1} of the edges' pair lists in the order of the edge list, and their counts.  The calls below are the other two
+ * links of match -> verify -> guided re-match for that list, whatever its order -- it need not be grouped by left view:
+ *   psx_ransac_*_graph*                   one model per edge;
+ *   psx_guides_from_ransac (above)        the E results as E guides, unchanged: n_sets = n_edges;
+ *   psx_match_pairs_guided_graph_u8*      every edge re-matched under its own guide.
+ * INTEGRATION.md ("Verify and re-match a list of view pairs") has the chain written out and the measured cost.
+ *
+ * RANSAC over an edge list.  The launch sequence of psx_ransac_*_many* with "set" read as "edge": 7 kernel launches and 1
+ * stream synchronisation without PSX_RANSAC_REFIT, 12 and 2 with it, whatever n_edges and n_sets are.
+ *   pairs        the concatenation, 16-byte records (host_pairs: HOST; d_pairs: DEVICE, 16-byte aligned), and
+ *   edge_counts  HOST array of n_edges counts: exactly what psx_match_pairs_graph_u8[_dev] left, passed on unchanged;
+ *   edges        HOST array of n_edges {left, right} indices into the set array;
+ *   d_xys, lens  HOST arrays of n_sets entries: d_xys[s] a DEVICE pointer to the lens[s] (x, y) pairs of view s, as
+ *                psx_desc_positions gives them, 8-byte aligned; edge e's records index d_xys[edges[e].left] with `left`
+ *                and d_xys[edges[e].right] with `right`;
+ *   opts         one tol, hypotheses = N, seed and flags for all edges: hypothesis h of edge e draws from its own n_e;
+ *   results      HOST array of n_edges results.
+ * With (result_e, I_e) = what the single call psx_ransac_<model>[_dev] returns at unlimited capacity for (P_e,
+ * d_xys[left_e], lens[left_e], d_xys[right_e], lens[right_e], opts), bit for bit: results[e] = result_e; the inlier output
+ * is the concatenation I_0 .. I_{E-1} in the order of the edge list, edge e's inliers starting at the sum of
+ * results[j].inliers for j < e; *count = the total; the first min(*count, capacity) records are written, nothing at or
+ * past capacity; capacity = 0 with a NULL output asks "how many?".  host_models (n_edges x N x 9 floats) and host_counts
+ * (n_edges x N ints) receive every edge's layers, either may be NULL.  The list is neither sorted nor deduplicated: a
+ * duplicate edge gives the same result twice, (a, b) and (b, a) are two edges, left == right is the single call with the
+ * same array on both sides.  An edge with fewer pairs than its model's minimum (4 / 8 / 3 / 2) yields the "no model"
+ * result, contributes nothing to the output and has zeros in its rows of the layers.  n_edges = 0, or all edges below the
+ * minimum, gives PSX_OK without touching a device.
+ * PSX_ERR_INVALID, with nothing touched and before any device call: everything psx_ransac_*_many* refuses, with edge_counts
+ * and n_edges in the place of set_counts and n_sets (a sum of counts, or n_edges * hypotheses, above 0x3fffffff among it);
+ * everything psx_match_pairs_graph_u8 refuses about lens, n_sets, edges and n_edges; d_xys NULL with n_sets > 0; a NULL
+ * d_xys[s] with lens[s] > 0, or under an edge that has pairs.  A pair index outside ITS OWN edge's left or right position
+ * array, in any edge that has a model to estimate, gives PSX_ERR_INVALID for the whole call and no inlier record is
+ * written; nothing is read out of bounds.  Scratch (psx_match_release) and thread safety as psx_ransac_*.  Synchronous. */
+int psx_ransac_homography_graph(int device, const void* host_pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                                const float* const* d_xys, const int* lens, int n_sets,
+                                const psx_ransac_opts* opts, psx_ransac_result* results,
+                                void* host_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_homography_graph_dev(int device, const void* d_pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                                    const float* const* d_xys, const int* lens, int n_sets,
+                                    const psx_ransac_opts* opts, psx_ransac_result* results,
+                                    void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_fundamental_graph(int device, const void* host_pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                                 const float* const* d_xys, const int* lens, int n_sets,
+                                 const psx_ransac_opts* opts, psx_ransac_result* results,
+                                 void* host_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_fundamental_graph_dev(int device, const void* d_pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                                     const float* const* d_xys, const int* lens, int n_sets,
+                                     const psx_ransac_opts* opts, psx_ransac_result* results,
+                                     void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_affine_graph(int device, const void* host_pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                            const float* const* d_xys, const int* lens, int n_sets,
+                            const psx_ransac_opts* opts, psx_ransac_result* results,
+                            void* host_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_affine_graph_dev(int device, const void* d_pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                                const float* const* d_xys, const int* lens, int n_sets,
+                                const psx_ransac_opts* opts, psx_ransac_result* results,
+                                void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_similarity_graph(int device, const void* host_pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                                const float* const* d_xys, const int* lens, int n_sets,
+                                const psx_ransac_opts* opts, psx_ransac_result* results,
+                                void* host_inliers, int capacity, int* count, float* host_models, int* host_counts);
+int psx_ransac_similarity_graph_dev(int device, const void* d_pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                                    const float* const* d_xys, const int* lens, int n_sets,
+                                    const psx_ransac_opts* opts, psx_ransac_result* results,
+                                    void* d_inliers, int capacity, int* count, float* host_models, int* host_counts);
+/* Host only, no device and no context: the loop over the single-list rule on host arrays (xys: n_sets HOST pointers), with
+ * the same argument checks; every pair index of every edge is checked before anything is written. */
+int psx_ransac_homography_graph_ref(const void* pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                                    const float* const* xys, const int* lens, int n_sets, const psx_ransac_opts* opts,
+                                    psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts);
+int psx_ransac_fundamental_graph_ref(const void* pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                                     const float* const* xys, const int* lens, int n_sets, const psx_ransac_opts* opts,
+                                     psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts);
+int psx_ransac_affine_graph_ref(const void* pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                                const float* const* xys, const int* lens, int n_sets, const psx_ransac_opts* opts,
+                                psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts);
+int psx_ransac_similarity_graph_ref(const void* pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                                    const float* const* xys, const int* lens, int n_sets, const psx_ransac_opts* opts,
+                                    psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts);
+
+/* Guided re-match over an edge list (byte descriptors).  One stream synchronisation and a number of kernel launches that
+ * grows neither with n_edges nor with n_sets: 4 without the cross-check, 6 with it, plus the table copy.
+ * d_sets, d_xys, lens: HOST arrays of n_sets entries, d_sets[s] / d_xys[s] DEVICE pointers to the lens[s] descriptors of
+ * 128 bytes (16-byte aligned) / (x, y) positions (8-byte aligned) of view s -- separate allocations, slices of one buffer,
+ * or the same pointer more than once; edges: HOST array of n_edges {left, right}; guides: HOST array of n_edges guides,
+ * guides[e] for EDGE e -- what psx_guides_from_ransac makes of the results of psx_ransac_*_graph*.
+ * With G_e = the list psx_match_pairs_guided_u8 returns at unlimited capacity for the two sets and position arrays of edge
+ * e under guides[e] and opts, bit for bit: the result is the concatenation G_0 .. G_{E-1} in the order of the edge list;
+ * edge_counts[e] = |G_e| (HOST array of n_edges ints), *count their sum: always the totals; the first min(*count,
+ * capacity) records are written -- the cut may fall inside an edge --, nothing at or past capacity; capacity = 0 with a
+ * NULL output asks "how many?".  An edge whose guide has kind == PSX_GUIDE_NONE is SKIPPED: its count is 0 and nothing of
+ * that edge is read (the rest of that guide is not looked at); so is an edge with an empty side.  The list is neither
+ * sorted nor deduplicated, left == right is the single call with the same arrays on both sides.
+ * n_edges = 0, or a call whose edges are all empty or skipped, gives zero counts and PSX_OK without touching a device.
+ * PSX_ERR_INVALID, with nothing touched and before any device call: everything psx_match_pairs_graph_u8 refuses (the sum
+ * over the edges of lens[left] or of lens[right] above INT_MAX among it); d_xys NULL with n_sets > 0; a NULL d_xys[s] with
+ * lens[s] > 0; guides NULL with n_edges > 0; any guide that is neither valid nor of kind 0 -- EVERY guide is checked before
+ * anything runs.  PSX_ERR_NOMEM where a grid would not fit an int.  Scratch (psx_match_release) and thread safety as for
+ * psx_match_u8.  Synchronous.  Only the byte form exists. */
+int psx_match_pairs_guided_graph_u8(int device, const unsigned char* const* d_sets, const float* const* d_xys,
+                                    const int* lens, int n_sets, const psx_view_edge* edges, int n_edges,
+                                    const psx_guide* guides, const psx_match_opts* opts,
+                                    psx_match_pair_u8* host_pairs, int capacity, int* edge_counts, int* count);
+/* the list stays in HBM: d_pairs is a DEVICE pointer, 16-byte aligned; edge_counts and count are still HOST memory */
+int psx_match_pairs_guided_graph_u8_dev(int device, const unsigned char* const* d_sets, const float* const* d_xys,
+                                        const int* lens, int n_sets, const psx_view_edge* edges, int n_edges,
+                                        const psx_guide* guides, const psx_match_opts* opts,
+                                        psx_match_pair_u8* d_pairs, int capacity, int* edge_counts, int* count);
 
 /* ---- caller-supplied keypoints ------------------------------------------------------------
  * Describing points the caller brings along instead of the ones the DoG detector finds (what OpenCV calls

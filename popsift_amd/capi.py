@@ -112,6 +112,11 @@ SYMBOLS = [
     "psx_similarity_fit", "psx_ransac_similarity_ref", "psx_ransac_similarity", "psx_ransac_similarity_dev",
     "psx_ransac_affine_many", "psx_ransac_affine_many_dev", "psx_ransac_affine_many_ref",
     "psx_ransac_similarity_many", "psx_ransac_similarity_many_dev", "psx_ransac_similarity_many_ref",
+    "psx_ransac_homography_graph", "psx_ransac_homography_graph_dev", "psx_ransac_homography_graph_ref",
+    "psx_ransac_fundamental_graph", "psx_ransac_fundamental_graph_dev", "psx_ransac_fundamental_graph_ref",
+    "psx_ransac_affine_graph", "psx_ransac_affine_graph_dev", "psx_ransac_affine_graph_ref",
+    "psx_ransac_similarity_graph", "psx_ransac_similarity_graph_dev", "psx_ransac_similarity_graph_ref",
+    "psx_match_pairs_guided_graph_u8", "psx_match_pairs_guided_graph_u8_dev",
     "psx_pyramid_plan", "psx_blur_grid_of",
 ]
 
@@ -174,6 +179,7 @@ class Guide(C.Structure):
 
 
 RANSAC_REFIT = 1         # PSX_RANSAC_REFIT
+RANSAC_MODELS = ("homography", "fundamental", "affine", "similarity")
 
 
 class RansacOpts(C.Structure):
@@ -299,6 +305,13 @@ def lib():
         for n in ("psx_ransac_homography_many_ref", "psx_ransac_fundamental_many_ref", "psx_ransac_affine_many_ref", "psx_ransac_similarity_many_ref"):
             getattr(L, n).argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(RansacOpts), vp, vp, C.c_int, ip, vp, vp]
         L.psx_ransac_many_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, ip]
+        for m in RANSAC_MODELS:
+            for n in ("psx_ransac_%s_graph" % m, "psx_ransac_%s_graph_dev" % m):
+                getattr(L, n).argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(RansacOpts), vp, vp, C.c_int, ip, vp, vp]
+            getattr(L, "psx_ransac_%s_graph_ref" % m).argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(RansacOpts), vp, vp, C.c_int, ip,
+                                                                   vp, vp]
+        for n in ("psx_match_pairs_guided_graph_u8", "psx_match_pairs_guided_graph_u8_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, C.POINTER(MatchOpts), vp, C.c_int, vp, ip]
         L.psx_pyramid_plan.argtypes = [C.c_int] * 4 + [vp] + [C.c_int] * 3 + [vp, C.c_int, ip]
         L.psx_blur_grid_of.argtypes = [C.c_int] * 3
         _LIB = L
@@ -1281,6 +1294,169 @@ def ransac_many_plan(set_counts, min_pairs, block_rows):
     if rc != 0:
         raise PopSiftError("psx_ransac_many_plan failed (%d)" % rc)
     return blocks
+
+
+def _ransac_graph_call(fn, name, pairs_ptr, edge_counts, edges, dtype, xy_ptrs, lens, opts, capacity, layers, out_ptr=None,
+                       kind=GUIDE_HOMOGRAPHY):
+    """One RANSAC call over an edge list: E pair lists behind one another, edge e on the position arrays xy_ptrs[left_e] and
+    xy_ptrs[right_e].  out_ptr None: the inliers come back in a host array.  Returns the dict of _ransac_many_call with one
+    entry per EDGE: results, count, for the host forms records and inliers, with layers models (E, N, 9) and counts (E, N)."""
+    ea = _graph_edges(edges)
+    E, k = len(ea), len(lens)
+    if len(edge_counts) != E:
+        raise ValueError("one pair list per edge")
+    ec = np.ascontiguousarray(edge_counts, dtype=np.int32)
+    la = np.ascontiguousarray(lens, dtype=np.int32)
+    ptrs = (C.c_void_p * max(k, 1))(*[p.value if isinstance(p, C.c_void_p) else p for p in xy_ptrs])
+    n = int(ec.sum())
+    cap = n if capacity is None else capacity
+    N = max(int(opts.hypotheses), 0)
+    res, cnt = (RansacResult * max(E, 1))(), C.c_int(-1)
+    out = np.zeros((cap,), dtype) if out_ptr is None else None
+    models = np.zeros((E, N, 9), np.float32) if layers else None
+    counts = np.zeros((E, N), np.int32) if layers else None
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    po = ptr(out) if out_ptr is None else (C.c_void_p(out_ptr) if cap else None)
+    rc = fn(pairs_ptr, ptr(ec), ptr(ea), E, ptrs if k else None, ptr(la), k, C.byref(opts), res if E else None, po, cap, C.byref(cnt),
+            ptr(models), ptr(counts))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    results = []
+    for i in range(E):
+        r = RansacResult.from_buffer_copy(res[i])
+        r.kind = kind
+        results.append(r)
+    got = dict(results=results, count=cnt.value)
+    if out is not None:
+        got["records"] = out[:min(cnt.value, cap)]
+        got["inliers"] = split_sets(got["records"], [r.inliers for r in results])
+    if layers:
+        got["models"], got["counts"] = models, counts
+    return got
+
+
+def ransac_graph_ref(pair_lists, edges, xys, opts=None, capacity=None, layers=False, model="homography"):
+    """psx_ransac_<model>_graph_ref: the loop over the single-list rule on host arrays, no device.  pair_lists: one
+    PAIR_DTYPE / PAIR_U8_DTYPE array per EDGE (what match_pairs_graph_u8 returns); edges: (left, right) indices into xys,
+    the views' (n_s, 2) position arrays.  Edge e's result equals ransac_<model>_ref(pair_lists[e], xys[left], xys[right])."""
+    L = lib()
+    pairs, edge_counts = _pair_lists(pair_lists)
+    xs = [_xy(x) for x in xys]
+    opts = opts or ransac_opts()
+    name, kind = _ransac_names(model)
+    return _ransac_graph_call(getattr(L, name + "_graph_ref"), name + "_graph_ref", pairs.ctypes.data_as(C.c_void_p) if pairs.size else None,
+                              edge_counts, edges, pairs.dtype, [x.ctypes.data if x.size else None for x in xs], [len(x) for x in xs], opts,
+                              capacity, layers, kind=kind)
+
+
+def ransac_graph(pair_lists, edges, xys, opts=None, device=0, capacity=None, layers=False, model="homography"):
+    """psx_ransac_<model>_graph on host arrays (the positions go through device buffers): the E pair lists of an edge list
+    verified in ONE call; edge e's result and inliers equal ransac_<model>(pair_lists[e], xys[left], xys[right], opts)."""
+    L = lib()
+    pairs, edge_counts = _pair_lists(pair_lists)
+    xs = [_xy(x) for x in xys]
+    opts = opts or ransac_opts()
+    bufs = []
+    try:
+        ptrs = _to_device(L, device, xs, bufs) if xs else []
+        name, kind = _ransac_names(model)
+        fn = lambda *a: getattr(L, name + "_graph")(device, *a)
+        return _ransac_graph_call(fn, name + "_graph", pairs.ctypes.data_as(C.c_void_p) if pairs.size else None, edge_counts, edges, pairs.dtype,
+                                  ptrs, [len(x) for x in xs], opts, capacity, layers, kind=kind)
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def ransac_graph_dev(pairs_ptr, edge_counts, edges, xy_ptrs, lens, out_ptr, capacity, opts=None, device=0, layers=False, model="homography"):
+    """psx_ransac_<model>_graph_dev on DEVICE pointers: pairs_ptr and edge_counts are what match_pairs_graph_dev left and
+    returned, xy_ptrs / lens the views' position arrays; the concatenated inlier records are written in device memory
+    (16-byte aligned, `capacity` records).  Returns a dict: results, count, and with layers the per-edge models and counts."""
+    L = lib()
+    opts = opts or ransac_opts()
+    name, kind = _ransac_names(model)
+    fn = lambda *a: getattr(L, name + "_graph_dev")(device, *a)
+    return _ransac_graph_call(fn, name + "_graph_dev", C.c_void_p(pairs_ptr) if pairs_ptr else None, edge_counts, edges, None, list(xy_ptrs),
+                              lens, opts, capacity, layers, out_ptr=out_ptr or 0, kind=kind)
+
+
+def _ransac_graph_forms(model):
+    """ransac_<model>_graph, _graph_dev and _graph_ref: the three functions above with the model fixed"""
+    def host(pair_lists, edges, xys, opts=None, device=0, capacity=None, layers=False):
+        return ransac_graph(pair_lists, edges, xys, opts, device, capacity, layers, model=model)
+
+    def dev(pairs_ptr, edge_counts, edges, xy_ptrs, lens, out_ptr, capacity, opts=None, device=0, layers=False):
+        return ransac_graph_dev(pairs_ptr, edge_counts, edges, xy_ptrs, lens, out_ptr, capacity, opts, device, layers, model=model)
+
+    def ref(pair_lists, edges, xys, opts=None, capacity=None, layers=False):
+        return ransac_graph_ref(pair_lists, edges, xys, opts, capacity, layers, model=model)
+
+    for f, suffix, base in ((host, "_graph", ransac_graph), (dev, "_graph_dev", ransac_graph_dev), (ref, "_graph_ref", ransac_graph_ref)):
+        f.__name__ = f.__qualname__ = "ransac_%s%s" % (model, suffix)
+        f.__doc__ = "psx_ransac_%s%s: %s(..., model=%r)" % (model, suffix, base.__name__, model)
+        globals()[f.__name__] = f
+
+
+for _m in RANSAC_MODELS:
+    _ransac_graph_forms(_m)
+
+
+def _guided_graph_call(fn, name, device, set_ptrs, xy_ptrs, lens, edges, guides, out_ptr, capacity, ratio, mutual):
+    """One guided edge-list call on device pointers: (per-edge counts (n_edges,) int32, total count)"""
+    k = len(lens)
+    ea = _graph_edges(edges)
+    if not (len(set_ptrs) == len(xy_ptrs) == k) or len(guides) != len(ea):
+        raise ValueError("one descriptor pointer and one position pointer per set, one guide per edge")
+    val = lambda p: p.value if isinstance(p, C.c_void_p) else p
+    ptrs = (C.c_void_p * max(k, 1))(*[val(p) for p in set_ptrs])
+    xptrs = (C.c_void_p * max(k, 1))(*[val(p) for p in xy_ptrs])
+    la = np.ascontiguousarray(lens, dtype=np.int32)
+    garr = _guide_array(guides)
+    counts = np.full((len(ea),), -1, np.int32)
+    n = C.c_int(-1)
+    o = match_opts(ratio, mutual)
+    E = len(ea)
+    rc = fn(device, ptrs if k else None, xptrs if k else None, la.ctypes.data_as(C.c_void_p) if k else None, k,
+            ea.ctypes.data_as(C.c_void_p) if E else None, E, garr if E else None, C.byref(o), out_ptr, capacity,
+            counts.ctypes.data_as(C.c_void_p) if E else None, C.byref(n))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    return counts, n.value
+
+
+def match_pairs_guided_graph_u8(sets, xys, edges, guides, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs_guided_graph_u8 on host arrays: `sets` are (n_s,128) uint8 arrays with positions xys[s] (n_s,2),
+    `edges` (left, right) index pairs into them, edge e re-matched under guides[e], all in ONE call.  A guide of kind
+    GUIDE_NONE (Guide.none(), or None) skips its edge.  Returns (list of per-edge PAIR_U8_DTYPE arrays -- edge e's equals
+    match_pairs_guided_u8(sets[left], xys[left], sets[right], xys[right], guides[e]) --, per-edge counts); with a capacity the
+    list holds the first `capacity` records of the concatenation and the counts are still the totals."""
+    L = lib()
+    if len(sets) != len(xys):
+        raise ValueError("one position array per descriptor set")
+    empty, empty_xy = np.zeros((0, 128), np.uint8), np.zeros((0, 2), np.float32)
+    sides = [_guided_sides(s, x, empty, empty_xy, np.uint8)[:2] for s, x in zip(sets, xys)]
+    ea = _graph_edges(edges)
+    bufs = []
+    try:
+        k = len(sides)
+        ptrs = _to_device(L, device, [s[0] for s in sides] + [s[1] for s in sides], bufs) if k else []
+        lens = [len(s[0]) for s in sides]
+        ok = all(0 <= a < k and 0 <= b < k for a, b in ea)
+        cap = (sum(lens[a] for a, _ in ea) if ok else 0) if capacity is None else capacity
+        out = np.zeros((cap,), PAIR_U8_DTYPE)
+        counts, n = _guided_graph_call(L.psx_match_pairs_guided_graph_u8, "psx_match_pairs_guided_graph_u8", device, ptrs[:k], ptrs[k:], lens, ea,
+                                       guides, out.ctypes.data_as(C.c_void_p) if cap else None, cap, ratio, mutual)
+        return split_sets(out[:min(n, cap)], counts), counts
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def match_pairs_guided_graph_dev(set_ptrs, xy_ptrs, lens, edges, guides, out_ptr, capacity, ratio=0.8, mutual=False, device=0):
+    """psx_match_pairs_guided_graph_u8_dev on DEVICE pointers (e.g. tensor.data_ptr()): the concatenated records go into the
+    caller's device buffer at out_ptr (16-byte aligned, `capacity` records); returns (per-edge counts, total count)."""
+    return _guided_graph_call(lib().psx_match_pairs_guided_graph_u8_dev, "psx_match_pairs_guided_graph_u8_dev", device, list(set_ptrs),
+                              list(xy_ptrs), lens, edges, guides, C.c_void_p(out_ptr), capacity, ratio, mutual)
 
 
 # psx_step kinds and the schedules of psx_pyramid_plan

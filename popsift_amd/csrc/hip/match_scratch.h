@@ -1,5 +1,6 @@
 // match_scratch.h -- what the matcher's translation units share (match.hip, match_guided.hip, match_many.hip,
-// match_many_f32.hip, match_guided_many.hip, match_graph.hip, ransac.hip, ransac_many.hip):
+// match_many_f32.hip, match_guided_many.hip, match_graph.hip, match_guided_graph.hip, ransac.hip, ransac_many.hip,
+// ransac_graph.hip):
 // the layout of a directed result, the per-thread scratch with its named buffers, and the runner of the pair join.
 // Internal to the HIP library.
 #pragma once
@@ -90,6 +91,12 @@ enum MatchSlot {
     MS_GRAPH_FWD,        // the forward direction's results of all edges
     MS_GRAPH_BWD,        // the backward direction's
     MS_GRAPH_TOT,        // the join's per-workgroup totals and their offsets
+    MS_RGRAPH_TABLES,    // RANSAC over an edge list (ransac_graph.hip): the edge table and its two block tables; the rest is RANSAC's
+    MS_GGRAPH_TABLES,    // the guided re-match over an edge list (match_guided_graph.hip): the edge table and the two {edge, row0} tables
+    MS_GGRAPH_LINES,     // the left rows' lines under their edge's guide, for the backward direction
+    MS_GGRAPH_FWD,       // the forward direction's results of all edges
+    MS_GGRAPH_BWD,       // the backward direction's
+    MS_GGRAPH_TOT,       // the join's per-workgroup totals and their offsets
     MS_NBUF
 };
 

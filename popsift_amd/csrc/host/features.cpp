@@ -1110,4 +1110,236 @@ std::vector<HomographyEstimate> FeaturesDev::estimateMany( const char* who, Rans
     return out;
 }
 
+namespace {
+typedef int (*RansacGraphFn)( int, const void*, const int*, const psx_view_edge*, int, const float* const*, const int*, int, const psx_ransac_opts*,
+                              psx_ransac_result*, void*, int, int*, float*, int* );
+const RansacGraphFn ransac_graph_models[4] = { psx_ransac_homography_graph, psx_ransac_fundamental_graph, psx_ransac_affine_graph,
+                                               psx_ransac_similarity_graph };
+
+// what the edge-list forms refuse about their views and edges, as matchPairsGraph does: an edge index outside `views`, a
+// null view that an edge names, named views on different devices.  Returns the device of the named views (-1: no edge).
+int graph_views_device( const char* who, const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                        int (*device_of)( FeaturesDev* ) )
+{
+    const int N = (int)views.size();
+    std::vector<char> named( views.size(), 0 );
+    for( const std::pair<int,int>& e : edges ) {
+        if( e.first < 0 || e.first >= N || e.second < 0 || e.second >= N ) {
+            std::ostringstream ss;
+            ss << who << ": edge (" << e.first << ", " << e.second << ") out of range (" << N << " views)";
+            fatal( __FILE__, __LINE__, ss.str() );
+        }
+        named[e.first] = named[e.second] = 1;
+    }
+    int device = -1;
+    for( int v = 0; v < N; v++ ) {
+        if( !named[v] ) continue;
+        if( views[v] == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
+        if( device < 0 ) device = device_of( views[v] );
+        if( device_of( views[v] ) != device ) {
+            std::ostringstream ss;
+            ss << who << ": the objects live on different devices (" << device << " and " << device_of( views[v] ) << ")";
+            fatal( __FILE__, __LINE__, ss.str() );
+        }
+    }
+    return device;
+}
+}
+
+std::vector<HomographyEstimate> FeaturesDev::estimateHomographyGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                      const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
+{
+    return estimateGraph( "FeaturesDev::estimateHomographyGraph", ModelHomography, views, edges, matches, opts );
+}
+
+std::vector<FundamentalEstimate> FeaturesDev::estimateFundamentalGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                        const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
+{
+    return estimateGraph( "FeaturesDev::estimateFundamentalGraph", ModelFundamental, views, edges, matches, opts );
+}
+
+std::vector<HomographyEstimate> FeaturesDev::estimateAffineGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                  const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
+{
+    return estimateGraph( "FeaturesDev::estimateAffineGraph", ModelAffine, views, edges, matches, opts );
+}
+
+std::vector<HomographyEstimate> FeaturesDev::estimateSimilarityGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                      const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
+{
+    return estimateGraph( "FeaturesDev::estimateSimilarityGraph", ModelSimilarity, views, edges, matches, opts );
+}
+
+// psx_ransac_homography_graph / _fundamental_graph / _affine_graph / _similarity_graph on the lists matchPairsGraph returned:
+// the lists that can have a model go behind one another into ONE call (a shorter list is "no model" without a device, as
+// estimate() has it), the positions of every view such an edge names are gathered once
+std::vector<HomographyEstimate> FeaturesDev::estimateGraph( const char* who, RansacModel model, const std::vector<FeaturesDev*>& views,
+                                                            const std::vector<std::pair<int,int>>& edges,
+                                                            const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
+{
+    if( edges.size() != matches.size() ) {
+        std::ostringstream ss;
+        ss << who << ": " << edges.size() << " edges but " << matches.size() << " match lists";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    const int device = graph_views_device( who, views, edges, []( FeaturesDev* f ) { return f->_device; } );
+    if( !( std::isfinite( opts.tol ) && opts.tol >= 0.0f ) || opts.hypotheses < 1 || opts.hypotheses > 65536 )
+        fatal( __FILE__, __LINE__, std::string( who ) + ": invalid options (finite tolerance >= 0, 1 to 65536 hypotheses)" );
+    const int N = (int)views.size(), E = (int)edges.size();
+    const int min_pairs = ransac_models[model].min_pairs;
+    HomographyEstimate none;
+    none.guide.kind = model == ModelFundamental ? MatchGuide::Epipolar : MatchGuide::Homography;
+    for( int k = 0; k < 9; k++ ) none.guide.m[k] = 0.0f;
+    none.guide.tol = opts.tol;
+    none.best = -1; none.sample_inliers = 0; none.refit_kept = false;
+    std::vector<HomographyEstimate> out( edges.size(), none );
+    std::vector<int> counts( edges.size(), 0 ), lens( views.size(), 0 );
+    std::vector<char> used( views.size(), 0 );               // named by an edge that has a model to estimate
+    size_t total = 0;
+    for( int e = 0; e < E; e++ )
+        if( (int)matches[e].size() >= min_pairs ) {
+            counts[e] = (int)matches[e].size(); total += matches[e].size();
+            used[edges[e].first] = used[edges[e].second] = 1;
+        }
+    if( total == 0 ) return out;
+    // the record is copied whole: its distance slots carry the index of the match within its list
+    std::vector<psx_match_pair_u8> rec( total ), inl( total );
+    size_t at = 0;
+    for( int e = 0; e < E; e++ )
+        for( int q = 0; q < counts[e]; q++, at++ ) {
+            rec[at].left = matches[e][q].left_descriptor; rec[at].right = matches[e][q].right_descriptor; rec[at].d1 = q; rec[at].d2 = 0;
+        }
+    psx_ransac_opts po;
+    po.tol = opts.tol; po.hypotheses = opts.hypotheses; po.seed = opts.seed; po.flags = opts.refit ? PSX_RANSAC_REFIT : 0;
+    std::vector<psx_view_edge> pe( edges.size() );
+    for( int e = 0; e < E; e++ ) { pe[e].left = edges[e].first; pe[e].right = edges[e].second; }
+    std::vector<psx_ransac_result> res( edges.size() );
+    std::vector<void*> bufs( views.size(), nullptr );
+    std::vector<const float*> xys( views.size(), nullptr );
+    int count = 0;
+    int rc = PSX_OK;
+    for( int v = 0; v < N && rc == PSX_OK; v++ ) {
+        if( !used[v] ) continue;
+        const int len = views[v]->getDescriptorCount();
+        if( len <= 0 ) { rc = PSX_ERR_INVALID; break; }
+        lens[v] = len;
+        rc = psx_dev_alloc( device, (size_t)len * 2 * sizeof(float), &bufs[v] );
+        if( rc == PSX_OK ) rc = psx_desc_positions( device, (const psx_feature_dev*)views[v]->_ext, views[v]->_rev, len, (float*)bufs[v] );
+        xys[v] = (const float*)bufs[v];
+    }
+    if( rc == PSX_OK )
+        rc = ransac_graph_models[model]( device, rec.data(), counts.data(), pe.data(), E, xys.data(), lens.data(), N, &po, res.data(), inl.data(),
+                                         (int)total, &count, nullptr, nullptr );
+    for( void* b : bufs ) psx_dev_free( device, b );
+    if( rc != PSX_OK ) {
+        std::ostringstream ss;
+        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options or a descriptor index outside its object" : "" ) << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    at = 0;
+    for( int e = 0; e < E; e++ ) {
+        if( counts[e] == 0 ) continue;
+        HomographyEstimate& est = out[e];
+        for( int j = 0; j < 9; j++ ) est.guide.m[j] = res[e].m[j];
+        est.best = res[e].best; est.sample_inliers = res[e].sample_inliers; est.refit_kept = res[e].refit_kept != 0;
+        est.inliers.reserve( res[e].inliers );
+        for( int q = 0; q < res[e].inliers; q++, at++ ) est.inliers.push_back( matches[e][inl[at].d1] );
+    }
+    return out;
+}
+
+// FeaturesDev::matchPairsGuidedGraph: psx_match_pairs_guided_graph_u8 on the bytes and positions of every view that an edge
+// names which is neither skipped nor has an empty side -- each quantised and its positions gathered once, ONE matching
+// call for all edges; the concatenated list is cut at the per-edge counts and mapped through the two views' reverse maps
+std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                    const std::vector<MatchGuide>& guides, const MatchOptions& opts )
+{
+    const char* who = "FeaturesDev::matchPairsGuidedGraph";
+    const int device = graph_views_device( who, views, edges, []( FeaturesDev* f ) { return f->_device; } );
+    if( !opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": the edge-list form is byte-only (set MatchOptions::bytes)" );
+    if( guides.size() != edges.size() ) {
+        std::ostringstream ss;
+        ss << who << ": " << edges.size() << " edges but " << guides.size() << " guides";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    const int N = (int)views.size(), E = (int)edges.size();
+    std::vector<psx_guide> pg( edges.size() );
+    for( int e = 0; e < E; e++ ) {
+        pg[e].kind = (int)guides[e].kind;
+        for( int q = 0; q < 9; q++ ) pg[e].m[q] = guides[e].m[q];
+        pg[e].tol = guides[e].tol;
+        if( pg[e].kind == PSX_GUIDE_NONE ) continue;
+        // refused here, before any device is touched (and for empty sides too): what the call refuses
+        bool ok = ( pg[e].kind == PSX_GUIDE_HOMOGRAPHY || pg[e].kind == PSX_GUIDE_EPIPOLAR ) && std::isfinite( pg[e].tol ) && pg[e].tol >= 0.0f;
+        for( int q = 0; q < 9; q++ ) ok = ok && std::isfinite( pg[e].m[q] );
+        if( !ok ) fatal( __FILE__, __LINE__, std::string( who ) + ": invalid guide (kind 0, 1 or 2, finite entries, finite tolerance >= 0)" );
+    }
+    std::vector<std::vector<Match>> out( edges.size() );
+    std::vector<int> lens( views.size(), 0 );
+    std::vector<char> used( views.size(), 0 );               // named by an edge that is not skipped and has two non-empty sides
+    long long room = 0;                                      // at most lens[left] pairs per edge exist
+    for( int e = 0; e < E; e++ ) {
+        const int l = edges[e].first, r = edges[e].second;
+        if( pg[e].kind == PSX_GUIDE_NONE || views[l]->getDescriptorCount() <= 0 || views[r]->getDescriptorCount() <= 0 ) continue;
+        room += views[l]->getDescriptorCount();
+        used[l] = used[r] = 1;
+    }
+    if( room == 0 ) return out;
+    psx_match_opts po;
+    po.ratio = opts.ratio;
+    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
+    // descriptors of view v at [v], its positions at [N + v]
+    std::vector<void*> bufs( 2 * views.size(), nullptr );
+    std::vector<const unsigned char*> ptrs( views.size(), nullptr );
+    std::vector<const float*> xys( views.size(), nullptr );
+    int rc = PSX_OK;
+    for( int v = 0; v < N && rc == PSX_OK; v++ ) {
+        if( !used[v] ) continue;                             // a view no live edge names is an empty set to the call
+        const int len = lens[v] = views[v]->getDescriptorCount();
+        rc = psx_dev_alloc( device, (size_t)len * 128, &bufs[v] );
+        if( rc == PSX_OK ) rc = psx_dev_alloc( device, (size_t)len * 2 * sizeof(float), &bufs[N + v] );
+        if( rc == PSX_OK ) rc = psx_quantize_desc( device, (const float*)views[v]->_ori, len, (unsigned char*)bufs[v] );
+        if( rc == PSX_OK ) rc = psx_desc_positions( device, (const psx_feature_dev*)views[v]->_ext, views[v]->_rev, len, (float*)bufs[N + v] );
+        ptrs[v] = (const unsigned char*)bufs[v];
+        xys[v] = (const float*)bufs[N + v];
+    }
+    std::vector<psx_view_edge> pe( edges.size() );
+    for( int e = 0; e < E; e++ ) { pe[e].left = edges[e].first; pe[e].right = edges[e].second; }
+    std::vector<psx_match_pair_u8> pb( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
+    std::vector<int> counts( edges.size(), 0 );
+    int count = 0;
+    if( rc == PSX_OK )
+        rc = psx_match_pairs_guided_graph_u8( device, ptrs.data(), xys.data(), lens.data(), N, pe.data(), E, pg.data(), &po, pb.data(),
+                                              (int)pb.size(), counts.data(), &count );
+    for( void* b : bufs ) psx_dev_free( device, b );
+    if( rc != PSX_OK ) {
+        std::ostringstream ss;
+        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    std::vector<std::vector<int>> fem( views.size() );       // every used view's reverse map, read once
+    for( int v = 0; v < N; v++ ) {
+        if( !used[v] ) continue;
+        fem[v].resize( lens[v] );
+        if( psx_dev_read( device, fem[v].data(), views[v]->_rev, (size_t)lens[v] * sizeof(int) ) != PSX_OK )
+            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
+    }
+    size_t at = 0;
+    for( int e = 0; e < E; e++ ) {
+        if( counts[e] <= 0 ) continue;
+        const std::vector<int>& l_fem = fem[pe[e].left];
+        const std::vector<int>& r_fem = fem[pe[e].right];
+        out[e].resize( counts[e] );
+        for( int q = 0; q < counts[e]; q++, at++ ) {
+            Match& m = out[e][q];
+            m.left_descriptor = pb[at].left; m.right_descriptor = pb[at].right;
+            m.distance        = pb[at].d1 == INT32_MAX ? INFINITY : (float)pb[at].d1;
+            m.second_distance = pb[at].d2 == INT32_MAX ? INFINITY : (float)pb[at].d2;
+            m.left_feature  = l_fem[m.left_descriptor];
+            m.right_feature = r_fem[m.right_descriptor];
+        }
+    }
+    return out;
+}
+
 } // namespace popsift

@@ -190,6 +190,9 @@ class FeaturesDev : public FeaturesBase
     HomographyEstimate estimate( const char* who, RansacModel model, FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts );
     std::vector<HomographyEstimate> estimateMany( const char* who, RansacModel model, const std::vector<FeaturesDev*>& others,
                                                   const std::vector<std::vector<Match>>& matches, const RansacOptions& opts );
+    static std::vector<HomographyEstimate> estimateGraph( const char* who, RansacModel model, const std::vector<FeaturesDev*>& views,
+                                                          const std::vector<std::pair<int,int>>& edges,
+                                                          const std::vector<std::vector<Match>>& matches, const RansacOptions& opts );
 
 public:
     FeaturesDev( );
@@ -268,6 +271,33 @@ public:
                                                         const RansacOptions& opts = RansacOptions() );
     std::vector<HomographyEstimate> estimateSimilarityMany( const std::vector<FeaturesDev*>& others, const std::vector<std::vector<Match>>& matches,
                                                             const RansacOptions& opts = RansacOptions() );
+    /// estimateHomography over a LIST OF VIEW PAIRS in ONE device call (psx_ransac_homography_graph: one or two
+    /// synchronisations and a number of launches that grows neither with edges.size() nor with views.size()): `views`,
+    /// `edges` and `matches` are what matchPairsGraph took and returned, element e equals
+    /// views[left]->estimateHomography( views[right], matches[e], opts ) field by field, whatever the order of the list.
+    /// Throws as estimateHomographyMany, for an edge index outside `views`, and when edges and matches differ in size.
+    /// From the result vector to the guides of matchPairsGuidedGraph: as for estimateHomographyMany.
+    static std::vector<HomographyEstimate> estimateHomographyGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                    const std::vector<std::vector<Match>>& matches,
+                                                                    const RansacOptions& opts = RansacOptions() );
+    /// the same for fundamental matrices, affine transforms and similarities (psx_ransac_fundamental_graph, _affine_graph,
+    /// _similarity_graph)
+    static std::vector<FundamentalEstimate> estimateFundamentalGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                      const std::vector<std::vector<Match>>& matches,
+                                                                      const RansacOptions& opts = RansacOptions() );
+    static std::vector<HomographyEstimate> estimateAffineGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                const std::vector<std::vector<Match>>& matches,
+                                                                const RansacOptions& opts = RansacOptions() );
+    static std::vector<HomographyEstimate> estimateSimilarityGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                    const std::vector<std::vector<Match>>& matches,
+                                                                    const RansacOptions& opts = RansacOptions() );
+    /// matchPairsGuided over a LIST OF VIEW PAIRS in ONE device call (psx_match_pairs_guided_graph_u8: one synchronisation,
+    /// a number of launches that grows neither with edges.size() nor with views.size()), edge e under guides[e]: element
+    /// e equals views[left]->matchPairsGuided( views[right], guides[e], opts ) with opts.bytes.  A guide of kind
+    /// MatchGuide::None skips its edge: element e is empty.  Byte descriptors only.  Throws as matchPairsGraph, for
+    /// guides.size() != edges.size(), and for a guide that is neither valid nor of kind None.
+    static std::vector<std::vector<Match>> matchPairsGuidedGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                  const std::vector<MatchGuide>& guides, const MatchOptions& opts );
 
     inline Feature*   getFeatures()    { return _ext; }
     inline Descriptor* getDescriptors() { return _ori; }
