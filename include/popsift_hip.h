@@ -946,6 +946,77 @@ int psx_match_pairs_guided_graph_u8_dev(int device, const unsigned char* const* 
                                         const psx_guide* guides, const psx_match_opts* opts,
                                         psx_match_pair_u8* d_pairs, int capacity, int* edge_counts, int* count);
 
+/* TRACKS FROM A LIST OF VIEW PAIRS: the fourth link.  The chain above ends with E separate pair lists; structure from
+ * motion, loop closure and retrieval need TRACKS next: the sets of rows in different views that the pairs connect
+ * transitively, one scene point each.  One call over the same edge list and the same concatenated records with per-edge
+ * counts; INTEGRATION.md ("Tracks from a list of view pairs") has the four-call chain and the measured cost.
+ *   pairs        the concatenation of 16-byte records (host_pairs: HOST; d_pairs: DEVICE, 16-byte aligned), edge e owning
+ *                edge_counts[e] consecutive records.  Only the first two ints {left, right} of a record are read: the
+ *                buffer may hold psx_match_pair_u8 or psx_match_pair records, a RANSAC inlier list (results[e].inliers as
+ *                counts) or a guided re-match list;
+ *   edge_counts, edges, lens   HOST arrays, as psx_ransac_*_graph* takes them;
+ *   opts         {min_views >= 2, flags}; {2, 0} is the usual choice.
+ * THE RULE (csrc/hip/tracks_rule.h, shared by host and device).  Row r of view v is node g = off[v] + r, off = the
+ * exclusive prefix sum of lens, M = their sum.  A record of edge e joins node (edges[e].left, left) with node
+ * (edges[e].right, right).  Nothing is special-cased: duplicate edges and records join again (a no-op); (a, b) and (b, a)
+ * are two edges; on an edge with left == right a record with equal rows is a self-loop (a no-op), one with different rows
+ * joins two rows of one view.  A component of the joins is named by its smallest node, its root.  A component is a TRACK
+ * iff it has >= 2 members in >= min_views distinct views and no two members in one view -- a CONFLICT, dropped as
+ * AliceVision drops it -- unless PSX_TRACKS_KEEP_CONFLICTS is set.  Tracks are numbered by ascending root; the members
+ * of a track are ordered by ascending node: by view, then by row.
+ * OUTPUTS.  track_starts[0 .. tracks]: a CSR row array, track t owns members[track_starts[t] .. track_starts[t + 1]);
+ * the values are always the unclipped offsets.  members: {view, row}, 8 bytes.  labels (M ints, may be NULL): the track
+ * number of every node, -1 for a node in no kept track.  info, always the totals whatever the capacities are: tracks;
+ * members; components (those of >= 2 members); conflicts (components with two members in one view); too_few_views
+ * (components of >= 2 members in fewer than min_views views; a component may count in both, and neither depends on the
+ * flags); joined_records (the records that are not self-loops).
+ * CAPACITIES.  track_starts has room for track_capacity + 1 ints, entries 0 .. min(tracks, track_capacity) are written;
+ * the first min(members, member_capacity) member records are written, the cut may fall inside a track; nothing at or
+ * past either capacity is touched.  Capacity 0 with a NULL pointer asks "how many?".
+ * n_edges = 0, all counts zero, or M = 0: zero totals and PSX_OK without touching a device; the host form and the
+ * reference then set labels to -1 and track_starts[0] to 0 where the arrays are given, the _dev form writes nothing to
+ * device memory.
+ * PSX_ERR_INVALID, before any device call and with nothing written: everything psx_ransac_*_graph* refuses about lens,
+ * n_sets, edges, n_edges and edge_counts (a negative count among it); pairs NULL with a count; NULL opts or info;
+ * min_views < 2; unknown flag bits; a negative capacity, or a NULL output with a positive capacity; an edge that has
+ * records and an empty side (no row can lie inside it); in the _dev form a misaligned device pointer (records 16 bytes,
+ * members 8, ints 4); M or the sum of the counts above 0x3fffffff.  A record whose left or right lies outside ITS OWN
+ * edge's view lengths refuses the whole call with PSX_ERR_INVALID, through one device flag: nothing is read or written out
+ * of bounds, info and the host outputs are untouched, the contents of device output buffers are unspecified.
+ * PSX_ERR_NOMEM where a grid or table would not fit an int.
+ * One table copy, 7 kernel launches and one radix sort (rocprim), one stream synchronisation, whatever n_edges, n_sets
+ * and M are.  Scratch (psx_match_release) and thread safety as for psx_match_u8.  Synchronous.
+ * Out of scope: merging the descriptor rows of one multi-orientation keypoint into one feature (tracks are over
+ * descriptor rows, as the pair records are), and triangulation. */
+#define PSX_TRACKS_KEEP_CONFLICTS 1
+typedef struct psx_track_opts   { int min_views; int flags; } psx_track_opts;      /* {2, 0} */
+typedef struct psx_track_member { int view, row; } psx_track_member;
+typedef struct psx_tracks_info  { int tracks, members, components, conflicts, too_few_views, joined_records; } psx_tracks_info;
+int psx_tracks_graph(int device, const void* host_pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                     const int* lens, int n_sets, const psx_track_opts* opts,
+                     int* host_labels, int* host_track_starts, int track_capacity,
+                     psx_track_member* host_members, int member_capacity, psx_tracks_info* info);
+/* everything stays in HBM: d_pairs, d_labels, d_track_starts and d_members are DEVICE pointers; edge_counts, edges, lens,
+ * opts and info stay HOST memory */
+int psx_tracks_graph_dev(int device, const void* d_pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                         const int* lens, int n_sets, const psx_track_opts* opts,
+                         int* d_labels, int* d_track_starts, int track_capacity,
+                         psx_track_member* d_members, int member_capacity, psx_tracks_info* info);
+/* Host only, no device: a sequential union-find under the same rule and the same argument checks -- the definition.  Every
+ * record of every edge is checked before anything is written. */
+int psx_tracks_graph_ref(const void* pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                         const int* lens, int n_sets, const psx_track_opts* opts,
+                         int* labels, int* track_starts, int track_capacity,
+                         psx_track_member* members, int member_capacity, psx_tracks_info* info);
+/* What a call of these sizes plans, on the HOST (csrc/hip/tracks_plan.h, the header the library itself plans with): nodes
+ * = M; records = the sum of the counts; record_blocks = the 256-record blocks of the join kernel, none crossing an edge;
+ * sort_bits = the key bits of the sort, ceil(log2 M) and at least 1; launches = the library's own kernel launches (the
+ * sort's come on top); scratch_bytes = the device scratch of the _dev form without the sort's temporary storage.  A call
+ * that touches no device plans zero blocks, launches and bytes.  PSX_ERR_INVALID for what the calls above refuse about
+ * lens, n_sets, edge_counts and n_edges, or a NULL out; PSX_ERR_NOMEM where a table would not fit an int. */
+typedef struct psx_tracks_plan_info { int nodes, records, record_blocks, sort_bits, launches; long long scratch_bytes; } psx_tracks_plan_info;
+int psx_tracks_plan(const int* lens, int n_sets, const int* edge_counts, int n_edges, psx_tracks_plan_info* out);
+
 /* ---- caller-supplied keypoints ------------------------------------------------------------
  * Describing points the caller brings along instead of the ones the DoG detector finds (what OpenCV calls
  * useProvidedKeypoints and VLFeat calls frames; the reference has no counterpart).  A record carries what a

@@ -117,6 +117,7 @@ SYMBOLS = [
     "psx_ransac_affine_graph", "psx_ransac_affine_graph_dev", "psx_ransac_affine_graph_ref",
     "psx_ransac_similarity_graph", "psx_ransac_similarity_graph_dev", "psx_ransac_similarity_graph_ref",
     "psx_match_pairs_guided_graph_u8", "psx_match_pairs_guided_graph_u8_dev",
+    "psx_tracks_graph", "psx_tracks_graph_dev", "psx_tracks_graph_ref", "psx_tracks_plan",
     "psx_pyramid_plan", "psx_blur_grid_of",
 ]
 
@@ -201,6 +202,27 @@ class RansacResult(C.Structure):
         """the kept model as the psx_guide of a guided re-match: a homography guide from ransac_homography*, an epipolar
         one from ransac_fundamental*"""
         return Guide.make(self.kind, self.matrix(), tol)
+
+
+TRACKS_KEEP_CONFLICTS = 1     # PSX_TRACKS_KEEP_CONFLICTS
+TRACK_MEMBER_DTYPE = np.dtype([("view", "<i4"), ("row", "<i4")])     # psx_track_member (8 bytes)
+
+
+class TrackOpts(C.Structure):
+    """psx_track_opts: a track has members in at least min_views (>= 2) views; flags: TRACKS_KEEP_CONFLICTS"""
+    _fields_ = [("min_views", C.c_int), ("flags", C.c_int)]
+
+
+class TracksInfo(C.Structure):
+    """psx_tracks_info: the totals of a tracks call, whatever the capacities were"""
+    _fields_ = [("tracks", C.c_int), ("members", C.c_int), ("components", C.c_int), ("conflicts", C.c_int), ("too_few_views", C.c_int),
+                ("joined_records", C.c_int)]
+
+
+class TracksPlanInfo(C.Structure):
+    """psx_tracks_plan_info: what psx_tracks_graph plans for the sizes of a call"""
+    _fields_ = [("nodes", C.c_int), ("records", C.c_int), ("record_blocks", C.c_int), ("sort_bits", C.c_int), ("launches", C.c_int),
+                ("scratch_bytes", C.c_longlong)]
 
 
 DESCFMT_F32 = 0      # PSX_DESCFMT_F32
@@ -312,6 +334,11 @@ def lib():
                                                                    vp, vp]
         for n in ("psx_match_pairs_guided_graph_u8", "psx_match_pairs_guided_graph_u8_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, C.POINTER(MatchOpts), vp, C.c_int, vp, ip]
+        for n in ("psx_tracks_graph", "psx_tracks_graph_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.POINTER(TrackOpts), vp, vp, C.c_int, vp, C.c_int,
+                                      C.POINTER(TracksInfo)]
+        L.psx_tracks_graph_ref.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.POINTER(TrackOpts), vp, vp, C.c_int, vp, C.c_int, C.POINTER(TracksInfo)]
+        L.psx_tracks_plan.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(TracksPlanInfo)]
         L.psx_pyramid_plan.argtypes = [C.c_int] * 4 + [vp] + [C.c_int] * 3 + [vp, C.c_int, ip]
         L.psx_blur_grid_of.argtypes = [C.c_int] * 3
         _LIB = L
@@ -1399,6 +1426,94 @@ def _ransac_graph_forms(model):
 
 for _m in RANSAC_MODELS:
     _ransac_graph_forms(_m)
+
+
+def track_opts(min_views=2, keep_conflicts=False):
+    return TrackOpts(int(min_views), TRACKS_KEEP_CONFLICTS if keep_conflicts else 0)
+
+
+def _tracks_call(fn, name, pairs_ptr, edge_counts, edges, lens, opts, labels_ptr, starts_ptr, track_capacity, members_ptr, member_capacity):
+    """One tracks call on raw pointers (host or device alike): the TracksInfo"""
+    ea = _graph_edges(edges)
+    E, k = len(ea), len(lens)
+    if len(edge_counts) != E:
+        raise ValueError("one record list per edge")
+    ec = np.ascontiguousarray(edge_counts, dtype=np.int32)
+    la = np.ascontiguousarray(lens, dtype=np.int32)
+    info = TracksInfo()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    rc = fn(pairs_ptr, ptr(ec), ptr(ea), E, ptr(la), k, C.byref(opts), labels_ptr, starts_ptr, track_capacity, members_ptr, member_capacity,
+            C.byref(info))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    return info
+
+
+def _tracks_host(fn, name, pair_lists, edges, lens, opts, labels, track_capacity, member_capacity):
+    """a host form: asks "how many?" unless both capacities are given, then fills arrays of that size"""
+    pairs, edge_counts = _pair_lists(pair_lists)
+    opts = opts or track_opts()
+    pp = pairs.ctypes.data_as(C.c_void_p) if pairs.size else None
+    if track_capacity is None or member_capacity is None:
+        how = _tracks_call(fn, name, pp, edge_counts, edges, lens, opts, None, None, 0, None, 0)
+        track_capacity = how.tracks if track_capacity is None else track_capacity
+        member_capacity = how.members if member_capacity is None else member_capacity
+    M = int(np.sum(np.asarray(lens, np.int64))) if len(lens) else 0
+    lab = np.zeros((M,), np.int32) if labels else None
+    starts = np.zeros((track_capacity + 1,), np.int32)
+    mem = np.zeros((member_capacity,), TRACK_MEMBER_DTYPE)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    info = _tracks_call(fn, name, pp, edge_counts, edges, lens, opts, vp(lab), vp(starts), track_capacity, vp(mem), member_capacity)
+    got = {n: int(getattr(info, n)) for n, _ in TracksInfo._fields_}
+    got["starts"] = starts[:min(info.tracks, track_capacity) + 1]
+    got["member_records"] = mem[:min(info.members, member_capacity)]
+    if labels:
+        got["labels"] = lab
+    return got
+
+
+def tracks_graph_ref(pair_lists, edges, lens, opts=None, labels=True, track_capacity=None, member_capacity=None):
+    """psx_tracks_graph_ref: the sequential union-find on host arrays, no device.  pair_lists: one 16-byte record array per
+    EDGE (what match_pairs_graph_u8, ransac_*_graph["inliers"] or match_pairs_guided_graph_u8 return); edges: (left, right)
+    indices into lens, the views' row counts.  Returns a dict: the six totals of TracksInfo by name, starts (CSR, tracks + 1
+    ints), member_records (TRACK_MEMBER_DTYPE; track t owns [starts[t], starts[t + 1])) and labels (sum(lens) ints, -1: in no
+    track)."""
+    L = lib()
+    return _tracks_host(L.psx_tracks_graph_ref, "psx_tracks_graph_ref", pair_lists, edges, lens, opts, labels, track_capacity, member_capacity)
+
+
+def tracks_graph(pair_lists, edges, lens, opts=None, device=0, labels=True, track_capacity=None, member_capacity=None):
+    """psx_tracks_graph on host arrays: the tracks of the E record lists of an edge list in ONE device call; the dict of
+    tracks_graph_ref, bit for bit."""
+    L = lib()
+    fn = lambda *a: L.psx_tracks_graph(device, *a)
+    return _tracks_host(fn, "psx_tracks_graph", pair_lists, edges, lens, opts, labels, track_capacity, member_capacity)
+
+
+def tracks_graph_dev(pairs_ptr, edge_counts, edges, lens, labels_ptr, starts_ptr, track_capacity, members_ptr, member_capacity, opts=None, device=0):
+    """psx_tracks_graph_dev on DEVICE pointers: pairs_ptr and edge_counts are what match_pairs_graph_dev, ransac_*_graph_dev
+    (counts: [r.inliers for r in results]) or match_pairs_guided_graph_dev left; labels (sum(lens) ints), track starts
+    (track_capacity + 1 ints) and members (member_capacity 8-byte records) are written in device memory, any of them 0 /
+    None with capacity 0.  Returns the totals as a dict."""
+    L = lib()
+    fn = lambda *a: L.psx_tracks_graph_dev(device, *a)
+    vp = lambda p: C.c_void_p(p) if p else None
+    info = _tracks_call(fn, "psx_tracks_graph_dev", vp(pairs_ptr), edge_counts, edges, lens, opts or track_opts(), vp(labels_ptr), vp(starts_ptr),
+                        track_capacity, vp(members_ptr), member_capacity)
+    return {n: int(getattr(info, n)) for n, _ in TracksInfo._fields_}
+
+
+def tracks_plan(lens, edge_counts):
+    """psx_tracks_plan: what psx_tracks_graph plans for these sizes, as a dict (nodes, records, record_blocks, sort_bits,
+    launches, scratch_bytes).  No device."""
+    la = np.ascontiguousarray(lens, dtype=np.int32)
+    ec = np.ascontiguousarray(edge_counts, dtype=np.int32)
+    out = TracksPlanInfo()
+    rc = lib().psx_tracks_plan(la.ctypes.data_as(C.c_void_p) if len(la) else None, len(la), ec.ctypes.data_as(C.c_void_p) if len(ec) else None,
+                               len(ec), C.byref(out))
+    if rc != 0:
+        raise PopSiftError("psx_tracks_plan failed (%d)" % rc)
+    return {n: int(getattr(out, n)) for n, _ in TracksPlanInfo._fields_}
 
 
 def _guided_graph_call(fn, name, device, set_ptrs, xy_ptrs, lens, edges, guides, out_ptr, capacity, ratio, mutual):

@@ -1,6 +1,6 @@
 // match_scratch.h -- what the matcher's translation units share (match.hip, match_guided.hip, match_many.hip,
 // match_many_f32.hip, match_guided_many.hip, match_graph.hip, match_guided_graph.hip, ransac.hip, ransac_many.hip,
-// ransac_graph.hip):
+// ransac_graph.hip, tracks.hip):
 // the layout of a directed result, the per-thread scratch with its named buffers, and the runner of the pair join.
 // Internal to the HIP library.
 #pragma once
@@ -97,6 +97,13 @@ enum MatchSlot {
     MS_GGRAPH_FWD,       // the forward direction's results of all edges
     MS_GGRAPH_BWD,       // the backward direction's
     MS_GGRAPH_TOT,       // the join's per-workgroup totals and their offsets
+    MS_TRACKS_TABLES,    // tracks over an edge list (tracks.hip): the edge table, the record blocks and the views' node offsets
+    MS_TRACKS_PAIRS,     // the uploaded records (the host form)
+    MS_TRACKS_NODES,     // per node: parent, view; per root: begin, end, view changes, conflict mark
+    MS_TRACKS_SORT,      // (root, node) keys and values, in and out, and the sort's temporary storage
+    MS_TRACKS_TOT,       // the compaction's per-workgroup totals (heads, nodes) and their offsets
+    MS_TRACKS_STATE,     // the six totals and the bad-record flag
+    MS_TRACKS_OUT,       // the host form's labels, track starts and members before they are copied back
     MS_NBUF
 };
 

@@ -1248,6 +1248,60 @@ std::vector<HomographyEstimate> FeaturesDev::estimateGraph( const char* who, Ran
     return out;
 }
 
+// FeaturesDev::buildTracks: psx_tracks_graph on the descriptor indices of the lists, at the capacities no result can exceed
+Tracks FeaturesDev::buildTracks( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                 const std::vector<std::vector<Match>>& matches, const TrackOptions& opts )
+{
+    const char* who = "FeaturesDev::buildTracks";
+    if( edges.size() != matches.size() ) {
+        std::ostringstream ss;
+        ss << who << ": " << edges.size() << " edges but " << matches.size() << " match lists";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    int device = graph_views_device( who, views, edges, []( FeaturesDev* f ) { return f->_device; } );
+    if( opts.min_views < 2 ) fatal( __FILE__, __LINE__, std::string( who ) + ": invalid options (min_views >= 2)" );
+    if( device < 0 ) device = 0;                             // no edge: the call touches no device
+    const int N = (int)views.size(), E = (int)edges.size();
+    std::vector<int> counts( edges.size(), 0 ), lens( views.size(), 0 );
+    Tracks out;
+    out.view_offsets.assign( views.size() + 1, 0 );
+    for( int v = 0; v < N; v++ ) {
+        lens[v] = views[v] != nullptr ? views[v]->getDescriptorCount() : 0;
+        out.view_offsets[v + 1] = out.view_offsets[v] + lens[v];
+    }
+    const int M = out.view_offsets[N];
+    size_t total = 0;
+    for( int e = 0; e < E; e++ ) { counts[e] = (int)matches[e].size(); total += matches[e].size(); }
+    std::vector<psx_match_pair_u8> rec( total );
+    size_t at = 0;
+    for( int e = 0; e < E; e++ )
+        for( const Match& m : matches[e] ) {
+            rec[at].left = m.left_descriptor; rec[at].right = m.right_descriptor; rec[at].d1 = 0; rec[at].d2 = 0;
+            at++;
+        }
+    std::vector<psx_view_edge> pe( edges.size() );
+    for( int e = 0; e < E; e++ ) { pe[e].left = edges[e].first; pe[e].right = edges[e].second; }
+    psx_track_opts po;
+    po.min_views = opts.min_views; po.flags = opts.keep_conflicts ? PSX_TRACKS_KEEP_CONFLICTS : 0;
+    std::vector<psx_track_member> mem( (size_t)M );
+    out.labels.assign( (size_t)M, -1 );
+    out.starts.assign( (size_t)M / 2 + 1, 0 );
+    psx_tracks_info info;
+    const int rc = psx_tracks_graph( device, rec.data(), counts.data(), pe.data(), E, lens.data(), N, &po, out.labels.data(), out.starts.data(),
+                                     M / 2, mem.data(), M, &info );
+    if( rc != PSX_OK ) {
+        std::ostringstream ss;
+        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": a descriptor index outside its object" : "" ) << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    out.starts.resize( (size_t)info.tracks + 1 );
+    out.members.resize( (size_t)info.members );
+    for( int i = 0; i < info.members; i++ ) { out.members[i].view = mem[i].view; out.members[i].descriptor = mem[i].row; }
+    out.n_tracks = info.tracks; out.n_members = info.members; out.components = info.components; out.conflicts = info.conflicts;
+    out.too_few_views = info.too_few_views; out.joined_records = info.joined_records;
+    return out;
+}
+
 // FeaturesDev::matchPairsGuidedGraph: psx_match_pairs_guided_graph_u8 on the bytes and positions of every view that an edge
 // names which is neither skipped nor has an empty side -- each quantised and its positions gathered once, ONE matching
 // call for all edges; the concatenated list is cut at the per-edge counts and mapped through the two views' reverse maps

@@ -178,6 +178,35 @@ typedef HomographyEstimate FundamentalEstimate;
 /// FeaturesDev::estimateAffine and estimateSimilarity return a HomographyEstimate: guide is Homography, a matrix whose last
 /// row is exactly (0, 0, 1); the sample has 3 / 2 points and best = -1 stands for fewer matches than that or no finite model
 
+/// How FeaturesDev::buildTracks runs: the options of psx_tracks_graph (include/popsift_hip.h, "TRACKS FROM A LIST OF VIEW PAIRS")
+struct TrackOptions
+{
+    int  min_views      = 2;       ///< a track has members in at least this many views, >= 2
+    bool keep_conflicts = false;   ///< keep the components that have two members in one view
+};
+
+/// One member of a track: a descriptor row of a view
+struct TrackMember
+{
+    int view;          ///< index into `views`
+    int descriptor;    ///< index into that view's descriptor array
+};
+
+/// What FeaturesDev::buildTracks returns: track t owns members[ starts[t] .. starts[t+1] ), tracks ordered by their
+/// smallest (view, descriptor), members by view, then by descriptor
+struct Tracks
+{
+    std::vector<int>         starts;         ///< n_tracks + 1 offsets into members
+    std::vector<TrackMember> members;
+    std::vector<int>         labels;         ///< labels[ view_offsets[v] + d ]: the track of descriptor d of view v, -1: in none
+    std::vector<int>         view_offsets;   ///< views.size() + 1: the exclusive prefix sum of the views' descriptor counts
+    int n_tracks, n_members;                 ///< starts.size() - 1 and members.size()
+    int components;                          ///< connected components of 2 or more members
+    int conflicts;                           ///< those with two members in one view
+    int too_few_views;                       ///< those in fewer than min_views views
+    int joined_records;                      ///< the matches that are not self-loops
+};
+
 /// Device-resident result (MatchingMode): arrays live in HBM of the extracting device.
 class FeaturesDev : public FeaturesBase
 {
@@ -298,6 +327,16 @@ public:
     /// guides.size() != edges.size(), and for a guide that is neither valid nor of kind None.
     static std::vector<std::vector<Match>> matchPairsGuidedGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
                                                                   const std::vector<MatchGuide>& guides, const MatchOptions& opts );
+
+    /// The TRACKS of a list of view pairs in ONE device call (psx_tracks_graph: one synchronisation, a number of launches
+    /// that grows neither with edges.size() nor with views.size()): the sets of descriptor rows in different views that
+    /// `matches` connect transitively.  `views` and `edges` are what matchPairsGraph took, `matches` what matchPairsGraph,
+    /// matchPairsGuidedGraph or -- as the inliers of their estimates -- estimate*Graph returned.  Tracks are over
+    /// descriptor rows, as the matches are: the several orientations of one keypoint are not merged.  Throws as
+    /// matchPairsGraph (a null referenced entry, views on different devices, an edge index outside `views`), when edges and
+    /// matches differ in size, for min_views < 2, and for a match whose descriptor index lies outside its own edge's views.
+    static Tracks buildTracks( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                               const std::vector<std::vector<Match>>& matches, const TrackOptions& opts = TrackOptions() );
 
     inline Feature*   getFeatures()    { return _ext; }
     inline Descriptor* getDescriptors() { return _ori; }
