@@ -606,8 +606,12 @@ int psx_match_pairs_guided_u8_dev(int device, const unsigned char* d_left, const
  * a device.  PSX_ERR_INVALID, with nothing touched and before any device call: everything psx_match_pairs_guided_u8 and
  * psx_match_pairs_many_u8 refuse; guides, d_rights, d_right_xys, r_lens or set_counts NULL with n_sets > 0; d_left or
  * d_left_xy NULL with l_len > 0; any guide that is neither valid nor of kind 0 -- EVERY guide is checked before anything
- * runs; a NULL d_rights[k] or d_right_xys[k] for a set that is not skipped and has rows.  Scratch (psx_match_release) and
- * thread safety as for psx_match_u8.  Synchronous, with exactly one stream synchronisation per call.  Only the byte form
+ * runs; a NULL d_rights[k] or d_right_xys[k] for a set that is not skipped and has rows.  PSX_ERR_NOMEM where a grid would
+ * not fit an int.  The call runs as psx_match_pairs_guided_graph_u8 on the star -- sets [left, rights...], edges {0, k + 1}
+ * --, whose forward search takes 64 workgroups per 256 left rows of every set that is neither skipped nor empty: with
+ * tens of millions of such sets of a handful of left rows each, 64 * (those sets) * ceil(l_len / 256) passes INT_MAX and
+ * the call returns PSX_ERR_NOMEM where it ran when the star had a grid of n_sets * ceil(l_len / 4) workgroups of its own.
+ * Scratch (psx_match_release) and thread safety as for psx_match_u8.  Synchronous, with exactly one stream synchronisation per call.  Only the byte form
  * exists, as for the unguided one-to-many call. */
 #define PSX_GUIDE_NONE 0         /* in the *_many and *_graph calls only: this set / edge is skipped */
 int psx_match_pairs_guided_many_u8(int device, const unsigned char* d_left, const float* d_left_xy, int l_len,

@@ -2,7 +2,7 @@
 // (include/popsift_hip.h, "geometric verification").
 //
 // ONE set of inline functions, compiled for the host (psx_affine_fit, psx_similarity_fit, psx_ransac_affine_ref,
-// psx_ransac_similarity_ref) and for the device (ransac.hip, ransac_many.hip): the two cannot drift apart.  Every step is
+// psx_ransac_similarity_ref) and for the device (ransac.hip, ransac_graph.hip): the two cannot drift apart.  Every step is
 // stated here operation by operation; the tests restate it from this comment.  The discipline is that of ransac_rule.h:
 // integer steps are uint32 / uint64 arithmetic; the fit is IEEE double, every operation rounded on its own in exactly the
 // order written (the translation units that include this header are compiled with -ffp-contract=off: no fused

@@ -27,8 +27,8 @@
 // 18 432 x 18 432 both ways took 0.506 ms instead of 0.468 under a window and 0.892 instead of 0.806 under an epipolar
 // band: profiles/match_guided_ms.txt).  The kernel writes a directed result in the layout of k_match_merge /
 // k_match_u8_merge, so the join of psx_match_pairs (k_pairs_count / k_pairs_write) runs on it unchanged.  The wave's
-// search itself is g_match_row of match_guided_core.h, which the one-to-many form (match_guided_many.hip) drives from a
-// set table.
+// search itself is g_match_row of match_guided_core.h, which the batched driver (match_guided_graph.hip) drives from an
+// edge table.
 #include "psx_internal.h"
 #include "guide_rule.h"
 #include "match_guided_core.h"

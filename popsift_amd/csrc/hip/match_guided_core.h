@@ -1,6 +1,6 @@
 // match_guided_core.h -- the guided directed search of ONE outer descriptor by one wave, stated once: k_match_guided
-// (match_guided.hip) hands it the operands of a single call, k_match_guided_many (match_guided_many.hip) those of one
-// entry of its set table.  Device code only; the dataflow is described at the top of match_guided.hip.
+// (match_guided.hip) hands it the operands of a single call, k_gg_match (match_guided_graph.hip) those of one
+// entry of its edge table.  Device code only; the dataflow is described at the top of match_guided.hip.
 #pragma once
 
 #include "psx_internal.h"

@@ -1,9 +1,12 @@
 // match_guided_graph.hip -- the guided re-match of a list of view pairs over N byte descriptor sets in one call:
 // psx_match_pairs_guided_graph_u8 (+ _dev) (include/popsift_hip.h).
 //
-// psx_match_pairs_guided_many_u8 (match_guided_many.hip) re-matches ONE left set against K right sets, each under its own
-// guide.  An edge list has a left view per edge: a loop of that call per left view pays a synchronisation, a table upload
-// and a count read-back per view, and a window or shortlist graph is all small stars.  Here the same wave-level search
+// This is the ONE batched guided re-match of the library.  psx_match_pairs_guided_u8 (match_guided.hip) is a fixed launch
+// sequence, one synchronisation and one count read-back per call; at 2k-4k descriptors per image that is what a loop over
+// view pairs pays per pair.  psx_match_pairs_guided_many_u8 -- ONE left set against K right sets, each under its own guide
+// -- is a star, an edge list whose edges share their left set: match_guided_many.hip only checks the star's arguments,
+// states it as such a list and calls psx_guided_edges_run below (a star costs nothing here against kernels written for
+// it: profiles/graph_chain_ms.txt).  The wave-level search of the single call
 // (g_match_row, match_guided_core.h, unchanged: one wave per outer descriptor) is driven over all edges by one grid per
 // step, its operands taken from an EDGE TABLE (match_guided_graph_plan.h): one entry per edge with both sides'
 // descriptors, positions and lengths, the edge's OWN guide, and its first forward row (which is its first line too) and
@@ -141,13 +144,15 @@ __global__ __launch_bounds__(256) void k_gg_write(const GGEdge* __restrict__ edg
 
 size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
 
-// host_pairs or d_pairs (the other is NULL; both NULL with capacity 0)
-int match_pairs_guided_graph(int device, const unsigned char* const* d_sets, const float* const* d_xys, const int* lens, int n_sets,
-                             const psx_view_edge* edges, int n_edges, const psx_guide* guides, const psx_match_opts* opts, void* host_pairs,
-                             void* d_pairs, int capacity, int* edge_counts, int* count)
+} // namespace
+
+// The ONE batched driver, behind the argument checks of its caller (psx_gg_args_ok for an edge list; the star's own,
+// match_guided_many.hip): internal, declared in match_scratch.h.  host_pairs or d_pairs (the other is NULL; both NULL with
+// capacity 0)
+int psx_guided_edges_run(int device, const unsigned char* const* d_sets, const float* const* d_xys, const int* lens, const psx_view_edge* edges,
+                         int n_edges, const psx_guide* guides, const psx_match_opts* opts, void* host_pairs, void* d_pairs, int capacity,
+                         int* edge_counts, int* count)
 {
-    if (!psx_gg_args_ok(d_sets, d_xys, lens, n_sets, edges, n_edges, guides, opts, host_pairs ? host_pairs : d_pairs, capacity, edge_counts, count))
-        return PSX_ERR_INVALID;
     const int E = n_edges;
     thread_local std::vector<psx_gg_edge> ep;
     ep.resize((size_t)E + 1);
@@ -229,6 +234,18 @@ int match_pairs_guided_graph(int device, const unsigned char* const* d_sets, con
     if (host_pairs && n > 0 && nrec > 0) memcpy(host_pairs, hp + off_rec, 16 * ((size_t)n < nrec ? (size_t)n : nrec));
     *count = n;
     return PSX_OK;
+}
+
+namespace {
+
+// the edge list's entry: its argument checks, then the driver
+int match_pairs_guided_graph(int device, const unsigned char* const* d_sets, const float* const* d_xys, const int* lens, int n_sets,
+                             const psx_view_edge* edges, int n_edges, const psx_guide* guides, const psx_match_opts* opts, void* host_pairs,
+                             void* d_pairs, int capacity, int* edge_counts, int* count)
+{
+    if (!psx_gg_args_ok(d_sets, d_xys, lens, n_sets, edges, n_edges, guides, opts, host_pairs ? host_pairs : d_pairs, capacity, edge_counts, count))
+        return PSX_ERR_INVALID;
+    return psx_guided_edges_run(device, d_sets, d_xys, lens, edges, n_edges, guides, opts, host_pairs, d_pairs, capacity, edge_counts, count);
 }
 
 } // namespace

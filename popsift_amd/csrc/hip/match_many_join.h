@@ -1,6 +1,6 @@
-// match_many_join.h -- the segmented pair join of the one-to-many calls, stated once: psx_match_pairs_many_u8
-// (match_many.hip), psx_match_pairs_guided_many_u8 (match_guided_many.hip) and psx_match_pairs_many (match_many_f32.hip)
-// queue it behind their directed passes.
+// match_many_join.h -- the segmented pair join of the one-to-many searches, stated once: psx_match_pairs_many_u8
+// (match_many.hip) and psx_match_pairs_many (match_many_f32.hip) queue it behind their directed passes.  (The guided
+// one-to-many call is a star handed to the edge list's driver, match_guided_graph.hip, and is joined there.)
 //
 // What it reads: fwd, K directed results (match_scratch.h) of 5 l_len ints each, set k's at fwd + 5 l_len k; bwd (with
 // the cross-check), the K sets' backward results, set k's at bwd + 5 * (its first row among all right rows); and of a

@@ -1,7 +1,8 @@
 // match_scratch.h -- what the matcher's translation units share (match.hip, match_guided.hip, match_many.hip,
 // match_many_f32.hip, match_guided_many.hip, match_graph.hip, match_guided_graph.hip, ransac.hip, ransac_many.hip,
 // ransac_graph.hip, tracks.hip):
-// the layout of a directed result, the per-thread scratch with its named buffers, and the runner of the pair join.
+// the layout of a directed result, the per-thread scratch with its named buffers, the runner of the pair join, and the
+// two batched drivers that a star form shares with its edge-list form.
 // Internal to the HIP library.
 #pragma once
 
@@ -34,9 +35,10 @@ __device__ __forceinline__ int psx_directed_best(const int* __restrict__ res, si
 // The buffers of a MatchScratch.  A buffer belongs to ONE use: calls queue work without waiting for the stream, so two
 // features sharing a buffer would alias under queued work.  F32: psx_match / psx_match_pairs, U8: psx_match_u8 /
 // psx_match_pairs_u8 (match.hip); GUIDED: match_guided.hip; MANY: the one-to-many search (match_many.hip), MANYF: its float form
-// (match_many_f32.hip); GMANY: the guided
-// one-to-many search (match_guided_many.hip); GRAPH: the pair search over an edge list (match_graph.hip).  RANSAC: ransac.hip AND the batched ransac_many.hip, which adds RMANY for its
-// tables: every call of either ends synchronised, so the two never have work queued on a thread's scratch at once.
+// (match_many_f32.hip); GRAPH: the pair search over an edge list (match_graph.hip); GGRAPH: the batched guided re-match
+// (match_guided_graph.hip), which the star form (match_guided_many.hip) runs too.  RANSAC: ransac.hip AND the one batched
+// driver (ransac_graph.hip, for an edge list and for the star of ransac_many.hip), which adds RGRAPH for its tables:
+// every call of any of them ends synchronised, so no two ever have work queued on a thread's scratch at once.
 enum MatchSlot {
     MS_F32_PARTIAL,      // the exact scan's per-chunk top-2
     MS_F32_RPERM,        // the exact scan's permuted right side
@@ -68,12 +70,6 @@ enum MatchSlot {
     MS_MANY_FWD,         // the forward direction's results of all sets
     MS_MANY_BWD,         // the backward direction's
     MS_MANY_TOT,         // the join's per-workgroup totals and their offsets
-    MS_RMANY_TABLES,     // the batched RANSAC's set table and its two block tables
-    MS_GMANY_TABLES,     // the guided one-to-many search (match_guided_many.hip): the set table and the backward block table
-    MS_GMANY_LINES,      // the left side's lines under every set's guide, for the backward direction
-    MS_GMANY_FWD,        // the forward direction's results of all sets
-    MS_GMANY_BWD,        // the backward direction's
-    MS_GMANY_TOT,        // the join's per-workgroup totals and their offsets
     MS_MANYF_TABLES,     // the float one-to-many search (match_many_f32.hip): the set / chunk / block tables
     MS_MANYF_STATE,      // the blocks' largest norms, the prefilter's parameters and its flag
     MS_MANYF_PERM,       // the scan: the permuted copy of every inner row
@@ -91,8 +87,8 @@ enum MatchSlot {
     MS_GRAPH_FWD,        // the forward direction's results of all edges
     MS_GRAPH_BWD,        // the backward direction's
     MS_GRAPH_TOT,        // the join's per-workgroup totals and their offsets
-    MS_RGRAPH_TABLES,    // RANSAC over an edge list (ransac_graph.hip): the edge table and its two block tables; the rest is RANSAC's
-    MS_GGRAPH_TABLES,    // the guided re-match over an edge list (match_guided_graph.hip): the edge table and the two {edge, row0} tables
+    MS_RGRAPH_TABLES,    // the batched RANSAC (ransac_graph.hip; an edge list or a star): the list table and its two block tables; the rest is RANSAC's
+    MS_GGRAPH_TABLES,    // the batched guided re-match (match_guided_graph.hip; an edge list or a star): the edge table and the two {edge, row0} tables
     MS_GGRAPH_LINES,     // the left rows' lines under their edge's guide, for the backward direction
     MS_GGRAPH_FWD,       // the forward direction's results of all edges
     MS_GGRAPH_BWD,       // the backward direction's
@@ -179,3 +175,19 @@ MatchScratch& psx_match_scratch();
 template <class Dist>
 int psx_pairs_finish(MatchScratch& sc, const int* d_fwd, int l_len, const int* d_bwd, const psx_match_opts* opts,
                      void* host_pairs, void* d_pairs, int capacity, int* count);
+
+// The batched drivers behind their argument checks, each stated once for an edge list and for a star; the star adapters
+// (ransac_many.hip, match_guided_many.hip) reach them through these.  Not part of the library's C API.
+//
+// ransac_graph.hip: n_lists pair lists with two sides each (psx_ransac_sides, ransac_many_plan.h), concatenated;
+// total_pairs = the sum of list_counts; model = PSX_RANSAC_MODEL_*.  host_pairs or d_pairs, host_inl or d_inl (the other
+// is NULL; both NULL with capacity 0).
+struct psx_ransac_sides;
+int psx_ransac_lists_run(int model, int device, const void* host_pairs, const void* d_pairs, const int* list_counts, const psx_ransac_sides* sides,
+                         int n_lists, long long total_pairs, const psx_ransac_opts* opts, psx_ransac_result* results, void* host_inl, void* d_inl,
+                         int capacity, int* count, float* host_models, int* host_counts);
+// match_guided_graph.hip: the edges over the set arrays, each under its own guide.  What psx_graph_args_ok asks of lens
+// and edges holds; a set that no live edge names (match_guided_graph_plan.h) may have NULL arrays.  host_pairs or d_pairs.
+int psx_guided_edges_run(int device, const unsigned char* const* d_sets, const float* const* d_xys, const int* lens, const psx_view_edge* edges,
+                         int n_edges, const psx_guide* guides, const psx_match_opts* opts, void* host_pairs, void* d_pairs, int capacity,
+                         int* edge_counts, int* count);

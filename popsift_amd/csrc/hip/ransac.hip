@@ -6,7 +6,7 @@
 //
 // The rule -- samples, fit, score, select, refit, inliers -- is ransac_rule.h (homography), fundamental_rule.h
 // (fundamental matrix) and affine_rule.h (affine, similarity), shared with the host references; the steps of the estimator around them are ransac_core.h, shared
-// with the batched call (ransac_many.hip).  This file is the call for ONE pair list: kernels that say where a step's
+// with the batched driver (ransac_graph.hip).  This file is the call for ONE pair list: kernels that say where a step's
 // operands live, and the sequence.  Kernels that evaluate the rule are templates on the model id (RModel).
 //   k_ransac_gather  r_gather per pair: the four floats, once, into a packed float4 array; everything after it streams 16 B
 //                    per lane, coalesced

@@ -1,4 +1,4 @@
-// ransac_core.h -- the steps of the RANSAC estimator, each stated once for ransac.hip (one pair list) and ransac_many.hip
+// ransac_core.h -- the steps of the RANSAC estimator, each stated once for ransac.hip (one pair list) and ransac_graph.hip
 // (many lists in one call): the traits of a model kind (RModel), the state a call keeps on the device (RHead, RState,
 // RRefit), the device pieces -- gather of one pair (r_gather), sample and fixed-size fit (r_sample_fit), the score walk
 // (r_score_walk), the workgroup arg-max (r_select), the keep test (r_keep), the refit decision (r_decide) -- and the host

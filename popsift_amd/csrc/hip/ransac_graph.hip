@@ -2,24 +2,37 @@
 // _ref), psx_ransac_fundamental_graph, psx_ransac_affine_graph, psx_ransac_similarity_graph (+ _dev, _ref each)
 // (include/popsift_hip.h).
 //
-// psx_ransac_*_many* (ransac_many.hip) verifies the K lists of ONE left view: its left position array is a kernel
-// argument.  psx_match_pairs_graph_u8* leaves E lists whose left view changes from edge to edge, and a window or shortlist
-// graph is all small stars: a loop of batched calls per left view pays a synchronisation and a table upload per view.
-// Here the launch sequence of ransac_many.hip runs once over all edges: "set" becomes "edge" in the block tables
-// (ransac_many_plan.h, unchanged), and the per-edge table entry carries BOTH position arrays and both lengths of its edge.
-// Only the gather reads positions; every kernel behind it works on the packed float4 correspondences and is the batched
-// call's, step by step.  The rule is ransac_rule.h, fundamental_rule.h and affine_rule.h, every step of the estimator is
-// the ONE statement of ransac_core.h that the single call runs too: edge e's result is the single call's, bit for bit.
+// This is the ONE batched RANSAC of the library.  psx_ransac_*_dev (ransac.hip) is a fixed sequence of launches and one
+// or two synchronisations per pair list; a list has a few hundred to a few thousand pairs, so the kernels are nearly empty
+// and the call is launch latency and round trips, paid again for every list.  Here the same sequence runs once over E
+// LISTS WITH TWO SIDES (psx_ransac_sides, ransac_many_plan.h), every kernel one grid over all lists, driven by block
+// tables in which no block crosses a list boundary (psx_ransac_many_blocks).  The per-list table entry carries BOTH
+// position arrays and both lengths of its list, so the left view may change from list to list:
+//   an edge list (psx_ransac_*_graph*, below)         edge e's sides are d_xys[edges[e].left] and d_xys[edges[e].right]
+//   a star (psx_ransac_*_many*, ransac_many.hip)      the K lists of ONE left view: every entry names the same left array.
+//                                                     That unit only checks the star's arguments and states the sides; it
+//                                                     reaches ransac_lists_run through psx_ransac_lists_run
+// A star costs nothing here against a gather that takes the left array as a kernel argument: profiles/graph_chain_ms.txt.
+// Only the gather reads positions; every kernel behind it works on the packed float4 correspondences.  The rule is
+// ransac_rule.h, fundamental_rule.h and affine_rule.h, every step of the estimator is the ONE statement of ransac_core.h
+// that the single call runs too: list e's result is the single call's, bit for bit.  "Edge" in the names below is a list.
 //   k_rgraph_gather  r_gather per pair of every edge that has a model to estimate, the pair's indices checked against ITS
 //                    OWN edge's two lengths, both position arrays through the edge table
 //   k_rgraph_hyp     one lane per (edge, hypothesis): r_sample_fit on the edge's own n_e; below the minimum: zeros
-//   k_rgraph_score   r_score_walk over a block of G_HB hypotheses; the block-table entry is workgroup uniform
+//   k_rgraph_score   the hot kernel: r_score_walk over a block of G_HB hypotheses.  The block-table entry and with it the
+//                    model address are workgroup uniform (scalar loads).  A wave owns G_PPL x 64 CONSECUTIVE pairs of its
+//                    block, and a wave without a resident pair leaves before the walk: a short list's last block is
+//                    mostly such waves
 //   k_rgraph_select  r_select, one workgroup per edge
-//   k_rgraph_count / k_rgraph_scan / k_rgraph_write   r_keep into the stable compaction of wg_compact.h, segmented by edge
+//   k_rgraph_count / k_rgraph_scan / k_rgraph_write   r_keep into the stable compaction of wg_compact.h, segmented by edge:
+//                    one total per 256-pair workgroup in edge-major order, an exclusive scan of the totals by one
+//                    workgroup, one 16-byte store per survivor; an edge's total is the difference of the scan at its
+//                    boundaries.  No atomics.  The payload is any 16-byte record array
 //   k_rgraph_decide  r_decide, one lane per edge
-// The refit's fit is serial by definition and runs on the host, as in the batched call: ONE compaction brings every
-// edge's winner correspondences, ONE upload carries all refit models.
-// Launches per call, whatever n_edges and n_sets are: the table copy and a memset, then gather, hyp, score, select and the
+// The refit's fit is serial by definition and runs on the host: ONE compaction brings every edge's winner
+// correspondences through the pinned staging buffer, the host fits the edges whose refit is due, ONE upload carries all
+// refit models with a per-edge "tried" word, and the score kernel runs once more with one model per edge.
+// Launches per call, whatever the number of lists is: the table copy and a memset, then gather, hyp, score, select and the
 // compaction's 3 -- 7 kernels and 1 synchronisation without the refit; with it 5 more (score, decide, the compaction's 3)
 // -- 12 kernels and 2 synchronisations.
 #include "psx_internal.h"
@@ -29,6 +42,7 @@
 
 #include <cstring>
 #include <new>
+#include <vector>
 
 namespace {
 
@@ -195,23 +209,22 @@ void queue_compact(const RGQueue& q, const void* src, void* out, int cap)
                        q.d_offs, static_cast<const int4*>(src), static_cast<int4*>(out), cap);
 }
 
-// host_pairs or d_pairs_in; host_inl or d_inl (the other is NULL; both NULL with capacity 0)
+// The ONE batched driver: E lists with two sides each (psx_ransac_sides, ransac_many_plan.h), their pairs concatenated,
+// total_pairs = the sum of list_counts.  The caller has checked its arguments (psx_ransac_graph_args_ok for an edge list,
+// psx_ransac_many_args_ok for a star).  host_pairs or d_pairs_in; host_inl or d_inl (the other is NULL; both NULL with
+// capacity 0)
 template <int KIND>
-int ransac_graph_run(int device, const void* host_pairs, const void* d_pairs_in, const int* edge_counts, const psx_view_edge* edges, int n_edges,
-                     const float* const* d_xys, const int* lens, int n_sets, const psx_ransac_opts* opts, psx_ransac_result* results,
-                     void* host_inl, void* d_inl, int capacity, int* count, float* host_models, int* host_counts)
+int ransac_lists_run(int device, const void* host_pairs, const void* d_pairs_in, const int* edge_counts, const psx_ransac_sides* sides, int n_lists,
+                     long long total_pairs, const psx_ransac_opts* opts, psx_ransac_result* results, void* host_inl, void* d_inl, int capacity,
+                     int* count, float* host_models, int* host_counts)
 {
-    long long total_pairs = 0;
-    if (!psx_ransac_graph_args_ok(host_pairs ? host_pairs : d_pairs_in, edge_counts, edges, n_edges, d_xys, lens, n_sets, opts, results,
-                                  host_inl ? host_inl : d_inl, capacity, count, &total_pairs))
-        return PSX_ERR_INVALID;
     constexpr int MIN = RModel<KIND>::MIN;
-    const int E = n_edges, N = opts->hypotheses, n = (int)total_pairs;
+    const int E = n_lists, N = opts->hypotheses, n = (int)total_pairs;
     const long long nsb = psx_ransac_many_blocks(edge_counts, E, MIN, PSX_RANSAC_MANY_SCORE_ROWS, nullptr, 0);
     const long long ncb = psx_ransac_many_blocks(edge_counts, E, MIN, PSX_RANSAC_MANY_ROWS, nullptr, 0);
     if (ncb == 0) { psx_ransac_many_none(E, N, results, count, host_models, host_counts); return PSX_OK; }
     for (int e = 0; e < E; e++)                                            // no index can lie inside an empty array
-        if (edge_counts[e] >= MIN && (lens[edges[e].left] == 0 || lens[edges[e].right] == 0)) return PSX_ERR_INVALID;
+        if (edge_counts[e] >= MIN && (sides[e].l_len == 0 || sides[e].r_len == 0)) return PSX_ERR_INVALID;
     const long long score_wgs = nsb * ((N + G_HB - 1) / G_HB), hyp_wgs = (long long)E * ((N + 63) / 64);
     if (score_wgs > 0x7fffffffLL || hyp_wgs > 0x7fffffffLL) return PSX_ERR_NOMEM;
     if (hipSetDevice(device) != hipSuccess) return PSX_ERR_HIP;
@@ -248,9 +261,8 @@ int ransac_graph_run(int device, const void* host_pairs, const void* d_pairs_in,
         psx_ransac_many_blocks(edge_counts, E, MIN, PSX_RANSAC_MANY_ROWS, tmp, ncb);
         long long off = 0;
         for (int e = 0; e < E; e++) {
-            const int l = edges[e].left, r = edges[e].right;
-            he[e] = RGEdge{reinterpret_cast<const float2*>(d_xys[l]), reinterpret_cast<const float2*>(d_xys[r]), lens[l], lens[r], edge_counts[e],
-                           (int)off, 0, 0, 0, 0};
+            he[e] = RGEdge{reinterpret_cast<const float2*>(sides[e].lxy), reinterpret_cast<const float2*>(sides[e].rxy), sides[e].l_len, sides[e].r_len,
+                           edge_counts[e], (int)off, 0, 0, 0, 0};
             off += edge_counts[e];
         }
         for (long long b = 0; b < ncb; b++) {
@@ -338,6 +350,23 @@ int ransac_graph_run(int device, const void* host_pairs, const void* d_pairs_in,
     return PSX_OK;
 }
 
+// the edge list's entry: its argument checks, then its sides to the driver
+template <int KIND>
+int ransac_graph_run(int device, const void* host_pairs, const void* d_pairs_in, const int* edge_counts, const psx_view_edge* edges, int n_edges,
+                     const float* const* d_xys, const int* lens, int n_sets, const psx_ransac_opts* opts, psx_ransac_result* results,
+                     void* host_inl, void* d_inl, int capacity, int* count, float* host_models, int* host_counts)
+{
+    long long total_pairs = 0;
+    if (!psx_ransac_graph_args_ok(host_pairs ? host_pairs : d_pairs_in, edge_counts, edges, n_edges, d_xys, lens, n_sets, opts, results,
+                                  host_inl ? host_inl : d_inl, capacity, count, &total_pairs))
+        return PSX_ERR_INVALID;
+    thread_local std::vector<psx_ransac_sides> sides;
+    sides.resize((size_t)n_edges);
+    for (int e = 0; e < n_edges; e++) sides[(size_t)e] = psx_ransac_graph_side(edges, d_xys, lens, e);
+    return ransac_lists_run<KIND>(device, host_pairs, d_pairs_in, edge_counts, sides.data(), n_edges, total_pairs, opts, results, host_inl, d_inl,
+                                  capacity, count, host_models, host_counts);
+}
+
 int graph_ref(int model, const void* pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges, const float* const* xys,
               const int* lens, int n_sets, const psx_ransac_opts* opts, psx_ransac_result* results, void* inliers, int capacity, int* count,
               float* models, int* counts)
@@ -354,6 +383,25 @@ int graph_ref(int model, const void* pairs, const int* edge_counts, const psx_vi
 }
 
 } // namespace
+
+// the driver for the star adapter (ransac_many.hip): internal, declared in match_scratch.h
+int psx_ransac_lists_run(int model, int device, const void* host_pairs, const void* d_pairs, const int* list_counts, const psx_ransac_sides* sides,
+                         int n_lists, long long total_pairs, const psx_ransac_opts* opts, psx_ransac_result* results, void* host_inl, void* d_inl,
+                         int capacity, int* count, float* host_models, int* host_counts)
+{
+#define PSX_RUN(KIND)                                                                                                                         \
+    case KIND:                                                                                                                                \
+        return ransac_lists_run<KIND>(device, host_pairs, d_pairs, list_counts, sides, n_lists, total_pairs, opts, results, host_inl, d_inl, \
+                                      capacity, count, host_models, host_counts)
+    switch (model) {
+        PSX_RUN(PSX_RANSAC_MODEL_HOMOGRAPHY);
+        PSX_RUN(PSX_RANSAC_MODEL_FUNDAMENTAL);
+        PSX_RUN(PSX_RANSAC_MODEL_AFFINE);
+        PSX_RUN(PSX_RANSAC_MODEL_SIMILARITY);
+    }
+#undef PSX_RUN
+    return PSX_ERR_INVALID;
+}
 
 // the three forms of one model: lists and inliers on the host, both in HBM, and the host reference
 #define PSX_RANSAC_GRAPH_FORMS(name, KIND)                                                                                                      \

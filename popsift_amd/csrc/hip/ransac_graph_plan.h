@@ -9,8 +9,8 @@
 // ransac_many_plan.h (psx_ransac_many_blocks over edge_counts), unchanged.  What is new is that BOTH position arrays of a
 // list come from the set array, through its edge: d_xys[edges[e].left] and d_xys[edges[e].right].
 //
-// The host reference is the loop over the single-list rule (psx_ransac_host_rule, affine_rule.h), nothing of which is
-// restated here.
+// The host reference is the loop over the single-list rule, which stands once for the star and the edge list
+// (psx_ransac_lists_host, ransac_many_plan.h): here are the edge list's own checks and its sides.
 #pragma once
 
 #include "match_graph_plan.h"
@@ -37,9 +37,15 @@ inline bool psx_ransac_graph_args_ok(const void* pairs, const int* edge_counts, 
     return true;
 }
 
-// The host reference (psx_ransac_*_graph_ref): the loop over the single-list rule, edge e on the two position arrays its
-// edge names.  Two passes: every argument and every pair index of every edge -- against ITS OWN two lengths -- is checked
-// before anything is written.  `scratch` holds as many psx_ransac_pt as the longest list has pairs and is the caller's.
+// edge e's list: both sides through its edge
+inline psx_ransac_sides psx_ransac_graph_side(const psx_view_edge* edges, const float* const* xys, const int* lens, int e)
+{
+    const int l = edges[e].left, r = edges[e].right;
+    return psx_ransac_sides{xys[l], lens[l], xys[r], lens[r]};
+}
+
+// The host reference (psx_ransac_*_graph_ref): the edge list's argument checks, every pair index of every edge against
+// ITS OWN two lengths -- all before anything is written --, then the loop over its sides (psx_ransac_lists_host).
 inline int psx_ransac_graph_host(int kind, const void* pairs, const int* edge_counts, const psx_view_edge* edges, int n_edges,
                                  const float* const* xys, const int* lens, int n_sets, const psx_ransac_opts* opts, psx_ransac_result* results,
                                  void* inliers, int capacity, int* count, float* models, int* counts, psx_ransac_pt* scratch)
@@ -47,32 +53,13 @@ inline int psx_ransac_graph_host(int kind, const void* pairs, const int* edge_co
     long long total = 0;
     if (!psx_ransac_graph_args_ok(pairs, edge_counts, edges, n_edges, xys, lens, n_sets, opts, results, inliers, capacity, count, &total))
         return PSX_ERR_INVALID;
-    const int MIN = psx_ransac_many_min(kind);
-    const int* rec = static_cast<const int*>(pairs);                             // 4 ints per record
+    const int* rec = static_cast<const int*>(pairs);
     size_t at = 0;
     for (int e = 0; e < n_edges; e++) {
-        if (edge_counts[e] >= MIN && scratch == nullptr) return PSX_ERR_INVALID;
         const int nl = lens[edges[e].left], nr = lens[edges[e].right];
         for (int p = 0; p < edge_counts[e]; p++, at++)
             if (rec[4 * at] < 0 || rec[4 * at] >= nl || rec[4 * at + 1] < 0 || rec[4 * at + 1] >= nr) return PSX_ERR_INVALID;
     }
-    const int N = opts->hypotheses;
-    psx_ransac_many_none(n_edges, N, results, count, models, counts);
-    const psx_ransac_host_fn rule = psx_ransac_many_rule(kind);
-    long long written = 0;                                                       // inliers of the edges before e
-    at = 0;
-    for (int e = 0; e < n_edges; at += (size_t)edge_counts[e], e++) {
-        if (edge_counts[e] < MIN) continue;
-        const int l = edges[e].left, r = edges[e].right;
-        const int room = written < capacity ? (int)(capacity - written) : 0;
-        int c = 0;
-        const int rc = rule(rec + 4 * at, edge_counts[e], xys[l], lens[l], xys[r], lens[r], opts, results + e,
-                            room > 0 ? static_cast<char*>(inliers) + 16 * (size_t)written : nullptr, room, &c,
-                            models != nullptr ? models + 9 * (size_t)e * (size_t)N : nullptr, counts != nullptr ? counts + (size_t)e * (size_t)N : nullptr,
-                            scratch);
-        if (rc != PSX_OK) return rc;                                             // not reached: everything was checked above
-        written += c;
-    }
-    *count = (int)written;
-    return PSX_OK;
+    return psx_ransac_lists_host(kind, pairs, edge_counts, n_edges, [=](int e) { return psx_ransac_graph_side(edges, xys, lens, e); }, opts, results,
+                                 inliers, capacity, count, models, counts, scratch);
 }

@@ -1,8 +1,8 @@
 // ransac_many_plan.h -- the host side of the batched geometric verification (psx_ransac_homography_many*,
 // psx_ransac_fundamental_many*, psx_ransac_many_plan; include/popsift_hip.h): the argument checks every form shares, the
-// block table the kernels of ransac_many.hip walk, and the host reference.
+// block table the kernels of the one batched driver (ransac_graph.hip) walk, and the host reference.
 //
-// Plain C++14, no HIP: ransac_many.hip builds its device tables with these functions, psx_ransac_many_plan hands them
+// Plain C++14, no HIP: ransac_graph.hip builds its device tables with these functions, psx_ransac_many_plan hands them
 // out, and a stand-alone program can include the header alone (tests/cpp/ransac_many_plan_san.cpp).
 //
 // The input is the concatenation P_0 .. P_{K-1} of K pair lists, set_counts[k] = |P_k|.  It is cut into
@@ -13,7 +13,8 @@
 //
 // The host reference is the loop over the single-list rule (psx_ransac_homography_host, psx_ransac_fundamental_host,
 // psx_ransac_affine_host, psx_ransac_similarity_host: ransac_rule.h, fundamental_rule.h, affine_rule.h), nothing of which
-// is restated here.
+// is restated here.  The loop stands once, psx_ransac_lists_host over LISTS WITH TWO SIDES (psx_ransac_sides): the star's
+// reference below and the edge list's (ransac_graph_plan.h) check their own arguments and indices and hand it their sides.
 #pragma once
 
 #include "affine_rule.h"
@@ -91,9 +92,53 @@ inline void psx_ransac_many_none(int n_sets, int N, psx_ransac_result* results, 
 inline psx_ransac_host_fn psx_ransac_many_rule(int model) { return psx_ransac_host_rule(model); }
 inline int psx_ransac_many_min(int model) { return psx_ransac_host_min(model); }
 
-// The host reference (psx_ransac_*_many_ref): the loop over the single-list rule.  Two passes: every argument and every
-// pair index of every set is checked before anything is written.  `scratch` holds as many psx_ransac_pt as the longest
-// set has pairs and is the caller's (a stand-alone program hands exact-size heap arrays to a sanitizer).
+// A LIST WITH TWO SIDES: what the star and the edge-list forms hand to the one driver (ransac_graph.hip) and to the one
+// host loop below.  A star's lists share their left side; an edge's two sides come from the set array through its edge.
+// The pointers are host or device pointers alike.
+struct psx_ransac_sides { const float* lxy; int l_len; const float* rxy; int r_len; };
+
+// the star's list k: the shared left array and set k's right array
+inline psx_ransac_sides psx_ransac_many_side(const float* left_xy, int l_len, const float* const* right_xys, const int* r_lens, int k)
+{
+    return psx_ransac_sides{left_xy, l_len, right_xys[k], r_lens[k]};
+}
+
+// The host reference's loop, stated once: list e under the single-list rule on its own two sides, side_of(e).  The caller
+// has checked its arguments and every pair index against its own lengths; nothing is written before the last refusal.
+// `scratch` holds as many psx_ransac_pt as the longest list has pairs and is the caller's (a stand-alone program hands
+// exact-size heap arrays to a sanitizer).
+template <class SideOf>
+inline int psx_ransac_lists_host(int kind, const void* pairs, const int* list_counts, int n_lists, SideOf side_of, const psx_ransac_opts* opts,
+                                 psx_ransac_result* results, void* inliers, int capacity, int* count, float* models, int* counts,
+                                 psx_ransac_pt* scratch)
+{
+    const int MIN = psx_ransac_many_min(kind);
+    for (int e = 0; e < n_lists; e++)
+        if (list_counts[e] >= MIN && scratch == nullptr) return PSX_ERR_INVALID;
+    const int* rec = static_cast<const int*>(pairs);                             // 4 ints per record
+    const int N = opts->hypotheses;
+    psx_ransac_many_none(n_lists, N, results, count, models, counts);
+    const psx_ransac_host_fn rule = psx_ransac_many_rule(kind);
+    long long written = 0;                                                       // inliers of the lists before e
+    size_t at = 0;
+    for (int e = 0; e < n_lists; at += (size_t)list_counts[e], e++) {
+        if (list_counts[e] < MIN) continue;
+        const psx_ransac_sides s = side_of(e);
+        const int room = written < capacity ? (int)(capacity - written) : 0;
+        int c = 0;
+        const int rc = rule(rec + 4 * at, list_counts[e], s.lxy, s.l_len, s.rxy, s.r_len, opts, results + e,
+                            room > 0 ? static_cast<char*>(inliers) + 16 * (size_t)written : nullptr, room, &c,
+                            models != nullptr ? models + 9 * (size_t)e * (size_t)N : nullptr, counts != nullptr ? counts + (size_t)e * (size_t)N : nullptr,
+                            scratch);
+        if (rc != PSX_OK) return rc;                                             // not reached: everything was checked above
+        written += c;
+    }
+    *count = (int)written;
+    return PSX_OK;
+}
+
+// The host reference (psx_ransac_*_many_ref): the star's argument checks, every pair index of every set against the left
+// length and ITS OWN right length -- all before anything is written --, then the loop over its sides.
 inline int psx_ransac_many_host(int kind, const void* pairs, const int* set_counts, int n_sets, const float* left_xy, int nl,
                                 const float* const* right_xys, const int* r_lens, const psx_ransac_opts* opts, psx_ransac_result* results,
                                 void* inliers, int capacity, int* count, float* models, int* counts, psx_ransac_pt* scratch)
@@ -101,30 +146,11 @@ inline int psx_ransac_many_host(int kind, const void* pairs, const int* set_coun
     long long total = 0;
     if (!psx_ransac_many_args_ok(pairs, set_counts, n_sets, left_xy, nl, right_xys, r_lens, opts, results, inliers, capacity, count, &total))
         return PSX_ERR_INVALID;
-    const int MIN = psx_ransac_many_min(kind);
-    const int* rec = static_cast<const int*>(pairs);                             // 4 ints per record
+    const int* rec = static_cast<const int*>(pairs);
     size_t at = 0;
-    for (int k = 0; k < n_sets; k++) {
-        if (set_counts[k] >= MIN && scratch == nullptr) return PSX_ERR_INVALID;
+    for (int k = 0; k < n_sets; k++)
         for (int p = 0; p < set_counts[k]; p++, at++)
             if (rec[4 * at] < 0 || rec[4 * at] >= nl || rec[4 * at + 1] < 0 || rec[4 * at + 1] >= r_lens[k]) return PSX_ERR_INVALID;
-    }
-    const int N = opts->hypotheses;
-    psx_ransac_many_none(n_sets, N, results, count, models, counts);
-    const psx_ransac_host_fn rule = psx_ransac_many_rule(kind);
-    long long written = 0;                                                       // inliers of the sets before k
-    at = 0;
-    for (int k = 0; k < n_sets; at += (size_t)set_counts[k], k++) {
-        if (set_counts[k] < MIN) continue;
-        const int room = written < capacity ? (int)(capacity - written) : 0;
-        int c = 0;
-        const int rc = rule(rec + 4 * at, set_counts[k], left_xy, nl, right_xys[k], r_lens[k], opts, results + k,
-                            room > 0 ? static_cast<char*>(inliers) + 16 * (size_t)written : nullptr, room, &c,
-                            models != nullptr ? models + 9 * (size_t)k * (size_t)N : nullptr, counts != nullptr ? counts + (size_t)k * (size_t)N : nullptr,
-                            scratch);
-        if (rc != PSX_OK) return rc;                                             // not reached: everything was checked above
-        written += c;
-    }
-    *count = (int)written;
-    return PSX_OK;
+    return psx_ransac_lists_host(kind, pairs, set_counts, n_sets, [=](int k) { return psx_ransac_many_side(left_xy, nl, right_xys, r_lens, k); },
+                                 opts, results, inliers, capacity, count, models, counts, scratch);
 }

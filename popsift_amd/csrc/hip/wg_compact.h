@@ -1,5 +1,5 @@
 // wg_compact.h -- the stable compaction that the pair join (match.hip), the one-to-many join (match_many.hip) and the
-// RANSAC inlier lists (ransac.hip, ransac_many.hip) share.  One lane per row, workgroups of 256 threads, two launches: a count kernel leaves
+// RANSAC inlier lists (ransac.hip; ransac_graph.hip, the batched driver of the star and edge-list forms) share.  One lane per row, workgroups of 256 threads, two launches: a count kernel leaves
 // one total per workgroup, a write kernel evaluates its rule again and stores each survivor at
 //   (survivors of the workgroups before its own) + (survivors of the waves before its own) + (ballot bits below its lane)
 // -- ascending row order, no atomics, nothing depends on arrival order.  The kernels keep their own rule and record and
@@ -31,8 +31,8 @@ __device__ __forceinline__ int wg_offset(unsigned long long m, const int (&s_cnt
     return woff + lane_rank(m);
 }
 
-// The body of a scan kernel of ONE workgroup of 1024 threads (k_many_scan, match_many.hip; k_rmany_scan,
-// ransac_many.hip): offs[w] = the totals before workgroup w, offs[n] = all of them.  1024 totals per round: a wave scan
+// The body of a scan kernel of ONE workgroup of 1024 threads (k_many_scan, match_many.hip; k_rgraph_scan,
+// ransac_graph.hip): offs[w] = the totals before workgroup w, offs[n] = all of them.  1024 totals per round: a wave scan
 // (shuffles), the 16 wave sums through LDS, the carry of the rounds before.
 __device__ __forceinline__ void wg_scan_totals(const int* __restrict__ wg_tot, int n, int* __restrict__ offs)
 {
@@ -59,7 +59,7 @@ __device__ __forceinline__ void wg_scan_totals(const int* __restrict__ wg_tot, i
 
 // This lane's slot when the survivors before the workgroup are the sum of wg_tot[0 .. blockIdx.x): every workgroup scans
 // for itself (at most gridDim.x ints each -- quadratic over the grid, for grids of a few hundred workgroups; k_many_write
-// and k_rmany_write take their base from a scan kernel instead).  The last workgroup writes the total.
+// and k_rgraph_write take their base from a scan kernel instead).  The last workgroup writes the total.
 __device__ __forceinline__ int wg_slot(unsigned long long m, const int* __restrict__ wg_tot, int* __restrict__ total)
 {
     __shared__ int s_part[4], s_cnt[4];

@@ -56,6 +56,10 @@ def test_entry_points_declared_and_bound(capi):
         assert slot in scratch and slot in gsrc, slot
     assert "MS_GMANY_" not in gsrc and "MS_GRAPH_" not in gsrc and "MS_GUIDED_" not in gsrc
     assert "MS_RGRAPH_TABLES" in scratch and "MS_RGRAPH_TABLES" in rsrc and "MS_RMANY_TABLES" not in rsrc
+    # the star forms run these two drivers: their own scratch slots are gone from every file
+    for name in sorted(os.listdir(hip)):
+        text = open(os.path.join(hip, name)).read()
+        assert "MS_RMANY_TABLES" not in text and "MS_GMANY_" not in text, name
     fh = open(os.path.join(ROOT, "popsift_amd", "csrc", "include", "popsift", "features.h")).read()
     for name in ("estimateHomographyGraph(", "estimateFundamentalGraph(", "estimateAffineGraph(", "estimateSimilarityGraph(", "matchPairsGuidedGraph("):
         assert name in fh, name

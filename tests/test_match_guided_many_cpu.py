@@ -32,13 +32,22 @@ def test_entry_points_declared_and_bound(capi):
     hip = os.path.join(ROOT, "popsift_amd", "csrc", "hip")
     src = open(os.path.join(hip, "match_guided_many.hip")).read()
     many = open(os.path.join(hip, "match_many.hip")).read()
-    # the segmented join and the wave's search are stated once, in headers both users include
-    for text in (src, many):
-        assert '#include "match_many_join.h"' in text and "void k_many_count(" not in text and "void k_many_write(" not in text
+    # the segmented join is stated once, in a header its users include
+    assert '#include "match_many_join.h"' in many and "void k_many_count(" not in many and "void k_many_write(" not in many
+    # the star form is an adapter: no device code and no launch of its own; it hands the star to the edge list's driver
+    for piece in ("__global__", "__device__", "__ballot", "atomic", "hipLaunchKernelGGL", "<<<", "match_many_join.h", "match_guided_core.h",
+                  "g_match_row"):
+        assert piece not in src, piece
+    assert "psx_guided_edges_run(" in src and "psx_view_edge{0, k + 1}" in src
+    # the wave's search is stated once, in the header the single call and the batched driver include
+    graph = open(os.path.join(hip, "match_guided_graph.hip")).read()
     single = open(os.path.join(hip, "match_guided.hip")).read()
-    for text in (src, single):
-        assert '#include "match_guided_core.h"' in text and "__ballot" not in text
-    assert "atomic" not in src                              # nothing in the ranking depends on arrival order
+    for text in (graph, single):
+        assert '#include "match_guided_core.h"' in text
+    assert "__ballot" not in single
+    for piece in ("g_match_row<unsigned char, int, false>(", "g_match_row<unsigned char, int, true>(", "int psx_guided_edges_run("):
+        assert graph.count(piece) == 1, piece
+    assert "atomic" not in graph.split("#include")[-1]      # the code: nothing in the ranking depends on arrival order
     fh = open(os.path.join(ROOT, "popsift_amd", "csrc", "include", "popsift", "features.h")).read()
     assert "matchPairsGuidedMany(" in fh and "MatchGuide none()" in fh
 

@@ -35,10 +35,13 @@ def test_entry_points_declared_and_bound(capi):
     plan = open(os.path.join(hip, "ransac_many_plan.h")).read()
     assert "hip/hip_runtime.h" not in plan and "__global__" not in plan and "__device__" not in plan      # plain C++
     src = open(os.path.join(hip, "ransac_many.hip")).read()
+    drv = open(os.path.join(hip, "ransac_graph.hip")).read()     # the one batched driver, for a star and for an edge list
     one = open(os.path.join(hip, "ransac.hip")).read()
     core = open(os.path.join(hip, "ransac_core.h")).read()
-    for piece in ('#include "ransac_many_plan.h"', '#include "ransac_core.h"', "wg_scan_totals("):
-        assert piece in src, piece
+    assert '#include "ransac_many_plan.h"' in src and "psx_ransac_lists_run(" in src and "psx_ransac_many_args_ok(" in src
+    for piece in ('#include "ransac_graph_plan.h"', '#include "ransac_core.h"', "wg_scan_totals(", "int psx_ransac_lists_run("):
+        assert piece in drv, piece
+    assert '#include "ransac_many_plan.h"' in open(os.path.join(hip, "ransac_graph_plan.h")).read()
     # the rule headers are used as they are: the device pieces call them, nothing is restated -- and the pieces stand once,
     # in the header that the single call's kernels use too
     assert '#include "ransac_core.h"' in one
@@ -46,9 +49,17 @@ def test_entry_points_declared_and_bound(capi):
                   "psx_fundamental_fit_rule<PSX_FUND_MIN>(", "psx_guide_left(", "psx_guide_right("):
         assert core.count(piece) >= 1, piece
     for piece in ("psx_homography_fit_rule<4>(", "psx_fundamental_fit_rule<PSX_FUND_MIN>(", "psx_guide_left(", "psx_guide_right("):
-        assert piece not in src and piece not in one, piece
-    for piece in ("r_gather(", "r_sample_fit<KIND>(", "r_score_walk<KIND, ", "r_select(", "r_keep<KIND>(", "r_decide<KIND>("):
-        assert piece in src and piece in one, piece
+        assert piece not in src and piece not in drv and piece not in one, piece
+    pieces = ("r_gather(", "r_sample_fit<KIND>(", "r_score_walk<KIND, ", "r_select(", "r_keep<KIND>(", "r_decide<KIND>(")
+    for piece in pieces:
+        assert piece in drv and piece in one, piece
+    # the batched sequence is stated once: the star form is an adapter without device code or a launch of its own
+    for piece in pieces + ("wg_scan_totals(", "__global__", "__device__", "hipLaunchKernelGGL", "<<<", '#include "ransac_core.h"'):
+        assert piece not in src, piece
+    # ... and so is the host reference's loop over the single-list rule
+    gplan = open(os.path.join(hip, "ransac_graph_plan.h")).read()
+    assert plan.count("psx_ransac_many_rule(kind)") == 1 and "psx_ransac_many_rule(" not in gplan
+    assert plan.count("inline int psx_ransac_lists_host(") == 1 and "return psx_ransac_lists_host(" in plan and "return psx_ransac_lists_host(" in gplan
     fh = open(os.path.join(ROOT, "popsift_amd", "csrc", "include", "popsift", "features.h")).read()
     assert "estimateHomographyMany(" in fh and "estimateFundamentalMany(" in fh
 
