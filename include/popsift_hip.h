@@ -435,7 +435,7 @@ int psx_match_many_plan(int l_len, const int* r_lens, int n_sets, int backward,
  * every edge is checked before anything runs, so n_sets = 0 admits no edge --; the sum over the edges of lens[left] (the
  * number of pairs that can exist) or of lens[right] (the backward rows) above INT_MAX.  PSX_ERR_NOMEM where a grid or a
  * table would not fit an int.  Scratch (psx_match_release) and thread safety as for psx_match_u8.  Synchronous, with
- * exactly one stream synchronisation per call.  There is no float form.  The next two links over the same edge list,
+ * exactly one stream synchronisation per call.  The float form is psx_match_pairs_graph (below).  The next two links over the same edge list,
  * whatever its order: psx_ransac_*_graph* and psx_match_pairs_guided_graph_u8* ("A LIST OF VIEW PAIRS", below). */
 typedef struct psx_view_edge { int left, right; } psx_view_edge;   /* indices into the set array */
 int psx_match_pairs_graph_u8(int device, const unsigned char* const* d_sets, const int* lens, int n_sets,
@@ -511,6 +511,63 @@ int psx_match_many_f32_plan(int l_len, const int* r_lens, int n_sets, int flags,
  * synchronisations made, counted where the call launches and synchronises.  PSX_ERR_INVALID for out == NULL. */
 typedef struct psx_many_f32_info { int path, fell_back, launches, syncs; } psx_many_f32_info;
 int psx_match_many_f32_last(psx_many_f32_info* out);
+
+/* ---- a list of view pairs over N descriptor sets (float descriptors) --------------------------
+ * The float form of psx_match_pairs_graph_u8: its contract, word for word, with psx_match_pairs in place of
+ * psx_match_pairs_u8.  d_sets[s] is a DEVICE pointer to lens[s] descriptors of 128 floats, 16-byte aligned (separate
+ * allocations, slices of one buffer, or the same pointer more than once).  With P_e = the list psx_match_pairs returns for
+ * (d_sets[edges[e].left], d_sets[edges[e].right], opts) at unlimited capacity, bit for bit (float distances compared as bit
+ * patterns):
+ *   - the result is the concatenation P_0, P_1, ..., P_{n_edges-1} in the order of the edge list, which is neither sorted
+ *     nor deduplicated; a duplicate, both orders of a pair and left == right are ordinary edges, nothing is special-cased;
+ *   - ties keep the earlier index, a NaN distance never wins, 0/0 fails the ratio test, a missing second neighbour is +inf;
+ *   - edge_counts[e] = |P_e|, *count their sum: always the totals.  The first min(*count, capacity) records are written --
+ *     the cut may fall inside an edge --, nothing at or past capacity; capacity = 0 with a NULL output asks "how many?";
+ *   - an edge with an empty side contributes nothing and has count 0.  Only sets named by an edge whose two sides are both
+ *     non-empty are read.
+ * Empty forms (no device is touched), PSX_ERR_INVALID (nothing touched, before any device call) and the pointer rules are
+ * psx_match_pairs_graph_u8's; PSX_ERR_NOMEM where a table, a grid, a row's place among the rows of all referenced sets
+ * or 32 x a group's candidate segments would not fit an int.  Scratch (psx_match_release) and thread safety as for
+ * psx_match.  Two paths, one result, as psx_match_pairs_many ("A list of view pairs", the float subsection):
+ * with the LIVE edges -- both sides non-empty, counted as listed -- the MFMA prefilter runs when POPSIFT_MATCH_MFMA is on,
+ * the sum of lens[right] is at least 4096 and the sum of lens[left] at least 256 x the number of live edges (for a star:
+ * psx_match_pairs_many's rule), the exact scan of every pair otherwise; one decision per call for both directions.  Every
+ * referenced set gets its permuted copy, or its norms and f16 copy, ONCE per call.  Synchronous: ONE stream synchronisation
+ * per call; a second one only when the prefilter's flag comes back up (a candidate segment overflowed, or a norm is zero
+ * everywhere, infinite or NaN) and the whole call is repeated by the exact scan.  The number of kernel launches grows
+ * neither with n_edges nor with n_sets.  The records go into psx_ransac_*_graph*, psx_match_pairs_guided_graph* and
+ * psx_tracks_graph* as the byte call's do. */
+int psx_match_pairs_graph(int device, const float* const* d_sets, const int* lens, int n_sets,
+                          const psx_view_edge* edges, int n_edges, const psx_match_opts* opts,
+                          psx_match_pair* host_pairs, int capacity, int* edge_counts, int* count);
+/* the list stays in HBM: d_pairs is a DEVICE pointer, 16-byte aligned; edge_counts and count are still HOST memory */
+int psx_match_pairs_graph_dev(int device, const float* const* d_sets, const int* lens, int n_sets,
+                              const psx_view_edge* edges, int n_edges, const psx_match_opts* opts,
+                              psx_match_pair* d_pairs, int capacity, int* edge_counts, int* count);
+
+/* What psx_match_pairs_graph decides for these sizes, on the HOST: no device, no context (csrc/hip/match_graph_f32_plan.h,
+ * the functions the library itself plans with); the float counterpart of psx_match_graph_plan and psx_match_many_f32_plan.
+ * flags: psx_match_opts.flags; mfma_enabled: 1 as POPSIFT_MATCH_MFMA's default, 0 as POPSIFT_MATCH_MFMA=0.  path: 1 the
+ * exact scan, 2 the prefilter (0: no edge is live, nothing runs and every other field is 0).  Every referenced set is cut
+ * ONCE per call into `blocks` outer blocks of 256 rows and `chunks` inner chunks of at most chunk_len rows: whole tiles, at
+ * most 512 rows, on the scan path; on the prefilter path whole staged blocks of 64 rows, the smallest length between 512
+ * and 4096 at which the direction with fewer items has at most 768 of them (4096 if none does).  fwd_items / bwd_items:
+ * blocks(outer) x chunks(inner) summed over the edges, one workgroup each (bwd: PSX_PAIRS_MUTUAL only); fwd_groups /
+ * bwd_groups: the runs of whole edges whose share of the one buffer that grows with (chunks x outer rows) -- 16 bytes per
+ * entry on the scan path, 264 on the prefilter path -- fits 256 MiB (a single edge above it is a group of its own);
+ * join_workgroups: the sum over the live edges of ceil(lens[left] / 256); launches: the kernels queued when the flag stays
+ * down, 1 or 2 + 2 per group + 3; scratch_bytes: that buffer for the largest group.  PSX_ERR_INVALID as above for the sets
+ * and the edges, for unknown flag bits, mfma_enabled not 0 or 1, out == NULL; PSX_ERR_NOMEM as the call. */
+typedef struct psx_graph_f32_plan_info { int path;        /* 1 scan, 2 prefilter */
+                                         int referenced_sets, blocks, chunks, chunk_len;
+                                         int fwd_items, bwd_items, fwd_groups, bwd_groups;
+                                         int join_workgroups, launches;
+                                         long long scratch_bytes; } psx_graph_f32_plan_info;
+int psx_match_graph_f32_plan(const int* lens, int n_sets, const psx_view_edge* edges, int n_edges, int flags,
+                             int mfma_enabled, psx_graph_f32_plan_info* out);
+/* The calling thread's last psx_match_pairs_graph / _dev call that passed its argument checks (zeros before any), as
+ * psx_match_many_f32_last reports the one-to-many call's.  PSX_ERR_INVALID for out == NULL. */
+int psx_match_graph_f32_last(psx_many_f32_info* out);
 
 /* ---- guided matching ---------------------------------------------------------------------
  * The 2-NN search restricted by what the caller knows about where a match can lie (AliceVision's guidedMatching, a
@@ -611,8 +668,8 @@ int psx_match_pairs_guided_u8_dev(int device, const unsigned char* d_left, const
  * --, whose forward search takes 64 workgroups per 256 left rows of every set that is neither skipped nor empty: with
  * tens of millions of such sets of a handful of left rows each, 64 * (those sets) * ceil(l_len / 256) passes INT_MAX and
  * the call returns PSX_ERR_NOMEM where it ran when the star had a grid of n_sets * ceil(l_len / 4) workgroups of its own.
- * Scratch (psx_match_release) and thread safety as for psx_match_u8.  Synchronous, with exactly one stream synchronisation per call.  Only the byte form
- * exists, as for the unguided one-to-many call. */
+ * Scratch (psx_match_release) and thread safety as for psx_match_u8.  Synchronous, with exactly one stream synchronisation per call.  The float form
+ * is psx_match_pairs_guided_many (below). */
 #define PSX_GUIDE_NONE 0         /* in the *_many and *_graph calls only: this set / edge is skipped */
 int psx_match_pairs_guided_many_u8(int device, const unsigned char* d_left, const float* d_left_xy, int l_len,
                                    const unsigned char* const* d_rights, const float* const* d_right_xys, const int* r_lens,
@@ -623,6 +680,19 @@ int psx_match_pairs_guided_many_u8_dev(int device, const unsigned char* d_left, 
                                        const unsigned char* const* d_rights, const float* const* d_right_xys, const int* r_lens,
                                        int n_sets, const psx_guide* guides, const psx_match_opts* opts,
                                        psx_match_pair_u8* d_pairs, int capacity, int* set_counts, int* count);
+/* The float form of psx_match_pairs_guided_many_u8: the same signature and contract, word for word, with descriptors of 128
+ * floats (16-byte aligned), psx_match_pair records and psx_match_pairs_guided as the single call -- set k yields, bit for
+ * bit (float distances compared as bit patterns), what psx_match_pairs_guided returns for (L, R_k) under guides[k].  The
+ * same driver on (float, float): 4 kernel launches, 6 with the cross-check, one stream synchronisation. */
+int psx_match_pairs_guided_many(int device, const float* d_left, const float* d_left_xy, int l_len,
+                                const float* const* d_rights, const float* const* d_right_xys, const int* r_lens,
+                                int n_sets, const psx_guide* guides, const psx_match_opts* opts,
+                                psx_match_pair* host_pairs, int capacity, int* set_counts, int* count);
+/* the list stays in HBM: d_pairs is a DEVICE pointer, 16-byte aligned; set_counts and count are still HOST memory */
+int psx_match_pairs_guided_many_dev(int device, const float* d_left, const float* d_left_xy, int l_len,
+                                    const float* const* d_rights, const float* const* d_right_xys, const int* r_lens,
+                                    int n_sets, const psx_guide* guides, const psx_match_opts* opts,
+                                    psx_match_pair* d_pairs, int capacity, int* set_counts, int* count);
 
 /* ---- geometric verification ---------------------------------------------------------------
  * The step between a match and a guided re-match: a homography estimated from the pair list by RANSAC on the device
@@ -939,7 +1009,7 @@ int psx_ransac_similarity_graph_ref(const void* pairs, const int* edge_counts, c
  * over the edges of lens[left] or of lens[right] above INT_MAX among it); d_xys NULL with n_sets > 0; a NULL d_xys[s] with
  * lens[s] > 0; guides NULL with n_edges > 0; any guide that is neither valid nor of kind 0 -- EVERY guide is checked before
  * anything runs.  PSX_ERR_NOMEM where a grid would not fit an int.  Scratch (psx_match_release) and thread safety as for
- * psx_match_u8.  Synchronous.  Only the byte form exists. */
+ * psx_match_u8.  Synchronous.  The float form is psx_match_pairs_guided_graph (below). */
 int psx_match_pairs_guided_graph_u8(int device, const unsigned char* const* d_sets, const float* const* d_xys,
                                     const int* lens, int n_sets, const psx_view_edge* edges, int n_edges,
                                     const psx_guide* guides, const psx_match_opts* opts,
@@ -949,6 +1019,21 @@ int psx_match_pairs_guided_graph_u8_dev(int device, const unsigned char* const* 
                                         const int* lens, int n_sets, const psx_view_edge* edges, int n_edges,
                                         const psx_guide* guides, const psx_match_opts* opts,
                                         psx_match_pair_u8* d_pairs, int capacity, int* edge_counts, int* count);
+/* The float form of psx_match_pairs_guided_graph_u8: the same signature and contract, word for word, with descriptors of
+ * 128 floats (16-byte aligned), psx_match_pair records and psx_match_pairs_guided as the single call -- edge e yields, bit
+ * for bit (float distances compared as bit patterns), what psx_match_pairs_guided returns for its two sets under guides[e].
+ * The same driver on (float, float): 4 kernel launches, 6 with the cross-check, one stream synchronisation.  Its input is
+ * what psx_match_pairs_graph[_dev] and psx_ransac_*_graph* leave, its output goes into psx_tracks_graph*: those read only
+ * `left` and `right` of a 16-byte record. */
+int psx_match_pairs_guided_graph(int device, const float* const* d_sets, const float* const* d_xys,
+                                 const int* lens, int n_sets, const psx_view_edge* edges, int n_edges,
+                                 const psx_guide* guides, const psx_match_opts* opts,
+                                 psx_match_pair* host_pairs, int capacity, int* edge_counts, int* count);
+/* the list stays in HBM: d_pairs is a DEVICE pointer, 16-byte aligned; edge_counts and count are still HOST memory */
+int psx_match_pairs_guided_graph_dev(int device, const float* const* d_sets, const float* const* d_xys,
+                                     const int* lens, int n_sets, const psx_view_edge* edges, int n_edges,
+                                     const psx_guide* guides, const psx_match_opts* opts,
+                                     psx_match_pair* d_pairs, int capacity, int* edge_counts, int* count);
 
 /* TRACKS FROM A LIST OF VIEW PAIRS: the fourth link.  The chain above ends with E separate pair lists; structure from
  * motion, loop closure and retrieval need TRACKS next: the sets of rows in different views that the pairs connect

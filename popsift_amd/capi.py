@@ -117,6 +117,8 @@ SYMBOLS = [
     "psx_ransac_affine_graph", "psx_ransac_affine_graph_dev", "psx_ransac_affine_graph_ref",
     "psx_ransac_similarity_graph", "psx_ransac_similarity_graph_dev", "psx_ransac_similarity_graph_ref",
     "psx_match_pairs_guided_graph_u8", "psx_match_pairs_guided_graph_u8_dev",
+    "psx_match_pairs_graph", "psx_match_pairs_graph_dev", "psx_match_graph_f32_plan", "psx_match_graph_f32_last",
+    "psx_match_pairs_guided_many", "psx_match_pairs_guided_many_dev", "psx_match_pairs_guided_graph", "psx_match_pairs_guided_graph_dev",
     "psx_tracks_graph", "psx_tracks_graph_dev", "psx_tracks_graph_ref", "psx_tracks_plan",
     "psx_pyramid_plan", "psx_blur_grid_of",
 ]
@@ -135,6 +137,13 @@ class ManyF32Plan(C.Structure):
 class GraphPlanInfo(C.Structure):
     """psx_graph_plan_info: what psx_match_pairs_graph_u8 plans for the sizes of a call"""
     _fields_ = [("referenced_sets", C.c_int), ("blocks", C.c_int), ("chunks", C.c_int), ("chunk_len", C.c_int),
+                ("fwd_items", C.c_int), ("bwd_items", C.c_int), ("fwd_groups", C.c_int), ("bwd_groups", C.c_int),
+                ("join_workgroups", C.c_int), ("launches", C.c_int), ("scratch_bytes", C.c_longlong)]
+
+
+class GraphF32PlanInfo(C.Structure):
+    """psx_graph_f32_plan_info: what psx_match_pairs_graph decides and plans for the sizes of a call"""
+    _fields_ = [("path", C.c_int), ("referenced_sets", C.c_int), ("blocks", C.c_int), ("chunks", C.c_int), ("chunk_len", C.c_int),
                 ("fwd_items", C.c_int), ("bwd_items", C.c_int), ("fwd_groups", C.c_int), ("bwd_groups", C.c_int),
                 ("join_workgroups", C.c_int), ("launches", C.c_int), ("scratch_bytes", C.c_longlong)]
 
@@ -298,16 +307,19 @@ def lib():
         L.psx_match_many_f32_plan.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(ManyF32Plan)]
         L.psx_match_many_f32_last.argtypes = [C.POINTER(ManyF32Info)]
         L.psx_match_many_plan.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, ip, vp, C.c_int, ip]
-        for n in ("psx_match_pairs_graph_u8", "psx_match_pairs_graph_u8_dev"):
+        for n in ("psx_match_pairs_graph_u8", "psx_match_pairs_graph_u8_dev", "psx_match_pairs_graph", "psx_match_pairs_graph_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, C.c_int, C.POINTER(MatchOpts), vp, C.c_int, vp, ip]
         L.psx_match_graph_plan.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(GraphPlanInfo)]
+        L.psx_match_graph_f32_plan.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(GraphF32PlanInfo)]
+        L.psx_match_graph_f32_last.argtypes = [C.POINTER(ManyF32Info)]
         L.psx_guide_allows.argtypes = [C.POINTER(Guide), vp, C.c_int, vp, C.c_int, vp]
         L.psx_desc_positions.argtypes = [C.c_int, vp, vp, C.c_int, vp]
         for n in ("psx_match_guided", "psx_match_guided_u8"):
             getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(Guide), vp, vp]
         for n in ("psx_match_pairs_guided", "psx_match_pairs_guided_u8", "psx_match_pairs_guided_dev", "psx_match_pairs_guided_u8_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(Guide), C.POINTER(MatchOpts), vp, C.c_int, ip]
-        for n in ("psx_match_pairs_guided_many_u8", "psx_match_pairs_guided_many_u8_dev"):
+        for n in ("psx_match_pairs_guided_many_u8", "psx_match_pairs_guided_many_u8_dev", "psx_match_pairs_guided_many",
+                  "psx_match_pairs_guided_many_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.POINTER(MatchOpts), vp, C.c_int, vp, ip]
         L.psx_guides_from_ransac.argtypes = [vp, C.c_int, C.c_int, C.c_float, vp]
         L.psx_ransac_opts_default.argtypes = [C.POINTER(RansacOpts)]
@@ -332,7 +344,8 @@ def lib():
                 getattr(L, n).argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(RansacOpts), vp, vp, C.c_int, ip, vp, vp]
             getattr(L, "psx_ransac_%s_graph_ref" % m).argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(RansacOpts), vp, vp, C.c_int, ip,
                                                                    vp, vp]
-        for n in ("psx_match_pairs_guided_graph_u8", "psx_match_pairs_guided_graph_u8_dev"):
+        for n in ("psx_match_pairs_guided_graph_u8", "psx_match_pairs_guided_graph_u8_dev", "psx_match_pairs_guided_graph",
+                  "psx_match_pairs_guided_graph_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, C.POINTER(MatchOpts), vp, C.c_int, vp, ip]
         for n in ("psx_tracks_graph", "psx_tracks_graph_dev"):
             getattr(L, n).argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.POINTER(TrackOpts), vp, vp, C.c_int, vp, C.c_int,
@@ -709,13 +722,9 @@ def _graph_call(fn, name, device, set_ptrs, lens, edges, out_ptr, capacity, rati
     return counts, n.value
 
 
-def match_pairs_graph_u8(sets, edges, ratio=0.8, mutual=False, device=0, capacity=None):
-    """psx_match_pairs_graph_u8 on host arrays: `sets` are (n_s,128) uint8 arrays, `edges` (left, right) index pairs into
-    them, all matched in ONE call.  Returns (list of per-edge PAIR_U8_DTYPE arrays -- edge e's equals
-    match_pairs_u8(sets[left], sets[right]), in the order of the edge list --, per-edge counts); with a capacity the list
-    holds the first `capacity` records of the concatenation and the counts are still the totals."""
+def _match_pairs_graph(name, dtype, pair_dtype, sets, edges, ratio, mutual, device, capacity):
     L = lib()
-    sets = [np.ascontiguousarray(s, dtype=np.uint8).reshape(-1, 128) for s in sets]
+    sets = [np.ascontiguousarray(s, dtype=dtype).reshape(-1, 128) for s in sets]
     ea = _graph_edges(edges)
     bufs = []
     try:
@@ -723,8 +732,8 @@ def match_pairs_graph_u8(sets, edges, ratio=0.8, mutual=False, device=0, capacit
         lens = [len(s) for s in sets]
         ok = all(0 <= a < len(sets) and 0 <= b < len(sets) for a, b in ea)
         cap = (sum(lens[a] for a, _ in ea) if ok else 0) if capacity is None else capacity
-        out = np.zeros((cap,), PAIR_U8_DTYPE)
-        counts, n = _graph_call(L.psx_match_pairs_graph_u8, "psx_match_pairs_graph_u8", device, ptrs, lens, ea,
+        out = np.zeros((cap,), pair_dtype)
+        counts, n = _graph_call(getattr(L, name), name, device, ptrs, lens, ea,
                                 out.ctypes.data_as(C.c_void_p) if cap else None, cap, ratio, mutual)
         return split_sets(out[:min(n, cap)], counts), counts
     finally:
@@ -732,13 +741,54 @@ def match_pairs_graph_u8(sets, edges, ratio=0.8, mutual=False, device=0, capacit
             L.psx_dev_free(device, p)
 
 
-def match_pairs_graph_dev(ptrs, lens, edges, out_ptr, capacity, ratio=0.8, mutual=False, device=0):
-    """psx_match_pairs_graph_u8_dev on DEVICE pointers (e.g. tensor.data_ptr()): the concatenated records go into the
-    caller's device buffer at out_ptr (16-byte aligned, `capacity` records); returns (per-edge counts, total count).  With
-    the edge list grouped by left, a left view's slice of the buffer and of the counts is what match_pairs_many_dev
-    leaves for that star: ransac_*_many_dev and match_pairs_guided_many_dev take it unchanged."""
-    return _graph_call(lib().psx_match_pairs_graph_u8_dev, "psx_match_pairs_graph_u8_dev", device, list(ptrs), lens, edges,
-                       C.c_void_p(out_ptr), capacity, ratio, mutual)
+def match_pairs_graph_u8(sets, edges, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs_graph_u8 on host arrays: `sets` are (n_s,128) uint8 arrays, `edges` (left, right) index pairs into
+    them, all matched in ONE call.  Returns (list of per-edge PAIR_U8_DTYPE arrays -- edge e's equals
+    match_pairs_u8(sets[left], sets[right]), in the order of the edge list --, per-edge counts); with a capacity the list
+    holds the first `capacity` records of the concatenation and the counts are still the totals."""
+    return _match_pairs_graph("psx_match_pairs_graph_u8", np.uint8, PAIR_U8_DTYPE, sets, edges, ratio, mutual, device, capacity)
+
+
+def match_pairs_graph(sets, edges, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs_graph on host arrays, the float form of match_pairs_graph_u8: `sets` are (n_s,128) float32 arrays.
+    Returns (list of per-edge PAIR_DTYPE arrays -- edge e's equals match_pairs(sets[left], sets[right]) --, per-edge
+    counts); capacity as there."""
+    return _match_pairs_graph("psx_match_pairs_graph", np.float32, PAIR_DTYPE, sets, edges, ratio, mutual, device, capacity)
+
+
+def match_pairs_graph_dev(ptrs, lens, edges, out_ptr, capacity, ratio=0.8, mutual=False, device=0, u8=True):
+    """psx_match_pairs_graph_u8_dev (u8=False: psx_match_pairs_graph_dev, float descriptors) on DEVICE pointers (e.g.
+    tensor.data_ptr()): the concatenated records go into the caller's device buffer at out_ptr (16-byte aligned,
+    `capacity` records); returns (per-edge counts, total count).  With the edge list grouped by left, a left view's slice
+    of the buffer and of the counts is what match_pairs_many_dev leaves for that star: ransac_*_many_dev and
+    match_pairs_guided_many_dev take it unchanged."""
+    name = "psx_match_pairs_graph_u8_dev" if u8 else "psx_match_pairs_graph_dev"
+    return _graph_call(getattr(lib(), name), name, device, list(ptrs), lens, edges, C.c_void_p(out_ptr), capacity, ratio, mutual)
+
+
+def match_graph_f32_plan(lens, edges, mutual=False, mfma_enabled=True):
+    """psx_match_graph_f32_plan: what psx_match_pairs_graph decides and plans for these sizes, as a dict (path,
+    referenced_sets, blocks, chunks, chunk_len, fwd_items, bwd_items, fwd_groups, bwd_groups, join_workgroups, launches,
+    scratch_bytes).  No device."""
+    la = np.ascontiguousarray(lens, dtype=np.int32)
+    ea = _graph_edges(edges)
+    out = GraphF32PlanInfo()
+    rc = lib().psx_match_graph_f32_plan(la.ctypes.data_as(C.c_void_p) if len(la) else None, len(la),
+                                        ea.ctypes.data_as(C.c_void_p) if len(ea) else None, len(ea), PAIRS_MUTUAL if mutual else 0,
+                                        1 if mfma_enabled else 0, C.byref(out))
+    if rc != 0:
+        raise PopSiftError("psx_match_graph_f32_plan failed (%d)" % rc)
+    return {n: int(getattr(out, n)) for n, _ in GraphF32PlanInfo._fields_}
+
+
+def match_graph_f32_last():
+    """psx_match_graph_f32_last: the calling thread's last match_pairs_graph / match_pairs_graph_dev(u8=False) call as a
+    dict (path, fell_back, launches, syncs); zeros before any"""
+    out = ManyF32Info()
+    rc = lib().psx_match_graph_f32_last(C.byref(out))
+    if rc != 0:
+        raise PopSiftError("psx_match_graph_f32_last failed (%d)" % rc)
+    return {n: int(getattr(out, n)) for n, _ in ManyF32Info._fields_}
 
 
 def match_graph_plan(lens, edges, mutual=False):
@@ -916,6 +966,13 @@ def _guided_many_call(fn, name, device, left_ptr, left_xy_ptr, l_len, right_ptrs
     return counts, n.value
 
 
+def match_pairs_guided_many(left, left_xy, rights, right_xys, guides, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs_guided_many on host arrays, the float form of match_pairs_guided_many_u8: (n,128) float32 arrays,
+    per-set PAIR_DTYPE arrays -- set k's equals match_pairs_guided(left, left_xy, rights[k], right_xys[k], guides[k])."""
+    return _match_pairs_guided_many("psx_match_pairs_guided_many", np.float32, PAIR_DTYPE, left, left_xy, rights, right_xys, guides, ratio,
+                                    mutual, device, capacity)
+
+
 def match_pairs_guided_many_u8(left, left_xy, rights, right_xys, guides, ratio=0.8, mutual=False, device=0, capacity=None):
     """psx_match_pairs_guided_many_u8 on host arrays: left (n,128) uint8 with positions left_xy (n,2) against every
     (m_k,128) uint8 array of `rights` with positions right_xys[k], set k under guides[k], in ONE call.  A guide of kind
@@ -923,19 +980,24 @@ def match_pairs_guided_many_u8(left, left_xy, rights, right_xys, guides, ratio=0
     PAIR_U8_DTYPE arrays -- set k's equals match_pairs_guided_u8(left, left_xy, rights[k], right_xys[k], guides[k]) --,
     per-set counts); with a capacity the list holds the first `capacity` records of the concatenation and the counts are
     still the totals."""
+    return _match_pairs_guided_many("psx_match_pairs_guided_many_u8", np.uint8, PAIR_U8_DTYPE, left, left_xy, rights, right_xys, guides, ratio,
+                                    mutual, device, capacity)
+
+
+def _match_pairs_guided_many(name, dtype, pair_dtype, left, left_xy, rights, right_xys, guides, ratio, mutual, device, capacity):
     L = lib()
     if not (len(rights) == len(right_xys) == len(guides)):
         raise ValueError("one descriptor array, one position array and one guide per set")
-    empty, empty_xy = np.zeros((0, 128), np.uint8), np.zeros((0, 2), np.float32)
-    sides = [_guided_sides(left, left_xy, empty if r is None else r, empty_xy if x is None else x, np.uint8) for r, x in zip(rights, right_xys)]
-    left, lx = _guided_sides(left, left_xy, empty, empty_xy, np.uint8)[:2]
+    empty, empty_xy = np.zeros((0, 128), dtype), np.zeros((0, 2), np.float32)
+    sides = [_guided_sides(left, left_xy, empty if r is None else r, empty_xy if x is None else x, dtype) for r, x in zip(rights, right_xys)]
+    left, lx = _guided_sides(left, left_xy, empty, empty_xy, dtype)[:2]
     bufs = []
     try:
         ptrs = _to_device(L, device, [left, lx] + [s[2] for s in sides] + [s[3] for s in sides], bufs)
         k = len(sides)
         cap = len(left) * k if capacity is None else capacity
-        out = np.zeros((cap,), PAIR_U8_DTYPE)
-        counts, n = _guided_many_call(L.psx_match_pairs_guided_many_u8, "psx_match_pairs_guided_many_u8", device, ptrs[0], ptrs[1], len(left),
+        out = np.zeros((cap,), pair_dtype)
+        counts, n = _guided_many_call(getattr(L, name), name, device, ptrs[0], ptrs[1], len(left),
                                       ptrs[2:2 + k], ptrs[2 + k:], [len(s[2]) for s in sides], guides,
                                       out.ctypes.data_as(C.c_void_p) if cap else None, cap, ratio, mutual)
         return split_sets(out[:min(n, cap)], counts), counts
@@ -945,10 +1007,12 @@ def match_pairs_guided_many_u8(left, left_xy, rights, right_xys, guides, ratio=0
 
 
 def match_pairs_guided_many_dev(left_ptr, left_xy_ptr, l_len, right_ptrs, right_xy_ptrs, r_lens, guides, out_ptr, capacity, ratio=0.8,
-                                mutual=False, device=0):
-    """psx_match_pairs_guided_many_u8_dev on DEVICE pointers (e.g. tensor.data_ptr()): the concatenated records go into
-    the caller's device buffer at out_ptr (16-byte aligned, `capacity` records); returns (per-set counts, total count)."""
-    return _guided_many_call(lib().psx_match_pairs_guided_many_u8_dev, "psx_match_pairs_guided_many_u8_dev", device, C.c_void_p(left_ptr),
+                                mutual=False, device=0, u8=True):
+    """psx_match_pairs_guided_many_u8_dev (u8=False: psx_match_pairs_guided_many_dev, float descriptors) on DEVICE pointers
+    (e.g. tensor.data_ptr()): the concatenated records go into the caller's device buffer at out_ptr (16-byte aligned,
+    `capacity` records); returns (per-set counts, total count)."""
+    name = "psx_match_pairs_guided_many_u8_dev" if u8 else "psx_match_pairs_guided_many_dev"
+    return _guided_many_call(getattr(lib(), name), name, device, C.c_void_p(left_ptr),
                              C.c_void_p(left_xy_ptr), l_len, list(right_ptrs), list(right_xy_ptrs), r_lens, guides, C.c_void_p(out_ptr),
                              capacity, ratio, mutual)
 
@@ -1539,17 +1603,30 @@ def _guided_graph_call(fn, name, device, set_ptrs, xy_ptrs, lens, edges, guides,
     return counts, n.value
 
 
+def match_pairs_guided_graph(sets, xys, edges, guides, ratio=0.8, mutual=False, device=0, capacity=None):
+    """psx_match_pairs_guided_graph on host arrays, the float form of match_pairs_guided_graph_u8: (n_s,128) float32 sets,
+    per-edge PAIR_DTYPE arrays -- edge e's equals match_pairs_guided(sets[left], xys[left], sets[right], xys[right],
+    guides[e])."""
+    return _match_pairs_guided_graph("psx_match_pairs_guided_graph", np.float32, PAIR_DTYPE, sets, xys, edges, guides, ratio, mutual, device,
+                                     capacity)
+
+
 def match_pairs_guided_graph_u8(sets, xys, edges, guides, ratio=0.8, mutual=False, device=0, capacity=None):
     """psx_match_pairs_guided_graph_u8 on host arrays: `sets` are (n_s,128) uint8 arrays with positions xys[s] (n_s,2),
     `edges` (left, right) index pairs into them, edge e re-matched under guides[e], all in ONE call.  A guide of kind
     GUIDE_NONE (Guide.none(), or None) skips its edge.  Returns (list of per-edge PAIR_U8_DTYPE arrays -- edge e's equals
     match_pairs_guided_u8(sets[left], xys[left], sets[right], xys[right], guides[e]) --, per-edge counts); with a capacity the
     list holds the first `capacity` records of the concatenation and the counts are still the totals."""
+    return _match_pairs_guided_graph("psx_match_pairs_guided_graph_u8", np.uint8, PAIR_U8_DTYPE, sets, xys, edges, guides, ratio, mutual,
+                                     device, capacity)
+
+
+def _match_pairs_guided_graph(name, dtype, pair_dtype, sets, xys, edges, guides, ratio, mutual, device, capacity):
     L = lib()
     if len(sets) != len(xys):
         raise ValueError("one position array per descriptor set")
-    empty, empty_xy = np.zeros((0, 128), np.uint8), np.zeros((0, 2), np.float32)
-    sides = [_guided_sides(s, x, empty, empty_xy, np.uint8)[:2] for s, x in zip(sets, xys)]
+    empty, empty_xy = np.zeros((0, 128), dtype), np.zeros((0, 2), np.float32)
+    sides = [_guided_sides(s, x, empty, empty_xy, dtype)[:2] for s, x in zip(sets, xys)]
     ea = _graph_edges(edges)
     bufs = []
     try:
@@ -1558,8 +1635,8 @@ def match_pairs_guided_graph_u8(sets, xys, edges, guides, ratio=0.8, mutual=Fals
         lens = [len(s[0]) for s in sides]
         ok = all(0 <= a < k and 0 <= b < k for a, b in ea)
         cap = (sum(lens[a] for a, _ in ea) if ok else 0) if capacity is None else capacity
-        out = np.zeros((cap,), PAIR_U8_DTYPE)
-        counts, n = _guided_graph_call(L.psx_match_pairs_guided_graph_u8, "psx_match_pairs_guided_graph_u8", device, ptrs[:k], ptrs[k:], lens, ea,
+        out = np.zeros((cap,), pair_dtype)
+        counts, n = _guided_graph_call(getattr(L, name), name, device, ptrs[:k], ptrs[k:], lens, ea,
                                        guides, out.ctypes.data_as(C.c_void_p) if cap else None, cap, ratio, mutual)
         return split_sets(out[:min(n, cap)], counts), counts
     finally:
@@ -1567,10 +1644,12 @@ def match_pairs_guided_graph_u8(sets, xys, edges, guides, ratio=0.8, mutual=Fals
             L.psx_dev_free(device, p)
 
 
-def match_pairs_guided_graph_dev(set_ptrs, xy_ptrs, lens, edges, guides, out_ptr, capacity, ratio=0.8, mutual=False, device=0):
-    """psx_match_pairs_guided_graph_u8_dev on DEVICE pointers (e.g. tensor.data_ptr()): the concatenated records go into the
-    caller's device buffer at out_ptr (16-byte aligned, `capacity` records); returns (per-edge counts, total count)."""
-    return _guided_graph_call(lib().psx_match_pairs_guided_graph_u8_dev, "psx_match_pairs_guided_graph_u8_dev", device, list(set_ptrs),
+def match_pairs_guided_graph_dev(set_ptrs, xy_ptrs, lens, edges, guides, out_ptr, capacity, ratio=0.8, mutual=False, device=0, u8=True):
+    """psx_match_pairs_guided_graph_u8_dev (u8=False: psx_match_pairs_guided_graph_dev, float descriptors) on DEVICE
+    pointers (e.g. tensor.data_ptr()): the concatenated records go into the caller's device buffer at out_ptr (16-byte
+    aligned, `capacity` records); returns (per-edge counts, total count)."""
+    name = "psx_match_pairs_guided_graph_u8_dev" if u8 else "psx_match_pairs_guided_graph_dev"
+    return _guided_graph_call(getattr(lib(), name), name, device, list(set_ptrs),
                               list(xy_ptrs), lens, edges, guides, C.c_void_p(out_ptr), capacity, ratio, mutual)
 
 

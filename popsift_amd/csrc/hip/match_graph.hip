@@ -12,7 +12,8 @@
 //                           backward (PSX_PAIRS_MUTUAL only) are the same kernel on the other item table
 //   k_match_u8_graph_merge  per (edge, outer row) the inner set's chunks in index order: the directed result
 //                           (match_scratch.h) at the edge's row offset
-//   k_graph_count / k_graph_scan / k_graph_write   the join, segmented by edge with the edge's OWN left length: the rule of
+//   k_graph_count / k_graph_scan / k_graph_write   (match_graph_join.h, which the float form match_graph_f32.hip queues too)
+//                           the join, segmented by edge with the edge's OWN left length: the rule of
 //                           match_rule.h (psx_match_keep) and the backward gather counted per workgroup (wg_compact.h), one
 //                           scan of the totals (wg_scan_totals), one 16-byte store per survivor, the per-edge counts and the
 //                           total.  The workgroups come from the {edge, row0} table in edge-major order, so the offsets
@@ -21,6 +22,7 @@
 // join -- 8 kernels with the cross-check, 6 without; one stream synchronisation.  Above PSX_GRAPH_PARTIAL_BUDGET of per-chunk
 // partials the edges are processed in groups of whole edges, each group its own match + merge on the same stream.
 #include "psx_internal.h"
+#include "match_graph_join.h"
 #include "match_graph_plan.h"
 #include "match_join.h"
 #include "match_rule.h"
@@ -96,64 +98,6 @@ __global__ __launch_bounds__(256) void k_match_u8_graph_merge(const GraphSet* __
     U8Best t;
     for (int c = is.c0; c < is.c1; c++, p += os.len) u8_merge_chunk(t, *p, chunks[c].y);
     psx_directed_store<int>(out + 5 * (size_t)(backward ? e.boff : e.foff), os.len, (size_t)row, t.i1, t.i2, u8_accept(t.d1, t.d2), t.d1, t.d2);
-}
-
-// The rule of match_rule.h for left row i of edge e, whose left set has l_len rows: the edge's forward result, and with the
-// cross-check the gather into the edge's backward rows.
-__device__ __forceinline__ bool graph_rule(const psx_graph_edge& e, int l_len, const int* __restrict__ fwd, const int* __restrict__ bwd,
-                                           int i, float ratio, int mutual, int4& rec)
-{
-    if (i >= l_len) return false;
-    int j, d1, d2;
-    psx_directed_load<int>(fwd + 5 * (size_t)e.foff, l_len, i, j, d1, d2);
-    bool keep = psx_match_keep(psx_match_dist(d1), psx_match_dist(d2), ratio);
-    if (keep && mutual) keep = psx_directed_best(bwd + 5 * (size_t)e.boff, j) == i;
-    rec = make_int4(i, j, d1, d2);
-    return keep;
-}
-
-// grid: the forward {edge, row0} table, edge-major: one total per workgroup
-__global__ __launch_bounds__(256) void k_graph_count(const GraphSet* __restrict__ sets, const psx_graph_edge* __restrict__ edges,
-                                                     const int2* __restrict__ wgs, const int* __restrict__ fwd, const int* __restrict__ bwd,
-                                                     float ratio, int mutual, int* __restrict__ wg_tot)
-{
-    const int2 wg = wgs[blockIdx.x];
-    const psx_graph_edge e = edges[wg.x];
-    int4 rec;
-    const bool keep = graph_rule(e, sets[e.left].len, fwd, bwd, wg.y + (int)threadIdx.x, ratio, mutual, rec);
-    __shared__ int s_cnt[4];
-    wg_count(__ballot(keep), s_cnt);
-    if (threadIdx.x == 0) wg_tot[blockIdx.x] = wg_total(s_cnt);
-}
-
-// ONE workgroup of 1024 threads: offs[w] = the totals before workgroup w, offs[n] = all of them (wg_compact.h)
-__global__ __launch_bounds__(1024) void k_graph_scan(const int* __restrict__ wg_tot, int n, int* __restrict__ offs)
-{
-    wg_scan_totals(wg_tot, n, offs);
-}
-
-// grid as k_graph_count.  Evaluates the rule again, ranks its lanes and writes each surviving record with ONE 16-byte store
-// at offs[workgroup] + rank, never at or past capacity; an edge's first workgroup writes the edge's count (an edge without
-// workgroups keeps the zero the host put there), workgroup 0 the total.
-__global__ __launch_bounds__(256) void k_graph_write(const GraphSet* __restrict__ sets, const psx_graph_edge* __restrict__ edges,
-                                                     const int2* __restrict__ wgs, const int* __restrict__ fwd, const int* __restrict__ bwd,
-                                                     float ratio, int mutual, const int* __restrict__ offs, int4* __restrict__ out,
-                                                     int capacity, int* __restrict__ edge_counts, int* __restrict__ total)
-{
-    const int2 wg = wgs[blockIdx.x];
-    const psx_graph_edge e = edges[wg.x];
-    const int l_len = sets[e.left].len;
-    int4 rec = make_int4(0, 0, 0, 0);
-    const bool keep = graph_rule(e, l_len, fwd, bwd, wg.y + (int)threadIdx.x, ratio, mutual, rec);
-    const unsigned long long m = __ballot(keep);
-    __shared__ int s_cnt[4];
-    wg_count(m, s_cnt);
-    const int pos = offs[blockIdx.x] + wg_offset(m, s_cnt);
-    if (keep && pos < capacity) out[pos] = rec;
-    if (threadIdx.x == 0) {
-        if (wg.y == 0) edge_counts[wg.x] = offs[blockIdx.x + (unsigned)((l_len + 255) / 256)] - offs[blockIdx.x];
-        if (blockIdx.x == 0) *total = offs[gridDim.x];
-    }
 }
 
 size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
@@ -265,7 +209,6 @@ int match_pairs_graph(int device, const unsigned char* const* d_sets, const int*
     // the kernel's capacity for the host form is the staging buffer's (nrec <= capacity)
     int4* out = host_pairs ? reinterpret_cast<int4*>(static_cast<char*>(dev_pin) + off_rec) : static_cast<int4*>(d_pairs);
     const int cap = host_pairs ? (int)nrec : capacity;
-    const int mflag = mutual ? 1 : 0;
     hipStream_t st = sc.stream;
 
     if (hipMemcpyAsync(sc.buf[MS_GRAPH_TABLES], hp + off_blob, blob_b, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
@@ -282,11 +225,7 @@ int match_pairs_graph(int device, const unsigned char* const* d_sets, const int*
         hipLaunchKernelGGL(k_match_u8_graph_merge, dim3((unsigned)g.nwgs), dim3(256), 0, st, t_sets, t_chunks, t_edges, t_wgs + FW + g.wg0, 1,
                            d_partial, d_bwd);
     }
-    int* d_offs = d_tot + FW;
-    hipLaunchKernelGGL(k_graph_count, dim3((unsigned)FW), dim3(256), 0, st, t_sets, t_edges, t_wgs, d_fwd, d_bwd, opts->ratio, mflag, d_tot);
-    hipLaunchKernelGGL(k_graph_scan, dim3(1), dim3(1024), 0, st, d_tot, (int)FW, d_offs);
-    hipLaunchKernelGGL(k_graph_write, dim3((unsigned)FW), dim3(256), 0, st, t_sets, t_edges, t_wgs, d_fwd, d_bwd, opts->ratio, mflag, d_offs, out,
-                       cap, d_counts, d_total);
+    psx_graph_join_queue<int>(st, t_sets, t_edges, t_wgs, d_fwd, d_bwd, (int)FW, opts->ratio, mutual, d_tot, out, cap, d_counts, d_total);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return PSX_ERR_HIP;
     const int n = *h_total;
     if (n < 0 || n > all_pairs) return PSX_ERR_HIP;

@@ -1,5 +1,7 @@
-// match_guided_graph.hip -- the guided re-match of a list of view pairs over N byte descriptor sets in one call:
-// psx_match_pairs_guided_graph_u8 (+ _dev) (include/popsift_hip.h).
+// match_guided_graph.hip -- the guided re-match of a list of view pairs over N descriptor sets in one call:
+// psx_match_pairs_guided_graph_u8 (+ _dev) for byte descriptors, psx_match_pairs_guided_graph (+ _dev) for float ones
+// (include/popsift_hip.h).  Everything below is stated once on (T, D) = (descriptor element, distance type) -- (unsigned
+// char, int) or (float, float), as g_match_row is -- and instantiated for both; the text speaks of the byte form.
 //
 // This is the ONE batched guided re-match of the library.  psx_match_pairs_guided_u8 (match_guided.hip) is a fixed launch
 // sequence, one synchronisation and one count read-back per call; at 2k-4k descriptors per image that is what a loop over
@@ -44,24 +46,26 @@
 namespace {
 
 // one entry per edge
+template <class T>
 struct GGEdge {
-    const unsigned char* ldesc;  // the left set's descriptors
+    const T* ldesc;              // the left set's descriptors
     const float2* lxy;           // ... and positions
-    const unsigned char* rdesc;  // the right set's
+    const T* rdesc;              // the right set's
     const float2* rxy;
     int l_len, r_len;            // rows; both 0 for an edge that is skipped or has an empty side
     int foff, boff;              // its first forward row (and line) / backward row among all edges' rows
     psx_guide guide;             // the edge's own guide
     int pad;
 };
-static_assert(sizeof(psx_guide) == 44 && sizeof(GGEdge) == 96, "whole 16-byte scalar loads per entry");
+static_assert(sizeof(psx_guide) == 44 && sizeof(GGEdge<unsigned char>) == 96 && sizeof(GGEdge<float>) == 96, "whole 16-byte scalar loads per entry");
 static_assert(sizeof(psx_graph_wg) == 8, "the plan's entries are the device's");
 
 // grid: the forward block table, one thread per (edge, left row)
-__global__ __launch_bounds__(256) void k_gg_lines(const GGEdge* __restrict__ edges, const int2* __restrict__ blocks, float4* __restrict__ lines)
+template <class T>
+__global__ __launch_bounds__(256) void k_gg_lines(const GGEdge<T>* __restrict__ edges, const int2* __restrict__ blocks, float4* __restrict__ lines)
 {
     const int2 blk = blocks[blockIdx.x];
-    const GGEdge* e = edges + blk.x;
+    const GGEdge<T>* e = edges + blk.x;
     const int i = blk.y + (int)threadIdx.x;
     if (i >= e->l_len) return;
     const float2 p = e->lxy[i];
@@ -73,42 +77,67 @@ __global__ __launch_bounds__(256) void k_gg_lines(const GGEdge* __restrict__ edg
 // blockIdx.x % 64) owns outer rows row0 + 4 q .. + 3 of its block's edge.  Forward (SWAP = false): the outer side is the
 // edge's left set, the inner geometry its right positions; lines is unused.  Backward (SWAP = true): the outer side is
 // the right set, the inner geometry the edge's lines.
-template <bool SWAP>
-__global__ __launch_bounds__(256) void k_gg_match(const GGEdge* __restrict__ edges, const int2* __restrict__ blocks,
+// The wave's search (g_match_row, match_guided_core.h) on edge e's operands, forward and backward, per descriptor type: the
+// distance type follows the element type
+__device__ __forceinline__ void gg_forward(const GGEdge<unsigned char>* e, int row, int* __restrict__ out)
+{
+    g_match_row<unsigned char, int, false>(e->ldesc, e->lxy, e->l_len, row, e->rdesc, e->rxy, e->r_len, e->guide, out + 5 * (size_t)e->foff);
+}
+__device__ __forceinline__ void gg_backward(const GGEdge<unsigned char>* e, int row, const float4* __restrict__ lines, int* __restrict__ out)
+{
+    g_match_row<unsigned char, int, true>(e->rdesc, e->rxy, e->r_len, row, e->ldesc, lines + (size_t)e->foff, e->l_len, e->guide,
+                                          out + 5 * (size_t)e->boff);
+}
+__device__ __forceinline__ void gg_forward(const GGEdge<float>* e, int row, int* __restrict__ out)
+{
+    g_match_row<float, float, false>(e->ldesc, e->lxy, e->l_len, row, e->rdesc, e->rxy, e->r_len, e->guide, out + 5 * (size_t)e->foff);
+}
+__device__ __forceinline__ void gg_backward(const GGEdge<float>* e, int row, const float4* __restrict__ lines, int* __restrict__ out)
+{
+    g_match_row<float, float, true>(e->rdesc, e->rxy, e->r_len, row, e->ldesc, lines + (size_t)e->foff, e->l_len, e->guide,
+                                    out + 5 * (size_t)e->boff);
+}
+
+template <class T, bool SWAP>
+__global__ __launch_bounds__(256) void k_gg_match(const GGEdge<T>* __restrict__ edges, const int2* __restrict__ blocks,
                                                   const float4* __restrict__ lines, int* __restrict__ out)
 {
     const int2 blk = blocks[blockIdx.x >> 6];
-    const GGEdge* e = edges + blk.x;
+    const GGEdge<T>* e = edges + blk.x;
     const int row = blk.y + 4 * (int)(blockIdx.x & 63u) + (int)(threadIdx.x >> 6);
-    if (!SWAP)
-        g_match_row<unsigned char, int, false>(e->ldesc, e->lxy, e->l_len, row, e->rdesc, e->rxy, e->r_len, e->guide, out + 5 * (size_t)e->foff);
-    else
-        g_match_row<unsigned char, int, true>(e->rdesc, e->rxy, e->r_len, row, e->ldesc, lines + (size_t)e->foff, e->l_len, e->guide,
-                                              out + 5 * (size_t)e->boff);
+    if (!SWAP) gg_forward(e, row, out);
+    else gg_backward(e, row, lines, out);
 }
+
+// the record carries the distance's bits, whichever type it has
+__device__ __forceinline__ int gg_bits(float d) { return __float_as_int(d); }
+__device__ __forceinline__ int gg_bits(int d) { return d; }
 
 // The rule of match_rule.h for left row i of edge e: the edge's forward result, and with the cross-check the gather into
 // the edge's backward rows.
-__device__ __forceinline__ bool gg_rule(const GGEdge* __restrict__ e, const int* __restrict__ fwd, const int* __restrict__ bwd, int i,
+template <class T, class D>
+__device__ __forceinline__ bool gg_rule(const GGEdge<T>* __restrict__ e, const int* __restrict__ fwd, const int* __restrict__ bwd, int i,
                                         float ratio, int mutual, int4& rec)
 {
     const int l_len = e->l_len;
     if (i >= l_len) return false;
-    int j, d1, d2;
-    psx_directed_load<int>(fwd + 5 * (size_t)e->foff, l_len, i, j, d1, d2);
+    int j;
+    D d1, d2;
+    psx_directed_load<D>(fwd + 5 * (size_t)e->foff, l_len, i, j, d1, d2);
     bool keep = psx_match_keep(psx_match_dist(d1), psx_match_dist(d2), ratio);
     if (keep && mutual) keep = psx_directed_best(bwd + 5 * (size_t)e->boff, j) == i;
-    rec = make_int4(i, j, d1, d2);
+    rec = make_int4(i, j, gg_bits(d1), gg_bits(d2));
     return keep;
 }
 
 // grid: the forward block table, edge-major: one total per workgroup
-__global__ __launch_bounds__(256) void k_gg_count(const GGEdge* __restrict__ edges, const int2* __restrict__ blocks, const int* __restrict__ fwd,
+template <class T, class D>
+__global__ __launch_bounds__(256) void k_gg_count(const GGEdge<T>* __restrict__ edges, const int2* __restrict__ blocks, const int* __restrict__ fwd,
                                                   const int* __restrict__ bwd, float ratio, int mutual, int* __restrict__ wg_tot)
 {
     const int2 blk = blocks[blockIdx.x];
     int4 rec;
-    const bool keep = gg_rule(edges + blk.x, fwd, bwd, blk.y + (int)threadIdx.x, ratio, mutual, rec);
+    const bool keep = gg_rule<T, D>(edges + blk.x, fwd, bwd, blk.y + (int)threadIdx.x, ratio, mutual, rec);
     __shared__ int s_cnt[4];
     wg_count(__ballot(keep), s_cnt);
     if (threadIdx.x == 0) wg_tot[blockIdx.x] = wg_total(s_cnt);
@@ -123,14 +152,15 @@ __global__ __launch_bounds__(1024) void k_gg_scan(const int* __restrict__ wg_tot
 // grid as k_gg_count.  Evaluates the rule again, ranks its lanes and writes each surviving record with ONE 16-byte store
 // at offs[workgroup] + rank, never at or past capacity; an edge's first workgroup writes the edge's count (an edge without
 // workgroups keeps the zero the host put there), workgroup 0 the total.
-__global__ __launch_bounds__(256) void k_gg_write(const GGEdge* __restrict__ edges, const int2* __restrict__ blocks, const int* __restrict__ fwd,
+template <class T, class D>
+__global__ __launch_bounds__(256) void k_gg_write(const GGEdge<T>* __restrict__ edges, const int2* __restrict__ blocks, const int* __restrict__ fwd,
                                                   const int* __restrict__ bwd, float ratio, int mutual, const int* __restrict__ offs,
                                                   int4* __restrict__ out, int capacity, int* __restrict__ edge_counts, int* __restrict__ total)
 {
     const int2 blk = blocks[blockIdx.x];
-    const GGEdge* e = edges + blk.x;
+    const GGEdge<T>* e = edges + blk.x;
     int4 rec = make_int4(0, 0, 0, 0);
-    const bool keep = gg_rule(e, fwd, bwd, blk.y + (int)threadIdx.x, ratio, mutual, rec);
+    const bool keep = gg_rule<T, D>(e, fwd, bwd, blk.y + (int)threadIdx.x, ratio, mutual, rec);
     const unsigned long long m = __ballot(keep);
     __shared__ int s_cnt[4];
     wg_count(m, s_cnt);
@@ -144,15 +174,22 @@ __global__ __launch_bounds__(256) void k_gg_write(const GGEdge* __restrict__ edg
 
 size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
 
+template <class T> struct GGDist;                                    // the distance type of a descriptor element
+template <> struct GGDist<unsigned char> { typedef int type; };
+template <> struct GGDist<float> { typedef float type; };
+
 } // namespace
 
 // The ONE batched driver, behind the argument checks of its caller (psx_gg_args_ok for an edge list; the star's own,
-// match_guided_many.hip): internal, declared in match_scratch.h.  host_pairs or d_pairs (the other is NULL; both NULL with
-// capacity 0)
-int psx_guided_edges_run(int device, const unsigned char* const* d_sets, const float* const* d_xys, const int* lens, const psx_view_edge* edges,
+// match_guided_many.hip): internal, declared in match_scratch.h and instantiated below for byte and for float descriptors.
+// host_pairs or d_pairs (the other is NULL; both NULL with capacity 0)
+template <class T>
+int psx_guided_edges_run(int device, const T* const* d_sets, const float* const* d_xys, const int* lens, const psx_view_edge* edges,
                          int n_edges, const psx_guide* guides, const psx_match_opts* opts, void* host_pairs, void* d_pairs, int capacity,
                          int* edge_counts, int* count)
 {
+    typedef GGEdge<T> GGEdge;
+    typedef typename GGDist<T>::type D;
     const int E = n_edges;
     thread_local std::vector<psx_gg_edge> ep;
     ep.resize((size_t)E + 1);
@@ -219,13 +256,13 @@ int psx_guided_edges_run(int device, const unsigned char* const* d_sets, const f
 
     if (hipMemcpyAsync(sc.buf[MS_GGRAPH_TABLES], hp + off_blob, blob_b, hipMemcpyHostToDevice, st) != hipSuccess) return PSX_ERR_HIP;
     if (mutual) {
-        hipLaunchKernelGGL(k_gg_lines, dim3((unsigned)FB), dim3(256), 0, st, t_edges, t_fblk, d_lines);
-        hipLaunchKernelGGL(k_gg_match<true>, dim3((unsigned)(BB * 64)), dim3(256), 0, st, t_edges, t_bblk, static_cast<const float4*>(d_lines), d_bwd);
+        hipLaunchKernelGGL(k_gg_lines<T>, dim3((unsigned)FB), dim3(256), 0, st, t_edges, t_fblk, d_lines);
+        hipLaunchKernelGGL((k_gg_match<T, true>), dim3((unsigned)(BB * 64)), dim3(256), 0, st, t_edges, t_bblk, static_cast<const float4*>(d_lines), d_bwd);
     }
-    hipLaunchKernelGGL(k_gg_match<false>, dim3((unsigned)(FB * 64)), dim3(256), 0, st, t_edges, t_fblk, static_cast<const float4*>(nullptr), d_fwd);
-    hipLaunchKernelGGL(k_gg_count, dim3((unsigned)FB), dim3(256), 0, st, t_edges, t_fblk, d_fwd, d_bwd, opts->ratio, mflag, d_tot);
+    hipLaunchKernelGGL((k_gg_match<T, false>), dim3((unsigned)(FB * 64)), dim3(256), 0, st, t_edges, t_fblk, static_cast<const float4*>(nullptr), d_fwd);
+    hipLaunchKernelGGL((k_gg_count<T, D>), dim3((unsigned)FB), dim3(256), 0, st, t_edges, t_fblk, d_fwd, d_bwd, opts->ratio, mflag, d_tot);
     hipLaunchKernelGGL(k_gg_scan, dim3(1), dim3(1024), 0, st, d_tot, (int)FB, d_offs);
-    hipLaunchKernelGGL(k_gg_write, dim3((unsigned)FB), dim3(256), 0, st, t_edges, t_fblk, d_fwd, d_bwd, opts->ratio, mflag, d_offs, out, cap,
+    hipLaunchKernelGGL((k_gg_write<T, D>), dim3((unsigned)FB), dim3(256), 0, st, t_edges, t_fblk, d_fwd, d_bwd, opts->ratio, mflag, d_offs, out, cap,
                        d_counts, d_total);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return PSX_ERR_HIP;
     const int n = *h_total;
@@ -236,10 +273,16 @@ int psx_guided_edges_run(int device, const unsigned char* const* d_sets, const f
     return PSX_OK;
 }
 
+template int psx_guided_edges_run<unsigned char>(int, const unsigned char* const*, const float* const*, const int*, const psx_view_edge*, int,
+                                                  const psx_guide*, const psx_match_opts*, void*, void*, int, int*, int*);
+template int psx_guided_edges_run<float>(int, const float* const*, const float* const*, const int*, const psx_view_edge*, int, const psx_guide*,
+                                         const psx_match_opts*, void*, void*, int, int*, int*);
+
 namespace {
 
 // the edge list's entry: its argument checks, then the driver
-int match_pairs_guided_graph(int device, const unsigned char* const* d_sets, const float* const* d_xys, const int* lens, int n_sets,
+template <class T>
+int match_pairs_guided_graph(int device, const T* const* d_sets, const float* const* d_xys, const int* lens, int n_sets,
                              const psx_view_edge* edges, int n_edges, const psx_guide* guides, const psx_match_opts* opts, void* host_pairs,
                              void* d_pairs, int capacity, int* edge_counts, int* count)
 {
@@ -263,6 +306,22 @@ extern "C" int psx_match_pairs_guided_graph_u8_dev(int device, const unsigned ch
                                                    int n_sets, const psx_view_edge* edges, int n_edges, const psx_guide* guides,
                                                    const psx_match_opts* opts, psx_match_pair_u8* d_pairs, int capacity, int* edge_counts,
                                                    int* count)
+{
+    return match_pairs_guided_graph(device, d_sets, d_xys, lens, n_sets, edges, n_edges, guides, opts, nullptr, d_pairs, capacity, edge_counts,
+                                    count);
+}
+
+extern "C" int psx_match_pairs_guided_graph(int device, const float* const* d_sets, const float* const* d_xys, const int* lens, int n_sets,
+                                            const psx_view_edge* edges, int n_edges, const psx_guide* guides, const psx_match_opts* opts,
+                                            psx_match_pair* host_pairs, int capacity, int* edge_counts, int* count)
+{
+    return match_pairs_guided_graph(device, d_sets, d_xys, lens, n_sets, edges, n_edges, guides, opts, host_pairs, nullptr, capacity, edge_counts,
+                                    count);
+}
+
+extern "C" int psx_match_pairs_guided_graph_dev(int device, const float* const* d_sets, const float* const* d_xys, const int* lens, int n_sets,
+                                                const psx_view_edge* edges, int n_edges, const psx_guide* guides, const psx_match_opts* opts,
+                                                psx_match_pair* d_pairs, int capacity, int* edge_counts, int* count)
 {
     return match_pairs_guided_graph(device, d_sets, d_xys, lens, n_sets, edges, n_edges, guides, opts, nullptr, d_pairs, capacity, edge_counts,
                                     count);

@@ -27,7 +27,8 @@ inline bool psx_gg_skipped(const psx_guide& g) { return g.kind == PSX_GUIDE_NONE
 // What every entry point refuses, before anything else is looked at: what psx_match_pairs_graph_u8 refuses (opts, output,
 // capacity, count, the sets and the edges) and what psx_match_pairs_guided_many_u8 refuses (the guides -- every one is
 // checked -- and the position arrays).  sets[s] / xys[s] are device pointers: only NULL is looked at.
-inline bool psx_gg_args_ok(const unsigned char* const* sets, const float* const* xys, const int* lens, int n_sets, const psx_view_edge* edges,
+template <class T>
+inline bool psx_gg_args_ok_t(const T* const* sets, const float* const* xys, const int* lens, int n_sets, const psx_view_edge* edges,
                            int n_edges, const psx_guide* guides, const psx_match_opts* opts, const void* pairs, int capacity,
                            const int* edge_counts, const int* count)
 {
@@ -39,6 +40,19 @@ inline bool psx_gg_args_ok(const unsigned char* const* sets, const float* const*
     for (int e = 0; e < n_edges; e++)
         if (!psx_gg_skipped(guides[e]) && !psx_guide_valid(guides + e)) return false;
     return true;
+}
+inline bool psx_gg_args_ok(const unsigned char* const* sets, const float* const* xys, const int* lens, int n_sets, const psx_view_edge* edges,
+                           int n_edges, const psx_guide* guides, const psx_match_opts* opts, const void* pairs, int capacity,
+                           const int* edge_counts, const int* count)
+{
+    return psx_gg_args_ok_t(sets, xys, lens, n_sets, edges, n_edges, guides, opts, pairs, capacity, edge_counts, count);
+}
+// the float forms (psx_match_pairs_guided_graph): the same checks
+inline bool psx_gg_args_ok(const float* const* sets, const float* const* xys, const int* lens, int n_sets, const psx_view_edge* edges,
+                           int n_edges, const psx_guide* guides, const psx_match_opts* opts, const void* pairs, int capacity,
+                           const int* edge_counts, const int* count)
+{
+    return psx_gg_args_ok_t(sets, xys, lens, n_sets, edges, n_edges, guides, opts, pairs, capacity, edge_counts, count);
 }
 
 inline long long psx_gg_nblocks(int len) { return ((long long)len + PSX_MANY_BLOCK - 1) / PSX_MANY_BLOCK; }

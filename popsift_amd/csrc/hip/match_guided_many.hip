@@ -1,5 +1,6 @@
-// match_guided_many.hip -- the guided re-match of one byte descriptor set against many in one call:
-// psx_match_pairs_guided_many_u8 (+ _dev), psx_guides_from_ransac (include/popsift_hip.h).
+// match_guided_many.hip -- the guided re-match of one descriptor set against many in one call:
+// psx_match_pairs_guided_many_u8 (+ _dev), its float form psx_match_pairs_guided_many (+ _dev), psx_guides_from_ransac
+// (include/popsift_hip.h).
 //
 // One left set against K right sets, each under its own guide, is a STAR: an edge list whose edges share their left set.
 // This unit is the star's ADAPTER and holds no device code.  It makes the star's own argument checks, answers the calls
@@ -22,9 +23,10 @@ namespace {
 
 bool guide_none(const psx_guide& g) { return g.kind == PSX_GUIDE_NONE; }
 
-// host_pairs or d_pairs (the other is NULL; both NULL with capacity 0)
-int match_pairs_guided_many(int device, const unsigned char* d_left, const float* d_left_xy, int l_len,
-                            const unsigned char* const* d_rights, const float* const* d_right_xys, const int* r_lens, int n_sets,
+// host_pairs or d_pairs (the other is NULL; both NULL with capacity 0).  T: unsigned char or float, the descriptor element
+template <class T>
+int match_pairs_guided_many(int device, const T* d_left, const float* d_left_xy, int l_len,
+                            const T* const* d_rights, const float* const* d_right_xys, const int* r_lens, int n_sets,
                             const psx_guide* guides, const psx_match_opts* opts, void* host_pairs, void* d_pairs, int capacity,
                             int* set_counts, int* count)
 {
@@ -48,7 +50,7 @@ int match_pairs_guided_many(int device, const unsigned char* d_left, const float
     }
     // one total per 256 left rows of every set, skipped or not, and one more had to fit an int: they still have to
     if ((long long)K * (((long long)l_len + 255) / 256) + 1 > INT_MAX) return PSX_ERR_NOMEM;
-    thread_local std::vector<const unsigned char*> sets;
+    thread_local std::vector<const T*> sets;
     thread_local std::vector<const float*> xys;
     thread_local std::vector<int> lens;
     thread_local std::vector<psx_view_edge> edges;
@@ -77,6 +79,24 @@ extern "C" int psx_match_pairs_guided_many_u8_dev(int device, const unsigned cha
                                                   const unsigned char* const* d_rights, const float* const* d_right_xys, const int* r_lens,
                                                   int n_sets, const psx_guide* guides, const psx_match_opts* opts,
                                                   psx_match_pair_u8* d_pairs, int capacity, int* set_counts, int* count)
+{
+    return match_pairs_guided_many(device, d_left, d_left_xy, l_len, d_rights, d_right_xys, r_lens, n_sets, guides, opts, nullptr, d_pairs,
+                                   capacity, set_counts, count);
+}
+
+extern "C" int psx_match_pairs_guided_many(int device, const float* d_left, const float* d_left_xy, int l_len,
+                                           const float* const* d_rights, const float* const* d_right_xys, const int* r_lens, int n_sets,
+                                           const psx_guide* guides, const psx_match_opts* opts, psx_match_pair* host_pairs, int capacity,
+                                           int* set_counts, int* count)
+{
+    return match_pairs_guided_many(device, d_left, d_left_xy, l_len, d_rights, d_right_xys, r_lens, n_sets, guides, opts, host_pairs, nullptr,
+                                   capacity, set_counts, count);
+}
+
+extern "C" int psx_match_pairs_guided_many_dev(int device, const float* d_left, const float* d_left_xy, int l_len,
+                                               const float* const* d_rights, const float* const* d_right_xys, const int* r_lens, int n_sets,
+                                               const psx_guide* guides, const psx_match_opts* opts, psx_match_pair* d_pairs, int capacity,
+                                               int* set_counts, int* count)
 {
     return match_pairs_guided_many(device, d_left, d_left_xy, l_len, d_rights, d_right_xys, r_lens, n_sets, guides, opts, nullptr, d_pairs,
                                    capacity, set_counts, count);

@@ -61,6 +61,7 @@
 // sets (match_many_f32_plan.h: the growing buffer above 256 MiB) adds 2 launches and no synchronisation.
 #include "psx_internal.h"
 #include "match_f32_core.h"
+#include "match_f32_many_core.h"
 #include "match_join.h"
 #include "match_many_f32_plan.h"
 #include "match_many_join.h"
@@ -102,13 +103,7 @@ __global__ __launch_bounds__(256) void k_f32_many_permute(const FSet* __restrict
     const int2 blk = blocks[blockIdx.x];
     const FSet s = sets[blk.x];
     const int rows = min(PSX_MANY_BLOCK, s.len - blk.y);
-    const float* src = s.desc + (size_t)blk.y * 128;
-    float2* out = reinterpret_cast<float2*>(dst + ((size_t)s.foff + blk.y) * 128);
-    for (int i = threadIdx.x; i < rows * 64; i += 256) {              // one output pair per step
-        const int d = i >> 6, k = i & 63;
-        const float* p = src + (size_t)d * 128;
-        out[i] = make_float2(p[perm_src(k, 0)], p[perm_src(k, 1)]);
-    }
+    fm_permute_block(s.desc + (size_t)blk.y * 128, rows, reinterpret_cast<float2*>(dst + ((size_t)s.foff + blk.y) * 128));
 }
 
 // grid nblocks x nchunks, 256 threads; workgroup (ob, ch) = (blockIdx.x % nblocks, blockIdx.x / nblocks).  k_match_partial
@@ -170,11 +165,7 @@ __global__ __launch_bounds__(256) void k_f32_many_merge(const FSet* __restrict__
 
 // ---- path B --------------------------------------------------------------------------------------------------------
 
-// par[0] = 2^k, par[1] = -2 / 4^k, par[2] = the largest squared norm of the right sets, par[3] = M (match_scale),
-// par[4] = the largest squared norm of L
-constexpr int FPAR = 8;
-constexpr int FX_SEGS = 32;                    // candidate segments the exact evaluation gathers per round (4 KB of list per wave)
-constexpr int FM_SEEDBLK = 2;                  // staged blocks (of 64 rows) at a chunk's start that seed its running maxima
+// (the parameters par[], FX_SEGS, FM_SEEDBLK and the device pieces of this path: match_f32_many_core.h)
 
 // grid: every block of both sides, 256 threads, 32 lanes per row (k_match_norms' sum): norm2[foff + row] and the block's
 // largest (bits of a non-negative float; a NaN norm has the bit pattern of a huge unsigned and wins)
@@ -184,21 +175,7 @@ __global__ __launch_bounds__(256) void k_f32_many_norms(const FSet* __restrict__
     const int2 blk = blocks[blockIdx.x];
     const FSet s = sets[blk.x];
     const int end = min(blk.y + PSX_MANY_BLOCK, s.len);
-    const int q = threadIdx.x & 31;
-    float mx = 0.0f;
-    for (int d = blk.y + (int)(threadIdx.x >> 5); d < end; d += 8) {
-        const float4 v = reinterpret_cast<const float4*>(s.desc + (size_t)d * 128)[q];
-        float ss = fmaf(v.w, v.w, fmaf(v.z, v.z, fmaf(v.y, v.y, v.x * v.x)));
-        for (int k = 16; k >= 1; k >>= 1) ss += __shfl_xor(ss, k, 32);
-        if (q == 0) norm2[(size_t)s.foff + d] = ss;
-        mx = __uint_as_float(max(__float_as_uint(mx), __float_as_uint(ss < 0.0f ? 0.0f : ss)));
-    }
-    __shared__ unsigned s_max;
-    if (threadIdx.x == 0) s_max = 0u;
-    __syncthreads();
-    if (q == 0) atomicMax(&s_max, __float_as_uint(mx));
-    __syncthreads();
-    if (threadIdx.x == 0) bmax[blockIdx.x] = s_max;
+    fm_norms_block(s.desc, blk.y, end, norm2 + s.foff, bmax + blockIdx.x);
 }
 
 // grid as k_f32_many_norms; blocks [0, br) belong to the right sets, [br, br + bl) to L.  Every workgroup derives the
@@ -208,163 +185,19 @@ __global__ __launch_bounds__(256) void k_f32_many_cvt(const FSet* __restrict__ s
                                                       const unsigned* __restrict__ bmax, unsigned short* __restrict__ h16,
                                                       float* __restrict__ par, int* __restrict__ flag)
 {
-    __shared__ unsigned s_r, s_l;
-    __shared__ float s_scale;
-    if (threadIdx.x == 0) { s_r = 0u; s_l = 0u; }
-    __syncthreads();
-    unsigned rb = 0u, lb = 0u;
-    for (int i = threadIdx.x; i < br + bl; i += 256) { const unsigned v = bmax[i]; if (i < br) rb = max(rb, v); else lb = max(lb, v); }
-    for (int k = 32; k >= 1; k >>= 1) { rb = max(rb, (unsigned)__shfl_xor((int)rb, k)); lb = max(lb, (unsigned)__shfl_xor((int)lb, k)); }
-    if ((threadIdx.x & 63) == 0) { atomicMax(&s_r, rb); atomicMax(&s_l, lb); }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float pp[4]; int bad;
-        match_scale(__uint_as_float(s_l), __uint_as_float(s_r), pp, &bad);
-        s_scale = pp[0];
-        if (blockIdx.x == 0) { par[0] = pp[0]; par[1] = pp[1]; par[2] = pp[2]; par[3] = pp[3]; par[4] = bad ? 0.0f : __uint_as_float(s_l); *flag = bad; }
-    }
-    __syncthreads();
+    const float sc = fm_cvt_params(br, bl, bmax, par, flag);
     const int2 blk = blocks[blockIdx.x];
     const FSet s = sets[blk.x];
     const int rows = min(PSX_MANY_BLOCK, s.len - blk.y);
-    const float sc = s_scale;
-    const float4* src = reinterpret_cast<const float4*>(s.desc + (size_t)blk.y * 128);
-    ushort4* dst = reinterpret_cast<ushort4*>(h16 + ((size_t)s.foff + blk.y) * 128);
-    for (int g = threadIdx.x; g < rows * 32; g += 256) {              // four elements per step
-        const float4 v = src[g];
-        ushort4 o; o.x = to_f16(v.x * sc); o.y = to_f16(v.y * sc); o.z = to_f16(v.z * sc); o.w = to_f16(v.w * sc);
-        dst[g] = o;
-    }
+    fm_cvt_block(reinterpret_cast<const float4*>(s.desc + (size_t)blk.y * 128), rows, sc,
+                 reinterpret_cast<ushort4*>(h16 + ((size_t)s.foff + blk.y) * 128));
 }
-
-// the segment of (outer row among the launch's rows, chunk among the launch's chunks, half wave): recomputed where a
-// candidate is stored (rare) instead of held in two registers
-__device__ __forceinline__ int fm_seg(int row, int nchunks, int ch, int half) { return (row * nchunks + ch) * 2 + half; }
-
-// One walk of the staged tile loop over staged blocks [0, nt) of the chunk [r0, r1) of the inner set (rh / rn2: its f16
-// rows and norms; row reads clamped to ITS last row): the loop of k_match_mfma, as a function so that the workgroup can
-// run it twice.  SEEDPH: every value updates the lane's running maxima, no candidates.  Otherwise: the test of k_match_mfma
-// against the threshold the column had before the tile; behind the nseed seeded blocks the maxima then take the tile's
-// largest value of BOTH half waves (one shuffle per column), which keeps them equal in the two halves.
-template <bool SEEDPH>
-__device__ __forceinline__ void fm_walk(unsigned char (*s_r)[MF_SUB * MF_TILE * MF_ROW], float (*s_n)[MF_SUB * MF_TILE],
-                                        const unsigned short* __restrict__ rh, const float* __restrict__ rn2, int r_len, int r0, int r1,
-                                        int nt, int nseed, float inv, bool has_rows, const f16x8 (&bfrag)[2][8], const float (&twoE)[2],
-                                        float (&m1)[2], float (&m2)[2], const int (&lidx)[2], int l_len, int (&cnt)[2],
-                                        int* __restrict__ cand, int prow, int nchunks, int ch)
-{
-    const int t = threadIdx.x, half = (t & 63) >> 5, col = t & 31;
-    // ---- staging, as k_match_mfma: issue() = global loads of block k + 2 into registers, commit() = registers into the LDS
-    // buffer of block k + 1; one barrier per two tiles.  Row reads are clamped to the inner set's own last row. ----
-    static_assert(MF_SUB == 2, "four staging loads per thread");
-    uint4 pre0 = make_uint4(0u, 0u, 0u, 0u), pre1 = make_uint4(0u, 0u, 0u, 0u), pre2 = make_uint4(0u, 0u, 0u, 0u), pre3 = make_uint4(0u, 0u, 0u, 0u);
-    float pre_n = INFINITY;
-    const int st_row0 = t >> 4, st_c16 = t & 15;             // rows st_row0 + 16 i, i = 0..3
-#define MF_LOAD_(i_) (*reinterpret_cast<const uint4*>(rh + (size_t)min(base_ + st_row0 + 16 * (i_), r_len - 1) * 128 + st_c16 * 8))
-#define MF_ISSUE(tile_) do { \
-        const int base_ = r0 + (tile_) * (MF_SUB * MF_TILE); \
-        pre0 = MF_LOAD_(0); pre1 = MF_LOAD_(1); pre2 = MF_LOAD_(2); pre3 = MF_LOAD_(3); \
-        if (t < MF_SUB * MF_TILE) pre_n = (base_ + t < r1) ? rn2[min(base_ + t, r_len - 1)] : INFINITY;     /* rows beyond the chunk never win */ \
-    } while (0)
-#define MF_COMMIT(buf_) do { \
-        *reinterpret_cast<uint4*>(&s_r[buf_][(st_row0 +  0) * MF_ROW + st_c16 * 16]) = pre0; \
-        *reinterpret_cast<uint4*>(&s_r[buf_][(st_row0 + 16) * MF_ROW + st_c16 * 16]) = pre1; \
-        *reinterpret_cast<uint4*>(&s_r[buf_][(st_row0 + 32) * MF_ROW + st_c16 * 16]) = pre2; \
-        *reinterpret_cast<uint4*>(&s_r[buf_][(st_row0 + 48) * MF_ROW + st_c16 * 16]) = pre3; \
-        if (t < MF_SUB * MF_TILE) s_n[buf_][t] = pre_n * inv;      /* +inf (rows beyond the chunk) becomes -inf: never a maximum */ \
-    } while (0)
-
-    if (nt > 0) { MF_ISSUE(0); MF_COMMIT(0); }
-    if (nt > 1) MF_ISSUE(1);
-    __syncthreads();
-    for (int tile = 0; tile < nt; tile++) {
-        const int buf = tile & 1;
-        if (tile + 1 < nt) MF_COMMIT(buf ^ 1);           // loaded during the previous iteration
-        if (tile + 2 < nt) MF_ISSUE(tile + 2);
-        if (has_rows) {
-#pragma unroll
-        for (int sub = 0; sub < MF_SUB; sub++) {
-        // accumulators start at |r|^2 / fneg2 of their row (C/D layout: row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5))
-        f32x16 acc[2];
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const f32x4 nr = *reinterpret_cast<const f32x4*>(&s_n[buf][sub * MF_TILE + 8 * g + 4 * half]);
-#pragma unroll
-            for (int e = 0; e < 4; e++) { acc[0][4 * g + e] = nr[e]; acc[1][4 * g + e] = nr[e]; }
-        }
-        const unsigned char* rp = &s_r[buf][(sub * MF_TILE + col) * MF_ROW + half * 16];
-#pragma unroll
-        for (int kk = 0; kk < 8; kk++) {
-            const f16x8 a = *reinterpret_cast<const f16x8*>(rp + kk * 32);
-            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bfrag[0][kk], acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bfrag[1][kk], acc[1], 0, 0, 0);
-        }
-        const int base = r0 + (tile * MF_SUB + sub) * MF_TILE;
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            if (SEEDPH) {
-                // the two largest of everything this half wave sees: no threshold, every value updates them
-#pragma unroll
-                for (int reg = 0; reg < 16; reg++) {
-                    m2[c] = __builtin_amdgcn_fmed3f(m1[c], m2[c], acc[c][reg]);
-                    m1[c] = fmaxf(m1[c], acc[c][reg]);
-                }
-                continue;
-            }
-            // The whole tile column against the threshold the column had BEFORE this tile (a superset test): one maximum of the
-            // lane's 16 values and one compare (k_match_mfma).  Behind the seeded blocks the maxima then take the tile's largest
-            // value of BOTH half waves (disjoint rows of the same column: one shuffle) -- a value below the threshold cannot
-            // change either of the two; the seeded blocks' rows are in the maxima already and must not enter twice.
-            float gm[4];
-#pragma unroll
-            for (int g = 0; g < 4; g++) gm[g] = fmaxf(fmaxf(fmaxf(acc[c][4 * g], acc[c][4 * g + 1]), acc[c][4 * g + 2]), acc[c][4 * g + 3]);
-            const float mx = fmaxf(fmaxf(fmaxf(gm[0], gm[1]), gm[2]), gm[3]);
-            const float thr = m2[c] - twoE[c];
-            const bool any = mx >= thr;
-            if (tile >= nseed) {
-                const float mo = __shfl_xor(mx, 32);
-                m2[c] = __builtin_amdgcn_fmed3f(m1[c], m2[c], mx);
-                m1[c] = fmaxf(m1[c], mx);
-                m2[c] = __builtin_amdgcn_fmed3f(m1[c], m2[c], mo);
-                m1[c] = fmaxf(m1[c], mo);
-            }
-            if (__ballot(any) != 0ull) {
-                if (any && lidx[c] < l_len) {
-                    unsigned hits = 0u;
-#pragma unroll
-                    for (int g = 0; g < 4; g++) {
-                        if (__ballot(gm[g] >= thr) != 0ull) {
-#pragma unroll
-                            for (int e = 0; e < 4; e++) hits |= (acc[c][4 * g + e] >= thr ? 1u : 0u) << (15 - (4 * g + e));
-                        }
-                    }
-                    while (hits != 0u) {
-                        const int b = 31 - __builtin_clz(hits);
-                        hits &= ~(1u << b);
-                        const int reg = 15 - b;
-                        const int ridx = base + 8 * (reg >> 2) + 4 * half + (reg & 3);
-                        if (ridx < r1) {
-                            if (cnt[c] < MF_SEGCAP) cand[fm_seg(prow + lidx[c], nchunks, ch, half) * MF_SEGCAP + cnt[c]] = ridx;
-                            cnt[c]++;
-                        }
-                    }
-                }
-            }
-        }
-        }   // sub
-        }   // has_rows
-        __syncthreads();
-    }
-}
-
-#undef MF_ISSUE
-#undef MF_COMMIT
-#undef MF_LOAD_
 
 // grid nblocks x nchunks, 256 threads; workgroup (ob, ch) as k_f32_many_partial.  The tile loop of k_match_mfma<false>
 // (match.hip: operand layout, the staged 2 x 32-row blocks, the norm term as the accumulator's initial value, one maximum
 // per tile column) with both sides taken from tables: wave w owns outer rows [row0 + 64 w, + 64) of ITS block's set as two B
 // fragment sets and walks rows [r0, r1) of ITS chunk's set.  lh / rh: the sets' rows in the gathered f16 copy.
+// The loop itself -- fm_prefilter_block and fm_walk, __builtin_amdgcn_mfma_f32_32x32x16_f16 -- is match_f32_many_core.h's.
 // Segment of (outer row, chunk, half wave): cand[(((row among the launch's rows) * nchunks + ch) * 2 + half) * MF_SEGCAP + ...],
 // its count in cand_ct at the same index without the last factor; indices within the inner set.
 __global__ __launch_bounds__(256, 3) void k_f32_many_mfma(const FSet* __restrict__ sets, const int4* __restrict__ chunks,
@@ -378,57 +211,9 @@ __global__ __launch_bounds__(256, 3) void k_f32_many_mfma(const FSet* __restrict
     const int2 blk = blocks[ps.block_base + ob];
     const int4 chk = chunks[ps.chunk_base + ch];
     const FSet os = sets[blk.x], is = sets[chk.x];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int col = lane & 31, half = lane >> 5;
-    const int l_len = os.len, r_len = is.len;
-    const unsigned short* lh = h16 + (size_t)os.foff * 128;
-    const unsigned short* rh = h16 + (size_t)is.foff * 128;
-    const float* ln2 = n2 + os.foff;
-    const float* rn2 = n2 + is.foff;
-    const int r0 = chk.y, r1 = min(chk.z, r_len);
-    const int ntiles = (r1 - r0 + MF_SUB * MF_TILE - 1) / (MF_SUB * MF_TILE);      // staged blocks of MF_SUB tiles
     // Rmax: over the rows this direction ranks -- all right rows forward, L backward
-    const float fneg2 = par[1], rmax2 = backward ? par[4] : par[2], bigM = par[3];
-    const float rmax = sqrtf(rmax2);
-    const float inv = 1.0f / fneg2;                           // the epilogue works on D = s' / fneg2 (k_match_mfma)
-    const bool has_rows = blk.y + wave * 64 < l_len;          // a wave without outer rows only stages (wave uniform)
-
-    // ---- this wave's outer rows: B operands (8 K-steps x 2 column sets), margins; the running maxima start empty ----
-    f16x8 bfrag[2][8];
-    float twoE[2], m1[2], m2[2];
-    int lidx[2];
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        const int li = blk.y + wave * 64 + c * 32 + col;
-        lidx[c] = li;
-        const int lq = min(li, l_len - 1);
-        const unsigned short* lp = lh + (size_t)lq * 128 + half * 8;
-#pragma unroll
-        for (int kk = 0; kk < 8; kk++) bfrag[c][kk] = *reinterpret_cast<const f16x8*>(lp + kk * 16);
-        const float nl = ln2[lq];
-        const float E = match_margin(nl, rmax, rmax2, bigM);
-        twoE[c] = 2.0f * E * -inv;                      // the margin in D units (-inv > 0, a power of two: exact)
-        m1[c] = m2[c] = -INFINITY;
-    }
-    int cnt[2] = {0, 0};                         // candidates of this lane's segment = (outer row, chunk, half wave)
-    // (the plan keeps 32 x the segments of a group below 2^31: fm_seg)
-    const int prow = os.roff - ps.row_base;
-
-    // phase 0 seeds the running maxima from the chunk's first FM_SEEDBLK staged blocks (no candidates; every value updates
-    // them), and the two half waves -- different rows of the same columns -- continue with the two largest of the union;
-    // phase 1 walks the whole chunk, those blocks again, and tests
-    const int nseed = min(FM_SEEDBLK, ntiles);
-    fm_walk<true>(s_r, s_n, rh, rn2, r_len, r0, r1, nseed, nseed, inv, has_rows, bfrag, twoE, m1, m2, lidx, l_len, cnt, cand, prow, ps.nchunks, ch);
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        const float o1 = __shfl_xor(m1[c], 32), o2 = __shfl_xor(m2[c], 32);
-        const float d1 = fmaxf(m1[c], o1), d2 = fmaxf(fminf(m1[c], o1), fmaxf(m2[c], o2));
-        m1[c] = d1; m2[c] = d2;
-    }
-    fm_walk<false>(s_r, s_n, rh, rn2, r_len, r0, r1, ntiles, nseed, inv, has_rows, bfrag, twoE, m1, m2, lidx, l_len, cnt, cand, prow, ps.nchunks, ch);
-#pragma unroll
-    for (int c = 0; c < 2; c++)
-        if (lidx[c] < l_len) cand_ct[fm_seg(prow + lidx[c], ps.nchunks, ch, half)] = cnt[c];
+    fm_prefilter_block(s_r, s_n, h16 + (size_t)os.foff * 128, n2 + os.foff, os.len, blk.y, h16 + (size_t)is.foff * 128, n2 + is.foff, is.len,
+                       chk.y, min(chk.z, is.len), par[1], backward ? par[4] : par[2], par[3], cand_ct, cand, os.roff - ps.row_base, ps.nchunks, ch);
 }
 
 // grid nblocks x 64 x ngroups, 256 threads: wave w of workgroup (ob, q, g) takes outer row blk.row0 + 4 q + w against inner
@@ -447,64 +232,16 @@ __global__ __launch_bounds__(256) void k_f32_many_exact(const FSet* __restrict__
     const int g = group_base + (int)(rest >> 6);
     const int2 blk = blocks[ps.block_base + ob];
     const FSet os = sets[blk.x], is = sets[g];
-    const int lane = threadIdx.x & 63, tl = lane & 31, half = lane >> 5;
+    const int lane = threadIdx.x & 63, tl = lane & 31;
     const int row = blk.y + (int)(rest & 63u) * 4 + (int)(threadIdx.x >> 6);
     if (row >= os.len || is.len == 0) return;                   // wave uniform
     const float4 l4 = reinterpret_cast<const float4*>(os.desc + (size_t)row * 128)[tl];
     const size_t prow = (size_t)(os.roff - ps.row_base) + row;
-    // the sentinel index is larger than any real one: an empty slot loses every tie
-    Top2 t = {INFINITY, INFINITY, 0x7fffffff, 0x7fffffff};
-    bool over = false;
-    // The set's segments -- two per chunk, contiguous for one outer row -- FX_SEGS at a time: lane s < FX_SEGS owns segment s
-    // of the round, the segments are compacted into one list in LDS (k_match_exact), and the list is walked two candidates
-    // per half wave and step.  One round for a set of up to 16 chunks.
+    // the set's segments -- two per chunk, contiguous for one outer row
     __shared__ int s_list[4][FX_SEGS * MF_SEGCAP];
-    int* cl = s_list[threadIdx.x >> 6];
-    const size_t seg0 = (prow * ps.nchunks + (size_t)(is.c0 - ps.chunk_base)) * 2;
-    const int nseg = 2 * (is.c1 - is.c0);
-    for (int s0 = 0; s0 < nseg; s0 += FX_SEGS) {
-        const bool mine = lane < FX_SEGS && s0 + lane < nseg;
-        const int rawct = mine ? cand_ct[seg0 + s0 + lane] : 0;
-        over |= rawct > MF_SEGCAP;
-        const int myct = min(rawct, MF_SEGCAP);
-        int off = myct;                                          // inclusive prefix sum over the 64 lanes
-#pragma unroll
-        for (int k = 1; k < 64; k <<= 1) { const int o = __shfl_up(off, k); if (lane >= k) off += o; }
-        const int n = __shfl(off, 63);
-        off -= myct;
-        for (int k = 0; k < myct; k++) cl[off + k] = cand[(seg0 + s0 + lane) * MF_SEGCAP + k];
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the wave reads what its own lanes wrote
-        __builtin_amdgcn_wave_barrier();
-        // 2 x EX_K candidates per step (EX_K per half wave): all 512-byte reads of a half are in flight before the first reduction
-        constexpr int EX_K = 2;
-        for (int c0 = 0; c0 < n; c0 += 2 * EX_K) {
-            int ri[EX_K];
-            float4 r4[EX_K];
-#pragma unroll
-            for (int k = 0; k < EX_K; ++k) {
-                const int c = c0 + 2 * k + half;
-                ri[k] = c < n ? cl[c] : -1;
-                r4[k] = reinterpret_cast<const float4*>(is.desc + (size_t)(ri[k] < 0 ? 0 : ri[k]) * 128)[tl];
-            }
-#pragma unroll
-            for (int k = 0; k < EX_K; ++k) {
-                const float qx = l4.x - r4[k].x, qy = l4.y - r4[k].y, qz = l4.z - r4[k].z, qw = l4.w - r4[k].w;
-                float v = fmaf(qw, qw, fmaf(qz, qz, fmaf(qx, qx, qy * qy)));
-                v += __shfl_down(v, 16, 32); v += __shfl_down(v, 8, 32); v += __shfl_down(v, 4, 32);
-                v += __shfl_down(v, 2, 32);  v += __shfl_down(v, 1, 32);
-                const float d = __shfl(v, 0, 32);                // the half's distance, in all of its lanes
-                if (ri[k] >= 0) top2_insert_lex(t, d, ri[k]);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next round overwrites the list
-        __builtin_amdgcn_wave_barrier();
-    }
-    {   // the two halves hold disjoint candidate subsets: merge
-        const float od1 = __shfl_xor(t.d1, 32), od2 = __shfl_xor(t.d2, 32);
-        const int oi1 = __shfl_xor(t.i1, 32), oi2 = __shfl_xor(t.i2, 32);
-        top2_insert_lex(t, od1, oi1);
-        top2_insert_lex(t, od2, oi2);
-    }
+    Top2 t;
+    const bool over = fm_exact_row(l4, is.desc, cand_ct, cand, (prow * ps.nchunks + (size_t)(is.c0 - ps.chunk_base)) * 2, 2 * (is.c1 - is.c0),
+                                   s_list[threadIdx.x >> 6], t);
     if (__ballot(over) != 0ull && lane == 0) *flag = 1;
     if (lane == 0) {
         // the reference starts from (inf, inf, index 0, index 0) and never replaces an entry by an equal one

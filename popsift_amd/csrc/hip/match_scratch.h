@@ -1,5 +1,5 @@
 // match_scratch.h -- what the matcher's translation units share (match.hip, match_guided.hip, match_many.hip,
-// match_many_f32.hip, match_guided_many.hip, match_graph.hip, match_guided_graph.hip, ransac.hip, ransac_many.hip,
+// match_many_f32.hip, match_guided_many.hip, match_graph.hip, match_graph_f32.hip, match_guided_graph.hip, ransac.hip, ransac_many.hip,
 // ransac_graph.hip, tracks.hip):
 // the layout of a directed result, the per-thread scratch with its named buffers, the runner of the pair join, and the
 // two batched drivers that a star form shares with its edge-list form.
@@ -70,7 +70,8 @@ enum MatchSlot {
     MS_MANY_FWD,         // the forward direction's results of all sets
     MS_MANY_BWD,         // the backward direction's
     MS_MANY_TOT,         // the join's per-workgroup totals and their offsets
-    MS_MANYF_TABLES,     // the float one-to-many search (match_many_f32.hip): the set / chunk / block tables
+    MS_MANYF_TABLES,     // the float one-to-many search (match_many_f32.hip) and the float edge list (match_graph_f32.hip), which never run
+                         // at once on a thread and share these: the set / (edge / item) / chunk / block tables
     MS_MANYF_STATE,      // the blocks' largest norms, the prefilter's parameters and its flag
     MS_MANYF_PERM,       // the scan: the permuted copy of every inner row
     MS_MANYF_PARTIAL,    // the scan: the per-chunk top-2
@@ -188,6 +189,8 @@ int psx_ransac_lists_run(int model, int device, const void* host_pairs, const vo
                          int capacity, int* count, float* host_models, int* host_counts);
 // match_guided_graph.hip: the edges over the set arrays, each under its own guide.  What psx_graph_args_ok asks of lens
 // and edges holds; a set that no live edge names (match_guided_graph_plan.h) may have NULL arrays.  host_pairs or d_pairs.
-int psx_guided_edges_run(int device, const unsigned char* const* d_sets, const float* const* d_xys, const int* lens, const psx_view_edge* edges,
+// T: unsigned char (psx_match_pair_u8 records) or float (psx_match_pair records); defined and instantiated for both there.
+template <class T>
+int psx_guided_edges_run(int device, const T* const* d_sets, const float* const* d_xys, const int* lens, const psx_view_edge* edges,
                          int n_edges, const psx_guide* guides, const psx_match_opts* opts, void* host_pairs, void* d_pairs, int capacity,
                          int* edge_counts, int* count);

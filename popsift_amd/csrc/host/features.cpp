@@ -1396,4 +1396,208 @@ std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedGraph( const std::v
     return out;
 }
 
+// ---- the float forms of the edge-list calls and of the batched guided calls -------------------------------------------------
+namespace {
+
+// the guides as the library takes them; refuses, before any device is touched (and for empty sides too), what the calls refuse
+std::vector<psx_guide> float_guides( const char* who, const std::vector<MatchGuide>& guides )
+{
+    std::vector<psx_guide> pg( guides.size() );
+    for( size_t e = 0; e < guides.size(); e++ ) {
+        pg[e].kind = (int)guides[e].kind;
+        for( int q = 0; q < 9; q++ ) pg[e].m[q] = guides[e].m[q];
+        pg[e].tol = guides[e].tol;
+        if( pg[e].kind == PSX_GUIDE_NONE ) continue;
+        bool ok = ( pg[e].kind == PSX_GUIDE_HOMOGRAPHY || pg[e].kind == PSX_GUIDE_EPIPOLAR ) && std::isfinite( pg[e].tol ) && pg[e].tol >= 0.0f;
+        for( int q = 0; q < 9; q++ ) ok = ok && std::isfinite( pg[e].m[q] );
+        if( !ok ) fatal( __FILE__, __LINE__, std::string( who ) + ": invalid guide (kind 0, 1 or 2, finite entries, finite tolerance >= 0)" );
+    }
+    return pg;
+}
+
+// the concatenated float records of an edge-list call, cut at the per-edge counts and mapped through the two views'
+// reverse maps (fem[v]: view v's, read by the caller for every view a counted edge names)
+std::vector<std::vector<Match>> float_lists( const std::vector<psx_match_pair>& pf, const std::vector<int>& counts, const std::vector<psx_view_edge>& pe,
+                                             const std::vector<std::vector<int>>& fem )
+{
+    std::vector<std::vector<Match>> out( counts.size() );
+    size_t at = 0;
+    for( size_t e = 0; e < counts.size(); e++ ) {
+        if( counts[e] <= 0 ) continue;
+        const std::vector<int>& l_fem = fem[pe[e].left];
+        const std::vector<int>& r_fem = fem[pe[e].right];
+        out[e].resize( counts[e] );
+        for( int q = 0; q < counts[e]; q++, at++ ) {
+            Match& m = out[e][q];
+            m.left_descriptor = pf[at].left; m.right_descriptor = pf[at].right;
+            m.distance = pf[at].d1; m.second_distance = pf[at].d2;
+            m.left_feature  = l_fem[m.left_descriptor];
+            m.right_feature = r_fem[m.right_descriptor];
+        }
+    }
+    return out;
+}
+
+}
+
+// Both edge-list float forms: psx_match_pairs_graph (guides == nullptr) or psx_match_pairs_guided_graph on the views' own
+// float descriptors -- nothing is quantised, no descriptor is copied; the guided form gathers every used view's positions once
+std::vector<std::vector<Match>> FeaturesDev::matchGraphFloat( const char* who, const std::vector<FeaturesDev*>& views,
+                                                              const std::vector<std::pair<int,int>>& edges, const std::vector<MatchGuide>* guides,
+                                                              const MatchOptions& opts )
+{
+    const int device = graph_views_device( who, views, edges, []( FeaturesDev* f ) { return f->_device; } );
+    if( opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": float descriptors only (use the byte form for MatchOptions::bytes)" );
+    if( guides && guides->size() != edges.size() ) {
+        std::ostringstream ss;
+        ss << who << ": " << edges.size() << " edges but " << guides->size() << " guides";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    const int N = (int)views.size(), E = (int)edges.size();
+    std::vector<psx_guide> pg;
+    if( guides ) pg = float_guides( who, *guides );
+    std::vector<std::vector<Match>> out( edges.size() );
+    std::vector<int> lens( views.size(), 0 );
+    std::vector<char> used( views.size(), 0 );               // named by an edge that is not skipped and has two non-empty sides
+    long long room = 0;                                      // at most lens[left] pairs per edge exist
+    for( int e = 0; e < E; e++ ) {
+        const int l = edges[e].first, r = edges[e].second;
+        if( ( guides && pg[e].kind == PSX_GUIDE_NONE ) || views[l]->getDescriptorCount() <= 0 || views[r]->getDescriptorCount() <= 0 ) continue;
+        room += views[l]->getDescriptorCount();
+        used[l] = used[r] = 1;
+    }
+    if( room == 0 ) return out;
+    psx_match_opts po;
+    po.ratio = opts.ratio;
+    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
+    std::vector<void*> bufs( views.size(), nullptr );        // the guided form: view v's positions
+    std::vector<const float*> ptrs( views.size(), nullptr ), xys( views.size(), nullptr );
+    int rc = PSX_OK;
+    for( int v = 0; v < N && rc == PSX_OK; v++ ) {
+        if( !used[v] ) continue;                             // a view no live edge names is an empty set to the call
+        const int len = lens[v] = views[v]->getDescriptorCount();
+        ptrs[v] = (const float*)views[v]->_ori;
+        if( !guides ) continue;
+        rc = psx_dev_alloc( device, (size_t)len * 2 * sizeof(float), &bufs[v] );
+        if( rc == PSX_OK ) rc = psx_desc_positions( device, (const psx_feature_dev*)views[v]->_ext, views[v]->_rev, len, (float*)bufs[v] );
+        xys[v] = (const float*)bufs[v];
+    }
+    std::vector<psx_view_edge> pe( edges.size() );
+    for( int e = 0; e < E; e++ ) { pe[e].left = edges[e].first; pe[e].right = edges[e].second; }
+    std::vector<psx_match_pair> pf( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
+    std::vector<int> counts( edges.size(), 0 );
+    int count = 0;
+    if( rc == PSX_OK )
+        rc = guides ? psx_match_pairs_guided_graph( device, ptrs.data(), xys.data(), lens.data(), N, pe.data(), E, pg.data(), &po, pf.data(),
+                                                    (int)pf.size(), counts.data(), &count )
+                    : psx_match_pairs_graph( device, ptrs.data(), lens.data(), N, pe.data(), E, &po, pf.data(), (int)pf.size(), counts.data(), &count );
+    for( void* b : bufs ) psx_dev_free( device, b );
+    if( rc != PSX_OK ) {
+        std::ostringstream ss;
+        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    std::vector<std::vector<int>> fem( views.size() );       // every used view's reverse map, read once
+    for( int v = 0; v < N; v++ ) {
+        if( !used[v] ) continue;
+        fem[v].resize( lens[v] );
+        if( psx_dev_read( device, fem[v].data(), views[v]->_rev, (size_t)lens[v] * sizeof(int) ) != PSX_OK )
+            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
+    }
+    return float_lists( pf, counts, pe, fem );
+}
+
+std::vector<std::vector<Match>> FeaturesDev::matchPairsGraphFloat( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                   const MatchOptions& opts )
+{
+    return matchGraphFloat( "FeaturesDev::matchPairsGraphFloat", views, edges, nullptr, opts );
+}
+
+std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedGraphFloat( const std::vector<FeaturesDev*>& views,
+                                                                         const std::vector<std::pair<int,int>>& edges,
+                                                                         const std::vector<MatchGuide>& guides, const MatchOptions& opts )
+{
+    return matchGraphFloat( "FeaturesDev::matchPairsGuidedGraphFloat", views, edges, &guides, opts );
+}
+
+// FeaturesDev::matchPairsGuidedManyFloat: psx_match_pairs_guided_many on this object's float descriptors and every other
+// object's that is neither empty nor skipped -- no quantisation, no descriptor copies, every side's positions gathered once
+std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedManyFloat( const std::vector<FeaturesDev*>& others, const std::vector<MatchGuide>& guides,
+                                                                        const MatchOptions& opts )
+{
+    const char* who = "FeaturesDev::matchPairsGuidedManyFloat";
+    for( FeaturesDev* o : others ) {
+        if( o == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
+        if( o->_device != _device ) {
+            std::ostringstream ss;
+            ss << who << ": the objects live on different devices (" << _device << " and " << o->_device << ")";
+            fatal( __FILE__, __LINE__, ss.str() );
+        }
+    }
+    if( opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": float descriptors only (use matchPairsGuidedMany for MatchOptions::bytes)" );
+    if( guides.size() != others.size() ) {
+        std::ostringstream ss;
+        ss << who << ": " << others.size() << " objects but " << guides.size() << " guides";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    const int K = (int)others.size();
+    const std::vector<psx_guide> pg = float_guides( who, guides );
+    const int l_len = getDescriptorCount();
+    std::vector<std::vector<Match>> out( others.size() );
+    std::vector<int> lens( K, 0 ), counts( K, 0 );
+    bool any = false;
+    for( int k = 0; k < K; k++ ) {
+        if( pg[k].kind != PSX_GUIDE_NONE && others[k]->getDescriptorCount() > 0 ) lens[k] = others[k]->getDescriptorCount();
+        any = any || lens[k] > 0;
+    }
+    if( l_len <= 0 || !any ) return out;
+    psx_match_opts po;
+    po.ratio = opts.ratio;
+    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
+    // the positions of set k at [k], this object's at [K]
+    std::vector<void*> bufs( (size_t)K + 1, nullptr );
+    std::vector<const float*> ptrs( K, nullptr ), xys( K, nullptr );
+    int rc = psx_dev_alloc( _device, (size_t)l_len * 2 * sizeof(float), &bufs[K] );
+    if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)_ext, _rev, l_len, (float*)bufs[K] );
+    for( int k = 0; k < K && rc == PSX_OK; k++ ) {
+        const int r_len = lens[k];
+        if( r_len <= 0 ) continue;
+        rc = psx_dev_alloc( _device, (size_t)r_len * 2 * sizeof(float), &bufs[k] );
+        if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)others[k]->_ext, others[k]->_rev, r_len, (float*)bufs[k] );
+        ptrs[k] = (const float*)others[k]->_ori;
+        xys[k] = (const float*)bufs[k];
+    }
+    // at most l_len pairs per set exist (a product above INT_MAX is the call's to refuse)
+    const long long room = (long long)K * l_len;
+    std::vector<psx_match_pair> pf( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
+    int count = 0;
+    if( rc == PSX_OK )
+        rc = psx_match_pairs_guided_many( _device, (const float*)_ori, (const float*)bufs[K], l_len, ptrs.data(), xys.data(), lens.data(), K,
+                                          pg.data(), &po, pf.data(), (int)pf.size(), counts.data(), &count );
+    for( void* b : bufs ) psx_dev_free( _device, b );
+    if( rc != PSX_OK ) {
+        std::ostringstream ss;
+        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    // the star as an edge list over [others..., this]: set k is edge (K, k)
+    std::vector<std::vector<int>> fem( (size_t)K + 1 );
+    std::vector<psx_view_edge> pe( K );
+    bool pairs = false;
+    for( int k = 0; k < K; k++ ) {
+        pe[k].left = K; pe[k].right = k;
+        if( counts[k] <= 0 ) continue;
+        pairs = true;
+        fem[k].resize( lens[k] );
+        if( psx_dev_read( _device, fem[k].data(), others[k]->_rev, (size_t)lens[k] * sizeof(int) ) != PSX_OK )
+            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
+    }
+    if( pairs ) {
+        fem[K].resize( l_len );
+        if( psx_dev_read( _device, fem[K].data(), _rev, (size_t)l_len * sizeof(int) ) != PSX_OK )
+            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
+    }
+    return float_lists( pf, counts, pe, fem );
+}
+
 } // namespace popsift

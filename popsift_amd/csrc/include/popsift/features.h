@@ -219,6 +219,9 @@ class FeaturesDev : public FeaturesBase
     HomographyEstimate estimate( const char* who, RansacModel model, FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts );
     std::vector<HomographyEstimate> estimateMany( const char* who, RansacModel model, const std::vector<FeaturesDev*>& others,
                                                   const std::vector<std::vector<Match>>& matches, const RansacOptions& opts );
+    static std::vector<std::vector<Match>> matchGraphFloat( const char* who, const std::vector<FeaturesDev*>& views,
+                                                            const std::vector<std::pair<int,int>>& edges, const std::vector<MatchGuide>* guides,
+                                                            const MatchOptions& opts );
     static std::vector<HomographyEstimate> estimateGraph( const char* who, RansacModel model, const std::vector<FeaturesDev*>& views,
                                                           const std::vector<std::pair<int,int>>& edges,
                                                           const std::vector<std::vector<Match>>& matches, const RansacOptions& opts );
@@ -327,6 +330,24 @@ public:
     /// guides.size() != edges.size(), and for a guide that is neither valid nor of kind None.
     static std::vector<std::vector<Match>> matchPairsGuidedGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
                                                                   const std::vector<MatchGuide>& guides, const MatchOptions& opts );
+    /// matchPairsGraph on the views' FLOAT descriptors (psx_match_pairs_graph): no quantisation, no copies; element e equals
+    /// views[left]->matchPairs( views[right], opts ) field by field, and estimate*Graph, matchPairsGuidedGraphFloat and
+    /// tracks accept the lists unchanged.  Throws as matchPairsGraph for a null referenced entry, views on different devices
+    /// and an edge index outside `views`, and for opts.bytes == true (use matchPairsGraph).
+    static std::vector<std::vector<Match>> matchPairsGraphFloat( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                 const MatchOptions& opts = MatchOptions() );
+    /// matchPairsGuidedMany on the objects' FLOAT descriptors (psx_match_pairs_guided_many): element k equals
+    /// matchPairsGuided( others[k], guides[k], opts ) field by field; a guide of kind MatchGuide::None skips its set.
+    /// Throws as matchPairsGuidedMany (a null entry, another device, one guide per object, an invalid guide), and for
+    /// opts.bytes == true.
+    std::vector<std::vector<Match>> matchPairsGuidedManyFloat( const std::vector<FeaturesDev*>& others, const std::vector<MatchGuide>& guides,
+                                                               const MatchOptions& opts = MatchOptions() );
+    /// matchPairsGuidedGraph on the views' FLOAT descriptors (psx_match_pairs_guided_graph): element e equals
+    /// views[left]->matchPairsGuided( views[right], guides[e], opts ) field by field; a guide of kind MatchGuide::None skips
+    /// its edge.  Throws as matchPairsGuidedGraph, and for opts.bytes == true.
+    static std::vector<std::vector<Match>> matchPairsGuidedGraphFloat( const std::vector<FeaturesDev*>& views,
+                                                                       const std::vector<std::pair<int,int>>& edges,
+                                                                       const std::vector<MatchGuide>& guides, const MatchOptions& opts = MatchOptions() );
 
     /// The TRACKS of a list of view pairs in ONE device call (psx_tracks_graph: one synchronisation, a number of launches
     /// that grows neither with edges.size() nor with views.size()): the sets of descriptor rows in different views that
