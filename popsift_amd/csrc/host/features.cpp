@@ -432,6 +432,386 @@ void FeaturesDev::reset( int num_ext, int num_ori )
     setDescriptorCount( num_ori );
 }
 
+// ---- the matching, RANSAC and track wrappers: their host steps, each stated once --------------------------------------------
+// Every form is VIEWS + EDGE LIST.  An edge-list call brings both; a star (this object against `others`) is
+// views = [others..., this] with edges[k] = (K, k); one pair is the star of one.  One path serves them all: check (the
+// number of guides or match lists, then edges and views, then the options, then the guides), find the views that live
+// edges name, prepare those views' inputs in owned device buffers, make the ONE call of the form -- single, _many or
+// _graph --, cut the records that come back at the per-edge counts.
+namespace {
+
+typedef std::vector<FeaturesDev*>       Views;
+typedef std::vector<std::pair<int,int>> Edges;
+typedef std::vector<std::vector<Match>> Lists;
+enum Form { OnePair, Star, EdgeList };      // which entry point makes the final call: the single one, _many or _graph
+
+Views star_views( FeaturesDev* centre, const Views& others ) { Views v( others ); v.push_back( centre ); return v; }
+Edges star_edges( size_t K ) { Edges e( K ); for( size_t k = 0; k < K; k++ ) e[k] = std::make_pair( (int)K, (int)k ); return e; }
+std::vector<const std::vector<Match>*> pointers( const Lists& lists )
+{
+    std::vector<const std::vector<Match>*> p;
+    for( const std::vector<Match>& l : lists ) p.push_back( &l );
+    return p;
+}
+
+[[noreturn]] void failed( const char* who, int rc, const char* invalid_means )
+{
+    std::ostringstream ss;
+    ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? invalid_means : "" ) << ")";
+    fatal( __FILE__, __LINE__, ss.str() );
+}
+
+// ---- options as the library takes them; what the calls would refuse is refused here, before any device is touched
+psx_match_opts to_psx( const MatchOptions& o )
+{
+    psx_match_opts po;
+    po.ratio = o.ratio;
+    po.flags = o.mutual ? PSX_PAIRS_MUTUAL : 0;
+    return po;
+}
+psx_ransac_opts to_psx( const char* who, const RansacOptions& o )
+{
+    if( !( std::isfinite( o.tol ) && o.tol >= 0.0f ) || o.hypotheses < 1 || o.hypotheses > 65536 )
+        fatal( __FILE__, __LINE__, std::string( who ) + ": invalid options (finite tolerance >= 0, 1 to 65536 hypotheses)" );
+    psx_ransac_opts po;
+    po.tol = o.tol; po.hypotheses = o.hypotheses; po.seed = o.seed; po.flags = o.refit ? PSX_RANSAC_REFIT : 0;
+    return po;
+}
+// batched: kind None is a set / an edge to skip, and is not looked at further
+psx_guide to_psx( const char* who, const MatchGuide& g, bool batched )
+{
+    psx_guide pg;
+    pg.kind = (int)g.kind;
+    for( int k = 0; k < 9; k++ ) pg.m[k] = g.m[k];
+    pg.tol = g.tol;
+    if( batched && pg.kind == PSX_GUIDE_NONE ) return pg;
+    bool ok = ( pg.kind == PSX_GUIDE_HOMOGRAPHY || pg.kind == PSX_GUIDE_EPIPOLAR ) && std::isfinite( pg.tol ) && pg.tol >= 0.0f;
+    for( int k = 0; k < 9; k++ ) ok = ok && std::isfinite( pg.m[k] );
+    if( !ok ) fatal( __FILE__, __LINE__, std::string( who ) + ": invalid guide (kind " + ( batched ? "0, 1 or 2" : "1 or 2" )
+                                         + ", finite entries, finite tolerance >= 0)" );
+    return pg;
+}
+std::vector<psx_view_edge> to_psx( const Edges& edges )
+{
+    std::vector<psx_view_edge> pe( edges.size() );
+    for( size_t e = 0; e < edges.size(); e++ ) { pe[e].left = edges[e].first; pe[e].right = edges[e].second; }
+    return pe;
+}
+
+// ---- the temporary device buffers of one wrapper call: freed when the call leaves, by return or by throw
+class DevBufs
+{
+    const int          _device;
+    std::vector<void*> _bufs;
+public:
+    explicit DevBufs( int device ) : _device( device ) { }
+    DevBufs( const DevBufs& ) = delete;
+    DevBufs& operator=( const DevBufs& ) = delete;
+    ~DevBufs( ) { for( void* b : _bufs ) psx_dev_free( _device, b ); }
+    int device( ) const { return _device; }
+    int alloc( size_t bytes, void** out )
+    {
+        _bufs.reserve( _bufs.size() + 1 );       // before the allocation: nothing can throw between it and its registration
+        const int rc = psx_dev_alloc( _device, bytes, out );
+        if( rc == PSX_OK ) _bufs.push_back( *out );
+        return rc;
+    }
+};
+
+// ---- per-view inputs: a view's descriptors as the matcher of D reads them -- quantised into an owned buffer, or its own floats
+int descriptors_of( DevBufs& bufs, FeaturesDev* f, int len, const unsigned char** out )
+{
+    void* b = nullptr;
+    int rc = bufs.alloc( (size_t)len * 128, &b );
+    if( rc == PSX_OK ) rc = psx_quantize_desc( bufs.device(), (const float*)f->getDescriptors(), len, (unsigned char*)b );
+    *out = (const unsigned char*)b;
+    return rc;
+}
+int descriptors_of( DevBufs&, FeaturesDev* f, int, const float** out ) { *out = (const float*)f->getDescriptors(); return PSX_OK; }
+
+// what the call needs of every used view, at the view's index: its length, its descriptors (ptrs == nullptr: none) and, where
+// asked for, the positions of its descriptors.  A view that is not used stays an empty set to the call and costs nothing.
+template<class D>
+int prepare( const Views& views, const std::vector<char>& used, bool positions, DevBufs& bufs, std::vector<const D*>* ptrs,
+             std::vector<const float*>& xys, std::vector<int>& lens )
+{
+    int rc = PSX_OK;
+    for( size_t v = 0; v < views.size() && rc == PSX_OK; v++ ) {
+        if( !used[v] ) continue;
+        const int len = views[v]->getDescriptorCount();
+        if( len <= 0 ) return PSX_ERR_INVALID;       // a match list on an empty object (no live edge of a matching call names one)
+        lens[v] = len;
+        if( ptrs ) rc = descriptors_of( bufs, views[v], len, &(*ptrs)[v] );
+        if( !positions ) continue;
+        void* xy = nullptr;
+        if( rc == PSX_OK ) rc = bufs.alloc( (size_t)len * 2 * sizeof(float), &xy );
+        if( rc == PSX_OK ) rc = psx_desc_positions( bufs.device(), (const psx_feature_dev*)views[v]->getFeatures(), views[v]->getReverseMap(), len, (float*)xy );
+        xys[v] = (const float*)xy;
+    }
+    return rc;
+}
+
+// a view's reverse map (descriptor -> feature) on the host
+bool read_reverse_map( int device, FeaturesDev* f, std::vector<int>& fem )
+{
+    fem.resize( f->getDescriptorCount() > 0 ? f->getDescriptorCount() : 0 );
+    return fem.empty() || psx_dev_read( device, fem.data(), f->getReverseMap(), fem.size() * sizeof(int) ) == PSX_OK;
+}
+
+// ---- lists out: a record as a Match (the feature indices follow from the reverse maps); byte distances convert exactly
+float byte_distance( int d ) { return d == INT32_MAX ? INFINITY : (float)d; }
+void to_match( const psx_match_pair& p, Match& m )    { m.left_descriptor = p.left; m.right_descriptor = p.right; m.distance = p.d1; m.second_distance = p.d2; }
+void to_match( const psx_match_pair_u8& p, Match& m ) { m.left_descriptor = p.left; m.right_descriptor = p.right;
+                                                        m.distance = byte_distance( p.d1 ); m.second_distance = byte_distance( p.d2 ); }
+
+// the concatenated records of a call, cut at the per-edge counts and mapped through the two views' reverse maps; the map
+// of every view that an edge with pairs names is read once
+template<class P>
+Lists lists_out( const char* who, int device, const Views& views, const Edges& edges, const std::vector<int>& counts, const std::vector<P>& pairs )
+{
+    Lists out( edges.size() );
+    std::vector<std::vector<int>> fem( views.size() );
+    size_t at = 0;
+    for( size_t e = 0; e < edges.size(); e++ ) {
+        if( counts[e] <= 0 ) continue;
+        const int side[2] = { edges[e].first, edges[e].second };
+        for( int v : side )
+            if( fem[v].empty() && !read_reverse_map( device, views[v], fem[v] ) )
+                fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
+        out[e].resize( counts[e] );
+        for( int q = 0; q < counts[e]; q++, at++ ) {
+            Match& m = out[e][q];
+            to_match( pairs[at], m );
+            m.left_feature  = fem[side[0]][m.left_descriptor];
+            m.right_feature = fem[side[1]][m.right_descriptor];
+        }
+    }
+    return out;
+}
+
+// ---- the entry points of the two descriptor formats, by form
+template<class D, class P> struct MatchFns
+{
+    int (*one)( int, const D*, int, const D*, int, const psx_match_opts*, P*, int, int* );
+    int (*one_guided)( int, const D*, const float*, int, const D*, const float*, int, const psx_guide*, const psx_match_opts*, P*, int, int* );
+    int (*many)( int, const D*, int, const D* const*, const int*, int, const psx_match_opts*, P*, int, int*, int* );
+    int (*many_guided)( int, const D*, const float*, int, const D* const*, const float* const*, const int*, int, const psx_guide*,
+                        const psx_match_opts*, P*, int, int*, int* );
+    int (*graph)( int, const D* const*, const int*, int, const psx_view_edge*, int, const psx_match_opts*, P*, int, int*, int* );
+    int (*graph_guided)( int, const D* const*, const float* const*, const int*, int, const psx_view_edge*, int, const psx_guide*,
+                         const psx_match_opts*, P*, int, int*, int* );
+};
+const MatchFns<unsigned char, psx_match_pair_u8> byte_fns = { psx_match_pairs_u8, psx_match_pairs_guided_u8, psx_match_pairs_many_u8,
+    psx_match_pairs_guided_many_u8, psx_match_pairs_graph_u8, psx_match_pairs_guided_graph_u8 };
+const MatchFns<float, psx_match_pair> float_fns = { psx_match_pairs, psx_match_pairs_guided, psx_match_pairs_many,
+    psx_match_pairs_guided_many, psx_match_pairs_graph, psx_match_pairs_guided_graph };
+
+// Every matching wrapper, after the views are checked: the guides, the live edges (not skipped by a guide of kind None, two
+// non-empty sides) and the views they name -- only these are quantised or gathered --, then ONE call.  A star and one pair
+// pass their centre (the last view) as the left side and the views before it as the right sets.
+template<class D, class P>
+Lists match_lists( const MatchFns<D, P>& fn, const char* who, Form form, int device, const Views& views, const Edges& edges,
+                   const std::vector<MatchGuide>* guides, const MatchOptions& opts )
+{
+    const int N = (int)views.size(), E = (int)edges.size(), C = N - 1;
+    std::vector<psx_guide> pg;
+    if( guides ) for( const MatchGuide& g : *guides ) pg.push_back( to_psx( who, g, form != OnePair ) );
+    std::vector<char> used( views.size(), 0 );
+    long long room = 0;                                      // at most lens[left] pairs per edge exist
+    for( int e = 0; e < E; e++ ) {
+        const int l = edges[e].first, r = edges[e].second;
+        if( ( guides && pg[e].kind == PSX_GUIDE_NONE ) || views[l]->getDescriptorCount() <= 0 || views[r]->getDescriptorCount() <= 0 ) continue;
+        room += views[l]->getDescriptorCount();
+        used[l] = used[r] = 1;
+    }
+    if( room == 0 ) return Lists( edges.size() );
+    // a star leaves room for every set (a product above INT_MAX is the call's to refuse)
+    if( form != EdgeList ) room = (long long)E * views[C]->getDescriptorCount();
+    const psx_match_opts po = to_psx( opts );
+    const std::vector<psx_view_edge> pe = to_psx( edges );
+    std::vector<const D*> ptrs( views.size(), nullptr );
+    std::vector<const float*> xys( views.size(), nullptr );
+    std::vector<int> lens( views.size(), 0 ), counts( edges.size(), 0 );
+    std::vector<P> pairs( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
+    const int capacity = (int)pairs.size();
+    int count = 0;
+    int rc;
+    {
+        DevBufs bufs( device );
+        rc = prepare( views, used, guides != nullptr, bufs, &ptrs, xys, lens );
+        if( rc != PSX_OK ) { }                               // a view could not be prepared: the call is not made
+        else if( form == OnePair ) {
+            rc = guides ? fn.one_guided( device, ptrs[C], xys[C], lens[C], ptrs[0], xys[0], lens[0], pg.data(), &po, pairs.data(), capacity, &count )
+                        : fn.one( device, ptrs[C], lens[C], ptrs[0], lens[0], &po, pairs.data(), capacity, &count );
+            counts[0] = count;
+        }
+        else if( form == Star )
+            rc = guides ? fn.many_guided( device, ptrs[C], xys[C], lens[C], ptrs.data(), xys.data(), lens.data(), E, pg.data(), &po, pairs.data(),
+                                          capacity, counts.data(), &count )
+                        : fn.many( device, ptrs[C], lens[C], ptrs.data(), lens.data(), E, &po, pairs.data(), capacity, counts.data(), &count );
+        else
+            rc = guides ? fn.graph_guided( device, ptrs.data(), xys.data(), lens.data(), N, pe.data(), E, pg.data(), &po, pairs.data(), capacity,
+                                           counts.data(), &count )
+                        : fn.graph( device, ptrs.data(), lens.data(), N, pe.data(), E, &po, pairs.data(), capacity, counts.data(), &count );
+    }
+    if( rc != PSX_OK ) failed( who, rc, ": invalid options" );
+    return lists_out( who, device, views, edges, counts, pairs );
+}
+
+// ---- RANSAC: what differs between the models, in the order of FeaturesDev::RansacModel
+typedef int (*RansacOneFn)( int, const void*, int, const float*, int, const float*, int, const psx_ransac_opts*, psx_ransac_result*, void*, int, int*,
+                            float*, int* );
+typedef int (*RansacManyFn)( int, const void*, const int*, int, const float*, int, const float* const*, const int*, const psx_ransac_opts*,
+                             psx_ransac_result*, void*, int, int*, float*, int* );
+typedef int (*RansacGraphFn)( int, const void*, const int*, const psx_view_edge*, int, const float* const*, const int*, int, const psx_ransac_opts*,
+                              psx_ransac_result*, void*, int, int*, float*, int* );
+const struct { int min_pairs; MatchGuide::Kind guide; RansacOneFn one; RansacManyFn many; RansacGraphFn graph; } ransac_models[4] = {
+    { 4, MatchGuide::Homography, psx_ransac_homography,  psx_ransac_homography_many,  psx_ransac_homography_graph },
+    { 8, MatchGuide::Epipolar,   psx_ransac_fundamental, psx_ransac_fundamental_many, psx_ransac_fundamental_graph },
+    { 3, MatchGuide::Homography, psx_ransac_affine,      psx_ransac_affine_many,      psx_ransac_affine_graph },
+    { 2, MatchGuide::Homography, psx_ransac_similarity,  psx_ransac_similarity_many,  psx_ransac_similarity_graph },
+};
+
+// the lists with a count behind one another as the library's records; the record is copied whole, so with `index` its
+// distance slots carry the index of the match within its list
+std::vector<psx_match_pair_u8> pack_records( const std::vector<const std::vector<Match>*>& lists, const std::vector<int>& counts, bool index )
+{
+    size_t total = 0;
+    for( int c : counts ) total += c;
+    std::vector<psx_match_pair_u8> rec( total );
+    size_t at = 0;
+    for( size_t e = 0; e < lists.size(); e++ )
+        for( int q = 0; q < counts[e]; q++, at++ ) {
+            const Match& m = (*lists[e])[q];
+            rec[at].left = m.left_descriptor; rec[at].right = m.right_descriptor; rec[at].d1 = index ? q : 0; rec[at].d2 = 0;
+        }
+    return rec;
+}
+
+// Every estimate*, after the views are checked: the lists that can have a model go behind one another into ONE call (a
+// shorter list is "no model" without a device), the positions of every view such an edge names are gathered once
+std::vector<HomographyEstimate> estimate_lists( const char* who, int model, Form form, int device, const Views& views, const Edges& edges,
+                                                const std::vector<const std::vector<Match>*>& lists, const RansacOptions& opts )
+{
+    const psx_ransac_opts po = to_psx( who, opts );
+    const int N = (int)views.size(), E = (int)edges.size(), C = N - 1;
+    HomographyEstimate none;
+    none.guide.kind = ransac_models[model].guide;
+    for( int k = 0; k < 9; k++ ) none.guide.m[k] = 0.0f;
+    none.guide.tol = opts.tol;
+    none.best = -1; none.sample_inliers = 0; none.refit_kept = false;
+    std::vector<HomographyEstimate> out( edges.size(), none );
+    std::vector<int> counts( edges.size(), 0 );
+    std::vector<char> used( views.size(), 0 );               // named by an edge that has a model to estimate
+    for( int e = 0; e < E; e++ )
+        if( (int)lists[e]->size() >= ransac_models[model].min_pairs ) {
+            counts[e] = (int)lists[e]->size();
+            used[edges[e].first] = used[edges[e].second] = 1;
+        }
+    const std::vector<psx_match_pair_u8> rec = pack_records( lists, counts, true );
+    if( rec.empty() ) return out;
+    std::vector<psx_match_pair_u8> inl( rec.size() );
+    const std::vector<psx_view_edge> pe = to_psx( edges );
+    std::vector<psx_ransac_result> res( edges.size() );
+    std::vector<const float*> xys( views.size(), nullptr );
+    std::vector<int> lens( views.size(), 0 );
+    const int capacity = (int)inl.size();
+    int count = 0;
+    int rc;
+    {
+        DevBufs bufs( device );
+        rc = prepare<float>( views, used, true, bufs, nullptr, xys, lens );
+        if( rc != PSX_OK ) { }                               // a view could not be prepared: the call is not made
+        else if( form == OnePair )
+            rc = ransac_models[model].one( device, rec.data(), counts[0], xys[C], lens[C], xys[0], lens[0], &po, res.data(), inl.data(), capacity, &count,
+                                           nullptr, nullptr );
+        else if( form == Star )
+            rc = ransac_models[model].many( device, rec.data(), counts.data(), E, xys[C], lens[C], xys.data(), lens.data(), &po, res.data(), inl.data(),
+                                            capacity, &count, nullptr, nullptr );
+        else
+            rc = ransac_models[model].graph( device, rec.data(), counts.data(), pe.data(), E, xys.data(), lens.data(), N, &po, res.data(), inl.data(),
+                                             capacity, &count, nullptr, nullptr );
+    }
+    if( rc != PSX_OK ) failed( who, rc, ": invalid options or a descriptor index outside its object" );
+    size_t at = 0;
+    for( int e = 0; e < E; e++ ) {
+        if( counts[e] == 0 ) continue;
+        HomographyEstimate& est = out[e];
+        for( int j = 0; j < 9; j++ ) est.guide.m[j] = res[e].m[j];
+        est.best = res[e].best; est.sample_inliers = res[e].sample_inliers; est.refit_kept = res[e].refit_kept != 0;
+        est.inliers.reserve( res[e].inliers );
+        for( int q = 0; q < res[e].inliers; q++, at++ ) est.inliers.push_back( (*lists[e])[inl[at].d1] );
+    }
+    return out;
+}
+
+// ---- match() and matchBytes(): one line per left descriptor, as the reference's show_distance prints them (features.cu:227-268)
+bool print_matches( int l_device, FeaturesDev* l, int r_device, FeaturesDev* r, const std::vector<int>& mm, const std::vector<float>& dd )
+{
+    std::vector<int> l_fem, r_fem;
+    if( !read_reverse_map( l_device, l, l_fem ) || !read_reverse_map( r_device, r, r_fem ) ) return false;
+    for( int i = 0; i < (int)l_fem.size(); i++ )
+    {
+        const int m1 = mm[3*i], m2 = mm[3*i+1];
+        printf( "%s feat %4d [%4d] matches feat %4d [%4d] ( 2nd feat %4d [%4d] ) dist %.3f vs %.3f\n",
+                mm[3*i+2] ? "accept" : "reject",
+                l_fem[i], i,
+                r_fem.empty() ? 0 : r_fem[m1], m1,
+                r_fem.empty() ? 0 : r_fem[m2], m2,
+                dd[2*i], dd[2*i+1] );
+    }
+    return true;
+}
+
+} // namespace
+
+// What every form refuses about its views and edges, in this order: a number of guides / match lists (`given`) other than
+// one per edge, an edge index outside `views`, a null view that an edge names, named views on different devices.  Returns
+// the device of the named views: a star's or a pair's is its centre's, an edge list without edges has none (-1).
+int FeaturesDev::checkViews( const char* who, int form, const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                             size_t given, const char* what )
+{
+    if( given != edges.size() ) {
+        std::ostringstream ss;
+        ss << who << ": " << edges.size() << ( form == EdgeList ? " edges but " : " objects but " ) << given << " " << what;
+        fatal( __FILE__, __LINE__, ss.str() );
+    }
+    const int N = (int)views.size();
+    std::vector<char> named( views.size(), 0 );
+    for( const std::pair<int,int>& e : edges ) {
+        if( e.first < 0 || e.first >= N || e.second < 0 || e.second >= N ) {
+            std::ostringstream ss;
+            ss << who << ": edge (" << e.first << ", " << e.second << ") out of range (" << N << " views)";
+            fatal( __FILE__, __LINE__, ss.str() );
+        }
+        named[e.first] = named[e.second] = 1;
+    }
+    int device = form == EdgeList ? -1 : views.back()->_device;
+    for( int v = 0; v < N; v++ ) {
+        if( !named[v] ) continue;
+        if( views[v] == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
+        if( device < 0 ) device = views[v]->_device;
+        if( views[v]->_device != device ) {
+            std::ostringstream ss;
+            ss << who << ": the " << ( form == OnePair ? "two " : "" ) << "objects live on different devices (" << device << " and " << views[v]->_device << ")";
+            fatal( __FILE__, __LINE__, ss.str() );
+        }
+    }
+    return device;
+}
+
+// Every matching wrapper: the checks in their one order, then the path of the descriptor format.  wrong_format: what to
+// say when the form does not take opts.bytes as it is (nullptr: it does).
+std::vector<std::vector<Match>> FeaturesDev::matchLists( const char* who, int form, const std::vector<FeaturesDev*>& views,
+                                                         const std::vector<std::pair<int,int>>& edges, const std::vector<MatchGuide>* guides,
+                                                         const MatchOptions& opts, const char* wrong_format )
+{
+    const int device = checkViews( who, form, views, edges, guides ? guides->size() : edges.size(), "guides" );
+    if( wrong_format ) fatal( __FILE__, __LINE__, std::string( who ) + wrong_format );
+    return opts.bytes ? match_lists( byte_fns, who, (Form)form, device, views, edges, guides, opts )
+                      : match_lists( float_fns, who, (Form)form, device, views, edges, guides, opts );
+}
+
 // FeaturesDev::match (features.cu:270-304): the reference computes the match matrix on the device and
 // prints one line per left descriptor from a device printf (show_distance, features.cu:227-268); same
 // lines here, printed by the host from the arrays psx_match returns.
@@ -443,21 +823,9 @@ void FeaturesDev::match( FeaturesDev* other )
     if( l_len <= 0 ) return;
     std::vector<int>   mm( 3 * (size_t)l_len );
     std::vector<float> dd( 2 * (size_t)l_len );
-    std::vector<int>   l_fem( l_len ), r_fem( r_len > 0 ? r_len : 1 );
     if( psx_match( _device, (const float*)_ori, l_len, (const float*)other->_ori, r_len, mm.data(), dd.data() ) != PSX_OK ||
-        psx_dev_read( _device, l_fem.data(), _rev, (size_t)l_len * sizeof(int) ) != PSX_OK ||
-        ( r_len > 0 && psx_dev_read( other->_device, r_fem.data(), other->_rev, (size_t)r_len * sizeof(int) ) != PSX_OK ) )
+        !print_matches( _device, this, other->_device, other, mm, dd ) )
         fatal( __FILE__, __LINE__, "FeaturesDev::match failed" );
-    for( int i = 0; i < l_len; i++ )
-    {
-        const int m1 = mm[3*i], m2 = mm[3*i+1];
-        printf( "%s feat %4d [%4d] matches feat %4d [%4d] ( 2nd feat %4d [%4d] ) dist %.3f vs %.3f\n",
-                mm[3*i+2] ? "accept" : "reject",
-                l_fem[i], i,
-                r_len > 0 ? r_fem[m1] : 0, m1,
-                r_len > 0 ? r_fem[m2] : 0, m2,
-                dd[2*i], dd[2*i+1] );
-    }
 }
 
 // FeaturesDev::matchBytes: both descriptor sets quantised on the device with the byte rule, then psx_match_u8 (exact:
@@ -468,458 +836,111 @@ void FeaturesDev::matchBytes( FeaturesDev* other )
     const int l_len = getDescriptorCount();
     const int r_len = other->getDescriptorCount();
     if( l_len <= 0 ) return;
-    std::vector<int> mm( 3 * (size_t)l_len ), dd( 2 * (size_t)l_len );
-    std::vector<int> l_fem( l_len ), r_fem( r_len > 0 ? r_len : 1 );
+    std::vector<int> mm( 3 * (size_t)l_len ), di( 2 * (size_t)l_len );
+    std::vector<float> dd( 2 * (size_t)l_len );
+    DevBufs bufs( _device );
     void *lb = nullptr, *rb = nullptr;
-    bool ok = psx_dev_alloc( _device, (size_t)l_len * 128, &lb ) == PSX_OK &&
-              psx_dev_alloc( _device, (size_t)( r_len > 0 ? r_len : 1 ) * 128, &rb ) == PSX_OK &&
-              psx_quantize_desc( _device, (const float*)_ori, l_len, (unsigned char*)lb ) == PSX_OK &&
-              psx_quantize_desc( _device, (const float*)other->_ori, r_len, (unsigned char*)rb ) == PSX_OK &&
-              psx_match_u8( _device, (const unsigned char*)lb, l_len, (const unsigned char*)rb, r_len, mm.data(), dd.data() ) == PSX_OK &&
-              psx_dev_read( _device, l_fem.data(), _rev, (size_t)l_len * sizeof(int) ) == PSX_OK &&
-              ( r_len <= 0 || psx_dev_read( other->_device, r_fem.data(), other->_rev, (size_t)r_len * sizeof(int) ) == PSX_OK );
-    psx_dev_free( _device, lb );
-    psx_dev_free( _device, rb );
-    if( !ok ) fatal( __FILE__, __LINE__, "FeaturesDev::matchBytes failed" );
-    for( int i = 0; i < l_len; i++ )
-    {
-        const int m1 = mm[3*i], m2 = mm[3*i+1];
-        const float d1 = dd[2*i] == INT32_MAX ? INFINITY : (float)dd[2*i];
-        const float d2 = dd[2*i+1] == INT32_MAX ? INFINITY : (float)dd[2*i+1];
-        printf( "%s feat %4d [%4d] matches feat %4d [%4d] ( 2nd feat %4d [%4d] ) dist %.3f vs %.3f\n",
-                mm[3*i+2] ? "accept" : "reject",
-                l_fem[i], i,
-                r_len > 0 ? r_fem[m1] : 0, m1,
-                r_len > 0 ? r_fem[m2] : 0, m2,
-                d1, d2 );
-    }
+    const bool ok = bufs.alloc( (size_t)l_len * 128, &lb ) == PSX_OK &&
+                    bufs.alloc( (size_t)( r_len > 0 ? r_len : 1 ) * 128, &rb ) == PSX_OK &&
+                    psx_quantize_desc( _device, (const float*)_ori, l_len, (unsigned char*)lb ) == PSX_OK &&
+                    psx_quantize_desc( _device, (const float*)other->_ori, r_len, (unsigned char*)rb ) == PSX_OK &&
+                    psx_match_u8( _device, (const unsigned char*)lb, l_len, (const unsigned char*)rb, r_len, mm.data(), di.data() ) == PSX_OK;
+    for( size_t i = 0; i < di.size(); i++ ) dd[i] = byte_distance( di[i] );
+    if( !ok || !print_matches( _device, this, other->_device, other, mm, dd ) ) fatal( __FILE__, __LINE__, "FeaturesDev::matchBytes failed" );
 }
 
-// FeaturesDev::matchPairs / matchPairsGuided: psx_match_pairs* / psx_match_pairs_guided* on the two descriptor arrays; the
-// pair list (16 bytes per pair) and the two reverse maps come back, nothing per descriptor.  guide == nullptr: unguided.
-static std::vector<Match> match_pairs_impl( const char* who, int device, int other_device,
-                                            Feature* l_ext, Descriptor* l_ori, int* l_rev, int l_len,
-                                            Feature* r_ext, Descriptor* r_ori, int* r_rev, int r_len,
-                                            const MatchGuide* guide, const MatchOptions& opts )
-{
-    std::vector<Match> out;
-    psx_guide pg;
-    if( guide != nullptr ) {
-        pg.kind = (int)guide->kind;
-        for( int k = 0; k < 9; k++ ) pg.m[k] = guide->m[k];
-        pg.tol = guide->tol;
-        // refused here, before any device is touched (and for empty sides too): what psx_match_pairs_guided refuses
-        bool ok = ( pg.kind == PSX_GUIDE_HOMOGRAPHY || pg.kind == PSX_GUIDE_EPIPOLAR ) && std::isfinite( pg.tol ) && pg.tol >= 0.0f;
-        for( int k = 0; k < 9; k++ ) ok = ok && std::isfinite( pg.m[k] );
-        if( !ok ) fatal( __FILE__, __LINE__, std::string( who ) + ": invalid guide (kind 1 or 2, finite entries, finite tolerance >= 0)" );
-    }
-    if( l_len <= 0 || r_len <= 0 ) return out;
-    psx_match_opts po;
-    po.ratio = opts.ratio;
-    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
-    int count = 0;
-    std::vector<psx_match_pair>    pf;
-    std::vector<psx_match_pair_u8> pb;
-    int rc = PSX_OK;
-    void *lb = nullptr, *rb = nullptr, *lxy = nullptr, *rxy = nullptr;
-    if( guide != nullptr ) {
-        rc = psx_dev_alloc( device, (size_t)l_len * 2 * sizeof(float), &lxy );
-        if( rc == PSX_OK ) rc = psx_dev_alloc( device, (size_t)r_len * 2 * sizeof(float), &rxy );
-        if( rc == PSX_OK ) rc = psx_desc_positions( device, (const psx_feature_dev*)l_ext, l_rev, l_len, (float*)lxy );
-        if( rc == PSX_OK ) rc = psx_desc_positions( device, (const psx_feature_dev*)r_ext, r_rev, r_len, (float*)rxy );
-    }
-    if( opts.bytes ) {
-        pb.resize( l_len );
-        if( rc == PSX_OK ) rc = psx_dev_alloc( device, (size_t)l_len * 128, &lb );
-        if( rc == PSX_OK ) rc = psx_dev_alloc( device, (size_t)r_len * 128, &rb );
-        if( rc == PSX_OK ) rc = psx_quantize_desc( device, (const float*)l_ori, l_len, (unsigned char*)lb );
-        if( rc == PSX_OK ) rc = psx_quantize_desc( device, (const float*)r_ori, r_len, (unsigned char*)rb );
-        if( rc == PSX_OK && guide == nullptr )
-            rc = psx_match_pairs_u8( device, (const unsigned char*)lb, l_len, (const unsigned char*)rb, r_len, &po, pb.data(), l_len, &count );
-        else if( rc == PSX_OK )
-            rc = psx_match_pairs_guided_u8( device, (const unsigned char*)lb, (const float*)lxy, l_len, (const unsigned char*)rb, (const float*)rxy, r_len,
-                                            &pg, &po, pb.data(), l_len, &count );
-    } else {
-        pf.resize( l_len );
-        if( rc == PSX_OK && guide == nullptr )
-            rc = psx_match_pairs( device, (const float*)l_ori, l_len, (const float*)r_ori, r_len, &po, pf.data(), l_len, &count );
-        else if( rc == PSX_OK )
-            rc = psx_match_pairs_guided( device, (const float*)l_ori, (const float*)lxy, l_len, (const float*)r_ori, (const float*)rxy, r_len,
-                                         &pg, &po, pf.data(), l_len, &count );
-    }
-    psx_dev_free( device, lb );
-    psx_dev_free( device, rb );
-    psx_dev_free( device, lxy );
-    psx_dev_free( device, rxy );
-    if( rc != PSX_OK ) {
-        std::ostringstream ss;
-        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    std::vector<int> l_fem( l_len ), r_fem( r_len );
-    if( psx_dev_read( device, l_fem.data(), l_rev, (size_t)l_len * sizeof(int) ) != PSX_OK ||
-        psx_dev_read( other_device, r_fem.data(), r_rev, (size_t)r_len * sizeof(int) ) != PSX_OK )
-        fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
-    out.resize( count );
-    for( int k = 0; k < count; k++ ) {
-        Match& m = out[k];
-        if( opts.bytes ) {
-            m.left_descriptor = pb[k].left; m.right_descriptor = pb[k].right;
-            m.distance        = pb[k].d1 == INT32_MAX ? INFINITY : (float)pb[k].d1;
-            m.second_distance = pb[k].d2 == INT32_MAX ? INFINITY : (float)pb[k].d2;
-        } else {
-            m.left_descriptor = pf[k].left; m.right_descriptor = pf[k].right;
-            m.distance = pf[k].d1; m.second_distance = pf[k].d2;
-        }
-        m.left_feature  = l_fem[m.left_descriptor];
-        m.right_feature = r_fem[m.right_descriptor];
-    }
-    return out;
-}
-
+// ---- matching: each public form names its views, its edges and what it takes
 std::vector<Match> FeaturesDev::matchPairs( FeaturesDev* other, const MatchOptions& opts )
 {
-    if( other == nullptr ) fatal( __FILE__, __LINE__, "FeaturesDev::matchPairs: null argument" );
-    if( other->_device != _device ) {
-        std::ostringstream ss;
-        ss << "FeaturesDev::matchPairs: the two objects live on different devices (" << _device << " and " << other->_device << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    return match_pairs_impl( "FeaturesDev::matchPairs", _device, other->_device, _ext, _ori, _rev, getDescriptorCount(),
-                             other->_ext, other->_ori, other->_rev, other->getDescriptorCount(), nullptr, opts );
+    return matchLists( "FeaturesDev::matchPairs", OnePair, star_views( this, Views( 1, other ) ), star_edges( 1 ), nullptr, opts, nullptr )[0];
 }
 
 std::vector<Match> FeaturesDev::matchPairsGuided( FeaturesDev* other, const MatchGuide& guide, const MatchOptions& opts )
 {
-    if( other == nullptr ) fatal( __FILE__, __LINE__, "FeaturesDev::matchPairsGuided: null argument" );
-    if( other->_device != _device ) {
-        std::ostringstream ss;
-        ss << "FeaturesDev::matchPairsGuided: the two objects live on different devices (" << _device << " and " << other->_device << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    return match_pairs_impl( "FeaturesDev::matchPairsGuided", _device, other->_device, _ext, _ori, _rev, getDescriptorCount(),
-                             other->_ext, other->_ori, other->_rev, other->getDescriptorCount(), &guide, opts );
+    const std::vector<MatchGuide> guides( 1, guide );
+    return matchLists( "FeaturesDev::matchPairsGuided", OnePair, star_views( this, Views( 1, other ) ), star_edges( 1 ), &guides, opts, nullptr )[0];
 }
 
-// FeaturesDev::matchPairsMany: psx_match_pairs_many_u8 on this object's bytes and every other object's -- each side
-// quantised once, ONE matching call for all of them; the concatenated list is cut at the per-set counts and mapped through
-// the reverse maps as matchPairs does
 std::vector<std::vector<Match>> FeaturesDev::matchPairsMany( const std::vector<FeaturesDev*>& others, const MatchOptions& opts )
 {
-    const char* who = "FeaturesDev::matchPairsMany";
-    for( FeaturesDev* o : others ) {
-        if( o == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
-        if( o->_device != _device ) {
-            std::ostringstream ss;
-            ss << who << ": the objects live on different devices (" << _device << " and " << o->_device << ")";
-            fatal( __FILE__, __LINE__, ss.str() );
-        }
-    }
-    if( !opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": the one-to-many form is byte-only (set MatchOptions::bytes)" );
-    const int K = (int)others.size();
-    const int l_len = getDescriptorCount();
-    std::vector<std::vector<Match>> out( others.size() );
-    bool any = false;
-    for( FeaturesDev* o : others ) any = any || o->getDescriptorCount() > 0;
-    if( l_len <= 0 || !any ) return out;
-    psx_match_opts po;
-    po.ratio = opts.ratio;
-    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
-    std::vector<void*> bufs( (size_t)K + 1, nullptr );
-    std::vector<const unsigned char*> ptrs( K, nullptr );
-    std::vector<int> lens( K, 0 ), counts( K, 0 );
-    int rc = psx_dev_alloc( _device, (size_t)l_len * 128, &bufs[K] );
-    if( rc == PSX_OK ) rc = psx_quantize_desc( _device, (const float*)_ori, l_len, (unsigned char*)bufs[K] );
-    for( int k = 0; k < K && rc == PSX_OK; k++ ) {
-        const int r_len = others[k]->getDescriptorCount();
-        if( r_len <= 0 ) continue;
-        lens[k] = r_len;
-        rc = psx_dev_alloc( _device, (size_t)r_len * 128, &bufs[k] );
-        if( rc == PSX_OK ) rc = psx_quantize_desc( _device, (const float*)others[k]->_ori, r_len, (unsigned char*)bufs[k] );
-        ptrs[k] = (const unsigned char*)bufs[k];
-    }
-    // at most l_len pairs per set exist (a product above INT_MAX is the call's to refuse)
-    const long long room = (long long)K * l_len;
-    std::vector<psx_match_pair_u8> pb( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
-    int count = 0;
-    if( rc == PSX_OK )
-        rc = psx_match_pairs_many_u8( _device, (const unsigned char*)bufs[K], l_len, ptrs.data(), lens.data(), K, &po,
-                                      pb.data(), (int)pb.size(), counts.data(), &count );
-    for( void* b : bufs ) psx_dev_free( _device, b );
-    if( rc != PSX_OK ) {
-        std::ostringstream ss;
-        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    std::vector<int> l_fem( l_len );
-    if( psx_dev_read( _device, l_fem.data(), _rev, (size_t)l_len * sizeof(int) ) != PSX_OK )
-        fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
-    size_t at = 0;
-    for( int k = 0; k < K; k++ ) {
-        if( counts[k] <= 0 ) continue;
-        std::vector<int> r_fem( lens[k] );
-        if( psx_dev_read( _device, r_fem.data(), others[k]->_rev, (size_t)lens[k] * sizeof(int) ) != PSX_OK )
-            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
-        out[k].resize( counts[k] );
-        for( int q = 0; q < counts[k]; q++, at++ ) {
-            Match& m = out[k][q];
-            m.left_descriptor = pb[at].left; m.right_descriptor = pb[at].right;
-            m.distance        = pb[at].d1 == INT32_MAX ? INFINITY : (float)pb[at].d1;
-            m.second_distance = pb[at].d2 == INT32_MAX ? INFINITY : (float)pb[at].d2;
-            m.left_feature  = l_fem[m.left_descriptor];
-            m.right_feature = r_fem[m.right_descriptor];
-        }
-    }
-    return out;
+    return matchLists( "FeaturesDev::matchPairsMany", Star, star_views( this, others ), star_edges( others.size() ), nullptr, opts,
+                       opts.bytes ? nullptr : ": the one-to-many form is byte-only (set MatchOptions::bytes)" );
 }
 
-// FeaturesDev::matchPairsGraph: psx_match_pairs_graph_u8 on the bytes of every view an edge names -- each quantised once
-// for the whole call, ONE matching call for all edges; the concatenated list is cut at the per-edge counts and mapped
-// through the two views' reverse maps as matchPairs does
-std::vector<std::vector<Match>> FeaturesDev::matchPairsGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
-                                                              const MatchOptions& opts )
-{
-    const char* who = "FeaturesDev::matchPairsGraph";
-    const int N = (int)views.size(), E = (int)edges.size();
-    std::vector<char> named( views.size(), 0 );
-    for( const std::pair<int,int>& e : edges ) {
-        if( e.first < 0 || e.first >= N || e.second < 0 || e.second >= N ) {
-            std::ostringstream ss;
-            ss << who << ": edge (" << e.first << ", " << e.second << ") out of range (" << N << " views)";
-            fatal( __FILE__, __LINE__, ss.str() );
-        }
-        named[e.first] = named[e.second] = 1;
-    }
-    int device = -1;
-    for( int v = 0; v < N; v++ ) {
-        if( !named[v] ) continue;
-        if( views[v] == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
-        if( device < 0 ) device = views[v]->_device;
-        if( views[v]->_device != device ) {
-            std::ostringstream ss;
-            ss << who << ": the objects live on different devices (" << device << " and " << views[v]->_device << ")";
-            fatal( __FILE__, __LINE__, ss.str() );
-        }
-    }
-    if( !opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": the edge-list form is byte-only (set MatchOptions::bytes)" );
-    std::vector<std::vector<Match>> out( edges.size() );
-    std::vector<int> lens( views.size(), 0 );
-    for( int v = 0; v < N; v++ ) if( named[v] && views[v]->getDescriptorCount() > 0 ) lens[v] = views[v]->getDescriptorCount();
-    long long room = 0;                                      // at most lens[left] pairs per edge exist
-    std::vector<char> used( views.size(), 0 );               // named by an edge with two non-empty sides: only these are quantised
-    for( const std::pair<int,int>& e : edges )
-        if( lens[e.first] > 0 && lens[e.second] > 0 ) { room += lens[e.first]; used[e.first] = used[e.second] = 1; }
-    if( room == 0 ) return out;
-    psx_match_opts po;
-    po.ratio = opts.ratio;
-    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
-    std::vector<void*> bufs( views.size(), nullptr );
-    std::vector<const unsigned char*> ptrs( views.size(), nullptr );
-    int rc = PSX_OK;
-    for( int v = 0; v < N && rc == PSX_OK; v++ ) {
-        if( !used[v] ) { lens[v] = 0; continue; }            // a view no live edge names is an empty set to the call
-        rc = psx_dev_alloc( device, (size_t)lens[v] * 128, &bufs[v] );
-        if( rc == PSX_OK ) rc = psx_quantize_desc( device, (const float*)views[v]->_ori, lens[v], (unsigned char*)bufs[v] );
-        ptrs[v] = (const unsigned char*)bufs[v];
-    }
-    std::vector<psx_view_edge> pe( edges.size() );
-    for( int e = 0; e < E; e++ ) { pe[e].left = edges[e].first; pe[e].right = edges[e].second; }
-    std::vector<psx_match_pair_u8> pb( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
-    std::vector<int> counts( edges.size(), 0 );
-    int count = 0;
-    if( rc == PSX_OK )
-        rc = psx_match_pairs_graph_u8( device, ptrs.data(), lens.data(), N, pe.data(), E, &po, pb.data(), (int)pb.size(), counts.data(), &count );
-    for( void* b : bufs ) psx_dev_free( device, b );
-    if( rc != PSX_OK ) {
-        std::ostringstream ss;
-        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    std::vector<std::vector<int>> fem( views.size() );       // every used view's reverse map, read once
-    for( int v = 0; v < N; v++ ) {
-        if( !used[v] ) continue;
-        fem[v].resize( lens[v] );
-        if( psx_dev_read( device, fem[v].data(), views[v]->_rev, (size_t)lens[v] * sizeof(int) ) != PSX_OK )
-            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
-    }
-    size_t at = 0;
-    for( int e = 0; e < E; e++ ) {
-        if( counts[e] <= 0 ) continue;
-        const std::vector<int>& l_fem = fem[pe[e].left];
-        const std::vector<int>& r_fem = fem[pe[e].right];
-        out[e].resize( counts[e] );
-        for( int q = 0; q < counts[e]; q++, at++ ) {
-            Match& m = out[e][q];
-            m.left_descriptor = pb[at].left; m.right_descriptor = pb[at].right;
-            m.distance        = pb[at].d1 == INT32_MAX ? INFINITY : (float)pb[at].d1;
-            m.second_distance = pb[at].d2 == INT32_MAX ? INFINITY : (float)pb[at].d2;
-            m.left_feature  = l_fem[m.left_descriptor];
-            m.right_feature = r_fem[m.right_descriptor];
-        }
-    }
-    return out;
-}
-
-// FeaturesDev::matchPairsManyFloat: psx_match_pairs_many on the objects' own float descriptors -- nothing is quantised,
-// nothing is copied, ONE matching call for all of them; the concatenated list is cut at the per-set counts and mapped
-// through the reverse maps as matchPairs does
 std::vector<std::vector<Match>> FeaturesDev::matchPairsManyFloat( const std::vector<FeaturesDev*>& others, const MatchOptions& opts )
 {
-    const char* who = "FeaturesDev::matchPairsManyFloat";
-    for( FeaturesDev* o : others ) {
-        if( o == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
-        if( o->_device != _device ) {
-            std::ostringstream ss;
-            ss << who << ": the objects live on different devices (" << _device << " and " << o->_device << ")";
-            fatal( __FILE__, __LINE__, ss.str() );
-        }
-    }
-    if( opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": float descriptors only (use matchPairsMany for MatchOptions::bytes)" );
-    const int K = (int)others.size();
-    const int l_len = getDescriptorCount();
-    std::vector<std::vector<Match>> out( others.size() );
-    bool any = false;
-    for( FeaturesDev* o : others ) any = any || o->getDescriptorCount() > 0;
-    if( l_len <= 0 || !any ) return out;
-    psx_match_opts po;
-    po.ratio = opts.ratio;
-    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
-    std::vector<const float*> ptrs( K, nullptr );
-    std::vector<int> lens( K, 0 ), counts( K, 0 );
-    for( int k = 0; k < K; k++ ) {
-        const int r_len = others[k]->getDescriptorCount();
-        if( r_len <= 0 ) continue;
-        lens[k] = r_len;
-        ptrs[k] = (const float*)others[k]->_ori;
-    }
-    // at most l_len pairs per set exist (a product above INT_MAX is the call's to refuse)
-    const long long room = (long long)K * l_len;
-    std::vector<psx_match_pair> pf( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
-    int count = 0;
-    const int rc = psx_match_pairs_many( _device, (const float*)_ori, l_len, ptrs.data(), lens.data(), K, &po,
-                                         pf.data(), (int)pf.size(), counts.data(), &count );
-    if( rc != PSX_OK ) {
-        std::ostringstream ss;
-        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    std::vector<int> l_fem( l_len );
-    if( psx_dev_read( _device, l_fem.data(), _rev, (size_t)l_len * sizeof(int) ) != PSX_OK )
-        fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
-    size_t at = 0;
-    for( int k = 0; k < K; k++ ) {
-        if( counts[k] <= 0 ) continue;
-        std::vector<int> r_fem( lens[k] );
-        if( psx_dev_read( _device, r_fem.data(), others[k]->_rev, (size_t)lens[k] * sizeof(int) ) != PSX_OK )
-            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
-        out[k].resize( counts[k] );
-        for( int q = 0; q < counts[k]; q++, at++ ) {
-            Match& m = out[k][q];
-            m.left_descriptor = pf[at].left; m.right_descriptor = pf[at].right;
-            m.distance = pf[at].d1; m.second_distance = pf[at].d2;
-            m.left_feature  = l_fem[m.left_descriptor];
-            m.right_feature = r_fem[m.right_descriptor];
-        }
-    }
-    return out;
+    return matchLists( "FeaturesDev::matchPairsManyFloat", Star, star_views( this, others ), star_edges( others.size() ), nullptr, opts,
+                       opts.bytes ? ": float descriptors only (use matchPairsMany for MatchOptions::bytes)" : nullptr );
 }
 
-// FeaturesDev::matchPairsGuidedMany: psx_match_pairs_guided_many_u8 on this object's bytes and positions and every other
-// object's that is neither empty nor skipped -- each side quantised and its positions gathered once, ONE matching call for
-// all of them; the concatenated list is cut at the per-set counts and mapped through the reverse maps as matchPairs does
 std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedMany( const std::vector<FeaturesDev*>& others, const std::vector<MatchGuide>& guides,
                                                                    const MatchOptions& opts )
 {
-    const char* who = "FeaturesDev::matchPairsGuidedMany";
-    for( FeaturesDev* o : others ) {
-        if( o == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
-        if( o->_device != _device ) {
-            std::ostringstream ss;
-            ss << who << ": the objects live on different devices (" << _device << " and " << o->_device << ")";
-            fatal( __FILE__, __LINE__, ss.str() );
-        }
-    }
-    if( !opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": the one-to-many form is byte-only (set MatchOptions::bytes)" );
-    if( guides.size() != others.size() ) {
-        std::ostringstream ss;
-        ss << who << ": " << others.size() << " objects but " << guides.size() << " guides";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    const int K = (int)others.size();
-    std::vector<psx_guide> pg( others.size() );
-    for( int k = 0; k < K; k++ ) {
-        pg[k].kind = (int)guides[k].kind;
-        for( int q = 0; q < 9; q++ ) pg[k].m[q] = guides[k].m[q];
-        pg[k].tol = guides[k].tol;
-        if( pg[k].kind == PSX_GUIDE_NONE ) continue;
-        // refused here, before any device is touched (and for empty sides too): what the call refuses
-        bool ok = ( pg[k].kind == PSX_GUIDE_HOMOGRAPHY || pg[k].kind == PSX_GUIDE_EPIPOLAR ) && std::isfinite( pg[k].tol ) && pg[k].tol >= 0.0f;
-        for( int q = 0; q < 9; q++ ) ok = ok && std::isfinite( pg[k].m[q] );
-        if( !ok ) fatal( __FILE__, __LINE__, std::string( who ) + ": invalid guide (kind 0, 1 or 2, finite entries, finite tolerance >= 0)" );
-    }
-    const int l_len = getDescriptorCount();
-    std::vector<std::vector<Match>> out( others.size() );
-    std::vector<int> lens( K, 0 ), counts( K, 0 );
-    bool any = false;
-    for( int k = 0; k < K; k++ ) {
-        if( pg[k].kind != PSX_GUIDE_NONE && others[k]->getDescriptorCount() > 0 ) lens[k] = others[k]->getDescriptorCount();
-        any = any || lens[k] > 0;
-    }
-    if( l_len <= 0 || !any ) return out;
-    psx_match_opts po;
-    po.ratio = opts.ratio;
-    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
-    // descriptors of set k at [k], its positions at [K + 1 + k]; this object's at [K] and [2 K + 1]
-    std::vector<void*> bufs( 2 * (size_t)K + 2, nullptr );
-    std::vector<const unsigned char*> ptrs( K, nullptr );
-    std::vector<const float*> xys( K, nullptr );
-    int rc = psx_dev_alloc( _device, (size_t)l_len * 128, &bufs[K] );
-    if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)l_len * 2 * sizeof(float), &bufs[2 * K + 1] );
-    if( rc == PSX_OK ) rc = psx_quantize_desc( _device, (const float*)_ori, l_len, (unsigned char*)bufs[K] );
-    if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)_ext, _rev, l_len, (float*)bufs[2 * K + 1] );
-    for( int k = 0; k < K && rc == PSX_OK; k++ ) {
-        const int r_len = lens[k];
-        if( r_len <= 0 ) continue;
-        rc = psx_dev_alloc( _device, (size_t)r_len * 128, &bufs[k] );
-        if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)r_len * 2 * sizeof(float), &bufs[K + 1 + k] );
-        if( rc == PSX_OK ) rc = psx_quantize_desc( _device, (const float*)others[k]->_ori, r_len, (unsigned char*)bufs[k] );
-        if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)others[k]->_ext, others[k]->_rev, r_len, (float*)bufs[K + 1 + k] );
-        ptrs[k] = (const unsigned char*)bufs[k];
-        xys[k] = (const float*)bufs[K + 1 + k];
-    }
-    // at most l_len pairs per set exist (a product above INT_MAX is the call's to refuse)
-    const long long room = (long long)K * l_len;
-    std::vector<psx_match_pair_u8> pb( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
-    int count = 0;
-    if( rc == PSX_OK )
-        rc = psx_match_pairs_guided_many_u8( _device, (const unsigned char*)bufs[K], (const float*)bufs[2 * K + 1], l_len, ptrs.data(), xys.data(),
-                                             lens.data(), K, pg.data(), &po, pb.data(), (int)pb.size(), counts.data(), &count );
-    for( void* b : bufs ) psx_dev_free( _device, b );
-    if( rc != PSX_OK ) {
-        std::ostringstream ss;
-        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    std::vector<int> l_fem( l_len );
-    if( psx_dev_read( _device, l_fem.data(), _rev, (size_t)l_len * sizeof(int) ) != PSX_OK )
-        fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
-    size_t at = 0;
-    for( int k = 0; k < K; k++ ) {
-        if( counts[k] <= 0 ) continue;
-        std::vector<int> r_fem( lens[k] );
-        if( psx_dev_read( _device, r_fem.data(), others[k]->_rev, (size_t)lens[k] * sizeof(int) ) != PSX_OK )
-            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
-        out[k].resize( counts[k] );
-        for( int q = 0; q < counts[k]; q++, at++ ) {
-            Match& m = out[k][q];
-            m.left_descriptor = pb[at].left; m.right_descriptor = pb[at].right;
-            m.distance        = pb[at].d1 == INT32_MAX ? INFINITY : (float)pb[at].d1;
-            m.second_distance = pb[at].d2 == INT32_MAX ? INFINITY : (float)pb[at].d2;
-            m.left_feature  = l_fem[m.left_descriptor];
-            m.right_feature = r_fem[m.right_descriptor];
-        }
-    }
-    return out;
+    return matchLists( "FeaturesDev::matchPairsGuidedMany", Star, star_views( this, others ), star_edges( others.size() ), &guides, opts,
+                       opts.bytes ? nullptr : ": the one-to-many form is byte-only (set MatchOptions::bytes)" );
+}
+
+std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedManyFloat( const std::vector<FeaturesDev*>& others, const std::vector<MatchGuide>& guides,
+                                                                        const MatchOptions& opts )
+{
+    return matchLists( "FeaturesDev::matchPairsGuidedManyFloat", Star, star_views( this, others ), star_edges( others.size() ), &guides, opts,
+                       opts.bytes ? ": float descriptors only (use matchPairsGuidedMany for MatchOptions::bytes)" : nullptr );
+}
+
+std::vector<std::vector<Match>> FeaturesDev::matchPairsGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                              const MatchOptions& opts )
+{
+    return matchLists( "FeaturesDev::matchPairsGraph", EdgeList, views, edges, nullptr, opts,
+                       opts.bytes ? nullptr : ": the edge-list form is byte-only (set MatchOptions::bytes)" );
+}
+
+std::vector<std::vector<Match>> FeaturesDev::matchPairsGraphFloat( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                   const MatchOptions& opts )
+{
+    return matchLists( "FeaturesDev::matchPairsGraphFloat", EdgeList, views, edges, nullptr, opts,
+                       opts.bytes ? ": float descriptors only (use the byte form for MatchOptions::bytes)" : nullptr );
+}
+
+std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                                                                    const std::vector<MatchGuide>& guides, const MatchOptions& opts )
+{
+    return matchLists( "FeaturesDev::matchPairsGuidedGraph", EdgeList, views, edges, &guides, opts,
+                       opts.bytes ? nullptr : ": the edge-list form is byte-only (set MatchOptions::bytes)" );
+}
+
+std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedGraphFloat( const std::vector<FeaturesDev*>& views,
+                                                                         const std::vector<std::pair<int,int>>& edges,
+                                                                         const std::vector<MatchGuide>& guides, const MatchOptions& opts )
+{
+    return matchLists( "FeaturesDev::matchPairsGuidedGraphFloat", EdgeList, views, edges, &guides, opts,
+                       opts.bytes ? ": float descriptors only (use the byte form for MatchOptions::bytes)" : nullptr );
+}
+
+// ---- RANSAC: three forms, four models each
+HomographyEstimate FeaturesDev::estimate( const char* who, RansacModel model, FeaturesDev* other, const std::vector<Match>& matches,
+                                          const RansacOptions& opts )
+{
+    const Views views = star_views( this, Views( 1, other ) );
+    const Edges edges = star_edges( 1 );
+    const int device = checkViews( who, OnePair, views, edges, 1, "match lists" );
+    return estimate_lists( who, model, OnePair, device, views, edges, std::vector<const std::vector<Match>*>( 1, &matches ), opts )[0];
+}
+
+std::vector<HomographyEstimate> FeaturesDev::estimateMany( const char* who, RansacModel model, const std::vector<FeaturesDev*>& others,
+                                                           const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
+{
+    const Views views = star_views( this, others );
+    const Edges edges = star_edges( others.size() );
+    const int device = checkViews( who, Star, views, edges, matches.size(), "match lists" );
+    return estimate_lists( who, model, Star, device, views, edges, pointers( matches ), opts );
+}
+
+std::vector<HomographyEstimate> FeaturesDev::estimateGraph( const char* who, RansacModel model, const std::vector<FeaturesDev*>& views,
+                                                            const std::vector<std::pair<int,int>>& edges,
+                                                            const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
+{
+    const int device = checkViews( who, EdgeList, views, edges, matches.size(), "match lists" );
+    return estimate_lists( who, model, EdgeList, device, views, edges, pointers( matches ), opts );
 }
 
 HomographyEstimate FeaturesDev::estimateHomography( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts )
@@ -940,69 +961,6 @@ HomographyEstimate FeaturesDev::estimateAffine( FeaturesDev* other, const std::v
 HomographyEstimate FeaturesDev::estimateSimilarity( FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts )
 {
     return estimate( "FeaturesDev::estimateSimilarity", ModelSimilarity, other, matches, opts );
-}
-
-// what differs between the models of estimate() and estimateMany(), in the order of FeaturesDev::RansacModel
-namespace {
-typedef int (*RansacOneFn)( int, const void*, int, const float*, int, const float*, int, const psx_ransac_opts*, psx_ransac_result*, void*, int, int*,
-                            float*, int* );
-typedef int (*RansacManyFn)( int, const void*, const int*, int, const float*, int, const float* const*, const int*, const psx_ransac_opts*,
-                             psx_ransac_result*, void*, int, int*, float*, int* );
-const struct { int min_pairs; RansacOneFn one; RansacManyFn many; } ransac_models[4] = {
-    { 4, psx_ransac_homography,  psx_ransac_homography_many },
-    { 8, psx_ransac_fundamental, psx_ransac_fundamental_many },
-    { 3, psx_ransac_affine,      psx_ransac_affine_many },
-    { 2, psx_ransac_similarity,  psx_ransac_similarity_many },
-};
-}
-
-HomographyEstimate FeaturesDev::estimate( const char* who, RansacModel model, FeaturesDev* other, const std::vector<Match>& matches,
-                                          const RansacOptions& opts )
-{
-    if( other == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
-    if( other->_device != _device ) {
-        std::ostringstream ss;
-        ss << who << ": the two objects live on different devices (" << _device << " and " << other->_device << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    // refused here, before any device is touched: what the psx_ransac_* calls refuse
-    if( !( std::isfinite( opts.tol ) && opts.tol >= 0.0f ) || opts.hypotheses < 1 || opts.hypotheses > 65536 )
-        fatal( __FILE__, __LINE__, std::string( who ) + ": invalid options (finite tolerance >= 0, 1 to 65536 hypotheses)" );
-    HomographyEstimate est;
-    est.guide.kind = model == ModelFundamental ? MatchGuide::Epipolar : MatchGuide::Homography;
-    for( int k = 0; k < 9; k++ ) est.guide.m[k] = 0.0f;
-    est.guide.tol = opts.tol;
-    est.best = -1; est.sample_inliers = 0; est.refit_kept = false;
-    const int n = (int)matches.size();
-    const int l_len = getDescriptorCount(), r_len = other->getDescriptorCount();
-    if( n < ransac_models[model].min_pairs ) return est;
-    // the record is copied whole: its distance slots carry the index of the match
-    std::vector<psx_match_pair_u8> rec( n ), inl( n );
-    for( int k = 0; k < n; k++ ) { rec[k].left = matches[k].left_descriptor; rec[k].right = matches[k].right_descriptor; rec[k].d1 = k; rec[k].d2 = 0; }
-    psx_ransac_opts po;
-    po.tol = opts.tol; po.hypotheses = opts.hypotheses; po.seed = opts.seed; po.flags = opts.refit ? PSX_RANSAC_REFIT : 0;
-    psx_ransac_result res;
-    int count = 0;
-    void *lxy = nullptr, *rxy = nullptr;
-    int rc = ( l_len > 0 && r_len > 0 ) ? PSX_OK : PSX_ERR_INVALID;
-    if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)l_len * 2 * sizeof(float), &lxy );
-    if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)r_len * 2 * sizeof(float), &rxy );
-    if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)_ext, _rev, l_len, (float*)lxy );
-    if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)other->_ext, other->_rev, r_len, (float*)rxy );
-    if( rc == PSX_OK ) rc = ransac_models[model].one( _device, rec.data(), n, (const float*)lxy, l_len, (const float*)rxy, r_len, &po, &res,
-                                                      inl.data(), n, &count, nullptr, nullptr );
-    psx_dev_free( _device, lxy );
-    psx_dev_free( _device, rxy );
-    if( rc != PSX_OK ) {
-        std::ostringstream ss;
-        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options or a descriptor index outside its object" : "" ) << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    for( int k = 0; k < 9; k++ ) est.guide.m[k] = res.m[k];
-    est.best = res.best; est.sample_inliers = res.sample_inliers; est.refit_kept = res.refit_kept != 0;
-    est.inliers.reserve( count );
-    for( int k = 0; k < count; k++ ) est.inliers.push_back( matches[inl[k].d1] );
-    return est;
 }
 
 std::vector<HomographyEstimate> FeaturesDev::estimateHomographyMany( const std::vector<FeaturesDev*>& others,
@@ -1029,123 +987,6 @@ std::vector<HomographyEstimate> FeaturesDev::estimateSimilarityMany( const std::
     return estimateMany( "FeaturesDev::estimateSimilarityMany", ModelSimilarity, others, matches, opts );
 }
 
-// psx_ransac_homography_many / _fundamental_many / _affine_many / _similarity_many on the lists matchPairsMany returned: the lists that can have
-// a model go behind one another into ONE call (a shorter list is "no model" without a device, as estimate() has it), the
-// left positions are gathered once, every other object's once
-std::vector<HomographyEstimate> FeaturesDev::estimateMany( const char* who, RansacModel model, const std::vector<FeaturesDev*>& others,
-                                                           const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
-{
-    if( others.size() != matches.size() ) {
-        std::ostringstream ss;
-        ss << who << ": " << others.size() << " objects but " << matches.size() << " match lists";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    for( FeaturesDev* o : others ) {
-        if( o == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
-        if( o->_device != _device ) {
-            std::ostringstream ss;
-            ss << who << ": the objects live on different devices (" << _device << " and " << o->_device << ")";
-            fatal( __FILE__, __LINE__, ss.str() );
-        }
-    }
-    if( !( std::isfinite( opts.tol ) && opts.tol >= 0.0f ) || opts.hypotheses < 1 || opts.hypotheses > 65536 )
-        fatal( __FILE__, __LINE__, std::string( who ) + ": invalid options (finite tolerance >= 0, 1 to 65536 hypotheses)" );
-    const int K = (int)others.size();
-    const int min_pairs = ransac_models[model].min_pairs;
-    HomographyEstimate none;
-    none.guide.kind = model == ModelFundamental ? MatchGuide::Epipolar : MatchGuide::Homography;
-    for( int k = 0; k < 9; k++ ) none.guide.m[k] = 0.0f;
-    none.guide.tol = opts.tol;
-    none.best = -1; none.sample_inliers = 0; none.refit_kept = false;
-    std::vector<HomographyEstimate> out( others.size(), none );
-    std::vector<int> counts( K, 0 ), lens( K, 0 );
-    size_t total = 0;
-    for( int k = 0; k < K; k++ )
-        if( (int)matches[k].size() >= min_pairs ) { counts[k] = (int)matches[k].size(); total += matches[k].size(); }
-    if( total == 0 ) return out;
-    // the record is copied whole: its distance slots carry the index of the match within its list
-    std::vector<psx_match_pair_u8> rec( total ), inl( total );
-    size_t at = 0;
-    for( int k = 0; k < K; k++ )
-        for( int q = 0; q < counts[k]; q++, at++ ) {
-            rec[at].left = matches[k][q].left_descriptor; rec[at].right = matches[k][q].right_descriptor; rec[at].d1 = q; rec[at].d2 = 0;
-        }
-    psx_ransac_opts po;
-    po.tol = opts.tol; po.hypotheses = opts.hypotheses; po.seed = opts.seed; po.flags = opts.refit ? PSX_RANSAC_REFIT : 0;
-    std::vector<psx_ransac_result> res( K );
-    std::vector<void*> bufs( (size_t)K + 1, nullptr );
-    std::vector<const float*> rxys( K, nullptr );
-    const int l_len = getDescriptorCount();
-    int count = 0;
-    int rc = l_len > 0 ? PSX_OK : PSX_ERR_INVALID;
-    if( rc == PSX_OK ) rc = psx_dev_alloc( _device, (size_t)l_len * 2 * sizeof(float), &bufs[K] );
-    if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)_ext, _rev, l_len, (float*)bufs[K] );
-    for( int k = 0; k < K && rc == PSX_OK; k++ ) {
-        const int r_len = others[k]->getDescriptorCount();
-        if( counts[k] == 0 ) continue;
-        if( r_len <= 0 ) { rc = PSX_ERR_INVALID; break; }
-        lens[k] = r_len;
-        rc = psx_dev_alloc( _device, (size_t)r_len * 2 * sizeof(float), &bufs[k] );
-        if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)others[k]->_ext, others[k]->_rev, r_len, (float*)bufs[k] );
-        rxys[k] = (const float*)bufs[k];
-    }
-    if( rc == PSX_OK )
-        rc = ransac_models[model].many( _device, rec.data(), counts.data(), K, (const float*)bufs[K], l_len, rxys.data(), lens.data(), &po, res.data(),
-                                        inl.data(), (int)total, &count, nullptr, nullptr );
-    for( void* b : bufs ) psx_dev_free( _device, b );
-    if( rc != PSX_OK ) {
-        std::ostringstream ss;
-        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options or a descriptor index outside its object" : "" ) << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    at = 0;
-    for( int k = 0; k < K; k++ ) {
-        if( counts[k] == 0 ) continue;
-        HomographyEstimate& est = out[k];
-        for( int j = 0; j < 9; j++ ) est.guide.m[j] = res[k].m[j];
-        est.best = res[k].best; est.sample_inliers = res[k].sample_inliers; est.refit_kept = res[k].refit_kept != 0;
-        est.inliers.reserve( res[k].inliers );
-        for( int q = 0; q < res[k].inliers; q++, at++ ) est.inliers.push_back( matches[k][inl[at].d1] );
-    }
-    return out;
-}
-
-namespace {
-typedef int (*RansacGraphFn)( int, const void*, const int*, const psx_view_edge*, int, const float* const*, const int*, int, const psx_ransac_opts*,
-                              psx_ransac_result*, void*, int, int*, float*, int* );
-const RansacGraphFn ransac_graph_models[4] = { psx_ransac_homography_graph, psx_ransac_fundamental_graph, psx_ransac_affine_graph,
-                                               psx_ransac_similarity_graph };
-
-// what the edge-list forms refuse about their views and edges, as matchPairsGraph does: an edge index outside `views`, a
-// null view that an edge names, named views on different devices.  Returns the device of the named views (-1: no edge).
-int graph_views_device( const char* who, const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
-                        int (*device_of)( FeaturesDev* ) )
-{
-    const int N = (int)views.size();
-    std::vector<char> named( views.size(), 0 );
-    for( const std::pair<int,int>& e : edges ) {
-        if( e.first < 0 || e.first >= N || e.second < 0 || e.second >= N ) {
-            std::ostringstream ss;
-            ss << who << ": edge (" << e.first << ", " << e.second << ") out of range (" << N << " views)";
-            fatal( __FILE__, __LINE__, ss.str() );
-        }
-        named[e.first] = named[e.second] = 1;
-    }
-    int device = -1;
-    for( int v = 0; v < N; v++ ) {
-        if( !named[v] ) continue;
-        if( views[v] == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
-        if( device < 0 ) device = device_of( views[v] );
-        if( device_of( views[v] ) != device ) {
-            std::ostringstream ss;
-            ss << who << ": the objects live on different devices (" << device << " and " << device_of( views[v] ) << ")";
-            fatal( __FILE__, __LINE__, ss.str() );
-        }
-    }
-    return device;
-}
-}
-
 std::vector<HomographyEstimate> FeaturesDev::estimateHomographyGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
                                                                       const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
 {
@@ -1170,95 +1011,12 @@ std::vector<HomographyEstimate> FeaturesDev::estimateSimilarityGraph( const std:
     return estimateGraph( "FeaturesDev::estimateSimilarityGraph", ModelSimilarity, views, edges, matches, opts );
 }
 
-// psx_ransac_homography_graph / _fundamental_graph / _affine_graph / _similarity_graph on the lists matchPairsGraph returned:
-// the lists that can have a model go behind one another into ONE call (a shorter list is "no model" without a device, as
-// estimate() has it), the positions of every view such an edge names are gathered once
-std::vector<HomographyEstimate> FeaturesDev::estimateGraph( const char* who, RansacModel model, const std::vector<FeaturesDev*>& views,
-                                                            const std::vector<std::pair<int,int>>& edges,
-                                                            const std::vector<std::vector<Match>>& matches, const RansacOptions& opts )
-{
-    if( edges.size() != matches.size() ) {
-        std::ostringstream ss;
-        ss << who << ": " << edges.size() << " edges but " << matches.size() << " match lists";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    const int device = graph_views_device( who, views, edges, []( FeaturesDev* f ) { return f->_device; } );
-    if( !( std::isfinite( opts.tol ) && opts.tol >= 0.0f ) || opts.hypotheses < 1 || opts.hypotheses > 65536 )
-        fatal( __FILE__, __LINE__, std::string( who ) + ": invalid options (finite tolerance >= 0, 1 to 65536 hypotheses)" );
-    const int N = (int)views.size(), E = (int)edges.size();
-    const int min_pairs = ransac_models[model].min_pairs;
-    HomographyEstimate none;
-    none.guide.kind = model == ModelFundamental ? MatchGuide::Epipolar : MatchGuide::Homography;
-    for( int k = 0; k < 9; k++ ) none.guide.m[k] = 0.0f;
-    none.guide.tol = opts.tol;
-    none.best = -1; none.sample_inliers = 0; none.refit_kept = false;
-    std::vector<HomographyEstimate> out( edges.size(), none );
-    std::vector<int> counts( edges.size(), 0 ), lens( views.size(), 0 );
-    std::vector<char> used( views.size(), 0 );               // named by an edge that has a model to estimate
-    size_t total = 0;
-    for( int e = 0; e < E; e++ )
-        if( (int)matches[e].size() >= min_pairs ) {
-            counts[e] = (int)matches[e].size(); total += matches[e].size();
-            used[edges[e].first] = used[edges[e].second] = 1;
-        }
-    if( total == 0 ) return out;
-    // the record is copied whole: its distance slots carry the index of the match within its list
-    std::vector<psx_match_pair_u8> rec( total ), inl( total );
-    size_t at = 0;
-    for( int e = 0; e < E; e++ )
-        for( int q = 0; q < counts[e]; q++, at++ ) {
-            rec[at].left = matches[e][q].left_descriptor; rec[at].right = matches[e][q].right_descriptor; rec[at].d1 = q; rec[at].d2 = 0;
-        }
-    psx_ransac_opts po;
-    po.tol = opts.tol; po.hypotheses = opts.hypotheses; po.seed = opts.seed; po.flags = opts.refit ? PSX_RANSAC_REFIT : 0;
-    std::vector<psx_view_edge> pe( edges.size() );
-    for( int e = 0; e < E; e++ ) { pe[e].left = edges[e].first; pe[e].right = edges[e].second; }
-    std::vector<psx_ransac_result> res( edges.size() );
-    std::vector<void*> bufs( views.size(), nullptr );
-    std::vector<const float*> xys( views.size(), nullptr );
-    int count = 0;
-    int rc = PSX_OK;
-    for( int v = 0; v < N && rc == PSX_OK; v++ ) {
-        if( !used[v] ) continue;
-        const int len = views[v]->getDescriptorCount();
-        if( len <= 0 ) { rc = PSX_ERR_INVALID; break; }
-        lens[v] = len;
-        rc = psx_dev_alloc( device, (size_t)len * 2 * sizeof(float), &bufs[v] );
-        if( rc == PSX_OK ) rc = psx_desc_positions( device, (const psx_feature_dev*)views[v]->_ext, views[v]->_rev, len, (float*)bufs[v] );
-        xys[v] = (const float*)bufs[v];
-    }
-    if( rc == PSX_OK )
-        rc = ransac_graph_models[model]( device, rec.data(), counts.data(), pe.data(), E, xys.data(), lens.data(), N, &po, res.data(), inl.data(),
-                                         (int)total, &count, nullptr, nullptr );
-    for( void* b : bufs ) psx_dev_free( device, b );
-    if( rc != PSX_OK ) {
-        std::ostringstream ss;
-        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options or a descriptor index outside its object" : "" ) << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    at = 0;
-    for( int e = 0; e < E; e++ ) {
-        if( counts[e] == 0 ) continue;
-        HomographyEstimate& est = out[e];
-        for( int j = 0; j < 9; j++ ) est.guide.m[j] = res[e].m[j];
-        est.best = res[e].best; est.sample_inliers = res[e].sample_inliers; est.refit_kept = res[e].refit_kept != 0;
-        est.inliers.reserve( res[e].inliers );
-        for( int q = 0; q < res[e].inliers; q++, at++ ) est.inliers.push_back( matches[e][inl[at].d1] );
-    }
-    return out;
-}
-
 // FeaturesDev::buildTracks: psx_tracks_graph on the descriptor indices of the lists, at the capacities no result can exceed
 Tracks FeaturesDev::buildTracks( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
                                  const std::vector<std::vector<Match>>& matches, const TrackOptions& opts )
 {
     const char* who = "FeaturesDev::buildTracks";
-    if( edges.size() != matches.size() ) {
-        std::ostringstream ss;
-        ss << who << ": " << edges.size() << " edges but " << matches.size() << " match lists";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    int device = graph_views_device( who, views, edges, []( FeaturesDev* f ) { return f->_device; } );
+    int device = checkViews( who, EdgeList, views, edges, matches.size(), "match lists" );
     if( opts.min_views < 2 ) fatal( __FILE__, __LINE__, std::string( who ) + ": invalid options (min_views >= 2)" );
     if( device < 0 ) device = 0;                             // no edge: the call touches no device
     const int N = (int)views.size(), E = (int)edges.size();
@@ -1270,17 +1028,9 @@ Tracks FeaturesDev::buildTracks( const std::vector<FeaturesDev*>& views, const s
         out.view_offsets[v + 1] = out.view_offsets[v] + lens[v];
     }
     const int M = out.view_offsets[N];
-    size_t total = 0;
-    for( int e = 0; e < E; e++ ) { counts[e] = (int)matches[e].size(); total += matches[e].size(); }
-    std::vector<psx_match_pair_u8> rec( total );
-    size_t at = 0;
-    for( int e = 0; e < E; e++ )
-        for( const Match& m : matches[e] ) {
-            rec[at].left = m.left_descriptor; rec[at].right = m.right_descriptor; rec[at].d1 = 0; rec[at].d2 = 0;
-            at++;
-        }
-    std::vector<psx_view_edge> pe( edges.size() );
-    for( int e = 0; e < E; e++ ) { pe[e].left = edges[e].first; pe[e].right = edges[e].second; }
+    for( int e = 0; e < E; e++ ) counts[e] = (int)matches[e].size();
+    const std::vector<psx_match_pair_u8> rec = pack_records( pointers( matches ), counts, false );
+    const std::vector<psx_view_edge> pe = to_psx( edges );
     psx_track_opts po;
     po.min_views = opts.min_views; po.flags = opts.keep_conflicts ? PSX_TRACKS_KEEP_CONFLICTS : 0;
     std::vector<psx_track_member> mem( (size_t)M );
@@ -1289,315 +1039,13 @@ Tracks FeaturesDev::buildTracks( const std::vector<FeaturesDev*>& views, const s
     psx_tracks_info info;
     const int rc = psx_tracks_graph( device, rec.data(), counts.data(), pe.data(), E, lens.data(), N, &po, out.labels.data(), out.starts.data(),
                                      M / 2, mem.data(), M, &info );
-    if( rc != PSX_OK ) {
-        std::ostringstream ss;
-        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": a descriptor index outside its object" : "" ) << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
+    if( rc != PSX_OK ) failed( who, rc, ": a descriptor index outside its object" );
     out.starts.resize( (size_t)info.tracks + 1 );
     out.members.resize( (size_t)info.members );
     for( int i = 0; i < info.members; i++ ) { out.members[i].view = mem[i].view; out.members[i].descriptor = mem[i].row; }
     out.n_tracks = info.tracks; out.n_members = info.members; out.components = info.components; out.conflicts = info.conflicts;
     out.too_few_views = info.too_few_views; out.joined_records = info.joined_records;
     return out;
-}
-
-// FeaturesDev::matchPairsGuidedGraph: psx_match_pairs_guided_graph_u8 on the bytes and positions of every view that an edge
-// names which is neither skipped nor has an empty side -- each quantised and its positions gathered once, ONE matching
-// call for all edges; the concatenated list is cut at the per-edge counts and mapped through the two views' reverse maps
-std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedGraph( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
-                                                                    const std::vector<MatchGuide>& guides, const MatchOptions& opts )
-{
-    const char* who = "FeaturesDev::matchPairsGuidedGraph";
-    const int device = graph_views_device( who, views, edges, []( FeaturesDev* f ) { return f->_device; } );
-    if( !opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": the edge-list form is byte-only (set MatchOptions::bytes)" );
-    if( guides.size() != edges.size() ) {
-        std::ostringstream ss;
-        ss << who << ": " << edges.size() << " edges but " << guides.size() << " guides";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    const int N = (int)views.size(), E = (int)edges.size();
-    std::vector<psx_guide> pg( edges.size() );
-    for( int e = 0; e < E; e++ ) {
-        pg[e].kind = (int)guides[e].kind;
-        for( int q = 0; q < 9; q++ ) pg[e].m[q] = guides[e].m[q];
-        pg[e].tol = guides[e].tol;
-        if( pg[e].kind == PSX_GUIDE_NONE ) continue;
-        // refused here, before any device is touched (and for empty sides too): what the call refuses
-        bool ok = ( pg[e].kind == PSX_GUIDE_HOMOGRAPHY || pg[e].kind == PSX_GUIDE_EPIPOLAR ) && std::isfinite( pg[e].tol ) && pg[e].tol >= 0.0f;
-        for( int q = 0; q < 9; q++ ) ok = ok && std::isfinite( pg[e].m[q] );
-        if( !ok ) fatal( __FILE__, __LINE__, std::string( who ) + ": invalid guide (kind 0, 1 or 2, finite entries, finite tolerance >= 0)" );
-    }
-    std::vector<std::vector<Match>> out( edges.size() );
-    std::vector<int> lens( views.size(), 0 );
-    std::vector<char> used( views.size(), 0 );               // named by an edge that is not skipped and has two non-empty sides
-    long long room = 0;                                      // at most lens[left] pairs per edge exist
-    for( int e = 0; e < E; e++ ) {
-        const int l = edges[e].first, r = edges[e].second;
-        if( pg[e].kind == PSX_GUIDE_NONE || views[l]->getDescriptorCount() <= 0 || views[r]->getDescriptorCount() <= 0 ) continue;
-        room += views[l]->getDescriptorCount();
-        used[l] = used[r] = 1;
-    }
-    if( room == 0 ) return out;
-    psx_match_opts po;
-    po.ratio = opts.ratio;
-    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
-    // descriptors of view v at [v], its positions at [N + v]
-    std::vector<void*> bufs( 2 * views.size(), nullptr );
-    std::vector<const unsigned char*> ptrs( views.size(), nullptr );
-    std::vector<const float*> xys( views.size(), nullptr );
-    int rc = PSX_OK;
-    for( int v = 0; v < N && rc == PSX_OK; v++ ) {
-        if( !used[v] ) continue;                             // a view no live edge names is an empty set to the call
-        const int len = lens[v] = views[v]->getDescriptorCount();
-        rc = psx_dev_alloc( device, (size_t)len * 128, &bufs[v] );
-        if( rc == PSX_OK ) rc = psx_dev_alloc( device, (size_t)len * 2 * sizeof(float), &bufs[N + v] );
-        if( rc == PSX_OK ) rc = psx_quantize_desc( device, (const float*)views[v]->_ori, len, (unsigned char*)bufs[v] );
-        if( rc == PSX_OK ) rc = psx_desc_positions( device, (const psx_feature_dev*)views[v]->_ext, views[v]->_rev, len, (float*)bufs[N + v] );
-        ptrs[v] = (const unsigned char*)bufs[v];
-        xys[v] = (const float*)bufs[N + v];
-    }
-    std::vector<psx_view_edge> pe( edges.size() );
-    for( int e = 0; e < E; e++ ) { pe[e].left = edges[e].first; pe[e].right = edges[e].second; }
-    std::vector<psx_match_pair_u8> pb( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
-    std::vector<int> counts( edges.size(), 0 );
-    int count = 0;
-    if( rc == PSX_OK )
-        rc = psx_match_pairs_guided_graph_u8( device, ptrs.data(), xys.data(), lens.data(), N, pe.data(), E, pg.data(), &po, pb.data(),
-                                              (int)pb.size(), counts.data(), &count );
-    for( void* b : bufs ) psx_dev_free( device, b );
-    if( rc != PSX_OK ) {
-        std::ostringstream ss;
-        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    std::vector<std::vector<int>> fem( views.size() );       // every used view's reverse map, read once
-    for( int v = 0; v < N; v++ ) {
-        if( !used[v] ) continue;
-        fem[v].resize( lens[v] );
-        if( psx_dev_read( device, fem[v].data(), views[v]->_rev, (size_t)lens[v] * sizeof(int) ) != PSX_OK )
-            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
-    }
-    size_t at = 0;
-    for( int e = 0; e < E; e++ ) {
-        if( counts[e] <= 0 ) continue;
-        const std::vector<int>& l_fem = fem[pe[e].left];
-        const std::vector<int>& r_fem = fem[pe[e].right];
-        out[e].resize( counts[e] );
-        for( int q = 0; q < counts[e]; q++, at++ ) {
-            Match& m = out[e][q];
-            m.left_descriptor = pb[at].left; m.right_descriptor = pb[at].right;
-            m.distance        = pb[at].d1 == INT32_MAX ? INFINITY : (float)pb[at].d1;
-            m.second_distance = pb[at].d2 == INT32_MAX ? INFINITY : (float)pb[at].d2;
-            m.left_feature  = l_fem[m.left_descriptor];
-            m.right_feature = r_fem[m.right_descriptor];
-        }
-    }
-    return out;
-}
-
-// ---- the float forms of the edge-list calls and of the batched guided calls -------------------------------------------------
-namespace {
-
-// the guides as the library takes them; refuses, before any device is touched (and for empty sides too), what the calls refuse
-std::vector<psx_guide> float_guides( const char* who, const std::vector<MatchGuide>& guides )
-{
-    std::vector<psx_guide> pg( guides.size() );
-    for( size_t e = 0; e < guides.size(); e++ ) {
-        pg[e].kind = (int)guides[e].kind;
-        for( int q = 0; q < 9; q++ ) pg[e].m[q] = guides[e].m[q];
-        pg[e].tol = guides[e].tol;
-        if( pg[e].kind == PSX_GUIDE_NONE ) continue;
-        bool ok = ( pg[e].kind == PSX_GUIDE_HOMOGRAPHY || pg[e].kind == PSX_GUIDE_EPIPOLAR ) && std::isfinite( pg[e].tol ) && pg[e].tol >= 0.0f;
-        for( int q = 0; q < 9; q++ ) ok = ok && std::isfinite( pg[e].m[q] );
-        if( !ok ) fatal( __FILE__, __LINE__, std::string( who ) + ": invalid guide (kind 0, 1 or 2, finite entries, finite tolerance >= 0)" );
-    }
-    return pg;
-}
-
-// the concatenated float records of an edge-list call, cut at the per-edge counts and mapped through the two views'
-// reverse maps (fem[v]: view v's, read by the caller for every view a counted edge names)
-std::vector<std::vector<Match>> float_lists( const std::vector<psx_match_pair>& pf, const std::vector<int>& counts, const std::vector<psx_view_edge>& pe,
-                                             const std::vector<std::vector<int>>& fem )
-{
-    std::vector<std::vector<Match>> out( counts.size() );
-    size_t at = 0;
-    for( size_t e = 0; e < counts.size(); e++ ) {
-        if( counts[e] <= 0 ) continue;
-        const std::vector<int>& l_fem = fem[pe[e].left];
-        const std::vector<int>& r_fem = fem[pe[e].right];
-        out[e].resize( counts[e] );
-        for( int q = 0; q < counts[e]; q++, at++ ) {
-            Match& m = out[e][q];
-            m.left_descriptor = pf[at].left; m.right_descriptor = pf[at].right;
-            m.distance = pf[at].d1; m.second_distance = pf[at].d2;
-            m.left_feature  = l_fem[m.left_descriptor];
-            m.right_feature = r_fem[m.right_descriptor];
-        }
-    }
-    return out;
-}
-
-}
-
-// Both edge-list float forms: psx_match_pairs_graph (guides == nullptr) or psx_match_pairs_guided_graph on the views' own
-// float descriptors -- nothing is quantised, no descriptor is copied; the guided form gathers every used view's positions once
-std::vector<std::vector<Match>> FeaturesDev::matchGraphFloat( const char* who, const std::vector<FeaturesDev*>& views,
-                                                              const std::vector<std::pair<int,int>>& edges, const std::vector<MatchGuide>* guides,
-                                                              const MatchOptions& opts )
-{
-    const int device = graph_views_device( who, views, edges, []( FeaturesDev* f ) { return f->_device; } );
-    if( opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": float descriptors only (use the byte form for MatchOptions::bytes)" );
-    if( guides && guides->size() != edges.size() ) {
-        std::ostringstream ss;
-        ss << who << ": " << edges.size() << " edges but " << guides->size() << " guides";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    const int N = (int)views.size(), E = (int)edges.size();
-    std::vector<psx_guide> pg;
-    if( guides ) pg = float_guides( who, *guides );
-    std::vector<std::vector<Match>> out( edges.size() );
-    std::vector<int> lens( views.size(), 0 );
-    std::vector<char> used( views.size(), 0 );               // named by an edge that is not skipped and has two non-empty sides
-    long long room = 0;                                      // at most lens[left] pairs per edge exist
-    for( int e = 0; e < E; e++ ) {
-        const int l = edges[e].first, r = edges[e].second;
-        if( ( guides && pg[e].kind == PSX_GUIDE_NONE ) || views[l]->getDescriptorCount() <= 0 || views[r]->getDescriptorCount() <= 0 ) continue;
-        room += views[l]->getDescriptorCount();
-        used[l] = used[r] = 1;
-    }
-    if( room == 0 ) return out;
-    psx_match_opts po;
-    po.ratio = opts.ratio;
-    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
-    std::vector<void*> bufs( views.size(), nullptr );        // the guided form: view v's positions
-    std::vector<const float*> ptrs( views.size(), nullptr ), xys( views.size(), nullptr );
-    int rc = PSX_OK;
-    for( int v = 0; v < N && rc == PSX_OK; v++ ) {
-        if( !used[v] ) continue;                             // a view no live edge names is an empty set to the call
-        const int len = lens[v] = views[v]->getDescriptorCount();
-        ptrs[v] = (const float*)views[v]->_ori;
-        if( !guides ) continue;
-        rc = psx_dev_alloc( device, (size_t)len * 2 * sizeof(float), &bufs[v] );
-        if( rc == PSX_OK ) rc = psx_desc_positions( device, (const psx_feature_dev*)views[v]->_ext, views[v]->_rev, len, (float*)bufs[v] );
-        xys[v] = (const float*)bufs[v];
-    }
-    std::vector<psx_view_edge> pe( edges.size() );
-    for( int e = 0; e < E; e++ ) { pe[e].left = edges[e].first; pe[e].right = edges[e].second; }
-    std::vector<psx_match_pair> pf( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
-    std::vector<int> counts( edges.size(), 0 );
-    int count = 0;
-    if( rc == PSX_OK )
-        rc = guides ? psx_match_pairs_guided_graph( device, ptrs.data(), xys.data(), lens.data(), N, pe.data(), E, pg.data(), &po, pf.data(),
-                                                    (int)pf.size(), counts.data(), &count )
-                    : psx_match_pairs_graph( device, ptrs.data(), lens.data(), N, pe.data(), E, &po, pf.data(), (int)pf.size(), counts.data(), &count );
-    for( void* b : bufs ) psx_dev_free( device, b );
-    if( rc != PSX_OK ) {
-        std::ostringstream ss;
-        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    std::vector<std::vector<int>> fem( views.size() );       // every used view's reverse map, read once
-    for( int v = 0; v < N; v++ ) {
-        if( !used[v] ) continue;
-        fem[v].resize( lens[v] );
-        if( psx_dev_read( device, fem[v].data(), views[v]->_rev, (size_t)lens[v] * sizeof(int) ) != PSX_OK )
-            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
-    }
-    return float_lists( pf, counts, pe, fem );
-}
-
-std::vector<std::vector<Match>> FeaturesDev::matchPairsGraphFloat( const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
-                                                                   const MatchOptions& opts )
-{
-    return matchGraphFloat( "FeaturesDev::matchPairsGraphFloat", views, edges, nullptr, opts );
-}
-
-std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedGraphFloat( const std::vector<FeaturesDev*>& views,
-                                                                         const std::vector<std::pair<int,int>>& edges,
-                                                                         const std::vector<MatchGuide>& guides, const MatchOptions& opts )
-{
-    return matchGraphFloat( "FeaturesDev::matchPairsGuidedGraphFloat", views, edges, &guides, opts );
-}
-
-// FeaturesDev::matchPairsGuidedManyFloat: psx_match_pairs_guided_many on this object's float descriptors and every other
-// object's that is neither empty nor skipped -- no quantisation, no descriptor copies, every side's positions gathered once
-std::vector<std::vector<Match>> FeaturesDev::matchPairsGuidedManyFloat( const std::vector<FeaturesDev*>& others, const std::vector<MatchGuide>& guides,
-                                                                        const MatchOptions& opts )
-{
-    const char* who = "FeaturesDev::matchPairsGuidedManyFloat";
-    for( FeaturesDev* o : others ) {
-        if( o == nullptr ) fatal( __FILE__, __LINE__, std::string( who ) + ": null argument" );
-        if( o->_device != _device ) {
-            std::ostringstream ss;
-            ss << who << ": the objects live on different devices (" << _device << " and " << o->_device << ")";
-            fatal( __FILE__, __LINE__, ss.str() );
-        }
-    }
-    if( opts.bytes ) fatal( __FILE__, __LINE__, std::string( who ) + ": float descriptors only (use matchPairsGuidedMany for MatchOptions::bytes)" );
-    if( guides.size() != others.size() ) {
-        std::ostringstream ss;
-        ss << who << ": " << others.size() << " objects but " << guides.size() << " guides";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    const int K = (int)others.size();
-    const std::vector<psx_guide> pg = float_guides( who, guides );
-    const int l_len = getDescriptorCount();
-    std::vector<std::vector<Match>> out( others.size() );
-    std::vector<int> lens( K, 0 ), counts( K, 0 );
-    bool any = false;
-    for( int k = 0; k < K; k++ ) {
-        if( pg[k].kind != PSX_GUIDE_NONE && others[k]->getDescriptorCount() > 0 ) lens[k] = others[k]->getDescriptorCount();
-        any = any || lens[k] > 0;
-    }
-    if( l_len <= 0 || !any ) return out;
-    psx_match_opts po;
-    po.ratio = opts.ratio;
-    po.flags = opts.mutual ? PSX_PAIRS_MUTUAL : 0;
-    // the positions of set k at [k], this object's at [K]
-    std::vector<void*> bufs( (size_t)K + 1, nullptr );
-    std::vector<const float*> ptrs( K, nullptr ), xys( K, nullptr );
-    int rc = psx_dev_alloc( _device, (size_t)l_len * 2 * sizeof(float), &bufs[K] );
-    if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)_ext, _rev, l_len, (float*)bufs[K] );
-    for( int k = 0; k < K && rc == PSX_OK; k++ ) {
-        const int r_len = lens[k];
-        if( r_len <= 0 ) continue;
-        rc = psx_dev_alloc( _device, (size_t)r_len * 2 * sizeof(float), &bufs[k] );
-        if( rc == PSX_OK ) rc = psx_desc_positions( _device, (const psx_feature_dev*)others[k]->_ext, others[k]->_rev, r_len, (float*)bufs[k] );
-        ptrs[k] = (const float*)others[k]->_ori;
-        xys[k] = (const float*)bufs[k];
-    }
-    // at most l_len pairs per set exist (a product above INT_MAX is the call's to refuse)
-    const long long room = (long long)K * l_len;
-    std::vector<psx_match_pair> pf( (size_t)( room < INT32_MAX ? room : INT32_MAX ) );
-    int count = 0;
-    if( rc == PSX_OK )
-        rc = psx_match_pairs_guided_many( _device, (const float*)_ori, (const float*)bufs[K], l_len, ptrs.data(), xys.data(), lens.data(), K,
-                                          pg.data(), &po, pf.data(), (int)pf.size(), counts.data(), &count );
-    for( void* b : bufs ) psx_dev_free( _device, b );
-    if( rc != PSX_OK ) {
-        std::ostringstream ss;
-        ss << who << " failed (" << rc << ( rc == PSX_ERR_INVALID ? ": invalid options" : "" ) << ")";
-        fatal( __FILE__, __LINE__, ss.str() );
-    }
-    // the star as an edge list over [others..., this]: set k is edge (K, k)
-    std::vector<std::vector<int>> fem( (size_t)K + 1 );
-    std::vector<psx_view_edge> pe( K );
-    bool pairs = false;
-    for( int k = 0; k < K; k++ ) {
-        pe[k].left = K; pe[k].right = k;
-        if( counts[k] <= 0 ) continue;
-        pairs = true;
-        fem[k].resize( lens[k] );
-        if( psx_dev_read( _device, fem[k].data(), others[k]->_rev, (size_t)lens[k] * sizeof(int) ) != PSX_OK )
-            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
-    }
-    if( pairs ) {
-        fem[K].resize( l_len );
-        if( psx_dev_read( _device, fem[K].data(), _rev, (size_t)l_len * sizeof(int) ) != PSX_OK )
-            fatal( __FILE__, __LINE__, std::string( who ) + ": reading the reverse maps failed" );
-    }
-    return float_lists( pf, counts, pe, fem );
 }
 
 } // namespace popsift

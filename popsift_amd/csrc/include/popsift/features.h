@@ -215,13 +215,16 @@ class FeaturesDev : public FeaturesBase
     int*         _rev;   // device: descriptor -> extremum
     int          _device;
 
+    // every wrapper below states its call as views + edge list (features.cpp): form = one pair, star or edge list
+    static int checkViews( const char* who, int form, const std::vector<FeaturesDev*>& views, const std::vector<std::pair<int,int>>& edges,
+                           size_t given, const char* what );
+    static std::vector<std::vector<Match>> matchLists( const char* who, int form, const std::vector<FeaturesDev*>& views,
+                                                       const std::vector<std::pair<int,int>>& edges, const std::vector<MatchGuide>* guides,
+                                                       const MatchOptions& opts, const char* wrong_format );
     enum RansacModel { ModelHomography, ModelFundamental, ModelAffine, ModelSimilarity };   // what estimate() fits
     HomographyEstimate estimate( const char* who, RansacModel model, FeaturesDev* other, const std::vector<Match>& matches, const RansacOptions& opts );
     std::vector<HomographyEstimate> estimateMany( const char* who, RansacModel model, const std::vector<FeaturesDev*>& others,
                                                   const std::vector<std::vector<Match>>& matches, const RansacOptions& opts );
-    static std::vector<std::vector<Match>> matchGraphFloat( const char* who, const std::vector<FeaturesDev*>& views,
-                                                            const std::vector<std::pair<int,int>>& edges, const std::vector<MatchGuide>* guides,
-                                                            const MatchOptions& opts );
     static std::vector<HomographyEstimate> estimateGraph( const char* who, RansacModel model, const std::vector<FeaturesDev*>& views,
                                                           const std::vector<std::pair<int,int>>& edges,
                                                           const std::vector<std::vector<Match>>& matches, const RansacOptions& opts );
