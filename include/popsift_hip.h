@@ -1106,6 +1106,80 @@ int psx_tracks_graph_ref(const void* pairs, const int* edge_counts, const psx_vi
 typedef struct psx_tracks_plan_info { int nodes, records, record_blocks, sort_bits, launches; long long scratch_bytes; } psx_tracks_plan_info;
 int psx_tracks_plan(const int* lens, int n_sets, const int* edge_counts, int n_edges, psx_tracks_plan_info* out);
 
+/* WHICH PAIRS TO MATCH: the zeroth link.  Every graph call above takes its edge list from the caller; all pairs grow as
+ * N^2 and a window only helps ordered video.  These three calls answer "which views could see the same thing?" the way
+ * structure-from-motion front ends do before feature matching (AliceVision's imageMatching step over a vocabulary tree;
+ * Nister & Stewenius, "Scalable recognition with a vocabulary tree", CVPR 2006, for the idf-weighted, L1-normalised
+ * scoring; Sivic & Zisserman, "Video Google", ICCV 2003): a visual vocabulary, a bag of words per view, the k most similar
+ * views per view.  The reference has no counterpart.  N byte descriptor sets in HBM go in, a sorted, deduplicated
+ * psx_view_edge list comes out, which the four graph calls take unchanged; INTEGRATION.md ("Which pairs to match") has the
+ * five-call chain and the measured cost.
+ * FORMS.  Each call has a form with HOST outputs, a _dev form whose arrays are all DEVICE memory, and a _ref form that runs
+ * on the host alone, is sequential and is the definition: the device forms equal it bit for bit.  The descriptor sets
+ * (d_sets[v]: lens[v] rows of 128 bytes, 16-byte aligned) are DEVICE pointers in both device forms and host arrays in the
+ * _ref form; a vocabulary, a histogram and every output are HOST memory in the host form and DEVICE memory in the _dev
+ * form; lens, opts, info and edge_count are always HOST memory.
+ * THE RULE (csrc/hip/bow_rule.h, shared by host and device).  Row r of view v is global row g = off[v] + r, off = the
+ * exclusive prefix sum of lens, M = their sum; d(x, c) = sum_k (x_k - c_k)^2, an exact integer.
+ *   TRAIN   integer k-means, opts = {words W, iterations T}, 2 <= W <= 65536, W <= M <= 2^24, T >= 1.  Word w starts as
+ *           global row floor(w M / W).  An iteration assigns every row to the word with the smallest (d, w) -- ties to the
+ *           lower word, the byte matcher's order -- and replaces every word that has rows by their mean, byte by byte
+ *           (2 sum + cnt) / (2 cnt) in integers (half rounds up); a word without rows keeps its bytes.  It stops after T
+ *           iterations or after the first one in which no row changed its word (in the first, every row counts as
+ *           changed).  info: iterations run; changed and empty_words of the last assignment; inertia = the sum of d(g, a(g))
+ *           of the last assignment against the words it was made with; reserved = 0.  Empty views are allowed.
+ *   BAGS    hist[v][w] (n_sets x words, uint32) = the rows of view v assigned to word w; words_out (M ints, may be NULL) =
+ *           a(g) of every row.  1 <= words <= 65536, M <= 0x3fffffff.  n_sets = 0 or M = 0 touches no device: the host form
+ *           and the reference write a zero histogram, the _dev form writes nothing.
+ *   LISTS   n_v = the sum of hist[v][.] (not a trusted length); df[w] = the views with hist[v][w] > 0; weight[w] = 0 for
+ *           df = 0, otherwise 1 + floor(16 log2(N / df) + 0.5) in double, evaluated ONLY on the host by psx_bow_weights(df,
+ *           words, n_views, out), which the library and the reference both call (the device counts df; one download of W
+ *           ints and one upload of W weights); q[v][w] = floor(hist[v][w] 65535 / n_v), 0 for n_v = 0; score(i, j) = sum_w
+ *           weight[w] min(q[i][w], q[j][w]), symmetric and below 2^24.  The list of view i: the views j != i with
+ *           score(i, j) > 0 by (score descending, j ascending), the first k; neighbours[i][0 .. k) and scores[i][0 .. k)
+ *           (either may be NULL), unused entries -1 and 0; k may exceed n_views - 1.  The edges: {(min(i, j), max(i, j)) :
+ *           j in the list of i}, once each, ascending by (left, right); with PSX_SHORTLIST_MUTUAL only the pairs in which
+ *           each view lists the other.  *edge_count is always the total, the first min(total, edge_capacity) edges are
+ *           written, nothing at or past the capacity is touched; capacity 0 with NULL asks "how many?".  n_views = 0: no
+ *           edge, nothing else written, no device.
+ * PSX_ERR_INVALID, before any device call and with nothing written: n_sets < 0, a NULL array that is needed, a negative
+ * length, a NULL set with a positive length, a misaligned device pointer (sets 16 bytes, ints 4, edges 8); NULL opts, info,
+ * vocabulary or edge_count; words or iterations out of range, words > M, M too large; n_views > 4096 (or < 0), k < 1,
+ * unknown flag bits, n_views * k above INT_MAX, a negative capacity or a NULL edge array with a positive one; for
+ * psx_bow_weights a df outside [0, n_views] or n_views < 1.
+ * LAUNCHES.  Training, once per call: the table copy, 3 kernels (the gather of all rows into one array, their norms, the
+ * initial words) and one clear; then per iteration one clear, 4 kernels (the words' norms, the assignment, the
+ * accumulation, the update) and ONE synchronisation that brings back the 16 bytes deciding the stop; the host form ends
+ * with one more copy and synchronisation for the vocabulary.  psx_bow_u8*: the table copy, 5 kernels and one clear, one
+ * synchronisation.  psx_shortlist_views*: 6 kernels and 2 clears, TWO synchronisations (the first brings df to the host for
+ * the weights).  None depends on n_sets, n_views or M.  The assignment is the byte matcher's i8-MFMA tile walk
+ * (csrc/hip/match_u8_core.h); the rows of all views are gathered into one scratch array of 128 M bytes first.  Scratch
+ * (psx_match_release) and thread safety as for psx_match_u8.  Synchronous. */
+#define PSX_SHORTLIST_MUTUAL 1
+typedef struct psx_vocab_opts     { int words; int iterations; } psx_vocab_opts;
+typedef struct psx_vocab_info     { int iterations, changed, empty_words, reserved; unsigned long long inertia; } psx_vocab_info;
+typedef struct psx_shortlist_opts { int k; int flags; } psx_shortlist_opts;
+int psx_vocab_train_u8(int device, const unsigned char* const* d_sets, const int* lens, int n_sets, const psx_vocab_opts* opts,
+                       unsigned char* host_vocab, psx_vocab_info* info);
+int psx_vocab_train_u8_dev(int device, const unsigned char* const* d_sets, const int* lens, int n_sets, const psx_vocab_opts* opts,
+                           unsigned char* d_vocab, psx_vocab_info* info);
+int psx_vocab_train_u8_ref(const unsigned char* const* sets, const int* lens, int n_sets, const psx_vocab_opts* opts,
+                           unsigned char* vocab, psx_vocab_info* info);
+int psx_bow_u8(int device, const unsigned char* host_vocab, int words, const unsigned char* const* d_sets, const int* lens, int n_sets,
+               unsigned* host_hist, int* host_words_out);
+int psx_bow_u8_dev(int device, const unsigned char* d_vocab, int words, const unsigned char* const* d_sets, const int* lens, int n_sets,
+                   unsigned* d_hist, int* d_words_out);
+int psx_bow_u8_ref(const unsigned char* vocab, int words, const unsigned char* const* sets, const int* lens, int n_sets,
+                   unsigned* hist, int* words_out);
+int psx_shortlist_views(int device, const unsigned* host_hist, int n_views, int words, const psx_shortlist_opts* opts,
+                        int* host_neighbours, unsigned* host_scores, psx_view_edge* host_edges, int edge_capacity, int* edge_count);
+int psx_shortlist_views_dev(int device, const unsigned* d_hist, int n_views, int words, const psx_shortlist_opts* opts,
+                            int* d_neighbours, unsigned* d_scores, psx_view_edge* d_edges, int edge_capacity, int* edge_count);
+int psx_shortlist_views_ref(const unsigned* hist, int n_views, int words, const psx_shortlist_opts* opts,
+                            int* neighbours, unsigned* scores, psx_view_edge* edges, int edge_capacity, int* edge_count);
+/* HOST only: out[w] = the weight of a word that df[w] of n_views views contain (the one logarithm of the step) */
+int psx_bow_weights(const int* df, int words, int n_views, int* out);
+
 /* ---- caller-supplied keypoints ------------------------------------------------------------
  * Describing points the caller brings along instead of the ones the DoG detector finds (what OpenCV calls
  * useProvidedKeypoints and VLFeat calls frames; the reference has no counterpart).  A record carries what a

@@ -120,6 +120,8 @@ SYMBOLS = [
     "psx_match_pairs_graph", "psx_match_pairs_graph_dev", "psx_match_graph_f32_plan", "psx_match_graph_f32_last",
     "psx_match_pairs_guided_many", "psx_match_pairs_guided_many_dev", "psx_match_pairs_guided_graph", "psx_match_pairs_guided_graph_dev",
     "psx_tracks_graph", "psx_tracks_graph_dev", "psx_tracks_graph_ref", "psx_tracks_plan",
+    "psx_vocab_train_u8", "psx_vocab_train_u8_dev", "psx_vocab_train_u8_ref", "psx_bow_u8", "psx_bow_u8_dev", "psx_bow_u8_ref",
+    "psx_shortlist_views", "psx_shortlist_views_dev", "psx_shortlist_views_ref", "psx_bow_weights",
     "psx_pyramid_plan", "psx_blur_grid_of",
 ]
 
@@ -232,6 +234,25 @@ class TracksPlanInfo(C.Structure):
     """psx_tracks_plan_info: what psx_tracks_graph plans for the sizes of a call"""
     _fields_ = [("nodes", C.c_int), ("records", C.c_int), ("record_blocks", C.c_int), ("sort_bits", C.c_int), ("launches", C.c_int),
                 ("scratch_bytes", C.c_longlong)]
+
+
+SHORTLIST_MUTUAL = 1          # PSX_SHORTLIST_MUTUAL
+VIEW_EDGE_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4")])      # psx_view_edge (8 bytes)
+
+
+class VocabOpts(C.Structure):
+    """psx_vocab_opts: words (2..65536, at most the number of rows) and iterations (>= 1) of the integer k-means"""
+    _fields_ = [("words", C.c_int), ("iterations", C.c_int)]
+
+
+class VocabInfo(C.Structure):
+    """psx_vocab_info: iterations run; changed rows, empty words and inertia of the last assignment"""
+    _fields_ = [("iterations", C.c_int), ("changed", C.c_int), ("empty_words", C.c_int), ("reserved", C.c_int), ("inertia", C.c_ulonglong)]
+
+
+class ShortlistOpts(C.Structure):
+    """psx_shortlist_opts: the k most similar views per view; flags: SHORTLIST_MUTUAL"""
+    _fields_ = [("k", C.c_int), ("flags", C.c_int)]
 
 
 DESCFMT_F32 = 0      # PSX_DESCFMT_F32
@@ -352,6 +373,16 @@ def lib():
                                       C.POINTER(TracksInfo)]
         L.psx_tracks_graph_ref.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.POINTER(TrackOpts), vp, vp, C.c_int, vp, C.c_int, C.POINTER(TracksInfo)]
         L.psx_tracks_plan.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(TracksPlanInfo)]
+        for n in ("psx_vocab_train_u8", "psx_vocab_train_u8_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int, C.POINTER(VocabOpts), vp, C.POINTER(VocabInfo)]
+        L.psx_vocab_train_u8_ref.argtypes = [vp, vp, C.c_int, C.POINTER(VocabOpts), vp, C.POINTER(VocabInfo)]
+        for n in ("psx_bow_u8", "psx_bow_u8_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp]
+        L.psx_bow_u8_ref.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
+        for n in ("psx_shortlist_views", "psx_shortlist_views_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(ShortlistOpts), vp, vp, vp, C.c_int, ip]
+        L.psx_shortlist_views_ref.argtypes = [vp, C.c_int, C.c_int, C.POINTER(ShortlistOpts), vp, vp, vp, C.c_int, ip]
+        L.psx_bow_weights.argtypes = [vp, C.c_int, C.c_int, vp]
         L.psx_pyramid_plan.argtypes = [C.c_int] * 4 + [vp] + [C.c_int] * 3 + [vp, C.c_int, ip]
         L.psx_blur_grid_of.argtypes = [C.c_int] * 3
         _LIB = L
@@ -1578,6 +1609,176 @@ def tracks_plan(lens, edge_counts):
     if rc != 0:
         raise PopSiftError("psx_tracks_plan failed (%d)" % rc)
     return {n: int(getattr(out, n)) for n, _ in TracksPlanInfo._fields_}
+
+
+def _set_table(ptrs, lens):
+    """(pointer array or None, lens array, lens pointer or None, n) of a list of sets given as addresses"""
+    k = len(lens)
+    val = lambda p: p.value if isinstance(p, C.c_void_p) else p
+    arr = (C.c_void_p * max(k, 1))(*[val(p) for p in ptrs])
+    la = np.ascontiguousarray(lens, dtype=np.int32)
+    return (arr if k else None), la, (la.ctypes.data_as(C.c_void_p) if k else None), k
+
+
+def _host_sets(sets):
+    sets = [np.ascontiguousarray(s, dtype=np.uint8).reshape(-1, 128) for s in sets]
+    return sets, [s.ctypes.data for s in sets], [len(s) for s in sets]
+
+
+def _vocab_info(info):
+    return {n: int(getattr(info, n)) for n, _ in VocabInfo._fields_ if n != "reserved"}
+
+
+def _vocab_train(fn, name, ptrs, lens, words, iterations, vocab_ptr):
+    arr, la, lp, k = _set_table(ptrs, lens)
+    o, info = VocabOpts(int(words), int(iterations)), VocabInfo()
+    rc = fn(arr, lp, k, C.byref(o), vocab_ptr, C.byref(info))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    return _vocab_info(info)
+
+
+def vocab_train_u8_ref(sets, words, iterations):
+    """psx_vocab_train_u8_ref: the sequential integer k-means on host arrays, no device.  sets: (n_v,128) uint8 arrays.
+    Returns (vocabulary (words,128) uint8, dict iterations / changed / empty_words / inertia)."""
+    sets, ptrs, lens = _host_sets(sets)
+    vocab = np.zeros((max(int(words), 0), 128), np.uint8)
+    info = _vocab_train(lib().psx_vocab_train_u8_ref, "psx_vocab_train_u8_ref", ptrs, lens, words, iterations, vocab.ctypes.data_as(C.c_void_p))
+    return vocab, info
+
+
+def vocab_train_u8(sets, words, iterations, device=0):
+    """psx_vocab_train_u8 on host arrays (the sets go through device buffers): what vocab_train_u8_ref returns, bit for bit"""
+    L = lib()
+    sets, _, lens = _host_sets(sets)
+    vocab = np.zeros((max(int(words), 0), 128), np.uint8)
+    bufs = []
+    try:
+        ptrs = _to_device(L, device, sets, bufs) if sets else []
+        fn = lambda *a: L.psx_vocab_train_u8(device, *a)
+        return vocab, _vocab_train(fn, "psx_vocab_train_u8", ptrs, lens, words, iterations, vocab.ctypes.data_as(C.c_void_p))
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def vocab_train_u8_dev(ptrs, lens, words, iterations, vocab_ptr, device=0):
+    """psx_vocab_train_u8_dev on DEVICE pointers: the vocabulary (words x 128 bytes, 16-byte aligned) is written in device
+    memory; returns the info dict"""
+    L = lib()
+    fn = lambda *a: L.psx_vocab_train_u8_dev(device, *a)
+    return _vocab_train(fn, "psx_vocab_train_u8_dev", list(ptrs), lens, words, iterations, C.c_void_p(vocab_ptr) if vocab_ptr else None)
+
+
+def _bow(fn, name, vocab_ptr, words, ptrs, lens, hist_ptr, words_ptr):
+    arr, la, lp, k = _set_table(ptrs, lens)
+    rc = fn(vocab_ptr, int(words), arr, lp, k, hist_ptr, words_ptr)
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+
+
+def _bow_host(fn, name, vocab, ptrs, lens, row_words):
+    vocab = np.ascontiguousarray(vocab, dtype=np.uint8).reshape(-1, 128)
+    hist = np.zeros((len(lens), len(vocab)), np.uint32)
+    rw = np.zeros((int(sum(lens)),), np.int32) if row_words else None
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    _bow(fn, name, vocab.ctypes.data_as(C.c_void_p), len(vocab), ptrs, lens, vp(hist), vp(rw))
+    return (hist, rw) if row_words else hist
+
+
+def bow_u8_ref(vocab, sets, row_words=False):
+    """psx_bow_u8_ref: the bags of words of N views on host arrays, no device.  Returns hist (N, words) uint32; with row_words
+    also the word of every row (sum of the lengths, int32)."""
+    sets, ptrs, lens = _host_sets(sets)
+    return _bow_host(lib().psx_bow_u8_ref, "psx_bow_u8_ref", vocab, ptrs, lens, row_words)
+
+
+def bow_u8(vocab, sets, device=0, row_words=False):
+    """psx_bow_u8 on host arrays (the sets go through device buffers): what bow_u8_ref returns, bit for bit, in ONE call"""
+    L = lib()
+    sets, _, lens = _host_sets(sets)
+    bufs = []
+    try:
+        ptrs = _to_device(L, device, sets, bufs) if sets else []
+        fn = lambda *a: L.psx_bow_u8(device, *a)
+        return _bow_host(fn, "psx_bow_u8", vocab, ptrs, lens, row_words)
+    finally:
+        for p in bufs:
+            L.psx_dev_free(device, p)
+
+
+def bow_u8_dev(vocab_ptr, words, ptrs, lens, hist_ptr, words_ptr=0, device=0):
+    """psx_bow_u8_dev on DEVICE pointers: the vocabulary is read and hist (N x words uint32) and, unless 0, the rows' words
+    (int32) are written in device memory"""
+    L = lib()
+    vp = lambda p: C.c_void_p(p) if p else None
+    fn = lambda *a: L.psx_bow_u8_dev(device, *a)
+    _bow(fn, "psx_bow_u8_dev", vp(vocab_ptr), words, list(ptrs), lens, vp(hist_ptr), vp(words_ptr))
+
+
+def shortlist_opts(k, mutual=False):
+    return ShortlistOpts(int(k), SHORTLIST_MUTUAL if mutual else 0)
+
+
+def _shortlist_call(fn, name, hist_ptr, n_views, words, opts, nb_ptr, sc_ptr, edges_ptr, capacity):
+    n = C.c_int(-1)
+    rc = fn(hist_ptr, n_views, words, C.byref(opts), nb_ptr, sc_ptr, edges_ptr, capacity, C.byref(n))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    return n.value
+
+
+def _shortlist_host(fn, name, hist, k, mutual, capacity):
+    """a host form: asks "how many?" unless the capacity is given, then fills arrays of that size"""
+    hist = np.ascontiguousarray(hist, dtype=np.uint32)
+    if hist.ndim != 2:
+        raise ValueError("hist is an (n_views, words) array")
+    N, W = hist.shape
+    o = shortlist_opts(k, mutual)
+    hp = hist.ctypes.data_as(C.c_void_p) if hist.size else None
+    if capacity is None:
+        capacity = _shortlist_call(fn, name, hp, N, W, o, None, None, None, 0)
+    nb = np.zeros((N, int(k)), np.int32)
+    sc = np.zeros((N, int(k)), np.uint32)
+    ed = np.zeros((capacity,), VIEW_EDGE_DTYPE)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    n = _shortlist_call(fn, name, hp, N, W, o, vp(nb), vp(sc), vp(ed), capacity)
+    return {"neighbours": nb, "scores": sc, "edges": ed[:min(n, capacity)], "count": n}
+
+
+def shortlist_views_ref(hist, k, mutual=False, capacity=None):
+    """psx_shortlist_views_ref on a host (n_views, words) uint32 histogram, no device.  Returns a dict: neighbours and scores
+    ((n_views, k), unused entries -1 and 0), edges (VIEW_EDGE_DTYPE, sorted by (left, right), each pair once; .tolist() is the
+    edge list the graph calls take) and count, the total whatever the capacity."""
+    return _shortlist_host(lib().psx_shortlist_views_ref, "psx_shortlist_views_ref", hist, k, mutual, capacity)
+
+
+def shortlist_views(hist, k, mutual=False, device=0, capacity=None):
+    """psx_shortlist_views on a host histogram: the dict of shortlist_views_ref, bit for bit"""
+    L = lib()
+    fn = lambda *a: L.psx_shortlist_views(device, *a)
+    return _shortlist_host(fn, "psx_shortlist_views", hist, k, mutual, capacity)
+
+
+def shortlist_views_dev(hist_ptr, n_views, words, k, nb_ptr, sc_ptr, edges_ptr, capacity, mutual=False, device=0):
+    """psx_shortlist_views_dev on DEVICE pointers (what bow_u8_dev left at hist_ptr): neighbours and scores (n_views x k
+    each, either 0 / None) and the first `capacity` edges are written in device memory; returns the total edge count"""
+    L = lib()
+    vp = lambda p: C.c_void_p(p) if p else None
+    fn = lambda *a: L.psx_shortlist_views_dev(device, *a)
+    return _shortlist_call(fn, "psx_shortlist_views_dev", vp(hist_ptr), n_views, words, shortlist_opts(k, mutual), vp(nb_ptr), vp(sc_ptr),
+                           vp(edges_ptr), capacity)
+
+
+def bow_weights(df, n_views):
+    """psx_bow_weights: the idf weight of every word from its document frequency, int32; host only"""
+    df = np.ascontiguousarray(df, dtype=np.int32).reshape(-1)
+    out = np.zeros_like(df)
+    rc = lib().psx_bow_weights(df.ctypes.data_as(C.c_void_p) if df.size else None, len(df), int(n_views),
+                               out.ctypes.data_as(C.c_void_p) if df.size else None)
+    if rc != 0:
+        raise PopSiftError("psx_bow_weights failed (%d)" % rc)
+    return out
 
 
 def _guided_graph_call(fn, name, device, set_ptrs, xy_ptrs, lens, edges, guides, out_ptr, capacity, ratio, mutual):

@@ -1,6 +1,6 @@
 // match_scratch.h -- what the matcher's translation units share (match.hip, match_guided.hip, match_many.hip,
 // match_many_f32.hip, match_guided_many.hip, match_graph.hip, match_graph_f32.hip, match_guided_graph.hip, ransac.hip, ransac_many.hip,
-// ransac_graph.hip, tracks.hip):
+// ransac_graph.hip, tracks.hip, bow.hip):
 // the layout of a directed result, the per-thread scratch with its named buffers, the runner of the pair join, and the
 // two batched drivers that a star form shares with its edge-list form.
 // Internal to the HIP library.
@@ -101,6 +101,19 @@ enum MatchSlot {
     MS_TRACKS_TOT,       // the compaction's per-workgroup totals (heads, nodes) and their offsets
     MS_TRACKS_STATE,     // the six totals and the bad-record flag
     MS_TRACKS_OUT,       // the host form's labels, track starts and members before they are copied back
+    MS_BOW_TABLES,       // the view shortlist (bow.hip): the views' pointers and row offsets
+    MS_BOW_ROWS,         // the rows of all views gathered into one array
+    MS_BOW_NORMS,        // the rows' norms, then the words'
+    MS_BOW_ASSIGN,       // per row: its word now and its word one iteration ago
+    MS_BOW_SUMS,         // per word: its row count and the 128 byte sums; behind them the 16 bytes that decide the stop
+    MS_BOW_VOCAB,        // the host form's vocabulary on the device
+    MS_BOW_OUT,          // the host form's histogram and row words before they are copied back
+    MS_SL_HIST,          // the host form's uploaded histogram
+    MS_SL_Q,             // df and the weights (W ints each), then the quantised histogram (N x W uint16)
+    MS_SL_SCORE,         // the N x N scores
+    MS_SL_LISTED,        // N x N bytes: is j in the list of i
+    MS_SL_TOT,           // the edge compaction's per-workgroup totals and their offsets
+    MS_SL_OUT,           // the host form's lists and edges before they are copied back
     MS_NBUF
 };
 

@@ -366,6 +366,7 @@ public:
     inline Descriptor* getDescriptors() { return _ori; }
     inline int*        getReverseMap()  { return _rev; }
     inline void        setDevice( int d ) { _device = d; }
+    inline int         getDevice() const  { return _device; }
 };
 
 } // namespace popsift
