@@ -1180,6 +1180,67 @@ int psx_shortlist_views_ref(const unsigned* hist, int n_views, int words, const 
 /* HOST only: out[w] = the weight of a word that df[w] of n_views views contain (the one logarithm of the step) */
 int psx_bow_weights(const int* df, int words, int n_views, int* out);
 
+/* QUERY A DATABASE OF VIEWS: the k stored views most like each of a few new ones.  psx_shortlist_views answers "every view
+ * against every other of one closed collection": when view N + 1 arrives it quantises and scores all N x N again, it stops
+ * at 4096 views (12 index bits, N x N scratch), and both follow from the symmetric form.  Incremental structure-from-motion
+ * and loop closure ask for one ROW: these calls keep the views as rows of q in the caller's HBM, which grow by appending,
+ * and rank n_queries <= 4096 rows against n_db <= 1 048 576 of them.  No n_queries x n_db array goes through HBM.
+ * INTEGRATION.md ("Query a database of views") has the chain with an arriving view and the measured cost.
+ * FORMS as above: host outputs, _dev (neighbours, scores and edges in HBM) and _ref (all on the host, sequential, the
+ * definition; the device forms equal it bit for bit).  d_db_q (n_db x words) and d_query_q (n_queries x words) are DEVICE
+ * arrays of uint16 in the first two forms; weights, db_limit, opts and edge_count are HOST memory in every form.
+ * THE RULE (csrc/hip/bow_rule.h).
+ *   QUANTISE  q[v][w] = floor(hist[v][w] 65535 / n_v), n_v = the row's own sum, 0 for n_v = 0: a view's q depends on nothing
+ *             but its own row, so a database grows by quantising new rows behind the old ones.  df_accum (HOST, words ints,
+ *             may be NULL): the number of these n_views views with hist[v][w] > 0 is ADDED to df_accum[w].  The weights of a
+ *             query are the caller's: psx_bow_weights(df_accum, words, views added so far, out) gives the shortlist's.
+ *   SCORE     score(i, j) = sum_w weights[w] min(qq[i][w], dbq[j][w]), weights in [0, 1023]: below 2^26 for rows that
+ *             psx_bow_quantize* wrote (their q add up to at most 65535); added in unsigned 32 bits in every form.
+ *   LIST      The candidates of query i: the database views j with j < limit_i (db_limit[i], or n_db when db_limit is
+ *             NULL), j != self_base + i (when self_base >= 0: query i IS database view self_base + i), score(i, j) > 0 and
+ *             score(i, j) >= min_score; by (score descending, j ascending), the first k.  neighbours[i][0 .. k) and
+ *             scores[i][0 .. k) (either may be NULL), unused entries -1 and 0; k may exceed n_db.
+ *   EDGES     For i ascending, then in list order, {left = edge_base + i, right = j}: grouped by left, every group a star
+ *             that the _many calls and the four graph calls take unchanged; a caller who appends the query sets behind the
+ *             database's in its set array passes edge_base = n_db.  NOT sorted by right and NOT deduplicated: with
+ *             self_base >= 0 a pair can appear as (a, b) and as (b, a), which the graph calls accept.  *edge_count is always
+ *             the total, the first min(total, edge_capacity) records are written, nothing at or past the capacity is
+ *             touched; capacity 0 with NULL asks "how many?".
+ *   With self_base = 0, db_limit = NULL, the database as its own queries and the weights of psx_bow_weights(df, words, N),
+ *   neighbours and scores are those of psx_shortlist_views.  db_limit[i] = self_base + i is the loop-closure form: every
+ *   view against the views before it.
+ * EMPTY FORMS.  n_queries = 0: no device, *edge_count = 0, nothing else written.  n_db = 0: every entry is written as unused
+ * (the _dev form launches one kernel for that: the caller's arrays must not stay stale), *edge_count = 0.  psx_bow_quantize*
+ * with n_views = 0 touches nothing.
+ * PSX_ERR_INVALID, before any device call and with nothing written (csrc/hip/bow_plan.h, once for all forms): a negative
+ * count; a NULL array that is needed (q arrays, weights, hist, opts, edge_count, plan); words outside [1, 65536]; n_db above
+ * 1 048 576; n_queries above 4096 (psx_bow_quantize*: n_views above 1 048 576); k < 1 or n_queries * k above INT_MAX;
+ * non-zero flags or reserved; self_base < -1 or self_base + n_queries > n_db; a weight outside [0, 1023] or a limit outside
+ * [0, n_db]; a misaligned device pointer (q arrays 2 bytes, ints 4, edges 8); a negative capacity or a NULL edge array with a
+ * positive one; plan.partial_keys above 2^27.
+ * PLAN, on the host: blocks = ceil(n_db / 64), the database blocks of the score grid; keys_per_block = min(k, 64);
+ * partial_keys = n_queries * blocks * keys_per_block 64-bit keys, the block lists between the two kernels; scratch_bytes =
+ * the device scratch of the _dev form called with a neighbours array.  n_queries = 0 or n_db = 0 plans zeros.
+ * LAUNCHES.  psx_shortlist_query*: ONE upload (weights and limits), 5 kernels (the score tiles with their block lists, the
+ * merge, the edge count / scan / write), no clear, ONE synchronisation, whatever n_db, n_queries, words and k are.
+ * psx_bow_quantize_dev: one kernel and ONE synchronisation; with df_accum also one clear before it and one download of
+ * words ints behind it.  Scratch (psx_match_release) and thread safety as for psx_match_u8.  Synchronous. */
+typedef struct psx_query_opts { int k; int flags /* must be 0 */; int self_base /* -1: none */; int edge_base;
+                                unsigned min_score; int reserved /* must be 0 */; } psx_query_opts;
+typedef struct psx_query_plan { int blocks; int keys_per_block; long long partial_keys; long long scratch_bytes; } psx_query_plan;
+int psx_bow_quantize_dev(int device, const unsigned* d_hist, int n_views, int words, unsigned short* d_q, int* df_accum);
+int psx_bow_quantize_ref(const unsigned* hist, int n_views, int words, unsigned short* q, int* df_accum);
+int psx_shortlist_query(int device, const unsigned short* d_db_q, int n_db, const unsigned short* d_query_q, int n_queries, int words,
+                        const int* weights, const int* db_limit, const psx_query_opts* opts,
+                        int* host_neighbours, unsigned* host_scores, psx_view_edge* host_edges, int edge_capacity, int* edge_count);
+int psx_shortlist_query_dev(int device, const unsigned short* d_db_q, int n_db, const unsigned short* d_query_q, int n_queries, int words,
+                            const int* weights, const int* db_limit, const psx_query_opts* opts,
+                            int* d_neighbours, unsigned* d_scores, psx_view_edge* d_edges, int edge_capacity, int* edge_count);
+int psx_shortlist_query_ref(const unsigned short* db_q, int n_db, const unsigned short* query_q, int n_queries, int words,
+                            const int* weights, const int* db_limit, const psx_query_opts* opts,
+                            int* neighbours, unsigned* scores, psx_view_edge* edges, int edge_capacity, int* edge_count);
+int psx_shortlist_query_plan(int n_db, int n_queries, int words, int k, psx_query_plan* plan);
+
 /* ---- caller-supplied keypoints ------------------------------------------------------------
  * Describing points the caller brings along instead of the ones the DoG detector finds (what OpenCV calls
  * useProvidedKeypoints and VLFeat calls frames; the reference has no counterpart).  A record carries what a

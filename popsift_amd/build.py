@@ -25,7 +25,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
 
-HIP_SOURCES = ["pyramid.hip", "pyramid_tile.hip", "pyramid_alt.hip", "pyramid_fixed.hip", "pyramid_interp.hip", "extrema.hip", "orient_desc.hip", "gridfilter.hip", "keypoints.hip", "match.hip", "match_many.hip", "match_many_f32.hip", "match_graph.hip", "match_graph_f32.hip", "match_guided.hip", "match_guided_many.hip", "match_guided_graph.hip", "ransac.hip", "ransac_many.hip", "ransac_graph.hip", "tracks.hip", "bow.hip", "util.hip", "api.hip"]
+HIP_SOURCES = ["pyramid.hip", "pyramid_tile.hip", "pyramid_alt.hip", "pyramid_fixed.hip", "pyramid_interp.hip", "extrema.hip", "orient_desc.hip", "gridfilter.hip", "keypoints.hip", "match.hip", "match_many.hip", "match_many_f32.hip", "match_graph.hip", "match_graph_f32.hip", "match_guided.hip", "match_guided_many.hip", "match_guided_graph.hip", "ransac.hip", "ransac_many.hip", "ransac_graph.hip", "tracks.hip", "bow.hip", "bow_query.hip", "util.hip", "api.hip"]
 HIP_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     # no implicit fused multiply-add: the arithmetic order is part of the parity contract

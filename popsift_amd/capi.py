@@ -122,6 +122,8 @@ SYMBOLS = [
     "psx_tracks_graph", "psx_tracks_graph_dev", "psx_tracks_graph_ref", "psx_tracks_plan",
     "psx_vocab_train_u8", "psx_vocab_train_u8_dev", "psx_vocab_train_u8_ref", "psx_bow_u8", "psx_bow_u8_dev", "psx_bow_u8_ref",
     "psx_shortlist_views", "psx_shortlist_views_dev", "psx_shortlist_views_ref", "psx_bow_weights",
+    "psx_bow_quantize_dev", "psx_bow_quantize_ref", "psx_shortlist_query", "psx_shortlist_query_dev", "psx_shortlist_query_ref",
+    "psx_shortlist_query_plan",
     "psx_pyramid_plan", "psx_blur_grid_of",
 ]
 
@@ -255,6 +257,22 @@ class ShortlistOpts(C.Structure):
     _fields_ = [("k", C.c_int), ("flags", C.c_int)]
 
 
+QUERY_MAX_VIEWS = 1 << 20     # PSX_QUERY_MAX_VIEWS
+QUERY_MAX_WEIGHT = 1023       # PSX_QUERY_MAX_WEIGHT
+
+
+class QueryOpts(C.Structure):
+    """psx_query_opts: the k most similar stored views per query; flags and reserved must be 0; self_base >= 0: query i IS
+    stored view self_base + i (-1: none); the left of query i's edges is edge_base + i; min_score: the least score listed"""
+    _fields_ = [("k", C.c_int), ("flags", C.c_int), ("self_base", C.c_int), ("edge_base", C.c_int), ("min_score", C.c_uint),
+                ("reserved", C.c_int)]
+
+
+class QueryPlan(C.Structure):
+    """psx_query_plan: database blocks of the score grid, keys per block list, keys between the two kernels, device scratch"""
+    _fields_ = [("blocks", C.c_int), ("keys_per_block", C.c_int), ("partial_keys", C.c_longlong), ("scratch_bytes", C.c_longlong)]
+
+
 DESCFMT_F32 = 0      # PSX_DESCFMT_F32
 DESCFMT_U8 = 1       # PSX_DESCFMT_U8
 
@@ -383,6 +401,12 @@ def lib():
             getattr(L, n).argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(ShortlistOpts), vp, vp, vp, C.c_int, ip]
         L.psx_shortlist_views_ref.argtypes = [vp, C.c_int, C.c_int, C.POINTER(ShortlistOpts), vp, vp, vp, C.c_int, ip]
         L.psx_bow_weights.argtypes = [vp, C.c_int, C.c_int, vp]
+        L.psx_bow_quantize_dev.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, vp]
+        L.psx_bow_quantize_ref.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+        for n in ("psx_shortlist_query", "psx_shortlist_query_dev"):
+            getattr(L, n).argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.POINTER(QueryOpts), vp, vp, vp, C.c_int, ip]
+        L.psx_shortlist_query_ref.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.POINTER(QueryOpts), vp, vp, vp, C.c_int, ip]
+        L.psx_shortlist_query_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(QueryPlan)]
         L.psx_pyramid_plan.argtypes = [C.c_int] * 4 + [vp] + [C.c_int] * 3 + [vp, C.c_int, ip]
         L.psx_blur_grid_of.argtypes = [C.c_int] * 3
         _LIB = L
@@ -1779,6 +1803,117 @@ def bow_weights(df, n_views):
     if rc != 0:
         raise PopSiftError("psx_bow_weights failed (%d)" % rc)
     return out
+
+
+def bow_quantize_ref(hist, df_accum=None):
+    """psx_bow_quantize_ref: q (n_views, words) uint16 of a host (n_views, words) uint32 histogram, every row by its own sum;
+    df_accum (words int32, or None) is added to IN PLACE"""
+    hist = np.ascontiguousarray(hist, dtype=np.uint32)
+    if hist.ndim != 2:
+        raise ValueError("hist is an (n_views, words) array")
+    q = np.zeros(hist.shape, np.uint16)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    rc = lib().psx_bow_quantize_ref(vp(hist), hist.shape[0], hist.shape[1], vp(q), _df_accum(df_accum, hist.shape[1]))
+    if rc != 0:
+        raise PopSiftError("psx_bow_quantize_ref failed (%d)" % rc)
+    return q
+
+
+def _df_accum(df_accum, words):
+    if df_accum is None:
+        return None
+    if not (isinstance(df_accum, np.ndarray) and df_accum.dtype == np.int32 and df_accum.flags.c_contiguous and df_accum.size == words):
+        raise ValueError("df_accum is a contiguous int32 array of `words` entries")
+    return df_accum.ctypes.data_as(C.c_void_p)
+
+
+def bow_quantize_dev(hist_ptr, n_views, words, q_ptr, df_accum=None, device=0):
+    """psx_bow_quantize_dev on DEVICE pointers: hist (n_views x words uint32) is read, q (uint16) written -- at the end of a
+    database's rows to grow it; df_accum (HOST int32 array of `words` entries, or None) is added to in place"""
+    vp = lambda p: C.c_void_p(p) if p else None
+    rc = lib().psx_bow_quantize_dev(device, vp(hist_ptr), int(n_views), int(words), vp(q_ptr), _df_accum(df_accum, words))
+    if rc != 0:
+        raise PopSiftError("psx_bow_quantize_dev failed (%d)" % rc)
+
+
+def query_opts(k, self_base=-1, edge_base=0, min_score=0):
+    return QueryOpts(int(k), 0, int(self_base), int(edge_base), int(min_score), 0)
+
+
+def _query_tables(weights, db_limit, n_queries):
+    w = np.ascontiguousarray(weights, dtype=np.int32).reshape(-1)
+    lim = None if db_limit is None else np.ascontiguousarray(db_limit, dtype=np.int32).reshape(-1)
+    if lim is not None and len(lim) != n_queries:
+        raise ValueError("db_limit has one entry per query")
+    return w, lim
+
+
+def _query_call(fn, name, db_ptr, n_db, q_ptr, n_queries, words, weights, db_limit, opts, nb_ptr, sc_ptr, edges_ptr, capacity):
+    """one query call on prepared pointers: the total edge count"""
+    w, lim = _query_tables(weights, db_limit, n_queries)
+    if len(w) != words:
+        raise ValueError("one weight per word")
+    n = C.c_int(-1)
+    rc = fn(db_ptr, int(n_db), q_ptr, int(n_queries), int(words), w.ctypes.data_as(C.c_void_p),
+            lim.ctypes.data_as(C.c_void_p) if lim is not None and lim.size else None, C.byref(opts), nb_ptr, sc_ptr, edges_ptr, int(capacity),
+            C.byref(n))
+    if rc != 0:
+        raise PopSiftError("%s failed (%d)" % (name, rc))
+    return n.value
+
+
+def _query_host(fn, name, db_ptr, n_db, q_ptr, n_queries, words, weights, db_limit, opts, capacity):
+    """a form with host outputs: asks "how many?" unless the capacity is given, then fills arrays of that size"""
+    if capacity is None:
+        capacity = _query_call(fn, name, db_ptr, n_db, q_ptr, n_queries, words, weights, db_limit, opts, None, None, None, 0)
+    nb = np.zeros((n_queries, opts.k), np.int32)
+    sc = np.zeros((n_queries, opts.k), np.uint32)
+    ed = np.zeros((capacity,), VIEW_EDGE_DTYPE)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    n = _query_call(fn, name, db_ptr, n_db, q_ptr, n_queries, words, weights, db_limit, opts, vp(nb), vp(sc), vp(ed), capacity)
+    return {"neighbours": nb, "scores": sc, "edges": ed[:min(n, capacity)], "count": n}
+
+
+def shortlist_query_ref(db_q, query_q, weights, k, db_limit=None, self_base=-1, edge_base=0, min_score=0, capacity=None):
+    """psx_shortlist_query_ref on host (n, words) uint16 arrays, no device.  Returns a dict: neighbours and scores ((n_queries,
+    k), unused entries -1 and 0), edges (VIEW_EDGE_DTYPE: {edge_base + i, neighbour}, grouped by left in list order) and count,
+    the total whatever the capacity."""
+    db_q, query_q = np.ascontiguousarray(db_q, dtype=np.uint16), np.ascontiguousarray(query_q, dtype=np.uint16)
+    if db_q.ndim != 2 or query_q.ndim != 2 or db_q.shape[1] != query_q.shape[1]:
+        raise ValueError("db_q and query_q are (n, words) arrays of one width")
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    return _query_host(lib().psx_shortlist_query_ref, "psx_shortlist_query_ref", vp(db_q), len(db_q), vp(query_q), len(query_q), db_q.shape[1],
+                       weights, db_limit, query_opts(k, self_base, edge_base, min_score), capacity)
+
+
+def shortlist_query(db_ptr, n_db, query_ptr, n_queries, words, weights, k, db_limit=None, self_base=-1, edge_base=0, min_score=0,
+                    device=0, capacity=None):
+    """psx_shortlist_query: the q arrays are DEVICE pointers, the dict of shortlist_query_ref comes back in host arrays"""
+    L = lib()
+    vp = lambda p: C.c_void_p(p) if p else None
+    fn = lambda *a: L.psx_shortlist_query(device, *a)
+    return _query_host(fn, "psx_shortlist_query", vp(db_ptr), n_db, vp(query_ptr), n_queries, words, weights, db_limit,
+                       query_opts(k, self_base, edge_base, min_score), capacity)
+
+
+def shortlist_query_dev(db_ptr, n_db, query_ptr, n_queries, words, weights, k, nb_ptr, sc_ptr, edges_ptr, capacity, db_limit=None,
+                        self_base=-1, edge_base=0, min_score=0, device=0):
+    """psx_shortlist_query_dev on DEVICE pointers: neighbours and scores (n_queries x k each, either 0 / None) and the first
+    `capacity` edges are written in device memory; returns the total edge count"""
+    L = lib()
+    vp = lambda p: C.c_void_p(p) if p else None
+    fn = lambda *a: L.psx_shortlist_query_dev(device, *a)
+    return _query_call(fn, "psx_shortlist_query_dev", vp(db_ptr), n_db, vp(query_ptr), n_queries, words, weights, db_limit,
+                       query_opts(k, self_base, edge_base, min_score), vp(nb_ptr), vp(sc_ptr), vp(edges_ptr), capacity)
+
+
+def shortlist_query_plan(n_db, n_queries, words, k):
+    """psx_shortlist_query_plan: dict blocks / keys_per_block / partial_keys / scratch_bytes of a query of these sizes; host only"""
+    out = QueryPlan()
+    rc = lib().psx_shortlist_query_plan(int(n_db), int(n_queries), int(words), int(k), C.byref(out))
+    if rc != 0:
+        raise PopSiftError("psx_shortlist_query_plan failed (%d)" % rc)
+    return {n: int(getattr(out, n)) for n, _ in QueryPlan._fields_}
 
 
 def _guided_graph_call(fn, name, device, set_ptrs, xy_ptrs, lens, edges, guides, out_ptr, capacity, ratio, mutual):

@@ -1,8 +1,9 @@
 // bow_plan.h -- the host side of the view shortlist (psx_vocab_train_u8*, psx_bow_u8*, psx_shortlist_views*, psx_bow_weights;
-// include/popsift_hip.h): the argument checks every form shares, the empty forms, and the host references.
+// include/popsift_hip.h) and, at the end, of the database query (psx_bow_quantize*, psx_shortlist_query*,
+// psx_shortlist_query_plan): the argument checks every form shares, the empty forms, and the host references.
 //
-// Plain C++14, no HIP: bow.hip checks its arguments with these functions, and a stand-alone program can include the header
-// alone (tests/cpp/shortlist_san.cpp).  The rule is bow_rule.h; the references below are sequential and are the definition
+// Plain C++14, no HIP: bow.hip and bow_query.hip check their arguments with these functions, and a stand-alone program can
+// include the header alone (tests/cpp/shortlist_san.cpp, tests/cpp/query_san.cpp).  The rule is bow_rule.h; the references below are sequential and are the definition
 // of the results.
 #pragma once
 
@@ -201,6 +202,139 @@ inline int psx_shortlist_host(const unsigned* hist, int n_views, int words, cons
             if (count < edge_capacity) edges[count] = psx_view_edge{a, b};
             count++;
         }
+    *edge_count = count;
+    return PSX_OK;
+}
+
+// ---- query a database of views (psx_bow_quantize*, psx_shortlist_query*, psx_shortlist_query_plan) ---------------------
+
+#include <cstdint>
+
+inline bool psx_aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+inline size_t psx_pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// psx_bow_quantize*: device_arrays = the _dev form, whose pointers are looked at for alignment too
+inline bool psx_bow_quantize_args_ok(const unsigned* hist, int n_views, int words, const unsigned short* q, bool device_arrays)
+{
+    if (n_views < 0 || n_views > PSX_QUERY_MAX_VIEWS || words < 1 || words > PSX_BOW_MAX_WORDS) return false;
+    if (n_views > 0 && (hist == nullptr || q == nullptr)) return false;
+    return !device_arrays || (psx_aligned_to(hist, 4) && psx_aligned_to(q, 2));
+}
+
+// the sizes alone: what psx_shortlist_query_plan refuses, and every query call with it
+inline bool psx_query_sizes_ok(int n_db, int n_queries, int words, int k)
+{
+    if (n_db < 0 || n_queries < 0 || n_db > PSX_QUERY_MAX_VIEWS || n_queries > PSX_QUERY_MAX_QUERIES) return false;
+    if (words < 1 || words > PSX_BOW_MAX_WORDS || k < 1) return false;
+    return (long long)n_queries * k <= 0x7fffffffLL;                    // the list arrays are indexed with ints
+}
+
+// the edge compaction's workgroups: one lane per list slot
+inline long long psx_query_slot_blocks(int n_queries, int k) { return ((long long)n_queries * k + 255) / 256; }
+
+// the plan of sizes that psx_query_sizes_ok accepts; false where the block lists would pass PSX_QUERY_MAX_PARTIAL_KEYS
+inline bool psx_query_plan_make(int n_db, int n_queries, int words, int k, psx_query_plan* plan)
+{
+    psx_query_plan p = {0, 0, 0, 0};
+    if (n_db > 0 && n_queries > 0) {
+        p.blocks = (n_db + PSX_QUERY_TILE - 1) / PSX_QUERY_TILE;
+        p.keys_per_block = k < PSX_QUERY_TILE ? k : PSX_QUERY_TILE;
+        p.partial_keys = (long long)n_queries * p.blocks * p.keys_per_block;
+        if (p.partial_keys > PSX_QUERY_MAX_PARTIAL_KEYS) return false;
+        // the weights and the limits, the block lists, the compaction's totals, offsets and total
+        p.scratch_bytes = (long long)(psx_pad16(4 * (size_t)words) + psx_pad16(4 * (size_t)n_queries)) + 8 * p.partial_keys +
+                          4 * (2 * psx_query_slot_blocks(n_queries, k) + 2);
+    }
+    *plan = p;
+    return true;
+}
+
+// psx_shortlist_query_plan
+inline int psx_query_plan_host(int n_db, int n_queries, int words, int k, psx_query_plan* plan)
+{
+    psx_query_plan p;
+    if (plan == nullptr || !psx_query_sizes_ok(n_db, n_queries, words, k) || !psx_query_plan_make(n_db, n_queries, words, k, &p))
+        return PSX_ERR_INVALID;
+    *plan = p;
+    return PSX_OK;
+}
+
+// every check of a query call; device_q: the q arrays are device memory (alignment is all that is looked at),
+// device_out: so are neighbours, scores and edges
+inline bool psx_query_args_ok(const unsigned short* db_q, int n_db, const unsigned short* query_q, int n_queries, int words, const int* weights,
+                              const int* db_limit, const psx_query_opts* opts, const int* neighbours, const unsigned* scores,
+                              const psx_view_edge* edges, int edge_capacity, const int* edge_count, bool device_q, bool device_out,
+                              psx_query_plan* plan)
+{
+    if (!psx_query_opts_ok(opts) || !psx_query_sizes_ok(n_db, n_queries, words, opts->k)) return false;
+    if (weights == nullptr || (n_db > 0 && db_q == nullptr) || (n_queries > 0 && query_q == nullptr)) return false;
+    if (edge_count == nullptr || edge_capacity < 0 || (edge_capacity > 0 && edges == nullptr)) return false;
+    if (opts->self_base >= 0 && (long long)opts->self_base + n_queries > n_db) return false;
+    for (int w = 0; w < words; w++)
+        if (weights[w] < 0 || weights[w] > PSX_QUERY_MAX_WEIGHT) return false;
+    if (db_limit != nullptr)
+        for (int i = 0; i < n_queries; i++)
+            if (db_limit[i] < 0 || db_limit[i] > n_db) return false;
+    if (device_q && (!psx_aligned_to(db_q, 2) || !psx_aligned_to(query_q, 2))) return false;
+    if (device_out && (!psx_aligned_to(neighbours, 4) || !psx_aligned_to(scores, 4) || !psx_aligned_to(edges, 8))) return false;
+    return psx_query_plan_make(n_db, n_queries, words, opts->k, plan);
+}
+
+// psx_bow_quantize_ref
+inline int psx_bow_quantize_host(const unsigned* hist, int n_views, int words, unsigned short* q, int* df_accum)
+{
+    if (!psx_bow_quantize_args_ok(hist, n_views, words, q, false)) return PSX_ERR_INVALID;
+    for (int v = 0; v < n_views; v++) {
+        const unsigned* h = hist + (size_t)v * (size_t)words;
+        unsigned long long n = 0;
+        for (int w = 0; w < words; w++) n += h[w];
+        for (int w = 0; w < words; w++) {
+            q[(size_t)v * (size_t)words + (size_t)w] = (unsigned short)psx_bow_quant(h[w], n);
+            if (df_accum != nullptr && h[w] > 0) df_accum[w]++;
+        }
+    }
+    return PSX_OK;
+}
+
+// psx_shortlist_query_ref
+inline int psx_shortlist_query_host(const unsigned short* db_q, int n_db, const unsigned short* query_q, int n_queries, int words,
+                                    const int* weights, const int* db_limit, const psx_query_opts* opts, int* neighbours, unsigned* scores,
+                                    psx_view_edge* edges, int edge_capacity, int* edge_count)
+{
+    psx_query_plan plan;
+    if (!psx_query_args_ok(db_q, n_db, query_q, n_queries, words, weights, db_limit, opts, neighbours, scores, edges, edge_capacity, edge_count,
+                           false, false, &plan))
+        return PSX_ERR_INVALID;
+    const int k = opts->k;
+    const size_t W = (size_t)words;
+    std::vector<unsigned long long> keys;
+    try { keys.resize((size_t)n_db); } catch (const std::bad_alloc&) { return PSX_ERR_NOMEM; }
+    psx_shortlist_none(n_queries, k, neighbours, scores);
+    int count = 0;
+    for (int i = 0; i < n_queries; i++) {
+        const unsigned short* a = query_q + (size_t)i * W;
+        const int limit = db_limit != nullptr ? db_limit[i] : n_db, self = opts->self_base >= 0 ? opts->self_base + i : -1;
+        for (int j = 0; j < n_db; j++) {
+            const unsigned short* b = db_q + (size_t)j * W;
+            unsigned s = 0;
+            if (j < limit && j != self)
+                for (size_t w = 0; w < W; w++) s += psx_bow_term((unsigned)weights[w], a[w], b[w]);
+            keys[(size_t)j] = psx_query_candidate(s, j, limit, self, opts->min_score) ? psx_query_key(s, j) : 0ULL;
+        }
+        unsigned long long last = ~0ULL;
+        for (int r = 0; r < k; r++) {                                    // the largest key below the last one taken
+            unsigned long long best = 0;
+            for (int j = 0; j < n_db; j++)
+                if (keys[(size_t)j] < last && keys[(size_t)j] > best) best = keys[(size_t)j];
+            if (best == 0) break;
+            const int j = psx_query_key_view(best);
+            if (neighbours != nullptr) neighbours[(size_t)i * k + r] = j;
+            if (scores != nullptr) scores[(size_t)i * k + r] = psx_query_key_score(best);
+            if (count < edge_capacity) edges[count] = psx_view_edge{opts->edge_base + i, j};
+            count++;
+            last = best;
+        }
+    }
     *edge_count = count;
     return PSX_OK;
 }

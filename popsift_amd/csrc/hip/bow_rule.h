@@ -1,6 +1,7 @@
-// bow_rule.h -- the rules of the view shortlist (psx_vocab_train_u8*, psx_bow_u8*, psx_shortlist_views*; include/popsift_hip.h).
+// bow_rule.h -- the rules of the view shortlist (psx_vocab_train_u8*, psx_bow_u8*, psx_shortlist_views*; include/popsift_hip.h)
+// and of the database query (psx_bow_quantize*, psx_shortlist_query*; QUERY below).
 //
-// ONE set of inline functions, compiled for the host (the references, bow_plan.h) and for the device (bow.hip): the two
+// ONE set of inline functions, compiled for the host (the references, bow_plan.h) and for the device (bow.hip, bow_query.hip): the two
 // cannot drift apart.  Integers only; the one logarithm of the step (psx_bow_weight) is host code and is never compiled
 // for the device.  No HIP header is needed when g++ compiles this file.
 //
@@ -87,6 +88,42 @@ PSX_BOW_HD inline int psx_shortlist_key_view(unsigned long long key) { return PS
 PSX_BOW_HD inline bool psx_shortlist_edge_keep(bool a_lists_b, bool b_lists_a, int flags)
 {
     return (flags & PSX_SHORTLIST_MUTUAL) != 0 ? (a_lists_b && b_lists_a) : (a_lists_b || b_lists_a);
+}
+
+// QUERY (psx_shortlist_query*): n_queries new views against n_db stored ones, both as rows of q (psx_bow_quantize*), under
+// weights the caller brings.  Nothing of the symmetric form is needed: no N x N matrix, 20 index bits instead of 12.
+// CANDIDATES of query i: the database views j with j < limit_i (db_limit[i], or n_db), j != self_base + i (when
+//          self_base >= 0), score(i, j) = sum_w weight[w] min(qq[i][w], dbq[j][w]) > 0 and score(i, j) >= min_score.
+// LIST     of query i: the candidates by (score descending, j ascending) -- the descending order of psx_query_key -- the
+//          first k; unused entries -1 and 0; k may exceed n_db.
+// EDGES.   For i ascending, then in list order, {edge_base + i, j}: grouped by left, NOT sorted by right and NOT
+//          deduplicated (with self_base >= 0 a pair can appear as (a, b) and as (b, a)).
+// The weights are at most PSX_QUERY_MAX_WEIGHT and the q of a row written by psx_bow_quantize* add up to at most 65535, so a
+// score stays below 2^26 and a key below 2^46.  Scores are added in unsigned 32 bits on both sides, so rows of another
+// origin still give the device what the reference gives.
+constexpr int PSX_QUERY_MAX_VIEWS = 1 << 20;           // 20 index bits in psx_query_key
+constexpr int PSX_QUERY_MAX_WEIGHT = 1023;
+constexpr int PSX_QUERY_MAX_QUERIES = 4096;
+constexpr long long PSX_QUERY_MAX_PARTIAL_KEYS = 1LL << 27;   // 1 GiB of block lists
+constexpr int PSX_QUERY_TILE = 64;                     // views per side of a score workgroup: the block of the partial lists
+
+PSX_BOW_HD inline bool psx_query_opts_ok(const psx_query_opts* o)
+{
+    return o != nullptr && o->k >= 1 && o->flags == 0 && o->reserved == 0 && o->self_base >= -1;
+}
+
+// larger key = earlier in a query's list; 0 is no candidate
+PSX_BOW_HD inline unsigned long long psx_query_key(unsigned score, int j)
+{
+    return ((unsigned long long)score << 20) | (unsigned long long)(PSX_QUERY_MAX_VIEWS - 1 - j);
+}
+PSX_BOW_HD inline unsigned psx_query_key_score(unsigned long long key) { return (unsigned)(key >> 20); }
+PSX_BOW_HD inline int psx_query_key_view(unsigned long long key) { return PSX_QUERY_MAX_VIEWS - 1 - (int)(key & 0xfffffULL); }
+
+// is database view j, with this score, a candidate of the query whose own database index is `self` (-1: none)?
+PSX_BOW_HD inline bool psx_query_candidate(unsigned score, int j, int limit, int self, unsigned min_score)
+{
+    return j < limit && j != self && score > 0u && score >= min_score;
 }
 
 #include <cmath>

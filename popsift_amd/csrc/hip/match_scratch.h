@@ -1,6 +1,6 @@
 // match_scratch.h -- what the matcher's translation units share (match.hip, match_guided.hip, match_many.hip,
 // match_many_f32.hip, match_guided_many.hip, match_graph.hip, match_graph_f32.hip, match_guided_graph.hip, ransac.hip, ransac_many.hip,
-// ransac_graph.hip, tracks.hip, bow.hip):
+// ransac_graph.hip, tracks.hip, bow.hip, bow_query.hip):
 // the layout of a directed result, the per-thread scratch with its named buffers, the runner of the pair join, and the
 // two batched drivers that a star form shares with its edge-list form.
 // Internal to the HIP library.
@@ -114,6 +114,11 @@ enum MatchSlot {
     MS_SL_LISTED,        // N x N bytes: is j in the list of i
     MS_SL_TOT,           // the edge compaction's per-workgroup totals and their offsets
     MS_SL_OUT,           // the host form's lists and edges before they are copied back
+    MS_SLQ_DF,           // the database query (bow_query.hip): psx_bow_quantize_dev's df counters
+    MS_SLQ_TABLES,       // the weights (W ints), then the queries' limits
+    MS_SLQ_PARTIAL,      // the block lists: n_queries x blocks x min(k, 64) keys
+    MS_SLQ_TOT,          // the edge compaction's per-workgroup totals, their offsets and the total
+    MS_SLQ_OUT,          // the host form's lists and edges before they are copied back; the neighbours of a _dev call without that array
     MS_NBUF
 };
 

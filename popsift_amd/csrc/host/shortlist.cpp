@@ -1,5 +1,7 @@
-/* popsift::Vocabulary (popsift/shortlist.h) over psx_vocab_train_u8, psx_bow_u8 and psx_shortlist_views. */
+/* popsift::Vocabulary and popsift::ViewDatabase (popsift/shortlist.h) over psx_vocab_train_u8, psx_bow_u8, psx_shortlist_views,
+ * psx_bow_quantize_dev and psx_shortlist_query. */
 #include <popsift/shortlist.h>
+#include <popsift/vocabulary_file.h>
 #include <popsift_hip.h>
 
 #include <sstream>
@@ -118,6 +120,140 @@ Shortlist Vocabulary::shortlist( const BagsOfWords& bags, int k, bool mutual, in
     s.edges.resize( (size_t)count );
     for( int e = 0; e < count; e++ ) { s.edges[(size_t)e].left = edges[(size_t)e].left; s.edges[(size_t)e].right = edges[(size_t)e].right; }
     return s;
+}
+
+void Vocabulary::save( const std::string& path ) const
+{
+    if( _words.empty() ) SHORTLIST_FAIL( "Vocabulary::save: no vocabulary" );
+    vocabulary_file::write( path, _words.data(), (unsigned)wordCount() );
+}
+
+Vocabulary Vocabulary::load( const std::string& path )
+{
+    Vocabulary v;
+    v._words = vocabulary_file::read( path );
+    return v;
+}
+
+void Vocabulary::assign( const unsigned char* bytes, int words )
+{
+    if( bytes == nullptr || words < 2 || words > 65536 ) SHORTLIST_FAIL( "Vocabulary::assign: invalid arguments" );
+    _words.assign( bytes, bytes + (size_t)words * 128 );
+    _info = VocabularyInfo();
+}
+
+std::vector<std::pair<int,int>> QueryResult::pairs( ) const
+{
+    std::vector<std::pair<int,int>> out;
+    out.reserve( edges.size() );
+    for( const ViewEdge& e : edges ) out.emplace_back( e.left, e.right );
+    return out;
+}
+
+namespace {
+
+// a device buffer that lives as long as this object
+struct DevBuf
+{
+    int   device;
+    void* p = nullptr;
+    DevBuf( const char* who, int dev, size_t bytes ) : device( dev )
+    {
+        if( psx_dev_alloc( dev, bytes, &p ) != PSX_OK ) SHORTLIST_FAIL( std::string( who ) + ": out of device memory" );
+    }
+    ~DevBuf( ) { psx_dev_free( device, p ); }
+    DevBuf( const DevBuf& ) = delete;
+    DevBuf& operator=( const DevBuf& ) = delete;
+};
+
+void check( const char* who, const char* call, int rc )
+{
+    if( rc == PSX_OK ) return;
+    std::ostringstream m;
+    m << who << ": " << call << " failed (" << rc << ")";
+    SHORTLIST_FAIL( m.str() );
+}
+
+} // namespace
+
+ViewDatabase::ViewDatabase( const Vocabulary& vocabulary, int device, int capacity )
+    : _voc( vocabulary ), _device( device ), _capacity( capacity )
+{
+    const char* who = "ViewDatabase";
+    if( _voc.wordCount() < 1 ) SHORTLIST_FAIL( std::string( who ) + ": no vocabulary" );
+    if( capacity < 1 || capacity > ( 1 << 20 ) ) SHORTLIST_FAIL( std::string( who ) + ": capacity outside [1, 1048576]" );
+    _df.assign( (size_t)_voc.wordCount(), 0 );
+    if( psx_dev_alloc( device, (size_t)capacity * _voc.wordCount() * 2, &_q ) != PSX_OK ) SHORTLIST_FAIL( std::string( who ) + ": out of device memory" );
+}
+
+ViewDatabase::~ViewDatabase( ) { if( _q ) psx_dev_free( _device, _q ); }
+
+std::vector<int> ViewDatabase::weights( ) const
+{
+    std::vector<int> w( _df.size(), 0 );
+    if( _size > 0 ) check( "ViewDatabase::weights", "psx_bow_weights", psx_bow_weights( _df.data(), (int)_df.size(), _size, w.data() ) );
+    return w;
+}
+
+int ViewDatabase::add( const std::vector<FeaturesDev*>& views )
+{
+    const char* who = "ViewDatabase::add";
+    const int n = (int)views.size(), W = _voc.wordCount();
+    if( n > _capacity - _size ) SHORTLIST_FAIL( std::string( who ) + ": capacity exceeded" );
+    if( n == 0 ) return _size;
+    const BagsOfWords bags = _voc.bagOfWords( views );
+    DevBuf hist( who, _device, bags.counts.size() * 4 );
+    check( who, "psx_dev_write", psx_dev_write( _device, hist.p, bags.counts.data(), bags.counts.size() * 4 ) );
+    std::vector<int> df = _df;                             // a failing call leaves the database as it was
+    check( who, "psx_bow_quantize_dev", psx_bow_quantize_dev( _device, (const unsigned*)hist.p, n, W, (unsigned short*)_q + (size_t)_size * W, df.data() ) );
+    _df.swap( df );
+    const int first = _size;
+    _size += n;
+    return first;
+}
+
+QueryResult ViewDatabase::run( const void* d_query_q, int n, int k, unsigned min_score, int self_base, const int* limits, int edge_base ) const
+{
+    const char* who = "ViewDatabase::query";
+    QueryResult r;
+    r.k = k;
+    r.edge_base = edge_base;
+    r.neighbours.assign( (size_t)n * k, -1 );
+    r.scores.assign( (size_t)n * k, 0u );
+    if( n == 0 ) return r;
+    const std::vector<int> w = weights();
+    std::vector<psx_view_edge> edges( (size_t)n * ( k < _size ? k : _size ) );                        // no more can exist
+    psx_query_opts o = { k, 0, self_base, edge_base, min_score, 0 };
+    int count = 0;
+    check( who, "psx_shortlist_query", psx_shortlist_query( _device, (const unsigned short*)_q, _size, (const unsigned short*)d_query_q, n,
+                                                            _voc.wordCount(), w.data(), limits, &o, r.neighbours.data(), r.scores.data(),
+                                                            edges.empty() ? nullptr : edges.data(), (int)edges.size(), &count ) );
+    r.edges.resize( (size_t)count );
+    for( int e = 0; e < count; e++ ) { r.edges[(size_t)e].left = edges[(size_t)e].left; r.edges[(size_t)e].right = edges[(size_t)e].right; }
+    return r;
+}
+
+QueryResult ViewDatabase::query( const std::vector<FeaturesDev*>& views, int k, unsigned min_score ) const
+{
+    const char* who = "ViewDatabase::query";
+    const int n = (int)views.size(), W = _voc.wordCount();
+    if( k < 1 || n > 4096 || (long long)n * k > 0x7fffffffLL ) SHORTLIST_FAIL( std::string( who ) + ": invalid arguments" );
+    if( n == 0 ) return run( nullptr, 0, k, min_score, -1, nullptr, _size );
+    const BagsOfWords bags = _voc.bagOfWords( views );
+    DevBuf hist( who, _device, bags.counts.size() * 4 ), q( who, _device, bags.counts.size() * 2 );
+    check( who, "psx_dev_write", psx_dev_write( _device, hist.p, bags.counts.data(), bags.counts.size() * 4 ) );
+    check( who, "psx_bow_quantize_dev", psx_bow_quantize_dev( _device, (const unsigned*)hist.p, n, W, (unsigned short*)q.p, nullptr ) );
+    return run( q.p, n, k, min_score, -1, nullptr, _size );
+}
+
+QueryResult ViewDatabase::queryStored( int first, int count, int k, bool earlier_only ) const
+{
+    const char* who = "ViewDatabase::queryStored";
+    if( k < 1 || first < 0 || count < 0 || count > 4096 || first > _size - count || (long long)count * k > 0x7fffffffLL )
+        SHORTLIST_FAIL( std::string( who ) + ": invalid arguments" );
+    std::vector<int> limits;
+    if( earlier_only ) for( int i = 0; i < count; i++ ) limits.push_back( first + i );
+    return run( (const unsigned short*)_q + (size_t)first * _voc.wordCount(), count, k, 0u, first, earlier_only && count > 0 ? limits.data() : nullptr, first );
 }
 
 } // namespace popsift
